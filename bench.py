@@ -21,10 +21,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# Batches in flight run on separate HIP streams: give the runtime enough hardware queues for them (default 4) BEFORE HIP initialises, so the
-# light, latency-bound kernels of one batch (top-k selection, exact replay) overlap the streaming kernels of another (measured: +10 % q/s).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
@@ -75,6 +71,25 @@ def roofline_by_kernel(roof):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, keys, scores, ties, counts, flags):
+    """--dump-outputs: the five arrays a caller of search_packed receives for one batch, as DIR/<name>.npy (integers as float64, exact below 2^53; scores and
+    ties as float32).  A batch whose arrays exceed DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its queries, listed in DIR/query_index.npy."""
+    arrays = {"keys": keys.astype(np.float64), "scores": scores.astype(np.float32), "ties": ties.astype(np.float32),
+              "counts": counts.astype(np.float64), "flags": flags.astype(np.float64)}
+    nq = len(counts)
+    per_query = sum(a.nbytes for a in arrays.values()) / max(1, nq)
+    if per_query * nq > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(20240).choice(nq, int(DUMP_LIMIT_BYTES // (per_query + 8)), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["query_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -99,7 +114,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="queries in the CPU-baseline sample (0 = auto, ~10-30 s)")
     ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (keys, scores, ties, counts, flags) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
 
     # --gpus N is the number of ranks.  Started bare (no WORLD_SIZE: `python bench.py --gpus N`), the script launches itself under torch.distributed.run with
     # one rank per GPU — the form the driver uses for N > 1 — and relays the ranks' output; started BY torch.distributed.run it checks that the launcher's
@@ -264,6 +285,7 @@ def main():
             if lock:
                 tim.append(searcher.last_timings())
             results.append((keys, counts))
+            last_out = (keys, scores, ties, counts, flags)
         lat = [(b - a) * 1000.0 for a, b in stamps]
         first_keys = (results[0][0].copy(), results[0][1].copy())
         nsess = len(searcher.sessions)
@@ -282,6 +304,7 @@ def main():
         tim = [None] * nsteps
         lat = [0.0] * nsteps
         results = [None] * nsteps
+        last_out = [None] * 5
         cursor = {"next": args.warmup}
         lock = threading.Lock()
         errors = []
@@ -300,6 +323,8 @@ def main():
                     stampsT[s] = (sessions.index(sess), ts, time.time())
                     tim[s] = sess.last_timings(kernels=(s % 4 == 0))      # kernel durations on every fourth batch: resolving them is HIP API traffic
                     results[s] = (keys, counts)
+                    if s == nsteps - 1:
+                        last_out[:] = [keys, scores, ties, counts, flags]
             except Exception as ex:  # noqa: BLE001
                 errors.append(ex)
 
@@ -329,6 +354,8 @@ def main():
     # sharded: all ranks cooperate on ONE stream (strong scaling of the 10 M corpus); replicas: every rank answers its own stream
     total_queries = args.steps * args.batch * (1 if sharded else world)
     qps = total_queries / elapsed
+    if args.dump_outputs and rank == 0:      # outside the timed region: what the last timed step returned
+        dump_outputs(args.dump_outputs, *last_out)
 
     # long leg (after the timed region, same process, same sessions): `--long-steps` FRESH batches through the same worker loop — the steady-state rate once the
     # fill and drain of the session pipeline no longer weigh (value_long); not the headline, which stays the driver's K steps

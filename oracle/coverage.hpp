@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's Stage 2: lexical coverage features + fusion score.
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   Metrics/LevenshteinDistance.cs:181-257 (Calculate), :281-341 (CalculateDamerau)
 //   Metrics/StringMetrics.cs:12-36         (Lcs = containment or common-prefix + tolerance)
 //   Coverage/CoverageTokenizer.cs:7-108    (TokenizeToSpan, Deduplicate*)

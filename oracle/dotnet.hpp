@@ -1,6 +1,6 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // Restatement of the .NET 8 BCL algorithms the reference's results depend on at tie boundaries.
-// The BCL is NOT under /root/reference (it is the runtime: Microsoft.NETCore.App 8.0.x, see
+// The BCL is NOT in the reference's sources (it is the runtime: Microsoft.NETCore.App 8.0.x, see
 // src/Infidex/Infidex.csproj:4). These follow the published dotnet/runtime sources from memory:
 //   System.Collections.Generic.ArraySortHelper<T>.IntrospectiveSort (List<T>.Sort / Array.Sort / Span.Sort)
 //   System.Collections.Generic.PriorityQueue<TElement,TPriority> (array-backed 4-ary min-heap)

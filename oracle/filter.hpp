@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's Infiscript post-filter and facet aggregation (BASELINE config 5).
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   Api/FilterParser.cs:35-693          Tokenize, ParseTernaryExpression / ParseExpression / ParseTerm / ParseFactor / ParseCondition
 //   Api/{ValueFilter,RangeFilter,InFilter,StringFilter,NullFilter,CompositeFilter,TernaryFilter,LiteralFilter}.cs   (tree node kinds)
 //   Filtering/FilterCompiler.cs:19-283  tree -> bytecode (short-circuit AND/OR through DUP / JUMP_IF_* / POP, ternary jumps)
@@ -12,7 +12,7 @@
 //   Core/FacetBuilder.cs:19-105         value counts of the facetable fields over the result rows, (count desc, value asc), <= 100 per field
 //   SearchEngine.cs:298-316             Execute(...maxResults) -> ApplyPostProcessing -> facets -> Take(max)
 // NOT restated (an expression using them is rejected by the oracle AND by the product): MATCHES (a .NET regex), SortBy / Boosts.
-// PARITY UNPINNED (BCL behaviour outside /root/reference): double.ToString() ("shortest round-trip" digits, restated), double.TryParse
+// PARITY UNPINNED (BCL behaviour outside the reference's sources): double.ToString() ("shortest round-trip" digits, restated), double.TryParse
 // (NumberStyles.Float | AllowThousands under the current culture: restated for invariant-culture plain / exponent numbers, no thousands
 // separators), and the facet tie order `ThenBy(kvp => kvp.Key)` (current-culture string comparer: restated as ordinal-ignore-case, then
 // ordinal — identical for the digit strings and capitalised words the reference's tests and the synthetic config use).

@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's index builder (the inputs of the hot path).
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   Api/DocumentFields.cs:124-172      GetSearchableTexts ('§' join, field boundaries)
 //   Indexing/VectorModel.cs:73-128     IndexDocument, DetermineFieldWeight
 //   Tokenization/Tokenizer.cs:89-139   EnumerateTokensForIndexing (n-grams of padded text, then words)

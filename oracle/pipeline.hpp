@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of SearchEngine.Search -> SearchPipeline.Execute (Stage 1 -> Stage 2 -> truncation).
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   SearchEngine.cs:256-319               Search (trim, normalise, lower-case, Take(max))
 //   Scoring/SearchPipeline.cs:49-206      Execute (short-query gates, coverage gate, fallback)
 //   Scoring/SearchPipeline.cs:208-296     ExecuteRelevancyStage  (n-gram path only; QueryAnalyzer.cs:10-54)

@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's Stage 1 (query terms -> candidate selection -> BM25+ top-k).
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   Tokenization/Tokenizer.cs:144-196     EnumerateShinglesForSearch (words first, then n-grams of padded text)
 //   Indexing/VectorModel.cs:376-602       SearchWithMaxScore (<=128 raw tokens, sort by (termId,text), RLE dedupe,
 //                                         fuzzy expansion, idf / maxScore)

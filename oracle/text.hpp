@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's text layer. Not part of the product path.
 //
-// Follows (reference paths relative to /root/reference/src/Infidex):
+// Follows (reference paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   Tokenization/TextNormalizer.cs:120-200,203-304  (Normalize, default char map)
 //   Tokenization/TokenizerSetup.cs:36-43            (default delimiters)
 //   .NET BCL char.ToLowerInvariant / ToUpperInvariant / IsWhiteSpace / IsLetter

@@ -1,7 +1,7 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see oracle/README.md).
 // CPU restatement of the reference's WordMatcher (extra Stage-2 candidate source).
 //
-// Follows (paths relative to /root/reference/src/Infidex):
+// Follows (paths relative to src/Infidex of the reference, lofcz/Infidex):
 //   WordMatcher/WordMatcher.cs:82-118   Load (lower-case THEN normalise; exact 2..8, LD1 deletions 3..8, affix >=3)
 //   WordMatcher/WordMatcher.cs:166-196  IndexWordInFst — _fstIndex is null while loading, so every word
 //                                       OCCURRENCE gets a fresh term id and the trie node keeps the last one:

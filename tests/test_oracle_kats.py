@@ -1,6 +1,6 @@
 """Pins the oracle (CPU restatement, oracle/) against the reference's OWN known-answer tests.
 
-Every case cites the reference test it restates (paths relative to /root/reference/src/Infidex.Tests).
+Every case cites the reference test it restates (paths relative to src/Infidex.Tests of the reference, lofcz/Infidex).
 The reference is C# and cannot run here (no .NET in the image), so these KATs are what pins the oracle.
 CPU-only: runs under `-m "not gpu"`.
 """
