@@ -618,7 +618,16 @@ struct CoverageEngine {
 };
 
 // ---- FusionScorer.Calculate --------------------------------------------------------------------
-inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documentText, const CoverageFeatures& f, float bm25Score) {
+// Branches of the scorer a call took, recorded when `taken` is given (tests' branch-coverage guard, orc_trace_branches); they do not change the result.
+enum FusionBranch : uint32_t {
+    FB_SINGLE_T1 = 1u << 0, FB_SINGLE_T2 = 1u << 1, FB_SINGLE_T3 = 1u << 2, FB_SINGLE_T4 = 1u << 3, FB_SINGLE_CLEAN = 1u << 4, FB_SINGLE_COMPLETE = 1u << 5,
+    FB_TIER0 = 1u << 6, FB_TIER1 = 1u << 7, FB_TIER2 = 1u << 8, FB_TIER3 = 1u << 9, FB_MT0 = 1u << 10, FB_MT1 = 1u << 11, FB_MT2 = 1u << 12, FB_MT3 = 1u << 13,
+    FB_EXACT_PREFIX = 1u << 14, FB_SUBSET = 1u << 15, FB_DOMINANT = 1u << 16, FB_ANCHOR = 1u << 17, FB_INFO_STEM = 1u << 18, FB_INFO_MISS = 1u << 19,
+    FB_INFO_DOMINANT = 1u << 20, FB_USE_IDF = 1u << 21, FB_INTENT = 1u << 22, FB_INTENT_CAP = 1u << 23, FB_TRAILING = 1u << 24, FB_NO_DOC_TOKENS = 1u << 25,
+    FB_SINGLE_CHAR = 1u << 26, FB_BASE_BLEND = 1u << 27, FB_CLAMP_HIGH = 1u << 28, FB_CLAMP_LOW = 1u << 29,
+};
+inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documentText, const CoverageFeatures& f, float bm25Score, uint32_t* taken = nullptr) {
+    uint32_t tk = 0;
     const FusionSignals& S = f.Fusion;
     int n = S.UnfilteredQueryTokenCount > 0 ? S.UnfilteredQueryTokenCount : f.TermsCount;
     bool single = n <= 1;
@@ -638,10 +647,11 @@ inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documen
         if (matched >= total) tier = 3; else if (matched == total - 1) tier = 2; else if (matched * 2 >= total) tier = 1; else tier = 0;
     }
     if (!single && tier > 0) precedence |= (tier & 3) << 16;
+    if (!single && f.TermsCount > 0) tk |= FB_TIER0 << tier;
     bool isExactPrefix = !single && isClean && startsAtBeginning && lexicalPrefixLast && isComplete;
     bool isSubset = !single && f.DocTokenCount > 0 && f.WordHits == f.DocTokenCount;
-    if (isExactPrefix) precedence |= (1 << 15);
-    if (isSubset) precedence |= (1 << 14);
+    if (isExactPrefix) { precedence |= (1 << 15); tk |= FB_EXACT_PREFIX; }
+    if (isSubset) { precedence |= (1 << 14); tk |= FB_SUBSET; }
     float avgIdf = 0.f;
     if (!single && f.TermsCount >= 2) {
         bool hasDominant = false;
@@ -658,25 +668,29 @@ inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documen
         }
         bool strongAnchor = S.HasAnchorStem && f.hasTermArrays && f.TermIdf.size() >= 1 && f.TermIdf[0] >= avgIdf;
         if (hasDominant || strongAnchor) precedence |= (1 << 13);
+        if (hasDominant) tk |= FB_DOMINANT;
+        if (strongAnchor) tk |= FB_ANCHOR;
         int unmatched = f.TermsCount - f.TermsWithAnyMatch;
-        if (hasDominant && unmatched == 1) precedence |= 8;
+        if (hasDominant && unmatched == 1) { precedence |= 8; tk |= FB_INFO_DOMINANT; }
     }
     if (single) {
-        if (isComplete) precedence |= (1 << 17);
-        if (isClean && f.TermsCount > 0) precedence |= (1 << 16);
+        if (isComplete) { precedence |= (1 << 17); tk |= FB_SINGLE_COMPLETE; }
+        if (isClean && f.TermsCount > 0) { precedence |= (1 << 16); tk |= FB_SINGLE_CLEAN; }
         int t = 0;
         if (isComplete) { if (startsAtBeginning) { if (isExact) t = 4; else if (isClean) t = 3; } else { if (isExact) t = 2; else if (isClean) t = 1; } }
         precedence |= t << 3;
+        if (t > 0) tk |= FB_SINGLE_T1 << (t - 1);
     } else {
         bool anchorRun = S.HasAnchorStem && f.LongestPrefixRun >= 2;
         int mt = isPrefixLastStrong ? 3 : (lexicalPrefixLast ? 2 : ((isPerfectDoc || anchorRun) ? 1 : 0));
-        if (S.UnfilteredQueryTokenCount > f.TermsCount) mt += S.SingleCharLastTokenBoost;
+        tk |= FB_MT0 << mt;
+        if (S.UnfilteredQueryTokenCount > f.TermsCount) { mt += S.SingleCharLastTokenBoost; if (S.SingleCharLastTokenBoost > 0) tk |= FB_SINGLE_CHAR; }
         precedence |= mt;
     }
     float coverageRatio = f.TermsCount > 0 ? (float)f.TermsWithAnyMatch / (float)f.TermsCount : 0.f;
     bool partial = coverageRatio > 0.f && coverageRatio < 1.f;
     if (partial && n >= 2) {
-        if (S.HasStemEvidence) precedence |= 8;
+        if (S.HasStemEvidence) { precedence |= 8; tk |= FB_INFO_STEM; }
         else {
             int unmatched = f.TermsCount - f.TermsWithAnyMatch;
             bool lastMatched = f.LastTokenHasPrefix || (f.TermsCount > 0 && f.TermsWithAnyMatch == f.TermsCount);
@@ -684,7 +698,7 @@ inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documen
             if (unmatched == 1 && canBoost) {
                 float missRatio = f.MissingIdf / f.TotalIdf;
                 float gap = 1.f - coverageRatio;
-                if (missRatio < gap) precedence |= 8;
+                if (missRatio < gap) { precedence |= 8; tk |= FB_INFO_MISS; }
             }
         }
     }
@@ -692,27 +706,30 @@ inline std::pair<float, uint8_t> fusion_calculate(uview queryText, uview documen
     float avgCi = f.TermsCount > 0 ? f.SumCi / (float)f.TermsCount : 0.f;
     float semantic;
     if (single) { float ls = (float)S.SingleTermLexicalSim / 255.f; semantic = (avgCi + ls) / 2.f; }
-    else if (f.DocTokenCount == 0) semantic = avgCi;
+    else if (f.DocTokenCount == 0) { semantic = avgCi; tk |= FB_NO_DOC_TOKENS; }
     else {
         int unmatched = f.TermsCount - f.TermsWithAnyMatch;
         bool lastMatched = f.LastTokenHasPrefix || (f.TermsCount > 0 && f.TermsWithAnyMatch == f.TermsCount);
         bool canUseIdf = (lastMatched || !f.LastTermIsTypeAhead) && f.TotalIdf > 0.f;
         bool useIdf = partial && unmatched == 1 && canUseIdf && f.IdfCoverage > coverageRatio;
         float base = useIdf ? f.IdfCoverage : avgCi;
+        if (useIdf) tk |= FB_USE_IDF;
         float density = (float)f.WordHits / (float)f.DocTokenCount;
         semantic = base * density;
         if (f.TermsCount >= 3) {   // ApplyIntentBonus
             int sc = (S.HasAnchorStem ? 1 : 0) + (f.SuffixPrefixRun >= 2 ? 1 : 0);
-            if (sc > 0) { float bonus = 0.15f * (float)sc; semantic = std::min(1.f, semantic + bonus); }
+            if (sc > 0) { float bonus = 0.15f * (float)sc; tk |= FB_INTENT; if (semantic + bonus > 1.f) tk |= FB_INTENT_CAP; semantic = std::min(1.f, semantic + bonus); }
         }
         if (f.TermsCount >= 2) {   // ApplyTrailingTermBonus
             float md = (float)S.TrailingMatchDensity / 255.f;
-            if (md > 0.f) { float head = 1.f - semantic; semantic += head * md; }
+            if (md > 0.f) { float head = 1.f - semantic; semantic += head * md; tk |= FB_TRAILING; }
         }
     }
     float gap = 1.f - coverageRatio;
-    if (partial && bm25Score >= gap) semantic = coverageRatio * semantic + gap * bm25Score;
-    if (semantic < 0.f) semantic = 0.f; if (semantic > 0.999f) semantic = 0.999f;
+    if (partial && bm25Score >= gap) { semantic = coverageRatio * semantic + gap * bm25Score; tk |= FB_BASE_BLEND; }
+    if (semantic < 0.f) { semantic = 0.f; tk |= FB_CLAMP_LOW; }
+    if (semantic > 0.999f) { semantic = 0.999f; tk |= FB_CLAMP_HIGH; }
+    if (taken) *taken = tk;
     uint8_t tie = 0;
     if (n >= 2 && !documentText.empty()) {
         float focus = std::min(1.f, (float)queryText.size() / (float)documentText.size());

@@ -102,6 +102,25 @@ int32_t orc_last_trace(void* h, int32_t* internal_ids, float* base, float* score
     }
     return n;
 }
+// FusionScorer.Calculate re-evaluated on the stored features of trace row `row` of the last search with a caller-chosen BM25 share (the row's own
+// baseScore reproduces its traced score and tiebreaker).  Returns 0, or -1 for a row that does not exist.
+int32_t orc_trace_rescore(void* h, int32_t row, float bm25, float* score, uint8_t* tie) {
+    Handle* H = (Handle*)h;
+    if (row < 0 || row >= (int32_t)H->last.trace.size()) return -1;
+    const CandidateTrace& t = H->last.trace[row];
+    auto sc = fusion_calculate(H->last.traceQuery, t.docText, t.f, bm25);
+    *score = sc.first; *tie = sc.second;
+    return 0;
+}
+// the FusionBranch bits (oracle/coverage.hpp) trace row `row` of the last search took under its own base; -1 for a row that does not exist
+int32_t orc_trace_branches(void* h, int32_t row) {
+    Handle* H = (Handle*)h;
+    if (row < 0 || row >= (int32_t)H->last.trace.size()) return -1;
+    const CandidateTrace& t = H->last.trace[row];
+    uint32_t taken = 0;
+    fusion_calculate(H->last.traceQuery, t.docText, t.f, t.baseScore, &taken);
+    return (int32_t)taken;
+}
 // last Stage-1 term list (ascending termId order as fed to Bm25Scorer): termId (-1 fuzzy), df, idf, maxScore
 int32_t orc_last_terms(void* h, int32_t* term_ids, int32_t* dfs, float* idfs, float* maxs, int32_t cap) {
     Handle* H = (Handle*)h;

@@ -23,14 +23,15 @@ struct QueryParams {       // Api/Query.cs defaults
     bool enableCoverage = true;
 };
 
-struct CandidateTrace {    // per Stage-2 evaluation, for parity checks of the integer features
-    int internalId; float baseScore; float score; uint8_t tie; CoverageFeatures f; int lcs;
+struct CandidateTrace {    // per Stage-2 evaluation, for parity checks of the features and for re-scoring a row under another base (orc_trace_rescore)
+    int internalId; float baseScore; float score; uint8_t tie; CoverageFeatures f; int lcs; ustr docText;
 };
 
 struct SearchOutput {
     std::vector<ScoreEntry> records;
     std::vector<ScoreEntry> stage1;           // consolidated Stage-1 results (<= depth)
     std::vector<CandidateTrace> trace;        // filled when Engine::keepTrace
+    ustr traceQuery;                          // the coverage query text the traced rows were scored against
     bool unsupported = false;
     bool usedCoverage = false;
     int totalCandidates = 0;
@@ -145,6 +146,7 @@ struct Engine {
         TopKHeap finalScores(depth);
         int maxWordHits = 0;
         QueryContext ctx = cov.prepare_query(searchText);
+        if (keepTrace) out.traceQuery = ctx.query;
         std::unordered_set<int> tfidfIds;
         for (auto& c : top) { auto it = ix.keyToFirstId.find(c.key); if (it != ix.keyToFirstId.end()) tfidfIds.insert(it->second); }
         std::vector<int> overlap, uniq;
@@ -173,7 +175,7 @@ struct Engine {
             if (docIndex < 2 && hitsRow[docIndex] == 0) hitsRow[docIndex] = (uint8_t)std::min(f.WordHits, 255);
             maxWordHits = std::max(maxWordHits, f.WordHits);
             finalScores.add(ScoreEntry{sc.first, ix.docKey[internalId], sc.second});
-            if (keepTrace) out.trace.push_back(CandidateTrace{internalId, baseScore, sc.first, sc.second, f, lcs});
+            if (keepTrace) out.trace.push_back(CandidateTrace{internalId, baseScore, sc.first, sc.second, f, lcs, docText});
         };
         for (int id : overlap) process(id, 0.f);
         int done = 0;

@@ -63,6 +63,13 @@ N_INT_FEAT = 25   # features [0, 25) are the integer "coverage counts" that must
 
 HIGH, MED, LOW = 0, 1, 2
 
+# FusionBranch bits of oracle/coverage.hpp, in bit order
+FUSION_BRANCHES = ["single_t1", "single_t2", "single_t3", "single_t4", "single_clean_bit16", "single_complete_bit17",
+                   "tier0", "tier1", "tier2", "tier3", "mt0", "mt1", "mt2", "mt3",
+                   "exact_prefix_bit15", "subset_bit14", "dominant", "anchor_stem", "info_stem", "info_miss_ratio",
+                   "info_dominant", "use_idf", "intent", "intent_cap", "trailing", "no_doc_tokens",
+                   "single_char_boost", "base_blend", "clamp_high", "clamp_low"]
+
 
 class OracleEngine:
     """Mirrors the reference's SearchEngine.CreateDefault() / CreateMinimal() for the hot path."""
@@ -140,6 +147,20 @@ class OracleEngine:
         n = self.L.orc_last_trace(self.h, _p(ids, C.c_int32), _p(base, C.c_float), _p(sc, C.c_float), _p(ties, C.c_uint8),
                                   _p(feat, C.c_int32), cap)
         return ids[:n].copy(), base[:n].copy(), sc[:n].copy(), ties[:n].copy(), feat[:n].copy()
+
+    def trace_rescore(self, row, bm25):
+        """FusionScorer.Calculate on the features of trace row `row` of the last search, with BM25 share `bm25` (fp32): (score, tiebreaker)."""
+        sc = C.c_float(0); tie = C.c_uint8(0)
+        self.L.orc_trace_rescore.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
+        rc = self.L.orc_trace_rescore(self.h, int(row), float(np.float32(bm25)), C.byref(sc), C.byref(tie))
+        assert rc == 0, (row, rc)
+        return np.float32(sc.value), int(tie.value)
+
+    def trace_branches(self, row):
+        """The FusionScorer branches trace row `row` of the last search took (names of FUSION_BRANCHES)."""
+        m = self.L.orc_trace_branches(self.h, int(row))
+        assert m >= 0, (row, m)
+        return {n for i, n in enumerate(FUSION_BRANCHES) if (m >> i) & 1}
 
     def last_terms(self, cap=256):
         t = np.zeros(cap, np.int32); df = np.zeros(cap, np.int32); idf = np.zeros(cap, np.float32); mx = np.zeros(cap, np.float32)

@@ -87,7 +87,7 @@ def test_device_abi_with_oracle_built_inputs():
     hits = (Hit * (nq * DEPTH))(); hc = np.zeros(nq, np.uint32)
     chk(L, L.infx_stage1_batch(st, nq, QA, len(terms), TA, 0, None, hits, _p(hc, C.c_uint32)))
     o.set_trace(True)
-    cov_rows, cov_q, want = [], [], []
+    cov_rows, cov_q, want, extra = [], [], [], []
     sz = L.infx_sizeof_cov_query()
     for i, q in enumerate(used):
         o.search(q, 10, DEPTH)
@@ -104,16 +104,30 @@ def test_device_abi_with_oracle_built_inputs():
         assert host.L.infx_engine_prepare_cov_query(host.h, _p(a, C.c_uint16), len(a), buf) == 0
         first2 = ok.tolist()[:2]                                                                       # docIndex 0 / 1: the first two Stage-1 keys (quirk Q7)
         for k in range(len(ids)):
-            cov_rows.append(CovCand(len(cov_q), int(ids[k]), float(base[k]), 1 if int(ids[k]) in first2 else 0)); want.append((q, float(sc2[k]), int(ties[k]), feat[k]))
+            lcs_flag = 1 if int(ids[k]) in first2 else 0
+            cov_rows.append(CovCand(len(cov_q), int(ids[k]), float(base[k]), lcs_flag)); want.append((q, sc2[k], int(ties[k]), feat[k]))
+            # the only base-dependent branch of FusionScorer (`partial && bm25 >= gap`), hit on purpose: copies of each partial-coverage row under chosen
+            # bases, scored by the oracle on the row's own features (orc_trace_rescore); features and tie stay the row's
+            matched, total = int(feat[k, 2]), int(feat[k, 1])
+            if 0 < matched < total:
+                gap = f32(1) - f32(matched) / f32(total)
+                for b in (gap, np.nextafter(gap, f32(0)), np.nextafter(gap, f32(1)), f32(0), f32(1), f32(4), f32(1e30)):
+                    r_sc, r_tie = o.trace_rescore(k, b)
+                    assert r_tie == ties[k]
+                    extra.append((CovCand(len(cov_q), int(ids[k]), float(b), lcs_flag), (q, r_sc, int(ties[k]), feat[k])))
         cov_q.append(bytes(buf))
-    assert len(cov_q) >= 12
+    assert len(cov_q) >= 12 and len(extra) >= 7 * 100, len(extra)
+    cov_rows += [c for c, _ in extra]; want += [w for _, w in extra]
     qbuf = (C.c_uint8 * (sz * len(cov_q))).from_buffer_copy(b"".join(cov_q))
     CA = (CovCand * len(cov_rows))(*cov_rows); outs = (CovOut * len(cov_rows))(); fo = np.zeros((len(cov_rows), NFEAT), np.int32)
     chk(L, L.infx_stage2_batch(st, len(cov_q), qbuf, len(cov_rows), CA, outs, _p(fo, C.c_int32)))
+    # the oracle's own base on every row: nothing may differ, not even by an ulp — score, tiebreaker and feat[:31] (integer counts and float features as bits)
     for k, (q, sc, tie, feat) in enumerate(want):
-        assert outs[k].status == 0
-        assert np.array_equal(fo[k, :O.N_INT_FEAT], feat[:O.N_INT_FEAT]), (q, cov_rows[k].doc, fo[k, :O.N_INT_FEAT].tolist(), feat[:O.N_INT_FEAT].tolist())
-        assert outs[k].tiebreaker == tie and abs(outs[k].score - sc) <= 2.0 ** -6 + 1e-6, (q, outs[k].score, sc)
+        assert outs[k].status == 0, (q, k, outs[k].status)
+        assert np.array_equal(fo[k, :31], feat[:31]), (q, cov_rows[k].doc, [O.FEAT_NAMES[j] for j in range(31) if fo[k, j] != feat[j]], fo[k, :31].tolist(), feat[:31].tolist())
+        assert outs[k].tiebreaker == tie, (q, k, outs[k].tiebreaker, tie)
+        assert f32(outs[k].score).view(np.uint32) == f32(sc).view(np.uint32), (q, cov_rows[k].doc, "base", cov_rows[k].base_score, outs[k].score, float(sc))
+    print("device ABI:", len(want) - len(extra), "oracle rows and", len(extra), "re-based copies bit-equal")
     L.infx_stream_destroy(st); L.infx_destroy(idx)
 
 

@@ -30,9 +30,9 @@ def _run(config, nq, nsample):
     keys, scores, ties, counts, flags = e.search_packed(a, of, k)
     again = e.search_packed(a, of, k)
     assert np.array_equal(keys, again[0]) and np.array_equal(counts, again[3])          # deterministic
-    same, flips = assert_final_rows_match_oracle(keys, scores, counts, o, texts[:nsample], k, what=f"config {config} at {s.cfg['docs']} documents")
+    same, flips, inexact = assert_final_rows_match_oracle(keys, scores, counts, o, texts[:nsample], k, what=f"config {config} at {s.cfg['docs']} documents")
     st = e.lookup_stats()
-    print(f"config {config}: {same} identical order, {flips} near-tie flips of {nsample}; lookups {st}; exact replays in the batch {e.last_timings()['exact_replays']}")
+    print(f"config {config}: {same} identical order, {flips} near-tie flips of {nsample}, {inexact} rows not bit-equal; lookups {st}; exact replays in the batch {e.last_timings()['exact_replays']}")
     assert int((counts > 0).sum()) >= nq * 9 // 10
     return st
 

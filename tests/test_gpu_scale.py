@@ -106,9 +106,9 @@ def test_sharded_equals_the_oracle_at_scale(corpus, oracle):
             assert np.array_equal(x, y)
     keys, scores, ties, counts, flags = res[0]
     sample = list(range(0, 500, 3))
-    same, flips = assert_final_rows_match_oracle(keys[sample], scores[sample], counts[sample], oracle, [texts[i] for i in sample], K, what="4 shards at 400k docs")
+    same, flips, inexact = assert_final_rows_match_oracle(keys[sample], scores[sample], counts[sample], oracle, [texts[i] for i in sample], K, what="4 shards at 400k docs")
     replays = sum(x.s.last_timings()["exact_replays"] for x in sess)
-    print("4 shards vs oracle:", same, "identical order,", flips, "near-tie flips of", len(sample), "; queries replayed on their owners:", replays)
+    print("4 shards vs oracle:", same, "identical order,", flips, "near-tie flips of", len(sample), ",", inexact, "rows not bit-equal; queries replayed on their owners:", replays)
     assert replays > 0
     # and the single index returns the same sets for the whole batch (both are the reference's)
     ref = e.search_packed(a2, o2, K)
@@ -120,26 +120,24 @@ def test_sharded_equals_the_oracle_at_scale(corpus, oracle):
 def test_oracle_sample_at_scale(corpus, oracle):
     """Final top-k sets AND order vs the oracle at 400k docs.  With the exact Stage-1 replay (k_exact1) no query may differ; should one
     differ it is classified (tests/parity_classify.py) and anything that is not a cut-off tie fails with its dump."""
-    from tests.parity_classify import classify
+    from tests.parity_classify import classify, assert_final_rows, stage2_scored
     s, arena, offs, e, texts = corpus
     o = oracle
     sample = texts[:160]
     keys, scores, ties, counts, flags = run(e, sample)
-    differ, order_differ = [], 0
+    differ, order_differ, inexact = [], 0, 0
     for i, q in enumerate(sample):
         r = o.search(q, K, 500)
         got = keys[i, :int(counts[i])].tolist()
         if set(got) != set(r["keys"]):
             differ.append(q)
             continue
-        if got != r["keys"]:
-            order_differ += 1            # order may flip only between rows whose final scores are equal after the 2^-6 quantisation
-            gs = dict(zip(got, scores[i, :len(got)].tolist())); os_ = dict(zip(r["keys"], r["scores"]))
-            assert all(abs(gs[d] - os_[d]) <= 2.0 ** -6 + 1e-6 for d in got), q
-        else:
-            assert np.allclose(scores[i, :len(got)], np.asarray(r["scores"], np.float32), rtol=0, atol=2.0 ** -6 + 1e-6), q
+        # the oracle's score bits or one ulp off; order flips only between one-ulp near-ties with a row that is not bit-equal
+        bad, swaps = assert_final_rows(got, scores[i, :len(got)], r["keys"], r["scores"], stage2_scored(o, r), q)
+        inexact += bad
+        order_differ += got != r["keys"]
     cls = classify(e, o, differ, K) if differ else []
-    print("scale sample:", len(sample) - len(differ), "identical,", order_differ, "order flips,", cls)
+    print("scale sample:", len(sample) - len(differ), "identical,", order_differ, "order flips,", inexact, "rows not bit-equal,", cls)
     assert not [c for c in cls if c["kind"] == "other"], cls
     assert len(differ) == 0, cls            # exact replay: no cut-off tie may survive either
     t = e.last_timings()

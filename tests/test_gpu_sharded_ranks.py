@@ -67,8 +67,8 @@ def test_two_ranks_equal_the_oracle(tmp_path):
     qa, qo = s.queries(300, qseed=91)
     texts = Synth.texts(qa, qo) + ["qu", "", "zzzzqq"]
     k, c = r["k"], r["c"]
-    same, flips = assert_final_rows_match_oracle(k, r["sc"], c, o, texts, 20, what="2 real ranks")
-    print("2 ranks vs oracle:", same, "identical order,", flips, "near-tie flips")
+    same, flips, inexact = assert_final_rows_match_oracle(k, r["sc"], c, o, texts, 20, what="2 real ranks")
+    print("2 ranks vs oracle:", same, "identical order,", flips, "near-tie flips,", inexact, "rows not bit-equal")
     assert np.array_equal(r["cs"], c) and np.array_equal(r["ks"], k)                      # search_packed == search_stream
     assert np.array_equal(r["k1"], k[:100]) and np.array_equal(r["c1"], c[:100]) and np.array_equal(r["k2"], k[100:]) and np.array_equal(r["c2"], c[100:])
 

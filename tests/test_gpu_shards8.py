@@ -55,9 +55,9 @@ def test_eight_shards_equal_the_oracle_config4(world):
             assert np.array_equal(x, y)                           # all eight ranks hold the same rows
     keys, scores, ties, counts, flags = res[0]
     sample = list(range(0, len(texts), 2))
-    same, flips = assert_final_rows_match_oracle(keys[sample], scores[sample], counts[sample], o, [texts[i] for i in sample], K, what="8 shards at 600k docs")
+    same, flips, inexact = assert_final_rows_match_oracle(keys[sample], scores[sample], counts[sample], o, [texts[i] for i in sample], K, what="8 shards at 600k docs")
     replays = sum(x.s.last_timings()["exact_replays"] for x in sess)
-    print("8 shards vs oracle:", same, "identical order,", flips, "near-tie flips of", len(sample), "; queries replayed on their owners:", replays)
+    print("8 shards vs oracle:", same, "identical order,", flips, "near-tie flips of", len(sample), ",", inexact, "rows not bit-equal; queries replayed on their owners:", replays)
     assert replays > 0
 
 

@@ -411,3 +411,32 @@ def test_quirk_q18_the_lcs_of_a_second_evaluation_comes_back_from_a_byte():
     lcs_i = O.FEAT_NAMES.index("Lcs")
     seen = [int(tfeat[i, lcs_i]) for i in range(len(tids)) if int(tids[i]) == 0]
     assert seen == [len(q), 255], seen                                        # first evaluation: the whole query; second: the byte
+
+
+def test_trace_rescore_reproduces_traced_rows(ten):
+    """orc_trace_rescore (FusionScorer.Calculate on a trace row's stored features with a chosen BM25 share) called with the row's own base reproduces the
+    traced score and tiebreaker bit for bit, on every row of a few searches; and the base enters only through `partial && bm25 >= gap`: any share below
+    the row's gap scores like 0."""
+    from tools.synth import Synth
+    s = Synth(2, docs=3000)
+    arena, offs = s.docs()
+    syn = O.OracleEngine.create_default(); syn.add_flat(None, arena, offs, s.field_weights); syn.finalize()
+    qa, qo = s.queries(12, qseed=4, fuzz=0.3)
+    cases = [(ten, q) for q in ("batman", "qick fux", "the fox", "gotham city crime", "quick brown fox lazy")] + [(syn, q) for q in Synth.texts(qa, qo)]
+    rows = partial = 0
+    for o, q in cases:
+        o.set_trace(True)
+        o.search(q, 10)
+        ids, base, sc, ties, feat = o.last_trace()
+        for i in range(len(ids)):
+            r_sc, r_tie = o.trace_rescore(i, base[i])
+            assert r_sc.view(np.uint32) == sc[i].view(np.uint32) and r_tie == ties[i], (q, i, r_sc, sc[i], r_tie, ties[i])
+            rows += 1
+            matched, total = int(feat[i, 2]), int(feat[i, 1])
+            if 0 < matched < total:
+                partial += 1
+                gap = np.float32(1) - np.float32(matched) / np.float32(total)
+                below = np.nextafter(gap, np.float32(0))
+                assert o.trace_rescore(i, below)[0] == o.trace_rescore(i, 0.0)[0], (q, i)
+        o.set_trace(False)
+    assert rows > 500 and partial > 20, (rows, partial)
