@@ -8,8 +8,12 @@ truncation) with the index resident in HBM.
 
 N>1 (launched by torch.distributed.run, one rank per GPU): see DESIGN.md "Multi-GPU".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (k_accumulate, HBM-bound) and
-`cpu_baseline` (the oracle = restated reference algorithm in C++, NOT the .NET binary, timed on this box's host cores).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with the batch latencies and
+per-phase milliseconds of the timed steps.  A plain run does only what that line needs: set-up, warm-up, the timed steps and `--dump-outputs`.
+
+`--full` adds the legs that take runs of their own, after the timed region: `value_long` (a longer stream of fresh batches), `roofline` /
+`roofline_by_kernel` (k_accumulate, HBM-bound; uncontended batches on one session), the single-query latency, and `cpu_baseline` (the oracle =
+restated reference algorithm in C++, NOT the .NET binary, timed on the host's cores; its index build alone takes minutes at 10 M docs).
 """
 import argparse
 import json
@@ -109,11 +113,13 @@ def main():
     ap.add_argument("--distinct-batches", type=int, default=0, help="distinct synthetic query batches the steps cycle through; 0 (default) = warmup + steps, "
                     "i.e. no batch — and so no misspelt word beyond what the Zipf stream itself repeats — occurs twice: planning is measured cold")
     ap.add_argument("--replicas", action="store_true", help="N>1: independent full-index replicas instead of document shards")
-    ap.add_argument("--long-steps", type=int, default=200, help="single-GPU runs: a second, longer stream of this many fresh batches after the timed region, reported as value_long "
-                                                                "(the driver's K steps time a quarter of a second, less than the box-to-box spread); 0 = off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="queries in the CPU-baseline sample (0 = auto, ~10-30 s)")
-    ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the legs beyond the headline: value_long, the roofline leg, the single-query "
+                                                        "latency and (single GPU) the CPU baseline; off by default")
+    ap.add_argument("--long-steps", type=int, default=200, help="--full, single-GPU runs: a second, longer stream of this many fresh batches after the timed region, reported as "
+                                                                "value_long (the driver's K steps time a quarter of a second, less than the box-to-box spread); 0 = off")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: queries in the CPU-baseline sample (0 = auto, ~10-30 s)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: host threads of the CPU baseline (0 = all the process may use)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (keys, scores, ties, counts, flags) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
@@ -215,8 +221,8 @@ def main():
     arena, offs = syn.docs() if leader else (None, None)
     t_gen = time.time() - t0
 
-    # ---- CPU baseline (rank 0, N=1 only): the oracle's index is built AFTER the timed GPU region (it would compete for the CPU quota) ----
-    want_cpu = (not args.no_cpu_baseline) and rank == 0 and world == 1
+    # ---- CPU baseline (--full, rank 0, N=1 only): the oracle's index is built AFTER the timed GPU region (it would compete for the CPU quota) ----
+    want_cpu = args.full and (not args.no_cpu_baseline) and rank == 0 and world == 1
     orc_box = {}
 
     # ---- product: index + upload ---------------------------------------------------------------------------------------
@@ -357,10 +363,10 @@ def main():
     if args.dump_outputs and rank == 0:      # outside the timed region: what the last timed step returned
         dump_outputs(args.dump_outputs, *last_out)
 
-    # long leg (after the timed region, same process, same sessions): `--long-steps` FRESH batches through the same worker loop — the steady-state rate once the
-    # fill and drain of the session pipeline no longer weigh (value_long); not the headline, which stays the driver's K steps
+    # long leg (--full, after the timed region, same process, same sessions): `--long-steps` FRESH batches through the same worker loop — the steady-state rate
+    # once the fill and drain of the session pipeline no longer weigh (value_long); not the headline, which stays the driver's K steps
     value_long = None
-    if not sharded and world == 1 and args.long_steps > 0:
+    if args.full and not sharded and world == 1 and args.long_steps > 0:
         lqa, lqo = syn.queries(args.long_steps * args.batch, qseed=5000)
         lb = []
         for s_ in range(args.long_steps):
@@ -392,17 +398,17 @@ def main():
                       "p50_batch_latency_ms": float(np.median(lat2)), "p95_batch_latency_ms": float(np.percentile(lat2, 95)),
                       "note": "same process and sessions, fresh batches, run after the timed region; the headline `value` is the driver's K-step form"}
 
-    # roofline leg: the same batches once more on ONE session (no concurrent kernels), HIP events on the launch stream
+    # roofline leg (--full): the same batches once more on ONE session (no concurrent kernels), HIP events on the launch stream
     roof = []
-    if sharded:
+    if args.full and sharded:
         roof = tim
-    else:
+    elif args.full:
         for s in range(args.warmup, min(nsteps, args.warmup + 3)):
             sessions[0].search_packed(batches[s][0], batches[s][1], k, 500)
             roof.append(sessions[0].last_timings())
-    # interactive use: one query per call (the reference's Search(Query)), on one session
+    # interactive use (--full): one query per call (the reference's Search(Query)), on one session
     single_ms = None
-    if not sharded:
+    if args.full and not sharded:
         from infidex_amd.engine import pack_texts
         texts1 = Synth.texts(batches[args.warmup][0], batches[args.warmup][1])[:40]
         ls = []
@@ -426,10 +432,6 @@ def main():
     if dist is not None and world > 1:          # per-phase milliseconds of EVERY rank (host phases are replicated, device phases shrink with W)
         stage_ranks = [None] * world
         dist.all_gather_object(stage_ranks, stage_me)
-    acc_ms = float(np.mean([t["k_accumulate_ms"] for t in roof]))
-    alg = float(np.mean([t["alg_bytes"] for t in roof]))
-    streamed = float(np.mean([t["streamed_bytes"] for t in roof]))
-    achieved = alg / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0
     qw = str(syn.cfg["qwords"][0]) if syn.cfg["qwords"][0] == syn.cfg["qwords"][1] else f"{syn.cfg['qwords'][0]}-{syn.cfg['qwords'][1]}"
     lk = eng.lookup_stats() if hasattr(eng, "lookup_stats") else None
     out = {
@@ -445,31 +447,50 @@ def main():
                    "parallelism": "single GPU" if world == 1 else (f"{world} document shards, count all-reduce + RCCL all-gather of per-shard top-500 + owner-scored Stage 2" if sharded
                                                                     else f"{world} independent replicas (one index per GPU, query stream split)")},
         "p50_batch_latency_ms": float(np.median(lat)), "p95_batch_latency_ms": float(np.percentile(lat, 95)),
-        "p50_single_query_latency_ms": single_ms,
-        "value_long": value_long,
         # host phases of a batch (per session; sessions overlap): planning (text prep, term lookup, LD1 expansion, idf/roles),
         # Stage-1 host part (phase API only), Stage-2 preparation (fused pipeline: WordMatcher descriptors + PrepareQuery),
         # the wait for the device (fused: the whole device pipeline behind one synchronisation), host post-processing
         "stage_ms_per_step": stage_me,
-        # "bound": what limits the kernel by the counters of profiles/ (instruction issue), NOT what it is priced against: `peak` stays the HBM roofline the
-        # path is bounded by in principle (byte streaming, no MFMA work), so `frac` is the achieved fraction of the HBM roofline by algorithmic bytes
-        "roofline": {"kernel": "Stage-1 accumulation = k_accumulate_sparse + k_accumulate (two kernels split the (query, stripe) pairs of a launch by candidate count; one after the other on the "
-                               "stream, timed as one span)", "bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_rate": achieved / HBM_COPY_GBS, "traffic": None,
-                     "limiter": "not bandwidth: the accumulation is priced against the HBM roofline (byte streaming, no MFMA work) by SURVEY 8(d)'s algorithmic bytes, but the streaming "
-                                "kernel (dense stripes: ~3.7 ms with all 4096 wave slots busy since its blocks run heaviest query first) is bound by VALU / SALU issue and latency of its (posting list, "
-                                "doc range) visits, and the sparse kernel (stripes of <= 96 candidates: ~2.0 ms) by the lane-loads of its dependent lookups - it does not stream its lists at "
-                                "all (profiles/r06_final_10m.md, r06_accumulate_blocks.md, r06_pmc.json)",
-                     "algorithmic_bytes_per_launch": alg, "avg_launch_ms": acc_ms,
-                     "streamed_bytes_per_launch": streamed, "stage1_candidates_per_launch": float(np.mean([t["stage1_candidates"] for t in roof])),
-                     "stage2_rows_per_launch": float(np.mean([t["stage2_candidates"] for t in roof])), "exact_replays_per_launch": float(np.mean([t["exact_replays"] for t in roof])), "streamed_GBps": streamed / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0,
-                     "other_kernels_ms": {kk: float(np.mean([t[kk + "_ms"] for t in roof])) for kk in ("k_select", "k_replay", "k_prep2", "k_stage2", "k_finalize")},
-                     "replay_flag_reasons_per_launch": {kk: float(np.mean([t["flag_" + kk] for t in roof])) for kk in ("plateau", "band", "unknown")},
-                     "note": "achieved = SURVEY 8(d) algorithmic bytes / duration of the two accumulation kernels together (HIP events on the launch stream around both, uncontended launch); the rocprofv3 kernel-trace averages of k_accumulate_sparse and k_accumulate add up to it"},
-        "roofline_by_kernel": roofline_by_kernel(roof),
         "planning_lookups": lk,
         "setup_s": {"corpus_gen": t_gen, "index_build_and_upload": t_index, "host_threads": bthreads},
     }
+    if args.full:
+        acc_ms = float(np.mean([t["k_accumulate_ms"] for t in roof]))
+        alg = float(np.mean([t["alg_bytes"] for t in roof]))
+        streamed = float(np.mean([t["streamed_bytes"] for t in roof]))
+        achieved = alg / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0
+        out["p50_single_query_latency_ms"] = single_ms
+        out["value_long"] = value_long
+        # "bound": what limits the kernel by the counters of profiles/ (instruction issue), NOT what it is priced against: `peak` stays the HBM roofline the
+        # path is bounded by in principle (byte streaming, no MFMA work), so `frac` is the achieved fraction of the HBM roofline by algorithmic bytes
+        out["roofline"] = {"kernel": "Stage-1 accumulation = k_accumulate_sparse + k_accumulate (two kernels split the (query, stripe) pairs of a launch by candidate count; one after the other on the "
+                                     "stream, timed as one span)", "bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_rate": achieved / HBM_COPY_GBS, "traffic": None,
+                           "limiter": "not bandwidth: the accumulation is priced against the HBM roofline (byte streaming, no MFMA work) by SURVEY 8(d)'s algorithmic bytes, but the streaming "
+                                      "kernel (dense stripes: ~3.7 ms with all 4096 wave slots busy since its blocks run heaviest query first) is bound by VALU / SALU issue and latency of its (posting list, "
+                                      "doc range) visits, and the sparse kernel (stripes of <= 96 candidates: ~2.0 ms) by the lane-loads of its dependent lookups - it does not stream its lists at "
+                                      "all (profiles/r06_final_10m.md, r06_accumulate_blocks.md, r06_pmc.json)",
+                           "algorithmic_bytes_per_launch": alg, "avg_launch_ms": acc_ms,
+                           "streamed_bytes_per_launch": streamed, "stage1_candidates_per_launch": float(np.mean([t["stage1_candidates"] for t in roof])),
+                           "stage2_rows_per_launch": float(np.mean([t["stage2_candidates"] for t in roof])), "exact_replays_per_launch": float(np.mean([t["exact_replays"] for t in roof])), "streamed_GBps": streamed / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0,
+                           "other_kernels_ms": {kk: float(np.mean([t[kk + "_ms"] for t in roof])) for kk in ("k_select", "k_replay", "k_prep2", "k_stage2", "k_finalize")},
+                           "replay_flag_reasons_per_launch": {kk: float(np.mean([t["flag_" + kk] for t in roof])) for kk in ("plateau", "band", "unknown")},
+                           "note": "achieved = SURVEY 8(d) algorithmic bytes / duration of the two accumulation kernels together (HIP events on the launch stream around both, uncontended launch); the rocprofv3 kernel-trace averages of k_accumulate_sparse and k_accumulate add up to it"}
+        out["roofline_by_kernel"] = roofline_by_kernel(roof)
+        # HBM traffic of the dominant kernel comes from a separate rocprofv3 --pmc pass (counters cannot be read from inside the process).  The committed
+        # measurement is attached only to the workload it was taken on (config 4, full size, 1000-query batches, one GPU) and only if it was taken on THIS
+        # build of the kernel: sha256 over csrc/stage1.hip.inc AND the launch code of csrc/infidex_hip.hip (launch_acc: grid, block map, LDS size).
+        try:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+            ksha = kernel_sha16()
+            if args.config == 4 and args.docs == full and args.batch == 1000 and not sharded and world == 1 and pmc.get("kernel_source_sha16") == ksha:
+                out["roofline"]["traffic"] = pmc["hbm_read_bytes_per_launch"]
+                out["roofline"]["traffic_unit"] = "HBM read bytes per launch (FETCH_SIZE x2, " + pmc["source"] + ")"
+                out["roofline"]["traffic_frac_of_peak"] = pmc["hbm_read_bytes_per_launch"] / (acc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if acc_ms > 0 else None
+            else:
+                out["roofline"]["traffic_note"] = f"profiles/{PMC_FILE} was measured on another build of the kernel or another workload (config 4 at full size only): not attached"
+        except Exception:
+            pass
     if stage_ranks is not None:
         out["stage_ms_per_step_per_rank"] = stage_ranks
     if sharded:
@@ -491,20 +512,6 @@ def main():
     if flt and not sharded:
         out["config"]["filter"] = flt; out["config"]["facets"] = ["year", "genre"]
         out["filter"] = {"documents_in_filter": in_filter, "first_use_s_incl_compile_and_device_count": t_filter_first_use}
-    # HBM traffic of the dominant kernel comes from a separate rocprofv3 --pmc pass (counters cannot be read from inside the process).  The committed
-    # measurement is attached only to the workload it was taken on (config 4, full size, 1000-query batches, one GPU) and only if it was taken on THIS
-    # build of the kernel: sha256 over csrc/stage1.hip.inc AND the launch code of csrc/infidex_hip.hip (launch_acc: grid, block map, LDS size).
-    try:
-        pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
-        ksha = kernel_sha16()
-        if args.config == 4 and args.docs == full and args.batch == 1000 and not sharded and world == 1 and pmc.get("kernel_source_sha16") == ksha:
-            out["roofline"]["traffic"] = pmc["hbm_read_bytes_per_launch"]
-            out["roofline"]["traffic_unit"] = "HBM read bytes per launch (FETCH_SIZE x2, " + pmc["source"] + ")"
-            out["roofline"]["traffic_frac_of_peak"] = pmc["hbm_read_bytes_per_launch"] / (acc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if acc_ms > 0 else None
-        else:
-            out["roofline"]["traffic_note"] = f"profiles/{PMC_FILE} was measured on another build of the kernel or another workload (config 4 at full size only): not attached"
-    except Exception:
-        pass
     if want_cpu:
         from tests import oracle_lib as O
         tb = time.time()

@@ -2,7 +2,7 @@
 # k_accumulate2 vs k_accumulate on the GPU box: PMC passes (each its own run; --pmc never together with trace flags).  Output under gpurun_out/prof_acc2/.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_acc2; rm -rf $O; mkdir -p $O
-B="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --sessions 1"
+B="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --sessions 1"
 export INFX_EXACT=${INFX_EXACT:-0}
 for v in 0 1; do
   export INFX_ACC_V1=$v

@@ -3,13 +3,13 @@
 # PMC passes for k_accumulate (each its own run; --pmc never together with trace flags).  Output: gpurun_out/prof_r04/
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r04; rm -rf $O; mkdir -p $O
-python $R/bench.py --steps 20 --warmup 5 > $O/bench_20steps.json 2> $O/bench_20steps.err
-python $R/bench.py --no-cpu-baseline > $O/bench_256steps.json 2> $O/bench_256steps.err
-python $R/bench.py --config 2 --steps 60 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python $R/bench.py --config 3 --steps 60 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python $R/bench.py --config 5 --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-INFX_FORCE_SHARDED=1 python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
-B="python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --sessions 1"
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_20steps.json 2> $O/bench_20steps.err
+python $R/bench.py --full --no-cpu-baseline > $O/bench_256steps.json 2> $O/bench_256steps.err
+python $R/bench.py --full --config 2 --steps 60 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python $R/bench.py --full --config 3 --steps 60 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python $R/bench.py --full --config 5 --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+INFX_FORCE_SHARDED=1 python $R/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
+B="python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --sessions 1"
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $B > $O/kt.json 2> $O/kt.err
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv; rm -rf $O/kt
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o p --output-format csv -- $B > $O/pmc_fetch.json 2> $O/pmc_fetch.err

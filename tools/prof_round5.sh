@@ -5,18 +5,18 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r05; rm -rf $O; mkdir -p $O
 ( cd $R && timeout 900 python -m pytest tests -m gpu -q > $O/gputest.log 2>&1; echo "gputest rc=$?" >> $O/gputest.log )
 ( cd $R && timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log )
-python $R/bench.py --steps 20 --warmup 5 > $O/bench_20steps.json 2> $O/bench_20steps.err
-python $R/bench.py --no-cpu-baseline > $O/bench_256steps.json 2> $O/bench_256steps.err
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --sessions 3 > $O/bench_20steps_sessions3.json 2> $O/bench_20steps_sessions3.err
-python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --sessions 5 > $O/bench_20steps_sessions5.json 2> $O/bench_20steps_sessions5.err
-python $R/bench.py --config 2 --steps 60 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python $R/bench.py --config 3 --steps 60 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-python $R/bench.py --config 5 --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
-INFX_FORCE_SHARDED=1 python $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
-B="python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --sessions 1"
+python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_20steps.json 2> $O/bench_20steps.err
+python $R/bench.py --full --no-cpu-baseline > $O/bench_256steps.json 2> $O/bench_256steps.err
+python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --sessions 3 > $O/bench_20steps_sessions3.json 2> $O/bench_20steps_sessions3.err
+python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --sessions 5 > $O/bench_20steps_sessions5.json 2> $O/bench_20steps_sessions5.err
+python $R/bench.py --full --config 2 --steps 60 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python $R/bench.py --full --config 3 --steps 60 --warmup 5 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+python $R/bench.py --full --config 5 --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_cfg5.json 2> $O/bench_cfg5.err
+INFX_FORCE_SHARDED=1 python $R/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
+B="python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --sessions 1"
 timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $B > $O/kt.json 2> $O/kt.err
 find $O/kt -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv; rm -rf $O/kt
-timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt3 -o kt --output-format csv -- python $R/bench.py --config 3 --steps 6 --warmup 2 --no-cpu-baseline --sessions 1 > $O/kt_cfg3.json 2> $O/kt_cfg3.err
+timeout 400 rocprofv3 --kernel-trace --stats -d $O/kt3 -o kt --output-format csv -- python $R/bench.py --full --config 3 --steps 6 --warmup 2 --no-cpu-baseline --sessions 1 > $O/kt_cfg3.json 2> $O/kt_cfg3.err
 find $O/kt3 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats_cfg3.csv; rm -rf $O/kt3
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch -o p --output-format csv -- $B > $O/pmc_fetch.json 2> $O/pmc_fetch.err
 timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_ANY -d $O/pmc_sq -o p --output-format csv -- $B > $O/pmc_sq.json 2> $O/pmc_sq.err

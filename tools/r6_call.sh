@@ -7,7 +7,7 @@ for step in "$@"; do
     test) ( timeout 1500 python -m pytest tests -m gpu -q -x > $O/gputest.log 2>&1; echo "gputest rc=$?" >> $O/gputest.log ); tail -5 $O/gputest.log ;;
     testfile:*) f=${step#testfile:}; n=$(echo $f | tr '/:' '__'); ( timeout 1500 python -m pytest $f -m gpu -q -x > $O/test_$n.log 2>&1; echo "rc=$?" >> $O/test_$n.log ); tail -15 $O/test_$n.log ;;
     bench:*) IFS=: read -r _ name envs args <<< "$step"
-      ( for kv in ${envs//,/ }; do export $kv; done; timeout 900 python bench.py $args > $O/$name.json 2> $O/$name.err )
+      ( for kv in ${envs//,/ }; do export $kv; done; timeout 900 python bench.py --full $args > $O/$name.json 2> $O/$name.err )
       python - $O/$name.json <<'PY'
 import json,sys
 try:
