@@ -234,6 +234,15 @@ int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, cha
 int32_t infx_engine_set_filter(infx_session* s, const char* expr_utf8 /* NULL = no filter */, int32_t enable_facets, uint32_t* n_in_filter);
 int32_t infx_engine_facet_column_count(infx_session* s);
 int32_t infx_engine_last_facets(infx_session* s, uint32_t nq, uint32_t qi, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap);
+/* Query.EnableBoost + Query.Boosts (ResultProcessor.ApplyBoosts, Scoring/ResultProcessor.cs:75-121) for the following searches on the session: n boosts,
+ * exprs[i] its Infiscript filter (NULL: a Boost whose Filter is null, dropped), strengths[i] = (int)BoostStrength (Low 1, Med 2, High 3).  enable = 0
+ * (or n = 0) clears and compiles nothing.  Filters are compiled through the engine's filter cache; a boost never counts NumberOfDocumentsInFilter.
+ * Status: INFX_EINVAL + message for a syntax error, INFX_EUNSUPPORTED for MATCHES, INFX_ECAPACITY for more than INFX_MAX_BOOSTS with a filter. */
+int32_t infx_engine_set_boosts(infx_session* s, uint32_t n, const char* const* exprs, const int32_t* strengths, int32_t enable);
+/* Query.SortBy / Query.SortAscending (ResultProcessor.ApplySort, :126-141): field = a column name (case sensitive; unknown: every row null), NULL = sort
+ * by relevance.  The first use of a column builds its dense sort rank (CompareValues: int64 / double — NaN lowest, -0 == +0 — numerically, strings
+ * OrdinalIgnoreCase then ordinal, PARITY UNPINNED) and uploads it to the device. */
+int32_t infx_engine_set_sort(infx_session* s, const char* field, int32_t ascending);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI
  * (infx_stage2_batch) prepare Stage-2 inputs without the engine's search path. */
 int32_t infx_engine_prepare_cov_query(infx_engine* e, const uint16_t* q, int32_t len, infx_cov_query* out);

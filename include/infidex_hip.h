@@ -272,6 +272,23 @@ int32_t infx_stream_set_postfilter(infx_stream* s, infx_filter* f, uint32_t nfac
  * [(q*nfacet+k)*INFX_FILTER_MAX_ROWS ..], in row order of first occurrence (the host orders them: count desc, value asc). */
 int32_t infx_last_facets(infx_stream* s, uint32_t nq, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out);
 
+/* ---- Query.Boosts + Query.SortBy on the returned rows (k_postproc) ----------------------------------------------------------------------
+ * Replaces ResultProcessor.ApplyBoosts / ApplySort (Scoring/ResultProcessor.cs:75-141, 180-201) as SearchEngine.ApplyPostProcessing calls them
+ * after ApplyFilter (SearchEngine.cs:348-361).  Installed on a stream, they apply to every following infx_search_fused / infx_shard_finalize,
+ * after the post-filter, on at most INFX_FILTER_MAX_ROWS rows per query (more: INFX_EUNSUPPORTED).  Both steps end in the BCL's unstable
+ * introsort (Array.Sort with a Comparison), replayed on the device, so rows that compare equal come back in the reference's order. */
+#define INFX_MAX_BOOSTS 8
+/* Sort rank of column col: rank[v] for each of its num_values distinct values (codes), dense — equal values share a rank — in the order of
+ * CompareValues (the host encodes the value semantics: numbers, NaN lowest, -0 == +0, strings).  num_values must be the column's. */
+int32_t infx_upload_sort_rank(infx_index* idx, uint32_t col, uint32_t num_values, const uint32_t* rank);
+/* Query.Boosts with Query.EnableBoost: n boosts, f[i] its filter (NULL: a Boost whose Filter is null, dropped), strengths[i] = (int)BoostStrength.
+ * At most INFX_MAX_BOOSTS with a filter (INFX_ECAPACITY).  Once one with a filter is installed, the rows are re-sorted by score descending even
+ * when no row was boosted.  n = 0 clears. */
+int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f, const int32_t* strengths);
+/* Query.SortBy / Query.SortAscending: sort the rows by column col (0xFFFFFFFF: no such field — every row null, the sort still permutes rows);
+ * enabled = 0 clears.  The column's sort rank must have been uploaded. */
+int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, int32_t enabled);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on
  * the stream the kernels ran on. */

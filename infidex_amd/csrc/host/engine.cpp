@@ -135,6 +135,7 @@ struct infx_engine {
     // non-indexed document fields (DocumentFields) as dictionary-encoded columns + compiled Infiscript filters (config 5)
     std::vector<filt::Column> columns; std::mutex filterMu; std::unordered_map<std::string, CompiledFilter> filters;
     std::vector<infx_filter*> retiredFilters;     // compiled against an older column set (a session's stream may still point at one): freed with the engine
+    std::vector<uint8_t> sortRanked;              // per column: its sort rank is on the device (infx_engine_set_sort, built on first use)
     // NumberOfDocumentsInFilter is cached per expression; a Filter parsed after a mutation counts again (the reference keeps the count on the Filter instance)
     void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = false; }
     void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); }
@@ -2170,6 +2171,30 @@ int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, cha
     if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
     return (int32_t)t.size();
 }
+// The compiled device program of an Infiscript expression, from the engine's cache (compiled on first use).  Caller holds e->filterMu.
+static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter** out) {
+    auto it = e->filters.find(expr);
+    if (it == e->filters.end()) {
+        filt::Program P;
+        try { P = filt::parse(expr); }
+        catch (const filt::Unsupported& x) { return efail(INFX_EUNSUPPORTED, x.what()); }
+        catch (const filt::SyntaxError& x) { return efail(INFX_EINVAL, std::string("filter syntax error: ") + x.what()); }
+        std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables, w;
+        for (auto& in : P.code) ops.push_back(infx_filter_op{in.op, in.arg});
+        for (auto& L : P.leaves) {
+            int ci = -1; for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == L.field) ci = (int)c;      // field names are case sensitive (Dictionary<string, Field>)
+            filt::leaf_table(L, ci >= 0 ? &e->columns[ci] : nullptr, w);
+            leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
+            tables.insert(tables.end(), w.begin(), w.end());
+        }
+        CompiledFilter cf;
+        int32_t rc = infx_filter_create(e->dev, (uint32_t)ops.size(), ops.data(), (uint32_t)leaves.size(), leaves.data(), (uint32_t)tables.size(), tables.data(), &cf.dev);
+        if (rc) { g_eerr = infx_last_error(); return rc; }
+        it = e->filters.emplace(expr, cf).first;
+    }
+    *out = &it->second;
+    return INFX_OK;
+}
 // Installs Query.Filter (expr, UTF-8; NULL = none) and Query.EnableFacets on the session: every following search on it post-filters its rows
 // on the device and counts the facetable fields.  n_in_filter = Filter.NumberOfDocumentsInFilter (this shard's share when sharded),
 // counted on the device the first time the expression is used.  Status: INFX_EINVAL + message for a syntax error (FilterParseException),
@@ -2181,31 +2206,14 @@ int32_t infx_engine_set_filter(infx_session* S, const char* expr, int32_t enable
     infx_filter* dev = nullptr; uint32_t cnt = 0;
     if (expr) {
         std::lock_guard<std::mutex> lk(e->filterMu);
-        auto it = e->filters.find(expr);
-        if (it == e->filters.end()) {
-            filt::Program P;
-            try { P = filt::parse(expr); }
-            catch (const filt::Unsupported& x) { return efail(INFX_EUNSUPPORTED, x.what()); }
-            catch (const filt::SyntaxError& x) { return efail(INFX_EINVAL, std::string("filter syntax error: ") + x.what()); }
-            std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables, w;
-            for (auto& in : P.code) ops.push_back(infx_filter_op{in.op, in.arg});
-            for (auto& L : P.leaves) {
-                int ci = -1; for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == L.field) ci = (int)c;      // field names are case sensitive (Dictionary<string, Field>)
-                filt::leaf_table(L, ci >= 0 ? &e->columns[ci] : nullptr, w);
-                leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
-                tables.insert(tables.end(), w.begin(), w.end());
-            }
-            CompiledFilter cf;
-            int32_t rc = infx_filter_create(e->dev, (uint32_t)ops.size(), ops.data(), (uint32_t)leaves.size(), leaves.data(), (uint32_t)tables.size(), tables.data(), &cf.dev);
+        CompiledFilter* cf = nullptr;
+        { int32_t rc = compile_filter(e, expr, &cf); if (rc) return rc; }
+        if (!cf->counted) {       // ResultProcessor.cs:39-54: first use runs the filter over every document
+            int32_t rc = infx_filter_count(S->stream, cf->dev, &cf->inFilter);
             if (rc) { g_eerr = infx_last_error(); return rc; }
-            it = e->filters.emplace(expr, cf).first;
+            cf->counted = true;
         }
-        if (!it->second.counted) {       // ResultProcessor.cs:39-54: first use runs the filter over every document
-            int32_t rc = infx_filter_count(S->stream, it->second.dev, &it->second.inFilter);
-            if (rc) { g_eerr = infx_last_error(); return rc; }
-            it->second.counted = true;
-        }
-        dev = it->second.dev; cnt = it->second.inFilter;
+        dev = cf->dev; cnt = cf->inFilter;
     }
     S->facetCols.clear();
     if (enable_facets) for (size_t c = 0; c < e->columns.size() && S->facetCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) S->facetCols.push_back((uint32_t)c);
@@ -2232,5 +2240,51 @@ int32_t infx_engine_last_facets(infx_session* S, uint32_t nq, uint32_t qi, uint3
     return m;
 }
 int32_t infx_engine_facet_column_count(infx_session* S) { return S ? (int32_t)S->facetCols.size() : -1; }
+
+// ---- Query.Boosts / Query.SortBy (SearchEngine.cs:355-359): ResultProcessor.ApplyBoosts / ApplySort on the device after the post-filter -------------
+int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* exprs, const int32_t* strengths, int32_t enable) {
+    if (!S || (enable && n && (!exprs || !strengths))) return efail(INFX_EINVAL, "bad boost arguments");
+    infx_engine* e = S->e;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: boosts run on the device");
+    std::vector<infx_filter*> devs; std::vector<int32_t> st;
+    if (enable) {       // SearchEngine.cs:355: only with EnableBoost; a Boost whose Filter is null is dropped (ResultProcessor.cs:84-85)
+        uint32_t withFilter = 0;
+        for (uint32_t i = 0; i < n; i++) withFilter += exprs[i] != nullptr;
+        if (withFilter > INFX_MAX_BOOSTS) return efail(INFX_ECAPACITY, "more than INFX_MAX_BOOSTS (8) boosts with a filter");
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < n; i++) {
+            if (!exprs[i]) continue;
+            CompiledFilter* cf = nullptr;
+            int32_t rc = compile_filter(e, exprs[i], &cf);      // ApplyBoosts never counts NumberOfDocumentsInFilter
+            if (rc) return rc;
+            devs.push_back(cf->dev); st.push_back(strengths[i]);
+        }
+    }
+    int32_t rc = infx_stream_set_boosts(S->stream, (uint32_t)devs.size(), devs.data(), st.data());
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    return INFX_OK;
+}
+int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascending) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    infx_engine* e = S->e;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: sort-by runs on the device");
+    uint32_t col = 0xFFFFFFFFu;
+    if (field) {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == field) col = (uint32_t)c;      // case sensitive, as the filter's fields
+        if (col != 0xFFFFFFFFu) {
+            if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
+            if (!e->sortRanked[col]) {
+                std::vector<uint32_t> rank; filt::sort_rank(e->columns[col], rank);
+                int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
+                if (rc) { g_eerr = infx_last_error(); return rc; }
+                e->sortRanked[col] = 1;
+            }
+        }
+    }
+    int32_t rc = infx_stream_set_sort(S->stream, col, ascending, field != nullptr);
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    return INFX_OK;
+}
 
 } // extern "C"

@@ -252,6 +252,28 @@ template <class Key, class Get> inline void encode_column(Column& c, size_t n, G
     c.rank.resize(ord.size()); for (size_t i = 0; i < ord.size(); i++) c.rank[ord[i]] = (uint32_t)i;
 }
 
+// ResultProcessor.CompareValues (Scoring/ResultProcessor.cs:180-201) of two values of one column: IComparable.CompareTo of the same type — long numerically;
+// double.CompareTo with NaN lowest, every NaN equal and -0 == +0; string with the current-culture comparer, read as OrdinalIgnoreCase then ordinal like
+// the facet order above (PARITY UNPINNED)
+inline int sort_cmp(const Boxed& a, const Boxed& b) {
+    if (a.kind == 1) return a.i < b.i ? -1 : (a.i > b.i ? 1 : 0);
+    if (a.kind == 2) {
+        const bool na = std::isnan(a.d), nb = std::isnan(b.d);
+        if (na || nb) return na && nb ? 0 : (na ? -1 : 1);
+        return a.d < b.d ? -1 : (a.d > b.d ? 1 : 0);
+    }
+    const int x = icmp(a.s, b.s);
+    return x ? x : (a.s < b.s ? -1 : (b.s < a.s ? 1 : 0));
+}
+// dense sort rank of the codes: values that compare equal share a rank (k_postproc sorts by it; the null of an absent field is below every rank)
+inline void sort_rank(const Column& c, std::vector<uint32_t>& rank) {
+    std::vector<uint32_t> ord(c.dict.size()); for (size_t i = 0; i < ord.size(); i++) ord[i] = (uint32_t)i;
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return sort_cmp(c.dict[a], c.dict[b]) < 0; });
+    rank.assign(ord.size(), 0u);
+    uint32_t r = 0;
+    for (size_t i = 1; i < ord.size(); i++) { if (sort_cmp(c.dict[ord[i - 1]], c.dict[ord[i]]) != 0) r++; rank[ord[i]] = r; }
+}
+
 // leaf -> bitmap over the codes of its column (bit = the leaf holds for that distinct value); an unknown field is null for every document
 inline void leaf_table(const Leaf& L, const Column* col, std::vector<uint32_t>& words) {
     const size_t nv = col ? col->dict.size() : 1;

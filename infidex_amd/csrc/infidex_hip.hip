@@ -78,6 +78,7 @@ struct infx_index {
     std::vector<uint32_t> hSkipIdx;   // host copy of DevIndex::skipIdx (filled by infx_upload_postings)
     uint8_t* dDeleted = nullptr;      // device copy of the global Document.Deleted flags (infx_set_deleted)
     const uint32_t* colCodes[FILT_MAXCOL] = {}; uint32_t colValues[FILT_MAXCOL] = {}; uint32_t colDocs[FILT_MAXCOL] = {}; uint32_t colCap[FILT_MAXCOL] = {};   // device-resident columns (infx_upload_column)
+    const uint32_t* colRank[FILT_MAXCOL] = {}; uint32_t colRankCap[FILT_MAXCOL] = {}; bool colRankOk[FILT_MAXCOL] = {};     // sort ranks of their codes (infx_upload_sort_rank); a column re-upload voids its rank
     std::vector<uint64_t> hPsOff;
     int rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;         // infx_set_shard_comm
@@ -235,6 +236,8 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "fused.hip.inc"
 #include "lookup.hip.inc"
 #include "filter.hip.inc"
+#include "bclsort.hip.inc"
+#include "postproc.hip.inc"
 
 // ---------------------------------------------------------------------------------------------------------------
 struct infx_filter {
@@ -248,6 +251,10 @@ struct infx_stream {
     void *dFDocs = nullptr, *dFacetCols = nullptr, *dFacCodes = nullptr, *dFacCounts = nullptr, *dFacN = nullptr;
     size_t capFDocs = 0, capFacCodes = 0, capFacCounts = 0, capFacN = 0;
     std::vector<uint32_t> hFacCodes, hFacCounts, hFacN; uint32_t facetNq = 0;
+    // boosts / sort-by (infx_stream_set_boosts / _set_sort): applied after the post-filter (k_postproc)
+    infx_filter* boosts[INFX_MAX_BOOSTS] = {}; int32_t boostStrength[INFX_MAX_BOOSTS] = {}; uint32_t nBoost = 0;
+    uint32_t sortCol = 0; bool sortOn = false, sortAsc = false;
+    void* dPostProc = nullptr;     // the DevPostProc of k_postproc, staged on the stream by each finalize that launches it
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1073,7 +1080,7 @@ void infx_stream_destroy(infx_stream* s) {
     hipSetDevice(s->ix->cfg.device);
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
-                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
+                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostProc, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
                   s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder};
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -1699,11 +1706,15 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     const size_t lds = (size_t)Cp * (8 + 4 + 4 + 2 + 1 + 1) + (P2_THREADS + 1) * 4 + 64;
     const bool post = s->postFilter != nullptr || s->nFacet > 0;
     if (post && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "post-filter / facets run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
-    if (post) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
+    const bool pp = s->nBoost > 0 || s->sortOn;         // boosts / sort-by: k_postproc after k_postfilter
+    if (pp && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "boosts / sort-by run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
+    const bool sortKnown = s->sortOn && s->sortCol != 0xFFFFFFFFu;
+    if (sortKnown && (s->sortCol >= FILT_MAXCOL || !ix->colCodes[s->sortCol] || !ix->colRankOk[s->sortCol])) return fail(INFX_EINVAL, "the sort column's rank is not uploaded%s");
+    if (post || pp) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
     k_finalize<<<nq, P2_THREADS, lds, s->st>>>(ix->d, (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
-                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, post ? (int32_t*)s->dFDocs : nullptr);
+                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, post || pp ? (int32_t*)s->dFDocs : nullptr);
     HIPCHK(hipGetLastError());
     s->facetNq = 0;
     if (post) {     // ResultProcessor.ApplyFilter + FacetBuilder on the rows just produced, before they leave the device
@@ -1720,6 +1731,19 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
             s->hFacCodes.resize(fe); s->hFacCounts.resize(fe); s->hFacN.resize((size_t)nq * s->nFacet); s->facetNq = nq;
             DOWN(s->hFacCodes.data(), s->dFacCodes, fe * 4); DOWN(s->hFacCounts.data(), s->dFacCounts, fe * 4); DOWN(s->hFacN.data(), s->dFacN, (size_t)nq * s->nFacet * 4);
         }
+    }
+    if (pp) {       // ResultProcessor.ApplyBoosts + ApplySort on the kept rows (facets count rows, not their order: FacetBuilder's result is the same)
+        DevPostProc P{};
+        for (uint32_t b = 0; b < s->nBoost; b++) { P.boost[b] = s->boosts[b]->d; P.strength[b] = s->boostStrength[b]; }
+        P.nboost = s->nBoost;
+        P.rank = sortKnown ? ix->colRank[s->sortCol] : nullptr; P.sortCol = sortKnown ? s->sortCol : 0; P.sortOn = s->sortOn ? 1 : 0; P.ascending = s->sortAsc ? 1 : 0;
+        P.keys = (long long*)s->dFKeys; P.scores = (float*)s->dFScores; P.ties = ties ? (uint8_t*)s->dFTies : nullptr; P.docs = (int32_t*)s->dFDocs;
+        P.counts = (const uint32_t*)s->dFCounts; P.stride = max_results;
+        if (!s->dPostProc) HIPCHK(hipMalloc(&s->dPostProc, sizeof(DevPostProc)));
+        UP(s->dPostProc, &P, sizeof(P));
+        DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+        k_postproc<<<nq, WAVE, 0, s->st>>>((const DevPostProc*)s->dPostProc, cols);
+        HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(s->evF1, s->st));
     s->timedFused = true;
@@ -2185,7 +2209,7 @@ int32_t infx_upload_column(infx_index* ix, uint32_t col, uint32_t total_docs, co
     uint32_t* d = const_cast<uint32_t*>(ix->colCodes[col]);
     if (!d || ix->colCap[col] < total_docs) { HIPCHK(dalloc(ix, &d, (size_t)total_docs + 1)); ix->colCap[col] = total_docs; }     // a re-upload reuses the column's buffer
     if (total_docs) HIPCHK(hipMemcpy(d, codes, (size_t)total_docs * 4, hipMemcpyHostToDevice));
-    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs;
+    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false;
     return INFX_OK;
 }
 int32_t infx_filter_create(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
@@ -2250,6 +2274,39 @@ int32_t infx_stream_set_postfilter(infx_stream* s, infx_filter* f, uint32_t nfac
         if (s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
     s->postFilter = f; s->nFacet = nfacet;
     for (uint32_t c = 0; c < INFX_MAX_FACET_COLS; c++) s->facetCols[c] = c < nfacet ? facet_cols[c] : 0;
+    return INFX_OK;
+}
+// ---- Query.Boosts + Query.SortBy (k_postproc) ----------------------------------------------------------------------------------------
+int32_t infx_upload_sort_rank(infx_index* ix, uint32_t col, uint32_t num_values, const uint32_t* rank) {
+    if (!ix || col >= FILT_MAXCOL || (num_values && !rank)) return fail(INFX_EINVAL, "bad sort-rank arguments%s");
+    if (!ix->colCodes[col] || num_values != ix->colValues[col]) return fail(INFX_EINVAL, "a sort rank needs one entry per distinct value of an uploaded column%s");
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());                      // exclusive call, as infx_upload_column: no search is reading a rank that is rewritten
+    uint32_t* d = const_cast<uint32_t*>(ix->colRank[col]);
+    if (!d || ix->colRankCap[col] < num_values) { HIPCHK(dalloc(ix, &d, (size_t)num_values)); ix->colRankCap[col] = num_values; }
+    if (num_values) HIPCHK(hipMemcpy(d, rank, (size_t)num_values * 4, hipMemcpyHostToDevice));
+    ix->colRank[col] = d; ix->colRankOk[col] = true;
+    return INFX_OK;
+}
+int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f, const int32_t* strengths) {
+    if (!s || (n && (!f || !strengths))) return fail(INFX_EINVAL, "bad boost arguments%s");
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; i++) if (f[i]) { if (f[i]->ix != s->ix) return fail(INFX_EINVAL, "a boost filter belongs to another index%s"); m++; }
+    if (m > INFX_MAX_BOOSTS) return fail(INFX_ECAPACITY, "more than INFX_MAX_BOOSTS boosts with a filter%s");
+    for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids: a column shorter than the corpus would be read out of bounds
+        if (m && s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    s->nBoost = 0;
+    for (uint32_t i = 0; i < n; i++) if (f[i]) { s->boosts[s->nBoost] = f[i]; s->boostStrength[s->nBoost] = strengths[i]; s->nBoost++; }
+    for (uint32_t i = s->nBoost; i < INFX_MAX_BOOSTS; i++) { s->boosts[i] = nullptr; s->boostStrength[i] = 0; }
+    return INFX_OK;
+}
+int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, int32_t enabled) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (enabled && col != 0xFFFFFFFFu) {
+        if (col >= FILT_MAXCOL || !s->ix->colCodes[col] || !s->ix->colRankOk[col]) return fail(INFX_EINVAL, "sort column or its rank was not uploaded%s");
+        if (s->ix->colDocs[col] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    }
+    s->sortOn = enabled != 0; s->sortCol = enabled ? col : 0; s->sortAsc = enabled && ascending != 0;
     return INFX_OK;
 }
 int32_t infx_last_facets(infx_stream* s, uint32_t nq, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out) {

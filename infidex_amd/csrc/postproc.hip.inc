@@ -1,0 +1,62 @@
+// Query.Boosts + Query.SortBy on the rows a search returns (SearchEngine.cs:348-361 after ApplyFilter).  Included by infidex_hip.hip after filter.hip.inc.
+//   k_postproc  one wave per query, one lane per row (<= INFX_FILTER_MAX_ROWS), after k_postfilter:
+//     1. ResultProcessor.ApplyBoosts (ResultProcessor.cs:75-121): per row the sum of the strengths of the boost programs its document satisfies
+//        (filt_eval), Score = Score + totalBoost as an fp32 add where totalBoost > 0; then Array.Sort by score descending — always, once a boost
+//        with a filter is installed, so rows with equal scores move even when none was boosted.
+//     2. ResultProcessor.ApplySort (:126-141, CompareValues :180-201): key = 1 + rank[code of the row's document] (0 = null: the field does not exist),
+//        Array.Sort with CompareValues(a, b) ascending or CompareValues(b, a) descending.
+//   Both sorts are the BCL's unstable introsort (bclsort.hip.inc), run serially over the <= 64 rows with wave-uniform control flow: lane i holds the
+//   row at position i and the i-th pending range; an element is read with v_readlane at a uniform index and written with a per-lane select, so the
+//   compares and branches are scalar and nothing lives in scratch or LDS.  The permuted rows are gathered with shuffles and written back in place.
+//   The launch's parameters live in device memory (staged on the stream): as kernel arguments the boost programs and row pointers stayed in scalar
+//   registers across filt_eval and the sorts and spilled.
+struct DevPostProc {
+    DevFilter boost[INFX_MAX_BOOSTS]; int32_t strength[INFX_MAX_BOOSTS]; uint32_t nboost;      // boost programs with a filter, in Query.Boosts order
+    const uint32_t* rank; uint32_t sortCol; int32_t sortOn, ascending;                             // rank == nullptr: unknown field, every row null
+    // rows of query q: [q * stride, + counts[q]), stride <= INFX_FILTER_MAX_ROWS — boosted and reordered in place (ties may be null)
+    long long* keys; float* scores; uint8_t* ties; int32_t* docs; const uint32_t* counts; int32_t stride;
+};
+__device__ __forceinline__ int pp_readlane(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
+// the sequence accessor of bclsort.hip.inc over the lanes of the wave; MODE 0 score descending, 1 key ascending, 2 key descending
+template <int MODE> struct PpLanes {
+    int lane, perm, frame;          // perm: the row at position `lane`; frame: slot `lane` of the pending-range stack
+    int v;                          // this lane's row: its score (float bits, MODE 0) or its sort key
+    __device__ __forceinline__ int get(int i) const { return pp_readlane(perm, i); }
+    __device__ __forceinline__ void set(int i, int x) { perm = lane == i ? x : perm; }
+    __device__ __forceinline__ int fget(int i) const { return pp_readlane(frame, i); }
+    __device__ __forceinline__ void fset(int i, int x) { frame = lane == i ? x : frame; }
+    __device__ __forceinline__ int cmp(int a, int b) const {
+        if (MODE == 0) return bcl_cmp_float(__int_as_float(pp_readlane(v, b)), __int_as_float(pp_readlane(v, a)));
+        const uint32_t x = (uint32_t)pp_readlane(v, a), y = (uint32_t)pp_readlane(v, b);
+        return MODE == 1 ? bcl_cmp_u32(x, y) : bcl_cmp_u32(y, x);
+    }
+};
+template <int MODE> __device__ __forceinline__ int pp_sort(int perm, int v, int n) {
+    PpLanes<MODE> L{(int)threadIdx.x, perm, 0, v};
+    bcl_introsort(L, n);
+    return L.perm;
+}
+__global__ __launch_bounds__(WAVE) void k_postproc(const DevPostProc* __restrict__ pp, DevColumns cols) {
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int stride = pp->stride;
+    const int n = (int)min(pp->counts[q], (uint32_t)min(stride, WAVE));
+    const bool have = lane < n;
+    const size_t o = (size_t)q * stride;
+    float s = 0.f; int32_t d = 0;
+    if (have) { s = pp->scores[o + lane]; d = pp->docs[o + lane]; }
+    uint32_t key = 0;
+    if (pp->sortOn && have && pp->rank) key = 1u + pp->rank[cols.codes[pp->sortCol][d]];       // the sort value of the row's document, before the boosts move it
+    const uint32_t nboost = pp->nboost;
+    if (nboost) {
+        uint32_t total = 0;                                                     // int arithmetic of the reference (wraps like unchecked C#)
+        if (have) for (uint32_t b = 0; b < nboost; b++) if (filt_eval(pp->boost[b], cols, d)) total += (uint32_t)pp->strength[b];
+        if ((int32_t)total > 0) s = s + (float)(int32_t)total;                 // float newScore = result.Score + totalBoost
+    }
+    int perm = lane;                                                            // the row at position `lane`: a permutation of [0, n) on the first n lanes
+    if (nboost) perm = pp_sort<0>(perm, __float_as_int(s), n);
+    if (pp->sortOn) perm = pp->ascending ? pp_sort<1>(perm, (int)key, n) : pp_sort<2>(perm, (int)key, n);
+    long long k = 0; int t = 0;
+    if (have) { k = pp->keys[o + lane]; if (pp->ties) t = pp->ties[o + lane]; }
+    const long long k2 = __shfl(k, perm); const float s2 = __shfl(s, perm); const int t2 = __shfl(t, perm); const int32_t d2 = __shfl(d, perm);
+    if (have) { pp->keys[o + lane] = k2; pp->scores[o + lane] = s2; if (pp->ties) pp->ties[o + lane] = (uint8_t)t2; pp->docs[o + lane] = d2; }
+}

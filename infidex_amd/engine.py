@@ -1,7 +1,7 @@
 """ctypes binding of libinfidex_hip.so with the reference's public names for the hot path.
 
 Mirrors (reference paths under src/Infidex): SearchEngine.cs (CreateDefault/CreateMinimal/IndexDocuments/Search),
-Api/Query.cs, Api/Result.cs, Core/Document.cs, Api/Weight.cs, Core/ScoreEntry.cs.
+Api/Query.cs, Api/Boost.cs, Api/BoostStrength.cs, Api/Result.cs, Core/Document.cs, Api/Weight.cs, Core/ScoreEntry.cs.
 """
 import ctypes as C
 import os
@@ -43,6 +43,16 @@ class Document:    # Core/Document.cs:76-88 (single text => one 'content' field,
         return [Field("content", self.fields, Weight.Med)] if isinstance(self.fields, str) else list(self.fields)
 
 
+class BoostStrength:    # Api/BoostStrength.cs
+    Low, Med, High = 1, 2, 3
+
+
+@dataclass
+class Boost:       # Api/Boost.cs: documents matching the filter get +strength on their score (ResultProcessor.ApplyBoosts)
+    filter: Optional[str]                  # Infiscript expression; None = a Boost whose Filter is null (ignored)
+    strength: int = BoostStrength.Med
+
+
 @dataclass
 class Query:       # Api/Query.cs:9-40
     text: str
@@ -51,6 +61,16 @@ class Query:       # Api/Query.cs:9-40
     enable_coverage: bool = True
     filter: Optional[str] = None           # Infiscript expression (Filter.Parse), applied to the returned rows (ResultProcessor.ApplyFilter)
     enable_facets: bool = False
+    enable_boost: bool = False             # Query.EnableBoost: Boosts apply only when set
+    boosts: Optional[Sequence[Boost]] = None
+    sort_by: Optional[str] = None          # Query.SortBy: a field (column) name, None = relevance order
+    sort_ascending: bool = False           # Query.SortAscending
+
+    @property
+    def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
+        if not self.enable_boost or self.boosts is None:
+            return 0
+        return sum(int(b.strength) for b in self.boosts)
 
 
 @dataclass
@@ -261,12 +281,16 @@ class SearchEngine:
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
 
-    def search_filtered(self, texts: Sequence[str], max_results=10, depth=500, enable_coverage=True, filter=None, enable_facets=False, session=None):
-        """Search(Query) with Query.Filter / Query.EnableFacets for a batch sharing one filter: post-filter and facet counts run on the device."""
+    def search_filtered(self, texts: Sequence[str], max_results=10, depth=500, enable_coverage=True, filter=None, enable_facets=False, session=None,
+                        enable_boost=False, boosts=None, sort_by=None, sort_ascending=False):
+        """Search(Query) with Query.Filter / Query.EnableFacets / Query.Boosts / Query.SortBy for a batch sharing them: post-filter, facet counts,
+        boosts and sort-by run on the device (SearchEngine.ApplyPostProcessing order: filter, boosts, sort-by)."""
         sh = session.h if session is not None else self._default_session()
         nin = C.c_uint32(0)
         self._check(self.L.infx_engine_set_filter(sh, filter.encode() if filter is not None else None, int(enable_facets), C.byref(nin)))
         try:
+            _set_boosts(self, sh, boosts, enable_boost)
+            _set_sort(self, sh, sort_by, sort_ascending)
             arena, offs = pack_texts(texts)
             keys, scores, ties, counts, flags = (session or self).search_packed(arena, offs, max_results, depth, enable_coverage)
             nq = len(texts)
@@ -278,12 +302,15 @@ class SearchEngine:
             return out
         finally:
             self.L.infx_engine_set_filter(sh, None, 0, None)
+            self.L.infx_engine_set_boosts(sh, 0, None, None, 0)
+            self.L.infx_engine_set_sort(sh, None, 0)
 
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
-        if q.filter is not None or q.enable_facets:
-            return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets)[0]
+        if q.filter is not None or q.enable_facets or (q.enable_boost and q.boosts) or q.sort_by is not None:
+            return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
+                                        enable_boost=q.enable_boost, boosts=q.boosts, sort_by=q.sort_by, sort_ascending=q.sort_ascending)[0]
         return self.search_batch([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage)[0]
 
     def search_batch_raw(self, texts: Sequence[str], max_results=10, depth=500, enable_coverage=True):
@@ -458,6 +485,14 @@ class Session:
         self.engine._check(self.L.infx_engine_set_filter(self.h, expr.encode() if expr is not None else None, int(enable_facets), C.byref(nin)))
         return int(nin.value)
 
+    def set_boosts(self, boosts=None, enable_boost=True):
+        """Installs Query.Boosts (a sequence of Boost; None or enable_boost=False clears) on this session."""
+        _set_boosts(self.engine, self.h, boosts, enable_boost)
+
+    def set_sort(self, sort_by=None, ascending=False):
+        """Installs Query.SortBy (a field name; None = relevance order) and Query.SortAscending on this session."""
+        _set_sort(self.engine, self.h, sort_by, ascending)
+
     def last_timings(self, kernels=True):
         """Host phase times of the session's last batch; kernels=True adds the kernel durations (HIP events on the session's stream).  Resolving those costs a
         handful of HIP API calls, which queue behind the launches of other sessions: a throughput run asks for them on a sample of its batches only."""
@@ -478,6 +513,19 @@ class Session:
                         "k_accumulate_ms": float(kern[0]), "k_select_ms": float(kern[1]), "k_stage2_ms": float(kern[2]),
                         "k_prep2_ms": float(kern[3]), "k_finalize_ms": float(kern[4])})
         return out
+
+
+def _set_boosts(engine, sh, boosts, enable_boost):
+    """infx_engine_set_boosts: Query.EnableBoost + Query.Boosts on session handle sh (boosts with filter None are passed as NULL and dropped there)."""
+    bs = list(boosts) if boosts else []
+    on = bool(enable_boost) and len(bs) > 0
+    exprs = (C.c_char_p * max(len(bs), 1))(*[b.filter.encode() if b.filter is not None else None for b in bs])
+    st = np.asarray([int(b.strength) for b in bs] or [0], np.int32)
+    engine._check(engine.L.infx_engine_set_boosts(sh, len(bs) if on else 0, exprs, _p(st, C.c_int32), int(on)))
+
+
+def _set_sort(engine, sh, sort_by, ascending):
+    engine._check(engine.L.infx_engine_set_sort(sh, sort_by.encode() if sort_by is not None else None, int(bool(ascending))))
 
 
 def normalize(s, lower=False):

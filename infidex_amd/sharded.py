@@ -194,6 +194,14 @@ class ShardSession:
         """Query.Filter / Query.EnableFacets on this session; returns THIS SHARD's share of Filter.NumberOfDocumentsInFilter (sum over the shards)."""
         return self.s.set_filter(expr, enable_facets)
 
+    def set_boosts(self, boosts=None, enable_boost=True):
+        """Query.Boosts on this session: phase 4 boosts and re-sorts the merged rows after the post-filter (identical on every rank)."""
+        self.s.set_boosts(boosts, enable_boost)
+
+    def set_sort(self, sort_by=None, ascending=False):
+        """Query.SortBy / Query.SortAscending on this session (phase 4, after the boosts)."""
+        self.s.set_sort(sort_by, ascending)
+
     def facets(self, i):
         """Facets of query i of the last batch (phase 4 ran the post-filter and counted the facet values of the kept rows; identical on every rank)."""
         return self.e.facets_of(self.s.h, self.nq, i)
@@ -638,6 +646,17 @@ class ShardedSearcher:
         self.in_filter = int(self.comm.allreduce_sum_i32(np.asarray([mine], np.uint32))[0]) if self.comm.world > 1 else int(mine)
         return self.in_filter
 
+    def set_boosts(self, boosts=None, enable_boost=True):
+        """Query.EnableBoost + Query.Boosts for the following searches (ResultProcessor.ApplyBoosts on the merged rows).  Collective: same call on every
+        rank; nothing is exchanged (a boost never counts documents)."""
+        for s in self.sessions:
+            s.set_boosts(boosts, enable_boost)
+
+    def set_sort(self, sort_by=None, ascending=False):
+        """Query.SortBy / Query.SortAscending for the following searches (ResultProcessor.ApplySort on the merged rows).  Collective: same call on every rank."""
+        for s in self.sessions:
+            s.set_sort(sort_by, ascending)
+
     def last_facets(self, i):
         return self.last.facets(i)
 
@@ -648,6 +667,18 @@ class ShardedSearcher:
 def simulate_set_filter(sessions: Sequence[ShardSession], expr=None, enable_facets=False) -> int:
     """ShardedSearcher.set_filter for the in-process simulation: installs the filter on every shard's session, sums the per-shard counts."""
     return int(sum(s.set_filter(expr, enable_facets) for s in sessions))
+
+
+def simulate_set_boosts(sessions: Sequence[ShardSession], boosts=None, enable_boost=True):
+    """ShardedSearcher.set_boosts for the in-process simulation: installs the boosts on every shard's session."""
+    for s in sessions:
+        s.set_boosts(boosts, enable_boost)
+
+
+def simulate_set_sort(sessions: Sequence[ShardSession], sort_by=None, ascending=False):
+    """ShardedSearcher.set_sort for the in-process simulation."""
+    for s in sessions:
+        s.set_sort(sort_by, ascending)
 
 
 def simulate_shards_dev(sessions: Sequence[ShardSession], arena, offs, max_results=10, depth=500, enable_coverage=True, device="cuda:0"):
