@@ -243,6 +243,39 @@ int32_t infx_engine_set_boosts(infx_session* s, uint32_t n, const char* const* e
  * by relevance.  The first use of a column builds its dense sort rank (CompareValues: int64 / double — NaN lowest, -0 == +0 — numerically, strings
  * OrdinalIgnoreCase then ordinal, PARITY UNPINNED) and uploads it to the device. */
 int32_t infx_engine_set_sort(infx_session* s, const char* field, int32_t ascending);
+/* ---- per-query options: SearchEngine.Search(Query) (SearchEngine.cs:256-362) for a batch of Query objects, each with its own options ----------------
+ * infx_engine_set_query_options installs the options of the session's NEXT search of nq queries, whichever path runs it (infx_engine_session_search_batch,
+ * INFX_PHASED, the sharded phases or infx_session_sharded_finish); that search consumes them.  The host phases (INFX_PHASED) have no device finalize:
+ * there max_results and enable_coverage apply, and a query with a filter, facets, boosts or sort is refused on its own (INFX_EUNSUPPORTED, see below).  The search call's max_results is the row stride and must be
+ * >= every query's (else INFX_EINVAL); its enable_coverage is ANDed with each query's; CoverageDepth stays one per call.  A query with no filter, facets,
+ * boosts or sort behaves as in a plain batch.  A query is rejected on its own — empty result, result flag bit 4 (INFX_RESULT_REJECTED), its status in
+ * out_status[i] and its message from infx_engine_query_error — for a filter syntax error (INFX_EINVAL), MATCHES (INFX_EUNSUPPORTED), more than
+ * INFX_MAX_BOOSTS boosts with a filter (INFX_ECAPACITY), or post-processing on more than INFX_FILTER_MAX_ROWS rows (INFX_EUNSUPPORTED; facets count as
+ * post-processing only when a facetable column exists); its neighbours are unaffected.  Installing while a session-wide filter, facets, boosts or sort is installed (infx_engine_set_filter / _set_boosts / _set_sort) is
+ * INFX_EINVAL, and so is the reverse; a search of another nq fails with INFX_EINVAL and clears the options.  nq = 0 clears.
+ * Filter.NumberOfDocumentsInFilter: the expressions the batch uses for the first time are counted in one k_filter_count_multi launch enqueued with the
+ * batch (no extra host wait); infx_engine_last_in_filter returns each query's count after the batch.  It counts every document of the WHOLE corpus that
+ * is not Deleted, on every rank of a sharded engine (each holds the whole columns and the global Deleted flags): no collective, unlike
+ * infx_engine_set_filter, which reports the shard's share.  Counts are cached per expression in the engine's filter cache (shared with
+ * infx_engine_set_filter), its host entries bounded, least recently used first (infx_engine_set_filter_cache_limit, default 4096: the device copies that
+ * infx_engine_set_filter / _set_boosts made of evicted entries are kept until the engine is destroyed); an installed entry is never evicted, an
+ * evicted one is counted again on its next use.  Deletions and new columns invalidate the counts. */
+typedef struct infx_query_options {
+    int32_t max_results;                    /* MaxNumberOfRecordsToReturn */
+    int32_t enable_coverage, enable_facets, enable_boost;
+    const char* filter;                     /* Infiscript, UTF-8; NULL = none */
+    uint32_t nboosts; const char* const* boost_filters; const int32_t* boost_strengths;      /* Boosts (a NULL filter: a Boost whose Filter is null, dropped) */
+    const char* sort_by; int32_t sort_ascending;                                             /* SortBy (column name, NULL = relevance) / SortAscending */
+} infx_query_options;
+int32_t infx_engine_set_query_options(infx_session* s, uint32_t nq, const infx_query_options* opts, int32_t* out_status /* nq */);
+/* NumberOfDocumentsInFilter of each query of the session's last per-query batch (0 for a query without a filter or rejected) */
+int32_t infx_engine_last_in_filter(infx_session* s, uint32_t nq, uint32_t* out);
+/* how many expressions the session's last per-query batch counted, and in how many kernel launches */
+int32_t infx_engine_last_count_stats(infx_session* s, uint32_t* counted, uint32_t* launches);
+/* the message of query qi's rejection in the last infx_engine_set_query_options ("" if it was accepted); returns its length, -1 out of range */
+int32_t infx_engine_query_error(infx_session* s, uint32_t qi, char* out, int32_t cap);
+int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
+int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI
  * (infx_stage2_batch) prepare Stage-2 inputs without the engine's search path. */
 int32_t infx_engine_prepare_cov_query(infx_engine* e, const uint16_t* q, int32_t len, infx_cov_query* out);

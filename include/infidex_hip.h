@@ -263,7 +263,7 @@ int32_t infx_upload_column(infx_index* idx, uint32_t col, uint32_t total_docs, c
 int32_t infx_filter_create(infx_index* idx, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
                            uint32_t ntable_words, const uint32_t* tables, infx_filter** out);
 void    infx_filter_destroy(infx_filter* f);
-/* Documents of THIS shard the filter accepts (sum over shards = Filter.NumberOfDocumentsInFilter). */
+/* Documents of THIS shard the filter accepts (sum over shards = Filter.NumberOfDocumentsInFilter): k_filter_count_multi with K = 1. */
 int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count);
 /* Installs (f != NULL) or clears the post-filter and the facet columns of this stream: every following infx_search_fused /
  * infx_shard_finalize filters its result rows on the device before they are returned and counts the facet values of the kept rows. */
@@ -288,6 +288,33 @@ int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f
 /* Query.SortBy / Query.SortAscending: sort the rows by column col (0xFFFFFFFF: no such field — every row null, the sort still permutes rows);
  * enabled = 0 clears.  The column's sort rank must have been uploaded. */
 int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, int32_t enabled);
+
+/* ---- per-query post-processing: a batch of Query objects, each with its own Filter / EnableFacets / Boosts / SortBy ----------------------------
+ * infx_stream_set_query_post installs the options of the NEXT batch on the stream (one infx_search_fused, or the infx_shard_finalize of the next
+ * sharded batch); that batch consumes them.  progs: the batch's distinct filter programs (host memory, copied: packed into one blob that is staged
+ * with the batch, nothing is allocated per program); boosts: the batch's boost list, each entry a program index + (int)BoostStrength; post[q]: query
+ * q's descriptor — filter = program index or -1, flags INFX_QP_*, sort_col = column (0xFFFFFFFF: no such field, every row null), boosts
+ * [boost_off, + nboost) with nboost <= INFX_MAX_BOOSTS.  nfacet / facet_cols: the columns a query with INFX_QP_FACETS counts (infx_last_facets;
+ * 0 pairs for the queries without).  A query without filter, facets, boosts or sort passes through unchanged, whatever its number of rows; a query
+ * with post-processing whose rows exceed INFX_FILTER_MAX_ROWS comes back empty with result flag INFX_RESULT_REJECTED (the others of the batch are
+ * unaffected).  ncount: programs [0, ncount) are counted over every document of the corpus that is not Deleted (Filter.NumberOfDocumentsInFilter,
+ * whole corpus on every shard: each holds the whole columns and the global Deleted flags) by k_filter_count_multi, enqueued with the batch: the
+ * counts land in counts_out when the batch's results do.  Exclusive with infx_stream_set_postfilter / _set_boosts / _set_sort (INFX_EINVAL); the
+ * session-wide setters are the case of one descriptor every query shares, on the same kernels.  nq = 0 clears; a batch of another size fails. */
+#define INFX_QP_FACETS 1u
+#define INFX_QP_SORT   2u
+#define INFX_QP_ASC    4u
+#define INFX_RESULT_REJECTED 16u        /* result flag bit 4: the query's post-processing was refused (see above / infx_engine_set_query_options) */
+typedef struct infx_filter_prog { const infx_filter_op* ops; const infx_filter_leaf* leaves; const uint32_t* tables; uint32_t nops, nleaves, ntable_words, reserved; } infx_filter_prog;
+typedef struct infx_query_boost { int32_t prog; int32_t strength; } infx_query_boost;
+typedef struct infx_query_post { int32_t filter; uint32_t flags; uint32_t sort_col; uint32_t boost_off; uint32_t nboost; uint32_t reserved[3]; } infx_query_post;
+int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, const infx_filter_prog* progs, uint32_t nboost, const infx_query_boost* boosts,
+                                   const infx_query_post* post, uint32_t nfacet, const uint32_t* facet_cols, uint32_t ncount, uint32_t* counts_out);
+/* k programs counted in one k_filter_count_multi launch (several past 4096 programs), synchronously: counts[i] = documents not Deleted that progs[i]
+ * accepts — this shard's documents (whole_corpus = 0, as infx_filter_count) or every document of the corpus (1). */
+int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_prog* progs, int32_t whole_corpus, uint32_t* counts);
+/* the programs the last finalize (or infx_filter_count_progs) on this stream counted, and in how many launches */
+int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -1,8 +1,12 @@
 // Infiscript post-filter + facet aggregation on device-resident columns (include/infidex_hip.h, "config 5").  Included by infidex_hip.hip.
-//   k_filter_count  FilterVM.Execute over ALL documents of the shard (Filter.NumberOfDocumentsInFilter, ResultProcessor.cs:39-54): a columnar
-//                   scan — per document one code load per leaf column and a handful of bit tests; HBM-bound at 4 B per (document, column).
-//   k_postfilter    ResultProcessor.ApplyFilter on the <= k rows a search returns (:56-69) + FacetBuilder.BuildFacetForField (:58-105): one wave
-//                   per query, one row per lane; ballot compaction keeps the row order; facet values are counted with wave shuffles.
+//   k_filter_count_multi  FilterVM.Execute of K programs over ALL documents of a range (Filter.NumberOfDocumentsInFilter, ResultProcessor.cs:39-54)
+//                         in one launch: each document's codes of the columns any program reads are loaded once into the thread's LDS slots, the K
+//                         programs run one after another with wave-uniform control flow, ballot + popcount per wave into per-workgroup LDS counters,
+//                         one global atomic per (workgroup, program).  infx_filter_count is the case K = 1.
+//   k_postfilter          ResultProcessor.ApplyFilter on the <= k rows a search returns (:56-69) + FacetBuilder.BuildFacetForField (:58-105): one wave
+//                         per query, one row per lane; ballot compaction keeps the row order; facet values are counted with wave shuffles.  Each
+//                         query reads its own descriptor (DevQPost: filter program or none, facets on or off); the session-wide setters stage one
+//                         descriptor that every query shares.
 struct DevFilter {
     const infx_filter_op* ops; uint32_t nops;
     const infx_filter_leaf* leaves; uint32_t nleaves;
@@ -10,55 +14,105 @@ struct DevFilter {
 };
 struct DevColumns { const uint32_t* codes[FILT_MAXCOL]; };
 
-// three-valued evaluation (F = 0, T = 1, N = 2 "not a bool") of the postfix program for one document (global internal id)
-__device__ __forceinline__ bool filt_eval(const DevFilter& f, const DevColumns& cols, int32_t doc) {
-    uint8_t st[32]; int sp = 0;
+// three-valued evaluation (F = 0, T = 1, N = 2 "not a bool") of the postfix program for one document; code(col) = the document's code in column col.
+// The stack is 2 bits per entry in one 64-bit word, top in the low bits (infx_filter_create bounds the depth at 32): a byte array indexed by the
+// stack pointer cost the boost loop of k_postproc its SGPR budget.
+template <class Code> __device__ __forceinline__ bool filt_eval_codes(const DevFilter& f, Code code) {
+    uint64_t st = 0; int sp = 0;
     for (uint32_t i = 0; i < f.nops; i++) {
         const infx_filter_op o = f.ops[i];
         switch (o.op) {
             case INFX_FOP_LEAF: {
                 const infx_filter_leaf L = f.leaves[o.arg];
-                const uint32_t code = L.col == 0xFFFFFFFFu ? 0u : cols.codes[L.col][doc];
-                const uint32_t bit = code < L.num_values ? (f.tables[L.table_off + (code >> 5)] >> (code & 31)) & 1u : 0u;
-                if (sp < 32) st[sp++] = (uint8_t)bit;
+                const uint32_t c = L.col == 0xFFFFFFFFu ? 0u : code(L.col);
+                const uint32_t bit = c < L.num_values ? (f.tables[L.table_off + (c >> 5)] >> (c & 31)) & 1u : 0u;
+                if (sp < 32) { st = (st << 2) | bit; sp++; }
                 break; }
-            case INFX_FOP_LIT: if (sp < 32) st[sp++] = 2; break;
-            case INFX_FOP_NOT: if (sp >= 1) st[sp - 1] = st[sp - 1] == 1 ? 0 : 1; break;
-            case INFX_FOP_AND: if (sp >= 2) { const uint8_t r = st[sp - 1], l = st[sp - 2]; sp--; st[sp - 1] = l == 0 ? 0 : r; } break;
-            case INFX_FOP_OR: if (sp >= 2) { const uint8_t r = st[sp - 1], l = st[sp - 2]; sp--; st[sp - 1] = l == 1 ? 1 : r; } break;
-            case INFX_FOP_TERN: if (sp >= 3) { const uint8_t b = st[sp - 1], a = st[sp - 2], c = st[sp - 3]; sp -= 2; st[sp - 1] = c == 0 ? b : a; } break;
+            case INFX_FOP_LIT: if (sp < 32) { st = (st << 2) | 2u; sp++; } break;
+            case INFX_FOP_NOT: if (sp >= 1) st = (st & ~3ull) | ((st & 3u) == 1 ? 0u : 1u); break;
+            case INFX_FOP_AND: if (sp >= 2) { const uint32_t r = (uint32_t)st & 3u, l = (uint32_t)(st >> 2) & 3u; st >>= 2; sp--; st = (st & ~3ull) | (l == 0 ? 0u : r); } break;
+            case INFX_FOP_OR: if (sp >= 2) { const uint32_t r = (uint32_t)st & 3u, l = (uint32_t)(st >> 2) & 3u; st >>= 2; sp--; st = (st & ~3ull) | (l == 1 ? 1u : r); } break;
+            case INFX_FOP_TERN: if (sp >= 3) { const uint32_t b = (uint32_t)st & 3u, a = (uint32_t)(st >> 2) & 3u, c = (uint32_t)(st >> 4) & 3u; st >>= 4; sp -= 2; st = (st & ~3ull) | (c == 0 ? b : a); } break;
         }
     }
-    return sp > 0 && st[sp - 1] == 1;
+    return sp > 0 && (st & 3u) == 1;
+}
+// ... of one document (global internal id), its codes read from the columns
+__device__ __forceinline__ bool filt_eval(const DevFilter& f, const DevColumns& cols, int32_t doc) {
+    return filt_eval_codes(f, [&](uint32_t c) { return cols.codes[c][doc]; });
 }
 
-__global__ __launch_bounds__(256) void k_filter_count(DevFilter f, DevColumns cols, int32_t docBase, int32_t n, const uint8_t* __restrict__ deleted, uint32_t* __restrict__ count) {
-    uint32_t c = 0;
-    // GetAllDocuments() is the documents that are not Deleted (Core/DocumentCollection.cs:216-219): flagged documents are not counted
-    for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < n; d += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t g = docBase + (int32_t)d;
-        if (deleted && deleted[g]) continue;
-        c += filt_eval(f, cols, g) ? 1u : 0u;
+// The columns the K programs of one k_filter_count_multi launch read: col[u] for u < nUsed, slot[c] = u for column c = col[u]
+struct DevCountCols { uint32_t nUsed; uint32_t col[FILT_MAXCOL]; uint8_t slot[FILT_MAXCOL]; };
+#define FCM_THREADS 256
+// counts[k] += documents of [docBase, docBase + n) that are not Deleted and that program progs[k] accepts, k < K.  Dynamic LDS: K + nUsed * 256 words.
+__global__ __launch_bounds__(FCM_THREADS) void k_filter_count_multi(const DevFilter* __restrict__ progs, uint32_t K, DevCountCols cc, DevColumns cols,
+                                                                     int32_t docBase, int32_t n, const uint8_t* __restrict__ deleted, uint32_t* __restrict__ counts) {
+    extern __shared__ uint32_t fcm_lds[];
+    uint32_t* cnt = fcm_lds;                      // per-workgroup count of each program
+    uint32_t* codes = fcm_lds + K;                // [u * FCM_THREADS + thread]: the codes of the thread's current document (read back by the same thread only)
+    const int tid = threadIdx.x;
+    for (uint32_t k = tid; k < K; k += FCM_THREADS) cnt[k] = 0;
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * FCM_THREADS; base < n; base += (int64_t)gridDim.x * FCM_THREADS) {
+        const int64_t d = base + tid;
+        const int32_t g = docBase + (int32_t)(d < n ? d : 0);
+        // GetAllDocuments() is the documents that are not Deleted (Core/DocumentCollection.cs:216-219): flagged documents are not counted
+        const bool live = d < n && !(deleted && deleted[g]);
+        for (uint32_t u = 0; u < cc.nUsed; u++) codes[u * FCM_THREADS + tid] = live ? cols.codes[cc.col[u]][g] : 0u;
+        for (uint32_t k = 0; k < K; k++) {
+            const DevFilter f = progs[k];
+            const bool hit = filt_eval_codes(f, [&](uint32_t c) { return codes[(uint32_t)cc.slot[c] * FCM_THREADS + tid]; }) && live;
+            const unsigned long long b = __ballot(hit);
+            if ((tid & (WAVE - 1)) == 0 && b) atomicAdd(&cnt[k], (uint32_t)__popcll(b));
+        }
     }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+    __syncthreads();
+    for (uint32_t k = tid; k < K; k += FCM_THREADS) if (cnt[k]) atomicAdd(&counts[k], cnt[k]);
 }
 
-// rows of query q: keys/scores/ties/docs [q * stride, + counts[q]) — filtered in place; facets of the kept rows
-__global__ __launch_bounds__(WAVE) void k_postfilter(DevFilter f, int haveFilter, DevColumns cols, int stride, long long* __restrict__ keys, float* __restrict__ scores,
-                                                      uint8_t* __restrict__ ties, int32_t* __restrict__ docs, uint32_t* __restrict__ counts,
-                                                      int nfacet, const uint32_t* __restrict__ facetCols, uint32_t* __restrict__ fCodes, uint32_t* __restrict__ fCounts, uint32_t* __restrict__ fN) {
+// ---- per-query post-processing (k_postfilter, k_postproc) ----
+#define QP_FACETS INFX_QP_FACETS           // count the facet columns of the kept rows
+#define QP_SORT   INFX_QP_SORT             // Query.SortBy set (sortCol 0xFFFFFFFF: no such field)
+#define QP_ASC    INFX_QP_ASC              // Query.SortAscending
+#define QP_REJECTED INFX_RESULT_REJECTED   // result flag of a query whose post-processing needs more than INFX_FILTER_MAX_ROWS rows
+struct DevQPost { int32_t filter; uint32_t flags; uint32_t sortCol; uint32_t boostOff; uint32_t nboost; uint32_t pad[3]; };   // filter: program index, -1 none
+struct DevQBoost { int32_t prog; int32_t strength; };
+// One batch's post-processing, staged on the stream by the finalize that launches the kernels
+struct DevPostBatch {
+    const DevFilter* progs; const DevQBoost* boosts; const DevQPost* desc; uint32_t descStride;       // query q: desc[q * descStride] (0: shared by all)
+    const uint32_t* rank[FILT_MAXCOL];                                                                // sort ranks of the columns (nullptr: not uploaded)
+    // rows of query q: [q * stride, + counts[q]), counts[q] <= INFX_FILTER_MAX_ROWS for a query with post-processing — filtered, boosted, reordered in place
+    long long* keys; float* scores; uint8_t* ties; int32_t* docs; uint32_t* counts; uint32_t* flags; int32_t stride;
+};
+
+// facets of query q, column c: fCodes / fCounts [(q * nfacet + c) * INFX_FILTER_MAX_ROWS ..], fN[q * nfacet + c] (0 for a query without facets)
+__global__ __launch_bounds__(WAVE) void k_postfilter(const DevPostBatch* __restrict__ pb, DevColumns cols, int nfacet, const uint32_t* __restrict__ facetCols,
+                                                      uint32_t* __restrict__ fCodes, uint32_t* __restrict__ fCounts, uint32_t* __restrict__ fN) {
     const int q = blockIdx.x, lane = threadIdx.x;
-    const uint32_t n = min(counts[q], (uint32_t)WAVE);
-    const size_t o = (size_t)q * stride;
+    const DevQPost D = pb->desc[(size_t)q * pb->descStride];
+    const bool haveFilter = D.filter >= 0, facets = (D.flags & QP_FACETS) != 0 && nfacet > 0;
+    if (!facets && lane < nfacet) fN[(size_t)q * nfacet + lane] = 0;
+    if (!haveFilter && !facets) return;                                         // no post-filter: the rows pass through, whatever their number
+    uint32_t* counts = pb->counts;
+    if (counts[q] > (uint32_t)WAVE) {                                           // more rows than one wave holds: the query is rejected (empty, flag bit 4)
+        if (lane == 0) { counts[q] = 0; pb->flags[q] |= QP_REJECTED; }
+        if (facets && lane < nfacet) fN[(size_t)q * nfacet + lane] = 0;
+        return;
+    }
+    const uint32_t n = counts[q];
+    const size_t o = (size_t)q * pb->stride;
+    long long* keys = pb->keys; float* scores = pb->scores; uint8_t* ties = pb->ties; int32_t* docs = pb->docs;
     const bool have = (uint32_t)lane < n;
     long long k = 0; float s = 0.f; uint8_t t = 0; int32_t d = 0;
     if (have) { k = keys[o + lane]; s = scores[o + lane]; if (ties) t = ties[o + lane]; d = docs[o + lane]; }
-    const bool keep = have && (!haveFilter || filt_eval(f, cols, d));
+    bool keep = have;
+    if (haveFilter) { const DevFilter f = pb->progs[D.filter]; keep = have && filt_eval(f, cols, d); }
     const unsigned long long bal = __ballot(keep);
     const uint32_t pos = (uint32_t)__popcll(bal & ((1ull << lane) - 1));
     if (keep) { keys[o + pos] = k; scores[o + pos] = s; if (ties) ties[o + pos] = t; docs[o + pos] = d; }      // every read above happened before any write
     if (lane == 0) counts[q] = (uint32_t)__popcll(bal);
+    if (!facets) return;
     for (int c = 0; c < nfacet; c++) {
         const uint32_t code = keep ? cols.codes[facetCols[c]][d] : 0xFFFFFFFFu;
         uint32_t cnt = 0; bool first = keep;

@@ -17,6 +17,7 @@
 #include "../../../include/infidex_engine.h"
 #include <chrono>
 #include <map>
+#include <list>
 #include <unordered_map>
 #include <unordered_set>
 #include <cstdio>
@@ -59,8 +60,20 @@ struct Batch {
     std::shared_ptr<FusedIn> pre;      // sharded phases: per-query device-pipeline inputs prepared in phase 0 (off the collective path)
 };
 
+// Per-query options of the session's next batch (infx_engine_set_query_options): consumed by that batch, whichever search path runs it
+struct QueryOpts {
+    bool on = false, bound = false; uint32_t nq = 0;      // bound: a sharded phase 0 took them for its batch (a second phase 0 finds them stale)
+    std::vector<int32_t> maxResults; std::vector<uint8_t> cov, reject; std::vector<int32_t> status; std::vector<std::string> err;
+    std::vector<std::string> filterExpr;       // per query: its filter ("" = none), for NumberOfDocumentsInFilter after the batch
+    std::vector<std::string> pinned;           // cache entries the batch holds (filters and boosts)
+    std::vector<std::string> countExprs; std::vector<uint32_t> counts;      // expressions the batch counts first (programs [0, n) of its table) + the device's counts
+};
 struct infx_session {
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
+    QueryOpts qo;
+    std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
+    bool swFilter = false, swBoost = false, swSort = false;      // session-wide options installed (infx_engine_set_filter / _set_boosts / _set_sort)
+    std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
     infx_stream* stream = nullptr;
@@ -89,7 +102,25 @@ struct infx_session {
     std::vector<uint8_t> planPeer;                          // planPre[i] came from a peer
 };
 
-struct CompiledFilter { infx_filter* dev = nullptr; uint32_t inFilter = 0; bool counted = false; };
+// One Infiscript expression of the engine's filter cache: its host program (a per-query batch packs it), its device copy (compiled on first use by a
+// session-wide setter), Filter.NumberOfDocumentsInFilter of this shard (infx_engine_set_filter) and of the whole corpus (per-query options; the same
+// number when the engine is not sharded)
+struct CompiledFilter {
+    std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables;
+    infx_filter* dev = nullptr;
+    uint32_t inFilter = 0, inAll = 0; bool counted = false, countedAll = false;
+    uint32_t pins = 0;                      // installs that hold the entry: it is not evicted while > 0
+    std::list<std::string>::iterator lru;
+};
+// per-query options of the session's batch (infx_engine_set_query_options): query i's MaxNumberOfRecordsToReturn (never above the call's row stride)
+// and EnableCoverage; the call's values for a session without options
+static inline int32_t qo_max(const infx_session* S, size_t i, int32_t mr) {
+    return S->qo.on && i < S->qo.nq && S->qo.maxResults[i] >= 1 ? std::min(S->qo.maxResults[i], mr) : mr;
+}
+static inline bool qo_cov(const infx_session* S, size_t i, bool cov) { return cov && (!S->qo.on || i >= S->qo.nq || S->qo.cov[i]); }
+static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results);
+static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static void clear_query_options(infx_session* S);
 // Order of the collectives of a rank's pipeline sessions.  Every session has a communicator and a HIP stream of its own, and its host thread enqueues the
 // collectives of its batch when it gets there — left alone, the relative order of DIFFERENT communicators' kernels on a device depends on thread timing and
 // differs from rank to rank, the classic multi-communicator hang (two collective kernels each holding the CUs the other's peer needs).  The ring makes the
@@ -137,8 +168,20 @@ struct infx_engine {
     std::vector<infx_filter*> retiredFilters;     // compiled against an older column set (a session's stream may still point at one): freed with the engine
     std::vector<uint8_t> sortRanked;              // per column: its sort rank is on the device (infx_engine_set_sort, built on first use)
     // NumberOfDocumentsInFilter is cached per expression; a Filter parsed after a mutation counts again (the reference keeps the count on the Filter instance)
-    void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = false; }
-    void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); }
+    void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = kv.second.countedAll = false; }
+    void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); filterLru.clear(); }
+    // The cache is bounded (per-user expressions would grow it without limit): least recently used first, never an entry an install holds.  An evicted
+    // expression is parsed and counted again on its next use.  Its device copy is parked with the retired ones (hipFree would wait for the whole device).
+    std::list<std::string> filterLru; size_t filterCacheLimit = 4096;
+    void evict_filters() {
+        for (auto it = filterLru.end(); filters.size() > filterCacheLimit && it != filterLru.begin();) {
+            --it;
+            auto f = filters.find(*it);
+            if (f == filters.end() || f->second.pins) continue;
+            if (f->second.dev) retiredFilters.push_back(f->second.dev);
+            filters.erase(f); it = filterLru.erase(it);
+        }
+    }
     HostIndex ix;
     PlanGate gate;
     CollSeq collSeq;
@@ -717,11 +760,11 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
             const ustr& st = P.searchText;
             bool isShort = !st.empty() && st.size() <= 3;
             if (isShort) for (u16 ch : st) if (is_delim(ch)) { isShort = false; break; }
-            if (isShort && (int)Sq.stage1.size() >= max_results) { Sq.done = true; continue; }     // SearchPipeline.cs:114-120
+            if (isShort && (int)Sq.stage1.size() >= qo_max(S, i, max_results)) { Sq.done = true; continue; }     // SearchPipeline.cs:114-120
             int shortCount = 0;
             if (isShort) { int64_t pk = ix.prefixKeys.find(st); shortCount = pk >= 0 ? (int)ix.prefixPop[pk] : 0; }
             bool skipCov = isShort && shortCount > 500;
-            if (!covEnabled || skipCov) { Sq.done = true; continue; }
+            if (!qo_cov(S, i, covEnabled) || skipCov) { Sq.done = true; continue; }
             Sq.runCov = true;
             if (dbg) nsMerge += since(tA);
             auto tB = tick();
@@ -841,12 +884,13 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
 static int32_t ph_finalize(infx_engine* e, infx_session* S, const infx_cov_out* outs, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                            uint32_t* out_counts, uint32_t* out_flags) {
     Batch& B = *S->batch; const HostIndex& ix = e->ix; const int threads = e->threads;
-    const uint32_t nq = B.nq; const int depth = B.depth, max_results = B.maxResults;
+    const uint32_t nq = B.nq; const int depth = B.depth, stride = B.maxResults;
     std::vector<QueryPlan>& plans = S->lastPlans; std::vector<infx_cov_cand>& cands = S->lastCands;
     parallel_dyn(nq, threads, 8, [&](int64_t b, int64_t en, int) {
         std::vector<Entry> fin, cons;
         for (int64_t i = b; i < en; i++) {
             PerQ& Sq = B.pq[i]; const QueryPlan& P = plans[i];
+            const int max_results = qo_max(S, i, B.maxResults);
             uint32_t flags = 0; const std::vector<Entry>* res = &Sq.stage1;
             if (P.unsupported || Sq.envelope) flags |= 1;
             if (Sq.runCov) {
@@ -885,8 +929,8 @@ static int32_t ph_finalize(infx_engine* e, infx_session* S, const infx_cov_out* 
             uint32_t cnt = (uint32_t)std::min<size_t>(res->size(), (size_t)max_results);
             out_counts[i] = cnt;
             for (uint32_t k = 0; k < cnt; k++) {
-                out_keys[(size_t)i * max_results + k] = (*res)[k].key; out_scores[(size_t)i * max_results + k] = (*res)[k].score;
-                if (out_ties) out_ties[(size_t)i * max_results + k] = (*res)[k].tie;
+                out_keys[(size_t)i * stride + k] = (*res)[k].key; out_scores[(size_t)i * stride + k] = (*res)[k].score;
+                if (out_ties) out_ties[(size_t)i * stride + k] = (*res)[k].tie;
             }
             if (out_flags) out_flags[i] = flags;
         }
@@ -977,14 +1021,14 @@ static int32_t build_fused_inputs(infx_engine* e, infx_session* S, int32_t max_r
         WmResult wm;
         for (int64_t i = b; i < en; i++) {
             const QueryPlan& P = plans[i]; infx_fused_query& F = fq[i];
-            F = infx_fused_query{}; F.dev = -1; F.max_results = max_results;
+            F = infx_fused_query{}; F.dev = -1; F.max_results = qo_max(S, i, max_results);
             if (P.blank || P.unsupported) { F.flags = INFX_FQ_SKIP | (P.unsupported ? INFX_FQ_UNSUPPORTED : 0u); continue; }
             F.dev = B.devOf.empty() ? -1 : B.devOf[i];      // (pre-built in phase 0: filled in by fused_inputs_for_phase3)
             const ustr& st = P.searchText;
             bool isShort = !st.empty() && st.size() <= 3;
             if (isShort) for (u16 ch : st) if (is_delim(ch)) { isShort = false; break; }
             if (isShort) { F.flags |= INFX_FQ_SHORT; int64_t pk = ix.prefixKeys.find(st); int shortCount = pk >= 0 ? (int)ix.prefixPop[pk] : 0; if (shortCount > 500) F.flags |= INFX_FQ_SHORTSKIP; }
-            if (!covEnabled || (F.flags & INFX_FQ_SHORTSKIP)) continue;
+            if (!qo_cov(S, i, covEnabled) || (F.flags & INFX_FQ_SHORTSKIP)) continue;
             F.flags |= INFX_FQ_COV;
             const infx_session::PlanPre* pp = S->planPre.size() == nq ? S->planPre[i].get() : nullptr;      // (ph_plan dropped the entries that were not made for this batch)
             if (pp && pp->hasCov) {
@@ -1031,9 +1075,9 @@ static int32_t fused_inputs_for_phase3(infx_engine* e, infx_session* S, int32_t 
     const bool cov = e->ix.cfg.enableCoverage && enable_coverage;
     for (uint32_t i = 0; i < B.nq; i++) {
         infx_fused_query& q = F.fq[i];
-        q.max_results = max_results;
+        q.max_results = qo_max(S, i, max_results);
         if (!(q.flags & INFX_FQ_SKIP)) q.dev = B.devOf.empty() ? -1 : B.devOf[i];
-        if (!cov) { q.flags &= ~(INFX_FQ_COV | INFX_FQ_WMDEV); q.wm_count = 0; }
+        if (!qo_cov(S, i, cov)) { q.flags &= ~(INFX_FQ_COV | INFX_FQ_WMDEV); q.wm_count = 0; }
     }
     out = B.pre;
     return INFX_OK;
@@ -1112,10 +1156,22 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     return INFX_OK;
 }
 
+static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
+                                int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
+                                uint32_t* out_counts, uint32_t* out_flags);
+// a search call on a session: per-query options installed on it apply to this batch (and are cleared after it, whatever its outcome)
 static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
                                  int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                  uint32_t* out_counts, uint32_t* out_flags) {
-    if (!e || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
+    if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
+    { int32_t rc = query_options_check(S, nq, max_results); if (rc) return rc; }
+    int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
+    const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
+    return rc ? rc : rc2;
+}
+static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
+                                int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
+                                uint32_t* out_counts, uint32_t* out_flags) {
     if (!e->indexed) { for (uint32_t i = 0; i < nq; i++) out_counts[i] = 0; return INFX_OK; }   // Result.MakeEmptyResult(), SearchEngine.cs:261-262
     if (e->nranks > 1) return efail(INFX_EINVAL, "sharded engine: drive the phase API (infx_session_phase1..4) with the collectives in between");
     static const bool phased = getenv("INFX_PHASED") != nullptr;     // host-driven phases (the sharded code path) on one GPU
@@ -1166,6 +1222,9 @@ int32_t infx_session_phase0(infx_session* S, uint32_t nq, const uint16_t* q_aren
     if (!S) return efail(INFX_EINVAL, "null session");
     // the exact cut across shards falls back to a chained sequential replay whose exchanged state is laid out for max_depth entries (infx_shard_replay_chain)
     if (S->e && S->e->nranks > 1 && depth != S->e->ix.cfg.maxDepth) return efail(INFX_EINVAL, "document shards search with CoverageDepth == the engine's max_depth");
+    if (S->qo.on && S->qo.bound) clear_query_options(S);        // left by a sharded batch that failed between its phase 0 and phase 4
+    { int32_t rc = query_options_check(S, nq, 0); if (rc) return rc; }
+    S->qo.bound = S->qo.on;
     PlanGateHold hold(S->e->gate);
     int32_t rc = ph_plan(S->e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     if (nunions) *nunions = (uint32_t)S->batch->pending.size();
@@ -1637,6 +1696,7 @@ int32_t infx_session_coll_stats(infx_session* S, uint64_t* out4) {      // all-r
 }
 int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits, const uint32_t* all_counts, int32_t max_results, int32_t enable_coverage, uint64_t* ncand) {
     if (!S || W < 1 || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (rc) return rc; }
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
     if (hostPhases) {
         int32_t rc = ph_stage2(S->e, S, W, all_hits, all_counts, max_results, enable_coverage); if (rc) return rc;
@@ -1680,6 +1740,7 @@ int32_t infx_session_phase2x(infx_session* S, const uint32_t* global_counts, voi
 }
 int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, const void* all_counts, int32_t max_results, int32_t enable_coverage, void* outs) {
     if (!S || W < 1 || max_results < 1 || !outs) return efail(INFX_EINVAL, "bad arguments");
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (rc) return rc; }
     infx_engine* e = S->e; Batch& B = *S->batch;
     B.maxResults = max_results;
     std::shared_ptr<FusedIn> FIp; int32_t rc = fused_inputs_for_phase3(e, S, max_results, enable_coverage, FIp); if (rc) return rc;
@@ -1704,11 +1765,16 @@ int32_t infx_session_outs(infx_session* S, int32_t* outs3) {   // ncand x 3 int3
 int32_t infx_session_phase4(infx_session* S, const int32_t* merged_outs3, int64_t* out_keys, float* out_scores, uint8_t* out_ties, uint32_t* out_counts, uint32_t* out_flags) {
     if (!S || !merged_outs3 || !out_keys || !out_scores || !out_counts) return efail(INFX_EINVAL, "null");
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    if (hostPhases) return ph_finalize(S->e, S, (const infx_cov_out*)merged_outs3, out_keys, out_scores, out_ties, out_counts, out_flags);
+    if (hostPhases) {
+        int32_t rc = ph_finalize(S->e, S, (const infx_cov_out*)merged_outs3, out_keys, out_scores, out_ties, out_counts, out_flags);
+        const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK);
+        return rc ? rc : rc2;
+    }
     Batch& B = *S->batch;
     if (B.nq) {
         int32_t rc = infx_shard_finalize(S->stream, B.nq, (const infx_cov_out*)merged_outs3, B.depth, B.maxResults, out_keys, out_scores, out_ties, out_counts, out_flags);
-        if (rc) { g_eerr = infx_last_error(); return rc; }
+        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); return rc; }
+        rc = query_options_finish(S, out_counts, out_flags, true); if (rc) return rc;
         float ms5[5] = {0, 0, 0, 0, 0}; infx_last_fused_timings(S->stream, ms5); S->msFin = ms5[4];
     }
     double t5 = now_ms();
@@ -2171,29 +2237,45 @@ int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, cha
     if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
     return (int32_t)t.size();
 }
-// The compiled device program of an Infiscript expression, from the engine's cache (compiled on first use).  Caller holds e->filterMu.
-static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter** out) {
+// The compiled program of an Infiscript expression, from the engine's cache (parsed on first use; its device copy made on the first use that needs it:
+// dev = true).  Caller holds e->filterMu.  Marks the entry most recently used; may evict others.
+static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter** out, bool dev) {
     auto it = e->filters.find(expr);
     if (it == e->filters.end()) {
         filt::Program P;
         try { P = filt::parse(expr); }
         catch (const filt::Unsupported& x) { return efail(INFX_EUNSUPPORTED, x.what()); }
         catch (const filt::SyntaxError& x) { return efail(INFX_EINVAL, std::string("filter syntax error: ") + x.what()); }
-        std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables, w;
-        for (auto& in : P.code) ops.push_back(infx_filter_op{in.op, in.arg});
+        CompiledFilter cf; std::vector<uint32_t> w;
+        for (auto& in : P.code) cf.ops.push_back(infx_filter_op{in.op, in.arg});
         for (auto& L : P.leaves) {
             int ci = -1; for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == L.field) ci = (int)c;      // field names are case sensitive (Dictionary<string, Field>)
             filt::leaf_table(L, ci >= 0 ? &e->columns[ci] : nullptr, w);
-            leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
-            tables.insert(tables.end(), w.begin(), w.end());
+            cf.leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)cf.tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
+            cf.tables.insert(cf.tables.end(), w.begin(), w.end());
         }
-        CompiledFilter cf;
-        int32_t rc = infx_filter_create(e->dev, (uint32_t)ops.size(), ops.data(), (uint32_t)leaves.size(), leaves.data(), (uint32_t)tables.size(), tables.data(), &cf.dev);
+        e->filterLru.push_front(expr);
+        it = e->filters.emplace(expr, std::move(cf)).first;
+        it->second.lru = e->filterLru.begin();
+        it->second.pins++;                // (held while the cache makes room)
+        e->evict_filters();
+        it->second.pins--;
+    } else e->filterLru.splice(e->filterLru.begin(), e->filterLru, it->second.lru);
+    CompiledFilter& cf = it->second;
+    if (dev && !cf.dev) {
+        int32_t rc = infx_filter_create(e->dev, (uint32_t)cf.ops.size(), cf.ops.data(), (uint32_t)cf.leaves.size(), cf.leaves.data(), (uint32_t)cf.tables.size(), cf.tables.data(), &cf.dev);
         if (rc) { g_eerr = infx_last_error(); return rc; }
-        it = e->filters.emplace(expr, cf).first;
     }
-    *out = &it->second;
+    *out = &cf;
     return INFX_OK;
+}
+static bool engine_sharded(const infx_engine* e) { return e->nranks > 1; }
+// pins / unpins cache entries by expression (an entry evicted meanwhile — after retire_filters — is simply gone).  Caller holds e->filterMu.
+static void pin_filters(infx_engine* e, const std::vector<std::string>& keys, int d) {
+    for (auto& k : keys) { auto it = e->filters.find(k); if (it != e->filters.end()) it->second.pins = (uint32_t)std::max<int64_t>(0, (int64_t)it->second.pins + d); }
+}
+static void set_session_pins(infx_session* S, std::vector<std::string>& slot, std::vector<std::string> keys) {      // caller holds e->filterMu
+    pin_filters(S->e, keys, +1); pin_filters(S->e, slot, -1); slot = std::move(keys); S->e->evict_filters();
 }
 // Installs Query.Filter (expr, UTF-8; NULL = none) and Query.EnableFacets on the session: every following search on it post-filters its rows
 // on the device and counts the facetable fields.  n_in_filter = Filter.NumberOfDocumentsInFilter (this shard's share when sharded),
@@ -2203,22 +2285,31 @@ int32_t infx_engine_set_filter(infx_session* S, const char* expr, int32_t enable
     if (!S) return efail(INFX_EINVAL, "null session");
     infx_engine* e = S->e;
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the post-filter runs on the device");
+    if (S->qo.on && (expr || enable_facets)) return efail(INFX_EINVAL, "per-query options are installed on this session: a session-wide filter would conflict");
+    if (S->qo.on) { if (n_in_filter) *n_in_filter = 0; return INFX_OK; }      // nothing session-wide is installed: clearing changes nothing (the batch's facet columns stay)
     infx_filter* dev = nullptr; uint32_t cnt = 0;
-    if (expr) {
+    std::vector<std::string> keep;
+    {
         std::lock_guard<std::mutex> lk(e->filterMu);
-        CompiledFilter* cf = nullptr;
-        { int32_t rc = compile_filter(e, expr, &cf); if (rc) return rc; }
-        if (!cf->counted) {       // ResultProcessor.cs:39-54: first use runs the filter over every document
-            int32_t rc = infx_filter_count(S->stream, cf->dev, &cf->inFilter);
-            if (rc) { g_eerr = infx_last_error(); return rc; }
-            cf->counted = true;
+        if (expr) {
+            CompiledFilter* cf = nullptr;
+            { int32_t rc = compile_filter(e, expr, &cf, true); if (rc) return rc; }
+            if (!cf->counted) {       // ResultProcessor.cs:39-54: first use runs the filter over every document
+                int32_t rc = infx_filter_count(S->stream, cf->dev, &cf->inFilter);
+                if (rc) { g_eerr = infx_last_error(); return rc; }
+                cf->counted = true;
+                if (!engine_sharded(e)) { cf->inAll = cf->inFilter; cf->countedAll = true; }
+            }
+            dev = cf->dev; cnt = cf->inFilter;
+            keep.push_back(expr);
         }
-        dev = cf->dev; cnt = cf->inFilter;
     }
     S->facetCols.clear();
     if (enable_facets) for (size_t c = 0; c < e->columns.size() && S->facetCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) S->facetCols.push_back((uint32_t)c);
     int32_t rc = infx_stream_set_postfilter(S->stream, dev, (uint32_t)S->facetCols.size(), S->facetCols.data());
     if (rc) { g_eerr = infx_last_error(); return rc; }
+    S->swFilter = expr != nullptr || enable_facets;
+    { std::lock_guard<std::mutex> lk(e->filterMu); set_session_pins(S, S->swPinFilter, keep); }
     if (n_in_filter) *n_in_filter = cnt;
     return INFX_OK;
 }
@@ -2246,7 +2337,8 @@ int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* e
     if (!S || (enable && n && (!exprs || !strengths))) return efail(INFX_EINVAL, "bad boost arguments");
     infx_engine* e = S->e;
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: boosts run on the device");
-    std::vector<infx_filter*> devs; std::vector<int32_t> st;
+    std::vector<infx_filter*> devs; std::vector<int32_t> st; std::vector<std::string> keep;
+    if (S->qo.on && enable && n) return efail(INFX_EINVAL, "per-query options are installed on this session: session-wide boosts would conflict");
     if (enable) {       // SearchEngine.cs:355: only with EnableBoost; a Boost whose Filter is null is dropped (ResultProcessor.cs:84-85)
         uint32_t withFilter = 0;
         for (uint32_t i = 0; i < n; i++) withFilter += exprs[i] != nullptr;
@@ -2255,36 +2347,202 @@ int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* e
         for (uint32_t i = 0; i < n; i++) {
             if (!exprs[i]) continue;
             CompiledFilter* cf = nullptr;
-            int32_t rc = compile_filter(e, exprs[i], &cf);      // ApplyBoosts never counts NumberOfDocumentsInFilter
+            int32_t rc = compile_filter(e, exprs[i], &cf, true);      // ApplyBoosts never counts NumberOfDocumentsInFilter
             if (rc) return rc;
-            devs.push_back(cf->dev); st.push_back(strengths[i]);
+            devs.push_back(cf->dev); st.push_back(strengths[i]); keep.push_back(exprs[i]);
         }
     }
     int32_t rc = infx_stream_set_boosts(S->stream, (uint32_t)devs.size(), devs.data(), st.data());
     if (rc) { g_eerr = infx_last_error(); return rc; }
+    S->swBoost = !devs.empty();
+    { std::lock_guard<std::mutex> lk(e->filterMu); set_session_pins(S, S->swPinBoosts, keep); }
+    return INFX_OK;
+}
+// the column of a SortBy field (0xFFFFFFFF: no such field); the first use of a column builds and uploads its sort rank.  Caller holds e->filterMu.
+static int32_t sort_column(infx_engine* e, const char* field, uint32_t* out) {
+    uint32_t col = 0xFFFFFFFFu;
+    for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == field) col = (uint32_t)c;      // case sensitive, as the filter's fields
+    if (col != 0xFFFFFFFFu) {
+        if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
+        if (!e->sortRanked[col]) {
+            std::vector<uint32_t> rank; filt::sort_rank(e->columns[col], rank);
+            int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
+            if (rc) { g_eerr = infx_last_error(); return rc; }
+            e->sortRanked[col] = 1;
+        }
+    }
+    *out = col;
     return INFX_OK;
 }
 int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascending) {
     if (!S) return efail(INFX_EINVAL, "null session");
     infx_engine* e = S->e;
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: sort-by runs on the device");
+    if (S->qo.on && field) return efail(INFX_EINVAL, "per-query options are installed on this session: a session-wide sort would conflict");
     uint32_t col = 0xFFFFFFFFu;
     if (field) {
         std::lock_guard<std::mutex> lk(e->filterMu);
-        for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == field) col = (uint32_t)c;      // case sensitive, as the filter's fields
-        if (col != 0xFFFFFFFFu) {
-            if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
-            if (!e->sortRanked[col]) {
-                std::vector<uint32_t> rank; filt::sort_rank(e->columns[col], rank);
-                int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
-                if (rc) { g_eerr = infx_last_error(); return rc; }
-                e->sortRanked[col] = 1;
-            }
-        }
+        int32_t rc = sort_column(e, field, &col); if (rc) return rc;
     }
     int32_t rc = infx_stream_set_sort(S->stream, col, ascending, field != nullptr);
     if (rc) { g_eerr = infx_last_error(); return rc; }
+    S->swSort = field != nullptr;
     return INFX_OK;
 }
+
+// ---- per-query options (Search(Query) for a batch of Query objects, each with its own options) ---------------------------------------------------
+static infx_filter_prog prog_of(const CompiledFilter& cf) {
+    infx_filter_prog P{};
+    P.ops = cf.ops.data(); P.leaves = cf.leaves.data(); P.tables = cf.tables.data();
+    P.nops = (uint32_t)cf.ops.size(); P.nleaves = (uint32_t)cf.leaves.size(); P.ntable_words = (uint32_t)cf.tables.size();
+    return P;
+}
+static void clear_query_options(infx_session* S) {
+    if (!S->qo.on) return;
+    { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, S->qo.pinned, -1); S->e->evict_filters(); }
+    if (S->stream) infx_stream_set_query_post(S->stream, 0, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr);
+    S->qo = QueryOpts();
+}
+int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_query_options* opts, int32_t* out_status) {
+    if (!S || (nq && !opts)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    clear_query_options(S);
+    if (nq == 0) return INFX_OK;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the per-query options run on the device");
+    if (S->swFilter || S->swBoost || S->swSort) return efail(INFX_EINVAL, "a session-wide filter, facets, boosts or sort is installed on this session: per-query options would conflict");
+    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
+    QueryOpts Q; Q.nq = nq;
+    Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string()); Q.filterExpr.assign(nq, std::string());
+    std::vector<infx_query_post> post(nq); std::vector<infx_query_boost> boosts;
+    std::vector<const CompiledFilter*> progs; std::unordered_map<std::string, int32_t> progIdx;
+    std::vector<uint32_t> facetCols;
+    for (size_t c = 0; c < e->columns.size() && facetCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) facetCols.push_back((uint32_t)c);
+    bool anyFacets = false;
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    // per query: compile what it uses (a failure rejects that query alone); the table's programs to count come first
+    struct QUse { std::string filter; std::vector<std::pair<std::string, int32_t>> boosts; uint32_t sortCol = 0xFFFFFFFFu; bool sort = false; };
+    std::vector<QUse> use(nq);
+    std::vector<std::string> toCount; std::unordered_set<std::string> toCountSet, all;
+    auto hold = [&](const char* x) { if (all.insert(x).second) { Q.pinned.push_back(x); pin_filters(e, {std::string(x)}, +1); } };      // pinned as compiled: a small cache bound cannot evict the batch's own
+    for (uint32_t i = 0; i < nq; i++) {
+        const infx_query_options& O = opts[i]; QUse& U = use[i];
+        auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
+        Q.maxResults[i] = O.max_results; Q.cov[i] = O.enable_coverage ? 1 : 0;
+        if (O.max_results < 1) { reject(INFX_EINVAL, "MaxNumberOfRecordsToReturn must be at least 1"); continue; }
+        int32_t rc = INFX_OK;
+        if (O.filter) { CompiledFilter* cf = nullptr; rc = compile_filter(e, O.filter, &cf, false); if (!rc) { U.filter = O.filter; hold(O.filter); } }
+        if (!rc && O.enable_boost && O.nboosts) {
+            uint32_t withFilter = 0;
+            for (uint32_t b = 0; b < O.nboosts; b++) withFilter += O.boost_filters && O.boost_filters[b] != nullptr;
+            if (!O.boost_filters || !O.boost_strengths) rc = efail(INFX_EINVAL, "bad boost arguments");
+            else if (withFilter > INFX_MAX_BOOSTS) rc = efail(INFX_ECAPACITY, "more than INFX_MAX_BOOSTS (8) boosts with a filter");
+            for (uint32_t b = 0; !rc && b < O.nboosts; b++) {
+                if (!O.boost_filters[b]) continue;          // a Boost whose Filter is null is dropped (ResultProcessor.cs:84-85)
+                CompiledFilter* cf = nullptr; rc = compile_filter(e, O.boost_filters[b], &cf, false);
+                if (!rc) { U.boosts.push_back({O.boost_filters[b], O.boost_strengths[b]}); hold(O.boost_filters[b]); }
+            }
+        }
+        if (!rc && O.sort_by) { U.sort = true; rc = sort_column(e, O.sort_by, &U.sortCol); }
+        if (rc) { reject(rc, g_eerr); U = QUse(); continue; }
+        const bool pp = O.filter || (O.enable_facets && !facetCols.empty()) || !U.boosts.empty() || U.sort;      // (facets without a facetable field: {} as the session path)
+        if (pp && hostPhases) { reject(INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run in the device finalize: the host phases (INFX_PHASED) do not post-process rows"); U = QUse(); continue; }
+        if (pp && O.max_results > INFX_FILTER_MAX_ROWS) { reject(INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run on at most INFX_FILTER_MAX_ROWS (64) returned rows per query"); U = QUse(); continue; }
+        if (O.enable_facets && !facetCols.empty()) anyFacets = true;
+        if (!U.filter.empty()) {
+            Q.filterExpr[i] = U.filter;
+            const CompiledFilter& cf = e->filters.at(U.filter);
+            if (!cf.countedAll && toCountSet.insert(U.filter).second) toCount.push_back(U.filter);      // ResultProcessor.cs:39-54: first use counts
+        }
+    }
+    // the program table: the expressions to count, then every other one the batch uses; each entry pinned until the batch is done
+    for (auto& x : toCount) { progIdx[x] = (int32_t)progs.size(); progs.push_back(&e->filters.at(x)); }
+    for (auto& x : Q.pinned) if (!progIdx.count(x)) { progIdx[x] = (int32_t)progs.size(); progs.push_back(&e->filters.at(x)); }
+    for (uint32_t i = 0; i < nq; i++) {
+        const QUse& U = use[i]; infx_query_post& D = post[i];
+        D = infx_query_post{}; D.filter = U.filter.empty() ? -1 : progIdx.at(U.filter);
+        if (!Q.reject[i] && opts[i].enable_facets && anyFacets) D.flags |= INFX_QP_FACETS;
+        D.boost_off = (uint32_t)boosts.size(); D.nboost = (uint32_t)U.boosts.size();
+        for (auto& b : U.boosts) boosts.push_back(infx_query_boost{progIdx.at(b.first), b.second});
+        if (U.sort) { D.flags |= INFX_QP_SORT | (opts[i].sort_ascending ? INFX_QP_ASC : 0u); D.sort_col = U.sortCol; }
+    }
+    std::vector<infx_filter_prog> P(progs.size());
+    for (size_t k = 0; k < progs.size(); k++) P[k] = prog_of(*progs[k]);
+    Q.countExprs = toCount; Q.counts.assign(toCount.size(), 0u);
+    if (!anyFacets) facetCols.clear();
+    int32_t rc = infx_stream_set_query_post(S->stream, nq, (uint32_t)P.size(), P.data(), (uint32_t)boosts.size(), boosts.data(), post.data(),
+                                            (uint32_t)facetCols.size(), facetCols.data(), (uint32_t)toCount.size(), Q.counts.data());
+    if (rc) { g_eerr = infx_last_error(); pin_filters(e, Q.pinned, -1); return rc; }
+    S->facetCols = facetCols;
+    S->lastErr = Q.err;
+    Q.on = true;
+    S->qo = std::move(Q);
+    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = S->qo.status[i];
+    return INFX_OK;
+}
+// A batch is about to run on the session: the per-query options installed must be for nq queries whose max_results fit the call's row stride
+static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results) {
+    if (!S->qo.on) return INFX_OK;
+    if (nq != S->qo.nq) { clear_query_options(S); return efail(INFX_EINVAL, "the per-query options were installed for a batch of another size"); }
+    if (max_results > 0) for (uint32_t i = 0; i < nq; i++) if (!S->qo.reject[i] && S->qo.maxResults[i] > max_results) {
+        clear_query_options(S); return efail(INFX_EINVAL, "a query's max_results exceeds the call's (the row stride)");
+    }
+    return INFX_OK;
+}
+// The batch is done: rejected queries come back empty with result flag bit 4, the expressions it counted enter the cache, the options are cleared
+static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
+    if (!S->qo.on) return INFX_OK;
+    infx_engine* e = S->e; QueryOpts& Q = S->qo; const uint32_t nq = Q.nq;
+    int32_t rc = INFX_OK;
+    S->lastInFilter.assign(nq, 0); S->lastErr = Q.err; S->lastCounted = 0; S->lastCountLaunches = 0;
+    if (ok) {
+        // The counts come from the batch's own finalize: infx_stream_set_query_post resets the stream's count stats and only the finalize that consumes
+        // the options sets them.  (The host phases refuse every query with a filter, so such a batch counts nothing.)
+        uint32_t counted = 0, launches = 0;
+        infx_last_filter_count_stats(S->stream, &counted, &launches);
+        if (counted != Q.countExprs.size()) rc = efail(INFX_EINVAL, "the batch's NumberOfDocumentsInFilter counts did not come back with it");
+        if (!rc) {
+            S->lastCounted = counted; S->lastCountLaunches = launches;
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t k = 0; k < Q.countExprs.size(); k++) {
+                auto it = e->filters.find(Q.countExprs[k]);
+                if (it == e->filters.end()) continue;
+                it->second.inAll = Q.counts[k]; it->second.countedAll = true;
+                if (!engine_sharded(e)) { it->second.inFilter = Q.counts[k]; it->second.counted = true; }
+            }
+            for (uint32_t i = 0; i < nq; i++) if (!Q.filterExpr[i].empty() && !Q.reject[i]) {
+                auto it = e->filters.find(Q.filterExpr[i]);
+                if (it != e->filters.end() && it->second.countedAll) S->lastInFilter[i] = it->second.inAll;
+            }
+        }
+        for (uint32_t i = 0; i < nq; i++) if (Q.reject[i]) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
+    }
+    clear_query_options(S);
+    return rc;
+}
+int32_t infx_engine_last_in_filter(infx_session* S, uint32_t nq, uint32_t* out) {
+    if (!S || (nq && !out)) return efail(INFX_EINVAL, "null argument");
+    if (nq != S->lastInFilter.size()) return efail(INFX_EINVAL, "no per-query batch of this size on the session");
+    std::memcpy(out, S->lastInFilter.data(), (size_t)nq * 4);
+    return INFX_OK;
+}
+int32_t infx_engine_last_count_stats(infx_session* S, uint32_t* counted, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (counted) *counted = S->lastCounted;
+    if (launches) *launches = S->lastCountLaunches;
+    return INFX_OK;
+}
+int32_t infx_engine_query_error(infx_session* S, uint32_t qi, char* out, int32_t cap) {
+    if (!S || qi >= S->lastErr.size()) return -1;
+    const std::string& t = S->lastErr[qi];
+    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
+    return (int32_t)t.size();
+}
+int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {
+    if (!e || limit < 1) return efail(INFX_EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    e->filterCacheLimit = (size_t)limit; e->evict_filters();
+    return INFX_OK;
+}
+int64_t infx_engine_filter_cache_size(infx_engine* e) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->filterMu); return (int64_t)e->filters.size(); }
 
 } // extern "C"

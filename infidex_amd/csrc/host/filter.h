@@ -9,7 +9,7 @@
 //   * an expression is parsed into a postfix boolean program over LEAVES (field <op> constants).  A leaf depends on one field only, so it
 //     is evaluated here, once per DISTINCT value, with the reference's coercion rules (FilterVM.AreEqual / CompareTo: case-insensitive
 //     ToString() equality; numeric order when both sides parse as doubles, else case-insensitive string order) — the result is a bitmap
-//     over the column's codes.  The device evaluates program + bitmaps per document (k_filter_count over all documents, k_postfilter over
+//     over the column's codes.  The device evaluates program + bitmaps per document (k_filter_count_multi over all documents, k_postfilter over
 //     the returned rows), so arbitrary string / number coercions cost nothing there.
 //   * the reference's VM is untyped: AND / OR / ?: pass non-boolean operands through (a literal in a ternary branch).  The program keeps
 //     that as a three-valued logic: F, T, N (not a bool): AND(l,r) = l==F ? F : r; OR(l,r) = l==T ? T : r; NOT(x) = x==T ? F : T;

@@ -242,6 +242,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 // ---------------------------------------------------------------------------------------------------------------
 struct infx_filter {
     infx_index* ix; DevFilter d{}; uint32_t nops = 0, nleaves = 0; void *dOps = nullptr, *dLeaves = nullptr, *dTables = nullptr;
+    std::vector<infx_filter_leaf> hLeaves;      // host copy of the leaves: the columns k_filter_count_multi loads for it
 };
 
 struct infx_stream {
@@ -250,11 +251,18 @@ struct infx_stream {
     infx_filter* postFilter = nullptr; uint32_t nFacet = 0; uint32_t facetCols[INFX_MAX_FACET_COLS] = {};
     void *dFDocs = nullptr, *dFacetCols = nullptr, *dFacCodes = nullptr, *dFacCounts = nullptr, *dFacN = nullptr;
     size_t capFDocs = 0, capFacCodes = 0, capFacCounts = 0, capFacN = 0;
-    std::vector<uint32_t> hFacCodes, hFacCounts, hFacN; uint32_t facetNq = 0;
+    std::vector<uint32_t> hFacCodes, hFacCounts, hFacN; uint32_t facetNq = 0, facetNFacet = 0;     // facets of the last batch: nq, facet columns
     // boosts / sort-by (infx_stream_set_boosts / _set_sort): applied after the post-filter (k_postproc)
     infx_filter* boosts[INFX_MAX_BOOSTS] = {}; int32_t boostStrength[INFX_MAX_BOOSTS] = {}; uint32_t nBoost = 0;
     uint32_t sortCol = 0; bool sortOn = false, sortAsc = false;
-    void* dPostProc = nullptr;     // the DevPostProc of k_postproc, staged on the stream by each finalize that launches it
+    // per-query post-processing of the NEXT batch (infx_stream_set_query_post), consumed by its finalize: the batch's programs packed into one blob
+    // (opsOff / leavesOff / tablesOff: byte offsets into qpCode), the boost list, one descriptor per query, the programs [0, qpNCount) to count
+    struct QpProg { uint32_t nops, nleaves, opsOff, leavesOff, tablesOff; };
+    bool qpOn = false; uint32_t qpNq = 0, qpNFacet = 0, qpFacetCols[INFX_MAX_FACET_COLS] = {}, qpNCount = 0; uint32_t* qpCountsOut = nullptr;
+    std::vector<QpProg> qpProgs; std::vector<uint8_t> qpCode; std::vector<DevQBoost> qpBoosts; std::vector<DevQPost> qpDesc; DevCountCols qpCols{};
+    uint32_t lastCountK = 0, lastCountLaunches = 0;     // the filter programs the last finalize counted, and its k_filter_count_multi launches
+    void* dPostBlob = nullptr; size_t capPostBlob = 0;     // the batch's DevPostBatch + program table + boost list + descriptors (+ packed programs)
+    void* dQCount = nullptr; size_t capQCount = 0;
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1080,7 +1088,7 @@ void infx_stream_destroy(infx_stream* s) {
     hipSetDevice(s->ix->cfg.device);
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
-                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostProc, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
+                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
                   s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder};
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -1691,6 +1699,41 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     return INFX_OK;
 }
 
+// k_filter_count_multi over documents [docBase, docBase + n): counts[k] = the documents programs dProgs[k] accept, K programs in
+// ceil(K / FCM_MAXK) launches (FCM_MAXK bounds the per-workgroup LDS counters)
+#define FCM_MAXK 4096u
+#define FCM_MAXGRID 2048
+static int32_t count_enqueue(infx_stream* s, const DevFilter* dProgs, uint32_t K, const DevCountCols& cc, int32_t docBase, int32_t n, uint32_t* dCounts) {
+    infx_index* ix = s->ix;
+    for (int c = 0; c < FILT_MAXCOL; c++)       // columns are indexed by GLOBAL internal id: every uploaded column must cover the counted range
+        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)docBase + (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the counted documents%s");
+    HIPCHK(hipMemsetAsync(dCounts, 0, (size_t)K * 4, s->st));
+    s->lastCountK = K; s->lastCountLaunches = 0;
+    if (n <= 0 || !K) return INFX_OK;
+    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+    const int grid = (int)std::min<int64_t>(FCM_MAXGRID, ((int64_t)n + FCM_THREADS - 1) / FCM_THREADS);
+    for (uint32_t k0 = 0; k0 < K; k0 += FCM_MAXK) {
+        const uint32_t k = std::min(FCM_MAXK, K - k0);
+        const size_t lds = ((size_t)k + (size_t)cc.nUsed * FCM_THREADS) * 4;
+        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_filter_count_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        k_filter_count_multi<<<grid, FCM_THREADS, lds, s->st>>>(dProgs + k0, k, cc, cols, docBase, n, ix->d.deleted, dCounts + k0);
+        HIPCHK(hipGetLastError());
+        s->lastCountLaunches++;
+    }
+    return INFX_OK;
+}
+// the columns programs [0, k) read, each once (k_filter_count_multi loads a document's codes of these columns once for all k programs)
+static DevCountCols count_columns(const infx_filter_leaf* const* leaves, const uint32_t* nleaves, uint32_t k) {
+    DevCountCols cc{};
+    for (int c = 0; c < FILT_MAXCOL; c++) cc.slot[c] = 0;
+    bool seen[FILT_MAXCOL] = {};
+    for (uint32_t p = 0; p < k; p++) for (uint32_t l = 0; l < nleaves[p]; l++) {
+        const uint32_t c = leaves[p][l].col;
+        if (c < FILT_MAXCOL && !seen[c]) { seen[c] = true; cc.slot[c] = (uint8_t)cc.nUsed; cc.col[cc.nUsed++] = c; }
+    }
+    return cc;
+}
+
 // k_finalize over s->dCovC / s->dCovO / s->dFMeta / s->dFS1 -> result rows in s->dFKeys ...
 static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth, int32_t max_results, bool ties) {
     infx_index* ix = s->ix;
@@ -1702,47 +1745,89 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     GROW(s->dFFlags, s->capFFlags, (size_t)nq * 4);
     GROW(s->dFErr, s->capFErr, 4);
     HIPCHK(hipMemsetAsync(s->dFErr, 0, 4, s->st));
-    HIPCHK(hipEventRecord(s->evF0, s->st));
     const size_t lds = (size_t)Cp * (8 + 4 + 4 + 2 + 1 + 1) + (P2_THREADS + 1) * 4 + 64;
-    const bool post = s->postFilter != nullptr || s->nFacet > 0;
+    // Post-processing of the rows: the per-query options of this batch (infx_stream_set_query_post, consumed here) or the session-wide post-filter /
+    // facets / boosts / sort, staged as one descriptor that every query shares.  Nothing is staged or launched for a batch without either.
+    const bool qp = s->qpOn;
+    s->qpOn = false; s->lastCountK = 0; s->lastCountLaunches = 0;
+    if (qp && s->qpNq != nq) return fail(INFX_EINVAL, "the per-query options were installed for a batch of another size%s");
+    const bool post = !qp && (s->postFilter != nullptr || s->nFacet > 0);
     if (post && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "post-filter / facets run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
-    const bool pp = s->nBoost > 0 || s->sortOn;         // boosts / sort-by: k_postproc after k_postfilter
+    const bool pp = !qp && (s->nBoost > 0 || s->sortOn);         // boosts / sort-by: k_postproc after k_postfilter
     if (pp && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "boosts / sort-by run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
-    const bool sortKnown = s->sortOn && s->sortCol != 0xFFFFFFFFu;
+    const bool sortKnown = !qp && s->sortOn && s->sortCol != 0xFFFFFFFFu;
     if (sortKnown && (s->sortCol >= FILT_MAXCOL || !ix->colCodes[s->sortCol] || !ix->colRankOk[s->sortCol])) return fail(INFX_EINVAL, "the sort column's rank is not uploaded%s");
-    if (post || pp) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
+    bool launchPF = post, launchPP = pp;
+    if (qp) for (const DevQPost& D : s->qpDesc) {
+        launchPF |= D.filter >= 0 || (D.flags & QP_FACETS); launchPP |= D.nboost > 0 || (D.flags & QP_SORT);
+        if ((D.flags & QP_SORT) && D.sortCol != 0xFFFFFFFFu && (D.sortCol >= FILT_MAXCOL || !ix->colCodes[D.sortCol] || !ix->colRankOk[D.sortCol]))
+            return fail(INFX_EINVAL, "the sort column's rank is not uploaded%s");
+    }
+    const uint32_t nfacet = qp ? s->qpNFacet : s->nFacet; const uint32_t* facetCols = qp ? s->qpFacetCols : s->facetCols;
+    const uint32_t ncount = qp ? s->qpNCount : 0;
+    if (launchPF || launchPP) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
+    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+    const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr;
+    if (launchPF || launchPP || ncount) {       // the batch's DevPostBatch, program table, boost list and descriptors (+ the packed per-query programs): one upload
+        std::vector<DevFilter> progs; std::vector<DevQBoost> sboost; std::vector<DevQPost> sdesc;
+        if (!qp) {
+            DevQPost D{}; D.filter = -1; D.sortCol = 0;
+            if (s->postFilter) { D.filter = (int32_t)progs.size(); progs.push_back(s->postFilter->d); }
+            if (s->nFacet) D.flags |= QP_FACETS;
+            D.boostOff = 0; D.nboost = s->nBoost;
+            for (uint32_t b = 0; b < s->nBoost; b++) { sboost.push_back(DevQBoost{(int32_t)progs.size(), s->boostStrength[b]}); progs.push_back(s->boosts[b]->d); }
+            if (s->sortOn) { D.flags |= QP_SORT | (s->sortAsc ? QP_ASC : 0u); D.sortCol = s->sortCol; }
+            sdesc.push_back(D);
+        }
+        const std::vector<DevQBoost>& boosts = qp ? s->qpBoosts : sboost; const std::vector<DevQPost>& desc = qp ? s->qpDesc : sdesc;
+        const size_t nprog = qp ? s->qpProgs.size() : progs.size();
+        auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        const size_t oProgs = al(sizeof(DevPostBatch)), oBoosts = al(oProgs + nprog * sizeof(DevFilter)), oDesc = al(oBoosts + boosts.size() * sizeof(DevQBoost));
+        const size_t oCode = al(oDesc + desc.size() * sizeof(DevQPost)), total = oCode + (qp ? s->qpCode.size() : 0);
+        GROW(s->dPostBlob, s->capPostBlob, total);
+        char* D = (char*)s->dPostBlob;
+        if (qp) for (const auto& P : s->qpProgs)
+            progs.push_back(DevFilter{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)});
+        DevPostBatch pb{};
+        pb.progs = (const DevFilter*)(D + oProgs); pb.boosts = (const DevQBoost*)(D + oBoosts); pb.desc = (const DevQPost*)(D + oDesc); pb.descStride = qp ? 1u : 0u;
+        for (int c = 0; c < FILT_MAXCOL; c++) pb.rank[c] = ix->colRankOk[c] ? ix->colRank[c] : nullptr;
+        pb.keys = (long long*)s->dFKeys; pb.scores = (float*)s->dFScores; pb.ties = ties ? (uint8_t*)s->dFTies : nullptr; pb.docs = (int32_t*)s->dFDocs;
+        pb.counts = (uint32_t*)s->dFCounts; pb.flags = (uint32_t*)s->dFFlags; pb.stride = max_results;
+        std::vector<uint8_t> H(total, 0);
+        std::memcpy(H.data(), &pb, sizeof pb);
+        if (nprog) std::memcpy(H.data() + oProgs, progs.data(), nprog * sizeof(DevFilter));
+        if (!boosts.empty()) std::memcpy(H.data() + oBoosts, boosts.data(), boosts.size() * sizeof(DevQBoost));
+        if (!desc.empty()) std::memcpy(H.data() + oDesc, desc.data(), desc.size() * sizeof(DevQPost));
+        if (qp && !s->qpCode.empty()) std::memcpy(H.data() + oCode, s->qpCode.data(), s->qpCode.size());
+        UP(D, H.data(), total);
+        dPB = (const DevPostBatch*)D; dProgs = (const DevFilter*)(D + oProgs);
+    }
+    if (ncount) {       // Filter.NumberOfDocumentsInFilter of the expressions this batch uses first, over the whole corpus (every shard holds the whole columns)
+        GROW(s->dQCount, s->capQCount, (size_t)ncount * 4);
+        { int32_t rc_ = count_enqueue(s, dProgs, ncount, s->qpCols, 0, ix->d.totalDocs, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+        DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
+    }
+    HIPCHK(hipEventRecord(s->evF0, s->st));
     k_finalize<<<nq, P2_THREADS, lds, s->st>>>(ix->d, (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
-                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, post || pp ? (int32_t*)s->dFDocs : nullptr);
+                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr);
     HIPCHK(hipGetLastError());
     s->facetNq = 0;
-    if (post) {     // ResultProcessor.ApplyFilter + FacetBuilder on the rows just produced, before they leave the device
-        const size_t fe = (size_t)nq * std::max<uint32_t>(1, s->nFacet) * INFX_FILTER_MAX_ROWS;
-        GROW(s->dFacCodes, s->capFacCodes, fe * 4); GROW(s->dFacCounts, s->capFacCounts, fe * 4); GROW(s->dFacN, s->capFacN, (size_t)nq * std::max<uint32_t>(1, s->nFacet) * 4);
+    if (launchPF) {     // ResultProcessor.ApplyFilter + FacetBuilder on the rows just produced, before they leave the device
+        const size_t fe = (size_t)nq * std::max<uint32_t>(1, nfacet) * INFX_FILTER_MAX_ROWS;
+        GROW(s->dFacCodes, s->capFacCodes, fe * 4); GROW(s->dFacCounts, s->capFacCounts, fe * 4); GROW(s->dFacN, s->capFacN, (size_t)nq * std::max<uint32_t>(1, nfacet) * 4);
         if (!s->dFacetCols) HIPCHK(hipMalloc(&s->dFacetCols, INFX_MAX_FACET_COLS * 4));
-        UP(s->dFacetCols, s->facetCols, INFX_MAX_FACET_COLS * 4);
-        DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
-        k_postfilter<<<nq, WAVE, 0, s->st>>>(s->postFilter ? s->postFilter->d : DevFilter{}, s->postFilter ? 1 : 0, cols, max_results, (long long*)s->dFKeys, (float*)s->dFScores,
-                                            ties ? (uint8_t*)s->dFTies : nullptr, (int32_t*)s->dFDocs, (uint32_t*)s->dFCounts, (int)s->nFacet, (const uint32_t*)s->dFacetCols,
-                                            (uint32_t*)s->dFacCodes, (uint32_t*)s->dFacCounts, (uint32_t*)s->dFacN);
+        UP(s->dFacetCols, facetCols, INFX_MAX_FACET_COLS * 4);
+        k_postfilter<<<nq, WAVE, 0, s->st>>>(dPB, cols, (int)nfacet, (const uint32_t*)s->dFacetCols, (uint32_t*)s->dFacCodes, (uint32_t*)s->dFacCounts, (uint32_t*)s->dFacN);
         HIPCHK(hipGetLastError());
-        if (s->nFacet) {
-            s->hFacCodes.resize(fe); s->hFacCounts.resize(fe); s->hFacN.resize((size_t)nq * s->nFacet); s->facetNq = nq;
-            DOWN(s->hFacCodes.data(), s->dFacCodes, fe * 4); DOWN(s->hFacCounts.data(), s->dFacCounts, fe * 4); DOWN(s->hFacN.data(), s->dFacN, (size_t)nq * s->nFacet * 4);
+        if (nfacet) {
+            s->hFacCodes.resize(fe); s->hFacCounts.resize(fe); s->hFacN.resize((size_t)nq * nfacet); s->facetNq = nq; s->facetNFacet = nfacet;
+            DOWN(s->hFacCodes.data(), s->dFacCodes, fe * 4); DOWN(s->hFacCounts.data(), s->dFacCounts, fe * 4); DOWN(s->hFacN.data(), s->dFacN, (size_t)nq * nfacet * 4);
         }
     }
-    if (pp) {       // ResultProcessor.ApplyBoosts + ApplySort on the kept rows (facets count rows, not their order: FacetBuilder's result is the same)
-        DevPostProc P{};
-        for (uint32_t b = 0; b < s->nBoost; b++) { P.boost[b] = s->boosts[b]->d; P.strength[b] = s->boostStrength[b]; }
-        P.nboost = s->nBoost;
-        P.rank = sortKnown ? ix->colRank[s->sortCol] : nullptr; P.sortCol = sortKnown ? s->sortCol : 0; P.sortOn = s->sortOn ? 1 : 0; P.ascending = s->sortAsc ? 1 : 0;
-        P.keys = (long long*)s->dFKeys; P.scores = (float*)s->dFScores; P.ties = ties ? (uint8_t*)s->dFTies : nullptr; P.docs = (int32_t*)s->dFDocs;
-        P.counts = (const uint32_t*)s->dFCounts; P.stride = max_results;
-        if (!s->dPostProc) HIPCHK(hipMalloc(&s->dPostProc, sizeof(DevPostProc)));
-        UP(s->dPostProc, &P, sizeof(P));
-        DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
-        k_postproc<<<nq, WAVE, 0, s->st>>>((const DevPostProc*)s->dPostProc, cols);
+    if (launchPP) {     // ResultProcessor.ApplyBoosts + ApplySort on the kept rows (facets count rows, not their order: FacetBuilder's result is the same)
+        k_postproc<<<nq, WAVE, 0, s->st>>>(dPB, cols);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(s->evF1, s->st));
@@ -2212,12 +2297,11 @@ int32_t infx_upload_column(infx_index* ix, uint32_t col, uint32_t total_docs, co
     ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false;
     return INFX_OK;
 }
-int32_t infx_filter_create(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
-                           uint32_t ntable_words, const uint32_t* tables, infx_filter** out) {
-    if (!ix || !out || !nops || !ops || (nleaves && (!leaves || !tables))) return fail(INFX_EINVAL, "null argument%s");
+// a program must be a well-formed postfix expression whose stack fits the kernels' 32 slots, over uploaded columns, with its leaf tables in range
+static int32_t check_filter_prog(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves, uint32_t ntable_words) {
     if (nops > INFX_FILTER_MAX_OPS) return fail(INFX_ECAPACITY, "filter program too long%s");
     int depth = 0, maxDepth = 0;
-    for (uint32_t i = 0; i < nops; i++) {          // the program must be a well-formed postfix expression whose stack fits the kernels' 32 slots
+    for (uint32_t i = 0; i < nops; i++) {
         const uint32_t o = ops[i].op;
         if (o == INFX_FOP_LEAF) { if (ops[i].arg >= nleaves) return fail(INFX_EINVAL, "filter leaf index out of range%s"); depth++; }
         else if (o == INFX_FOP_LIT) depth++;
@@ -2233,8 +2317,14 @@ int32_t infx_filter_create(infx_index* ix, uint32_t nops, const infx_filter_op* 
         if (L.col != 0xFFFFFFFFu && (L.col >= FILT_MAXCOL || !ix->colCodes[L.col])) return fail(INFX_EINVAL, "filter refers to a column that was not uploaded%s");
         if ((uint64_t)L.table_off + (L.num_values + 31) / 32 > ntable_words) return fail(INFX_EINVAL, "filter leaf table out of range%s");
     }
+    return INFX_OK;
+}
+int32_t infx_filter_create(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
+                           uint32_t ntable_words, const uint32_t* tables, infx_filter** out) {
+    if (!ix || !out || !nops || !ops || (nleaves && (!leaves || !tables))) return fail(INFX_EINVAL, "null argument%s");
+    { int32_t rc_ = check_filter_prog(ix, nops, ops, nleaves, leaves, ntable_words); if (rc_) return rc_; }
     HIPCHK(enter_device(ix->cfg.device));
-    infx_filter* f = new infx_filter(); f->ix = ix; f->nops = nops; f->nleaves = nleaves;
+    infx_filter* f = new infx_filter(); f->ix = ix; f->nops = nops; f->nleaves = nleaves; f->hLeaves.assign(leaves, leaves + nleaves);
     auto bail = [&](int32_t rc) { infx_filter_destroy(f); return rc; };
     if (hipMalloc(&f->dOps, nops * sizeof(infx_filter_op)) != hipSuccess || hipMalloc(&f->dLeaves, std::max<size_t>(1, nleaves) * sizeof(infx_filter_leaf)) != hipSuccess ||
         hipMalloc(&f->dTables, std::max<size_t>(1, ntable_words) * 4) != hipSuccess) return bail(fail(INFX_ENOMEM, "filter allocation failed%s"));
@@ -2256,14 +2346,14 @@ int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count) {
     if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    for (int c = 0; c < FILT_MAXCOL; c++)       // columns are indexed by GLOBAL internal id: every uploaded column must cover this shard
-        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)ix->d.docBase + (uint64_t)ix->d.N) return fail(INFX_EINVAL, "a column holds fewer rows than this shard's documents%s");
-    HIPCHK(hipMemsetAsync(s->dExactStat, 0, 4, s->st));
-    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
-    const int n = ix->d.N;
-    if (n > 0) k_filter_count<<<std::min(4096, (n + 255) / 256), 256, 0, s->st>>>(f->d, cols, ix->d.docBase, n, ix->d.deleted, s->dExactStat);
-    HIPCHK(hipGetLastError());
-    DOWN(count, s->dExactStat, 4);
+    // k_filter_count_multi with a one-entry program table (the filter's device copy) over this shard's documents
+    GROW(s->dPostBlob, s->capPostBlob, sizeof(DevFilter));
+    GROW(s->dQCount, s->capQCount, 4);
+    UP(s->dPostBlob, &f->d, sizeof(DevFilter));
+    const infx_filter_leaf* lv = f->hLeaves.data(); const uint32_t nl = (uint32_t)f->hLeaves.size();
+    const DevCountCols cc = count_columns(&lv, &nl, 1);
+    { int32_t rc_ = count_enqueue(s, (const DevFilter*)s->dPostBlob, 1, cc, ix->d.docBase, ix->d.N, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+    DOWN(count, s->dQCount, 4);
     SYNC();
     return INFX_OK;
 }
@@ -2272,6 +2362,7 @@ int32_t infx_stream_set_postfilter(infx_stream* s, infx_filter* f, uint32_t nfac
     for (uint32_t c = 0; c < nfacet; c++) if (facet_cols[c] >= FILT_MAXCOL || !s->ix->colCodes[facet_cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
     for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids: a column shorter than the corpus would be read out of bounds
         if (s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    if (s->qpOn && (f || nfacet)) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->postFilter = f; s->nFacet = nfacet;
     for (uint32_t c = 0; c < INFX_MAX_FACET_COLS; c++) s->facetCols[c] = c < nfacet ? facet_cols[c] : 0;
     return INFX_OK;
@@ -2295,6 +2386,7 @@ int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f
     if (m > INFX_MAX_BOOSTS) return fail(INFX_ECAPACITY, "more than INFX_MAX_BOOSTS boosts with a filter%s");
     for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids: a column shorter than the corpus would be read out of bounds
         if (m && s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    if (s->qpOn && m) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->nBoost = 0;
     for (uint32_t i = 0; i < n; i++) if (f[i]) { s->boosts[s->nBoost] = f[i]; s->boostStrength[s->nBoost] = strengths[i]; s->nBoost++; }
     for (uint32_t i = s->nBoost; i < INFX_MAX_BOOSTS; i++) { s->boosts[i] = nullptr; s->boostStrength[i] = 0; }
@@ -2306,12 +2398,104 @@ int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, in
         if (col >= FILT_MAXCOL || !s->ix->colCodes[col] || !s->ix->colRankOk[col]) return fail(INFX_EINVAL, "sort column or its rank was not uploaded%s");
         if (s->ix->colDocs[col] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
     }
+    if (s->qpOn && enabled) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->sortOn = enabled != 0; s->sortCol = enabled ? col : 0; s->sortAsc = enabled && ascending != 0;
+    return INFX_OK;
+}
+// ---- per-query post-processing (k_postfilter / k_postproc with one descriptor per query) + k_filter_count_multi ----------------------------------
+// packs programs [0, n) into one blob (ops, leaves, tables of each, 16-byte aligned), validated as infx_filter_create does
+static int32_t pack_progs(infx_index* ix, uint32_t n, const infx_filter_prog* progs, std::vector<infx_stream::QpProg>& out, std::vector<uint8_t>& code) {
+    out.clear(); code.clear();
+    auto put = [&](const void* p, size_t bytes) { const size_t o = (code.size() + 15) & ~(size_t)15; code.resize(o + bytes); if (bytes) std::memcpy(code.data() + o, p, bytes); return (uint32_t)o; };
+    for (uint32_t i = 0; i < n; i++) {
+        const infx_filter_prog& P = progs[i];
+        if (!P.nops || !P.ops || (P.nleaves && (!P.leaves || !P.tables))) return fail(INFX_EINVAL, "null filter program%s");
+        { int32_t rc_ = check_filter_prog(ix, P.nops, P.ops, P.nleaves, P.leaves, P.ntable_words); if (rc_) return rc_; }
+        infx_stream::QpProg Q{};
+        Q.nops = P.nops; Q.nleaves = P.nleaves;
+        Q.opsOff = put(P.ops, (size_t)P.nops * sizeof(infx_filter_op));
+        Q.leavesOff = put(P.leaves, (size_t)P.nleaves * sizeof(infx_filter_leaf));
+        Q.tablesOff = put(P.tables, (size_t)P.ntable_words * 4);
+        out.push_back(Q);
+    }
+    if (code.size() > 0xFFFFFFF0ull) return fail(INFX_ECAPACITY, "the batch's filter programs exceed 4 GiB%s");
+    return INFX_OK;
+}
+int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, const infx_filter_prog* progs, uint32_t nboost, const infx_query_boost* boosts,
+                                   const infx_query_post* post, uint32_t nfacet, const uint32_t* facet_cols, uint32_t ncount, uint32_t* counts_out) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    s->qpOn = false; s->lastCountK = 0; s->lastCountLaunches = 0;      // the count stats are set again only by the finalize that consumes these options
+    if (nq == 0) return INFX_OK;
+    if (!post || (nprog && !progs) || (nboost && !boosts) || nfacet > INFX_MAX_FACET_COLS || (nfacet && !facet_cols) || ncount > nprog || (ncount && !counts_out))
+        return fail(INFX_EINVAL, "bad per-query post-processing arguments%s");
+    if (s->postFilter || s->nFacet || s->nBoost || s->sortOn) return fail(INFX_EINVAL, "per-query options and a session-wide post-filter, facets, boosts or sort exclude each other%s");
+    infx_index* ix = s->ix;
+    for (uint32_t c = 0; c < nfacet; c++) if (facet_cols[c] >= FILT_MAXCOL || !ix->colCodes[facet_cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
+    for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids and the counts run over the whole corpus: every column covers it
+        if (ix->colCodes[c] && ix->colDocs[c] < (uint32_t)ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    for (uint32_t b = 0; b < nboost; b++) if (boosts[b].prog < 0 || (uint32_t)boosts[b].prog >= nprog) return fail(INFX_EINVAL, "boost program index out of range%s");
+    for (uint32_t q = 0; q < nq; q++) {
+        const infx_query_post& D = post[q];
+        if (D.filter >= 0 && (uint32_t)D.filter >= nprog) return fail(INFX_EINVAL, "filter program index out of range%s");
+        if (D.nboost > INFX_MAX_BOOSTS || (uint64_t)D.boost_off + D.nboost > nboost) return fail(INFX_EINVAL, "boost list out of range%s");
+        if ((D.flags & INFX_QP_SORT) && D.sort_col != 0xFFFFFFFFu && (D.sort_col >= FILT_MAXCOL || !ix->colCodes[D.sort_col] || !ix->colRankOk[D.sort_col]))
+            return fail(INFX_EINVAL, "sort column or its rank was not uploaded%s");
+        if (D.flags & ~(uint32_t)(INFX_QP_FACETS | INFX_QP_SORT | INFX_QP_ASC)) return fail(INFX_EINVAL, "unknown per-query flag%s");
+    }
+    { int32_t rc_ = pack_progs(ix, nprog, progs, s->qpProgs, s->qpCode); if (rc_) return rc_; }
+    s->qpBoosts.resize(nboost); for (uint32_t b = 0; b < nboost; b++) s->qpBoosts[b] = DevQBoost{boosts[b].prog, boosts[b].strength};
+    s->qpDesc.resize(nq);
+    for (uint32_t q = 0; q < nq; q++) {
+        const infx_query_post& D = post[q]; DevQPost& E = s->qpDesc[q];
+        E = DevQPost{}; E.filter = D.filter < 0 ? -1 : D.filter; E.flags = D.flags; E.sortCol = (D.flags & INFX_QP_SORT) ? D.sort_col : 0u; E.boostOff = D.boost_off; E.nboost = D.nboost;
+    }
+    std::vector<const infx_filter_leaf*> lv(ncount); std::vector<uint32_t> nl(ncount);
+    for (uint32_t i = 0; i < ncount; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
+    s->qpCols = count_columns(lv.data(), nl.data(), ncount);
+    s->qpNq = nq; s->qpNFacet = nfacet; s->qpNCount = ncount; s->qpCountsOut = counts_out;
+    for (uint32_t c = 0; c < INFX_MAX_FACET_COLS; c++) s->qpFacetCols[c] = c < nfacet ? facet_cols[c] : 0;
+    s->qpOn = true;
+    return INFX_OK;
+}
+int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_prog* progs, int32_t whole_corpus, uint32_t* counts) {
+    if (!s || (k && (!progs || !counts))) return fail(INFX_EINVAL, "null argument%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    if (!k) return INFX_OK;
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    std::vector<infx_stream::QpProg> packed; std::vector<uint8_t> code;
+    { int32_t rc_ = pack_progs(ix, k, progs, packed, code); if (rc_) return rc_; }
+    const size_t oCode = ((size_t)k * sizeof(DevFilter) + 15) & ~(size_t)15, total = oCode + code.size();
+    GROW(s->dPostBlob, s->capPostBlob, total);
+    GROW(s->dQCount, s->capQCount, (size_t)k * 4);
+    char* D = (char*)s->dPostBlob;
+    std::vector<uint8_t> H(total, 0);
+    for (uint32_t i = 0; i < k; i++) {
+        const auto& P = packed[i];
+        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
+        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
+    }
+    if (!code.empty()) std::memcpy(H.data() + oCode, code.data(), code.size());
+    UP(D, H.data(), total);
+    std::vector<const infx_filter_leaf*> lv(k); std::vector<uint32_t> nl(k);
+    for (uint32_t i = 0; i < k; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
+    const DevCountCols cc = count_columns(lv.data(), nl.data(), k);
+    const int32_t base = whole_corpus ? 0 : ix->d.docBase, n = whole_corpus ? ix->d.totalDocs : ix->d.N;
+    { int32_t rc_ = count_enqueue(s, (const DevFilter*)D, k, cc, base, n, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+    DOWN(counts, s->dQCount, (size_t)k * 4);
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (counted) *counted = s->lastCountK;
+    if (launches) *launches = s->lastCountLaunches;
     return INFX_OK;
 }
 int32_t infx_last_facets(infx_stream* s, uint32_t nq, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out) {
     if (!s || !codes_out || !counts_out || !n_out) return fail(INFX_EINVAL, "null argument%s");
-    if (nq != s->facetNq || !s->nFacet) return fail(INFX_EINVAL, "no facets of a batch of this size on the stream%s");
+    if (nq != s->facetNq || !s->facetNFacet) return fail(INFX_EINVAL, "no facets of a batch of this size on the stream%s");
     std::memcpy(codes_out, s->hFacCodes.data(), s->hFacCodes.size() * 4); std::memcpy(counts_out, s->hFacCounts.data(), s->hFacCounts.size() * 4);
     std::memcpy(n_out, s->hFacN.data(), s->hFacN.size() * 4);
     return INFX_OK;

@@ -89,6 +89,7 @@ class Result:      # Api/Result.cs
     skipped_candidates: bool = False       # a candidate document exceeded the Stage-2 envelope (INFX_MAX_DOC_TOKENS) and was left out
     facets: Optional[dict] = None          # field -> [(value, count)] (count desc, value asc), Api/Result.cs Facets
     total_in_filter: int = 0               # Filter.NumberOfDocumentsInFilter
+    error: Optional[str] = None            # search_queries: why this query alone was rejected (empty result); None when it ran
 
 
 class _Cfg(C.Structure):
@@ -305,6 +306,28 @@ class SearchEngine:
             self.L.infx_engine_set_boosts(sh, 0, None, None, 0)
             self.L.infx_engine_set_sort(sh, None, 0)
 
+    def search_queries(self, queries: Sequence[Query], session=None) -> List[Result]:
+        """Search(Query) for a batch of Query objects, each with its own MaxNumberOfRecordsToReturn, EnableCoverage, Filter, EnableFacets, Boosts and
+        SortBy (infx_engine_set_query_options): one device batch per CoverageDepth, results in input order.  A query whose options are refused
+        (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than 64 rows) comes back empty with Result.error set; the
+        others of the batch are unaffected."""
+        sh = session.h if session is not None else self._default_session()
+        runner = (session or self).search_packed
+        out = [None] * len(queries)
+        for depth, idx in _by_depth(queries):
+            qs = [queries[i] for i in idx]
+            status = _install_query_options(self, sh, qs)
+            stride = max(1, max(int(q.max_number_of_records_to_return) for q in qs))
+            arena, offs = pack_texts([q.text for q in qs])
+            try:
+                keys, scores, ties, counts, flags = runner(arena, offs, stride, depth, True)
+            except Exception:
+                self.L.infx_engine_set_query_options(sh, 0, None, None)
+                raise
+            for i, r in zip(idx, _query_results(self, sh, qs, status, keys, scores, ties, counts, flags)):
+                out[i] = r
+        return out
+
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
@@ -312,6 +335,18 @@ class SearchEngine:
             return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
                                         enable_boost=q.enable_boost, boosts=q.boosts, sort_by=q.sort_by, sort_ascending=q.sort_ascending)[0]
         return self.search_batch([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage)[0]
+
+    def last_count_stats(self, session=None):
+        """(expressions the session's last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
+        return _count_stats(self, session.h if session is not None else self._default_session())
+
+    def set_filter_cache_limit(self, n: int):
+        """Bound of the engine's filter cache (compiled expressions + their counts), least recently used first."""
+        self._check(self.L.infx_engine_set_filter_cache_limit(self.h, C.c_uint64(int(n))))
+
+    def filter_cache_size(self) -> int:
+        self.L.infx_engine_filter_cache_size.restype = C.c_int64
+        return int(self.L.infx_engine_filter_cache_size(self.h))
 
     def search_batch_raw(self, texts: Sequence[str], max_results=10, depth=500, enable_coverage=True):
         arena, offs = pack_texts(texts)
@@ -489,6 +524,14 @@ class Session:
         """Installs Query.Boosts (a sequence of Boost; None or enable_boost=False clears) on this session."""
         _set_boosts(self.engine, self.h, boosts, enable_boost)
 
+    def search_queries(self, queries: Sequence[Query]) -> List[Result]:
+        """SearchEngine.search_queries on this session."""
+        return self.engine.search_queries(queries, session=self)
+
+    def last_count_stats(self):
+        """(expressions the last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
+        return _count_stats(self.engine, self.h)
+
     def set_sort(self, sort_by=None, ascending=False):
         """Installs Query.SortBy (a field name; None = relevance order) and Query.SortAscending on this session."""
         _set_sort(self.engine, self.h, sort_by, ascending)
@@ -522,6 +565,64 @@ def _set_boosts(engine, sh, boosts, enable_boost):
     exprs = (C.c_char_p * max(len(bs), 1))(*[b.filter.encode() if b.filter is not None else None for b in bs])
     st = np.asarray([int(b.strength) for b in bs] or [0], np.int32)
     engine._check(engine.L.infx_engine_set_boosts(sh, len(bs) if on else 0, exprs, _p(st, C.c_int32), int(on)))
+
+
+class _QueryOptions(C.Structure):      # infx_query_options (include/infidex_engine.h)
+    _fields_ = [("max_results", C.c_int32), ("enable_coverage", C.c_int32), ("enable_facets", C.c_int32), ("enable_boost", C.c_int32),
+                ("filter", C.c_char_p), ("nboosts", C.c_uint32), ("boost_filters", C.POINTER(C.c_char_p)), ("boost_strengths", C.POINTER(C.c_int32)),
+                ("sort_by", C.c_char_p), ("sort_ascending", C.c_int32)]
+
+
+def _by_depth(queries):
+    """[(CoverageDepth, [indices in input order])]: one device batch per depth."""
+    groups = {}
+    for i, q in enumerate(queries):
+        groups.setdefault(int(q.coverage_depth), []).append(i)
+    return list(groups.items())
+
+
+def _install_query_options(engine, sh, qs):
+    """infx_engine_set_query_options for the queries qs on session handle sh; returns each query's status (0: accepted)."""
+    n = len(qs)
+    arr = (_QueryOptions * max(n, 1))()
+    keep = []
+    for o, q in zip(arr, qs):
+        o.max_results = int(q.max_number_of_records_to_return); o.enable_coverage = int(bool(q.enable_coverage))
+        o.enable_facets = int(bool(q.enable_facets)); o.enable_boost = int(bool(q.enable_boost))
+        o.filter = q.filter.encode() if q.filter is not None else None
+        bs = list(q.boosts) if q.boosts else []
+        if bs:
+            ex = (C.c_char_p * len(bs))(*[b.filter.encode() if b.filter is not None else None for b in bs])
+            st = (C.c_int32 * len(bs))(*[int(b.strength) for b in bs])
+            keep += [ex, st]
+            o.nboosts = len(bs); o.boost_filters = C.cast(ex, C.POINTER(C.c_char_p)); o.boost_strengths = C.cast(st, C.POINTER(C.c_int32))
+        o.sort_by = q.sort_by.encode() if q.sort_by is not None else None; o.sort_ascending = int(bool(q.sort_ascending))
+    status = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_set_query_options(sh, n, arr, _p(status, C.c_int32)))
+    return status[:n]
+
+
+def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
+    """The Results of a per-query batch just searched on session handle sh."""
+    n = len(qs)
+    inf = np.zeros(max(n, 1), np.uint32)
+    engine._check(engine.L.infx_engine_last_in_filter(sh, n, _p(inf, C.c_uint32)))
+    out = []
+    for j, q in enumerate(qs):
+        err = None
+        if status[j] != 0:
+            buf = C.create_string_buffer(512); engine.L.infx_engine_query_error(sh, j, buf, 512)
+            err = buf.value.decode(errors="replace") or ("status %d" % int(status[j]))
+        recs = [ScoreEntry(float(scores[j, k]), int(keys[j, k]), int(ties[j, k])) for k in range(int(counts[j]))]
+        facets = engine.facets_of(sh, n, j) if q.enable_facets and err is None else None
+        out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]), err))
+    return out
+
+
+def _count_stats(engine, sh):
+    k = C.c_uint32(0); n = C.c_uint32(0)
+    engine._check(engine.L.infx_engine_last_count_stats(sh, C.byref(k), C.byref(n)))
+    return int(k.value), int(n.value)
 
 
 def _set_sort(engine, sh, sort_by, ascending):

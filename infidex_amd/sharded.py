@@ -26,7 +26,7 @@ from typing import List, Sequence
 import os
 import numpy as np
 
-from .engine import SearchEngine, Session, _p, INFX_NFEAT  # noqa: F401
+from .engine import SearchEngine, Session, Result, _p, INFX_NFEAT, pack_texts, _by_depth, _install_query_options, _query_results  # noqa: F401
 
 INFX_NCLASS = 136
 CHAIN = 0xFFFFFFFF
@@ -201,6 +201,15 @@ class ShardSession:
     def set_sort(self, sort_by=None, ascending=False):
         """Query.SortBy / Query.SortAscending on this session (phase 4, after the boosts)."""
         self.s.set_sort(sort_by, ascending)
+
+    def set_query_options(self, queries):
+        """Per-query options (infx_engine_set_query_options) of the next batch on this session; returns each query's status.  Phase 4 applies them to
+        the merged rows (identical on every rank); NumberOfDocumentsInFilter is counted over the WHOLE corpus on every rank (no sum)."""
+        return _install_query_options(self.e, self.s.h, queries)
+
+    def query_results(self, queries, status, res):
+        """The Results of the per-query batch just run on this session (res: its phase-4 arrays)."""
+        return _query_results(self.e, self.s.h, queries, status, *res)
 
     def facets(self, i):
         """Facets of query i of the last batch (phase 4 ran the post-filter and counted the facet values of the kept rows; identical on every rank)."""
@@ -657,6 +666,25 @@ class ShardedSearcher:
         for s in self.sessions:
             s.set_sort(sort_by, ascending)
 
+    def search_queries(self, queries) -> List[Result]:
+        """SearchEngine.search_queries across the shards: one batch per CoverageDepth, each query with its own options.  Collective: same call with the
+        same queries on every rank.  NumberOfDocumentsInFilter is the GLOBAL count on every rank (each counts the whole corpus): nothing is summed."""
+        out = [None] * len(queries)
+        for depth, idx in _by_depth(queries):
+            qs = [queries[i] for i in idx]
+            s = self.sessions[0]
+            status = s.set_query_options(qs)
+            stride = max(1, max(int(q.max_number_of_records_to_return) for q in qs))
+            arena, offs = pack_texts([q.text for q in qs])
+            try:
+                res = self.search_packed(arena, offs, stride, depth, True)
+            except Exception:
+                s.L.infx_engine_set_query_options(s.s.h, 0, None, None)
+                raise
+            for i, r in zip(idx, s.query_results(qs, status, res)):
+                out[i] = r
+        return out
+
     def last_facets(self, i):
         return self.last.facets(i)
 
@@ -686,6 +714,27 @@ def simulate_shards_dev(sessions: Sequence[ShardSession], arena, offs, max_resul
     replaced by torch.stack / sum on the same device)."""
     ucs = [s.phase0(arena, offs, depth) for s in sessions]
     return _run_batch(sessions, _LocalX(len(sessions), _DevBufs(device)), ucs, max_results, depth, enable_coverage)
+
+
+def simulate_search_queries(sessions: Sequence[ShardSession], queries, device="cuda:0", every_shard=False):
+    """ShardedSearcher.search_queries for the in-process simulation (simulate_shards_dev): every shard's session gets the same per-query options.
+    Returns shard 0's Results (every shard computes the same rows, facets and global counts), or with every_shard=True one list per shard."""
+    outs = [[None] * len(queries) for _ in sessions]
+    for depth, idx in _by_depth(queries):
+        qs = [queries[i] for i in idx]
+        status = [s.set_query_options(qs) for s in sessions]
+        stride = max(1, max(int(q.max_number_of_records_to_return) for q in qs))
+        arena, offs = pack_texts([q.text for q in qs])
+        try:
+            res = simulate_shards_dev(sessions, arena, offs, stride, depth, True, device=device)
+        except Exception:
+            for s in sessions:
+                s.L.infx_engine_set_query_options(s.s.h, 0, None, None)
+            raise
+        for out, s, st, r in zip(outs, sessions, status, res):
+            for i, x in zip(idx, s.query_results(qs, st, r)):
+                out[i] = x
+    return outs if every_shard else outs[0]
 
 
 def simulate_shards(sessions: Sequence[ShardSession], arena, offs, max_results=10, depth=500, enable_coverage=True):
