@@ -212,6 +212,11 @@ int32_t infx_engine_verify_segment(infx_engine* e, const char* path, int32_t doc
 int32_t infx_engine_index_from_segments(infx_engine* e, int64_t n, const int64_t* keys, const uint16_t* arena, const uint64_t* offs, int32_t field_count, const int32_t* field_weights,
                                         int32_t n_segments, const char* const* paths, const int32_t* doc_bases);
 int32_t infx_engine_restore_documents(infx_engine* e);      /* clears every Deleted flag */
+/* Document.Deleted = true on single documents by internal id (indexing order), e.g. one of several documents of a key; otherwise as
+ * infx_engine_delete_documents.  The documents of one key then differ in their flag, which deletion by key never produces: browse rows and the
+ * whole-corpus facets are held to the reference in that state (first live document of the key); the text-query paths skip each Deleted document as
+ * they always do, but their key lookups (consolidation, post-filter, facets) have no test on a key that is partly deleted. */
+int32_t infx_engine_delete_document_ids(infx_engine* e, const int64_t* ids, int64_t n, int64_t* out_marked);
 /* One host-index build per node instead of one per rank (document shards: every process needs the whole host index — global df / avgdl / N, the term and
  * word dictionaries, the WordMatcher lists).  The node's leader indexes the documents (infx_engine_set_build_threads lets that build use every
  * core of the node while planning keeps the rank's share), saves the host index to a node-local file (e.g. under /dev/shm) and the other ranks call
@@ -234,6 +239,21 @@ int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, cha
 int32_t infx_engine_set_filter(infx_session* s, const char* expr_utf8 /* NULL = no filter */, int32_t enable_facets, uint32_t* n_in_filter);
 int32_t infx_engine_facet_column_count(infx_session* s);
 int32_t infx_engine_last_facets(infx_session* s, uint32_t nq, uint32_t qi, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap);
+/* A query whose text is empty (or all whitespace) and that has EnableFacets — through infx_engine_set_filter(.., enable_facets = 1, ..) or its
+ * infx_query_options — is a browse query (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346): it returns the first max_results documents
+ * in indexing order that are not Deleted and whose key's first live document passes the filter, each with score 65535 and tiebreaker 0, and the facets
+ * of those rows; Boosts, SortBy and coverage do not apply.  NumberOfDocumentsInFilter, the 64-row limit and the refusals are those of a text query.
+ * Without EnableFacets (or without a facetable column) a blank query returns nothing, as before.
+ *
+ * FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): infx_engine_facets_all counts, in one device pass, the values of every
+ * facetable column (the first INFX_MAX_FACET_COLS) over all documents that are not Deleted — per document, not per key; *ncols = those columns.
+ * infx_engine_facets_all_column then gives the k-th column's (code, count) pairs, count descending then value ascending, at most 100, null and empty
+ * values left out; it returns their number, -1 on error.  INFX_EHIP on an engine without a GPU.
+ * infx_engine_last_browse_stats: the groups (distinct filter programs, the counted ones included) and the k_browse_scan launches (256 groups each) of the
+ * session's last batch that had a browse query. */
+int32_t infx_engine_last_browse_stats(infx_session* s, uint32_t* groups, uint32_t* launches);
+int32_t infx_engine_facets_all(infx_session* s, int32_t* ncols);
+int32_t infx_engine_facets_all_column(infx_session* s, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap);
 /* Query.EnableBoost + Query.Boosts (ResultProcessor.ApplyBoosts, Scoring/ResultProcessor.cs:75-121) for the following searches on the session: n boosts,
  * exprs[i] its Infiscript filter (NULL: a Boost whose Filter is null, dropped), strengths[i] = (int)BoostStrength (Low 1, Med 2, High 3).  enable = 0
  * (or n = 0) clears and compiles nothing.  Filters are compiled through the engine's filter cache; a boost never counts NumberOfDocumentsInFilter.

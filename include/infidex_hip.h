@@ -313,8 +313,31 @@ int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, 
 /* k programs counted in one k_filter_count_multi launch (several past 4096 programs), synchronously: counts[i] = documents not Deleted that progs[i]
  * accepts — this shard's documents (whole_corpus = 0, as infx_filter_count) or every document of the corpus (1). */
 int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_prog* progs, int32_t whole_corpus, uint32_t* counts);
-/* the programs the last finalize (or infx_filter_count_progs) on this stream counted, and in how many launches */
+/* the programs the last finalize (or infx_filter_count_progs) on this stream counted, and in how many k_filter_count_multi launches (0 when a batch's
+ * browse scan counted them, see below) */
 int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches);
+
+/* ---- browse rows: a query with no text and EnableFacets (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346) -------------------------
+ * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= INFX_FILTER_MAX_ROWS, else INFX_EUNSUPPORTED) documents in
+ * internal order that are not Deleted and that its filter accepts — the filter of its infx_query_post descriptor (which must carry INFX_QP_FACETS) or
+ * the stream's post-filter (with facet columns installed) — each with score 65535 and tiebreaker 0; result flags 0.  The rows are written where a text
+ * query's rows land before the post-filter, so the facets of infx_last_facets are those of the rows.  All browse queries of a batch are grouped by
+ * program and answered by one ordered scan of the whole corpus (every shard holds the whole columns: each rank computes the same rows, no collective);
+ * when the batch has one, that scan also produces the ncount counts of infx_stream_set_query_post and k_filter_count_multi is not launched.
+ * The output order is the document order by construction (per-range counts, a prefix, ballot compaction): it does not vary from run to run.
+ * infx_set_first_live: first[d] = first live document carrying document d's key, one entry per GLOBAL internal id; a browse row's filter and facets
+ * look at that document (ResultProcessor.ApplyFilter / FacetBuilder look a row up by key), while the counts evaluate each document's own fields.
+ * Needed only for a corpus with duplicate keys, to be refreshed when Deleted flags change; NULL clears; infx_upload_docs and a change of total_docs
+ * (infx_set_shard) void it.  Exclusive call, as infx_set_deleted.
+ * A group that only needs rows (count cached, or no filter) stops inside a range of the scan once the range holds enough matches; the environment
+ * variable INFX_BROWSE_EARLY_STOP=0, read once per process, switches that off for measurements (tools/bench_browse.py) — the results do not change. */
+int32_t infx_set_first_live(infx_index* idx, uint32_t total, const int32_t* first);
+/* groups (distinct programs, counted ones included) and k_browse_scan launches of the last finalize that had browse queries */
+int32_t infx_last_browse_stats(infx_stream* s, uint32_t* groups, uint32_t* launches);
+/* FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): for each of the ncol (<= INFX_MAX_FACET_COLS) uploaded columns cols[k] in
+ * turn, the number of documents of the WHOLE corpus that are not Deleted per distinct value — counts_out holds sum(num_values) words, column k's
+ * behind those of the columns before it.  One pass over the documents for all columns, synchronous.  The host drops null / empty values, orders and cuts. */
+int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uint32_t* counts_out);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on
@@ -375,6 +398,7 @@ int32_t infx_wm_lookup_debug(infx_stream* s, const infx_cov_query* cq, infx_wm_l
 #define INFX_FQ_SHORTSKIP 4u       /* short query whose prefix population exceeds 500: coverage is skipped */
 #define INFX_FQ_COV 8u             /* coverage enabled (engine setup && Query.EnableCoverage) */
 #define INFX_FQ_UNSUPPORTED 16u    /* result flag bit0 is set */
+#define INFX_FQ_BROWSE 64u         /* with INFX_FQ_SKIP: empty text + EnableFacets — the first max_results live documents the query's filter accepts (browse rows, above) */
 #define INFX_FQ_WMDEV 32u          /* the WordMatcher lists of this query are looked up on the device (infx_upload_wm_dictionary) from the words of its
                                       infx_cov_query; wm_off / wm_count are ignored (leave wm_count 0).  Admissible while words x (3 + 2*max_ld1) <= INFX_MAX_WM_LISTS */
 #define INFX_MAX_WM_LISTS 256

@@ -84,6 +84,8 @@ struct DevPostBatch {
     const uint32_t* rank[FILT_MAXCOL];                                                                // sort ranks of the columns (nullptr: not uploaded)
     // rows of query q: [q * stride, + counts[q]), counts[q] <= INFX_FILTER_MAX_ROWS for a query with post-processing — filtered, boosted, reordered in place
     long long* keys; float* scores; uint8_t* ties; int32_t* docs; uint32_t* counts; uint32_t* flags; int32_t stride;
+    // the batch's fused queries when it has browse queries (INFX_FQ_BROWSE: their rows take no boosts and no sort-by, SearchEngine.cs:292-293), else nullptr
+    const infx_fused_query* fqs;
 };
 
 // facets of query q, column c: fCodes / fCounts [(q * nfacet + c) * INFX_FILTER_MAX_ROWS ..], fN[q * nfacet + c] (0 for a query without facets)

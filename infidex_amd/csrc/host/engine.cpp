@@ -63,7 +63,7 @@ struct Batch {
 // Per-query options of the session's next batch (infx_engine_set_query_options): consumed by that batch, whichever search path runs it
 struct QueryOpts {
     bool on = false, bound = false; uint32_t nq = 0;      // bound: a sharded phase 0 took them for its batch (a second phase 0 finds them stale)
-    std::vector<int32_t> maxResults; std::vector<uint8_t> cov, reject; std::vector<int32_t> status; std::vector<std::string> err;
+    std::vector<int32_t> maxResults; std::vector<uint8_t> cov, reject, facets; std::vector<int32_t> status; std::vector<std::string> err;      // facets: the query counts facets (a blank text then browses)
     std::vector<std::string> filterExpr;       // per query: its filter ("" = none), for NumberOfDocumentsInFilter after the batch
     std::vector<std::string> pinned;           // cache entries the batch holds (filters and boosts)
     std::vector<std::string> countExprs; std::vector<uint32_t> counts;      // expressions the batch counts first (programs [0, n) of its table) + the device's counts
@@ -73,6 +73,7 @@ struct infx_session {
     QueryOpts qo;
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
     bool swFilter = false, swBoost = false, swSort = false;      // session-wide options installed (infx_engine_set_filter / _set_boosts / _set_sort)
+    std::vector<uint32_t> facAllCols; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> facAll;      // infx_engine_facets_all: columns and their ordered (code, count) lists
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -116,6 +117,12 @@ struct CompiledFilter {
 // and EnableCoverage; the call's values for a session without options
 static inline int32_t qo_max(const infx_session* S, size_t i, int32_t mr) {
     return S->qo.on && i < S->qo.nq && S->qo.maxResults[i] >= 1 ? std::min(S->qo.maxResults[i], mr) : mr;
+}
+// A blank text with EnableFacets is a browse query (SearchEngine.cs:292-293, HandleEmptyQueryWithFacets): per query with its options, or for every
+// query of the batch while the session-wide facets are installed.  (The facets need a facetable column; without one a blank query stays empty.)
+static inline bool qo_browse(const infx_session* S, size_t i) {
+    if (S->qo.on) return i < S->qo.nq && S->qo.facets[i] && !S->qo.reject[i];
+    return S->swFilter && !S->facetCols.empty();
 }
 static inline bool qo_cov(const infx_session* S, size_t i, bool cov) { return cov && (!S->qo.on || i >= S->qo.nq || S->qo.cov[i]); }
 static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results);
@@ -422,6 +429,7 @@ static int32_t upload_lookups(infx_engine* e) {
     return INFX_OK;
 }
 
+static int32_t refresh_first_live(infx_engine* e);
 // After the host index exists (built here or read from a node-local cache): key map, shard bounds, upload of this rank's slice
 static int32_t finish_index(infx_engine* e) {
     if (!e->keysAreIds) { const int64_t n = e->ix.N; e->keyToFirst.reserve((size_t)n * 2); for (int64_t d = 0; d < n; d++) e->keyToFirst.emplace(e->ix.docKey[d], (int32_t)d); }
@@ -477,11 +485,27 @@ static int32_t finish_index(infx_engine* e) {
         if (!rc) rc = upload_lookups(e);
         if (!rc) rc = infx_stream_create(e->dev, &e->def->stream);
         if (rc) { g_eerr = infx_last_error(); return rc; }
+        rc = refresh_first_live(e); if (rc) return rc;
     }
     e->indexed = true;
     return INFX_OK;
 }
 
+// The device's map "first live document of each document's key" (browse rows look a row up by key: include/infidex_hip.h, infx_set_first_live).
+// Only a corpus with duplicate keys has one; rebuilt whenever Deleted flags change.
+static int32_t refresh_first_live(infx_engine* e) {
+    if (!e->dev) return INFX_OK;
+    const int64_t N = e->ix.N;
+    if (e->keysAreIds || (int64_t)e->keyToFirst.size() == N) return INFX_OK;      // unique keys: no map (as deleted[] is absent while nothing is deleted)
+    std::vector<int32_t> first((size_t)N); std::unordered_map<int64_t, int32_t> live; live.reserve(e->keyToFirst.size() * 2);
+    for (int64_t d = 0; d < N; d++) {
+        if (!e->deleted.empty() && e->deleted[(size_t)d]) { first[(size_t)d] = (int32_t)d; continue; }
+        first[(size_t)d] = live.emplace(e->ix.docKey[(size_t)d], (int32_t)d).first->second;
+    }
+    int32_t rc = infx_set_first_live(e->dev, (uint32_t)N, first.data());
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
 static int32_t key_to_id(infx_engine* e, int64_t key) {
     if (e->keysAreIds) return (key >= 0 && key < e->ix.N) ? (int32_t)key : -1;
     auto it = e->keyToFirst.find(key); return it == e->keyToFirst.end() ? -1 : it->second;
@@ -1022,7 +1046,7 @@ static int32_t build_fused_inputs(infx_engine* e, infx_session* S, int32_t max_r
         for (int64_t i = b; i < en; i++) {
             const QueryPlan& P = plans[i]; infx_fused_query& F = fq[i];
             F = infx_fused_query{}; F.dev = -1; F.max_results = qo_max(S, i, max_results);
-            if (P.blank || P.unsupported) { F.flags = INFX_FQ_SKIP | (P.unsupported ? INFX_FQ_UNSUPPORTED : 0u); continue; }
+            if (P.blank || P.unsupported) { F.flags = INFX_FQ_SKIP | (P.unsupported ? INFX_FQ_UNSUPPORTED : 0u) | (P.blank && !P.unsupported && qo_browse(S, i) ? INFX_FQ_BROWSE : 0u); continue; }
             F.dev = B.devOf.empty() ? -1 : B.devOf[i];      // (pre-built in phase 0: filled in by fused_inputs_for_phase3)
             const ustr& st = P.searchText;
             bool isShort = !st.empty() && st.size() <= 3;
@@ -1077,6 +1101,7 @@ static int32_t fused_inputs_for_phase3(infx_engine* e, infx_session* S, int32_t 
         infx_fused_query& q = F.fq[i];
         q.max_results = qo_max(S, i, max_results);
         if (!(q.flags & INFX_FQ_SKIP)) q.dev = B.devOf.empty() ? -1 : B.devOf[i];
+        else if (!(q.flags & INFX_FQ_UNSUPPORTED)) /* skipped and not unsupported: a blank text */ q.flags = (q.flags & ~INFX_FQ_BROWSE) | (qo_browse(S, i) ? INFX_FQ_BROWSE : 0u);      // (the options the batch runs with)
         if (!qo_cov(S, i, cov)) { q.flags &= ~(INFX_FQ_COV | INFX_FQ_WMDEV); q.wm_count = 0; }
     }
     out = B.pre;
@@ -2191,7 +2216,20 @@ int32_t infx_engine_delete_documents(infx_engine* e, const int64_t* keys, int64_
     if (out_marked) *out_marked = marked;
     if (e->dev) { int32_t rc = infx_set_deleted(e->dev, (uint32_t)N, e->deleted.data()); if (rc) { g_eerr = infx_last_error(); return rc; } }
     e->invalidate_filter_counts();
-    return INFX_OK;
+    return refresh_first_live(e);
+}
+// Document.Deleted = true on single documents, by internal id (indexing order): the documents of one key need not share the flag (a persisted index
+// restores it per document, Indexing/IndexPersistence.cs:334).  Exclusive, as infx_engine_delete_documents.
+int32_t infx_engine_delete_document_ids(infx_engine* e, const int64_t* ids, int64_t n, int64_t* out_marked) {
+    if (!e || (n > 0 && !ids)) return efail(INFX_EINVAL, "null argument");
+    if (!e->indexed) return efail(INFX_EINVAL, "delete before index_documents");
+    const int64_t N = e->ix.N; int64_t marked = 0;
+    if (e->deleted.empty()) e->deleted.assign((size_t)N, 0);
+    for (int64_t i = 0; i < n; i++) if (ids[i] >= 0 && ids[i] < N && !e->deleted[(size_t)ids[i]]) { e->deleted[(size_t)ids[i]] = 1; marked++; }
+    if (out_marked) *out_marked = marked;
+    if (e->dev) { int32_t rc = infx_set_deleted(e->dev, (uint32_t)N, e->deleted.data()); if (rc) { g_eerr = infx_last_error(); return rc; } }
+    e->invalidate_filter_counts();
+    return refresh_first_live(e);
 }
 // Clears every Deleted flag (what a reload of the undeleted documents would give).
 int32_t infx_engine_restore_documents(infx_engine* e) {
@@ -2199,7 +2237,7 @@ int32_t infx_engine_restore_documents(infx_engine* e) {
     e->deleted.clear();
     if (e->dev && e->indexed) { int32_t rc = infx_set_deleted(e->dev, 0, nullptr); if (rc) { g_eerr = infx_last_error(); return rc; } }
     e->invalidate_filter_counts();
-    return INFX_OK;
+    return e->indexed ? refresh_first_live(e) : INFX_OK;
 }
 
 // ---- Infiscript post-filter + facets (config 5): Query.Filter / Query.EnableFacets (SearchEngine.cs:298-316) ------------------------------
@@ -2331,6 +2369,42 @@ int32_t infx_engine_last_facets(infx_session* S, uint32_t nq, uint32_t qi, uint3
     return m;
 }
 int32_t infx_engine_facet_column_count(infx_session* S) { return S ? (int32_t)S->facetCols.size() : -1; }
+// FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): value counts of every facetable column over all documents that are not
+// Deleted, one device pass for all columns (infx_facets_all); per column the values ordered count descending, value ascending, cut to 100, null and
+// empty values left out — as infx_engine_last_facets orders the row facets.  *ncols = facetable columns; their lists: infx_engine_facets_all_column.
+int32_t infx_engine_facets_all(infx_session* S, int32_t* ncols) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    infx_engine* e = S->e;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the facet counts run on the device");
+    if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
+    S->facAllCols.clear(); S->facAll.clear();
+    size_t total = 0;
+    for (size_t c = 0; c < e->columns.size() && S->facAllCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) { S->facAllCols.push_back((uint32_t)c); total += e->columns[c].dict.size(); }
+    if (ncols) *ncols = (int32_t)S->facAllCols.size();
+    if (S->facAllCols.empty()) return INFX_OK;
+    std::vector<uint32_t> counts(std::max<size_t>(total, 1));
+    int32_t rc = infx_facets_all(S->stream, (uint32_t)S->facAllCols.size(), S->facAllCols.data(), counts.data());
+    if (rc) { g_eerr = infx_last_error(); S->facAllCols.clear(); return rc; }
+    size_t o = 0;
+    for (uint32_t col : S->facAllCols) {
+        const filt::Column& C = e->columns[col];
+        std::vector<std::pair<uint32_t, uint32_t>> v;
+        for (uint32_t code = 0; code < C.dict.size(); code++) if (counts[o + code] && !C.text[code].empty()) v.push_back({code, counts[o + code]});     // empty strings are not facet values (:170-174)
+        std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
+        if (v.size() > 100) v.resize(100);
+        S->facAll.push_back(std::move(v));
+        o += C.dict.size();
+    }
+    return INFX_OK;
+}
+// The k-th facetable column of the session's last infx_engine_facets_all: engine column index in *col, up to cap (code, count) pairs; returns their
+// number, -1 on error.
+int32_t infx_engine_facets_all_column(infx_session* S, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap) {
+    if (!S || k >= S->facAll.size() || (cap > 0 && (!codes || !counts))) return -1;
+    if (col) *col = (int32_t)S->facAllCols[k];
+    int32_t m = 0; for (auto& x : S->facAll[k]) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
+    return m;
+}
 
 // ---- Query.Boosts / Query.SortBy (SearchEngine.cs:355-359): ResultProcessor.ApplyBoosts / ApplySort on the device after the post-filter -------------
 int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* exprs, const int32_t* strengths, int32_t enable) {
@@ -2412,7 +2486,7 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     if (S->swFilter || S->swBoost || S->swSort) return efail(INFX_EINVAL, "a session-wide filter, facets, boosts or sort is installed on this session: per-query options would conflict");
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
     QueryOpts Q; Q.nq = nq;
-    Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string()); Q.filterExpr.assign(nq, std::string());
+    Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.reject.assign(nq, 0); Q.facets.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string()); Q.filterExpr.assign(nq, std::string());
     std::vector<infx_query_post> post(nq); std::vector<infx_query_boost> boosts;
     std::vector<const CompiledFilter*> progs; std::unordered_map<std::string, int32_t> progIdx;
     std::vector<uint32_t> facetCols;
@@ -2460,7 +2534,7 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     for (uint32_t i = 0; i < nq; i++) {
         const QUse& U = use[i]; infx_query_post& D = post[i];
         D = infx_query_post{}; D.filter = U.filter.empty() ? -1 : progIdx.at(U.filter);
-        if (!Q.reject[i] && opts[i].enable_facets && anyFacets) D.flags |= INFX_QP_FACETS;
+        if (!Q.reject[i] && opts[i].enable_facets && anyFacets) { D.flags |= INFX_QP_FACETS; Q.facets[i] = 1; }
         D.boost_off = (uint32_t)boosts.size(); D.nboost = (uint32_t)U.boosts.size();
         for (auto& b : U.boosts) boosts.push_back(infx_query_boost{progIdx.at(b.first), b.second});
         if (U.sort) { D.flags |= INFX_QP_SORT | (opts[i].sort_ascending ? INFX_QP_ASC : 0u); D.sort_col = U.sortCol; }
@@ -2530,6 +2604,13 @@ int32_t infx_engine_last_count_stats(infx_session* S, uint32_t* counted, uint32_
     if (counted) *counted = S->lastCounted;
     if (launches) *launches = S->lastCountLaunches;
     return INFX_OK;
+}
+int32_t infx_engine_last_browse_stats(infx_session* S, uint32_t* groups, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (!S->stream) return efail(INFX_EHIP, "no GPU: browse queries run on the device");
+    int32_t rc = infx_last_browse_stats(S->stream, groups, launches);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
 }
 int32_t infx_engine_query_error(infx_session* S, uint32_t qi, char* out, int32_t cap) {
     if (!S || qi >= S->lastErr.size()) return -1;

@@ -22,6 +22,7 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
+#include <functional>
 #include <unordered_map>
 #include <algorithm>
 #include <mutex>
@@ -77,6 +78,7 @@ struct infx_index {
     std::vector<int32_t> hDf;
     std::vector<uint32_t> hSkipIdx;   // host copy of DevIndex::skipIdx (filled by infx_upload_postings)
     uint8_t* dDeleted = nullptr;      // device copy of the global Document.Deleted flags (infx_set_deleted)
+    int32_t* dFirstLive = nullptr; uint32_t firstLiveCap = 0; const int32_t* firstLive = nullptr;      // first live document of each document's key, by GLOBAL internal id (infx_set_first_live; nullptr: keys are unique)
     const uint32_t* colCodes[FILT_MAXCOL] = {}; uint32_t colValues[FILT_MAXCOL] = {}; uint32_t colDocs[FILT_MAXCOL] = {}; uint32_t colCap[FILT_MAXCOL] = {};   // device-resident columns (infx_upload_column)
     const uint32_t* colRank[FILT_MAXCOL] = {}; uint32_t colRankCap[FILT_MAXCOL] = {}; bool colRankOk[FILT_MAXCOL] = {};     // sort ranks of their codes (infx_upload_sort_rank); a column re-upload voids its rank
     std::vector<uint64_t> hPsOff;
@@ -236,6 +238,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "fused.hip.inc"
 #include "lookup.hip.inc"
 #include "filter.hip.inc"
+#include "browse.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -263,6 +266,11 @@ struct infx_stream {
     uint32_t lastCountK = 0, lastCountLaunches = 0;     // the filter programs the last finalize counted, and its k_filter_count_multi launches
     void* dPostBlob = nullptr; size_t capPostBlob = 0;     // the batch's DevPostBatch + program table + boost list + descriptors (+ packed programs)
     void* dQCount = nullptr; size_t capQCount = 0;
+    // browse queries (INFX_FQ_BROWSE) of the batch being staged: (query, rows asked), recorded by the prep stage and consumed by the finalize
+    std::vector<std::pair<uint32_t, uint32_t>> browseQ;
+    void *dBrwBlob = nullptr, *dBrwWork = nullptr; size_t capBrwBlob = 0, capBrwWork = 0;
+    uint32_t lastBrowseGroups = 0, lastBrowseLaunches = 0;      // groups and k_browse_scan launches of the last finalize
+    void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -820,12 +828,29 @@ int32_t infx_set_deleted(infx_index* ix, uint32_t total, const uint8_t* deleted)
     return INFX_OK;
 }
 
+// first[d] = the first live document carrying document d's key, by GLOBAL internal id (every shard holds the whole map): what a browse row's filter and
+// facets look at.  Only a corpus with duplicate keys needs it; nullptr clears (keys unique: first[d] == d).  Exclusive call, as infx_set_deleted.
+int32_t infx_set_first_live(infx_index* ix, uint32_t total, const int32_t* first) {
+    if (!ix) return fail(INFX_EINVAL, "null argument%s");
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "infx_set_first_live before infx_upload_docs%s");
+    if (first && total != (uint32_t)ix->d.totalDocs) return fail(INFX_EINVAL, "infx_set_first_live: one entry per global internal id (total_docs) is required%s");
+    if (first) for (uint32_t i = 0; i < total; i++) if (first[i] < 0 || (uint32_t)first[i] >= total) return fail(INFX_EINVAL, "infx_set_first_live: entry out of range%s");
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!first) { ix->firstLive = nullptr; return INFX_OK; }
+    if (!ix->dFirstLive || ix->firstLiveCap < total) { HIPCHK(dalloc(ix, &ix->dFirstLive, (size_t)total)); ix->firstLiveCap = total; }
+    HIPCHK(hipMemcpy(ix->dFirstLive, first, (size_t)total * 4, hipMemcpyHostToDevice));
+    ix->firstLive = ix->dFirstLive;
+    return INFX_OK;
+}
+
 int32_t infx_upload_docs(infx_index* ix, uint32_t N, const float* doc_len, float avgdl, const int64_t* doc_key, const uint8_t* deleted,
                          const uint64_t* text_offs, const uint16_t* text) {
     if (!ix || !doc_len || !doc_key) return fail(INFX_EINVAL, "null argument%s");
     if (deleted && (ix->d.docBase != 0 || (ix->d.totalDocs != 0 && ix->d.totalDocs != (int32_t)N)))
         return fail(INFX_EINVAL, "infx_upload_docs: deleted[] is for unsharded indexes; a shard takes the global flags through infx_set_deleted%s");
     HIPCHK(enter_device(ix->cfg.device));
+    ix->firstLive = nullptr;       // a map of other documents is void (infx_set_first_live follows the upload)
     float *dLen = nullptr, *dNorm = nullptr; int64_t* dKey = nullptr; uint64_t* dTO = nullptr; uint16_t* dTx = nullptr;
     HIPCHK(dalloc(ix, &dNorm, N)); HIPCHK(dalloc(ix, &dKey, N)); HIPCHK(dalloc(ix, &dLen, N));
     HIPCHK(hipMemcpy(dLen, doc_len, (size_t)N * 4, hipMemcpyHostToDevice));
@@ -956,6 +981,7 @@ int32_t infx_upload_prefix_docsets(infx_index* ix, uint32_t nsets, const uint64_
 
 int32_t infx_set_shard(infx_index* ix, int32_t rank, int32_t nranks, int32_t doc_base, int32_t total_docs) {
     if (!ix || nranks < 1 || rank < 0 || rank >= nranks) return fail(INFX_EINVAL, "bad shard arguments%s");
+    if (ix->d.totalDocs != total_docs) ix->firstLive = nullptr;
     ix->rank = rank; ix->nranks = nranks; ix->d.docBase = doc_base; ix->d.totalDocs = total_docs;
     return INFX_OK;
 }
@@ -1088,7 +1114,7 @@ void infx_stream_destroy(infx_stream* s) {
     hipSetDevice(s->ix->cfg.device);
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
-                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
+                  s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
                   s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder};
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -1560,6 +1586,10 @@ static int32_t fused_check_queries(infx_index* ix, uint32_t nd, uint32_t nq, con
         if (fq[i].dev >= (int32_t)nd) return fail(INFX_EINVAL, "fused query refers to a missing Stage-1 query%s");
         if (fq[i].wm_count > INFX_MAX_WM_LISTS || (uint64_t)fq[i].wm_off + fq[i].wm_count > nlists) return fail(INFX_ECAPACITY, "too many WordMatcher lists for one query%s");
         if (fq[i].wm_count) anyWm = true;
+        if (fq[i].flags & INFX_FQ_BROWSE) {
+            if (!(fq[i].flags & INFX_FQ_SKIP) || (fq[i].flags & INFX_FQ_UNSUPPORTED)) return fail(INFX_EINVAL, "INFX_FQ_BROWSE goes with INFX_FQ_SKIP: a browse query has no text%s");
+            if (fq[i].max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "a browse query returns at most INFX_FILTER_MAX_ROWS rows (its facets run on them)%s");
+        }
         if (fq[i].flags & INFX_FQ_WMDEV) {
             if (!ix->haveDict) return fail(INFX_EINVAL, "INFX_FQ_WMDEV needs infx_upload_wm_dictionary%s");
             if (fq[i].wm_count) return fail(INFX_EINVAL, "a query takes its WordMatcher lists either from the caller or from the device lookup%s");
@@ -1629,6 +1659,8 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     const uint32_t Dp = pow2_at_least((uint32_t)depth, 8);
     const uint32_t Dall = W > 1 ? pow2_at_least((uint32_t)W * (uint32_t)depth, 8) : 0;
     if (Dall > 8192) return fail(INFX_ECAPACITY, "shards x depth exceeds the in-LDS merge (8192 rows); merge hierarchically%s");
+    s->browseQ.clear();
+    for (uint32_t i = 0; i < nq; i++) if (fq[i].flags & INFX_FQ_BROWSE) s->browseQ.push_back({i, (uint32_t)std::max(fq[i].max_results, 0)});
     GROW(s->dFQ, s->capFQ, (size_t)nq * sizeof(infx_fused_query));
     GROW(s->dFLists, s->capFLists, std::max<size_t>(1, nlists) * sizeof(infx_wm_list));
     GROW(s->dFOwned, s->capFOwned, ((size_t)owned_n + 1) * 4);
@@ -1734,6 +1766,81 @@ static DevCountCols count_columns(const infx_filter_leaf* const* leaves, const u
     return cc;
 }
 
+// The batch's browse queries (s->browseQ; browse.hip.inc): grouped by filter program, all groups answered by one ordered scan of the corpus, which
+// also counts the ncount programs whose NumberOfDocumentsInFilter the batch needs (into s->dQCount — k_filter_count_multi is not launched for such a
+// batch).  filterOf(q) = the program of query q or -1; leavesOf(p) = host leaves of program p.  Enqueued after k_finalize, before k_postfilter.
+#define BRW_MAXG 256u           // groups per k_browse_scan launch: at 256 programs a launch spends ~99 % of its time evaluating, so reading
+                                // the codes again for the next 256 costs nothing measurable, and the per-range counts of a launch stay at 2 MB
+#define BRW_MAXRANGES 2048
+static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& progs, uint32_t ncount, int32_t max_results, bool ties, const std::function<int32_t(uint32_t)>& filterOf,
+                              const std::function<std::pair<const infx_filter_leaf*, uint32_t>(int32_t)>& leavesOf) {
+    infx_index* ix = s->ix;
+    const int32_t n = ix->d.totalDocs;
+    for (int c = 0; c < FILT_MAXCOL; c++) if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    static const bool earlyStop = [] { const char* e = getenv("INFX_BROWSE_EARLY_STOP"); return !(e && e[0] == '0'); }();
+    std::vector<DevBrowseGroup> groups; std::vector<DevBrowseQuery> bq; std::unordered_map<int32_t, uint32_t> groupOf;
+    for (auto& b : s->browseQ) {
+        const int32_t prog = filterOf(b.first);
+        auto it = groupOf.find(prog);
+        if (it == groupOf.end()) { it = groupOf.emplace(prog, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{prog >= 0 ? progs[(size_t)prog] : DevFilter{}, prog, 0u, 0u, 0u}); }
+        const uint32_t rows = std::min<uint32_t>(std::min<uint32_t>(b.second, (uint32_t)max_results), INFX_FILTER_MAX_ROWS);
+        groups[it->second].rows = std::max(groups[it->second].rows, rows);
+        bq.push_back(DevBrowseQuery{b.first, it->second, rows, 0u});
+    }
+    for (uint32_t k = 0; k < ncount; k++) {      // the programs to count: those no browse query uses are groups without rows
+        auto it = groupOf.find((int32_t)k);
+        if (it == groupOf.end()) { it = groupOf.emplace((int32_t)k, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{progs[k], (int32_t)k, 0u, 0u, 0u}); }
+        groups[it->second].flags |= BRW_COUNT; groups[it->second].countIdx = k;
+    }
+    const uint32_t G = (uint32_t)groups.size();
+    const int64_t tiles = ((int64_t)std::max(n, 1) + BRW_THREADS - 1) / BRW_THREADS;
+    const uint32_t nRanges = (uint32_t)std::min<int64_t>(BRW_MAXRANGES, tiles);
+    const bool dup = ix->firstLive != nullptr;
+    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t oBq = al((size_t)G * sizeof(DevBrowseGroup)), blob = oBq + bq.size() * sizeof(DevBrowseQuery);
+    const size_t oPre = al((size_t)G * nRanges * 4), oTot = oPre + oPre, oOwn = oTot + al((size_t)G * 4), oRows = oOwn + al((size_t)G * 4), work = oRows + (size_t)G * INFX_FILTER_MAX_ROWS * 4;
+    GROW(s->dBrwBlob, s->capBrwBlob, blob); GROW(s->dBrwWork, s->capBrwWork, work);
+    std::vector<uint8_t> H(blob, 0);
+    std::memcpy(H.data(), groups.data(), (size_t)G * sizeof(DevBrowseGroup)); std::memcpy(H.data() + oBq, bq.data(), bq.size() * sizeof(DevBrowseQuery));
+    UP(s->dBrwBlob, H.data(), blob);
+    const DevBrowseGroup* dGroups = (const DevBrowseGroup*)s->dBrwBlob; const DevBrowseQuery* dBq = (const DevBrowseQuery*)((char*)s->dBrwBlob + oBq);
+    char* W = (char*)s->dBrwWork;
+    uint32_t *dCnt = (uint32_t*)W, *dPre = (uint32_t*)(W + oPre), *dTot = (uint32_t*)(W + oTot), *dOwn = (uint32_t*)(W + oOwn); int32_t* dRows = (int32_t*)(W + oRows);
+    if (ncount) { GROW(s->dQCount, s->capQCount, (size_t)ncount * 4); HIPCHK(hipMemsetAsync(s->dQCount, 0, (size_t)ncount * 4, s->st)); }
+    if (dup) HIPCHK(hipMemsetAsync(dOwn, 0, (size_t)G * 4, s->st));
+    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+    s->lastBrowseGroups = G; s->lastBrowseLaunches = 0;
+    for (uint32_t g0 = 0; g0 < G; g0 += BRW_MAXG) {
+        const uint32_t g = std::min(BRW_MAXG, G - g0);
+        std::vector<const infx_filter_leaf*> lv; std::vector<uint32_t> nl;
+        for (uint32_t i = 0; i < g; i++) if (groups[g0 + i].prog >= 0) { auto L = leavesOf(groups[g0 + i].prog); lv.push_back(L.first); nl.push_back(L.second); }
+        const DevCountCols cc = count_columns(lv.data(), nl.data(), (uint32_t)lv.size());
+        const size_t lds = ((size_t)g * (dup ? 2 : 1) + (size_t)cc.nUsed * BRW_THREADS * (dup ? 2 : 1)) * 4;
+        if (dup) {
+            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_browse_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            k_browse_scan<true><<<nRanges, BRW_THREADS, lds, s->st>>>(dGroups + g0, g, cc, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, ix->firstLive, earlyStop ? 1 : 0,
+                                                                       dCnt + (size_t)g0 * nRanges, dOwn + g0);
+        } else {
+            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_browse_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            k_browse_scan<false><<<nRanges, BRW_THREADS, lds, s->st>>>(dGroups + g0, g, cc, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, nullptr, earlyStop ? 1 : 0,
+                                                                        dCnt + (size_t)g0 * nRanges, nullptr);
+        }
+        HIPCHK(hipGetLastError());
+        s->lastBrowseLaunches++;
+    }
+    k_browse_prefix<<<G, BRW_THREADS, 0, s->st>>>(dGroups, nRanges, dCnt, dup ? dOwn : nullptr, dPre, dTot, (uint32_t*)s->dQCount);
+    HIPCHK(hipGetLastError());
+    if (!bq.empty()) {
+        k_browse_gather<<<dim3(nRanges, std::min<uint32_t>(G, 32u)), WAVE, 0, s->st>>>(dGroups, G, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, ix->firstLive, dCnt, dPre, dRows);
+        HIPCHK(hipGetLastError());
+        k_browse_rows<<<(uint32_t)bq.size(), WAVE, 0, s->st>>>(dBq, dGroups, dTot, dRows, (const long long*)ix->d.docKeyAll, ix->firstLive, max_results, (long long*)s->dFKeys,
+                                                                  (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr, (int32_t*)s->dFDocs, (uint32_t*)s->dFCounts);
+        HIPCHK(hipGetLastError());
+    }
+    s->lastCountK = ncount; s->lastCountLaunches = 0;      // counted by the scan: no k_filter_count_multi launch
+    return INFX_OK;
+}
+
 // k_finalize over s->dCovC / s->dCovO / s->dFMeta / s->dFS1 -> result rows in s->dFKeys ...
 static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth, int32_t max_results, bool ties) {
     infx_index* ix = s->ix;
@@ -1765,11 +1872,19 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     }
     const uint32_t nfacet = qp ? s->qpNFacet : s->nFacet; const uint32_t* facetCols = qp ? s->qpFacetCols : s->facetCols;
     const uint32_t ncount = qp ? s->qpNCount : 0;
+    // browse queries (empty text + facets): each needs a descriptor that counts facets; their rows come from the ordered scan after k_finalize
+    const bool browse = !s->browseQ.empty();
+    if (browse) {
+        if (!nfacet) { s->browseQ.clear(); return fail(INFX_EINVAL, "a browse query needs facet columns on the stream%s"); }
+        if (qp) for (auto& b : s->browseQ) if (!(s->qpDesc[b.first].flags & QP_FACETS)) { s->browseQ.clear(); return fail(INFX_EINVAL, "a browse query needs INFX_QP_FACETS in its descriptor%s"); }
+        if (!ix->d.docKeyAll) { s->browseQ.clear(); return fail(INFX_EINVAL, "index not uploaded%s"); }
+    }
     if (launchPF || launchPP) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
     DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
     const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr;
+    std::vector<DevFilter> progs;       // the batch's program table (device pointers)
     if (launchPF || launchPP || ncount) {       // the batch's DevPostBatch, program table, boost list and descriptors (+ the packed per-query programs): one upload
-        std::vector<DevFilter> progs; std::vector<DevQBoost> sboost; std::vector<DevQPost> sdesc;
+        std::vector<DevQBoost> sboost; std::vector<DevQPost> sdesc;
         if (!qp) {
             DevQPost D{}; D.filter = -1; D.sortCol = 0;
             if (s->postFilter) { D.filter = (int32_t)progs.size(); progs.push_back(s->postFilter->d); }
@@ -1793,6 +1908,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         for (int c = 0; c < FILT_MAXCOL; c++) pb.rank[c] = ix->colRankOk[c] ? ix->colRank[c] : nullptr;
         pb.keys = (long long*)s->dFKeys; pb.scores = (float*)s->dFScores; pb.ties = ties ? (uint8_t*)s->dFTies : nullptr; pb.docs = (int32_t*)s->dFDocs;
         pb.counts = (uint32_t*)s->dFCounts; pb.flags = (uint32_t*)s->dFFlags; pb.stride = max_results;
+        pb.fqs = browse ? (const infx_fused_query*)s->dFQ : nullptr;
         std::vector<uint8_t> H(total, 0);
         std::memcpy(H.data(), &pb, sizeof pb);
         if (nprog) std::memcpy(H.data() + oProgs, progs.data(), nprog * sizeof(DevFilter));
@@ -1802,7 +1918,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         UP(D, H.data(), total);
         dPB = (const DevPostBatch*)D; dProgs = (const DevFilter*)(D + oProgs);
     }
-    if (ncount) {       // Filter.NumberOfDocumentsInFilter of the expressions this batch uses first, over the whole corpus (every shard holds the whole columns)
+    if (ncount && !browse) {       // Filter.NumberOfDocumentsInFilter of the expressions this batch uses first, over the whole corpus (every shard holds the whole columns)
         GROW(s->dQCount, s->capQCount, (size_t)ncount * 4);
         { int32_t rc_ = count_enqueue(s, dProgs, ncount, s->qpCols, 0, ix->d.totalDocs, (uint32_t*)s->dQCount); if (rc_) return rc_; }
         DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
@@ -1813,6 +1929,16 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
                                                 (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr);
     HIPCHK(hipGetLastError());
+    if (browse) {
+        int32_t rc_;
+        if (qp) rc_ = browse_enqueue(s, progs, ncount, max_results, ties, [&](uint32_t q) { return s->qpDesc[q].filter; },
+                                     [&](int32_t p) { const auto& P = s->qpProgs[(size_t)p]; return std::make_pair((const infx_filter_leaf*)(s->qpCode.data() + P.leavesOff), P.nleaves); });
+        else rc_ = browse_enqueue(s, progs, 0, max_results, ties, [&](uint32_t) { return s->postFilter ? 0 : -1; },
+                                  [&](int32_t) { return std::make_pair((const infx_filter_leaf*)s->postFilter->hLeaves.data(), (uint32_t)s->postFilter->hLeaves.size()); });
+        s->browseQ.clear();
+        if (rc_) return rc_;
+        if (ncount) DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
+    }
     s->facetNq = 0;
     if (launchPF) {     // ResultProcessor.ApplyFilter + FacetBuilder on the rows just produced, before they leave the device
         const size_t fe = (size_t)nq * std::max<uint32_t>(1, nfacet) * INFX_FILTER_MAX_ROWS;
@@ -2484,6 +2610,45 @@ int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_pr
     const int32_t base = whole_corpus ? 0 : ix->d.docBase, n = whole_corpus ? ix->d.totalDocs : ix->d.N;
     { int32_t rc_ = count_enqueue(s, (const DevFilter*)D, k, cc, base, n, (uint32_t*)s->dQCount); if (rc_) return rc_; }
     DOWN(counts, s->dQCount, (size_t)k * 4);
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_browse_stats(infx_stream* s, uint32_t* groups, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (groups) *groups = s->lastBrowseGroups;
+    if (launches) *launches = s->lastBrowseLaunches;
+    return INFX_OK;
+}
+// FacetBuilder.BuildFacetsFromAllDocuments: counts_out = for each of the ncol columns in turn, one count per distinct value (the column's num_values)
+int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uint32_t* counts_out) {
+    if (!s || ncol > INFX_MAX_FACET_COLS || (ncol && (!cols || !counts_out))) return fail(INFX_EINVAL, "bad facet arguments%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    if (!ncol) return INFX_OK;
+    const int32_t n = ix->d.totalDocs;
+    DevFacetAll F{}; size_t total = 0; uint32_t ldsWords = 0;
+    for (uint32_t c = 0; c < ncol; c++) {
+        if (cols[c] >= FILT_MAXCOL || !ix->colCodes[cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
+        if ((uint64_t)ix->colDocs[cols[c]] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        total += ix->colValues[cols[c]];
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    GROW(s->dFacAll, s->capFacAll, std::max<size_t>(total, 1) * 4);
+    HIPCHK(hipMemsetAsync(s->dFacAll, 0, std::max<size_t>(total, 1) * 4, s->st));
+    size_t o = 0;
+    for (uint32_t c = 0; c < ncol; c++) {
+        const uint32_t nv = ix->colValues[cols[c]];
+        F.codes[c] = ix->colCodes[cols[c]]; F.out[c] = (uint32_t*)s->dFacAll + o; F.nvals[c] = nv; o += nv;
+        // LDS counters for the small dictionaries, within 64 KiB per workgroup in all (two workgroups per CU stay resident)
+        if (nv <= FALL_LDS_VALUES && ldsWords + nv <= 16384u) { F.ldsOff[c] = ldsWords; ldsWords += nv; } else F.ldsOff[c] = 0xFFFFFFFFu;
+    }
+    if (n > 0) {
+        const int grid = (int)std::min<int64_t>(2048, ((int64_t)n + FALL_THREADS - 1) / FALL_THREADS);
+        k_facets_all<<<grid, FALL_THREADS, (size_t)ldsWords * 4, s->st>>>(F, (int)ncol, ldsWords, n, ix->d.deleted);
+        HIPCHK(hipGetLastError());
+    }
+    if (total) DOWN(counts_out, s->dFacAll, total * 4);
     SYNC();
     return INFX_OK;
 }

@@ -36,6 +36,7 @@ __global__ __launch_bounds__(WAVE) void k_postproc(const DevPostBatch* __restric
     const DevQPost* __restrict__ D = pb->desc + (size_t)q * pb->descStride;
     const uint32_t nboost = D->nboost, flags = D->flags;
     if (!nboost && !(flags & QP_SORT)) return;                                  // nothing to do: the rows pass through, whatever their number
+    if (pb->fqs && (pb->fqs[q].flags & INFX_FQ_BROWSE)) return;                 // browse rows: HandleEmptyQueryWithFacets returns before ApplyPostProcessing
     if (pb->counts[q] > (uint32_t)WAVE) {                                       // more rows than one wave holds: the query is rejected (empty, flag bit 4)
         if (lane == 0) { pb->counts[q] = 0; pb->flags[q] |= QP_REJECTED; }
         return;

@@ -235,6 +235,14 @@ class SearchEngine:
         self._check(self.L.infx_engine_delete_documents(self.h, _p(k, C.c_int64), C.c_int64(len(k)), C.byref(marked)))
         return int(marked.value)
 
+    def delete_document_ids(self, ids) -> int:
+        """Document.Deleted = true on single documents by internal id (indexing order), e.g. one of several documents of a key; returns how many were
+        newly marked.  Exclusive: no search may be in flight."""
+        k = np.ascontiguousarray(list(ids) if not isinstance(ids, np.ndarray) else ids, np.int64)
+        marked = C.c_int64(0)
+        self._check(self.L.infx_engine_delete_document_ids(self.h, _p(k, C.c_int64), C.c_int64(len(k)), C.byref(marked)))
+        return int(marked.value)
+
     def shard_info(self):
         """(first internal id, number of documents) of the doc range this engine's GPU holds (the whole corpus when unsharded)."""
         b = C.c_int32(0); n = C.c_int32(0)
@@ -278,6 +286,12 @@ class SearchEngine:
                     vals.append((vb.value.decode(), int(cnts[j])))
                 facets[nb.value.decode()] = vals
         return facets
+
+    def facets_of_all_documents(self, session=None):
+        """FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): {field: [(value, count)]} over every document that is not Deleted
+        (per document, not per key), for every facetable column, counted in one device pass; (count desc, value asc), at most 100 values per field,
+        null / empty values left out, fields without a value absent."""
+        return _facets_all(self, session.h if session is not None else self._default_session())
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -339,6 +353,12 @@ class SearchEngine:
     def last_count_stats(self, session=None):
         """(expressions the session's last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
         return _count_stats(self, session.h if session is not None else self._default_session())
+
+    def last_browse_stats(self, session=None):
+        """(groups — distinct filter programs, counted ones included —, k_browse_scan launches) of the session's last batch that had a browse query."""
+        g = C.c_uint32(0); n = C.c_uint32(0)
+        self._check(self.L.infx_engine_last_browse_stats(session.h if session is not None else self._default_session(), C.byref(g), C.byref(n)))
+        return int(g.value), int(n.value)
 
     def set_filter_cache_limit(self, n: int):
         """Bound of the engine's filter cache (compiled expressions + their counts), least recently used first."""
@@ -528,6 +548,10 @@ class Session:
         """SearchEngine.search_queries on this session."""
         return self.engine.search_queries(queries, session=self)
 
+    def facets_of_all_documents(self):
+        """SearchEngine.facets_of_all_documents on this session."""
+        return _facets_all(self.engine, self.h)
+
     def last_count_stats(self):
         """(expressions the last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
         return _count_stats(self.engine, self.h)
@@ -617,6 +641,25 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
         facets = engine.facets_of(sh, n, j) if q.enable_facets and err is None else None
         out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]), err))
     return out
+
+
+def _facets_all(engine, sh):
+    ncols = C.c_int32(0)
+    engine._check(engine.L.infx_engine_facets_all(sh, C.byref(ncols)))
+    facets = {}
+    for k in range(int(ncols.value)):
+        col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
+        m = engine.L.infx_engine_facets_all_column(sh, k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
+        if m < 0:
+            engine._check(1)
+        if m > 0:
+            nb = C.create_string_buffer(256); engine.L.infx_engine_column_info(engine.h, col.value, nb, 256, None, None)
+            vals = []
+            for j in range(m):
+                vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col.value, int(codes[j]), vb, 1024)
+                vals.append((vb.value.decode(), int(cnts[j])))
+            facets[nb.value.decode()] = vals
+    return facets
 
 
 def _count_stats(engine, sh):

@@ -688,6 +688,11 @@ class ShardedSearcher:
     def last_facets(self, i):
         return self.last.facets(i)
 
+    def facets_of_all_documents(self):
+        """SearchEngine.facets_of_all_documents: every rank holds the whole columns and the global Deleted flags, so each counts the whole corpus on its
+        own GPU and gets the same result — nothing is exchanged."""
+        return self.sessions[0].s.facets_of_all_documents()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
