@@ -294,6 +294,36 @@ int32_t infx_engine_last_in_filter(infx_session* s, uint32_t nq, uint32_t* out);
 int32_t infx_engine_last_count_stats(infx_session* s, uint32_t* counted, uint32_t* launches);
 /* the message of query qi's rejection in the last infx_engine_set_query_options ("" if it was accepted); returns its length, -1 out of range */
 int32_t infx_engine_query_error(infx_session* s, uint32_t qi, char* out, int32_t cap);
+/* ---- CoverageSetup (Coverage/CoverageSetup.cs): the Stage-2 settings, engine-wide and per query ---------------------------------------------------
+ * infx_coverage_setup carries the 17 settable members (CoverageDepth is never read by the reference: Query.CoverageDepth is used instead).
+ * ENGINE-WIDE (SearchEngine's coverageSetup: argument, SearchEngine.cs:51,64-67,74) — infx_engine_set_coverage_setup; NULL = CoverageSetup's defaults.  It feeds
+ *   - the matchers (CoverageEngine._setup): min_word_size, the five cover_* switches, num_typos (above 2 behaves as 2), min_length_one_typo,
+ *     min_length_two_typos, levenshtein_max_word_size;
+ *   - the WordMatcher lookup: cover_prefix_suffix off = no affix matches (WordMatcherLookup.cs:51);
+ *   - the defaults of the pipeline-level members below.
+ *   Nothing built at index time depends on it, so the call is legal before or after infx_engine_index_documents and between batches (not while a search is
+ *   in flight; on a sharded engine every rank makes the same call; plans prefetched for a coming batch keep the tokens they were made with).
+ * PER QUERY (Query.CoverageSetup, `q.CoverageSetup ?? _coverageSetup`, SearchEngine.cs:300) — infx_engine_set_query_coverage installs the setups of the session's
+ *   NEXT search of nq queries (setups[i] == NULL: the engine-wide setup), consumed by that search like infx_engine_set_query_options and usable with or without
+ *   it, on every path it supports.  As in the reference a per-query setup replaces only what SearchPipeline itself reads — truncate, coverage_min_word_hits_abs,
+ *   coverage_min_word_hits_relative, truncation_score, coverage_q_limit_for_error_tolerance, coverage_lcs_error_tolerance_relativeq; its matcher members are
+ *   IGNORED: the matchers and the WordMatcher lookup keep the engine's object (quirk Q19).
+ * Validation: integers outside [0, 65535], truncation_score outside [0, 255], a non-finite or negative relativeq -> INFX_EINVAL (per query: that query is
+ * rejected on its own, see below).  enable_lexical_prescreen (LexicalPrescreen.cs) is not implemented: engine-wide it is refused with INFX_EUNSUPPORTED; a query
+ * with it is rejected on its own like a MATCHES filter — empty result, result flag bit 4, its status in out_status[i], its message from infx_engine_query_error,
+ * neighbours unaffected.  With coverage off (CreateMinimal engine, EnableCoverage = false) a setup has no effect. */
+typedef struct infx_coverage_setup {
+    int32_t min_word_size, levenshtein_max_word_size, num_typos, min_length_one_typo, min_length_two_typos;        /* 2, 20, 2, 3, 7 */
+    int32_t coverage_min_word_hits_abs, coverage_min_word_hits_relative, coverage_q_limit_for_error_tolerance;       /* 1, 0, 5 */
+    double  coverage_lcs_error_tolerance_relativeq;                                                                   /* 0.2 */
+    int32_t cover_whole_query, cover_whole_words, cover_fuzzy_words, cover_joined_words, cover_prefix_suffix;        /* 1 each */
+    int32_t truncate, enable_lexical_prescreen, truncation_score;                                                    /* 1, 0, 254 */
+} infx_coverage_setup;
+int32_t infx_coverage_setup_default(infx_coverage_setup* out);
+int32_t infx_sizeof_coverage_setup(void);
+int32_t infx_engine_set_coverage_setup(infx_engine* e, const infx_coverage_setup* setup /* NULL = defaults */);
+int32_t infx_engine_get_coverage_setup(infx_engine* e, infx_coverage_setup* out);
+int32_t infx_engine_set_query_coverage(infx_session* s, uint32_t nq, const infx_coverage_setup* const* setups, int32_t* out_status /* nq, may be NULL */);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

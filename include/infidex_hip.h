@@ -236,6 +236,24 @@ typedef struct infx_cov_out {
 /* Long queries of the NEXT Stage-2 call on this stream (infx_stage2_batch, infx_search_fused, infx_shard_stage2): n records, referred to by
  * infx_cov_query.reserved = 1 + index.  The table is consumed by that call; n = 0 clears it. */
 int32_t infx_stage2_long_queries(infx_stream* s, uint32_t n, const infx_cov_query_long* q);
+/* CoverageSetup (Coverage/CoverageSetup.cs) on the device.  infx_stage2_setup: the ENGINE-WIDE matcher settings — CoverageEngine._setup, CoverageEngine.cs:71,269,
+ * 323-341,378 and FuzzyWordMatcher.cs:14-144; min_word_size is also minStemLength of the fusion signals; cover_prefix_suffix off also means that k_wm looks up
+ * no affix matches (WordMatcherLookup.cs:51).  Values in [0, 65535]; num_typos above 2 behaves as 2 (the reference's formula never asks for more).
+ * infx_finalize_setup: what ResultProcessor.CalculateTruncationIndex (ResultProcessor.cs:151-171) and SearchPipeline.cs:425,433 read, one record PER QUERY.
+ * infx_stream_set_coverage hands both to the stream: `matchers` (NULL = CoverageSetup's defaults) to the NEXT Stage-2 call (infx_stage2_batch, infx_search_fused,
+ * infx_shard_stage2, infx_wm_lookup_debug), `per_query` (nq records, NULL = the defaults for every query) to the NEXT finalize (infx_search_fused,
+ * infx_shard_finalize); each consumes its part, and a call replaces whatever an earlier one left.  Matcher settings that differ from the defaults run the
+ * "custom setup" instantiations of k_stage2 (the settings as kernel arguments; six more kernels); the defaults keep the instantiations in which they are compile-time constants. */
+typedef struct infx_stage2_setup {
+    int32_t min_word_size, lev_max_word_size, num_typos, min_len_one_typo, min_len_two_typos;                       /* 2, 20, 2, 3, 7 */
+    int32_t cover_whole_query, cover_whole_words, cover_fuzzy_words, cover_joined_words, cover_prefix_suffix;        /* 1 each */
+} infx_stage2_setup;
+typedef struct infx_finalize_setup {
+    int32_t truncate;                                 /* Truncate: 1 */
+    int32_t min_hits_abs, min_hits_relative;          /* CoverageMinWordHitsAbs 1, CoverageMinWordHitsRelative 0 */
+    int32_t truncation_score;                         /* TruncationScore 254, in [0, 255] */
+} infx_finalize_setup;
+int32_t infx_stream_set_coverage(infx_stream* s, const infx_stage2_setup* matchers, uint32_t nq, const infx_finalize_setup* per_query);
 int32_t infx_stage2_batch(infx_stream* s, uint32_t nq, const infx_cov_query* q, uint32_t ncand,
                           const infx_cov_cand* cand, infx_cov_out* out, int32_t* feat_out);
 

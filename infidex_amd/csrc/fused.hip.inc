@@ -316,7 +316,7 @@ __global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx
                                                           const infx_hit* __restrict__ s1, int depth, int Cp, int maxResults,
                                                           long long* __restrict__ outKeys, float* __restrict__ outScores, uint8_t* __restrict__ outTies,
                                                           uint32_t* __restrict__ outCounts, uint32_t* __restrict__ outFlags, uint32_t* __restrict__ errFlag,
-                                                          int32_t* __restrict__ outDocs) {
+                                                          int32_t* __restrict__ outDocs, const infx_finalize_setup* __restrict__ fins) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     long long* sKey = (long long*)smem;
     uint32_t* sBits = (uint32_t*)(sKey + Cp);
@@ -383,7 +383,9 @@ __global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx
             __syncthreads();
             ncons = wg_scan_flags(sFlag, sPos, nf, part, tid, P2_THREADS);
             // CalculateTruncationIndex: last consolidated row that has enough word hits / an LCS / a near-perfect score
-            const int minHits = max(1, maxWordHits);
+            const infx_finalize_setup FS = fins[qi];      // Truncate, CoverageMinWordHitsAbs / Relative, TruncationScore of this query (ResultProcessor.cs:151-171)
+            const int minHits = max(FS.min_hits_abs, maxWordHits - FS.min_hits_relative);
+            const float truncScore = (float)FS.truncation_score;
             const long long k0 = M.idx0 >= 0 ? ix.docKeyAll[M.idx0] : (long long)0x8000000000000000ull;
             const long long k1 = M.idx1 >= 0 ? ix.docKeyAll[M.idx1] : (long long)0x8000000000000000ull;
             int myTr = -1;
@@ -391,11 +393,11 @@ __global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx
                 const uint16_t s = sIdx[i]; int wh = 0, lc = 0;
                 if (M.idx0 >= 0 && sKey[s] == k0) { wh = hits0; lc = lcs0; }
                 else if (M.idx1 >= 0 && sKey[s] == k1) { wh = hits1; lc = lcs1; }
-                if (wh >= minHits || lc > 0 || __uint_as_float(sBits[s]) >= 254.f) myTr = max(myTr, (int)sPos[i]);
+                if (wh >= minHits || lc > 0 || __uint_as_float(sBits[s]) >= truncScore) myTr = max(myTr, (int)sPos[i]);
             }
             if (myTr >= 0) atomicMax(&shTrunc, myTr);
             __syncthreads();
-            const int truncIdx = shTrunc;
+            const int truncIdx = FS.truncate ? shTrunc : -1;      // !Truncate: the full MaxNumberOfRecordsToReturn rows (SearchPipeline.cs:425,433)
             const int resultCount = truncIdx == -1 ? mr : min(truncIdx + 1, mr);
             ncons = min(ncons, (uint32_t)max(0, resultCount));
             if (ncons > 0) {

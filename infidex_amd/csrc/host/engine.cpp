@@ -68,7 +68,15 @@ struct QueryOpts {
     std::vector<std::string> pinned;           // cache entries the batch holds (filters and boosts)
     std::vector<std::string> countExprs; std::vector<uint32_t> counts;      // expressions the batch counts first (programs [0, n) of its table) + the device's counts
 };
+// Per-query CoverageSetup of the session's next batch (infx_engine_set_query_coverage): consumed by that batch like QueryOpts, with or without them.
+// fin / qLimit / relativeq: the six members SearchPipeline reads, already resolved against the engine-wide setup for a query without one of its own.
+struct QueryCov {
+    bool on = false, bound = false; uint32_t nq = 0;
+    std::vector<infx_finalize_setup> fin; std::vector<int32_t> qLimit; std::vector<double> relativeq;
+    std::vector<uint8_t> reject; std::vector<int32_t> status; std::vector<std::string> err;
+};
 struct infx_session {
+    QueryCov qc;
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
     QueryOpts qo;
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
@@ -128,6 +136,11 @@ static inline bool qo_cov(const infx_session* S, size_t i, bool cov) { return co
 static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results);
 static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static void clear_query_options(infx_session* S);
+static int32_t query_cov_check(infx_session* S, uint32_t nq);
+static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
+static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len);
+static inline infx_finalize_setup qc_finalize(const infx_session* S, size_t i);
 // Order of the collectives of a rank's pipeline sessions.  Every session has a communicator and a HIP stream of its own, and its host thread enqueues the
 // collectives of its batch when it gets there — left alone, the relative order of DIFFERENT communicators' kernels on a device depends on thread timing and
 // differs from rank to rank, the classic multi-communicator hang (two collective kernels each holding the CUs the other's peer needs).  The ring makes the
@@ -189,6 +202,7 @@ struct infx_engine {
             filters.erase(f); it = filterLru.erase(it);
         }
     }
+    infx_coverage_setup cs = {2, 20, 2, 3, 7, 1, 0, 5, 0.2, 1, 1, 1, 1, 1, 1, 0, 254};      // the engine-wide CoverageSetup (infx_engine_set_coverage_setup)
     HostIndex ix;
     PlanGate gate;
     CollSeq collSeq;
@@ -793,7 +807,7 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
             if (dbg) nsMerge += since(tA);
             auto tB = tick();
             // ---- ExecuteCoverageStage preparation ----
-            wm_collect(ix, st, true, wm);
+            wm_collect(ix, st, ix.cfg.coverPrefixSuffix, wm);
             Sq.wmAny = wm.any;
             if (dbg) nsWm += since(tB);
             auto tC = tick();
@@ -816,6 +830,7 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
             if (dbg) { long long d = since(tC); nsSel += d; long long cur = nsSelMax.load(); while (d > cur && !nsSelMax.compare_exchange_weak(cur, d)) {} }
             auto tD = tick();
             covErr[i] = prepare_cov_any(ix, st, covQ[i], covL[i]);
+            if (!covErr[i]) { if (covL[i]) covL[i]->lcs_tolerance = qc_tolerance(S, (size_t)i, covL[i]->text_len); else covQ[i].lcs_tolerance = qc_tolerance(S, (size_t)i, covQ[i].text_len); }
             if (dbg) nsCovQ += since(tD);
             if (covErr[i]) continue;
             auto tE = tick();
@@ -870,6 +885,7 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
         S->s2Candidates = cands.size();
         if (!cands.empty()) {
             int32_t rc = covBatchL.empty() ? INFX_OK : infx_stage2_long_queries(S->stream, (uint32_t)covBatchL.size(), covBatchL.data());
+            if (!rc) rc = stage_coverage_setup(S, nq, false);
             if (!rc) rc = infx_stage2_batch(S->stream, (uint32_t)covBatch.size(), covBatch.data(), (uint32_t)cands.size(), cands.data(), outs.data(), wantF ? S->lastFeat.data() : nullptr);
             if (rc) { g_eerr = infx_last_error(); return rc; }
             infx_last_timings(S->stream, nullptr, nullptr, &S->msCov);
@@ -888,6 +904,7 @@ static int32_t ph_stage2(infx_engine* e, infx_session* S, int W, const infx_hit*
         if (wantF) lfeat.assign(local.size() * INFX_NFEAT, 0);
         if (!local.empty()) {
             int32_t rc = covBatchL.empty() ? INFX_OK : infx_stage2_long_queries(S->stream, (uint32_t)covBatchL.size(), covBatchL.data());
+            if (!rc) rc = stage_coverage_setup(S, nq, false);
             if (!rc) rc = infx_stage2_batch(S->stream, (uint32_t)covBatch.size(), covBatch.data(), (uint32_t)local.size(), local.data(), lout.data(), wantF ? lfeat.data() : nullptr);
             if (rc) { g_eerr = infx_last_error(); return rc; }
             infx_last_timings(S->stream, nullptr, nullptr, &S->msCov);
@@ -937,13 +954,14 @@ static int32_t ph_finalize(infx_engine* e, infx_session* S, const infx_cov_out* 
                     std::unordered_map<int64_t, char> seen; seen.reserve(fin.size() * 2);
                     for (auto& x : fin) if (seen.emplace(x.key, 1).second) cons.push_back(x);
                     int truncIdx = -1;
-                    int minHits = std::max(1, maxWordHits - 0);
+                    const infx_finalize_setup FS = qc_finalize(S, (size_t)i);      // the values k_finalize reads from its per-query record
+                    int minHits = std::max(FS.min_hits_abs, maxWordHits - FS.min_hits_relative);
                     int64_t k0 = Sq.idx0 >= 0 ? ix.docKey[Sq.idx0] : INT64_MIN, k1 = Sq.idx1 >= 0 ? ix.docKey[Sq.idx1] : INT64_MIN;
-                    for (int r = (int)cons.size() - 1; r >= 0; r--) {
+                    for (int r = (int)cons.size() - 1; r >= 0 && FS.truncate; r--) {
                         uint8_t wh = 0, lc = 0;
                         if (Sq.idx0 >= 0 && cons[r].key == k0) { wh = hits01[0]; lc = lcs01[0]; }
                         else if (Sq.idx1 >= 0 && cons[r].key == k1) { wh = hits01[1]; lc = lcs01[1]; }
-                        if (wh >= minHits || lc > 0 || cons[r].score >= 254.f) { truncIdx = r; break; }
+                        if (wh >= minHits || lc > 0 || cons[r].score >= (float)FS.truncation_score) { truncIdx = r; break; }
                     }
                     int resultCount = truncIdx == -1 ? max_results : std::min(std::max(0, truncIdx) + 1, max_results);
                     if ((int)cons.size() > resultCount) cons.resize(resultCount);
@@ -982,7 +1000,7 @@ static void wm_descriptors(const HostIndex& ix, const ustr& st, WmResult& wm, st
     const int32_t* exB = ix.wmExact.doc.data(); const int32_t* exE = exB + ix.wmExact.doc.size();
     const int32_t* l1B = ix.wmLd1.doc.data(); const int32_t* l1E = l1B + ix.wmLd1.doc.size();
     lists.clear(); owned.clear();
-    wm_collect(ix, st, true, wm);
+    wm_collect(ix, st, ix.cfg.coverPrefixSuffix, wm);
     for (auto& l : wm.lists) {
         if (!l.n) continue;
         infx_wm_list L{}; L.len = (uint32_t)l.n;
@@ -1065,6 +1083,8 @@ static int32_t build_fused_inputs(infx_engine* e, infx_session* S, int32_t max_r
                 else if (!covErr[i] && pp->rec) { if (const char* why = parse_cov_record(st, pp->rec, pp->recLen, pp->covOff, cq[i])) badRec.store(why); }
                 else if (!covErr[i]) cq[i] = pp->own->cq;
             } else covErr[i] = prepare_cov_any(ix, st, cq[i], qLong[i]);
+            // the LCS tolerance follows the QUERY's CoverageSetup (SearchPipeline.cs:498-499), whoever prepared the record: this rank, or the slice's owner in the plan exchange
+            if (!covErr[i]) { if (qLong[i]) qLong[i]->lcs_tolerance = qc_tolerance(S, (size_t)i, qLong[i]->text_len); else cq[i].lcs_tolerance = qc_tolerance(S, (size_t)i, cq[i].text_len); }
             if (devWm && !covErr[i] && !qLong[i] && wm_on_device(ix, st)) { F.flags |= INFX_FQ_WMDEV; nDev++; continue; }      // k_wm resolves the words of cq[i] (lookup.hip.inc; fast-envelope queries)
             auto pre = S->wmPre.find(st);            // computed by a peer rank (sharded planning): same index, same text, same descriptors
             if (pre != S->wmPre.end()) { qLists[i] = pre->second.lists; qOwned[i] = pre->second.owned; }
@@ -1133,6 +1153,7 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     B.t2 = now_ms();
     const bool dbg = e->cfg.want_features != 0;
     rc = stage_long_queries(S, FI); if (rc) return rc;
+    rc = stage_coverage_setup(S, nq, true); if (rc) return rc;
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
@@ -1189,9 +1210,10 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
                                  int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                  uint32_t* out_counts, uint32_t* out_flags) {
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, nq, max_results); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (rc) return rc; }
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
+    query_cov_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     return rc ? rc : rc2;
 }
 static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
@@ -1248,8 +1270,9 @@ int32_t infx_session_phase0(infx_session* S, uint32_t nq, const uint16_t* q_aren
     // the exact cut across shards falls back to a chained sequential replay whose exchanged state is laid out for max_depth entries (infx_shard_replay_chain)
     if (S->e && S->e->nranks > 1 && depth != S->e->ix.cfg.maxDepth) return efail(INFX_EINVAL, "document shards search with CoverageDepth == the engine's max_depth");
     if (S->qo.on && S->qo.bound) clear_query_options(S);        // left by a sharded batch that failed between its phase 0 and phase 4
-    { int32_t rc = query_options_check(S, nq, 0); if (rc) return rc; }
-    S->qo.bound = S->qo.on;
+    if (S->qc.on && S->qc.bound) S->qc = QueryCov();
+    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (rc) return rc; }
+    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on;
     PlanGateHold hold(S->e->gate);
     int32_t rc = ph_plan(S->e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     if (nunions) *nunions = (uint32_t)S->batch->pending.size();
@@ -1721,7 +1744,7 @@ int32_t infx_session_coll_stats(infx_session* S, uint64_t* out4) {      // all-r
 }
 int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits, const uint32_t* all_counts, int32_t max_results, int32_t enable_coverage, uint64_t* ncand) {
     if (!S || W < 1 || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (rc) return rc; }
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
     if (hostPhases) {
         int32_t rc = ph_stage2(S->e, S, W, all_hits, all_counts, max_results, enable_coverage); if (rc) return rc;
@@ -1736,6 +1759,7 @@ int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits
     S->lastOuts.assign((size_t)B.nq * 2 * B.depth, infx_cov_out{});
     if (B.nq) {
         rc = stage_long_queries(S, FI); if (rc) return rc;
+        rc = stage_coverage_setup(S, B.nq, true); if (rc) return rc;
         rc = infx_shard_stage2(S->stream, W, B.nd, all_hits, all_counts, B.nq, FI.fq.data(), FI.cq.data(), (uint32_t)FI.lists.size(), FI.lists.data(),
                                (uint32_t)FI.owned.size(), FI.owned.data(), B.depth, max_results, 0, S->lastOuts.data());
         if (rc) { g_eerr = infx_last_error(); return rc; }
@@ -1765,7 +1789,7 @@ int32_t infx_session_phase2x(infx_session* S, const uint32_t* global_counts, voi
 }
 int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, const void* all_counts, int32_t max_results, int32_t enable_coverage, void* outs) {
     if (!S || W < 1 || max_results < 1 || !outs) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (rc) return rc; }
     infx_engine* e = S->e; Batch& B = *S->batch;
     B.maxResults = max_results;
     std::shared_ptr<FusedIn> FIp; int32_t rc = fused_inputs_for_phase3(e, S, max_results, enable_coverage, FIp); if (rc) return rc;
@@ -1773,6 +1797,7 @@ int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, c
     B.t3 = now_ms();
     if (B.nq) {
         rc = stage_long_queries(S, FI); if (rc) return rc;
+        rc = stage_coverage_setup(S, B.nq, true); if (rc) return rc;
         rc = infx_shard_stage2(S->stream, W, B.nd, (const infx_hit*)all_hits, (const uint32_t*)all_counts, B.nq, FI.fq.data(), FI.cq.data(), (uint32_t)FI.lists.size(), FI.lists.data(),
                                (uint32_t)FI.owned.size(), FI.owned.data(), B.depth, max_results, 0, (infx_cov_out*)outs);
         if (rc) { g_eerr = infx_last_error(); return rc; }
@@ -1793,13 +1818,16 @@ int32_t infx_session_phase4(infx_session* S, const int32_t* merged_outs3, int64_
     if (hostPhases) {
         int32_t rc = ph_finalize(S->e, S, (const infx_cov_out*)merged_outs3, out_keys, out_scores, out_ties, out_counts, out_flags);
         const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK);
+        query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
         return rc ? rc : rc2;
     }
     Batch& B = *S->batch;
     if (B.nq) {
         int32_t rc = infx_shard_finalize(S->stream, B.nq, (const infx_cov_out*)merged_outs3, B.depth, B.maxResults, out_keys, out_scores, out_ties, out_counts, out_flags);
-        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); return rc; }
-        rc = query_options_finish(S, out_counts, out_flags, true); if (rc) return rc;
+        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); return rc; }
+        rc = query_options_finish(S, out_counts, out_flags, true);
+        query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
+        if (rc) return rc;
         float ms5[5] = {0, 0, 0, 0, 0}; infx_last_fused_timings(S->stream, ms5); S->msFin = ms5[4];
     }
     double t5 = now_ms();
@@ -1911,7 +1939,7 @@ int32_t infx_engine_host_plan_profile(infx_engine* e, uint32_t nq, const uint16_
     for (uint32_t i = 0; i < nq; i++) plan_finish(ix, plans[i]);
     auto t3 = std::chrono::steady_clock::now();
     WmResult wm; size_t sink = 0;
-    for (uint32_t i = 0; i < nq; i++) { const QueryPlan& P = plans[i]; if (P.blank || P.unsupported) continue; wm_collect(ix, P.searchText, true, wm); sink += wm.lists.size(); }
+    for (uint32_t i = 0; i < nq; i++) { const QueryPlan& P = plans[i]; if (P.blank || P.unsupported) continue; wm_collect(ix, P.searchText, ix.cfg.coverPrefixSuffix, wm); sink += wm.lists.size(); }
     auto t4 = std::chrono::steady_clock::now();
     infx_cov_query cq;
     for (uint32_t i = 0; i < nq; i++) { const QueryPlan& P = plans[i]; if (P.blank || P.unsupported) continue; sink += (size_t)prepare_cov_query(ix, P.searchText, cq); }
@@ -1946,7 +1974,7 @@ int32_t infx_engine_host_plan_profile(infx_engine* e, uint32_t nq, const uint16_
 int64_t infx_engine_wordmatcher(infx_engine* e, const uint16_t* q, int32_t len, int32_t* out, int64_t cap) {
     if (!e || len < 0 || (len && !q) || (cap > 0 && !out)) return -1;
     WmResult wm; ustr t = normalize(uview((const u16*)q, len)); lower_inplace(t);
-    wm_collect(e->ix, t, true, wm);
+    wm_collect(e->ix, t, e->ix.cfg.coverPrefixSuffix, wm);
     std::vector<int32_t> all;
     for (auto& l : wm.lists) all.insert(all.end(), l.p, l.p + l.n);
     std::sort(all.begin(), all.end()); all.erase(std::unique(all.begin(), all.end()), all.end());
@@ -1980,7 +2008,8 @@ int64_t infx_engine_wordmatcher_device(infx_engine* e, const uint16_t* q, int32_
     infx_cov_query cq; if (prepare_cov_query(ix, st, cq)) { g_eerr = "query exceeds the Stage-2 envelope"; return -2; }
     size_t words = 0; for_each_word(st, [&](int, int l) { if (l >= 2) words++; });
     std::vector<infx_wm_list> lists(INFX_MAX_WM_LISTS); std::vector<int32_t> owned(words * 4096 + 1); uint32_t nl = 0;
-    int32_t rc = infx_wm_lookup_debug(e->def->stream, &cq, lists.data(), &nl, owned.data(), (uint64_t)words * 4096);
+    int32_t rc = stage_coverage_setup(e->def, 0, false);      // (CoverPrefixSuffix off: no affix walk)
+    if (!rc) rc = infx_wm_lookup_debug(e->def->stream, &cq, lists.data(), &nl, owned.data(), (uint64_t)words * 4096);
     if (rc) { g_eerr = infx_last_error(); return -1; }
     std::vector<int32_t> all;
     for (uint32_t l = 0; l < nl; l++) {
@@ -2548,6 +2577,7 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     if (rc) { g_eerr = infx_last_error(); pin_filters(e, Q.pinned, -1); return rc; }
     S->facetCols = facetCols;
     S->lastErr = Q.err;
+    if (S->qc.on && S->qc.nq == nq) for (uint32_t i = 0; i < nq; i++) if (S->qc.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = S->qc.err[i];
     Q.on = true;
     S->qo = std::move(Q);
     if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = S->qo.status[i];
@@ -2618,6 +2648,102 @@ int32_t infx_engine_query_error(infx_session* S, uint32_t qi, char* out, int32_t
     if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
     return (int32_t)t.size();
 }
+// ---- CoverageSetup: engine-wide (SearchEngine's coverageSetup: argument) and per query (Query.CoverageSetup) -----------------------------------------
+static const infx_coverage_setup COVERAGE_SETUP_DEFAULT = {2, 20, 2, 3, 7, 1, 0, 5, 0.2, 1, 1, 1, 1, 1, 1, 0, 254};
+// nullptr = acceptable; else what is wrong.  *status: INFX_EINVAL, or INFX_EUNSUPPORTED for the lexical pre-screen.
+static const char* coverage_setup_problem(const infx_coverage_setup& c, int32_t* status) {
+    *status = INFX_EINVAL;
+    const int32_t ints[8] = {c.min_word_size, c.levenshtein_max_word_size, c.num_typos, c.min_length_one_typo, c.min_length_two_typos,
+                             c.coverage_min_word_hits_abs, c.coverage_min_word_hits_relative, c.coverage_q_limit_for_error_tolerance};
+    for (int32_t v : ints) if (v < 0 || v > 65535) return "CoverageSetup: an integer member lies outside [0, 65535]";
+    if (c.truncation_score < 0 || c.truncation_score > 255) return "CoverageSetup: TruncationScore lies outside [0, 255]";
+    if (!std::isfinite(c.coverage_lcs_error_tolerance_relativeq) || c.coverage_lcs_error_tolerance_relativeq < 0.0) return "CoverageSetup: CoverageLcsErrorToleranceRelativeq must be finite and not negative";
+    if (c.enable_lexical_prescreen) { *status = INFX_EUNSUPPORTED; return "CoverageSetup.EnableLexicalPrescreen is not implemented"; }
+    return nullptr;
+}
+int32_t infx_coverage_setup_default(infx_coverage_setup* out) { if (!out) return efail(INFX_EINVAL, "null argument"); *out = COVERAGE_SETUP_DEFAULT; return INFX_OK; }
+int32_t infx_sizeof_coverage_setup(void) { return (int32_t)sizeof(infx_coverage_setup); }
+int32_t infx_engine_set_coverage_setup(infx_engine* e, const infx_coverage_setup* setup) {
+    if (!e) return efail(INFX_EINVAL, "null engine");
+    const infx_coverage_setup c = setup ? *setup : COVERAGE_SETUP_DEFAULT;
+    int32_t st = INFX_OK;
+    if (const char* why = coverage_setup_problem(c, &st)) return efail(st, why);
+    e->cs = c;
+    HostConfig& h = e->ix.cfg;
+    h.covMinWordSize = c.min_word_size; h.coverPrefixSuffix = c.cover_prefix_suffix != 0;
+    h.covQLimit = c.coverage_q_limit_for_error_tolerance; h.covRelativeq = c.coverage_lcs_error_tolerance_relativeq;
+    return INFX_OK;
+}
+int32_t infx_engine_get_coverage_setup(infx_engine* e, infx_coverage_setup* out) { if (!e || !out) return efail(INFX_EINVAL, "null argument"); *out = e->cs; return INFX_OK; }
+static infx_finalize_setup finalize_of(const infx_coverage_setup& c) {
+    infx_finalize_setup f; f.truncate = c.truncate != 0; f.min_hits_abs = c.coverage_min_word_hits_abs; f.min_hits_relative = c.coverage_min_word_hits_relative; f.truncation_score = c.truncation_score;
+    return f;
+}
+static inline infx_finalize_setup qc_finalize(const infx_session* S, size_t i) { return S->qc.on && i < S->qc.nq ? S->qc.fin[i] : finalize_of(S->e->cs); }
+static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len) {
+    const HostConfig& h = S->e->ix.cfg;
+    return S->qc.on && i < S->qc.nq ? cov_lcs_tolerance(len, S->qc.qLimit[i], S->qc.relativeq[i]) : cov_lcs_tolerance(len, h.covQLimit, h.covRelativeq);
+}
+int32_t infx_engine_set_query_coverage(infx_session* S, uint32_t nq, const infx_coverage_setup* const* setups, int32_t* out_status) {
+    if (!S || (nq && !setups)) return efail(INFX_EINVAL, "null argument");
+    S->qc = QueryCov();
+    if (nq == 0) return INFX_OK;
+    QueryCov Q; Q.nq = nq;
+    Q.fin.assign(nq, finalize_of(S->e->cs)); Q.qLimit.assign(nq, S->e->ix.cfg.covQLimit); Q.relativeq.assign(nq, S->e->ix.cfg.covRelativeq);
+    Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
+    for (uint32_t i = 0; i < nq; i++) {
+        if (!setups[i]) continue;
+        const infx_coverage_setup& c = *setups[i];
+        int32_t st = INFX_OK;
+        if (const char* why = coverage_setup_problem(c, &st)) { Q.reject[i] = 1; Q.status[i] = st; Q.err[i] = why; continue; }
+        // Only what SearchPipeline reads; the matcher members stay the engine's (quirk Q19)
+        Q.fin[i] = finalize_of(c); Q.qLimit[i] = c.coverage_q_limit_for_error_tolerance; Q.relativeq[i] = c.coverage_lcs_error_tolerance_relativeq;
+    }
+    if (S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
+    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i]) S->lastErr[i] = Q.err[i];
+    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
+    Q.on = true;
+    S->qc = std::move(Q);
+    return INFX_OK;
+}
+static int32_t query_cov_check(infx_session* S, uint32_t nq) {
+    if (!S->qc.on) return INFX_OK;
+    if (nq != S->qc.nq) { S->qc = QueryCov(); return efail(INFX_EINVAL, "the per-query coverage setups were installed for a batch of another size"); }
+    return INFX_OK;
+}
+// The batch is done: a query whose setup was refused comes back empty with result flag bit 4; the setups are consumed
+static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
+    if (!S->qc.on) return;
+    const QueryCov& Q = S->qc;
+    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
+    for (uint32_t i = 0; i < Q.nq; i++) if (Q.reject[i]) {
+        if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
+        if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
+    }
+    S->qc = QueryCov();
+}
+// The stream's next Stage-2 call gets the engine-wide matcher settings, its next finalize the per-query truncation records (deviceFinalize: the batch is
+// finalized by k_finalize; the host phases apply the same values in ph_finalize).  Defaults everywhere: nothing is staged.
+static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize) {
+    if (!S->stream) return INFX_OK;
+    const infx_coverage_setup& c = S->e->cs;
+    infx_stage2_setup m;
+    m.min_word_size = c.min_word_size; m.lev_max_word_size = c.levenshtein_max_word_size; m.num_typos = c.num_typos;
+    m.min_len_one_typo = c.min_length_one_typo; m.min_len_two_typos = c.min_length_two_typos;
+    m.cover_whole_query = c.cover_whole_query; m.cover_whole_words = c.cover_whole_words; m.cover_fuzzy_words = c.cover_fuzzy_words;
+    m.cover_joined_words = c.cover_joined_words; m.cover_prefix_suffix = c.cover_prefix_suffix;
+    const infx_finalize_setup engineFin = finalize_of(c);
+    static const infx_finalize_setup defFin = finalize_of(COVERAGE_SETUP_DEFAULT);
+    std::vector<infx_finalize_setup> fin;
+    if (deviceFinalize && nq) {
+        if (S->qc.on && S->qc.nq == nq) fin = S->qc.fin;
+        else if (std::memcmp(&engineFin, &defFin, sizeof defFin) != 0) fin.assign(nq, engineFin);
+    }
+    int32_t rc = infx_stream_set_coverage(S->stream, &m, (uint32_t)fin.size(), fin.empty() ? nullptr : fin.data());
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {
     if (!e || limit < 1) return efail(INFX_EINVAL, "bad arguments");
     std::lock_guard<std::mutex> lk(e->filterMu);

@@ -225,6 +225,9 @@ struct HostConfig {
     float fieldWeights[3] = {1.5f, 1.25f, 1.0f};
     bool enableCoverage = true, wordMatcher = true;
     int wmMinExact = 2, wmMaxExact = 8, wmMinLD1 = 3, wmMaxLD1 = 8;
+    // engine-wide CoverageSetup members the host reads (infx_engine_set_coverage_setup): MinWordSize of CoverageEngine.PrepareQuery, CoverPrefixSuffix of
+    // WordMatcherLookup.Execute, and the defaults of the LCS tolerance (SearchPipeline.cs:498-499)
+    int covMinWordSize = 2; bool coverPrefixSuffix = true; int covQLimit = 5; double covRelativeq = 0.2;
     int maxDepth = 500;            // prefix DocSets with population > 20*maxDepth are never acceptable (only counted)
     int threads = 0;
     SynMap syn;                    // SearchEngine(..., synonymMap): empty by default

@@ -539,6 +539,8 @@ inline void wm_first_unique(const WmResult& R, const std::vector<int32_t>& exclu
 
 // ---- CoverageEngine.PrepareQuery -------------------------------------------------------------------------------------------
 // QT = infx_cov_query (the fast envelope: INFX_MAX_QUERY_CHARS / INFX_MAX_QUERY_TOKENS) or infx_cov_query_long (INFX_LONGQ_CHARS / INFX_LONGQ_TOKENS); same members.
+// SearchPipeline.cs:498-499: the error tolerance of StringMetrics.Lcs for a coverage query of `len` characters
+inline int32_t cov_lcs_tolerance(int len, int qLimit, double relativeq) { return len >= qLimit ? (int32_t)((double)len * relativeq) : 0; }
 template <class QT, int MAXCHARS, int MAXTOK>
 inline int32_t prepare_cov_query_t(const HostIndex& ix, uview query, QT& C) {
     std::memset(&C, 0, sizeof C);
@@ -546,7 +548,7 @@ inline int32_t prepare_cov_query_t(const HostIndex& ix, uview query, QT& C) {
     std::memcpy(C.text, query.data(), query.size() * 2); C.text_len = (int)query.size();
     struct Tk { int off, len; };
     std::vector<Tk> raw, uq, fus;
-    for_each_word(query, [&](int off, int len) { fus.push_back({off, len}); if (len >= 2) raw.push_back({off, len}); });
+    for_each_word(query, [&](int off, int len) { fus.push_back({off, len}); if (len >= ix.cfg.covMinWordSize) raw.push_back({off, len}); });
     for (auto& t : raw) {
         bool dup = false;
         for (auto& u : uq) if (ic_equal(query.substr(u.off, u.len), query.substr(t.off, t.len))) { dup = true; break; }      // CoverageTokenizer.cs:50-57: OrdinalIgnoreCase
@@ -579,7 +581,7 @@ inline int32_t prepare_cov_query_t(const HostIndex& ix, uview query, QT& C) {
     C.has_word_idf = uq.empty() ? 0 : 1;
     C.num_fusion_tokens = (int)fus.size();
     for (int i = 0; i < (int)fus.size(); i++) { C.ftok_off[i] = (uint16_t)fus[i].off; C.ftok_len[i] = (uint16_t)std::min(fus[i].len, 65535); }
-    C.lcs_tolerance = (int)query.size() >= 5 ? (int)((double)query.size() * 0.2) : 0;
+    C.lcs_tolerance = cov_lcs_tolerance((int)query.size(), ix.cfg.covQLimit, ix.cfg.covRelativeq);      // (a query with its own CoverageSetup: recomputed by the caller)
     return INFX_OK;
 }
 inline int32_t prepare_cov_query(const HostIndex& ix, uview query, infx_cov_query& C) { return prepare_cov_query_t<infx_cov_query, INFX_MAX_QUERY_CHARS, INFX_MAX_QUERY_TOKENS>(ix, query, C); }

@@ -305,6 +305,9 @@ struct infx_stream {
     void* dDense = nullptr; size_t capDense = 0;      // k_accumulate_sparse -> k_accumulate hand-over flags, one byte per (query, stripe)
     void* dCovQ = nullptr; size_t capCovQ = 0;
     void* dCovQL = nullptr; size_t capCovQL = 0; uint32_t nLongQ = 0;      // infx_stage2_long_queries: the long-query table of the next Stage-2 call
+    // infx_stream_set_coverage: the matcher settings of the next Stage-2 call (csOn: they differ from the defaults -> the custom-setup instantiations) and the
+    // per-query truncation records of the next finalize (finOn; else dFin holds finDefaultN default records)
+    bool csOn = false; infx_stage2_setup cs{}; bool finOn = false; std::vector<infx_finalize_setup> finH; void* dFin = nullptr; size_t capFin = 0; uint32_t finDefaultN = 0;
     void* dCovC = nullptr; size_t capCovC = 0;
     void* dCovO = nullptr; size_t capCovO = 0;
     void* dCovF = nullptr; size_t capCovF = 0;
@@ -378,26 +381,41 @@ static void ws_release(infx_stream* s, void* p) { if (p) s->parked.push_back(p);
 static int s2_waves() { static const int w = [] { const char* e = getenv("INFX_S2_WAVES"); int v = e ? atoi(e) : 0; return (v == 2 || v == 4 || v == 6 || v == 8) ? v : S2_MIN_WAVES; }(); return w; }
 // LDS pool of the fast launch: UTF-16 units of document text per 64-candidate workgroup (INFX_S2_POOL overrides; 0 = texts stay in global memory)
 static int s2_pool() { static const int w = [] { const char* e = getenv("INFX_S2_POOL"); int v = e ? atoi(e) : S2_POOL_CHARS; return (v < 0 || v > 32768) ? S2_POOL_CHARS : v; }(); return w; }
+// INFX_S2_CUSTOM=1 (measurement, like the two above): a stream that is handed matcher settings (infx_stream_set_coverage; the engine does so for every batch) runs the
+// custom-setup instantiations of k_stage2 also when the settings are CoverageSetup's defaults — what the settings cost as kernel arguments against compile-time
+// constants, same results (profiles/coverage_setup.md)
+static bool s2_force_custom() { static const bool f = [] { const char* e = getenv("INFX_S2_CUSTOM"); return e && e[0] == '1'; }(); return f; }
 #define S2_GRID(lds) (ncand + S2_THREADS - 1) / S2_THREADS, S2_THREADS, (lds), s->st
 #define S2_FAST_TAIL pool_, (uint16_t*)nullptr, (uint32_t*)nullptr, 0u, (const infx_cov_query_long*)nullptr, s->nLongQ      /* the first launch tells long-query rows apart (and checks their table index) */
 // AL: the ALIAS instantiation (stage2.hip.inc: OrdinalIgnoreCase sites compare class representatives) — whenever the corpus or the batch's queries hold one of the 22 alias
 // characters; else the plain one (every comparison `==`, exact without them)
 #define S2_AL (s->ix->hasAlias || s->batchAlias)
-#define S2_LAUNCH_FAST(...) do { const int pool_ = s2_pool(); if (S2_AL) { k_stage2<S2_FASTD, 6, false, false, true><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; } \
+// CS: the custom-setup instantiations (stage2.hip.inc), whenever the stream holds matcher settings that differ from CoverageSetup's defaults.  The fast launch — where
+// the time goes — exists in the plain and the ALIAS form; the retry, huge-pool and long-query launches only in the ALIAS form (exact with or without alias characters)
+#define S2_CS (s->csOn)
+#define S2_NOHUGE (uint16_t*)nullptr, (uint32_t*)nullptr, 0u
+#define S2_HUGEWS (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16
+#define S2_NOLONG (const infx_cov_query_long*)nullptr, 0u
+#define S2_LONGT (const infx_cov_query_long*)s->dCovQL, s->nLongQ
+#define S2_LAUNCH_FAST(...) do { const int pool_ = s2_pool(); if (S2_CS) { if (S2_AL) k_stage2<S2_FASTD, 6, false, false, true, true><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL, s->cs); \
+                                              else k_stage2<S2_FASTD, 6, false, false, false, true><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL, s->cs); break; } \
+                                 if (S2_AL) { k_stage2<S2_FASTD, 6, false, false, true><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; } \
                                  switch (s2_waves()) { case 2: k_stage2<S2_FASTD, 2><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; case 6: k_stage2<S2_FASTD, 6><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; \
                                                      case 8: k_stage2<S2_FASTD, 8><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; default: k_stage2<S2_FASTD, 4><<<S2_GRID(pool_ * 2)>>>(__VA_ARGS__, S2_FAST_TAIL); break; } } while (0)
-#define S2_LAUNCH_SLOW(...) do { if (S2_AL) k_stage2<S2_MAXD, 4, false, false, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0); else k_stage2<S2_MAXD, 4><<<S2_GRID(0)>>>(__VA_ARGS__, 0); } while (0)
-#define S2_LAUNCH_HUGE(...) do { if (S2_AL) k_stage2<S2_HUGE_TOKENS, 1, true, false, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16); \
+#define S2_LAUNCH_SLOW(...) do { if (S2_CS) k_stage2<S2_MAXD, 4, false, false, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, S2_NOHUGE, S2_NOLONG, s->cs); else if (S2_AL) k_stage2<S2_MAXD, 4, false, false, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0); else k_stage2<S2_MAXD, 4><<<S2_GRID(0)>>>(__VA_ARGS__, 0); } while (0)
+#define S2_LAUNCH_HUGE(...) do { if (S2_CS) k_stage2<S2_HUGE_TOKENS, 1, true, false, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, S2_HUGEWS, S2_NOLONG, s->cs); else if (S2_AL) k_stage2<S2_HUGE_TOKENS, 1, true, false, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16); \
                                  else k_stage2<S2_HUGE_TOKENS, 1, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16); } while (0)
 // rows of long queries (marked by the first launch): documents up to S2_MAXD words, then the rest through the global-workspace pass; nothing is launched for a batch without long queries.
 // The table is consumed: the next Stage-2 call starts without one.
 #define S2_LAUNCH_LONGQ(...) do { if (s->nLongQ) { \
-    if (S2_AL) k_stage2<S2_MAXD, 2, false, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)nullptr, (uint32_t*)nullptr, 0u, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
+    if (S2_CS) k_stage2<S2_MAXD, 2, false, true, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, S2_NOHUGE, S2_LONGT, s->cs); \
+    else if (S2_AL) k_stage2<S2_MAXD, 2, false, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)nullptr, (uint32_t*)nullptr, 0u, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
     else k_stage2<S2_MAXD, 2, false, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)nullptr, (uint32_t*)nullptr, 0u, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
     (void)hipMemsetAsync(s->dHugeCnt, 0, 4, s->st);      /* the long-query rows get the whole token-table pool, not what the ordinary rows' pool pass left of it */ \
-    if (S2_AL) k_stage2<S2_HUGE_TOKENS, 1, true, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
+    if (S2_CS) k_stage2<S2_HUGE_TOKENS, 1, true, true, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, S2_HUGEWS, S2_LONGT, s->cs); \
+    else if (S2_AL) k_stage2<S2_HUGE_TOKENS, 1, true, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
     else k_stage2<S2_HUGE_TOKENS, 1, true, true><<<S2_GRID(0)>>>(__VA_ARGS__, 0, (uint16_t*)s->dHugeWs, (uint32_t*)s->dHugeCnt, (uint32_t)S2_HUGE_POOL_U16, (const infx_cov_query_long*)s->dCovQL, s->nLongQ); \
-    s->nLongQ = 0; s->longAlias = false; } } while (0)
+    s->nLongQ = 0; s->longAlias = false; } s->csOn = false;      /* the matcher settings are consumed with the call's last launch */ } while (0)
 static int32_t s2_huge_ready(infx_stream* s);
 
 // ---- host <-> device transfers through pinned staging -------------------------------------------------------------------
@@ -1115,7 +1133,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin};
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
     for (void* p : s->parked) hipFree(p);
@@ -1412,6 +1430,30 @@ int32_t infx_stage2_long_queries(infx_stream* s, uint32_t n, const infx_cov_quer
     return INFX_OK;
 }
 
+static const infx_stage2_setup S2_DEFAULT_SETUP = {2, 20, 2, 3, 7, 1, 1, 1, 1, 1};
+static const infx_finalize_setup FIN_DEFAULT_SETUP = {1, 1, 0, 254};
+int32_t infx_stream_set_coverage(infx_stream* s, const infx_stage2_setup* matchers, uint32_t nq, const infx_finalize_setup* per_query) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    s->csOn = false; s->finOn = false;
+    auto bad = [](int32_t v) { return v < 0 || v > 65535; };
+    if (matchers) {
+        const infx_stage2_setup& m = *matchers;
+        if (bad(m.min_word_size) || bad(m.lev_max_word_size) || bad(m.num_typos) || bad(m.min_len_one_typo) || bad(m.min_len_two_typos))
+            return fail(INFX_EINVAL, "coverage setup: a matcher setting lies outside [0, 65535]%s");
+        infx_stage2_setup c = m;      // the switches as 0 / 1
+        c.cover_whole_query = m.cover_whole_query != 0; c.cover_whole_words = m.cover_whole_words != 0; c.cover_fuzzy_words = m.cover_fuzzy_words != 0;
+        c.cover_joined_words = m.cover_joined_words != 0; c.cover_prefix_suffix = m.cover_prefix_suffix != 0;
+        s->cs = c; s->csOn = s2_force_custom() || std::memcmp(&c, &S2_DEFAULT_SETUP, sizeof c) != 0;
+    }
+    if (per_query && nq) {
+        for (uint32_t i = 0; i < nq; i++) if (bad(per_query[i].min_hits_abs) || bad(per_query[i].min_hits_relative) || per_query[i].truncation_score < 0 || per_query[i].truncation_score > 255) {
+            s->csOn = false; return fail(INFX_EINVAL, "coverage setup: a truncation setting lies outside its range%s");
+        }
+        s->finH.assign(per_query, per_query + nq); s->finOn = true;
+    }
+    return INFX_OK;
+}
+
 int32_t infx_stage2_batch(infx_stream* s, uint32_t nq, const infx_cov_query* q, uint32_t ncand, const infx_cov_cand* cand,
                           infx_cov_out* out, int32_t* feat_out) {
     if (!s || (ncand && (!q || !cand || !out))) return fail(INFX_EINVAL, "null argument%s");
@@ -1694,7 +1736,8 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     HIPCHK(hipMemsetAsync(s->dCovO, 0, (size_t)ncand * sizeof(infx_cov_out), s->st));
     HIPCHK(hipEventRecord(s->evP0, s->st));
     if (wmDev) {
-        k_wm<<<nq, WAVE, 0, s->st>>>(*ix->lk, (infx_fused_query*)s->dFQ, (const infx_cov_query*)s->dCovQ, nq, (infx_wm_list*)s->dFLists, nlists, (int32_t*)s->dFOwned, (uint64_t)owned_n);
+        DevLookup lk = *ix->lk; if (s->csOn && !s->cs.cover_prefix_suffix) lk.nAffix = 0;      // !CoverPrefixSuffix: no LookupAffix (WordMatcherLookup.cs:51) -> no source-2 lists
+        k_wm<<<nq, WAVE, 0, s->st>>>(lk, (infx_fused_query*)s->dFQ, (const infx_cov_query*)s->dCovQ, nq, (infx_wm_list*)s->dFLists, nlists, (int32_t*)s->dFOwned, (uint64_t)owned_n);
         HIPCHK(hipGetLastError());
     }
     {
@@ -1923,11 +1966,20 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         { int32_t rc_ = count_enqueue(s, dProgs, ncount, s->qpCols, 0, ix->d.totalDocs, (uint32_t*)s->dQCount); if (rc_) return rc_; }
         DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
     }
+    {   // the per-query truncation records (infx_stream_set_coverage, consumed here); the defaults stay on the device from one batch to the next
+        const bool fin = s->finOn; s->finOn = false;
+        if (fin && s->finH.size() != nq) return fail(INFX_EINVAL, "the per-query coverage setups were installed for a batch of another size%s");
+        if ((size_t)nq * sizeof(infx_finalize_setup) > s->capFin) s->finDefaultN = 0;
+        GROW(s->dFin, s->capFin, (size_t)nq * sizeof(infx_finalize_setup));
+        if (fin) { UP(s->dFin, s->finH.data(), (size_t)nq * sizeof(infx_finalize_setup)); s->finDefaultN = 0; }
+        else if (s->finDefaultN < nq) { std::vector<infx_finalize_setup> d(nq, FIN_DEFAULT_SETUP); UP(s->dFin, d.data(), (size_t)nq * sizeof(infx_finalize_setup)); s->finDefaultN = nq; }
+    }
     HIPCHK(hipEventRecord(s->evF0, s->st));
     k_finalize<<<nq, P2_THREADS, lds, s->st>>>(ix->d, (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
-                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr);
+                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr,
+                                                (const infx_finalize_setup*)s->dFin);
     HIPCHK(hipGetLastError());
     if (browse) {
         int32_t rc_;
@@ -2001,7 +2053,9 @@ int32_t infx_wm_lookup_debug(infx_stream* s, const infx_cov_query* cq, infx_wm_l
     GROW(s->dFOwned, s->capFOwned, ((size_t)words * WM_AFFIX_CAP + 1) * 4);
     GROW(s->dCovQ, s->capCovQ, sizeof(infx_cov_query));
     UP(s->dFQ, &fq, sizeof fq); UP(s->dCovQ, cq, sizeof *cq);
-    k_wm<<<1, WAVE, 0, s->st>>>(*ix->lk, (infx_fused_query*)s->dFQ, (const infx_cov_query*)s->dCovQ, 1, (infx_wm_list*)s->dFLists, 0, (int32_t*)s->dFOwned, 0ull);
+    DevLookup lk = *ix->lk; if (s->csOn && !s->cs.cover_prefix_suffix) lk.nAffix = 0;
+    s->csOn = false;
+    k_wm<<<1, WAVE, 0, s->st>>>(lk, (infx_fused_query*)s->dFQ, (const infx_cov_query*)s->dCovQ, 1, (infx_wm_list*)s->dFLists, 0, (int32_t*)s->dFOwned, 0ull);
     HIPCHK(hipGetLastError());
     infx_fused_query back{};
     DOWN(&back, s->dFQ, sizeof back);

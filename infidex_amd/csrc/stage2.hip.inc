@@ -167,13 +167,20 @@ __device__ int s2_count_tokens(S2Str t) {                    // non-empty tokens
 #ifndef S2_POOL_CHARS
 #define S2_POOL_CHARS 3072   // 6 KB of LDS per 64-candidate workgroup (measured on the 10M-doc batch: 0 -> 2.21 ms, 2048 -> 2.00, 3072 -> 1.84, 4096 -> 2.03, 6144 -> 2.47: larger pools cost occupancy)
 #endif
-template <int MAXD, int MINW, bool HUGE = false, bool LQ = false, bool AL = false>
+// CS: the "custom setup" instantiations.  The engine-wide matcher settings of CoverageSetup (infx_stage2_setup: MinWordSize — also minStemLength of the fusion
+// signals —, the five Cover* switches, the three typo thresholds, LevenshteinMaxWordSize) arrive as the kernel argument `cs` (uniform: scalar registers) instead of
+// being the literals of CoverageSetup.cs:6-103.  Without CS every one of them folds to its default at compile time and `cs` is never read: those instantiations
+// compile to what they were before the argument existed.  The fast launch has a plain and an ALIAS custom instantiation (the ALIAS form forgoes the one-pass
+// distance-1 Damerau and folds at every comparison: half as fast again); the retry, huge-pool and the two long-query launches — a few rows of a batch — only the ALIAS
+// one, which is exact with or without alias characters: six kernels more, not ten.
+template <int MAXD, int MINW, bool HUGE = false, bool LQ = false, bool AL = false, bool CS = false>
 __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const infx_cov_query* __restrict__ queries, uint32_t nq,
                                                         const infx_cov_cand* __restrict__ cands, uint32_t ncand,
                                                         infx_cov_out* __restrict__ outs, int32_t* __restrict__ featOut, int globalIds, int retryPass,
                                                         const int32_t* __restrict__ pairs, int poolChars,
                                                         uint16_t* __restrict__ hugeWs = nullptr, uint32_t* __restrict__ hugeCounter = nullptr, uint32_t hugeUnits = 0,
-                                                        const infx_cov_query_long* __restrict__ longq = nullptr, uint32_t nLong = 0) {
+                                                        const infx_cov_query_long* __restrict__ longq = nullptr, uint32_t nLong = 0,
+                                                        const infx_stage2_setup cs = infx_stage2_setup{}) {
     constexpr int LOC = HUGE ? 1 : MAXD;                              // per-lane table capacity held in registers / scratch
     constexpr int MAXQ = LQ ? INFX_LONGQ_TOKENS : INFX_MAX_QUERY_TOKENS;      // capacity of the per-lane query-word tables
     typedef typename std::conditional<LQ, infx_cov_query_long, infx_cov_query>::type QCT;
@@ -254,14 +261,15 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
         if (C.want_lcs == 2) lcs = min(lcs, 255);      // this row IS the document's second evaluation (rows handed over one by one: infx_cov_cand.want_lcs)
         O.lcs = (uint8_t)min(lcs, 255);
     }
-    double lcsSum = (double)lcs;
+    const bool wholeQuery = !CS || cs.cover_whole_query != 0;      // !CoverWholeQuery: the coverage score ignores the LCS (CoverageEngine.cs:269); the row keeps it for the truncation
+    double lcsSum = wholeQuery ? (double)lcs : 0.0;
     // Quirk Q18 (SearchPipeline.cs:492-503): the LCS of docIndex 0 / 1 is kept in a BYTE span; a document evaluated twice — overlap row, then Stage-1 row — reads it
     // back for its second evaluation, so a value above 255 (queries longer than 255 characters contained in the document) comes back as 255.  The partner row
     // derived below is that second evaluation: where the two values differ, the features the LCS feeds (CoverageScore's fallback, the single-term SumCi) and the
     // score are computed a second time for it.
     const int lcsP = min(lcs, 255);
     const bool split = partner >= 0 && lcsP != lcs;
-    const double lcsSumP = (double)lcsP;
+    const double lcsSumP = wholeQuery ? (double)lcsP : 0.0;
     uint8_t CoverageScoreP = 0; float SumCiP = 0.f;
 
     // feature state
@@ -297,7 +305,7 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
     }
 
     if (qCount > 0) {
-        const int MinWordSize = 2;
+        const int MinWordSize = CS ? cs.min_word_size : 2;
         int dCountRaw = s2_tokenize(D, MinWordSize, dOff, dLen, cap, &over);
         docTokenCount = dCountRaw;
         // dedupe (CoverageTokenizer.DeduplicateDocTokens): the first occurrences, in order
@@ -324,7 +332,7 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
 #define SETPOS(i, pos) do { int p_ = (pos); if (firstPos[i] == -1 || p_ < firstPos[i]) firstPos[i] = p_; } while (0)
 
         // ---- WholeWordMatcher.Match ----
-        {
+        if (!CS || cs.cover_whole_words) {
             int pInc = qCount > 1 ? 1 : 0;
             for (int i = 0; i < qCount; i++) {
                 S2Str qt = QTOK(i);
@@ -341,7 +349,7 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
             }
         }
         // ---- JoinedWordMatcher.Match ----
-        {
+        if (!CS || cs.cover_joined_words) {
             for (int i = 0; i < qCount - 1; i++) {
                 if (!qActive.test(i) || !qActive.test(i + 1)) continue;
                 int next = -1;
@@ -375,7 +383,7 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
             }
         }
         // ---- PrefixSuffixMatcher.Match ----
-        {
+        if (!CS || cs.cover_prefix_suffix) {
             uint8_t qi[MAXQ]; int nqa = 0, nda = 0;
             for (int i = 0; i < qCount; i++) if (qActive.test(i)) qi[nqa++] = (uint8_t)i;
             for (int j = 0; j < dCount; j++) if (s2_get(dActive, j)) di[nda++] = (idx_t)j;
@@ -441,11 +449,11 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
             }
         }
         // ---- FuzzyWordMatcher.Match (unless all terms fully matched) ----
-        {
+        if (!CS || cs.cover_fuzzy_words) {
             bool allFull = true;
             for (int i = 0; i < qCount; i++) if (QLEN(i) > 0 && matched[i] < (float)QLEN(i)) { allFull = false; break; }
             if (!allFull) {
-                const int NumTypos = 2, MinLengthOneTypo = 3, MinLengthTwoTypos = 7, LevMaxWord = 20;
+                const int NumTypos = CS ? cs.num_typos : 2, MinLengthOneTypo = CS ? cs.min_len_one_typo : 3, MinLengthTwoTypos = CS ? cs.min_len_two_typos : 7, LevMaxWord = CS ? cs.lev_max_word_size : 20;
                 int maxQL = 0;
                 for (int i = 0; i < qCount; i++) if (qActive.test(i) && QLEN(i) > maxQL) maxQL = QLEN(i);
                 if (maxQL != 0) {
@@ -575,7 +583,7 @@ __global__ __launch_bounds__(S2_THREADS, MINW) void k_stage2(DevIndex ix, const 
                 }
                 // 3. CheckStemEvidence (minStemLength = MinWordSize = 2, CoverageEngine.cs:376)
                 if (fq >= 2) {
-                    const int minStem = 2; int unmatched = 0, evidence = 0;
+                    const int minStem = CS ? cs.min_word_size : 2; int unmatched = 0, evidence = 0;
                     for (int qi2 = 0; qi2 < fq; qi2++) {
                         S2Str qx = FQ(qi2);
                         if (qx.len < minStem) continue;

@@ -1,7 +1,7 @@
 """ctypes binding of libinfidex_hip.so with the reference's public names for the hot path.
 
 Mirrors (reference paths under src/Infidex): SearchEngine.cs (CreateDefault/CreateMinimal/IndexDocuments/Search),
-Api/Query.cs, Api/Boost.cs, Api/BoostStrength.cs, Api/Result.cs, Core/Document.cs, Api/Weight.cs, Core/ScoreEntry.cs.
+Api/Query.cs, Api/Boost.cs, Api/BoostStrength.cs, Api/Result.cs, Core/Document.cs, Api/Weight.cs, Core/ScoreEntry.cs, Coverage/CoverageSetup.cs.
 """
 import ctypes as C
 import os
@@ -54,7 +54,40 @@ class Boost:       # Api/Boost.cs: documents matching the filter get +strength o
 
 
 @dataclass
-class Query:       # Api/Query.cs:9-40
+class CoverageSetup:    # Coverage/CoverageSetup.cs:6-103 (names and defaults)
+    """The Stage-2 settings.  Engine-wide (SearchEngine(coverage_setup=...)) every member applies; on a Query only the six that SearchPipeline itself
+    reads do — truncate, coverage_min_word_hits_abs, coverage_min_word_hits_relative, truncation_score, coverage_q_limit_for_error_tolerance,
+    coverage_lcs_error_tolerance_relativeq — because the matchers keep the engine's object, as in the reference."""
+    min_word_size: int = 2
+    levenshtein_max_word_size: int = 20
+    num_typos: int = 2                     # 0, 1 or 2 (more behaves as 2)
+    min_length_one_typo: int = 3
+    min_length_two_typos: int = 7
+    coverage_min_word_hits_abs: int = 1
+    coverage_min_word_hits_relative: int = 0
+    coverage_q_limit_for_error_tolerance: int = 5
+    coverage_lcs_error_tolerance_relativeq: float = 0.2
+    cover_whole_query: bool = True
+    cover_whole_words: bool = True
+    cover_fuzzy_words: bool = True
+    cover_joined_words: bool = True
+    cover_prefix_suffix: bool = True
+    truncate: bool = True
+    enable_lexical_prescreen: bool = False     # not implemented: refused (INFX_EUNSUPPORTED)
+    truncation_score: int = 254
+    coverage_depth: int = 500              # never read (Query.coverage_depth is used instead): carried for shape only
+
+    @classmethod
+    def create_default(cls):
+        return cls()
+
+    @classmethod
+    def create_minimal(cls):               # CoverageSetup.cs:153-162: exact matching only
+        return cls(cover_whole_words=True, cover_fuzzy_words=False, cover_joined_words=False, cover_prefix_suffix=False, cover_whole_query=False)
+
+
+@dataclass
+class Query:       # Api/Query.cs:9-45
     text: str
     max_number_of_records_to_return: int = 10
     coverage_depth: int = 500
@@ -65,6 +98,7 @@ class Query:       # Api/Query.cs:9-40
     boosts: Optional[Sequence[Boost]] = None
     sort_by: Optional[str] = None          # Query.SortBy: a field (column) name, None = relevance order
     sort_ascending: bool = False           # Query.SortAscending
+    coverage_setup: Optional[CoverageSetup] = None      # Query.CoverageSetup: None = the engine's (its matcher members are ignored, see CoverageSetup)
 
     @property
     def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
@@ -91,11 +125,44 @@ class Result:      # Api/Result.cs
     total_in_filter: int = 0               # Filter.NumberOfDocumentsInFilter
     error: Optional[str] = None            # search_queries: why this query alone was rejected (empty result); None when it ran
 
+    # SearchEngine.cs:312-316: index and score of the last returned row, and the row count
+    @property
+    def truncation_index(self) -> int:
+        return len(self.records) - 1 if self.records else 0
+
+    @property
+    def truncation_score(self) -> float:
+        return self.records[-1].score if self.records else 0.0
+
+    @property
+    def total_candidates(self) -> int:
+        return len(self.records)
+
 
 class _Cfg(C.Structure):
     _fields_ = [("device", C.c_int32), ("range_docs", C.c_int32), ("max_depth", C.c_int32), ("threads", C.c_int32),
                 ("enable_coverage", C.c_int32), ("word_matcher", C.c_int32), ("stop_term_limit", C.c_int32),
                 ("want_features", C.c_int32), ("no_exact_replay", C.c_int32)]
+
+
+class _CoverageSetup(C.Structure):     # infx_coverage_setup (include/infidex_engine.h)
+    _fields_ = [("min_word_size", C.c_int32), ("levenshtein_max_word_size", C.c_int32), ("num_typos", C.c_int32), ("min_length_one_typo", C.c_int32),
+                ("min_length_two_typos", C.c_int32), ("coverage_min_word_hits_abs", C.c_int32), ("coverage_min_word_hits_relative", C.c_int32),
+                ("coverage_q_limit_for_error_tolerance", C.c_int32), ("coverage_lcs_error_tolerance_relativeq", C.c_double),
+                ("cover_whole_query", C.c_int32), ("cover_whole_words", C.c_int32), ("cover_fuzzy_words", C.c_int32), ("cover_joined_words", C.c_int32),
+                ("cover_prefix_suffix", C.c_int32), ("truncate", C.c_int32), ("enable_lexical_prescreen", C.c_int32), ("truncation_score", C.c_int32)]
+
+
+def _coverage_struct(cs: CoverageSetup) -> _CoverageSetup:
+    st = _CoverageSetup()
+    for name, ty in _CoverageSetup._fields_:
+        v = getattr(cs, name)
+        if ty is C.c_double:
+            setattr(st, name, float(v))
+        else:
+            v = int(v)
+            setattr(st, name, v if -2 ** 31 <= v < 2 ** 31 else -1)      # (out of the int32 range: out of the accepted range too)
+    return st
 
 
 _lib = None
@@ -136,13 +203,34 @@ def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
 
 class SearchEngine:
     def __init__(self, enable_coverage=True, word_matcher=True, device: int = 0, range_docs: int = 0, max_depth: int = 500,
-                 threads: int = 0, stop_term_limit: int = 0, want_features: bool = False, exact_replay: bool = True):
+                 threads: int = 0, stop_term_limit: int = 0, want_features: bool = False, exact_replay: bool = True,
+                 coverage_setup: Optional[CoverageSetup] = None):
         self.L = load_library()
         cfg = _Cfg(device, range_docs, max_depth, threads, int(enable_coverage), int(word_matcher), stop_term_limit, int(want_features), int(not exact_replay))
         h = C.c_void_p()
         self._check(self.L.infx_engine_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self.device = device
+        if coverage_setup is not None:
+            try:
+                self.set_coverage_setup(coverage_setup)
+            except Exception:
+                self.close()
+                raise
+
+    def set_coverage_setup(self, coverage_setup: Optional[CoverageSetup]):
+        """The engine-wide CoverageSetup (SearchEngine's coverageSetup: argument; None = the defaults).  Legal between batches."""
+        st = _coverage_struct(coverage_setup) if coverage_setup is not None else None
+        self._check(self.L.infx_engine_set_coverage_setup(self.h, C.byref(st) if st is not None else None))
+
+    def coverage_setup(self) -> CoverageSetup:
+        st = _CoverageSetup()
+        self._check(self.L.infx_engine_get_coverage_setup(self.h, C.byref(st)))
+        kw = {}
+        for name, ty in _CoverageSetup._fields_:
+            d = CoverageSetup.__dataclass_fields__[name].default
+            kw[name] = type(d)(getattr(st, name))
+        return CoverageSetup(**kw)
 
     # SearchEngine.cs:78-94
     @classmethod
@@ -322,9 +410,9 @@ class SearchEngine:
 
     def search_queries(self, queries: Sequence[Query], session=None) -> List[Result]:
         """Search(Query) for a batch of Query objects, each with its own MaxNumberOfRecordsToReturn, EnableCoverage, Filter, EnableFacets, Boosts and
-        SortBy (infx_engine_set_query_options): one device batch per CoverageDepth, results in input order.  A query whose options are refused
-        (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than 64 rows) comes back empty with Result.error set; the
-        others of the batch are unaffected."""
+        SortBy (infx_engine_set_query_options) and CoverageSetup (infx_engine_set_query_coverage): one device batch per CoverageDepth, results in
+        input order.  A query whose options are refused (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than 64 rows,
+        a CoverageSetup out of range or with the lexical pre-screen) comes back empty with Result.error set; the others of the batch are unaffected."""
         sh = session.h if session is not None else self._default_session()
         runner = (session or self).search_packed
         out = [None] * len(queries)
@@ -336,7 +424,7 @@ class SearchEngine:
             try:
                 keys, scores, ties, counts, flags = runner(arena, offs, stride, depth, True)
             except Exception:
-                self.L.infx_engine_set_query_options(sh, 0, None, None)
+                _clear_query_options(self, sh)
                 raise
             for i, r in zip(idx, _query_results(self, sh, qs, status, keys, scores, ties, counts, flags)):
                 out[i] = r
@@ -345,6 +433,8 @@ class SearchEngine:
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
+        if q.coverage_setup is not None:
+            return self.search_queries([q])[0]
         if q.filter is not None or q.enable_facets or (q.enable_boost and q.boosts) or q.sort_by is not None:
             return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
                                         enable_boost=q.enable_boost, boosts=q.boosts, sort_by=q.sort_by, sort_ascending=q.sort_ascending)[0]
@@ -623,7 +713,25 @@ def _install_query_options(engine, sh, qs):
         o.sort_by = q.sort_by.encode() if q.sort_by is not None else None; o.sort_ascending = int(bool(q.sort_ascending))
     status = np.zeros(max(n, 1), np.int32)
     engine._check(engine.L.infx_engine_set_query_options(sh, n, arr, _p(status, C.c_int32)))
+    if any(q.coverage_setup is not None for q in qs):      # Query.CoverageSetup: installed beside the options, consumed by the same batch
+        sts = [_coverage_struct(q.coverage_setup) if q.coverage_setup is not None else None for q in qs]
+        ptrs = (C.POINTER(_CoverageSetup) * max(n, 1))(*[C.pointer(st) if st is not None else None for st in sts])
+        cst = np.zeros(max(n, 1), np.int32)
+        try:
+            engine._check(engine.L.infx_engine_set_query_coverage(sh, n, ptrs, _p(cst, C.c_int32)))
+        except Exception:
+            engine.L.infx_engine_set_query_options(sh, 0, None, None)
+            raise
+        status = np.where(status != 0, status, cst)
+    else:
+        engine._check(engine.L.infx_engine_set_query_coverage(sh, 0, None, None))
     return status[:n]
+
+
+def _clear_query_options(engine, sh):
+    """Drops the per-query options and coverage setups installed on session handle sh (a batch that failed before it consumed them)."""
+    engine.L.infx_engine_set_query_options(sh, 0, None, None)
+    engine.L.infx_engine_set_query_coverage(sh, 0, None, None)
 
 
 def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):

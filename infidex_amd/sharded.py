@@ -26,7 +26,7 @@ from typing import List, Sequence
 import os
 import numpy as np
 
-from .engine import SearchEngine, Session, Result, _p, INFX_NFEAT, pack_texts, _by_depth, _install_query_options, _query_results  # noqa: F401
+from .engine import SearchEngine, Session, Result, _p, INFX_NFEAT, pack_texts, _by_depth, _install_query_options, _query_results, _clear_query_options  # noqa: F401
 
 INFX_NCLASS = 136
 CHAIN = 0xFFFFFFFF
@@ -679,7 +679,7 @@ class ShardedSearcher:
             try:
                 res = self.search_packed(arena, offs, stride, depth, True)
             except Exception:
-                s.L.infx_engine_set_query_options(s.s.h, 0, None, None)
+                _clear_query_options(s.e, s.s.h)
                 raise
             for i, r in zip(idx, s.query_results(qs, status, res)):
                 out[i] = r
@@ -734,7 +734,7 @@ def simulate_search_queries(sessions: Sequence[ShardSession], queries, device="c
             res = simulate_shards_dev(sessions, arena, offs, stride, depth, True, device=device)
         except Exception:
             for s in sessions:
-                s.L.infx_engine_set_query_options(s.s.h, 0, None, None)
+                _clear_query_options(s.e, s.s.h)
             raise
         for out, s, st, r in zip(outs, sessions, status, res):
             for i, x in zip(idx, s.query_results(qs, st, r)):
