@@ -65,6 +65,14 @@ int32_t infx_engine_session_last_timings(infx_session* s, double* host_ms5, floa
 int32_t infx_engine_session_plan_breakdown(infx_session* S, double* out4);
 int32_t infx_engine_session_replay_breakdown(infx_session* S, float* ms4 /* scan (k_ex_walk x2 + k_ex_prefix + k_ex_theta), k_ex_chunk, k_ex_heap, k_exact1 of the last batch */);
 int32_t infx_engine_session_last_replay(infx_session* s, float* ms, uint32_t* why3);
+/* HIP streams the session launches on, by priority (infx_stream_budget) */
+int32_t infx_engine_session_stream_budget(infx_session* s, int32_t* normal, int32_t* high);
+/* The main hipStream_t of a session / of the engine's own session (infx_engine_search_batch).  Main streams come from the device's pool of INFX_MAIN_STREAMS (default 4)
+ * streams, fewest users first: the engine's own session is created first and takes the first, so with four sessions it shares that stream with the fourth.  Users of one
+ * stream run in order on it: their batches serialise, and the per-phase kernel times of one (infx_engine_session_last_timings) include the other's kernels queued in
+ * between.  That costs nothing while the engine's own session is idle, which is the intended use once sessions exist. */
+int32_t infx_engine_session_stream_native(infx_session* s, void** hip_stream);
+int32_t infx_engine_stream_native(infx_engine* e, void** hip_stream);
 
 /* Document-sharded operation: every rank indexes the whole corpus on the host (global df / avgdl / N), uploads
  * its contiguous doc range, and a batch runs as four phases with the collectives in between:

@@ -113,6 +113,12 @@ int32_t infx_stream_fill0(infx_stream* s, void* dev, uint64_t bytes);
 int32_t infx_stream_unpack(infx_stream* s, const void* src, uint64_t stride, int32_t nranks, int32_t nparts /* <= 4 */, const uint64_t* part_bytes, void* const* dsts);
 int32_t infx_stream_wait(infx_stream* s);
 int32_t infx_stream_native(infx_stream* s, void** hip_stream);      /* the hipStream_t the stream's kernels, copies and collectives are ordered on */
+/* The HIP streams this stream object launches on, by priority.  The runtime serves streams from a small pool of hardware queues and streams beyond the pool
+ * share one: normal = 1 (the hot path, one of the index's INFX_MAIN_STREAMS main streams), 2 with INFX_REPLAY_AUX=1 (the replay's k_ex_chunk launches side by
+ * side, on a stream of its own); high = 1 (planning) where the device offers stream priorities and INFX_PLAN_PRIORITY is not 0.  The main stream is shared with other
+ * infx_streams once more of them exist on the device than the pool has streams (infx_stream_native tells which): they run in order on it, and event timings on it span
+ * each other's kernels. */
+int32_t infx_stream_budget(infx_stream* s, int32_t* normal, int32_t* high);
 
 int32_t infx_stream_create(infx_index* idx, infx_stream** out);
 void    infx_stream_destroy(infx_stream* s);

@@ -1246,6 +1246,24 @@ int32_t infx_engine_session_create(infx_engine* e, infx_session** out) {
     *out = S; return INFX_OK;
 }
 void infx_engine_session_destroy(infx_session* S) { if (!S) return; if (S->stream) infx_stream_destroy(S->stream); delete S->batch; delete S; }
+int32_t infx_engine_session_stream_native(infx_session* S, void** hip_stream) {
+    if (!S || !S->stream) return efail(INFX_EINVAL, "null");
+    int32_t rc = infx_stream_native(S->stream, hip_stream);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+int32_t infx_engine_stream_native(infx_engine* e, void** hip_stream) {
+    if (!e || !e->def || !e->def->stream) return efail(INFX_EINVAL, "the engine has no GPU stream (not indexed, or no device)");
+    int32_t rc = infx_stream_native(e->def->stream, hip_stream);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+int32_t infx_engine_session_stream_budget(infx_session* S, int32_t* normal, int32_t* high) {
+    if (!S || !S->stream) return efail(INFX_EINVAL, "null");
+    int32_t rc = infx_stream_budget(S->stream, normal, high);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
 int32_t infx_engine_session_search_batch(infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
                                          int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                          uint32_t* out_counts, uint32_t* out_flags) {

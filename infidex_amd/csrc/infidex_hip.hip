@@ -25,6 +25,7 @@
 #include <functional>
 #include <unordered_map>
 #include <algorithm>
+#include <map>
 #include <mutex>
 #include <chrono>
 #include <thread>
@@ -66,6 +67,18 @@ struct DevIndex {
     const uint64_t* psOff; const int32_t* psDocs; uint32_t nSets;
 };
 
+// Main streams of the sessions, one pool per device for the whole process.  The runtime serves the streams of a process from a pool of hardware queues per
+// priority (4 by default): a stream created once that pool is full is put on the queue with the fewest streams, busy or idle, the most recently created first
+// among equals, and kernels of streams on one queue run one after the other.  With a stream per session created as the sessions came, the engine's own (idle)
+// session and the null stream held two of the four queues and the main streams of four sessions shared the other two (profiles/hwqueues_default.md).  The first
+// infx_create on a device therefore creates the main streams up front, before the uploads touch the null stream, and every session of every index on that device
+// draws the one with the fewest users: four sessions, four queues.  PRECONDITION: nothing else in the process has created HIP streams on the device before that
+// first infx_create; where a host program has, the pool's streams are placed by the runtime's sharing rule like any others and may share queues.  Users beyond
+// the pool share a stream, which is what the runtime would do with their queues.  INFX_MAIN_STREAMS (1..32, default 4) sizes the pool for processes that run
+// with more queues.  The streams live as long as the process.
+struct MainPool { std::mutex mu; std::vector<hipStream_t> st; std::vector<int> users; };
+static int32_t main_pool(int device, MainPool** out);
+
 struct infx_index {
     infx_config cfg;
     DevIndex d{};
@@ -87,6 +100,7 @@ struct infx_index {
     struct DevLookup* lk = nullptr;    // dictionaries / term trie of the device-side planning lookups (lookup.hip.inc); owned, freed by infx_destroy
     // Turnstile of the full-width phase (k_accumulate .. k_select) between the streams of an index: see infx_search_fused
     std::mutex turnMu; hipEvent_t turnEvent = nullptr;
+    struct MainPool* pool = nullptr;   // the device's main streams (below); owned by the process
     bool haveDict = false, haveTrie = false;
     bool hasAlias = false;            // the corpus text holds one of the 22 OrdinalIgnoreCase alias characters (infx_upload_docs counts them): Stage 2 runs its ALIAS instantiation
 };
@@ -276,8 +290,9 @@ struct infx_stream {
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
     // run on a stream of their own with the highest priority the device offers, so their few hundred waves are placed as soon as any CU has room.
     hipStream_t stPlan = nullptr, stMain = nullptr; hipEvent_t evPlan = nullptr;
+    int mainSlot = -1;                                             // stMain is the device's MainPool::st[mainSlot]: owned by the process, shared with the users beyond the pool
     hipEvent_t evTurn = nullptr;                                   // end of this stream's k_select: what the next batch's k_accumulate (another stream) waits for
-    hipStream_t stAux = nullptr; hipEvent_t evJoin = nullptr;      // the replay's two k_ex_chunk launches run side by side (both are tail-bound: one wave per chunk)
+    hipStream_t stAux = nullptr; hipEvent_t evJoin = nullptr;      // INFX_REPLAY_AUX=1 only: the replay's workgroup k_ex_chunk launches run beside the one-wave launch (all are tail-bound)
     hipEvent_t evA0, evA1, evS0, evS1, evC0, evC1, evP0, evP1, evF0, evF1, evX0, evX1, evSync;
     hipEvent_t evXa, evXb, evXc; bool timedReplayParts = false; float msReplayParts[4] = {0, 0, 0, 0};      // inside the replay: after the scan (k_ex_walk x2, k_ex_prefix, k_ex_theta), after the k_ex_chunk launches, after k_ex_heap
     bool timedReplay = false; float msReplay = 0.f; uint32_t lastFlagWhy[4] = {0, 0, 0, 0};     // exact replay of the last batch: kernel time, why its queries were flagged
@@ -673,8 +688,8 @@ static int32_t exact_chunk_tables(infx_stream* s, uint32_t nq, ExBufs& xb) {
                 (uint32_t*)s->exTasks + 2 * cap, (uint32_t*)s->exContEnd, nullptr, nullptr};
     return INFX_OK;
 }
-// The scan and the chunk pass of the parallel replay on stream `st` (k_ex_cand, k_ex_theta, k_ex_chunk<1|4|16>).  With an auxiliary stream the two
-// workgroup variants of k_ex_chunk run beside the one-wave variant (disjoint chunks; each launch ends in a tail of a few long tasks).
+// The scan and the chunk pass of the parallel replay on stream `st` (k_ex_cand, k_ex_theta, k_ex_chunk<16|4|1>, widest tasks first).  With an auxiliary stream
+// (INFX_REPLAY_AUX=1) the two workgroup variants of k_ex_chunk run beside the one-wave variant (disjoint chunks; each launch ends in a tail of a few long tasks).
 static int32_t launch_scan_and_chunks(infx_stream* s, uint32_t nq, Arena ar, ExBufs xb, const float* prior, bool useAux) {
     infx_index* ix = s->ix;
     const int rpc = 65536 / ix->d.R, nCont = (ix->d.nRanges + rpc - 1) / rpc;
@@ -800,6 +815,23 @@ static RcclApi& rccl_api() {
 }
 #define NCCLCHK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) return fail(INFX_ENCCL, #x ": %s", rccl_api().errstr(r_)); } while (0)
 
+static int32_t main_pool(int device, MainPool** out) {
+    static std::mutex mu; static std::map<int, MainPool*> pools;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = pools.find(device);
+    if (it == pools.end()) {
+        static const int nMain = [] { const char* e = getenv("INFX_MAIN_STREAMS"); const int n = e ? atoi(e) : 4; return n < 1 ? 1 : n > 32 ? 32 : n; }();
+        MainPool* mp = new MainPool();
+        for (int i = 0; i < nMain; i++) {
+            hipStream_t st = nullptr; const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+            if (e != hipSuccess) { for (hipStream_t p : mp->st) hipStreamDestroy(p); delete mp; return fail(INFX_EHIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(e)); }
+            mp->st.push_back(st); mp->users.push_back(0);
+        }
+        it = pools.emplace(device, mp).first;
+    }
+    *out = it->second; return INFX_OK;
+}
+
 extern "C" {
 
 const char* infx_last_error(void) { return g_err.c_str(); }
@@ -818,6 +850,7 @@ int32_t infx_create(const infx_config* cfg, infx_index** out) {
     ix->d.R = R; ix->d.rshift = __builtin_ctz(R);
     if (ix->cfg.max_depth <= 0) ix->cfg.max_depth = 500;
     if (ix->cfg.max_depth > SEL_CAP / 2) { delete ix; return fail(INFX_EINVAL, "max_depth too large%s"); }
+    { int32_t rc_ = main_pool(cfg->device, &ix->pool); if (rc_) { delete ix; return rc_; } }
     *out = ix;
     return INFX_OK;
 }
@@ -1098,13 +1131,15 @@ int32_t infx_stream_native(infx_stream* s, void** hip_stream) {
     if (!s || !hip_stream) return fail(INFX_EINVAL, "null argument%s");
     *hip_stream = (void*)s->st; return INFX_OK;
 }
+int32_t infx_stream_budget(infx_stream* s, int32_t* normal, int32_t* high) {
+    if (!s || !normal || !high) return fail(INFX_EINVAL, "null argument%s");
+    *normal = (s->stMain ? 1 : 0) + (s->stAux ? 1 : 0); *high = s->stPlan ? 1 : 0; return INFX_OK;
+}
 
 int32_t infx_stream_create(infx_index* ix, infx_stream** out) {
     if (!ix || !out) return fail(INFX_EINVAL, "null argument%s");
     HIPCHK(enter_device(ix->cfg.device));
     infx_stream* s = new infx_stream(); s->ix = ix;
-    HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    s->stMain = s->st;
     {
         static const bool noPrio = [] { const char* e = getenv("INFX_PLAN_PRIORITY"); return e && e[0] == '0'; }();
         int least = 0, greatest = 0;
@@ -1113,9 +1148,11 @@ int32_t infx_stream_create(infx_index* ix, infx_stream** out) {
         else { (void)hipGetLastError(); s->stPlan = nullptr; }
     }
     {
-        static const bool noAux = [] { const char* e = getenv("INFX_REPLAY_AUX"); return e && e[0] == '0'; }();
-        if (!noAux && hipStreamCreateWithFlags(&s->stAux, hipStreamNonBlocking) == hipSuccess) HIPCHK(hipEventCreateWithFlags(&s->evJoin, hipEventDisableTiming));
-        else { (void)hipGetLastError(); s->stAux = nullptr; }
+        // Opt-in (INFX_REPLAY_AUX=1), for processes with more hardware queues than streams.  The runtime serves streams from a small pool of hardware queues
+        // (4 by default) and a stream beyond the pool shares a queue, idle or not: with a second normal-priority stream per session the main streams of two
+        // sessions met on one queue and ran one after the other (profiles/hwqueues_default.md).  Not created unless asked for.
+        static const bool aux = [] { const char* e = getenv("INFX_REPLAY_AUX"); return e && e[0] == '1'; }();
+        if (aux) { HIPCHK(hipStreamCreateWithFlags(&s->stAux, hipStreamNonBlocking)); HIPCHK(hipEventCreateWithFlags(&s->evJoin, hipEventDisableTiming)); }
     }
     HIPCHK(hipEventCreateWithFlags(&s->evTurn, hipEventDisableTiming));
     hipEvent_t* ev[] = {&s->evA0, &s->evA1, &s->evS0, &s->evS1, &s->evC0, &s->evC1, &s->evP0, &s->evP1, &s->evF0, &s->evF1, &s->evX0, &s->evX1, &s->evXa, &s->evXb, &s->evXc};
@@ -1125,6 +1162,12 @@ int32_t infx_stream_create(infx_index* ix, infx_stream** out) {
     HIPCHK(hipMalloc((void**)&s->dStats, 64)); HIPCHK(hipMemset(s->dStats, 0, 64));
     HIPCHK(hipMalloc((void**)&s->dExactStat, 32)); HIPCHK(hipMemset(s->dExactStat, 0, 32));      // [0..3] replay outcome counters, [4..7] k_select flag reasons
     HIPCHK(hipMalloc((void**)&s->exCounters, 32)); HIPCHK(hipMemset(s->exCounters, 0, 32));
+    {   // taken last, so that a creation that fails above leaves no user count behind: the device's main stream with the fewest users (the first among equals: the engine's own session, created first and idle while sessions run, is the one shared)
+        MainPool* mp = ix->pool; std::lock_guard<std::mutex> lk(mp->mu);
+        int best = 0; for (int i = 1; i < (int)mp->st.size(); i++) if (mp->users[i] < mp->users[best]) best = i;
+        s->st = mp->st[best]; s->mainSlot = best; mp->users[best]++;
+    }
+    s->stMain = s->st;
     *out = s; return INFX_OK;
 }
 void infx_stream_destroy(infx_stream* s) {
@@ -1149,7 +1192,7 @@ void infx_stream_destroy(infx_stream* s) {
     if (s->evTurn) hipEventDestroy(s->evTurn);
     if (s->stAux) { hipStreamSynchronize(s->stAux); hipStreamDestroy(s->stAux); }
     if (s->stPlan) { hipStreamSynchronize(s->stPlan); hipStreamDestroy(s->stPlan); }
-    if (s->st) hipStreamDestroy(s->st);
+    if (s->mainSlot >= 0) { std::lock_guard<std::mutex> lk(s->ix->pool->mu); s->ix->pool->users[s->mainSlot]--; }
     delete s;
 }
 
