@@ -244,13 +244,21 @@ int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, i
 int32_t infx_engine_column_count(infx_engine* e);
 int32_t infx_engine_column_info(infx_engine* e, int32_t col, char* name, int32_t cap, int32_t* facetable, int32_t* num_values);
 int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, char* out, int32_t cap);
+/* Post rows: how many returned rows per query the filter, facets, boosts, sort-by and browse rows accept — INFX_FILTER_MAX_ROWS (64, the default) up to
+ * INFX_POST_MAX_ROWS (1024 = the largest max_depth, so no text query returns more).  The reference post-filters the truncated top-MaxNumberOfRecordsToReturn
+ * rows (SearchEngine.cs:304-310): a caller who wants twenty rows that pass a selective filter asks for a few hundred.  An engine left at the default
+ * behaves exactly as before, refusals at 65 rows included; queries of at most 64 rows run on the same one-wave kernels whatever the setting, wider ones
+ * on workgroup-per-query kernels launched only for a batch that has one.  Legal between create and the first search (the sessions size their facet
+ * readout by it); afterwards, and outside the range, INFX_EINVAL with a message. */
+int32_t infx_engine_set_post_rows(infx_engine* e, int32_t rows);
+int32_t infx_engine_get_post_rows(infx_engine* e, int32_t* out);
 int32_t infx_engine_set_filter(infx_session* s, const char* expr_utf8 /* NULL = no filter */, int32_t enable_facets, uint32_t* n_in_filter);
 int32_t infx_engine_facet_column_count(infx_session* s);
 int32_t infx_engine_last_facets(infx_session* s, uint32_t nq, uint32_t qi, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap);
 /* A query whose text is empty (or all whitespace) and that has EnableFacets — through infx_engine_set_filter(.., enable_facets = 1, ..) or its
  * infx_query_options — is a browse query (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346): it returns the first max_results documents
  * in indexing order that are not Deleted and whose key's first live document passes the filter, each with score 65535 and tiebreaker 0, and the facets
- * of those rows; Boosts, SortBy and coverage do not apply.  NumberOfDocumentsInFilter, the 64-row limit and the refusals are those of a text query.
+ * of those rows; Boosts, SortBy and coverage do not apply.  NumberOfDocumentsInFilter, the row limit (the engine's post rows, 64 by default) and the refusals are those of a text query.
  * Without EnableFacets (or without a facetable column) a blank query returns nothing, as before.
  *
  * FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): infx_engine_facets_all counts, in one device pass, the values of every
@@ -278,7 +286,7 @@ int32_t infx_engine_set_sort(infx_session* s, const char* field, int32_t ascendi
  * >= every query's (else INFX_EINVAL); its enable_coverage is ANDed with each query's; CoverageDepth stays one per call.  A query with no filter, facets,
  * boosts or sort behaves as in a plain batch.  A query is rejected on its own — empty result, result flag bit 4 (INFX_RESULT_REJECTED), its status in
  * out_status[i] and its message from infx_engine_query_error — for a filter syntax error (INFX_EINVAL), MATCHES (INFX_EUNSUPPORTED), more than
- * INFX_MAX_BOOSTS boosts with a filter (INFX_ECAPACITY), or post-processing on more than INFX_FILTER_MAX_ROWS rows (INFX_EUNSUPPORTED; facets count as
+ * INFX_MAX_BOOSTS boosts with a filter (INFX_ECAPACITY), or post-processing on more rows than the engine's post rows (INFX_FILTER_MAX_ROWS unless infx_engine_set_post_rows raised them; INFX_EUNSUPPORTED; facets count as
  * post-processing only when a facetable column exists); its neighbours are unaffected.  Installing while a session-wide filter, facets, boosts or sort is installed (infx_engine_set_filter / _set_boosts / _set_sort) is
  * INFX_EINVAL, and so is the reverse; a search of another nq fails with INFX_EINVAL and clears the options.  nq = 0 clears.
  * Filter.NumberOfDocumentsInFilter: the expressions the batch uses for the first time are counted in one k_filter_count_multi launch enqueued with the

@@ -279,10 +279,18 @@ typedef struct infx_filter infx_filter;
 #define INFX_FOP_TERN 4
 #define INFX_FOP_LIT  5
 #define INFX_FILTER_MAX_OPS 256
-#define INFX_FILTER_MAX_ROWS 64         /* post-filter / facets run on <= 64 returned rows per query (Query.MaxNumberOfRecordsToReturn) */
+#define INFX_FILTER_MAX_ROWS 64         /* post-filter / facets run on <= 64 returned rows per query (Query.MaxNumberOfRecordsToReturn) unless the index is configured for more */
+#define INFX_POST_MAX_ROWS 1024         /* the most rows per query an index can be configured to post-process (infx_set_post_rows): SEL_CAP / 2, the largest max_depth */
 #define INFX_MAX_FACET_COLS 8
 typedef struct infx_filter_op { uint32_t op; uint32_t arg; } infx_filter_op;                 /* arg: leaf index for INFX_FOP_LEAF */
 typedef struct infx_filter_leaf { uint32_t col; uint32_t table_off; uint32_t num_values; uint32_t reserved; } infx_filter_leaf;   /* col 0xFFFFFFFF: no such field (null) */
+/* Post rows of the index: how many returned rows per query the post-filter, facets, boosts, sort-by and browse rows accept, INFX_FILTER_MAX_ROWS (the
+ * default) .. INFX_POST_MAX_ROWS.  A query with post-processing that asks for at most INFX_FILTER_MAX_ROWS rows runs on the one-wave kernels whatever the
+ * setting; one that asks for more, up to the post rows, runs on workgroup-per-query kernels (k_postfilter_wide, k_postproc_wide, k_browse_rows_wide) that
+ * are launched only for a batch that has such a query.  The post rows are also the stride of the facet pairs of infx_last_facets.  Exclusive call, between
+ * searches (as infx_upload_column). */
+int32_t infx_set_post_rows(infx_index* idx, int32_t rows);
+int32_t infx_get_post_rows(infx_index* idx, int32_t* rows);
 int32_t infx_upload_column(infx_index* idx, uint32_t col, uint32_t total_docs, const uint32_t* codes, uint32_t num_values);
 int32_t infx_filter_create(infx_index* idx, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
                            uint32_t ntable_words, const uint32_t* tables, infx_filter** out);
@@ -293,13 +301,15 @@ int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count);
  * infx_shard_finalize filters its result rows on the device before they are returned and counts the facet values of the kept rows. */
 int32_t infx_stream_set_postfilter(infx_stream* s, infx_filter* f, uint32_t nfacet, const uint32_t* facet_cols);
 /* Facets of the last search on this stream: for query q and facet column k, n_out[q*nfacet+k] pairs at codes_out / counts_out
- * [(q*nfacet+k)*INFX_FILTER_MAX_ROWS ..], in row order of first occurrence (the host orders them: count desc, value asc). */
+ * [(q*nfacet+k)*R ..], R = the index's post rows (infx_get_post_rows; INFX_FILTER_MAX_ROWS unless set), in row order of first occurrence (the host orders them: count desc, value asc). */
 int32_t infx_last_facets(infx_stream* s, uint32_t nq, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out);
+/* ... of query q and facet column k alone: *n_out pairs (at most the index's post rows) at codes_out / counts_out */
+int32_t infx_last_facets_of(infx_stream* s, uint32_t nq, uint32_t q, uint32_t k, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out);
 
 /* ---- Query.Boosts + Query.SortBy on the returned rows (k_postproc) ----------------------------------------------------------------------
  * Replaces ResultProcessor.ApplyBoosts / ApplySort (Scoring/ResultProcessor.cs:75-141, 180-201) as SearchEngine.ApplyPostProcessing calls them
  * after ApplyFilter (SearchEngine.cs:348-361).  Installed on a stream, they apply to every following infx_search_fused / infx_shard_finalize,
- * after the post-filter, on at most INFX_FILTER_MAX_ROWS rows per query (more: INFX_EUNSUPPORTED).  Both steps end in the BCL's unstable
+ * after the post-filter, on at most the index's post rows per query (INFX_FILTER_MAX_ROWS unless infx_set_post_rows raised them; more: INFX_EUNSUPPORTED).  Both steps end in the BCL's unstable
  * introsort (Array.Sort with a Comparison), replayed on the device, so rows that compare equal come back in the reference's order. */
 #define INFX_MAX_BOOSTS 8
 /* Sort rank of column col: rank[v] for each of its num_values distinct values (codes), dense — equal values share a rank — in the order of
@@ -320,7 +330,7 @@ int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, in
  * q's descriptor — filter = program index or -1, flags INFX_QP_*, sort_col = column (0xFFFFFFFF: no such field, every row null), boosts
  * [boost_off, + nboost) with nboost <= INFX_MAX_BOOSTS.  nfacet / facet_cols: the columns a query with INFX_QP_FACETS counts (infx_last_facets;
  * 0 pairs for the queries without).  A query without filter, facets, boosts or sort passes through unchanged, whatever its number of rows; a query
- * with post-processing whose rows exceed INFX_FILTER_MAX_ROWS comes back empty with result flag INFX_RESULT_REJECTED (the others of the batch are
+ * with post-processing whose rows exceed the index's post rows (INFX_FILTER_MAX_ROWS by default) comes back empty with result flag INFX_RESULT_REJECTED (the others of the batch are
  * unaffected).  ncount: programs [0, ncount) are counted over every document of the corpus that is not Deleted (Filter.NumberOfDocumentsInFilter,
  * whole corpus on every shard: each holds the whole columns and the global Deleted flags) by k_filter_count_multi, enqueued with the batch: the
  * counts land in counts_out when the batch's results do.  Exclusive with infx_stream_set_postfilter / _set_boosts / _set_sort (INFX_EINVAL); the
@@ -342,7 +352,7 @@ int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_pr
 int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches);
 
 /* ---- browse rows: a query with no text and EnableFacets (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346) -------------------------
- * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= INFX_FILTER_MAX_ROWS, else INFX_EUNSUPPORTED) documents in
+ * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= the index's post rows, else INFX_EUNSUPPORTED) documents in
  * internal order that are not Deleted and that its filter accepts — the filter of its infx_query_post descriptor (which must carry INFX_QP_FACETS) or
  * the stream's post-filter (with facet columns installed) — each with score 65535 and tiebreaker 0; result flags 0.  The rows are written where a text
  * query's rows land before the post-filter, so the facets of infx_last_facets are those of the rows.  All browse queries of a batch are grouped by

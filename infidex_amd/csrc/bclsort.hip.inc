@@ -10,6 +10,8 @@
 //   int  S::fget(int i) / void S::fset(int i, int v)    slot i of the pending-range stack (BCL_MAX_FRAMES slots)
 // The recursion of IntroSort becomes that explicit stack.  Pending ranges are disjoint, so the order they are sorted in does not change the result;
 // the depths on the stack strictly decrease from bottom to top, so it never holds more than depthLimit + 1 = 2 * (log2 n + 1) + 1 ranges (15 for n <= 64).
+// Two entry points over the same sequence: bcl_introsort for n <= BCL_MAX_N (k_postproc: frames in lanes, 10-bit length) and bcl_introsort_wide for
+// n <= BCL_WIDE_MAX_N (k_postproc_wide: frames in LDS, 11-bit length, 23 of BCL_WIDE_MAX_FRAMES slots at n = 1024).
 #pragma once
 #ifndef BCL_FN
 #define BCL_FN __device__ __forceinline__
@@ -19,6 +21,8 @@
 #endif
 #define BCL_MAX_N 64               // sequences of at most 64 elements (a frame packs lo / length / depth into 10 bits each)
 #define BCL_MAX_FRAMES 16
+#define BCL_WIDE_MAX_N 1024         // the wide entry point: lo in 10 bits, length in 11, depth (<= 22) above them
+#define BCL_WIDE_MAX_FRAMES 24
 #define BCL_SMALL 16               // IntrosortSizeThreshold
 
 // float.CompareTo(float): NaN is less than every number and equal to NaN; -0 == +0
@@ -74,19 +78,17 @@ template <class S> BCL_FN int bcl_partition(S& s, int lo, int n) {
     if (l != hi - 1) bcl_swap(s, lo + l, lo + hi - 1);
     return l;
 }
-BCL_FN int bcl_frame(int lo, int n, int depth) { return lo | (n << 10) | (depth << 20); }
-
-// Array.Sort(keys[0..n), comparison), n <= BCL_MAX_N
-template <class S> BCL_FN void bcl_introsort(S& s, int n) {
+// Array.Sort(keys[0..n), comparison); a frame packs lo (10 bits) / length (NBITS bits) / depth, the stack holds MAXF frames
+template <class S, int NBITS, int MAXF> BCL_FN void bcl_introsort_frames(S& s, int n) {
     if (n < 2) return;
     int lg = 0;
     for (unsigned x = (unsigned)n; x >>= 1;) lg++;
     int sp = 0;
-    s.fset(sp++, bcl_frame(0, n, 2 * (lg + 1)));
+    s.fset(sp++, 0 | (n << 10) | ((2 * (lg + 1)) << (10 + NBITS)));
     while (sp > 0) {
         const int f = s.fget(--sp);
         const int lo = f & 1023;
-        int part = (f >> 10) & 1023, depth = f >> 20;
+        int part = (f >> 10) & ((1 << NBITS) - 1), depth = f >> (10 + NBITS);
         while (part > 1) {
             if (part <= BCL_SMALL) {
                 BCL_BRANCH(0);
@@ -99,8 +101,12 @@ template <class S> BCL_FN void bcl_introsort(S& s, int n) {
             depth--;
             BCL_BRANCH(1);
             const int p = bcl_partition(s, lo, part);
-            if (part - (p + 1) > 1 && sp < BCL_MAX_FRAMES) s.fset(sp++, bcl_frame(lo + p + 1, part - (p + 1), depth));     // IntroSort(keys[(p+1)..part), depth)
+            if (part - (p + 1) > 1 && sp < MAXF) s.fset(sp++, (lo + p + 1) | ((part - (p + 1)) << 10) | (depth << (10 + NBITS)));     // IntroSort(keys[(p+1)..part), depth)
             part = p;
         }
     }
 }
+// n <= BCL_MAX_N
+template <class S> BCL_FN void bcl_introsort(S& s, int n) { bcl_introsort_frames<S, 10, BCL_MAX_FRAMES>(s, n); }
+// n <= BCL_WIDE_MAX_N
+template <class S> BCL_FN void bcl_introsort_wide(S& s, int n) { bcl_introsort_frames<S, 11, BCL_WIDE_MAX_FRAMES>(s, n); }

@@ -11,9 +11,11 @@
 //                    alone holds rows[g] matches (its stored count is then a lower bound >= rows[g], which is all the prefix needs).
 //   k_browse_prefix  per group the exclusive prefix of its range counts; the total is the group's NumberOfDocumentsInFilter.
 //   k_browse_gather  one wave per (range, group) whose prefix lies below rows[g] and whose count is not 0: evaluates the range again, 64 documents
-//                    per step, ballot compaction -> rowDocs[g * INFX_FILTER_MAX_ROWS + prefix + i].  At most rows[g] ranges per group do any work.
+//                    per step, ballot compaction -> rowDocs[g * rowStride + prefix + i] (rowStride: the index's post rows).  At most rows[g] ranges
+//                    per group do any work.
 //   k_browse_rows    one wave per browse query: the first min(total, MaxNumberOfRecordsToReturn) documents of its group become its result rows
 //                    (key, score 65535, tiebreaker 0, and the document the post-filter / facets look at) where k_finalize left an empty result.
+//   k_browse_rows_wide  the same with one workgroup per query, launched instead when a query of the batch wants more than 64 rows.
 // Duplicate keys (firstLive != nullptr): the rows' filter looks at firstLive[d], the first live document carrying d's key
 // (ResultProcessor.ApplyFilter -> GetDocumentByPublicKey), while NumberOfDocumentsInFilter evaluates each live document's own fields
 // (ResultProcessor.cs:39-54): the DUP instantiation holds both sets of codes and adds the own-field count with one atomic per (range, group).
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(BRW_THREADS) void k_browse_prefix(const DevBrowseGr
 __global__ __launch_bounds__(WAVE) void k_browse_gather(const DevBrowseGroup* __restrict__ groups, uint32_t G, DevColumns cols,
                                                          int32_t n, uint32_t tiles, uint32_t nRanges, const uint8_t* __restrict__ deleted,
                                                          const int32_t* __restrict__ firstLive, const uint32_t* __restrict__ rangeCnt,
-                                                         const uint32_t* __restrict__ rangePre, int32_t* __restrict__ rowDocs) {
+                                                         const uint32_t* __restrict__ rangePre, int32_t* __restrict__ rowDocs, uint32_t rowStride) {
     const uint32_t r = blockIdx.x; const int lane = threadIdx.x;
     const int32_t lo = brw_range_start(r, tiles, nRanges, n), hi = brw_range_start(r + 1, tiles, nRanges, n);
     for (uint32_t g = blockIdx.y; g < G; g += gridDim.y) {
@@ -126,26 +128,41 @@ __global__ __launch_bounds__(WAVE) void k_browse_gather(const DevBrowseGroup* __
             if (Gp.prog >= 0) { const int32_t rep = firstLive && live ? firstLive[d] : d; hit = filt_eval(f, cols, rep) && live; }
             const unsigned long long b = __ballot(hit);
             const uint32_t p = pos + (uint32_t)__popcll(b & ((1ull << lane) - 1));
-            if (hit && p < Gp.rows) rowDocs[(size_t)g * INFX_FILTER_MAX_ROWS + p] = d;
+            if (hit && p < Gp.rows) rowDocs[(size_t)g * rowStride + p] = d;
             pos += (uint32_t)__popcll(b);
         }
     }
 }
 
-// one wave per browse query: its rows, where k_finalize wrote an empty result (counts 0, flags 0)
+// one wave per browse query: its rows (at most 64), where k_finalize wrote an empty result (counts 0, flags 0)
 __global__ __launch_bounds__(WAVE) void k_browse_rows(const DevBrowseQuery* __restrict__ bq, const DevBrowseGroup* __restrict__ groups, const uint32_t* __restrict__ totals,
-                                                       const int32_t* __restrict__ rowDocs, const long long* __restrict__ docKeyAll, const int32_t* __restrict__ firstLive,
+                                                       const int32_t* __restrict__ rowDocs, uint32_t rowStride, const long long* __restrict__ docKeyAll, const int32_t* __restrict__ firstLive,
                                                        int32_t stride, long long* __restrict__ keys, float* __restrict__ scores, uint8_t* __restrict__ ties,
                                                        int32_t* __restrict__ docs, uint32_t* __restrict__ counts) {
     const DevBrowseQuery Q = bq[blockIdx.x]; const uint32_t lane = threadIdx.x;
     const uint32_t nrow = min(min(totals[Q.group], groups[Q.group].rows), min(Q.rows, (uint32_t)stride));
     const size_t o = (size_t)Q.q * stride;
     if (lane < nrow) {
-        const int32_t d = rowDocs[(size_t)Q.group * INFX_FILTER_MAX_ROWS + lane];
+        const int32_t d = rowDocs[(size_t)Q.group * rowStride + lane];
         keys[o + lane] = docKeyAll[d]; scores[o + lane] = BRW_SCORE; if (ties) ties[o + lane] = 0;
         docs[o + lane] = firstLive ? firstLive[d] : d;                  // ApplyFilter and BuildFacets look the row up by key: the key's first live document
     }
     if (lane == 0) counts[Q.q] = nrow;
+}
+// one workgroup per browse query: up to rowStride rows
+__global__ __launch_bounds__(BRW_THREADS) void k_browse_rows_wide(const DevBrowseQuery* __restrict__ bq, const DevBrowseGroup* __restrict__ groups, const uint32_t* __restrict__ totals,
+                                                                   const int32_t* __restrict__ rowDocs, uint32_t rowStride, const long long* __restrict__ docKeyAll,
+                                                                   const int32_t* __restrict__ firstLive, int32_t stride, long long* __restrict__ keys, float* __restrict__ scores,
+                                                                   uint8_t* __restrict__ ties, int32_t* __restrict__ docs, uint32_t* __restrict__ counts) {
+    const DevBrowseQuery Q = bq[blockIdx.x];
+    const uint32_t nrow = min(min(min(totals[Q.group], groups[Q.group].rows), min(Q.rows, (uint32_t)stride)), rowStride);
+    const size_t o = (size_t)Q.q * stride;
+    for (uint32_t r = threadIdx.x; r < nrow; r += BRW_THREADS) {
+        const int32_t d = rowDocs[(size_t)Q.group * rowStride + r];
+        keys[o + r] = docKeyAll[d]; scores[o + r] = BRW_SCORE; if (ties) ties[o + r] = 0;
+        docs[o + r] = firstLive ? firstLive[d] : d;
+    }
+    if (threadIdx.x == 0) counts[Q.q] = nrow;
 }
 
 // ---- whole-corpus facets -------------------------------------------------------------------------------------------------------------------

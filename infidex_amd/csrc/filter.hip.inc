@@ -7,6 +7,10 @@
 //                         per query, one row per lane; ballot compaction keeps the row order; facet values are counted with wave shuffles.  Each
 //                         query reads its own descriptor (DevQPost: filter program or none, facets on or off); the session-wide setters stage one
 //                         descriptor that every query shares.
+//   k_postfilter_wide     the same for a query flagged QP_WIDE (an index configured with infx_set_post_rows, a query asking for more than
+//                         INFX_FILTER_MAX_ROWS rows): one workgroup per query, up to INFX_POST_MAX_ROWS rows held in registers, row order kept by a
+//                         per-wave ballot + a prefix over the wave totals in LDS; facet values counted by an all-pairs pass over the kept rows' codes
+//                         in LDS.  k_postfilter skips those queries, k_postfilter_wide every other one.
 struct DevFilter {
     const infx_filter_op* ops; uint32_t nops;
     const infx_filter_leaf* leaves; uint32_t nleaves;
@@ -75,26 +79,28 @@ __global__ __launch_bounds__(FCM_THREADS) void k_filter_count_multi(const DevFil
 #define QP_FACETS INFX_QP_FACETS           // count the facet columns of the kept rows
 #define QP_SORT   INFX_QP_SORT             // Query.SortBy set (sortCol 0xFFFFFFFF: no such field)
 #define QP_ASC    INFX_QP_ASC              // Query.SortAscending
-#define QP_REJECTED INFX_RESULT_REJECTED   // result flag of a query whose post-processing needs more than INFX_FILTER_MAX_ROWS rows
+#define QP_WIDE   8u                       // internal: post-processing on more than INFX_FILTER_MAX_ROWS rows (the finalize sets it; the *_wide kernels take the query)
+#define QP_REJECTED INFX_RESULT_REJECTED   // result flag of a query whose post-processing needs more rows than the index is configured for
 struct DevQPost { int32_t filter; uint32_t flags; uint32_t sortCol; uint32_t boostOff; uint32_t nboost; uint32_t pad[3]; };   // filter: program index, -1 none
 struct DevQBoost { int32_t prog; int32_t strength; };
 // One batch's post-processing, staged on the stream by the finalize that launches the kernels
 struct DevPostBatch {
     const DevFilter* progs; const DevQBoost* boosts; const DevQPost* desc; uint32_t descStride;       // query q: desc[q * descStride] (0: shared by all)
     const uint32_t* rank[FILT_MAXCOL];                                                                // sort ranks of the columns (nullptr: not uploaded)
-    // rows of query q: [q * stride, + counts[q]), counts[q] <= INFX_FILTER_MAX_ROWS for a query with post-processing — filtered, boosted, reordered in place
+    // rows of query q: [q * stride, + counts[q]), counts[q] <= INFX_FILTER_MAX_ROWS (QP_WIDE: the index's post rows) for a query with post-processing — filtered, boosted, reordered in place
     long long* keys; float* scores; uint8_t* ties; int32_t* docs; uint32_t* counts; uint32_t* flags; int32_t stride;
     // the batch's fused queries when it has browse queries (INFX_FQ_BROWSE: their rows take no boosts and no sort-by, SearchEngine.cs:292-293), else nullptr
     const infx_fused_query* fqs;
 };
 
-// facets of query q, column c: fCodes / fCounts [(q * nfacet + c) * INFX_FILTER_MAX_ROWS ..], fN[q * nfacet + c] (0 for a query without facets)
+// facets of query q, column c: fCodes / fCounts [(q * nfacet + c) * frows ..] (frows: the index's post rows), fN[q * nfacet + c] (0 for a query without facets)
 __global__ __launch_bounds__(WAVE) void k_postfilter(const DevPostBatch* __restrict__ pb, DevColumns cols, int nfacet, const uint32_t* __restrict__ facetCols,
-                                                      uint32_t* __restrict__ fCodes, uint32_t* __restrict__ fCounts, uint32_t* __restrict__ fN) {
+                                                      uint32_t* __restrict__ fCodes, uint32_t* __restrict__ fCounts, uint32_t* __restrict__ fN, uint32_t frows) {
     const int q = blockIdx.x, lane = threadIdx.x;
     const DevQPost D = pb->desc[(size_t)q * pb->descStride];
     const bool haveFilter = D.filter >= 0, facets = (D.flags & QP_FACETS) != 0 && nfacet > 0;
-    if (!facets && lane < nfacet) fN[(size_t)q * nfacet + lane] = 0;
+    if (!facets && lane < nfacet) fN[(size_t)q * nfacet + lane] = 0;           // (also for a QP_WIDE query: k_postfilter_wide is not launched for a batch whose wide queries only have boosts / sort-by)
+    if (D.flags & QP_WIDE) return;                                              // k_postfilter_wide's
     if (!haveFilter && !facets) return;                                         // no post-filter: the rows pass through, whatever their number
     uint32_t* counts = pb->counts;
     if (counts[q] > (uint32_t)WAVE) {                                           // more rows than one wave holds: the query is rejected (empty, flag bit 4)
@@ -123,8 +129,78 @@ __global__ __launch_bounds__(WAVE) void k_postfilter(const DevPostBatch* __restr
             if (keep && cj == code) { cnt++; if (j < lane) first = false; }
         }
         const unsigned long long fb = __ballot(first);
-        const size_t fo = ((size_t)q * nfacet + c) * INFX_FILTER_MAX_ROWS;
+        const size_t fo = ((size_t)q * nfacet + c) * frows;
         if (first) { const uint32_t p = (uint32_t)__popcll(fb & ((1ull << lane) - 1)); fCodes[fo + p] = code; fCounts[fo + p] = cnt; }
         if (lane == 0) fN[(size_t)q * nfacet + c] = (uint32_t)__popcll(fb);
+    }
+}
+
+// ---- the same on up to INFX_POST_MAX_ROWS rows: one workgroup per query ----
+#define PW_THREADS 256
+#define PW_ROWS (INFX_POST_MAX_ROWS / PW_THREADS)      // rows per thread: row j * PW_THREADS + thread, j < PW_ROWS
+// Ordered compaction over the workgroup: item (j, thread) precedes (j', thread') iff j < j' or j == j' and thread < thread' — the row order.
+// pos[j] = set flags before item (j, thread); returns their total.  wtot: PW_ROWS * (PW_THREADS / WAVE) words of LDS, free again on return.
+__device__ __forceinline__ uint32_t pw_compact(const bool (&f)[PW_ROWS], uint32_t (&pos)[PW_ROWS], uint32_t* wtot) {
+    const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) {
+        const unsigned long long b = __ballot(f[j]);
+        pos[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
+        if (lane == 0) wtot[j * (PW_THREADS / WAVE) + wave] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    uint32_t run = 0;
+    _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++)
+        _Pragma("unroll") for (int w = 0; w < PW_THREADS / WAVE; w++) { if (w == wave) pos[j] += run; run += wtot[j * (PW_THREADS / WAVE) + w]; }
+    __syncthreads();
+    return run;
+}
+// cap: the index's post rows (<= INFX_POST_MAX_ROWS), also the stride of the facet pairs
+__global__ __launch_bounds__(PW_THREADS) void k_postfilter_wide(const DevPostBatch* __restrict__ pb, DevColumns cols, int nfacet, const uint32_t* __restrict__ facetCols,
+                                                                 uint32_t* __restrict__ fCodes, uint32_t* __restrict__ fCounts, uint32_t* __restrict__ fN, uint32_t cap) {
+    __shared__ uint32_t wtot[PW_ROWS * (PW_THREADS / WAVE)];
+    __shared__ uint32_t fcode[INFX_POST_MAX_ROWS];                              // the kept rows' codes of one facet column, in row order
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const DevQPost D = pb->desc[(size_t)q * pb->descStride];
+    if (!(D.flags & QP_WIDE)) return;                                           // k_postfilter's
+    const bool haveFilter = D.filter >= 0, facets = (D.flags & QP_FACETS) != 0 && nfacet > 0;
+    if (!facets && tid < nfacet) fN[(size_t)q * nfacet + tid] = 0;
+    if (!haveFilter && !facets) return;
+    uint32_t* counts = pb->counts;
+    const uint32_t n = counts[q];
+    if (n > cap || n > (uint32_t)INFX_POST_MAX_ROWS) {                          // more rows than the index is configured for: rejected (empty, flag bit 4)
+        if (tid == 0) { counts[q] = 0; pb->flags[q] |= QP_REJECTED; }
+        if (facets && tid < nfacet) fN[(size_t)q * nfacet + tid] = 0;
+        return;
+    }
+    const size_t o = (size_t)q * pb->stride;
+    long long* keys = pb->keys; float* scores = pb->scores; uint8_t* ties = pb->ties; int32_t* docs = pb->docs;
+    long long k[PW_ROWS]; float s[PW_ROWS]; uint8_t t[PW_ROWS]; int32_t d[PW_ROWS]; bool keep[PW_ROWS]; uint32_t pos[PW_ROWS];
+    DevFilter f{}; if (haveFilter) f = pb->progs[D.filter];
+    _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) {
+        const uint32_t r = (uint32_t)(j * PW_THREADS + tid);
+        const bool have = r < n;
+        k[j] = 0; s[j] = 0.f; t[j] = 0; d[j] = 0;
+        if (have) { k[j] = keys[o + r]; s[j] = scores[o + r]; if (ties) t[j] = ties[o + r]; d[j] = docs[o + r]; }
+        keep[j] = have && (!haveFilter || filt_eval(f, cols, d[j]));
+    }
+    const uint32_t kept = pw_compact(keep, pos, wtot);                          // its barriers: every row of the query is in registers before any is written
+    _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) if (keep[j]) { const size_t w = o + pos[j]; keys[w] = k[j]; scores[w] = s[j]; if (ties) ties[w] = t[j]; docs[w] = d[j]; }
+    if (tid == 0) counts[q] = kept;
+    if (!facets) return;
+    for (int c = 0; c < nfacet; c++) {
+        const uint32_t* __restrict__ col = cols.codes[facetCols[c]];
+        uint32_t code[PW_ROWS];
+        _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) { code[j] = 0xFFFFFFFFu; if (keep[j]) { code[j] = col[d[j]]; fcode[pos[j]] = code[j]; } }
+        __syncthreads();
+        // kept row i = pos[j]: how many kept rows carry its code, and whether an earlier one does (n^2 / 256 compares per thread)
+        uint32_t cnt[PW_ROWS]; bool first[PW_ROWS]; uint32_t fpos[PW_ROWS];
+        _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) {
+            cnt[j] = 0; first[j] = keep[j];
+            if (keep[j]) for (uint32_t m = 0; m < kept; m++) if (fcode[m] == code[j]) { cnt[j]++; if (m < pos[j]) first[j] = false; }
+        }
+        const uint32_t nd = pw_compact(first, fpos, wtot);                      // (its barriers also free fcode for the next column)
+        const size_t fo = ((size_t)q * nfacet + c) * cap;
+        _Pragma("unroll") for (int j = 0; j < PW_ROWS; j++) if (first[j]) { fCodes[fo + fpos[j]] = code[j]; fCounts[fo + fpos[j]] = cnt[j]; }
+        if (tid == 0) fN[(size_t)q * nfacet + c] = nd;
     }
 }

@@ -209,6 +209,8 @@ struct infx_engine {
     infx_engine_config cfg{};
     infx_index* dev = nullptr;
     bool indexed = false;
+    int32_t postRows = INFX_FILTER_MAX_ROWS;      // rows per query that filter / facets / boosts / sort-by / browse accept (infx_engine_set_post_rows, before the first search)
+    std::atomic<bool> searched{false};            // a search has begun on this engine
     FuzzyCache fuzzy;
     std::unordered_map<int64_t, int32_t> keyToFirst;
     bool keysAreIds = false;
@@ -578,6 +580,7 @@ static int32_t expand_pending(infx_engine* e, infx_session* S, std::vector<Query
 }
 static int32_t ph_plan(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t depth) {
     if (!e || (nq && (!q_arena || !q_offs))) return efail(INFX_EINVAL, "bad arguments");
+    e->searched.store(true, std::memory_order_relaxed);
     if (!e->dev || !S || !S->stream) return efail(INFX_EHIP, "no GPU: the scoring hot path has no CPU fallback");
     if (depth <= 0 || depth > e->ix.cfg.maxDepth) return efail(INFX_EINVAL, "CoverageDepth exceeds the engine's max_depth");
     const HostIndex& ix = e->ix; const int threads = e->threads;
@@ -1211,6 +1214,7 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
                                  uint32_t* out_counts, uint32_t* out_flags) {
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
     { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (rc) return rc; }
+    e->searched.store(true, std::memory_order_relaxed);
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     query_cov_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
@@ -2402,13 +2406,11 @@ int32_t infx_engine_set_filter(infx_session* S, const char* expr, int32_t enable
 // as FacetBuilder does (count descending, value ascending), at most 100.  Returns the number of pairs, -1 on error.
 int32_t infx_engine_last_facets(infx_session* S, uint32_t nq, uint32_t qi, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap) {
     if (!S || !S->stream || qi >= nq || k >= S->facetCols.size()) return -1;
-    const uint32_t nf = (uint32_t)S->facetCols.size();
-    std::vector<uint32_t> cd((size_t)nq * nf * INFX_FILTER_MAX_ROWS), ct(cd.size()), nn((size_t)nq * nf);
-    if (infx_last_facets(S->stream, nq, cd.data(), ct.data(), nn.data())) { g_eerr = infx_last_error(); return -1; }
+    std::vector<uint32_t> cd((size_t)S->e->postRows), ct(cd.size()); uint32_t n = 0;      // one (query, column) slice: at most the engine's post rows pairs
+    if (infx_last_facets_of(S->stream, nq, qi, k, cd.data(), ct.data(), &n)) { g_eerr = infx_last_error(); return -1; }
     const filt::Column& C = S->e->columns[S->facetCols[k]];
-    const size_t o = ((size_t)qi * nf + k) * INFX_FILTER_MAX_ROWS; const uint32_t n = nn[(size_t)qi * nf + k];
     std::vector<std::pair<uint32_t, uint32_t>> v;
-    for (uint32_t i = 0; i < n; i++) if (cd[o + i] < C.text.size() && !C.text[cd[o + i]].empty()) v.push_back({cd[o + i], ct[o + i]});     // empty strings are not facet values (:95-99)
+    for (uint32_t i = 0; i < n; i++) if (cd[i] < C.text.size() && !C.text[cd[i]].empty()) v.push_back({cd[i], ct[i]});     // empty strings are not facet values (:95-99)
     std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
     if (v.size() > 100) v.resize(100);
     if (col) *col = (int32_t)S->facetCols[k];
@@ -2567,7 +2569,11 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
         if (rc) { reject(rc, g_eerr); U = QUse(); continue; }
         const bool pp = O.filter || (O.enable_facets && !facetCols.empty()) || !U.boosts.empty() || U.sort;      // (facets without a facetable field: {} as the session path)
         if (pp && hostPhases) { reject(INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run in the device finalize: the host phases (INFX_PHASED) do not post-process rows"); U = QUse(); continue; }
-        if (pp && O.max_results > INFX_FILTER_MAX_ROWS) { reject(INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run on at most INFX_FILTER_MAX_ROWS (64) returned rows per query"); U = QUse(); continue; }
+        if (pp && O.max_results > e->postRows) {
+            reject(INFX_EUNSUPPORTED, e->postRows == INFX_FILTER_MAX_ROWS ? std::string("filter / facets / boosts / sort-by run on at most INFX_FILTER_MAX_ROWS (64) returned rows per query")
+                                                                          : "filter / facets / boosts / sort-by run on at most " + std::to_string(e->postRows) + " returned rows per query (the engine's post rows)");
+            U = QUse(); continue;
+        }
         if (O.enable_facets && !facetCols.empty()) anyFacets = true;
         if (!U.filter.empty()) {
             Q.filterExpr[i] = U.filter;
@@ -2692,6 +2698,17 @@ int32_t infx_engine_set_coverage_setup(infx_engine* e, const infx_coverage_setup
     h.covQLimit = c.coverage_q_limit_for_error_tolerance; h.covRelativeq = c.coverage_lcs_error_tolerance_relativeq;
     return INFX_OK;
 }
+// Post rows: how many returned rows per query filter / facets / boosts / sort-by / browse accept.  Fixed once a search has begun: sessions size their
+// facet readout by it.
+int32_t infx_engine_set_post_rows(infx_engine* e, int32_t rows) {
+    if (!e) return efail(INFX_EINVAL, "null engine");
+    if (rows < INFX_FILTER_MAX_ROWS || rows > INFX_POST_MAX_ROWS) return efail(INFX_EINVAL, "post rows lie outside [64, 1024]");
+    if (e->searched.load(std::memory_order_relaxed)) return efail(INFX_EINVAL, "the post rows are set between create and the first search");
+    if (e->dev) { int32_t rc = infx_set_post_rows(e->dev, rows); if (rc) { g_eerr = infx_last_error(); return rc; } }
+    e->postRows = rows;
+    return INFX_OK;
+}
+int32_t infx_engine_get_post_rows(infx_engine* e, int32_t* out) { if (!e || !out) return efail(INFX_EINVAL, "null argument"); *out = e->postRows; return INFX_OK; }
 int32_t infx_engine_get_coverage_setup(infx_engine* e, infx_coverage_setup* out) { if (!e || !out) return efail(INFX_EINVAL, "null argument"); *out = e->cs; return INFX_OK; }
 static infx_finalize_setup finalize_of(const infx_coverage_setup& c) {
     infx_finalize_setup f; f.truncate = c.truncate != 0; f.min_hits_abs = c.coverage_min_word_hits_abs; f.min_hits_relative = c.coverage_min_word_hits_relative; f.truncation_score = c.truncation_score;

@@ -102,6 +102,7 @@ struct infx_index {
     std::mutex turnMu; hipEvent_t turnEvent = nullptr;
     struct MainPool* pool = nullptr;   // the device's main streams (below); owned by the process
     bool haveDict = false, haveTrie = false;
+    uint32_t postRows = INFX_FILTER_MAX_ROWS;      // rows per query the post-filter / facets / boosts / sort-by / browse accept (infx_set_post_rows)
     bool hasAlias = false;            // the corpus text holds one of the 22 OrdinalIgnoreCase alias characters (infx_upload_docs counts them): Stage 2 runs its ALIAS instantiation
 };
 
@@ -268,7 +269,7 @@ struct infx_stream {
     infx_filter* postFilter = nullptr; uint32_t nFacet = 0; uint32_t facetCols[INFX_MAX_FACET_COLS] = {};
     void *dFDocs = nullptr, *dFacetCols = nullptr, *dFacCodes = nullptr, *dFacCounts = nullptr, *dFacN = nullptr;
     size_t capFDocs = 0, capFacCodes = 0, capFacCounts = 0, capFacN = 0;
-    std::vector<uint32_t> hFacCodes, hFacCounts, hFacN; uint32_t facetNq = 0, facetNFacet = 0;     // facets of the last batch: nq, facet columns
+    std::vector<uint32_t> hFacCodes, hFacCounts, hFacN; uint32_t facetNq = 0, facetNFacet = 0, facetRows = 0;     // facets of the last batch: nq, facet columns, pairs held per (query, column)
     // boosts / sort-by (infx_stream_set_boosts / _set_sort): applied after the post-filter (k_postproc)
     infx_filter* boosts[INFX_MAX_BOOSTS] = {}; int32_t boostStrength[INFX_MAX_BOOSTS] = {}; uint32_t nBoost = 0;
     uint32_t sortCol = 0; bool sortOn = false, sortAsc = false;
@@ -282,6 +283,7 @@ struct infx_stream {
     void* dQCount = nullptr; size_t capQCount = 0;
     // browse queries (INFX_FQ_BROWSE) of the batch being staged: (query, rows asked), recorded by the prep stage and consumed by the finalize
     std::vector<std::pair<uint32_t, uint32_t>> browseQ;
+    std::vector<int32_t> qpRows;      // max_results of each fused query of the batch, kept only by an index with more than INFX_FILTER_MAX_ROWS post rows
     void *dBrwBlob = nullptr, *dBrwWork = nullptr; size_t capBrwBlob = 0, capBrwWork = 0;
     uint32_t lastBrowseGroups = 0, lastBrowseLaunches = 0;      // groups and k_browse_scan launches of the last finalize
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
@@ -881,6 +883,17 @@ int32_t infx_set_deleted(infx_index* ix, uint32_t total, const uint8_t* deleted)
 
 // first[d] = the first live document carrying document d's key, by GLOBAL internal id (every shard holds the whole map): what a browse row's filter and
 // facets look at.  Only a corpus with duplicate keys needs it; nullptr clears (keys unique: first[d] == d).  Exclusive call, as infx_set_deleted.
+int32_t infx_set_post_rows(infx_index* ix, int32_t rows) {
+    if (!ix) return fail(INFX_EINVAL, "null argument%s");
+    if (rows < INFX_FILTER_MAX_ROWS || rows > INFX_POST_MAX_ROWS) return fail(INFX_EINVAL, "post rows lie outside [INFX_FILTER_MAX_ROWS (64), INFX_POST_MAX_ROWS (1024)]%s");
+    ix->postRows = (uint32_t)rows;
+    return INFX_OK;
+}
+int32_t infx_get_post_rows(infx_index* ix, int32_t* rows) {
+    if (!ix || !rows) return fail(INFX_EINVAL, "null argument%s");
+    *rows = (int32_t)ix->postRows;
+    return INFX_OK;
+}
 int32_t infx_set_first_live(infx_index* ix, uint32_t total, const int32_t* first) {
     if (!ix) return fail(INFX_EINVAL, "null argument%s");
     if (!ix->haveDocs) return fail(INFX_EINVAL, "infx_set_first_live before infx_upload_docs%s");
@@ -1655,6 +1668,7 @@ int32_t infx_ld1_expand(infx_stream* s, uint32_t nwords, const uint32_t* word_of
     return INFX_OK;
 }
 
+static std::string post_rows_text(const infx_index* ix) { return ix->postRows == INFX_FILTER_MAX_ROWS ? "INFX_FILTER_MAX_ROWS (64)" : std::to_string(ix->postRows); }
 static uint32_t pow2_at_least(uint32_t v, uint32_t lo) { uint32_t p = lo; while (p < v) p <<= 1; return p; }
 
 // ---- fused pipeline pieces (shared by infx_search_fused and the sharded stage API) ------------------------------------------
@@ -1673,7 +1687,7 @@ static int32_t fused_check_queries(infx_index* ix, uint32_t nd, uint32_t nq, con
         if (fq[i].wm_count) anyWm = true;
         if (fq[i].flags & INFX_FQ_BROWSE) {
             if (!(fq[i].flags & INFX_FQ_SKIP) || (fq[i].flags & INFX_FQ_UNSUPPORTED)) return fail(INFX_EINVAL, "INFX_FQ_BROWSE goes with INFX_FQ_SKIP: a browse query has no text%s");
-            if (fq[i].max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "a browse query returns at most INFX_FILTER_MAX_ROWS rows (its facets run on them)%s");
+            if (fq[i].max_results > (int32_t)ix->postRows) return fail(INFX_EUNSUPPORTED, "a browse query returns at most %s rows (its facets run on them; infx_set_post_rows)", post_rows_text(ix).c_str());
         }
         if (fq[i].flags & INFX_FQ_WMDEV) {
             if (!ix->haveDict) return fail(INFX_EINVAL, "INFX_FQ_WMDEV needs infx_upload_wm_dictionary%s");
@@ -1746,6 +1760,8 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     if (Dall > 8192) return fail(INFX_ECAPACITY, "shards x depth exceeds the in-LDS merge (8192 rows); merge hierarchically%s");
     s->browseQ.clear();
     for (uint32_t i = 0; i < nq; i++) if (fq[i].flags & INFX_FQ_BROWSE) s->browseQ.push_back({i, (uint32_t)std::max(fq[i].max_results, 0)});
+    s->qpRows.clear();       // the rows each query asks for: the finalize decides with them which queries the wide post-processing kernels take
+    if (ix->postRows > INFX_FILTER_MAX_ROWS) { s->qpRows.resize(nq); for (uint32_t i = 0; i < nq; i++) s->qpRows[i] = fq[i].max_results; }
     GROW(s->dFQ, s->capFQ, (size_t)nq * sizeof(infx_fused_query));
     GROW(s->dFLists, s->capFLists, std::max<size_t>(1, nlists) * sizeof(infx_wm_list));
     GROW(s->dFOwned, s->capFOwned, ((size_t)owned_n + 1) * 4);
@@ -1864,12 +1880,13 @@ static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& prog
     const int32_t n = ix->d.totalDocs;
     for (int c = 0; c < FILT_MAXCOL; c++) if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
     static const bool earlyStop = [] { const char* e = getenv("INFX_BROWSE_EARLY_STOP"); return !(e && e[0] == '0'); }();
+    const uint32_t rowStride = ix->postRows;       // rows a group can hand out: the stride of rowDocs
     std::vector<DevBrowseGroup> groups; std::vector<DevBrowseQuery> bq; std::unordered_map<int32_t, uint32_t> groupOf;
     for (auto& b : s->browseQ) {
         const int32_t prog = filterOf(b.first);
         auto it = groupOf.find(prog);
         if (it == groupOf.end()) { it = groupOf.emplace(prog, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{prog >= 0 ? progs[(size_t)prog] : DevFilter{}, prog, 0u, 0u, 0u}); }
-        const uint32_t rows = std::min<uint32_t>(std::min<uint32_t>(b.second, (uint32_t)max_results), INFX_FILTER_MAX_ROWS);
+        const uint32_t rows = std::min<uint32_t>(std::min<uint32_t>(b.second, (uint32_t)max_results), rowStride);
         groups[it->second].rows = std::max(groups[it->second].rows, rows);
         bq.push_back(DevBrowseQuery{b.first, it->second, rows, 0u});
     }
@@ -1884,7 +1901,7 @@ static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& prog
     const bool dup = ix->firstLive != nullptr;
     auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t oBq = al((size_t)G * sizeof(DevBrowseGroup)), blob = oBq + bq.size() * sizeof(DevBrowseQuery);
-    const size_t oPre = al((size_t)G * nRanges * 4), oTot = oPre + oPre, oOwn = oTot + al((size_t)G * 4), oRows = oOwn + al((size_t)G * 4), work = oRows + (size_t)G * INFX_FILTER_MAX_ROWS * 4;
+    const size_t oPre = al((size_t)G * nRanges * 4), oTot = oPre + oPre, oOwn = oTot + al((size_t)G * 4), oRows = oOwn + al((size_t)G * 4), work = oRows + (size_t)G * rowStride * 4;
     GROW(s->dBrwBlob, s->capBrwBlob, blob); GROW(s->dBrwWork, s->capBrwWork, work);
     std::vector<uint8_t> H(blob, 0);
     std::memcpy(H.data(), groups.data(), (size_t)G * sizeof(DevBrowseGroup)); std::memcpy(H.data() + oBq, bq.data(), bq.size() * sizeof(DevBrowseQuery));
@@ -1917,10 +1934,15 @@ static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& prog
     k_browse_prefix<<<G, BRW_THREADS, 0, s->st>>>(dGroups, nRanges, dCnt, dup ? dOwn : nullptr, dPre, dTot, (uint32_t*)s->dQCount);
     HIPCHK(hipGetLastError());
     if (!bq.empty()) {
-        k_browse_gather<<<dim3(nRanges, std::min<uint32_t>(G, 32u)), WAVE, 0, s->st>>>(dGroups, G, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, ix->firstLive, dCnt, dPre, dRows);
+        k_browse_gather<<<dim3(nRanges, std::min<uint32_t>(G, 32u)), WAVE, 0, s->st>>>(dGroups, G, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, ix->firstLive, dCnt, dPre, dRows, rowStride);
         HIPCHK(hipGetLastError());
-        k_browse_rows<<<(uint32_t)bq.size(), WAVE, 0, s->st>>>(dBq, dGroups, dTot, dRows, (const long long*)ix->d.docKeyAll, ix->firstLive, max_results, (long long*)s->dFKeys,
-                                                                  (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr, (int32_t*)s->dFDocs, (uint32_t*)s->dFCounts);
+        uint32_t mostRows = 0; for (const DevBrowseQuery& Q : bq) mostRows = std::max(mostRows, Q.rows);
+        if (mostRows <= INFX_FILTER_MAX_ROWS)
+            k_browse_rows<<<(uint32_t)bq.size(), WAVE, 0, s->st>>>(dBq, dGroups, dTot, dRows, rowStride, (const long long*)ix->d.docKeyAll, ix->firstLive, max_results, (long long*)s->dFKeys,
+                                                                      (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr, (int32_t*)s->dFDocs, (uint32_t*)s->dFCounts);
+        else
+            k_browse_rows_wide<<<(uint32_t)bq.size(), BRW_THREADS, 0, s->st>>>(dBq, dGroups, dTot, dRows, rowStride, (const long long*)ix->d.docKeyAll, ix->firstLive, max_results, (long long*)s->dFKeys,
+                                                                                (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr, (int32_t*)s->dFDocs, (uint32_t*)s->dFCounts);
         HIPCHK(hipGetLastError());
     }
     s->lastCountK = ncount; s->lastCountLaunches = 0;      // counted by the scan: no k_filter_count_multi launch
@@ -1945,12 +1967,24 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     s->qpOn = false; s->lastCountK = 0; s->lastCountLaunches = 0;
     if (qp && s->qpNq != nq) return fail(INFX_EINVAL, "the per-query options were installed for a batch of another size%s");
     const bool post = !qp && (s->postFilter != nullptr || s->nFacet > 0);
-    if (post && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "post-filter / facets run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
+    if (post && max_results > (int32_t)ix->postRows) return fail(INFX_EUNSUPPORTED, "post-filter / facets run on at most %s returned rows per query (infx_set_post_rows)", post_rows_text(ix).c_str());
     const bool pp = !qp && (s->nBoost > 0 || s->sortOn);         // boosts / sort-by: k_postproc after k_postfilter
-    if (pp && max_results > INFX_FILTER_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "boosts / sort-by run on at most INFX_FILTER_MAX_ROWS returned rows per query%s");
+    if (pp && max_results > (int32_t)ix->postRows) return fail(INFX_EUNSUPPORTED, "boosts / sort-by run on at most %s returned rows per query (infx_set_post_rows)", post_rows_text(ix).c_str());
     const bool sortKnown = !qp && s->sortOn && s->sortCol != 0xFFFFFFFFu;
     if (sortKnown && (s->sortCol >= FILT_MAXCOL || !ix->colCodes[s->sortCol] || !ix->colRankOk[s->sortCol])) return fail(INFX_EINVAL, "the sort column's rank is not uploaded%s");
     bool launchPF = post, launchPP = pp;
+    // Queries whose post-processing runs on more than INFX_FILTER_MAX_ROWS rows (an index with infx_set_post_rows) are flagged QP_WIDE: the one-wave
+    // kernels skip them, the *_wide kernels — launched only for a batch that has one — take them.  A query beyond the index's post rows stays unflagged
+    // and is rejected by the one-wave kernels as ever.
+    bool widePF = (post || pp) && max_results > INFX_FILTER_MAX_ROWS, widePP = pp && max_results > INFX_FILTER_MAX_ROWS;
+    const bool wideShared = widePF;
+    bool wideFacets = post && s->nFacet > 0 && max_results > INFX_FILTER_MAX_ROWS;      // a query counts facets on more than INFX_FILTER_MAX_ROWS rows
+    if (qp && ix->postRows > INFX_FILTER_MAX_ROWS && s->qpRows.size() == nq) for (uint32_t q = 0; q < nq; q++) {
+        DevQPost& D = s->qpDesc[q];
+        const bool f = D.filter >= 0 || (D.flags & QP_FACETS), p = D.nboost > 0 || (D.flags & QP_SORT);
+        if ((!f && !p) || s->qpRows[q] <= (int32_t)INFX_FILTER_MAX_ROWS || s->qpRows[q] > (int32_t)ix->postRows) continue;
+        D.flags |= QP_WIDE; widePF |= f; widePP |= p; wideFacets |= (D.flags & QP_FACETS) != 0;
+    }
     if (qp) for (const DevQPost& D : s->qpDesc) {
         launchPF |= D.filter >= 0 || (D.flags & QP_FACETS); launchPP |= D.nboost > 0 || (D.flags & QP_SORT);
         if ((D.flags & QP_SORT) && D.sortCol != 0xFFFFFFFFu && (D.sortCol >= FILT_MAXCOL || !ix->colCodes[D.sortCol] || !ix->colRankOk[D.sortCol]))
@@ -1978,6 +2012,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
             D.boostOff = 0; D.nboost = s->nBoost;
             for (uint32_t b = 0; b < s->nBoost; b++) { sboost.push_back(DevQBoost{(int32_t)progs.size(), s->boostStrength[b]}); progs.push_back(s->boosts[b]->d); }
             if (s->sortOn) { D.flags |= QP_SORT | (s->sortAsc ? QP_ASC : 0u); D.sortCol = s->sortCol; }
+            if (wideShared) D.flags |= QP_WIDE;
             sdesc.push_back(D);
         }
         const std::vector<DevQBoost>& boosts = qp ? s->qpBoosts : sboost; const std::vector<DevQPost>& desc = qp ? s->qpDesc : sdesc;
@@ -2036,19 +2071,31 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     }
     s->facetNq = 0;
     if (launchPF) {     // ResultProcessor.ApplyFilter + FacetBuilder on the rows just produced, before they leave the device
-        const size_t fe = (size_t)nq * std::max<uint32_t>(1, nfacet) * INFX_FILTER_MAX_ROWS;
+        const size_t fe = (size_t)nq * std::max<uint32_t>(1, nfacet) * ix->postRows;
         GROW(s->dFacCodes, s->capFacCodes, fe * 4); GROW(s->dFacCounts, s->capFacCounts, fe * 4); GROW(s->dFacN, s->capFacN, (size_t)nq * std::max<uint32_t>(1, nfacet) * 4);
         if (!s->dFacetCols) HIPCHK(hipMalloc(&s->dFacetCols, INFX_MAX_FACET_COLS * 4));
         UP(s->dFacetCols, facetCols, INFX_MAX_FACET_COLS * 4);
-        k_postfilter<<<nq, WAVE, 0, s->st>>>(dPB, cols, (int)nfacet, (const uint32_t*)s->dFacetCols, (uint32_t*)s->dFacCodes, (uint32_t*)s->dFacCounts, (uint32_t*)s->dFacN);
+        k_postfilter<<<nq, WAVE, 0, s->st>>>(dPB, cols, (int)nfacet, (const uint32_t*)s->dFacetCols, (uint32_t*)s->dFacCodes, (uint32_t*)s->dFacCounts, (uint32_t*)s->dFacN, ix->postRows);
+        if (widePF) k_postfilter_wide<<<nq, PW_THREADS, 0, s->st>>>(dPB, cols, (int)nfacet, (const uint32_t*)s->dFacetCols, (uint32_t*)s->dFacCodes, (uint32_t*)s->dFacCounts, (uint32_t*)s->dFacN, ix->postRows);
         HIPCHK(hipGetLastError());
         if (nfacet) {
-            s->hFacCodes.resize(fe); s->hFacCounts.resize(fe); s->hFacN.resize((size_t)nq * nfacet); s->facetNq = nq; s->facetNFacet = nfacet;
-            DOWN(s->hFacCodes.data(), s->dFacCodes, fe * 4); DOWN(s->hFacCounts.data(), s->dFacCounts, fe * 4); DOWN(s->hFacN.data(), s->dFacN, (size_t)nq * nfacet * 4);
+            // Only the pairs that can exist travel back: INFX_FILTER_MAX_ROWS per (query, column) unless a query of the batch counts facets on more
+            // rows, so a batch of narrow queries on an index with more post rows downloads what a default index does.  The host copy is packed at that width.
+            const uint32_t w = wideFacets ? ix->postRows : std::min<uint32_t>(ix->postRows, INFX_FILTER_MAX_ROWS);
+            const size_t slices = (size_t)nq * nfacet, feh = slices * w;
+            s->hFacCodes.resize(feh); s->hFacCounts.resize(feh); s->hFacN.resize(slices); s->facetNq = nq; s->facetNFacet = nfacet; s->facetRows = w;
+            if (w == ix->postRows) { DOWN(s->hFacCodes.data(), s->dFacCodes, feh * 4); DOWN(s->hFacCounts.data(), s->dFacCounts, feh * 4); }
+            else for (int a = 0; a < 2; a++) {
+                void* p = pin_take(s, feh * 4); if (!p) return fail(INFX_ENOMEM, "hipHostMalloc staging failed%s");
+                HIPCHK(hipMemcpy2DAsync(p, (size_t)w * 4, a ? s->dFacCounts : s->dFacCodes, (size_t)ix->postRows * 4, (size_t)w * 4, slices, hipMemcpyDeviceToHost, s->st)); s->unsynced = true;
+                s->pendingOut.push_back({a ? (void*)s->hFacCounts.data() : (void*)s->hFacCodes.data(), p, feh * 4});
+            }
+            DOWN(s->hFacN.data(), s->dFacN, slices * 4);
         }
     }
     if (launchPP) {     // ResultProcessor.ApplyBoosts + ApplySort on the kept rows (facets count rows, not their order: FacetBuilder's result is the same)
         k_postproc<<<nq, WAVE, 0, s->st>>>(dPB, cols);
+        if (widePP) k_postproc_wide<<<nq, PW_THREADS, 0, s->st>>>(dPB, cols, ix->postRows);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(s->evF1, s->st));
@@ -2758,9 +2805,20 @@ int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t
 int32_t infx_last_facets(infx_stream* s, uint32_t nq, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out) {
     if (!s || !codes_out || !counts_out || !n_out) return fail(INFX_EINVAL, "null argument%s");
     if (nq != s->facetNq || !s->facetNFacet) return fail(INFX_EINVAL, "no facets of a batch of this size on the stream%s");
-    std::memcpy(codes_out, s->hFacCodes.data(), s->hFacCodes.size() * 4); std::memcpy(counts_out, s->hFacCounts.data(), s->hFacCounts.size() * 4);
+    const size_t rows = s->ix->postRows, w = s->facetRows, slices = (size_t)nq * s->facetNFacet;      // the caller's stride: the index's post rows
+    if (w == rows) { std::memcpy(codes_out, s->hFacCodes.data(), s->hFacCodes.size() * 4); std::memcpy(counts_out, s->hFacCounts.data(), s->hFacCounts.size() * 4); }
+    else for (size_t i = 0; i < slices; i++) { std::memcpy(codes_out + i * rows, s->hFacCodes.data() + i * w, w * 4); std::memcpy(counts_out + i * rows, s->hFacCounts.data() + i * w, w * 4); }
     std::memcpy(n_out, s->hFacN.data(), s->hFacN.size() * 4);
     return INFX_OK;
 }
 
+int32_t infx_last_facets_of(infx_stream* s, uint32_t nq, uint32_t q, uint32_t k, uint32_t* codes_out, uint32_t* counts_out, uint32_t* n_out) {
+    if (!s || !codes_out || !counts_out || !n_out) return fail(INFX_EINVAL, "null argument%s");
+    if (nq != s->facetNq || !s->facetNFacet || q >= nq || k >= s->facetNFacet) return fail(INFX_EINVAL, "no facets of a batch of this size on the stream%s");
+    const size_t i = (size_t)q * s->facetNFacet + k, rows = s->facetRows;
+    const uint32_t n = std::min<uint32_t>(s->hFacN[i], (uint32_t)rows);
+    std::memcpy(codes_out, s->hFacCodes.data() + i * rows, (size_t)n * 4); std::memcpy(counts_out, s->hFacCounts.data() + i * rows, (size_t)n * 4);
+    *n_out = n;
+    return INFX_OK;
+}
 } // extern "C"

@@ -204,19 +204,31 @@ def pack_texts(texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
 class SearchEngine:
     def __init__(self, enable_coverage=True, word_matcher=True, device: int = 0, range_docs: int = 0, max_depth: int = 500,
                  threads: int = 0, stop_term_limit: int = 0, want_features: bool = False, exact_replay: bool = True,
-                 coverage_setup: Optional[CoverageSetup] = None):
+                 coverage_setup: Optional[CoverageSetup] = None, max_post_rows: int = 64):
+        """max_post_rows (64..1024): how many returned rows per query Filter, EnableFacets, Boosts, SortBy and browse queries accept.  The reference
+        post-filters the truncated top-MaxNumberOfRecordsToReturn rows, so a selective filter wants a few hundred rows to filter; the default keeps the
+        64-row envelope and its refusals."""
         self.L = load_library()
         cfg = _Cfg(device, range_docs, max_depth, threads, int(enable_coverage), int(word_matcher), stop_term_limit, int(want_features), int(not exact_replay))
         h = C.c_void_p()
         self._check(self.L.infx_engine_create(C.byref(cfg), C.byref(h)))
         self.h = h
         self.device = device
-        if coverage_setup is not None:
-            try:
+        try:
+            if coverage_setup is not None:
                 self.set_coverage_setup(coverage_setup)
-            except Exception:
-                self.close()
-                raise
+            if not 64 <= int(max_post_rows) <= 1024:          # (checked here too: ctypes would wrap a value beyond int32)
+                raise InfidexError(1, "max_post_rows lies outside [64, 1024]")
+            self._check(self.L.infx_engine_set_post_rows(self.h, int(max_post_rows)))
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def max_post_rows(self) -> int:
+        v = C.c_int32(0)
+        self._check(self.L.infx_engine_get_post_rows(self.h, C.byref(v)))
+        return int(v.value)
 
     def set_coverage_setup(self, coverage_setup: Optional[CoverageSetup]):
         """The engine-wide CoverageSetup (SearchEngine's coverageSetup: argument; None = the defaults).  Legal between batches."""
@@ -411,7 +423,7 @@ class SearchEngine:
     def search_queries(self, queries: Sequence[Query], session=None) -> List[Result]:
         """Search(Query) for a batch of Query objects, each with its own MaxNumberOfRecordsToReturn, EnableCoverage, Filter, EnableFacets, Boosts and
         SortBy (infx_engine_set_query_options) and CoverageSetup (infx_engine_set_query_coverage): one device batch per CoverageDepth, results in
-        input order.  A query whose options are refused (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than 64 rows,
+        input order.  A query whose options are refused (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than max_post_rows (default 64) rows,
         a CoverageSetup out of range or with the lexical pre-screen) comes back empty with Result.error set; the others of the batch are unaffected."""
         sh = session.h if session is not None else self._default_session()
         runner = (session or self).search_packed

@@ -103,6 +103,7 @@ class TorchComm:
 
 
 def create_sharded_engine(rank: int, world: int, device: int, **kw) -> SearchEngine:
+    """One rank's engine; **kw are SearchEngine's arguments (max_depth, coverage_setup, max_post_rows, ...): the same on every rank."""
     eng = SearchEngine.create_default(device=device, **kw)
     eng._check(eng.L.infx_engine_set_shard(eng.h, rank, world))
     return eng
@@ -586,6 +587,12 @@ class ShardedSearcher:
             return
         hs = (C.c_void_p * max(1, n))(*[self.sessions[k].s.h for k in range(n)])
         self.sessions[0].e._check(self.sessions[0].L.infx_engine_coll_ring(self.sessions[0].e.h, n, hs))
+
+    @property
+    def max_post_rows(self) -> int:
+        """The engine's post rows (SearchEngine(max_post_rows=...)): the rows per query that set_filter / set_boosts / set_sort and search_queries accept.
+        Every rank's engine must be created with the same value."""
+        return self.sessions[0].e.max_post_rows
 
     def plan_exchange_stats(self, k=None):
         """(queries of session k's last phase 0 planned from the exchange, of them imported from peers); k = None: the last session used."""

@@ -6,8 +6,11 @@ Three cases over the same 1000-query batches, `--sessions` host threads with one
   (iii) per query, a filter drawn from a pool of `--pool` expressions (or none), facets on half, boosts or a sort on a third.
 The batches of (iii) that count the pool's expressions for the first time (NumberOfDocumentsInFilter, k_filter_count_multi) are timed on their own
 before the steady state.  Prints one JSON line.
+  (iv)  with --wide-leg: the engine is created with max_post_rows=1024 and every query of the same batches asks WIDE_K = 500 rows (coverage off) with
+        the config-5 filter, facets and a sort-by — the workgroup-per-query kernels (k_postfilter_wide, k_postproc_wide), whose serial sort of up to
+        500 rows is paid per query.  Cases (i)-(iii) run first, on the same engine: their queries stay on the one-wave kernels.
 
-    python tools/bench_query_options.py [--docs N] [--steps 20] [--warmup 4] [--sessions 4] [--pool 200]
+    python tools/bench_query_options.py [--docs N] [--steps 20] [--warmup 4] [--sessions 4] [--pool 200] [--wide-leg]
 """
 import argparse
 import json
@@ -24,6 +27,7 @@ from infidex_amd.engine import Session, pack_texts, _install_query_options  # no
 from tools.synth import Synth, config5_columns  # noqa: E402
 
 K = 20
+WIDE_K = 500
 
 
 def pool_exprs(n, seed=3):
@@ -37,7 +41,7 @@ def pool_exprs(n, seed=3):
     return list(dict.fromkeys(out))[:n]
 
 
-def run(sessions, batches, prep):
+def run(sessions, batches, prep, k=K, coverage=True):
     """Every batch through `prep(session, i)` (installs its options; returns the packed texts) and search_packed; returns seconds."""
     cur = {"i": 0}; lock = threading.Lock(); err = []
 
@@ -49,7 +53,7 @@ def run(sessions, batches, prep):
                 if i >= len(batches):
                     return
                 arena, offs = prep(se, i)
-                se.search_packed(arena, offs, K, 500, True)
+                se.search_packed(arena, offs, k, 500, coverage)
         except Exception as ex:
             err.append(ex)
 
@@ -72,10 +76,11 @@ def main():
     ap.add_argument("--batch", type=int, default=1000)
     ap.add_argument("--sessions", type=int, default=4)
     ap.add_argument("--pool", type=int, default=200)
+    ap.add_argument("--wide-leg", action="store_true", help="add case (iv): 500 rows per query with filter, facets and sort-by (max_post_rows=1024)")
     args = ap.parse_args()
     syn = Synth(5, docs=args.docs)
     arena, offs = syn.docs()
-    e = SearchEngine.create_default(device=0); e.index_flat(None, arena, offs, syn.field_weights)
+    e = SearchEngine.create_default(device=0, **({"max_post_rows": 1024} if args.wide_leg else {})); e.index_flat(None, arena, offs, syn.field_weights)
     year, rating, genre = config5_columns(args.docs)
     e.set_column("year", year, facetable=True); e.set_column("rating", rating, facetable=False); e.set_column("genre", genre, facetable=True)
     flt = syn.cfg["filter"]
@@ -135,6 +140,22 @@ def main():
     out["iii_per_query_mix_qps"] = args.steps * args.batch / dt
     out["ii_over_i"] = out["ii_per_query_same_filter_qps"] / out["i_session_filter_qps"]
     out["iii_over_i"] = out["iii_per_query_mix_qps"] / out["i_session_filter_qps"]
+
+    if args.wide_leg:       # (iv) 500 rows per query, coverage off, filter + facets + sort-by on every query
+        widq = [[Query(t, WIDE_K, enable_coverage=False, filter=flt, enable_facets=True, sort_by="year", sort_ascending=bool(j & 1)) for j, t in enumerate(b)] for b in tb]
+
+        def prep4(se, i, off=0):
+            _install_query_options(e, se.h, widq[off + i]); return packed[off + i]
+        run(sessions, packed[:args.warmup], prep4, WIDE_K, False)
+        dt = run(sessions, packed[args.warmup:], lambda se, i: prep4(se, i, args.warmup), WIDE_K, False)
+        out["iv_wide_rows"] = WIDE_K
+        # how many rows the wide kernels actually worked on: one batch plain (the rows before the filter) and with the options
+        se = sessions[0]
+        before = se.search_packed(*packed[0], WIDE_K, 500, False)[3]
+        after = se.search_packed(*prep4(se, 0), WIDE_K, 500, False)[3]
+        out["iv_mean_rows_before_filter"] = float(before.mean()); out["iv_max_rows_before_filter"] = int(before.max())
+        out["iv_mean_rows_returned"] = float(after.mean())
+        out["iv_wide_500_rows_filter_facets_sort_qps"] = args.steps * args.batch / dt
     print(json.dumps(out))
 
 
