@@ -340,6 +340,32 @@ int32_t infx_sizeof_coverage_setup(void);
 int32_t infx_engine_set_coverage_setup(infx_engine* e, const infx_coverage_setup* setup /* NULL = defaults */);
 int32_t infx_engine_get_coverage_setup(infx_engine* e, infx_coverage_setup* out);
 int32_t infx_engine_set_query_coverage(infx_session* s, uint32_t nq, const infx_coverage_setup* const* setups, int32_t* out_status /* nq, may be NULL */);
+/* ---- Query.pre_filter: rank only the documents a filter accepts -----------------------------------------------------------------------------------
+ * Query.Filter is a post-filter (SearchEngine.cs:304-310): it runs on the truncated top rows.  A PRE-filter restricts the set that is ranked: a query with
+ * pre-filter P returns what the same query returns on the same index if every document P does not accept carried Document.Deleted = true.  "Accept" is the
+ * filter VM's three-valued evaluation of the document's own column values (only True accepts, an absent column is null) — what NumberOfDocumentsInFilter counts.
+ * Index statistics (df, avgdl, N, stop terms) are untouched, as with deletions; real deletions stay in force; the mask is per document, not per key.  Filter,
+ * EnableFacets, Boosts and SortBy then post-process the returned rows as without it.  A query without a pre-filter, alone or beside pre-filtered ones, runs
+ * the code and returns the bits it would in a batch without any.
+ * infx_engine_set_query_prefilters installs the pre-filters (Infiscript, UTF-8; exprs[i] == NULL: none) of the session's NEXT search of nq queries: consumed
+ * by that search like infx_engine_set_query_coverage, usable with or without infx_engine_set_query_options, nq = 0 clears, a search of another nq fails with
+ * INFX_EINVAL and clears them.  Expressions go through the engine's filter cache.  A query is rejected on its own — empty result, result flag bit 4, its
+ * status in out_status[i], its message from infx_engine_query_error when its options were accepted, neighbours unaffected — for a syntax error (INFX_EINVAL),
+ * MATCHES (INFX_EUNSUPPORTED), a 17th distinct pre-filter in one batch (INFX_ECAPACITY: split the batch), an empty text with EnableFacets (a browse query,
+ * whose Filter already restricts the scan; known when the batch runs: the status then shows in the result flag and the message only), the host phases
+ * (INFX_PHASED) and a sharded engine (INFX_EUNSUPPORTED each).
+ * Masks: one byte per document, at most INFX_MAX_PREFILTERS (16) per session, keyed by the expression, least recently used first out, reused across batches.
+ * The masks a batch is missing are built by ONE k_filter_mask_multi launch on the session's stream in front of the batch — no extra host wait, nothing shared
+ * between sessions.  infx_engine_delete_documents / _delete_document_ids / _restore_documents / _add_column and indexing start a new mask epoch: every
+ * session builds its masks again on next use. */
+int32_t infx_engine_set_query_prefilters(infx_session* s, uint32_t nq, const char* const* exprs, int32_t* out_status /* nq, may be NULL */);
+/* live documents each query's pre-filter accepts, of the session's last search (0 for a query without one, or rejected) */
+int32_t infx_engine_last_in_prefilter(infx_session* s, uint32_t nq, uint32_t* out);
+/* masks the session's last search (or infx_engine_prefilter_mask) built and took from its cache, and the k_filter_mask_multi launches that took */
+int32_t infx_engine_last_prefilter_stats(infx_session* s, uint32_t* built, uint32_t* reused, uint32_t* launches);
+/* Parity tooling: the mask of one expression as the device holds it — built, or taken from the session's cache — one byte per indexed document in
+ * out_bytes (cap >= the number of documents): 1 = Deleted or not accepted. */
+int32_t infx_engine_prefilter_mask(infx_session* s, const char* expr, uint8_t* out_bytes, uint64_t cap);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

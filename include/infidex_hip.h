@@ -351,6 +351,26 @@ int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_pr
  * browse scan counted them, see below) */
 int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches);
 
+/* ---- pre-filter masks: rank only the documents a filter accepts ---------------------------------------------------------------------------
+ * A query with a pre-filter P returns what it would return on the same index if every document P does not accept carried Document.Deleted: the
+ * query reads a MASK — one byte per GLOBAL internal id, mask[g] = Deleted(g) || !accept_P(g) — wherever it would read the index's Deleted flags
+ * (Stage-1 emission, the exact replay, the WordMatcher-only candidates).  Index statistics are untouched, as with deletions; the count, browse and
+ * whole-corpus facet kernels keep the real flags.  Unsharded indexes only (infx_search_fused).
+ *   infx_stream_mask_slot   the device buffer of mask slot `slot` (< INFX_MAX_PREFILTERS) of this stream: total_docs bytes padded to a multiple of four,
+ *                           allocated on first use, owned by the stream.  What a slot holds is the caller's bookkeeping.
+ *   infx_filter_masks       stages the build of k (<= INFX_MAX_PREFILTERS) masks: masks[i] (device, as from infx_stream_mask_slot) receives the mask of
+ *                           progs[i], counts[i] (host) the number of live documents it accepts.  The build is ONE k_filter_mask_multi launch over the
+ *                           whole corpus, enqueued on the stream in front of its next infx_search_fused — no host wait of its own: the counts land when
+ *                           that batch's results do — or by infx_stream_wait, whichever comes first.  k = 0 drops a staged build.
+ *   infx_stream_set_doc_masks  the flags of each query of the stream's NEXT infx_search_fused of nq queries: masks[i] (device), or NULL = the index's
+ *                           Deleted flags.  Consumed by that batch, whatever its outcome; nq = 0 clears; a batch of another size fails.
+ *   infx_last_filter_mask_stats  masks built and k_filter_mask_multi launches of the last build on this stream. */
+#define INFX_MAX_PREFILTERS 16
+int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out);
+int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint8_t* const* masks, uint32_t* counts);
+int32_t infx_stream_set_doc_masks(infx_stream* s, uint32_t nq, const uint8_t* const* masks);
+int32_t infx_last_filter_mask_stats(infx_stream* s, uint32_t* built, uint32_t* launches);
+
 /* ---- browse rows: a query with no text and EnableFacets (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346) -------------------------
  * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= the index's post rows, else INFX_EUNSUPPORTED) documents in
  * internal order that are not Deleted and that its filter accepts — the filter of its infx_query_post descriptor (which must carry INFX_QP_FACETS) or

@@ -164,7 +164,8 @@ __global__ __launch_bounds__(EX_THREADS) void k_exact1(DevIndex ix, const DevQue
         const bool full = shHeapN >= depth;
         uint32_t cp = 0;
         // a deleted document (Bm25Scorer.cs:322-323) keeps its place in the chunk but is never offered to UpdateTopK
-        const uint8_t* del = ix.deleted ? ix.deleted + ix.docBase : nullptr;
+        const uint8_t* qdel = q_deleted(ix, (uint32_t)q);
+        const uint8_t* del = qdel ? qdel + ix.docBase : nullptr;
         for (int j = j0; j < j1; j++) { const float s = sCur[j]; if (s > 0.f && (!full || s > th) && !(del && del[sDoc[j]])) cp++; }
         uint32_t np; uint32_t o = ex_scan(cp, sPart, tog, tid, np);
         for (int j = j0; j < j1; j++) { const float s = sCur[j]; if (s > 0.f && (!full || s > th) && !(del && del[sDoc[j]])) sList[o++] = (uint16_t)j; }

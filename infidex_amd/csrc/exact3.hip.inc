@@ -434,13 +434,14 @@ __global__ __launch_bounds__(W * WAVE) void k_ex_chunk(DevIndex ix, const DevQue
         const float keep = th * (1.0f - 1e-5f);
         infx_hit* out = xb.out + qb + C.i0;
         bool f[4]; int32_t gd[4]; unsigned long long eb[4];
+        const uint8_t* del = q_deleted(ix, (uint32_t)q);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int k = i * W + wv, j = k * WAVE + lane;
             const float sv = (k < T && j < n) ? rCur[i] : 0.f;
             // a deleted document (Bm25Scorer.cs:322-323) is scored with its chunk (it holds its position in the match lists) but never reaches UpdateTopK
             gd[i] = rDoc[i] + ix.docBase;
-            f[i] = sv > 0.f && (!C.full || sv > keep) && !(ix.deleted && ix.deleted[gd[i]]);
+            f[i] = sv > 0.f && (!C.full || sv > keep) && !(del && del[gd[i]]);
             eb[i] = __ballot(f[i]);
         }
         for (int d = 32; d > 0; d >>= 1) { lo = fmaxf(lo, __shfl_xor(lo, d)); hi = fminf(hi, __shfl_xor(hi, d)); }

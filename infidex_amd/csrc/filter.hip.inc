@@ -3,6 +3,8 @@
 //                         in one launch: each document's codes of the columns any program reads are loaded once into the thread's LDS slots, the K
 //                         programs run one after another with wave-uniform control flow, ballot + popcount per wave into per-workgroup LDS counters,
 //                         one global atomic per (workgroup, program).  infx_filter_count is the case K = 1.
+//   k_filter_mask_multi   the same evaluation written out per document: mask[k][g] = Deleted(g) || !accept_k(g), the per-query Deleted flags of a pre-filter
+//                         (Query.pre_filter: "rank only the documents the filter accepts"), four documents per thread, + the count of live accepted documents
 //   k_postfilter          ResultProcessor.ApplyFilter on the <= k rows a search returns (:56-69) + FacetBuilder.BuildFacetForField (:58-105): one wave
 //                         per query, one row per lane; ballot compaction keeps the row order; facet values are counted with wave shuffles.  Each
 //                         query reads its own descriptor (DevQPost: filter program or none, facets on or off); the session-wide setters stage one
@@ -73,6 +75,57 @@ __global__ __launch_bounds__(FCM_THREADS) void k_filter_count_multi(const DevFil
     }
     __syncthreads();
     for (uint32_t k = tid; k < K; k += FCM_THREADS) if (cnt[k]) atomicAdd(&counts[k], cnt[k]);
+}
+
+// ---- pre-filter masks: "for this query, every document the filter rejects is Deleted" (infx_filter_masks) ----
+// mask[k][g] = Deleted(g) || !accept_k(g) for every document g of the corpus and K <= INFX_MAX_PREFILTERS programs in ONE pass: a thread takes four consecutive
+// documents, so the codes of a column arrive as one 16-byte load and each program's four results leave as one dword store (the masks are padded to a multiple
+// of four bytes; the padding reads as rejected).  The last, partial group of a corpus reads its codes and flags one by one: the columns and the Deleted flags
+// are not padded.  counts[k] += live accepted documents: ballot + popcount per wave, an LDS counter per workgroup, one global atomic per (workgroup, program).
+// Dynamic LDS: (nUsed * 4 * blockDim.x + K) words — the thread's codes, one word per (column, document), laid out lane-fastest; read back by the same thread only.  The host launches 256
+// threads while that stays within 40 KiB (four workgroups per CU), else one wave per workgroup (64 columns: 64 KiB).
+#define FMM_THREADS 256
+struct DevMaskOut { uint8_t* mask[INFX_MAX_PREFILTERS]; };
+__global__ __launch_bounds__(FMM_THREADS) void k_filter_mask_multi(const DevFilter* __restrict__ progs, uint32_t K, DevCountCols cc, DevColumns cols, int32_t n,
+                                                                    const uint8_t* __restrict__ deleted, DevMaskOut out, uint32_t* __restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t fmm_lds[];
+    const int tid = threadIdx.x, T = blockDim.x;
+    uint32_t* codes = fmm_lds;                               // [(u * 4 + j) * T + tid]: document j of the thread's four, column slot u — consecutive lanes, consecutive banks
+    uint32_t* cnt = fmm_lds + (size_t)cc.nUsed * 4u * T;     // per-workgroup count of each program
+    for (uint32_t k = tid; k < K; k += T) cnt[k] = 0;
+    __syncthreads();
+    const int64_t groups = ((int64_t)n + 3) >> 2;
+    for (int64_t gb = (int64_t)blockIdx.x * T; gb < groups; gb += (int64_t)gridDim.x * T) {
+        const int64_t gi = gb + tid, d0 = gi * 4;
+        const bool have = gi < groups, full = have && d0 + 4 <= (int64_t)n;
+        uint32_t dead = 0;                                   // byte j: document d0 + j is Deleted, or lies beyond the corpus
+        if (!have) dead = 0x01010101u;
+        else if (full) { if (deleted) dead = *(const uint32_t*)(deleted + d0); }
+        else for (int j = 0; j < 4; j++) if (d0 + j >= (int64_t)n || (deleted && deleted[d0 + j])) dead |= 1u << (8 * j);
+        for (uint32_t u = 0; u < cc.nUsed; u++) {
+            const uint32_t* __restrict__ col = cols.codes[cc.col[u]];
+            uint4 c = make_uint4(0, 0, 0, 0);
+            if (full) c = *(const uint4*)(col + d0);
+            else if (have) { c.x = col[d0]; if (d0 + 1 < (int64_t)n) c.y = col[d0 + 1]; if (d0 + 2 < (int64_t)n) c.z = col[d0 + 2]; }      // (d0 + 3 >= n in a partial group)
+            uint32_t* cu = codes + (size_t)u * 4u * T + tid;
+            cu[0] = c.x; cu[T] = c.y; cu[2 * T] = c.z; cu[3 * T] = c.w;
+        }
+        for (uint32_t k = 0; k < K; k++) {
+            const DevFilter f = progs[k];
+            uint32_t word = 0, hits = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const bool acc = filt_eval_codes(f, [&](uint32_t c) { return codes[((uint32_t)cc.slot[c] * 4u + j) * T + tid]; });
+                const bool hit = acc && !((dead >> (8 * j)) & 0xFFu);
+                hits += (uint32_t)__popcll(__ballot(hit));
+                word |= (hit ? 0u : 1u) << (8 * j);
+            }
+            if (have) *(uint32_t*)(out.mask[k] + d0) = word;
+            if ((tid & (WAVE - 1)) == 0 && hits) atomicAdd(&cnt[k], hits);
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < K; k += T) if (cnt[k]) atomicAdd(&counts[k], cnt[k]);
 }
 
 // ---- per-query post-processing (k_postfilter, k_postproc) ----

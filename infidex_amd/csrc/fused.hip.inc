@@ -197,7 +197,7 @@ __global__ __launch_bounds__(P2_THREADS) void k_prep2(DevIndex ix, const infx_hi
     // <= T lies inside its list's window, so one round gathers at most nL * B <= P2_CAP ids, sorts and de-duplicates them.
     // Deleted documents (SearchPipeline.cs:463-465, 532-537): a deleted WordMatcher-only id still counts against wmLimit but is not scored and
     // gets no docIndex — lv0/lv1 track the first two LIVE WordMatcher-only ids (only needed while Stage 1 supplies fewer than two documents).
-    const uint8_t* del = ix.deleted;
+    const uint8_t* del = q_deleted(ix, (uint32_t)nd + (uint32_t)qi);      // (the table holds the Stage-1 queries' entries, then the fused queries')
     int32_t lv0 = -1, lv1 = -1;
     uint32_t nu = 0;
     while ((nu < need || (del && ntop + (lv0 >= 0) + (lv1 >= 0) < 2u)) && nL > 0) {

@@ -75,8 +75,21 @@ struct QueryCov {
     std::vector<infx_finalize_setup> fin; std::vector<int32_t> qLimit; std::vector<double> relativeq;
     std::vector<uint8_t> reject; std::vector<int32_t> status; std::vector<std::string> err;
 };
+// Pre-filters of the session's next batch (infx_engine_set_query_prefilters): consumed by that batch like QueryCov, with or without QueryOpts.
+struct QueryPre {
+    bool on = false, bound = false; uint32_t nq = 0;
+    std::vector<std::string> expr;             // per query: its pre-filter ("" = none, or refused)
+    std::vector<uint8_t> has, reject; std::vector<int32_t> status; std::vector<std::string> err;      // has: the query asked for one
+    std::vector<std::string> pinned;           // cache entries the batch holds
+};
+// One mask of the session's cache (mask slot i of its stream): the expression it was built from, the engine's mask epoch at that time, the live documents
+// it accepts, when it was last used (least recently used first out)
+struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t count = 0; bool valid = false; };
 struct infx_session {
     QueryCov qc;
+    QueryPre qp;
+    PreMask preMask[INFX_MAX_PREFILTERS]; uint64_t preTick = 0; uint32_t preCountBuf[INFX_MAX_PREFILTERS] = {};      // preCountBuf: where a build's counts land
+    std::vector<uint32_t> lastInPre; uint32_t preBuilt = 0, preReused = 0, preLaunches = 0;      // of the last batch (or infx_engine_prefilter_mask)
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
     QueryOpts qo;
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
@@ -137,6 +150,12 @@ static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_res
 static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static void clear_query_options(infx_session* S);
 static int32_t query_cov_check(infx_session* S, uint32_t nq);
+static int32_t query_pre_check(infx_session* S, uint32_t nq);
+static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static void clear_query_prefilters(infx_session* S);
+static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, std::vector<int>& builtSlots);
+static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots);
+static void take_prefilter_counts(infx_session* S, uint32_t nq, const std::vector<int>& builtSlots);
 static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
 static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len);
@@ -203,6 +222,9 @@ struct infx_engine {
         }
     }
     infx_coverage_setup cs = {2, 20, 2, 3, 7, 1, 0, 5, 0.2, 1, 1, 1, 1, 1, 1, 0, 254};      // the engine-wide CoverageSetup (infx_engine_set_coverage_setup)
+    // Pre-filter masks (one byte per document, cached per session) are valid for one epoch: whatever changes a document's Deleted flag or what a compiled
+    // filter accepts — a deletion, a restore, a new column, a (re-)index — starts the next one
+    std::atomic<uint64_t> maskEpoch{1};
     HostIndex ix;
     PlanGate gate;
     CollSeq collSeq;
@@ -504,6 +526,7 @@ static int32_t finish_index(infx_engine* e) {
         rc = refresh_first_live(e); if (rc) return rc;
     }
     e->indexed = true;
+    e->maskEpoch++;
     return INFX_OK;
 }
 
@@ -1157,10 +1180,14 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     const bool dbg = e->cfg.want_features != 0;
     rc = stage_long_queries(S, FI); if (rc) return rc;
     rc = stage_coverage_setup(S, nq, true); if (rc) return rc;
+    // Pre-filters: the masks the batch is missing are staged on the session's stream (one launch in front of the batch, no host wait), each query's flags installed
+    std::vector<int> builtSlots;
+    rc = stage_prefilters(e, S, nq, fq, builtSlots); if (rc) return rc;
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
-    if (rc) { g_eerr = infx_last_error(); return rc; }
+    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); return rc; }
+    take_prefilter_counts(S, nq, builtSlots);
     B.t3 = now_ms();
     // Kernel durations are resolved when somebody asks (infx_engine_session_last_timings): every hipEventElapsedTime is a HIP API call that queues behind the
     // launches of the other sessions (measured: 2.8-3.3 ms of "post" time per batch on two of three boxes with six sessions).
@@ -1213,11 +1240,13 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
                                  int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                  uint32_t* out_counts, uint32_t* out_flags) {
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (rc) return rc; }
     e->searched.store(true, std::memory_order_relaxed);
+    S->lastInPre.assign(nq, 0);
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     query_cov_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
+    query_pre_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     return rc ? rc : rc2;
 }
 static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
@@ -1293,8 +1322,9 @@ int32_t infx_session_phase0(infx_session* S, uint32_t nq, const uint16_t* q_aren
     if (S->e && S->e->nranks > 1 && depth != S->e->ix.cfg.maxDepth) return efail(INFX_EINVAL, "document shards search with CoverageDepth == the engine's max_depth");
     if (S->qo.on && S->qo.bound) clear_query_options(S);        // left by a sharded batch that failed between its phase 0 and phase 4
     if (S->qc.on && S->qc.bound) S->qc = QueryCov();
-    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (rc) return rc; }
-    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on;
+    if (S->qp.on && S->qp.bound) clear_query_prefilters(S);
+    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (rc) return rc; }
+    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on; S->qp.bound = S->qp.on; S->lastInPre.assign(nq, 0);
     PlanGateHold hold(S->e->gate);
     int32_t rc = ph_plan(S->e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     if (nunions) *nunions = (uint32_t)S->batch->pending.size();
@@ -1766,7 +1796,7 @@ int32_t infx_session_coll_stats(infx_session* S, uint64_t* out4) {      // all-r
 }
 int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits, const uint32_t* all_counts, int32_t max_results, int32_t enable_coverage, uint64_t* ncand) {
     if (!S || W < 1 || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (rc) return rc; }
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
     if (hostPhases) {
         int32_t rc = ph_stage2(S->e, S, W, all_hits, all_counts, max_results, enable_coverage); if (rc) return rc;
@@ -1811,7 +1841,7 @@ int32_t infx_session_phase2x(infx_session* S, const uint32_t* global_counts, voi
 }
 int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, const void* all_counts, int32_t max_results, int32_t enable_coverage, void* outs) {
     if (!S || W < 1 || max_results < 1 || !outs) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (rc) return rc; }
     infx_engine* e = S->e; Batch& B = *S->batch;
     B.maxResults = max_results;
     std::shared_ptr<FusedIn> FIp; int32_t rc = fused_inputs_for_phase3(e, S, max_results, enable_coverage, FIp); if (rc) return rc;
@@ -1841,14 +1871,16 @@ int32_t infx_session_phase4(infx_session* S, const int32_t* merged_outs3, int64_
         int32_t rc = ph_finalize(S->e, S, (const infx_cov_out*)merged_outs3, out_keys, out_scores, out_ties, out_counts, out_flags);
         const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK);
         query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
+        query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
         return rc ? rc : rc2;
     }
     Batch& B = *S->batch;
     if (B.nq) {
         int32_t rc = infx_shard_finalize(S->stream, B.nq, (const infx_cov_out*)merged_outs3, B.depth, B.maxResults, out_keys, out_scores, out_ties, out_counts, out_flags);
-        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); return rc; }
+        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); query_pre_finish(S, out_counts, out_flags, false); return rc; }
         rc = query_options_finish(S, out_counts, out_flags, true);
         query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
+        query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
         if (rc) return rc;
         float ms5[5] = {0, 0, 0, 0, 0}; infx_last_fused_timings(S->stream, ms5); S->msFin = ms5[4];
     }
@@ -2266,7 +2298,7 @@ int32_t infx_engine_delete_documents(infx_engine* e, const int64_t* keys, int64_
     }
     if (out_marked) *out_marked = marked;
     if (e->dev) { int32_t rc = infx_set_deleted(e->dev, (uint32_t)N, e->deleted.data()); if (rc) { g_eerr = infx_last_error(); return rc; } }
-    e->invalidate_filter_counts();
+    e->invalidate_filter_counts(); e->maskEpoch++;
     return refresh_first_live(e);
 }
 // Document.Deleted = true on single documents, by internal id (indexing order): the documents of one key need not share the flag (a persisted index
@@ -2279,7 +2311,7 @@ int32_t infx_engine_delete_document_ids(infx_engine* e, const int64_t* ids, int6
     for (int64_t i = 0; i < n; i++) if (ids[i] >= 0 && ids[i] < N && !e->deleted[(size_t)ids[i]]) { e->deleted[(size_t)ids[i]] = 1; marked++; }
     if (out_marked) *out_marked = marked;
     if (e->dev) { int32_t rc = infx_set_deleted(e->dev, (uint32_t)N, e->deleted.data()); if (rc) { g_eerr = infx_last_error(); return rc; } }
-    e->invalidate_filter_counts();
+    e->invalidate_filter_counts(); e->maskEpoch++;
     return refresh_first_live(e);
 }
 // Clears every Deleted flag (what a reload of the undeleted documents would give).
@@ -2287,7 +2319,7 @@ int32_t infx_engine_restore_documents(infx_engine* e) {
     if (!e) return efail(INFX_EINVAL, "null argument");
     e->deleted.clear();
     if (e->dev && e->indexed) { int32_t rc = infx_set_deleted(e->dev, 0, nullptr); if (rc) { g_eerr = infx_last_error(); return rc; } }
-    e->invalidate_filter_counts();
+    e->invalidate_filter_counts(); e->maskEpoch++;
     return e->indexed ? refresh_first_live(e) : INFX_OK;
 }
 
@@ -2309,6 +2341,7 @@ int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, i
         if (rc) { g_eerr = infx_last_error(); return rc; }
     }
     e->columns.push_back(std::move(c));
+    e->maskEpoch++;
     e->retire_filters();      // leaf tables of filters compiled before this field existed treat it as null: compile again on next use
     return INFX_OK;
 }
@@ -2602,6 +2635,7 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     S->facetCols = facetCols;
     S->lastErr = Q.err;
     if (S->qc.on && S->qc.nq == nq) for (uint32_t i = 0; i < nq; i++) if (S->qc.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = S->qc.err[i];
+    if (S->qp.on && S->qp.nq == nq) for (uint32_t i = 0; i < nq; i++) if (S->qp.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = S->qp.err[i];
     Q.on = true;
     S->qo = std::move(Q);
     if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = S->qo.status[i];
@@ -2777,6 +2811,185 @@ static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFin
     int32_t rc = infx_stream_set_coverage(S->stream, &m, (uint32_t)fin.size(), fin.empty() ? nullptr : fin.data());
     if (rc) g_eerr = infx_last_error();
     return rc;
+}
+
+// ---- Query.pre_filter: rank only the documents a filter accepts -----------------------------------------------------------------------------------------
+// A query with a pre-filter P returns what it would return if every document P does not accept carried Document.Deleted (include/infidex_hip.h, "pre-filter
+// masks").  The masks live per session, in the mask slots of its stream: at most INFX_MAX_PREFILTERS, keyed by the expression, least recently used first out,
+// valid for one mask epoch of the engine.
+static void clear_query_prefilters(infx_session* S) {
+    if (!S->qp.on) return;
+    { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, S->qp.pinned, -1); S->e->evict_filters(); }
+    S->qp = QueryPre();
+}
+int32_t infx_engine_set_query_prefilters(infx_session* S, uint32_t nq, const char* const* exprs, int32_t* out_status) {
+    if (!S || (nq && !exprs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    clear_query_prefilters(S);
+    if (nq == 0) return INFX_OK;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the pre-filter masks are built on the device");
+    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
+    QueryPre Q; Q.nq = nq;
+    Q.expr.assign(nq, std::string()); Q.has.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        std::unordered_set<std::string> distinct;
+        for (uint32_t i = 0; i < nq; i++) {
+            if (!exprs[i]) continue;
+            Q.has[i] = 1;
+            auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
+            if (engine_sharded(e)) { reject(INFX_EUNSUPPORTED, "a pre-filter needs an engine that is not sharded: the masks cover one device's documents"); continue; }
+            if (hostPhases) { reject(INFX_EUNSUPPORTED, "a pre-filter runs in the device pipeline: the host phases (INFX_PHASED) do not read the masks"); continue; }
+            CompiledFilter* cf = nullptr;
+            const int32_t rc = compile_filter(e, exprs[i], &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
+            if (rc) { reject(rc, g_eerr); continue; }
+            if (!distinct.count(exprs[i])) {
+                if (distinct.size() >= INFX_MAX_PREFILTERS) { reject(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch; split the batch"); continue; }
+                distinct.insert(exprs[i]); Q.pinned.push_back(exprs[i]); pin_filters(e, {std::string(exprs[i])}, +1);
+            }
+            Q.expr[i] = exprs[i];
+        }
+    }
+    // the messages of this batch: beside the ones its options and coverage setups left (installed before, for the same nq); a message of an EARLIER batch goes
+    const bool sameBatch = (S->qo.on && S->qo.nq == nq) || (S->qc.on && S->qc.nq == nq);
+    if (!sameBatch || S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
+    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
+    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
+    Q.on = true;
+    S->qp = std::move(Q);
+    return INFX_OK;
+}
+static int32_t query_pre_check(infx_session* S, uint32_t nq) {
+    if (!S->qp.on) return INFX_OK;
+    if (nq != S->qp.nq) { clear_query_prefilters(S); return efail(INFX_EINVAL, "the per-query pre-filters were installed for a batch of another size"); }
+    return INFX_OK;
+}
+// The batch is done: a query whose pre-filter was refused comes back empty with result flag bit 4; the pre-filters are consumed
+static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
+    if (!S->qp.on) return;
+    const QueryPre& Q = S->qp;
+    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
+    for (uint32_t i = 0; i < Q.nq; i++) if (Q.reject[i]) {
+        if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
+        if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
+    }
+    clear_query_prefilters(S);
+}
+// The mask slots of `exprs` (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: slots[k] for exprs[k]; the ones that have to be built are staged on
+// the stream as ONE build (infx_filter_masks) and listed in builtSlots — their counts land in S->preCountBuf, in that order, when the stream is next waited for.
+static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<std::string>& exprs, std::vector<int>& slots, std::vector<int>& builtSlots) {
+    const uint64_t ep = e->maskEpoch.load(); const uint64_t tick = ++S->preTick;
+    slots.assign(exprs.size(), -1); builtSlots.clear();
+    S->preBuilt = S->preReused = S->preLaunches = 0;
+    for (size_t k = 0; k < exprs.size(); k++)
+        for (int i = 0; i < INFX_MAX_PREFILTERS; i++) { PreMask& M = S->preMask[i]; if (M.valid && M.epoch == ep && M.expr == exprs[k]) { slots[k] = i; M.lastUse = tick; S->preReused++; break; } }
+    std::vector<infx_filter_prog> progs; std::vector<uint8_t*> ptrs;
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    for (size_t k = 0; k < exprs.size(); k++) {
+        if (slots[k] >= 0) continue;
+        int best = -1;      // a slot of an earlier epoch or an empty one first, else the least recently used that this batch does not use
+        for (int i = 0; i < INFX_MAX_PREFILTERS; i++) {
+            PreMask& M = S->preMask[i];
+            if (M.valid && M.epoch == ep && M.lastUse == tick) continue;
+            const bool stale = !M.valid || M.epoch != ep;
+            if (best < 0) { best = i; continue; }
+            const PreMask& Bm = S->preMask[best]; const bool bestStale = !Bm.valid || Bm.epoch != ep;
+            if (stale != bestStale ? stale : (!stale && M.lastUse < Bm.lastUse)) best = i;
+        }
+        if (best < 0) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch");
+        CompiledFilter* cf = nullptr;
+        { int32_t rc = compile_filter(e, exprs[k].c_str(), &cf, false); if (rc) return rc; }
+        uint8_t* p = nullptr;
+        { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &p); if (rc) { g_eerr = infx_last_error(); return rc; } }
+        PreMask& M = S->preMask[best]; M.expr = exprs[k]; M.epoch = ep; M.lastUse = tick; M.count = 0; M.valid = true;
+        slots[k] = best; builtSlots.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(p);
+    }
+    if (!builtSlots.empty()) {
+        int32_t rc = infx_filter_masks(S->stream, (uint32_t)progs.size(), progs.data(), ptrs.data(), S->preCountBuf);
+        if (rc) { g_eerr = infx_last_error(); for (int b : builtSlots) S->preMask[b].valid = false; builtSlots.clear(); return rc; }
+        S->preBuilt = (uint32_t)builtSlots.size();
+    }
+    return INFX_OK;
+}
+static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots) {
+    for (int b : builtSlots) S->preMask[b].valid = false;
+    if (S->stream) { infx_filter_masks(S->stream, 0, nullptr, nullptr, nullptr); infx_stream_set_doc_masks(S->stream, 0, nullptr); }
+}
+// Before the batch's infx_search_fused: refuses a pre-filter on a browse query, finds or stages the masks, installs each query's flags on the stream
+static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, std::vector<int>& builtSlots) {
+    builtSlots.clear();
+    S->lastInPre.assign(nq, 0); S->preBuilt = S->preReused = S->preLaunches = 0;
+    if (!S->qp.on || S->qp.nq != nq) return INFX_OK;
+    QueryPre& Q = S->qp;
+    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nq, -1);
+    for (uint32_t i = 0; i < nq; i++) {
+        if (!Q.has[i] || Q.reject[i]) continue;
+        if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: Filter already restricts the scan
+            Q.reject[i] = 1; Q.status[i] = INFX_EUNSUPPORTED; Q.err[i] = "a pre-filter does not apply to a browse query (empty text with EnableFacets): its Filter already restricts the scan";
+            fq[i].flags &= ~INFX_FQ_BROWSE;
+            continue;
+        }
+        auto it = idx.find(Q.expr[i]);
+        if (it == idx.end()) { it = idx.emplace(Q.expr[i], (int)exprs.size()).first; exprs.push_back(Q.expr[i]); }
+        of[i] = it->second;
+    }
+    if (exprs.empty()) return INFX_OK;
+    std::vector<int> slots;
+    { int32_t rc = acquire_masks(e, S, exprs, slots, builtSlots); if (rc) { unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; } }
+    std::vector<const uint8_t*> masks(nq, nullptr);
+    for (uint32_t i = 0; i < nq; i++) if (of[i] >= 0) {
+        uint8_t* p = nullptr;
+        int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[of[i]], &p);
+        if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; }
+        masks[i] = p;
+    }
+    int32_t rc = infx_stream_set_doc_masks(S->stream, nq, masks.data());
+    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; }
+    return INFX_OK;
+}
+// After the batch: the counts of the masks it built have landed; each pre-filtered query's count
+static void take_prefilter_counts(infx_session* S, uint32_t nq, const std::vector<int>& builtSlots) {
+    for (size_t k = 0; k < builtSlots.size(); k++) S->preMask[builtSlots[k]].count = S->preCountBuf[k];
+    if (!builtSlots.empty()) { uint32_t b = 0, l = 0; infx_last_filter_mask_stats(S->stream, &b, &l); S->preLaunches = l; }
+    if (!S->qp.on || S->qp.nq != nq) return;
+    const uint64_t ep = S->e->maskEpoch.load();
+    for (uint32_t i = 0; i < nq; i++) {
+        if (!S->qp.has[i] || S->qp.reject[i]) continue;
+        for (const PreMask& M : S->preMask) if (M.valid && M.epoch == ep && M.expr == S->qp.expr[i]) { S->lastInPre[i] = M.count; break; }
+    }
+}
+int32_t infx_engine_last_in_prefilter(infx_session* S, uint32_t nq, uint32_t* out) {
+    if (!S || (nq && !out)) return efail(INFX_EINVAL, "null argument");
+    if (nq != S->lastInPre.size()) return efail(INFX_EINVAL, "no batch of this size on the session");
+    if (nq) std::memcpy(out, S->lastInPre.data(), (size_t)nq * 4);
+    return INFX_OK;
+}
+int32_t infx_engine_last_prefilter_stats(infx_session* S, uint32_t* built, uint32_t* reused, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (built) *built = S->preBuilt;
+    if (reused) *reused = S->preReused;
+    if (launches) *launches = S->preLaunches;
+    return INFX_OK;
+}
+int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* out_bytes, uint64_t cap) {
+    if (!S || !expr || !out_bytes) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    if (!e->dev || !S->stream || !e->indexed) return efail(INFX_EHIP, "no GPU: the pre-filter masks are built on the device");
+    if (engine_sharded(e)) return efail(INFX_EUNSUPPORTED, "a pre-filter needs an engine that is not sharded");
+    const uint64_t N = (uint64_t)e->ix.N;
+    if (cap < N) return efail(INFX_EINVAL, "the mask holds one byte per indexed document");
+    { std::lock_guard<std::mutex> lk(e->filterMu); CompiledFilter* cf = nullptr; int32_t rc = compile_filter(e, expr, &cf, false); if (rc) return rc; }
+    std::vector<int> slots, built;
+    { int32_t rc = acquire_masks(e, S, {std::string(expr)}, slots, built); if (rc) { unstage_prefilters(S, built); return rc; } }
+    int32_t rc = infx_stream_wait(S->stream);      // builds what was staged
+    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); return rc; }
+    take_prefilter_counts(S, 0, built);
+    uint8_t* p = nullptr;
+    rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[0], &p);
+    if (!rc && N) rc = infx_stream_copy(S->stream, out_bytes, p, N);
+    if (!rc) rc = infx_stream_wait(S->stream);
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    return INFX_OK;
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

@@ -65,7 +65,13 @@ struct DevIndex {
     const int64_t* docKeyAll;  // DocumentKey by GLOBAL internal id (== docKey when unsharded)
     int packed;                // 1: postDoc entries are (doc << 8) | tf (shards below 2^24 - 1 documents), 0: plain doc ids + postW
     const uint64_t* psOff; const int32_t* psDocs; uint32_t nSets;
+    // Pre-filters (infx_stream_set_doc_masks): per query of the batch its own Deleted flags — the mask of its pre-filter, or `deleted` for a query without
+    // one — by GLOBAL internal id; entries [0, nd) belong to the Stage-1 queries, [nd, nd + nq) to the fused queries.  nullptr unless the batch has a
+    // pre-filtered query: every query then reads `deleted`.
+    const uint8_t* const* qDeleted;
 };
+// Document.Deleted flags of query q (nullptr = nothing deleted).  Wave-uniform: read once per wave / workgroup, never per posting.
+__device__ __forceinline__ const uint8_t* q_deleted(const DevIndex& ix, uint32_t q) { return ix.qDeleted ? ix.qDeleted[q] : ix.deleted; }
 
 // Main streams of the sessions, one pool per device for the whole process.  The runtime serves the streams of a process from a pool of hardware queues per
 // priority (4 by default): a stream created once that pool is full is put on the queue with the fewest streams, busy or idle, the most recently created first
@@ -281,6 +287,13 @@ struct infx_stream {
     uint32_t lastCountK = 0, lastCountLaunches = 0;     // the filter programs the last finalize counted, and its k_filter_count_multi launches
     void* dPostBlob = nullptr; size_t capPostBlob = 0;     // the batch's DevPostBatch + program table + boost list + descriptors (+ packed programs)
     void* dQCount = nullptr; size_t capQCount = 0;
+    // pre-filter masks: the stream's mask slots (infx_stream_mask_slot), a staged build (infx_filter_masks: programs packed as qpCode is, enqueued by the next
+    // batch or by infx_stream_wait), the per-query flags of the next batch (infx_stream_set_doc_masks) and their device table (DevIndex::qDeleted while qDelOn)
+    uint8_t* dMask[INFX_MAX_PREFILTERS] = {}; size_t capMask[INFX_MAX_PREFILTERS] = {};
+    bool mkStaged = false; std::vector<QpProg> mkProgs; std::vector<uint8_t> mkCode; DevCountCols mkCols{}; DevMaskOut mkOut{}; uint32_t* mkCountsOut = nullptr;
+    void* dMaskBlob = nullptr; size_t capMaskBlob = 0; void* dMaskCnt = nullptr; size_t capMaskCnt = 0;
+    uint32_t lastMaskBuilt = 0, lastMaskLaunches = 0;
+    std::vector<const uint8_t*> docMasks; void* dQDel = nullptr; size_t capQDel = 0; bool qDelOn = false;
     // browse queries (INFX_FQ_BROWSE) of the batch being staged: (query, rows asked), recorded by the prep stage and consumed by the finalize
     std::vector<std::pair<uint32_t, uint32_t>> browseQ;
     std::vector<int32_t> qpRows;      // max_results of each fused query of the batch, kept only by an index with more than INFX_FILTER_MAX_ROWS post rows
@@ -393,6 +406,9 @@ static int32_t grow(infx_stream* s, void** p, size_t* cap, size_t need) {
 }
 static void ws_release(infx_stream* s, void* p) { if (p) s->parked.push_back(p); }
 #define GROW(p, cap, need) do { int32_t rc_ = grow(s, (void**)&(p), &(cap), (need)); if (rc_) return rc_; } while (0)      /* `s`: the stream of the enclosing call */
+// The index as a launch on stream s sees it: every kernel that takes DevIndex by value takes it from here.  qDeleted is the stream's per-query flags table
+// while a batch with a pre-filtered query is being enqueued (infx_search_fused), else nullptr: the kernels then read the index's Deleted flags.
+static inline DevIndex dev_index(const infx_stream* s) { DevIndex d = s->ix->d; d.qDeleted = s->qDelOn ? (const uint8_t* const*)s->dQDel : nullptr; return d; }
 
 // Stage-2 launches: the register budget of the fast variant is selectable for tuning (INFX_S2_WAVES = 2, 4 or 6 waves per SIMD)
 static int s2_waves() { static const int w = [] { const char* e = getenv("INFX_S2_WAVES"); int v = e ? atoi(e) : 0; return (v == 2 || v == 4 || v == 6 || v == 8) ? v : S2_MIN_WAVES; }(); return w; }
@@ -540,7 +556,7 @@ struct PlanStream {
 template <int R> static void launch_union(infx_stream* s, uint32_t nv, const uint32_t* dBeg, const uint32_t* dEnd, const int32_t* dMembers, uint32_t* dRangeCount,
                                             const unsigned long long* dBase, int32_t* outDocs) {
     uint64_t blocks = (uint64_t)nv * s->ix->d.nRanges;
-    k_union<R><<<dim3((unsigned)blocks), dim3(WAVE), 0, s->st>>>(s->ix->d, dBeg, dEnd, dMembers, nv, dRangeCount, dBase, outDocs);
+    k_union<R><<<dim3((unsigned)blocks), dim3(WAVE), 0, s->st>>>(dev_index(s), dBeg, dEnd, dMembers, nv, dRangeCount, dBase, outDocs);
 }
 static void launch_union_any(infx_stream* s, uint32_t nv, const uint32_t* dBeg, const uint32_t* dEnd, const int32_t* dMembers, uint32_t* dRangeCount,
                              const unsigned long long* dBase, int32_t* outDocs) {
@@ -591,14 +607,14 @@ template <int R> static void launch_acc(infx_stream* s, uint32_t nq, Arena ar, i
         const int maxTl = (std::min(64, std::max(1, maxT)) + 3) & ~3;
         static const int dbgS = [] { const char* e = getenv("INFX_ACCS_SKIP"); return e ? atoi(e) : 0; }();      // kernel ablation for profiling only
         const size_t ldsS = (sw + 64 + 4) * 4 + INFX_NCLASS * 4 + WAVE * 2 + WAVE * 12 + (size_t)WAVE * maxTl + (size_t)64 * maxTl;      // padded bitmap (one pad word per lane) | class histogram | slot table | slice table | hit matrix | slice samples
-#define ACCS_LAUNCH(MW_) k_accumulate_sparse<R, MW_><<<dim3((unsigned)blocks), dim3(WAVE), ldsS, s->st>>>(s->ix->d, (const DevQuery*)s->dQueries, (const DevTerm*)s->dTerms, (const int32_t*)s->dExtra, \
+#define ACCS_LAUNCH(MW_) k_accumulate_sparse<R, MW_><<<dim3((unsigned)blocks), dim3(WAVE), ldsS, s->st>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevTerm*)s->dTerms, (const int32_t*)s->dExtra, \
             (const int32_t*)s->dUDocs, (const uint32_t*)s->dURange, nq, ar, stripe, useGrp, (uint8_t*)s->dDense, (uint32_t)sparseT, nStripes, maxTl, dbgS)
         if (ar.maskWords == 4) ACCS_LAUNCH(4); else if (ar.maskWords == 2) ACCS_LAUNCH(2); else ACCS_LAUNCH(1);
 #undef ACCS_LAUNCH
         dense = (const uint8_t*)s->dDense;
     }
     const size_t lds = (size_t)R + 128 + ((size_t)(R / 32) + 2) * 4 + INFX_NCLASS * 4 + ACC_CAP_DEFAULT * 2;
-#define ACC_LAUNCH(MW_) k_accumulate<R, MW_><<<dim3((unsigned)blocks), dim3(WAVE), lds, s->st>>>(s->ix->d, (const DevQuery*)s->dQueries, (const DevTerm*)s->dTerms, (const int32_t*)s->dExtra, \
+#define ACC_LAUNCH(MW_) k_accumulate<R, MW_><<<dim3((unsigned)blocks), dim3(WAVE), lds, s->st>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevTerm*)s->dTerms, (const int32_t*)s->dExtra, \
         (const int32_t*)s->dUDocs, (const uint32_t*)s->dURange, nq, ar, maxT, stripe, useGrp, dbgSkip, (unsigned long long*)s->dStats, dense, nStripes, \
         s->nAccHeavy != 0xFFFFFFFFu ? (const uint32_t*)s->dAccOrder : nullptr, s->nAccHeavy != 0xFFFFFFFFu ? s->nAccHeavy : 0u)
     if (ar.maskWords == 4) ACC_LAUNCH(4); else if (ar.maskWords == 2) ACC_LAUNCH(2); else ACC_LAUNCH(1);
@@ -696,17 +712,17 @@ static int32_t launch_scan_and_chunks(infx_stream* s, uint32_t nq, Arena ar, ExB
     infx_index* ix = s->ix;
     const int rpc = 65536 / ix->d.R, nCont = (ix->d.nRanges + rpc - 1) / rpc;
     if (nCont > 65535) return fail(INFX_ECAPACITY, "exact replay: more than 65535 containers of 65536 documents in one shard%s");
-    k_ex_walk<false><<<dim3(nq, nCont), WAVE, 0, s->st>>>(ix->d, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag, xb, nCont);
+    k_ex_walk<false><<<dim3(nq, nCont), WAVE, 0, s->st>>>(dev_index(s), ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag, xb, nCont);
     k_ex_prefix<<<nq, EXS_THREADS, 0, s->st>>>((const uint32_t*)s->dExactFlag, xb, nCont);
-    k_ex_walk<true><<<dim3(nq, nCont), WAVE, 0, s->st>>>(ix->d, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag, xb, nCont);
+    k_ex_walk<true><<<dim3(nq, nCont), WAVE, 0, s->st>>>(dev_index(s), ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag, xb, nCont);
     k_ex_theta<<<nq, WAVE, 0, s->st>>>(ar, (const SelRule*)s->dRules, (uint32_t*)s->dExactFlag, xb, prior, nCont);
     HIPCHK(hipEventRecord(s->evXa, s->st));
     hipStream_t bigSt = s->st;
     if (useAux && s->stAux && s->st == s->stMain) { HIPCHK(hipStreamWaitEvent(s->stAux, s->evXa, 0)); bigSt = s->stAux; }
-    k_ex_chunk<16><<<EXP_GRID16, 16 * WAVE, 0, bigSt>>>(ix->d, (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksBig, 4, ix->avgdl);
-    k_ex_chunk<4><<<EXP_GRID4, 4 * WAVE, 0, bigSt>>>(ix->d, (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksMid, 2, ix->avgdl);
+    k_ex_chunk<16><<<EXP_GRID16, 16 * WAVE, 0, bigSt>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksBig, 4, ix->avgdl);
+    k_ex_chunk<4><<<EXP_GRID4, 4 * WAVE, 0, bigSt>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksMid, 2, ix->avgdl);
     if (bigSt != s->st) HIPCHK(hipEventRecord(s->evJoin, bigSt));
-    k_ex_chunk<1><<<EXP_GRID1, WAVE, 0, s->st>>>(ix->d, (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksSmall, 1, ix->avgdl);
+    k_ex_chunk<1><<<EXP_GRID1, WAVE, 0, s->st>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, xb, xb.tasksSmall, 1, ix->avgdl);
     if (bigSt != s->st) HIPCHK(hipStreamWaitEvent(s->st, s->evJoin, 0));
     HIPCHK(hipGetLastError());
     return INFX_OK;
@@ -766,7 +782,7 @@ static int32_t enqueue_exact(infx_stream* s, uint32_t nq, int stride) {
             }
         }
     }
-    k_exact1<<<nq, EX_THREADS, lds1, s->st>>>(ix->d, (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag,
+    k_exact1<<<nq, EX_THREADS, lds1, s->st>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag,
                                              fast ? 2u : 1u, ix->avgdl, (infx_hit*)s->dHits, (uint32_t*)s->dHitCount, stride, depthCap, s->dExactStat, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->evX1, s->st)); s->timedReplay = true;
@@ -1134,9 +1150,14 @@ int32_t infx_stream_fill0(infx_stream* s, void* dev, uint64_t bytes) {
     if (bytes) { HIPCHK(enter_device(s->ix->cfg.device)); HIPCHK(hipMemsetAsync(dev, 0, bytes, s->st)); s->unsynced = true; }
     return INFX_OK;
 }
+static int32_t mask_flush(infx_stream* s);
 int32_t infx_stream_wait(infx_stream* s) {
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     HIPCHK(enter_device(s->ix->cfg.device));
+    if (s->mkStaged) {      // a staged mask build (infx_filter_masks) that no batch has taken: built now
+        { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+        { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }
+    }
     return stream_sync(s);
 }
 
@@ -1189,7 +1210,8 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel};
+    for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
     for (void* p : s->parked) hipFree(p);
@@ -1535,14 +1557,14 @@ int32_t infx_stage2_batch(infx_stream* s, uint32_t nq, const infx_cov_query* q, 
     for (uint32_t i = 0; i < nq && !s->batchAlias; i++) if (q[i].reserved == 0) for (int32_t k = 0; k < q[i].text_len && k < (int32_t)INFX_MAX_QUERY_CHARS; k++) if (s2_host_is_alias(q[i].text[k])) { s->batchAlias = true; break; }
     UP(s->dCovC, cand, (size_t)ncand * sizeof(infx_cov_cand));
     HIPCHK(hipEventRecord(s->evC0, s->st));
-    S2_LAUNCH_FAST(ix->d, (const infx_cov_query*)s->dCovQ, nq,
+    S2_LAUNCH_FAST(dev_index(s), (const infx_cov_query*)s->dCovQ, nq,
                                                                                  (const infx_cov_cand*)s->dCovC, ncand, (infx_cov_out*)s->dCovO, feat_out ? (int32_t*)s->dCovF : nullptr, 0, 0, nullptr);
-    S2_LAUNCH_SLOW(ix->d, (const infx_cov_query*)s->dCovQ, nq,
+    S2_LAUNCH_SLOW(dev_index(s), (const infx_cov_query*)s->dCovQ, nq,
                                                                                  (const infx_cov_cand*)s->dCovC, ncand, (infx_cov_out*)s->dCovO, feat_out ? (int32_t*)s->dCovF : nullptr, 0, 1, nullptr);
     { int32_t rc_ = s2_huge_ready(s); if (rc_) return rc_; }
-    S2_LAUNCH_HUGE(ix->d, (const infx_cov_query*)s->dCovQ, nq,
+    S2_LAUNCH_HUGE(dev_index(s), (const infx_cov_query*)s->dCovQ, nq,
                                                                                  (const infx_cov_cand*)s->dCovC, ncand, (infx_cov_out*)s->dCovO, feat_out ? (int32_t*)s->dCovF : nullptr, 0, 1, nullptr);
-    S2_LAUNCH_LONGQ(ix->d, (const infx_cov_query*)s->dCovQ, nq,
+    S2_LAUNCH_LONGQ(dev_index(s), (const infx_cov_query*)s->dCovQ, nq,
                                                                                  (const infx_cov_cand*)s->dCovC, ncand, (infx_cov_out*)s->dCovO, feat_out ? (int32_t*)s->dCovF : nullptr, 0, 1, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->evC1, s->st));
@@ -1807,7 +1829,7 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
         static unsigned long long* dP2 = nullptr; static int p2Calls = 0;
         if (getenv("INFX_SEL_PROF") && nq >= 500) { if (!dP2) { hipMalloc((void**)&dP2, 4096 * 64); hipMemcpyToSymbol(HIP_SYMBOL(g_p2Prof), &dP2, sizeof(dP2)); } hipMemsetAsync(dP2, 0, (size_t)nq * 64, s->st); }
 #endif
-        k_prep2<<<nq, P2_THREADS, lds, s->st>>>(ix->d, dHitsAll, dHcAll, depth, W, (int)nd, (int)Dall, (const infx_fused_query*)s->dFQ,
+        k_prep2<<<nq, P2_THREADS, lds, s->st>>>(dev_index(s), dHitsAll, dHcAll, depth, W, (int)nd, (int)Dall, (const infx_fused_query*)s->dFQ,
                                                  (const infx_wm_list*)s->dFLists, (const int32_t*)s->dFOwned, depth, (int)Dp,
                                                  (infx_hit*)s->dFS1, (infx_cov_cand*)s->dCovC, (int32_t*)s->dFPairs, (FusedMeta*)s->dFMeta);
 #ifdef SEL_PROF
@@ -1817,14 +1839,14 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->evP1, s->st));
     HIPCHK(hipEventRecord(s->evC0, s->st));
-    S2_LAUNCH_FAST(ix->d, (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
+    S2_LAUNCH_FAST(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
                                                                                  (infx_cov_out*)s->dCovO, want_debug ? (int32_t*)s->dCovF : nullptr, 1, 0, (const int32_t*)s->dFPairs);
-    S2_LAUNCH_SLOW(ix->d, (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
+    S2_LAUNCH_SLOW(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
                                                                                  (infx_cov_out*)s->dCovO, want_debug ? (int32_t*)s->dCovF : nullptr, 1, 1, (const int32_t*)s->dFPairs);
     { int32_t rc_ = s2_huge_ready(s); if (rc_) return rc_; }
-    S2_LAUNCH_HUGE(ix->d, (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
+    S2_LAUNCH_HUGE(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
                                                                                  (infx_cov_out*)s->dCovO, want_debug ? (int32_t*)s->dCovF : nullptr, 1, 1, (const int32_t*)s->dFPairs);
-    S2_LAUNCH_LONGQ(ix->d, (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
+    S2_LAUNCH_LONGQ(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
                                                                                  (infx_cov_out*)s->dCovO, want_debug ? (int32_t*)s->dCovF : nullptr, 1, 1, (const int32_t*)s->dFPairs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->evC1, s->st));
@@ -1866,6 +1888,79 @@ static DevCountCols count_columns(const infx_filter_leaf* const* leaves, const u
         if (c < FILT_MAXCOL && !seen[c]) { seen[c] = true; cc.slot[c] = (uint8_t)cc.nUsed; cc.col[cc.nUsed++] = c; }
     }
     return cc;
+}
+
+// ---- pre-filter masks (k_filter_mask_multi) ----
+static int mask_slot_of(const infx_stream* s, const uint8_t* p) { for (int i = 0; i < INFX_MAX_PREFILTERS; i++) if (p && s->dMask[i] == p) return i; return -1; }
+static inline size_t mask_bytes(const infx_index* ix) { return (((size_t)std::max(ix->d.totalDocs, 0) + 3) & ~(size_t)3) + 4; }
+// enqueues the staged build on s->st: the programs' blob, one launch over the whole corpus, the counts' way back (they land at the next stream_sync)
+static int32_t mask_flush(infx_stream* s) {
+    if (!s->mkStaged) return INFX_OK;
+    s->mkStaged = false;
+    infx_index* ix = s->ix;
+    const uint32_t K = (uint32_t)s->mkProgs.size();
+    const int32_t n = ix->d.totalDocs;
+    s->lastMaskBuilt = K; s->lastMaskLaunches = 0;
+    if (!K) return INFX_OK;
+    for (int c = 0; c < FILT_MAXCOL; c++)
+        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    for (uint32_t k = 0; k < K; k++) {      // the kernel stores whole dwords up to the padded size
+        const int slot = mask_slot_of(s, s->mkOut.mask[k]);
+        if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a mask buffer is not a mask slot of this stream, or was made for a smaller corpus%s");
+    }
+    const size_t oCode = ((size_t)K * sizeof(DevFilter) + 15) & ~(size_t)15, total = oCode + s->mkCode.size();
+    GROW(s->dMaskBlob, s->capMaskBlob, total);
+    GROW(s->dMaskCnt, s->capMaskCnt, (size_t)INFX_MAX_PREFILTERS * 4);
+    char* D = (char*)s->dMaskBlob;
+    std::vector<uint8_t> H(total, 0);
+    for (uint32_t i = 0; i < K; i++) {
+        const auto& P = s->mkProgs[i];
+        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
+        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
+    }
+    if (!s->mkCode.empty()) std::memcpy(H.data() + oCode, s->mkCode.data(), s->mkCode.size());
+    UP(D, H.data(), total);
+    HIPCHK(hipMemsetAsync(s->dMaskCnt, 0, (size_t)K * 4, s->st));
+    if (n > 0) {
+        DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+        const DevCountCols& cc = s->mkCols;
+        // 256 threads while four workgroups' LDS fit a CU (40 KiB each), else one wave per workgroup (64 columns: 64 KiB)
+        const int threads = ((size_t)cc.nUsed * 4 * FMM_THREADS + K) * 4 <= 40 * 1024 ? FMM_THREADS : WAVE;
+        const size_t lds = ((size_t)cc.nUsed * 4 * threads + K) * 4;
+        const int64_t groups = ((int64_t)n + 3) / 4;
+        const int grid = (int)std::min<int64_t>(FCM_MAXGRID, (groups + threads - 1) / threads);
+        {   // sessions launch from several threads: the attribute is raised under a lock, and only past its high-water mark
+            static std::mutex mu; static size_t attr = 0;
+            std::lock_guard<std::mutex> lk(mu);
+            if (lds > 64 * 1024 && lds > attr) { HIPCHK(hipFuncSetAttribute((const void*)k_filter_mask_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = lds; }
+        }
+        k_filter_mask_multi<<<grid, threads, lds, s->st>>>((const DevFilter*)D, K, cc, cols, n, ix->d.deleted, s->mkOut, (uint32_t*)s->dMaskCnt);
+        HIPCHK(hipGetLastError());
+        s->lastMaskLaunches = 1;
+    }
+    if (s->mkCountsOut) DOWN(s->mkCountsOut, s->dMaskCnt, (size_t)K * 4);
+    return INFX_OK;
+}
+// the flags table of the batch being enqueued: DevIndex::qDeleted of its launches (dev_index).  Only for a batch with a pre-filtered query.
+static int32_t stage_doc_masks(infx_stream* s, uint32_t nd, uint32_t nq, const infx_fused_query* fq) {
+    s->qDelOn = false;
+    bool any = false; for (auto m : s->docMasks) any = any || m != nullptr;
+    if (!any) return INFX_OK;
+    infx_index* ix = s->ix;
+    std::vector<const uint8_t*> tbl((size_t)nd + nq, ix->d.deleted); std::vector<uint8_t> set(nd, 0);
+    for (uint32_t i = 0; i < nq; i++) {
+        const uint8_t* m = s->docMasks[i] ? s->docMasks[i] : ix->d.deleted;
+        if (s->docMasks[i]) { const int slot = mask_slot_of(s, m); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a document mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
+        tbl[(size_t)nd + i] = m;
+        const int32_t d = fq[i].dev;
+        if (d < 0 || (uint32_t)d >= nd) continue;
+        if (set[d] && tbl[d] != m) return fail(INFX_EINVAL, "two queries with different document masks share one Stage-1 query%s");
+        tbl[d] = m; set[d] = 1;
+    }
+    GROW(s->dQDel, s->capQDel, tbl.size() * sizeof(const uint8_t*));
+    UP(s->dQDel, tbl.data(), tbl.size() * sizeof(const uint8_t*));
+    s->qDelOn = true;
+    return INFX_OK;
 }
 
 // The batch's browse queries (s->browseQ; browse.hip.inc): grouped by filter program, all groups answered by one ordered scan of the corpus, which
@@ -2053,7 +2148,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         else if (s->finDefaultN < nq) { std::vector<infx_finalize_setup> d(nq, FIN_DEFAULT_SETUP); UP(s->dFin, d.data(), (size_t)nq * sizeof(infx_finalize_setup)); s->finDefaultN = nq; }
     }
     HIPCHK(hipEventRecord(s->evF0, s->st));
-    k_finalize<<<nq, P2_THREADS, lds, s->st>>>(ix->d, (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
+    k_finalize<<<nq, P2_THREADS, lds, s->st>>>(dev_index(s), (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
                                                 (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr,
@@ -2164,13 +2259,18 @@ int32_t infx_search_fused(infx_stream* s, uint32_t nd, const infx_query* q, uint
     if (!s || (nd && (!q || (nterms && !terms))) || (nq && (!fq || !cq || !out_keys || !out_scores || !out_counts)) || (nlists && !lists) || (owned_n && !owned))
         return fail(INFX_EINVAL, "null argument%s");
     infx_index* ix = s->ix;
+    struct MaskUse { infx_stream* s; ~MaskUse() { s->qDelOn = false; s->docMasks.clear(); } } maskUse{s};      // the per-query flags are this batch's, whatever its outcome
     if (!ix->havePostings || !ix->haveDocs || !ix->d.text) return fail(INFX_EINVAL, "index not uploaded%s");
     if (ix->nranks > 1 || ix->d.docBase != 0) return fail(INFX_EINVAL, "infx_search_fused needs an unsharded index (sharded engines use infx_shard_*)%s");
+    if (!s->docMasks.empty() && s->docMasks.size() != nq) return fail(INFX_EINVAL, "the per-query document masks were installed for a batch of another size%s");
     if (nq == 0) return INFX_OK;
     { int32_t rc_ = fused_check_queries(ix, nd, nq, fq, cq, nlists, lists, owned_n, depth, max_results, s->nLongQ); if (rc_) return rc_; }
     for (uint32_t i = 0; i < nd; i++) if (q[i].depth != depth) return fail(INFX_EINVAL, "all queries of a fused batch share one depth%s");
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    // Pre-filters: the masks this batch is missing are built first, on this stream (one launch, no host wait); then the table of each query's flags
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }
+    { int32_t rc_ = stage_doc_masks(s, nd, nq, fq); if (rc_) return rc_; }
     // Turnstile.  k_accumulate and k_select fill the GPU on their own; the replay, candidate assembly and Stage 2 behind them are narrow.  Sessions that
     // submit together run their wide kernels against each other and then sit in their narrow phases together — convoys that leave the GPU half empty (the
     // bench timeline showed three batches finishing within a millisecond of each other, then nothing wide to run).  Each batch's k_accumulate therefore waits
@@ -2300,7 +2400,7 @@ int32_t infx_shard_replay_local(infx_stream* s, int32_t nshards, uint32_t nd, co
         const size_t lds = (size_t)Dall * 8 + 257 * 4;
         static std::mutex mu; static size_t attr = 0;
         { std::lock_guard<std::mutex> lk(mu); if (lds > 64 * 1024 && lds > attr) { HIPCHK(hipFuncSetAttribute((const void*)k_gflag, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = lds; } }
-        k_gflag<<<nd, 256, lds, s->st>>>(ix->d, nshards, (int)nd, depth, (int)Dall, (const infx_hit*)s->dFHitsAll, (const uint32_t*)s->dFHcAll, (const float*)s->dAllNext,
+        k_gflag<<<nd, 256, lds, s->st>>>(dev_index(s), nshards, (int)nd, depth, (int)Dall, (const infx_hit*)s->dFHitsAll, (const uint32_t*)s->dFHcAll, (const float*)s->dAllNext,
                                         (uint32_t*)s->dExactFlag, (float*)s->dPrior, s->dExactStat + 4, possible ? 1 : 0, (const uint32_t*)s->dWideQ, s->nWide);
     }
     ExBufs xb{};
@@ -2384,7 +2484,7 @@ int32_t infx_shard_replay_chain(infx_stream* s, uint32_t nd, const uint32_t* nee
     UPX(s->dChainNeed, need, (size_t)nd * 4);
     size_t lds1 = 0; { int32_t rc_ = exact1_lds_ready(ix, s->maskWords, &lds1); if (rc_) return rc_; }
     Arena ar = make_arena(s);
-    k_exact1<<<nd, EX_THREADS, lds1, s->st>>>(ix->d, (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag,
+    k_exact1<<<nd, EX_THREADS, lds1, s->st>>>(dev_index(s), (const DevQuery*)s->dQueries, (const DevRefTerm*)s->dRefTerms, ar, (const SelRule*)s->dRules, (const uint32_t*)s->dExactFlag,
                                              0u, ix->avgdl, (infx_hit*)s->dHits, (uint32_t*)s->dHitCount, depth, depthCap, nullptr, (uint32_t*)s->dChainState, (const uint32_t*)s->dChainNeed);
     HIPCHK(hipGetLastError());
     DOWNX(state, s->dChainState, words * 4);
@@ -2794,6 +2894,56 @@ int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uin
     }
     if (total) DOWN(counts_out, s->dFacAll, total * 4);
     SYNC();
+    return INFX_OK;
+}
+int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {
+    if (!s || !out || slot >= INFX_MAX_PREFILTERS) return fail(INFX_EINVAL, "bad mask slot%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const size_t need = mask_bytes(ix);
+    if (s->capMask[slot] < need) {
+        HIPCHK(enter_device(ix->cfg.device));
+        if (s->unsynced) { int32_t rc_ = stream_sync(s); if (rc_) return rc_; }      // work queued on the old buffer
+        if (s->dMask[slot]) ws_release(s, s->dMask[slot]);
+        s->dMask[slot] = nullptr; s->capMask[slot] = 0;
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) return fail(INFX_ENOMEM, "hipMalloc of a document mask failed%s");
+        s->dMask[slot] = (uint8_t*)p; s->capMask[slot] = need;
+    }
+    *out = s->dMask[slot];
+    return INFX_OK;
+}
+int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint8_t* const* masks, uint32_t* counts) {
+    if (!s || (k && (!progs || !masks))) return fail(INFX_EINVAL, "null argument%s");
+    s->mkStaged = false; s->mkProgs.clear(); s->mkCode.clear(); s->mkCountsOut = nullptr;
+    if (!k) return INFX_OK;
+    if (k > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) masks in one build%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    if (ix->nranks > 1 || ix->d.docBase != 0) return fail(INFX_EUNSUPPORTED, "document masks need an unsharded index%s");
+    for (uint32_t i = 0; i < k; i++) {
+        if (mask_slot_of(s, masks[i]) < 0) return fail(INFX_EINVAL, "a mask buffer is not a mask slot of this stream%s");
+        for (uint32_t j = 0; j < i; j++) if (masks[j] == masks[i]) return fail(INFX_EINVAL, "two masks of one build share a slot%s");
+    }
+    { int32_t rc_ = pack_progs(ix, k, progs, s->mkProgs, s->mkCode); if (rc_) { s->mkProgs.clear(); s->mkCode.clear(); return rc_; } }
+    std::vector<const infx_filter_leaf*> lv(k); std::vector<uint32_t> nl(k);
+    for (uint32_t i = 0; i < k; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
+    s->mkCols = count_columns(lv.data(), nl.data(), k);
+    s->mkOut = DevMaskOut{}; for (uint32_t i = 0; i < k; i++) s->mkOut.mask[i] = masks[i];
+    s->mkCountsOut = counts; s->mkStaged = true;
+    return INFX_OK;
+}
+int32_t infx_stream_set_doc_masks(infx_stream* s, uint32_t nq, const uint8_t* const* masks) {
+    if (!s || (nq && !masks)) return fail(INFX_EINVAL, "null argument%s");
+    s->docMasks.clear();
+    for (uint32_t i = 0; i < nq; i++) if (masks[i] && mask_slot_of(s, masks[i]) < 0) return fail(INFX_EINVAL, "a document mask is not a mask slot of this stream%s");
+    s->docMasks.assign(masks, masks + nq);
+    return INFX_OK;
+}
+int32_t infx_last_filter_mask_stats(infx_stream* s, uint32_t* built, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (built) *built = s->lastMaskBuilt;
+    if (launches) *launches = s->lastMaskLaunches;
     return INFX_OK;
 }
 int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t* launches) {

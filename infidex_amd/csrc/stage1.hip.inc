@@ -108,6 +108,9 @@ __global__ __launch_bounds__(WAVE, ACC_WPS) void k_accumulate(DevIndex ix, const
     if (sIdx * stripe >= ix.nRanges) return;
     if (dense && !dense[(size_t)q * nStripes + (size_t)sIdx]) return;      // behind k_accumulate_sparse (stage1_sparse.hip.inc): only the (query, stripe) pairs that kernel left to this one
     const DevQuery Q = queries[q];
+    // The query's Document.Deleted flags (its pre-filter mask, or the index's): selected once per wave, here, so that ONE pointer stays alive across the list
+    // loop — inside the emission loop the select keeps the table pointer and the index's flags pointer alive as well (profiles/prefilter.md).
+    const uint8_t* const del = q_deleted(ix, q);
     const int mode = Q.mode;
     const int nT = (int)Q.numTerms;
     const DevTerm* T = terms + Q.termOff;
@@ -453,7 +456,7 @@ __global__ __launch_bounds__(WAVE, ACC_WPS) void k_accumulate(DevIndex ix, const
                 ar.doc[pos] = ix.docBase + base + l;
                 // Document.Deleted (Bm25Scorer.cs:322-323): the row stays (tier counts and the reference's chunk positions include it) with score 0 —
                 // k_select and the replay's heap never see it.  One byte gather per emitted row, only while the index holds deletions.
-                const float stored = (ix.deleted && ix.deleted[ix.docBase + base + l]) ? 0.f : sc;
+                const float stored = (del && del[ix.docBase + base + l]) ? 0.f : sc;
                 ar.score[pos] = stored; myMax = max(myMax, __float_as_uint(stored));
                 ar.cls[pos] = cls;
                 if (ar.maskWords) {

@@ -48,6 +48,7 @@ __global__ __launch_bounds__(WAVE) void k_accumulate_sparse(DevIndex ix, const D
     const int32_t send = min(rEnd * R, ix.N);
     const uint32_t span = (uint32_t)(send - base);
     const DevQuery Q = queries[q];
+    const uint8_t* const del = q_deleted(ix, q);                       // the query's Document.Deleted flags, selected once per wave (as in k_accumulate)
     const int mode = Q.mode;
     const int nT = (int)Q.numTerms;
     const DevTerm* T = terms + Q.termOff;
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(WAVE) void k_accumulate_sparse(DevIndex ix, const D
             if (emit) {
                 const unsigned long long pos = outBase + written + __popcll(m & lt);
                 ar.doc[pos] = ix.docBase + (int32_t)docS;
-                const float stored = (ix.deleted && ix.deleted[ix.docBase + (int32_t)docS]) ? 0.f : sc;      // Document.Deleted (Bm25Scorer.cs:322-323): the row stays, with score 0
+                const float stored = (del && del[ix.docBase + (int32_t)docS]) ? 0.f : sc;      // Document.Deleted (Bm25Scorer.cs:322-323): the row stays, with score 0
                 ar.score[pos] = stored; myMax = max(myMax, __float_as_uint(stored));
                 ar.cls[pos] = cls;
                 if (ar.maskWords) {

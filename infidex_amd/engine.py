@@ -99,6 +99,9 @@ class Query:       # Api/Query.cs:9-45
     sort_by: Optional[str] = None          # Query.SortBy: a field (column) name, None = relevance order
     sort_ascending: bool = False           # Query.SortAscending
     coverage_setup: Optional[CoverageSetup] = None      # Query.CoverageSetup: None = the engine's (its matcher members are ignored, see CoverageSetup)
+    # Not in the reference: an Infiscript expression that restricts the set that is RANKED — the query returns what it would if every document the expression
+    # does not accept were deleted (index statistics untouched).  `filter` then post-processes the returned rows as usual.
+    pre_filter: Optional[str] = None
 
     @property
     def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
@@ -123,6 +126,7 @@ class Result:      # Api/Result.cs
     skipped_candidates: bool = False       # a candidate document exceeded the Stage-2 envelope (INFX_MAX_DOC_TOKENS) and was left out
     facets: Optional[dict] = None          # field -> [(value, count)] (count desc, value asc), Api/Result.cs Facets
     total_in_filter: int = 0               # Filter.NumberOfDocumentsInFilter
+    total_in_pre_filter: int = 0           # live documents Query.pre_filter accepts (0 without one)
     error: Optional[str] = None            # search_queries: why this query alone was rejected (empty result); None when it ran
 
     # SearchEngine.cs:312-316: index and score of the last returned row, and the row count
@@ -397,23 +401,33 @@ class SearchEngine:
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
 
     def search_filtered(self, texts: Sequence[str], max_results=10, depth=500, enable_coverage=True, filter=None, enable_facets=False, session=None,
-                        enable_boost=False, boosts=None, sort_by=None, sort_ascending=False):
+                        enable_boost=False, boosts=None, sort_by=None, sort_ascending=False, pre_filter=None):
         """Search(Query) with Query.Filter / Query.EnableFacets / Query.Boosts / Query.SortBy for a batch sharing them: post-filter, facet counts,
-        boosts and sort-by run on the device (SearchEngine.ApplyPostProcessing order: filter, boosts, sort-by)."""
+        boosts and sort-by run on the device (SearchEngine.ApplyPostProcessing order: filter, boosts, sort-by).  pre_filter: one Query.pre_filter
+        for the whole batch (a query it cannot apply to comes back empty with Result.error set)."""
         sh = session.h if session is not None else self._default_session()
         nin = C.c_uint32(0)
         self._check(self.L.infx_engine_set_filter(sh, filter.encode() if filter is not None else None, int(enable_facets), C.byref(nin)))
         try:
             _set_boosts(self, sh, boosts, enable_boost)
             _set_sort(self, sh, sort_by, sort_ascending)
-            arena, offs = pack_texts(texts)
-            keys, scores, ties, counts, flags = (session or self).search_packed(arena, offs, max_results, depth, enable_coverage)
             nq = len(texts)
+            pst = _install_prefilters(self, sh, [pre_filter] * nq) if pre_filter is not None else None
+            arena, offs = pack_texts(texts)
+            try:
+                keys, scores, ties, counts, flags = (session or self).search_packed(arena, offs, max_results, depth, enable_coverage)
+            except Exception:
+                self.L.infx_engine_set_query_prefilters(sh, 0, None, None)
+                raise
+            inpre = _in_prefilter(self, sh, nq) if pre_filter is not None else None
             out = []
             for i in range(nq):
                 recs = [ScoreEntry(float(scores[i, k]), int(keys[i, k]), int(ties[i, k])) for k in range(int(counts[i]))]
-                facets = self.facets_of(sh, nq, i) if enable_facets else None
-                out.append(Result(recs, bool(flags[i] & 1), bool(flags[i] & 2), bool(flags[i] & 4), bool(flags[i] & 8), facets, int(nin.value)))
+                rejected = pre_filter is not None and (pst[i] != 0 or bool(flags[i] & 16))
+                facets = self.facets_of(sh, nq, i) if enable_facets and not rejected else None
+                out.append(Result(recs, bool(flags[i] & 1), bool(flags[i] & 2), bool(flags[i] & 4), bool(flags[i] & 8), facets, int(nin.value),
+                                  total_in_pre_filter=int(inpre[i]) if inpre is not None else 0,
+                                  error=_query_error(self, sh, i, int(pst[i])) if rejected else None))
             return out
         finally:
             self.L.infx_engine_set_filter(sh, None, 0, None)
@@ -424,11 +438,13 @@ class SearchEngine:
         """Search(Query) for a batch of Query objects, each with its own MaxNumberOfRecordsToReturn, EnableCoverage, Filter, EnableFacets, Boosts and
         SortBy (infx_engine_set_query_options) and CoverageSetup (infx_engine_set_query_coverage): one device batch per CoverageDepth, results in
         input order.  A query whose options are refused (syntax error, MATCHES, more than 8 filtered boosts, post-processing on more than max_post_rows (default 64) rows,
-        a CoverageSetup out of range or with the lexical pre-screen) comes back empty with Result.error set; the others of the batch are unaffected."""
+        a CoverageSetup out of range or with the lexical pre-screen, a pre_filter that cannot apply) comes back empty with Result.error set; the others of
+        the batch are unaffected.  Query.pre_filter (infx_engine_set_query_prefilters) is installed beside the options; a depth group is split further so
+        that no device batch carries more than 16 distinct pre-filters."""
         sh = session.h if session is not None else self._default_session()
         runner = (session or self).search_packed
         out = [None] * len(queries)
-        for depth, idx in _by_depth(queries):
+        for depth, idx in _split_prefilters(queries, _by_depth(queries)):
             qs = [queries[i] for i in idx]
             status = _install_query_options(self, sh, qs)
             stride = max(1, max(int(q.max_number_of_records_to_return) for q in qs))
@@ -445,7 +461,7 @@ class SearchEngine:
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
-        if q.coverage_setup is not None:
+        if q.coverage_setup is not None or q.pre_filter is not None:
             return self.search_queries([q])[0]
         if q.filter is not None or q.enable_facets or (q.enable_boost and q.boosts) or q.sort_by is not None:
             return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
@@ -455,6 +471,15 @@ class SearchEngine:
     def last_count_stats(self, session=None):
         """(expressions the session's last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
         return _count_stats(self, session.h if session is not None else self._default_session())
+
+    def last_prefilter_stats(self, session=None):
+        """(masks built, masks taken from the session's cache, k_filter_mask_multi launches) of the session's last search (or prefilter_mask call)."""
+        return _prefilter_stats(self, session.h if session is not None else self._default_session())
+
+    def prefilter_mask(self, expr: str, session=None) -> np.ndarray:
+        """Parity tooling: the device's mask of a pre-filter expression, one byte per indexed document (1 = Deleted or not accepted) — built, or taken
+        from the session's cache."""
+        return _prefilter_mask(self, session.h if session is not None else self._default_session(), expr)
 
     def last_browse_stats(self, session=None):
         """(groups — distinct filter programs, counted ones included —, k_browse_scan launches) of the session's last batch that had a browse query."""
@@ -654,6 +679,14 @@ class Session:
         """SearchEngine.facets_of_all_documents on this session."""
         return _facets_all(self.engine, self.h)
 
+    def last_prefilter_stats(self):
+        """SearchEngine.last_prefilter_stats of this session."""
+        return _prefilter_stats(self.engine, self.h)
+
+    def prefilter_mask(self, expr: str) -> np.ndarray:
+        """SearchEngine.prefilter_mask on this session (its own mask cache)."""
+        return _prefilter_mask(self.engine, self.h, expr)
+
     def last_count_stats(self):
         """(expressions the last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
         return _count_stats(self.engine, self.h)
@@ -707,6 +740,59 @@ def _by_depth(queries):
     return list(groups.items())
 
 
+MAX_PREFILTERS = 16      # INFX_MAX_PREFILTERS: distinct pre-filters one device batch can carry
+
+
+def _split_prefilters(queries, groups, limit=MAX_PREFILTERS):
+    """Splits each (depth, [indices]) group further, keeping input order, so that no group holds more than `limit` distinct Query.pre_filter expressions."""
+    out = []
+    for depth, idx in groups:
+        cur, seen = [], set()
+        for i in idx:
+            p = queries[i].pre_filter
+            if p is not None and p not in seen and len(seen) >= limit:
+                out.append((depth, cur)); cur, seen = [], set()
+            if p is not None:
+                seen.add(p)
+            cur.append(i)
+        if cur:
+            out.append((depth, cur))
+    return out
+
+
+def _install_prefilters(engine, sh, exprs):
+    """infx_engine_set_query_prefilters for the coming batch on session handle sh (None entries: no pre-filter); returns each query's status."""
+    n = len(exprs)
+    arr = (C.c_char_p * max(n, 1))(*[x.encode() if x is not None else None for x in exprs])
+    st = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_set_query_prefilters(sh, n, arr, _p(st, C.c_int32)))
+    return st[:n]
+
+
+def _in_prefilter(engine, sh, n):
+    out = np.zeros(max(n, 1), np.uint32)
+    engine._check(engine.L.infx_engine_last_in_prefilter(sh, n, _p(out, C.c_uint32)))
+    return out[:n]
+
+
+def _query_error(engine, sh, j, status):
+    buf = C.create_string_buffer(512); engine.L.infx_engine_query_error(sh, j, buf, 512)
+    return buf.value.decode(errors="replace") or ("status %d" % status)
+
+
+def _prefilter_stats(engine, sh):
+    b = C.c_uint32(0); r = C.c_uint32(0); n = C.c_uint32(0)
+    engine._check(engine.L.infx_engine_last_prefilter_stats(sh, C.byref(b), C.byref(r), C.byref(n)))
+    return int(b.value), int(r.value), int(n.value)
+
+
+def _prefilter_mask(engine, sh, expr):
+    n = int(engine.index_stats()["docs"])
+    out = np.zeros(max(n, 1), np.uint8)
+    engine._check(engine.L.infx_engine_prefilter_mask(sh, expr.encode(), _p(out, C.c_uint8), C.c_uint64(len(out))))
+    return out[:n]
+
+
 def _install_query_options(engine, sh, qs):
     """infx_engine_set_query_options for the queries qs on session handle sh; returns each query's status (0: accepted)."""
     n = len(qs)
@@ -737,6 +823,15 @@ def _install_query_options(engine, sh, qs):
         status = np.where(status != 0, status, cst)
     else:
         engine._check(engine.L.infx_engine_set_query_coverage(sh, 0, None, None))
+    if any(q.pre_filter is not None for q in qs):          # Query.pre_filter: likewise
+        try:
+            pst = _install_prefilters(engine, sh, [q.pre_filter for q in qs])
+        except Exception:
+            _clear_query_options(engine, sh)
+            raise
+        status[:n] = np.where(status[:n] != 0, status[:n], pst)
+    else:
+        engine._check(engine.L.infx_engine_set_query_prefilters(sh, 0, None, None))
     return status[:n]
 
 
@@ -744,6 +839,7 @@ def _clear_query_options(engine, sh):
     """Drops the per-query options and coverage setups installed on session handle sh (a batch that failed before it consumed them)."""
     engine.L.infx_engine_set_query_options(sh, 0, None, None)
     engine.L.infx_engine_set_query_coverage(sh, 0, None, None)
+    engine.L.infx_engine_set_query_prefilters(sh, 0, None, None)
 
 
 def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
@@ -751,15 +847,17 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
     n = len(qs)
     inf = np.zeros(max(n, 1), np.uint32)
     engine._check(engine.L.infx_engine_last_in_filter(sh, n, _p(inf, C.c_uint32)))
+    inpre = _in_prefilter(engine, sh, n) if any(q.pre_filter is not None for q in qs) else None
     out = []
     for j, q in enumerate(qs):
         err = None
-        if status[j] != 0:
-            buf = C.create_string_buffer(512); engine.L.infx_engine_query_error(sh, j, buf, 512)
-            err = buf.value.decode(errors="replace") or ("status %d" % int(status[j]))
+        # (a pre-filter on a browse query is refused when the batch runs: result flag bit 4 without an install status)
+        if status[j] != 0 or (q.pre_filter is not None and flags[j] & 16):
+            err = _query_error(engine, sh, j, int(status[j]) or 5)
         recs = [ScoreEntry(float(scores[j, k]), int(keys[j, k]), int(ties[j, k])) for k in range(int(counts[j]))]
         facets = engine.facets_of(sh, n, j) if q.enable_facets and err is None else None
-        out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]), err))
+        out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]),
+                          total_in_pre_filter=int(inpre[j]) if inpre is not None else 0, error=err))
     return out
 
 

@@ -675,7 +675,8 @@ class ShardedSearcher:
 
     def search_queries(self, queries) -> List[Result]:
         """SearchEngine.search_queries across the shards: one batch per CoverageDepth, each query with its own options.  Collective: same call with the
-        same queries on every rank.  NumberOfDocumentsInFilter is the GLOBAL count on every rank (each counts the whole corpus): nothing is summed."""
+        same queries on every rank.  NumberOfDocumentsInFilter is the GLOBAL count on every rank (each counts the whole corpus): nothing is summed.
+        A query with Query.pre_filter comes back empty with Result.error set: the masks cover one device's documents, document shards are not supported."""
         out = [None] * len(queries)
         for depth, idx in _by_depth(queries):
             qs = [queries[i] for i in idx]
