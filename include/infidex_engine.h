@@ -366,6 +366,28 @@ int32_t infx_engine_last_prefilter_stats(infx_session* s, uint32_t* built, uint3
 /* Parity tooling: the mask of one expression as the device holds it — built, or taken from the session's cache — one byte per indexed document in
  * out_bytes (cap >= the number of documents): 1 = Deleted or not accepted. */
 int32_t infx_engine_prefilter_mask(infx_session* s, const char* expr, uint8_t* out_bytes, uint64_t cap);
+/* ---- facets of the documents a filter accepts (not in the reference: the facet side of Query.pre_filter) --------------------------------------------------
+ * The facets of an Infiscript expression P: the value counts of every facetable column (the first INFX_MAX_FACET_COLS) over the documents that are not Deleted
+ * and whose OWN fields P accepts — per document, as NumberOfDocumentsInFilter counts and as the pre-filter masks are built, not through the key's first live
+ * document.  Downstream of the counts they are infx_engine_facets_all's: null and empty values dropped, count descending then value ascending, at most 100
+ * values per field.  The total of P is the number of those documents (= infx_engine_last_in_prefilter of a query with pre-filter P).
+ * infx_engine_facets_filtered answers k expressions at once.  Answers are cached per expression in the engine (shared by its sessions, at most 256, least
+ * recently used first out) for one mask epoch: deletions, restores, infx_engine_add_column and indexing invalidate them exactly as they invalidate the
+ * pre-filter masks.  Only the distinct expressions the cache is missing go to the device, INFX_MAX_PREFILTERS (16) per infx_facets_filtered call: one pass
+ * over the columns evaluates them all and counts every column.  An expression is refused ON ITS OWN — out_status[i], message from
+ * infx_engine_facets_filtered_error, the other expressions unaffected — for a syntax error (INFX_EINVAL) or MATCHES (INFX_EUNSUPPORTED); the call itself then
+ * still returns INFX_OK.  INFX_EHIP on an engine without a GPU.  Works on a sharded engine without a collective (every rank holds the whole columns and the
+ * global Deleted flags, and returns the same answer).
+ * Readers, for expression `which` of the session's last call: infx_engine_facets_filtered_column gives the k-th facet column (k <
+ * infx_engine_facets_filtered_column_count) as infx_engine_facets_all_column does, -1 for a refused expression; infx_engine_facets_filtered_total the total
+ * (returning the expression's status).  infx_engine_last_facets_filtered_stats: expressions counted on the device, expressions taken from the cache, and
+ * k_facets_filtered launches of the session's last call. */
+int32_t infx_engine_facets_filtered(infx_session* s, uint32_t k, const char* const* exprs, int32_t* out_status /* k, may be NULL */);
+int32_t infx_engine_facets_filtered_column_count(infx_session* s);
+int32_t infx_engine_facets_filtered_column(infx_session* s, uint32_t which, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap);
+int32_t infx_engine_facets_filtered_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_facets_filtered_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_facets_filtered_stats(infx_session* s, uint32_t* counted, uint32_t* cached, uint32_t* launches);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

@@ -392,6 +392,17 @@ int32_t infx_last_browse_stats(infx_stream* s, uint32_t* groups, uint32_t* launc
  * turn, the number of documents of the WHOLE corpus that are not Deleted per distinct value — counts_out holds sum(num_values) words, column k's
  * behind those of the columns before it.  One pass over the documents for all columns, synchronous.  The host drops null / empty values, orders and cuts. */
 int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uint32_t* counts_out);
+/* Facets of the documents a filter accepts (not in the reference: the facet side of a pre-filter).  For each of the k (<= INFX_MAX_PREFILTERS) programs
+ * progs[i] and each of the ncol (<= INFX_MAX_FACET_COLS) uploaded columns cols[c]: the number of documents of the WHOLE corpus that are not Deleted (the index's
+ * real flags, never a per-query mask) and whose OWN column values the program accepts, per distinct value.  counts_out holds k x sum(num_values) words,
+ * program-major: program i's block is laid out as infx_facets_all's; totals_out[i] = the documents program i accepts (= the count infx_filter_masks reports for
+ * it).  ONE pass over the columns evaluates all k programs and counts every column (k_facets_filtered); it is split into several launches only when
+ * the per-workgroup counters of the columns with few values would not fit in LDS for all k programs at once.  Works on a sharded index as infx_facets_all does
+ * (every rank holds the whole columns and the global Deleted flags).  Synchronous.  ncol = 0 gives the totals alone.
+ * infx_last_facets_filtered_stats: programs counted and k_facets_filtered launches of the stream's last call. */
+int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint32_t ncol, const uint32_t* cols,
+                             uint32_t* counts_out /* k x sum(num_values), program-major */, uint32_t* totals_out /* k */);
+int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -85,6 +85,10 @@ struct QueryPre {
 // One mask of the session's cache (mask slot i of its stream): the expression it was built from, the engine's mask epoch at that time, the live documents
 // it accepts, when it was last used (least recently used first out)
 struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t count = 0; bool valid = false; };
+// The facets of one Infiscript expression (infx_engine_facets_filtered), as the engine caches them: per facet column the ordered (code, count) list, cut to 100,
+// and the number of live documents the expression accepts; valid for the mask epoch it was counted in
+struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists; std::list<std::string>::iterator lru; };
+struct FfAnswer { int32_t status = INFX_OK; std::string err; std::shared_ptr<const FfEntry> r; };
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
@@ -95,6 +99,9 @@ struct infx_session {
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
     bool swFilter = false, swBoost = false, swSort = false;      // session-wide options installed (infx_engine_set_filter / _set_boosts / _set_sort)
     std::vector<uint32_t> facAllCols; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> facAll;      // infx_engine_facets_all: columns and their ordered (code, count) lists
+    // infx_engine_facets_filtered: the facet columns of the session's last call, one answer per expression of it (its entry of the engine's cache, or why it
+    // was refused), and what the call cost: expressions counted on the device, expressions taken from the cache, k_facets_filtered launches
+    std::vector<uint32_t> ffCols; std::vector<FfAnswer> ff; uint32_t ffCounted = 0, ffCached = 0, ffLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -225,6 +232,9 @@ struct infx_engine {
     // Pre-filter masks (one byte per document, cached per session) are valid for one epoch: whatever changes a document's Deleted flag or what a compiled
     // filter accepts — a deletion, a restore, a new column, a (re-)index — starts the next one
     std::atomic<uint64_t> maskEpoch{1};
+    // Facets of the documents a filter accepts, per expression (infx_engine_facets_filtered): shared by the sessions, least recently used first out, an entry
+    // of an earlier mask epoch is counted again on its next use
+    std::mutex ffMu; std::unordered_map<std::string, std::shared_ptr<FfEntry>> ffCache; std::list<std::string> ffLru; size_t ffCacheLimit = 256;
     HostIndex ix;
     PlanGate gate;
     CollSeq collSeq;
@@ -2451,6 +2461,15 @@ int32_t infx_engine_last_facets(infx_session* S, uint32_t nq, uint32_t qi, uint3
     return m;
 }
 int32_t infx_engine_facet_column_count(infx_session* S) { return S ? (int32_t)S->facetCols.size() : -1; }
+// One column's value counts (one word per distinct value) as a facet list: null and empty values left out, count descending then value ascending in the row
+// facets' rank, cut to 100
+static std::vector<std::pair<uint32_t, uint32_t>> facet_list(const filt::Column& C, const uint32_t* counts) {
+    std::vector<std::pair<uint32_t, uint32_t>> v;
+    for (uint32_t code = 0; code < C.dict.size(); code++) if (counts[code] && !C.text[code].empty()) v.push_back({code, counts[code]});     // empty strings are not facet values (:170-174)
+    std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
+    if (v.size() > 100) v.resize(100);
+    return v;
+}
 // FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): value counts of every facetable column over all documents that are not
 // Deleted, one device pass for all columns (infx_facets_all); per column the values ordered count descending, value ascending, cut to 100, null and
 // empty values left out — as infx_engine_last_facets orders the row facets.  *ncols = facetable columns; their lists: infx_engine_facets_all_column.
@@ -2470,11 +2489,7 @@ int32_t infx_engine_facets_all(infx_session* S, int32_t* ncols) {
     size_t o = 0;
     for (uint32_t col : S->facAllCols) {
         const filt::Column& C = e->columns[col];
-        std::vector<std::pair<uint32_t, uint32_t>> v;
-        for (uint32_t code = 0; code < C.dict.size(); code++) if (counts[o + code] && !C.text[code].empty()) v.push_back({code, counts[o + code]});     // empty strings are not facet values (:170-174)
-        std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
-        if (v.size() > 100) v.resize(100);
-        S->facAll.push_back(std::move(v));
+        S->facAll.push_back(facet_list(C, counts.data() + o));
         o += C.dict.size();
     }
     return INFX_OK;
@@ -2989,6 +3004,105 @@ int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* o
     if (!rc && N) rc = infx_stream_copy(S->stream, out_bytes, p, N);
     if (!rc) rc = infx_stream_wait(S->stream);
     if (rc) { g_eerr = infx_last_error(); return rc; }
+    return INFX_OK;
+}
+
+// ---- facets of the documents a filter accepts (not in the reference: the facet side of Query.pre_filter) -----------------------------------------------
+// For each expression: the value counts of every facetable column (the first INFX_MAX_FACET_COLS) over the documents that are not Deleted and whose OWN fields the
+// expression accepts, ordered and cut as infx_engine_facets_all does, and the number of those documents.  Answers are cached per expression in the engine for
+// one mask epoch; the expressions a call is missing go to the device INFX_MAX_PREFILTERS at a time, each time one pass over the columns (infx_facets_filtered).
+// An expression is refused on its own (its status in out_status[i], its message from infx_engine_facets_filtered_error): INFX_EINVAL for a syntax error,
+// INFX_EUNSUPPORTED for MATCHES.
+int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* const* exprs, int32_t* out_status) {
+    if (!S || (k && !exprs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->ff.clear(); S->ffCols.clear(); S->ffCounted = S->ffCached = S->ffLaunches = 0;
+    if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the filtered facet counts run on the device");
+    if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
+    S->ff.assign(k, FfAnswer());
+    size_t total = 0;
+    for (size_t c = 0; c < e->columns.size() && S->ffCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) { S->ffCols.push_back((uint32_t)c); total += e->columns[c].dict.size(); }
+    const uint64_t ep = e->maskEpoch.load();
+    // the call's distinct expressions: from the cache, refused, or missing (compiled here; the programs are copied out of the filter cache, which other
+    // sessions may evict from while the device counts)
+    struct Missing { std::string expr; std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables; };
+    std::unordered_map<std::string, FfAnswer> answer; std::vector<Missing> miss;
+    for (uint32_t i = 0; i < k; i++) {
+        if (!exprs[i]) { S->ff[i].status = INFX_EINVAL; S->ff[i].err = "null expression"; continue; }
+        if (answer.count(exprs[i])) continue;
+        FfAnswer A;
+        {
+            std::lock_guard<std::mutex> lk(e->ffMu);
+            auto it = e->ffCache.find(exprs[i]);
+            if (it != e->ffCache.end() && it->second->epoch == ep) { e->ffLru.splice(e->ffLru.begin(), e->ffLru, it->second->lru); A.r = it->second; S->ffCached++; }
+        }
+        if (!A.r) {
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            CompiledFilter* cf = nullptr;
+            const int32_t rc = compile_filter(e, exprs[i], &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
+            if (rc) { A.status = rc; A.err = g_eerr; }
+            else miss.push_back(Missing{exprs[i], cf->ops, cf->leaves, cf->tables});
+        }
+        answer.emplace(exprs[i], std::move(A));
+    }
+    std::vector<uint32_t> counts, totals(INFX_MAX_PREFILTERS);
+    for (size_t m0 = 0; m0 < miss.size(); m0 += INFX_MAX_PREFILTERS) {
+        const uint32_t kk = (uint32_t)std::min<size_t>(INFX_MAX_PREFILTERS, miss.size() - m0);
+        std::vector<infx_filter_prog> progs(kk);
+        for (uint32_t j = 0; j < kk; j++) {
+            const Missing& M = miss[m0 + j]; infx_filter_prog& P = progs[j]; P = infx_filter_prog{};
+            P.ops = M.ops.data(); P.leaves = M.leaves.data(); P.tables = M.tables.data();
+            P.nops = (uint32_t)M.ops.size(); P.nleaves = (uint32_t)M.leaves.size(); P.ntable_words = (uint32_t)M.tables.size();
+        }
+        counts.resize(std::max<size_t>((size_t)kk * total, 1));
+        int32_t rc = infx_facets_filtered(S->stream, kk, progs.data(), (uint32_t)S->ffCols.size(), S->ffCols.data(), counts.data(), totals.data());
+        if (rc) { g_eerr = infx_last_error(); S->ff.clear(); S->ffCols.clear(); return rc; }
+        uint32_t np = 0, nl = 0; infx_last_facets_filtered_stats(S->stream, &np, &nl);
+        S->ffCounted += kk; S->ffLaunches += nl;
+        for (uint32_t j = 0; j < kk; j++) {
+            auto E = std::make_shared<FfEntry>(); E->epoch = ep; E->total = totals[j];
+            size_t o = (size_t)j * total;
+            for (uint32_t col : S->ffCols) { const filt::Column& C = e->columns[col]; E->lists.push_back(facet_list(C, counts.data() + o)); o += C.dict.size(); }
+            answer[miss[m0 + j].expr].r = E;
+            std::lock_guard<std::mutex> lk(e->ffMu);
+            auto it = e->ffCache.find(miss[m0 + j].expr);
+            if (it != e->ffCache.end()) { e->ffLru.erase(it->second->lru); e->ffCache.erase(it); }
+            e->ffLru.push_front(miss[m0 + j].expr); E->lru = e->ffLru.begin();
+            e->ffCache.emplace(miss[m0 + j].expr, E);
+            while (e->ffCache.size() > e->ffCacheLimit) { e->ffCache.erase(e->ffLru.back()); e->ffLru.pop_back(); }
+        }
+    }
+    for (uint32_t i = 0; i < k; i++) if (exprs[i]) S->ff[i] = answer[exprs[i]];
+    if (out_status) for (uint32_t i = 0; i < k; i++) out_status[i] = S->ff[i].status;
+    return INFX_OK;
+}
+int32_t infx_engine_facets_filtered_column_count(infx_session* S) { return S ? (int32_t)S->ffCols.size() : -1; }
+// Expression `which` of the session's last infx_engine_facets_filtered, its k-th facet column: engine column index in *col, up to cap (code, count) pairs; returns
+// their number, -1 on error (also for an expression that was refused).
+int32_t infx_engine_facets_filtered_column(infx_session* S, uint32_t which, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap) {
+    if (!S || which >= S->ff.size() || !S->ff[which].r || k >= S->ff[which].r->lists.size() || k >= S->ffCols.size() || (cap > 0 && (!codes || !counts))) return -1;
+    if (col) *col = (int32_t)S->ffCols[k];
+    int32_t m = 0; for (auto& x : S->ff[which].r->lists[k]) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
+    return m;
+}
+// the live documents expression `which` accepts (0 for a refused one, whose status is returned)
+int32_t infx_engine_facets_filtered_total(infx_session* S, uint32_t which, uint32_t* total) {
+    if (!S || !total || which >= S->ff.size()) return efail(INFX_EINVAL, "no such expression in the session's last filtered-facet call");
+    *total = S->ff[which].r ? S->ff[which].r->total : 0;
+    return S->ff[which].status;
+}
+// the message of expression `which`'s refusal ("" if it was counted); returns its length, -1 out of range
+int32_t infx_engine_facets_filtered_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
+    if (!S || which >= S->ff.size()) return -1;
+    const std::string& m = S->ff[which].err;
+    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", m.c_str());
+    return (int32_t)m.size();
+}
+int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counted, uint32_t* cached, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (counted) *counted = S->ffCounted;
+    if (cached) *cached = S->ffCached;
+    if (launches) *launches = S->ffLaunches;
     return INFX_OK;
 }
 

@@ -260,6 +260,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "lookup.hip.inc"
 #include "filter.hip.inc"
 #include "browse.hip.inc"
+#include "facets_filtered.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -300,6 +301,8 @@ struct infx_stream {
     void *dBrwBlob = nullptr, *dBrwWork = nullptr; size_t capBrwBlob = 0, capBrwWork = 0;
     uint32_t lastBrowseGroups = 0, lastBrowseLaunches = 0;      // groups and k_browse_scan launches of the last finalize
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
+    void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
+    uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -2894,6 +2897,118 @@ int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uin
     }
     if (total) DOWN(counts_out, s->dFacAll, total * 4);
     SYNC();
+    return INFX_OK;
+}
+// ---- facets of the documents a filter accepts (k_facets_filtered) ----
+// Where the counters of one launch live.  The LDS budget is k_facets_all's: FFL_LDS_WORDS words per workgroup, and a column of more than FALL_LDS_VALUES
+// values always counts in global memory.  Contention decides the rest: the fewer values a column has, the more adds meet on one counter, so
+//   1. a column of at most FFL_HOT_VALUES values is ALWAYS counted in LDS: the programs of a call are spread evenly over as many launches as it takes
+//      for (programs of a launch) x (words of those columns) to fit (8 such columns hold at most 2048 words: a launch always takes 8 programs or more);
+//   2. the other columns of at most FALL_LDS_VALUES values get LDS counters in ascending order of their size while (programs of the launch) x words
+//      still fits, and global counters after that.
+#define FFL_LDS_WORDS 16384u
+#define FFL_HOT_VALUES 256u
+#define FFL_CU_LDS ((size_t)160 * 1024)      // LDS of a CU (gfx950)
+static uint32_t ffl_programs_per_launch(uint32_t K, uint32_t ncol, const uint32_t* nv) {
+    uint32_t hot = 0; for (uint32_t c = 0; c < ncol; c++) if (nv[c] <= FFL_HOT_VALUES) hot += nv[c];
+    const uint32_t fit = hot ? std::max(1u, FFL_LDS_WORDS / hot) : K;
+    if (!K || fit >= K) return K;
+    const uint32_t launches = (K + fit - 1) / fit;
+    return (K + launches - 1) / launches;
+}
+static uint32_t ffl_place(uint32_t k, uint32_t ncol, const uint32_t* nv, uint32_t* ldsOff) {      // returns the LDS words of the facet counters
+    uint32_t order[INFX_MAX_FACET_COLS]; for (uint32_t c = 0; c < ncol; c++) order[c] = c;
+    std::stable_sort(order, order + ncol, [&](uint32_t a, uint32_t b) { return nv[a] < nv[b]; });
+    uint32_t words = 0;
+    for (uint32_t i = 0; i < ncol; i++) {
+        const uint32_t c = order[i]; const uint64_t w = (uint64_t)k * nv[c];
+        if (nv[c] && nv[c] <= FALL_LDS_VALUES && words + w <= FFL_LDS_WORDS) { ldsOff[c] = words; words += (uint32_t)w; } else ldsOff[c] = 0xFFFFFFFFu;
+    }
+    return words;
+}
+int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint32_t ncol, const uint32_t* cols, uint32_t* counts_out, uint32_t* totals_out) {
+    if (!s || ncol > INFX_MAX_FACET_COLS || (ncol && !cols) || (k && (!progs || !totals_out))) return fail(INFX_EINVAL, "bad filtered-facet arguments%s");
+    s->lastFfProgs = 0; s->lastFfLaunches = 0;
+    if (!k) return INFX_OK;
+    if (k > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) programs in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = ix->d.totalDocs;
+    uint64_t total = 0; uint32_t nv[INFX_MAX_FACET_COLS] = {};
+    for (uint32_t c = 0; c < ncol; c++) {
+        if (cols[c] >= FILT_MAXCOL || !ix->colCodes[cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
+        nv[c] = ix->colValues[cols[c]]; total += nv[c];
+    }
+    for (int c = 0; c < FILT_MAXCOL; c++)       // the programs may read any uploaded column, by GLOBAL internal id
+        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    if (total && !counts_out) return fail(INFX_EINVAL, "bad filtered-facet arguments%s");
+    if (total > 0xFFFFFFFFull / INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "the facet columns hold too many distinct values%s");
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    std::vector<infx_stream::QpProg> packed; std::vector<uint8_t> code;
+    { int32_t rc_ = pack_progs(ix, k, progs, packed, code); if (rc_) return rc_; }      // (validates every program against the uploaded columns)
+    const size_t oCode = ((size_t)k * sizeof(DevFilter) + 15) & ~(size_t)15, blob = oCode + code.size();
+    const size_t words = (size_t)k * (size_t)total + k;                                  // counters [k][total], then totals [k]
+    GROW(s->dFfBlob, s->capFfBlob, blob);
+    GROW(s->dFfCnt, s->capFfCnt, words * 4);
+    char* D = (char*)s->dFfBlob;
+    std::vector<uint8_t> H(blob, 0);
+    for (uint32_t i = 0; i < k; i++) {
+        const auto& P = packed[i];
+        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
+        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
+    }
+    if (!code.empty()) std::memcpy(H.data() + oCode, code.data(), code.size());
+    UP(D, H.data(), blob);
+    HIPCHK(hipMemsetAsync(s->dFfCnt, 0, words * 4, s->st));
+    uint32_t* dOut = (uint32_t*)s->dFfCnt; uint32_t* dTot = dOut + (size_t)k * (size_t)total;
+    s->lastFfProgs = k;
+    if (n > 0) {
+        DevColumns dc; for (int c = 0; c < FILT_MAXCOL; c++) dc.codes[c] = ix->colCodes[c];
+        const uint32_t per = ffl_programs_per_launch(k, ncol, nv);
+        for (uint32_t k0 = 0; k0 < k; k0 += per) {
+            const uint32_t kk = std::min(per, k - k0);
+            std::vector<const infx_filter_leaf*> lv(kk); std::vector<uint32_t> nl(kk);
+            for (uint32_t i = 0; i < kk; i++) { lv[i] = progs[k0 + i].leaves; nl[i] = progs[k0 + i].nleaves; }
+            const DevCountCols cc = count_columns(lv.data(), nl.data(), kk);
+            DevFacetFilt F{}; uint32_t o = 0;
+            const uint32_t ldsWords = ffl_place(kk, ncol, nv, F.ldsOff);
+            for (uint32_t c = 0; c < ncol; c++) {
+                F.codes[c] = ix->colCodes[cols[c]]; F.nvals[c] = nv[c]; F.outOff[c] = o; o += nv[c];
+                F.slot[c] = 0xFFu; for (uint32_t u = 0; u < cc.nUsed; u++) if (cc.col[u] == cols[c]) F.slot[c] = (uint8_t)u;
+            }
+            // 256 threads while the codes of a workgroup stay within 16 KiB, else one wave per workgroup.  Counters beyond 16 KiB change the shape (measured,
+            // profiles/filtered_facets.md: at 80 KiB per workgroup two 256-thread workgroups fit a CU, 2 waves per SIMD, and each of 2048 workgroups merges its
+            // counters into global memory): then one workgroup of FFL_BIG_THREADS threads per CU-sized share of LDS and only as many workgroups as are resident
+            const bool big = (size_t)ldsWords * 4 > 16 * 1024 && ((size_t)cc.nUsed * 4 * FFL_BIG_THREADS + kk + ldsWords) * 4 <= FFL_CU_LDS;
+            const int threads = big ? FFL_BIG_THREADS : (size_t)cc.nUsed * 4 * FMM_THREADS * 4 <= 16 * 1024 ? FMM_THREADS : WAVE;
+            const size_t lds = ((size_t)cc.nUsed * 4 * threads + kk + ldsWords) * 4;
+            const int64_t groups = ((int64_t)n + 3) / 4;
+            int64_t maxGrid = FCM_MAXGRID;
+            if (big) { int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device)); maxGrid = std::max<int64_t>(1, (int64_t)cus * (int64_t)(FFL_CU_LDS / lds)); }
+            const int grid = (int)std::min<int64_t>(maxGrid, (groups + threads - 1) / threads);
+            {   // sessions launch from several threads: the attribute is raised under a lock, and only past its high-water mark — one mark per device (a function's
+                // attributes belong to the device that is current when they are set)
+                static std::mutex mu; static std::map<int, size_t> attr;
+                std::lock_guard<std::mutex> lk(mu);
+                size_t& hw = attr[ix->cfg.device];
+                if (lds > 64 * 1024 && lds > hw) { HIPCHK(hipFuncSetAttribute((const void*)k_facets_filtered, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hw = lds; }
+            }
+            k_facets_filtered<<<grid, threads, lds, s->st>>>((const DevFilter*)D + k0, kk, cc, dc, n, ix->d.deleted, F, (int)ncol, ldsWords, (uint32_t)total,
+                                                            dOut + (size_t)k0 * (size_t)total, dTot + k0);
+            HIPCHK(hipGetLastError());
+            s->lastFfLaunches++;
+        }
+    }
+    if (total) DOWN(counts_out, dOut, (size_t)k * (size_t)total * 4);
+    DOWN(totals_out, dTot, (size_t)k * 4);
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (programs) *programs = s->lastFfProgs;
+    if (launches) *launches = s->lastFfLaunches;
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

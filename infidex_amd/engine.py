@@ -102,6 +102,9 @@ class Query:       # Api/Query.cs:9-45
     # Not in the reference: an Infiscript expression that restricts the set that is RANKED — the query returns what it would if every document the expression
     # does not accept were deleted (index statistics untouched).  `filter` then post-processes the returned rows as usual.
     pre_filter: Optional[str] = None
+    # ... and the facets of that set: Result.pre_filter_facets = the facets of every live document pre_filter accepts (SearchEngine.facets_of_documents),
+    # what a drill-down sidebar shows beside the ranked rows.  Ignored without a pre_filter.
+    pre_filter_facets: bool = False
 
     @property
     def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
@@ -129,6 +132,10 @@ class Result:      # Api/Result.cs
     total_in_pre_filter: int = 0           # live documents Query.pre_filter accepts (0 without one)
     error: Optional[str] = None            # search_queries: why this query alone was rejected (empty result); None when it ran
 
+    # Query.pre_filter_facets: the facets of the documents Query.pre_filter accepts (None: not asked for, or refused).  Set by search_queries; a plain
+    # attribute, not a dataclass field: the constructor's positional fields end with total_in_filter, total_in_pre_filter and error, which callers rely on.
+    pre_filter_facets = None
+
     # SearchEngine.cs:312-316: index and score of the last returned row, and the row count
     @property
     def truncation_index(self) -> int:
@@ -141,6 +148,13 @@ class Result:      # Api/Result.cs
     @property
     def total_candidates(self) -> int:
         return len(self.records)
+
+
+@dataclass
+class FilteredFacets:      # SearchEngine.facets_of_documents: one per expression
+    facets: dict = _dc_field(default_factory=dict)      # field -> [(value, count)] over the live documents the expression accepts (count desc, value asc, at most 100)
+    total: int = 0                                      # how many live documents it accepts
+    error: Optional[str] = None                         # why this expression alone was refused (syntax error, MATCHES); None when it was counted
 
 
 class _Cfg(C.Structure):
@@ -397,6 +411,18 @@ class SearchEngine:
         null / empty values left out, fields without a value absent."""
         return _facets_all(self, session.h if session is not None else self._default_session())
 
+    def facets_of_documents(self, filters, session=None):
+        """The facets of the documents an Infiscript expression accepts: {field: [(value, count)]} over every document that is not Deleted and whose own
+        fields the expression accepts (per document, as total_in_pre_filter counts), ordered and cut as facets_of_all_documents, plus their number.
+        filters: one expression -> one FilteredFacets; a sequence -> a list, one per expression.  All expressions the engine has no cached answer for
+        are evaluated and counted in one pass over the columns (16 per pass); an expression with a syntax error or MATCHES gets `error` set, alone."""
+        return _facets_filtered(self, session.h if session is not None else self._default_session(), filters)
+
+    def last_filtered_facet_stats(self, session=None):
+        """(expressions counted on the device, expressions taken from the engine's cache, k_facets_filtered launches) of the session's last
+        facets_of_documents call (or batch with Query.pre_filter_facets)."""
+        return _filtered_facet_stats(self, session.h if session is not None else self._default_session())
+
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
 
@@ -454,7 +480,9 @@ class SearchEngine:
             except Exception:
                 _clear_query_options(self, sh)
                 raise
-            for i, r in zip(idx, _query_results(self, sh, qs, status, keys, scores, ties, counts, flags)):
+            res = _query_results(self, sh, qs, status, keys, scores, ties, counts, flags)
+            _attach_pre_filter_facets(self, sh, qs, res)
+            for i, r in zip(idx, res):
                 out[i] = r
         return out
 
@@ -679,6 +707,14 @@ class Session:
         """SearchEngine.facets_of_all_documents on this session."""
         return _facets_all(self.engine, self.h)
 
+    def facets_of_documents(self, filters):
+        """SearchEngine.facets_of_documents on this session (the cached answers are the engine's)."""
+        return _facets_filtered(self.engine, self.h, filters)
+
+    def last_filtered_facet_stats(self):
+        """SearchEngine.last_filtered_facet_stats of this session."""
+        return _filtered_facet_stats(self.engine, self.h)
+
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
         return _prefilter_stats(self.engine, self.h)
@@ -878,6 +914,67 @@ def _facets_all(engine, sh):
                 vals.append((vb.value.decode(), int(cnts[j])))
             facets[nb.value.decode()] = vals
     return facets
+
+
+def _column_facets(engine, col, m, codes, cnts):
+    """(field name, [(value, count)]) of m (code, count) pairs of engine column col."""
+    nb = C.create_string_buffer(256); engine.L.infx_engine_column_info(engine.h, col, nb, 256, None, None)
+    vals = []
+    for j in range(m):
+        vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col, int(codes[j]), vb, 1024)
+        vals.append((vb.value.decode(), int(cnts[j])))
+    return nb.value.decode(), vals
+
+
+def _facets_filtered(engine, sh, filters):
+    """infx_engine_facets_filtered on session handle sh: a FilteredFacets for a str, a list of them for a sequence."""
+    single = isinstance(filters, str)
+    exprs = [filters] if single else list(filters)
+    n = len(exprs)
+    arr = (C.c_char_p * max(n, 1))(*[x.encode() for x in exprs])
+    st = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_facets_filtered(sh, n, arr, _p(st, C.c_int32)))
+    ncols = int(engine.L.infx_engine_facets_filtered_column_count(sh))
+    out = []
+    for i in range(n):
+        if st[i] != 0:
+            buf = C.create_string_buffer(512); engine.L.infx_engine_facets_filtered_error(sh, i, buf, 512)
+            out.append(FilteredFacets({}, 0, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
+            continue
+        tot = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_facets_filtered_total(sh, i, C.byref(tot)))
+        facets = {}
+        for k in range(ncols):
+            col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
+            m = engine.L.infx_engine_facets_filtered_column(sh, i, k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
+            if m < 0:
+                engine._check(1)
+            if m > 0:
+                name, vals = _column_facets(engine, col.value, m, codes, cnts)
+                facets[name] = vals
+        out.append(FilteredFacets(facets, int(tot.value), None))
+    return out[0] if single else out
+
+
+def _filtered_facet_stats(engine, sh):
+    a = C.c_uint32(0); b = C.c_uint32(0); n = C.c_uint32(0)
+    engine._check(engine.L.infx_engine_last_facets_filtered_stats(sh, C.byref(a), C.byref(b), C.byref(n)))
+    return int(a.value), int(b.value), int(n.value)
+
+
+def _attach_pre_filter_facets(engine, sh, qs, results):
+    """Query.pre_filter_facets of a batch just searched on session handle sh: the distinct pre-filters that ran are counted in ONE facets_of_documents call
+    (a device batch carries at most 16, so at most one pass; none when the engine has them cached) and each asking query gets its expression's facets."""
+    want = []
+    for q, r in zip(qs, results):
+        if q.pre_filter_facets and q.pre_filter is not None and r.error is None and q.pre_filter not in want:
+            want.append(q.pre_filter)
+    if not want:
+        return
+    got = dict(zip(want, _facets_filtered(engine, sh, want)))
+    for q, r in zip(qs, results):
+        if q.pre_filter_facets and q.pre_filter is not None and r.error is None and got[q.pre_filter].error is None:
+            r.pre_filter_facets = got[q.pre_filter].facets
 
 
 def _count_stats(engine, sh):

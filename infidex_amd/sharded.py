@@ -701,6 +701,14 @@ class ShardedSearcher:
         own GPU and gets the same result — nothing is exchanged."""
         return self.sessions[0].s.facets_of_all_documents()
 
+    def facets_of_documents(self, filters):
+        """SearchEngine.facets_of_documents: like facets_of_all_documents, every rank evaluates the filters over the whole columns with the global Deleted
+        flags on its own GPU and gets the same result — nothing is exchanged."""
+        return self.sessions[0].s.facets_of_documents(filters)
+
+    def last_filtered_facet_stats(self):
+        return self.sessions[0].s.last_filtered_facet_stats()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
