@@ -295,6 +295,9 @@ int32_t infx_upload_column(infx_index* idx, uint32_t col, uint32_t total_docs, c
 int32_t infx_filter_create(infx_index* idx, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
                            uint32_t ntable_words, const uint32_t* tables, infx_filter** out);
 void    infx_filter_destroy(infx_filter* f);
+/* The validation infx_filter_create and the per-query program tables apply, on its own: INFX_OK, or the status and message they would refuse the program with
+ * (more than INFX_FILTER_MAX_OPS ops, a stack deeper than the kernels' 32 slots, a malformed program, a column that was not uploaded).  Touches no device. */
+int32_t infx_filter_check(infx_index* idx, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves, uint32_t ntable_words);
 /* Documents of THIS shard the filter accepts (sum over shards = Filter.NumberOfDocumentsInFilter): k_filter_count_multi with K = 1. */
 int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count);
 /* Installs (f != NULL) or clears the post-filter and the facet columns of this stream: every following infx_search_fused /

@@ -2386,6 +2386,12 @@ static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter**
             cf.leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)cf.tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
             cf.tables.insert(cf.tables.end(), w.begin(), w.end());
         }
+        // what the device cannot run (more than INFX_FILTER_MAX_OPS ops, a stack deeper than 32) is refused here, for this expression alone — as a syntax
+        // error is — on every path; checked only later, by the batch's program table or mask build, it would fail the whole batch
+        if (e->dev) {
+            int32_t rc = infx_filter_check(e->dev, (uint32_t)cf.ops.size(), cf.ops.data(), (uint32_t)cf.leaves.size(), cf.leaves.data(), (uint32_t)cf.tables.size());
+            if (rc) { g_eerr = infx_last_error(); return rc; }
+        }
         e->filterLru.push_front(expr);
         it = e->filters.emplace(expr, std::move(cf)).first;
         it->second.lru = e->filterLru.begin();

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
+#include "../unicode_tables.h"
 
 namespace infx { namespace filt {
 
@@ -70,21 +71,17 @@ inline bool as_number(const std::string& t, double& out) {        // double.TryP
     return end != plain.c_str() && *end == 0;
 }
 // OrdinalIgnoreCase (and RegexOptions.IgnoreCase for LIKE): .NET upper-cases each UTF-16 code unit with the invariant simple mapping and compares the
-// units.  Case pairs are described as runs: {first lower, last lower, stride, delta to upper}; U+0131 / U+017F are left alone as in the BCL's ordinal
-// casing.  Covers Latin (incl. the Czech school corpus), Greek, Cyrillic, Armenian, Latin Extended Additional.
-struct CaseRun { uint16_t lo, hi, step; int32_t delta; };
+// units.  The mapping is the generated table the text layer ships (../unicode_tables.h, char.ToUpperInvariant of the whole BMP; U+0131 maps to itself there);
+// on top of it the BCL's ordinal casing leaves U+017F alone.  A surrogate pair is two units, neither of which has a mapping: non-BMP letters are not folded.
 inline uint16_t fold_unit(uint16_t c) {
-    static const CaseRun runs[] = {
-        {0x0061, 0x007A, 1, -32}, {0x00B5, 0x00B5, 1, 0x39C - 0xB5}, {0x00E0, 0x00F6, 1, -32}, {0x00F8, 0x00FE, 1, -32}, {0x00FF, 0x00FF, 1, 0x178 - 0xFF},
-        {0x0101, 0x012F, 2, -1}, {0x0133, 0x0137, 2, -1}, {0x013A, 0x0148, 2, -1}, {0x014B, 0x0177, 2, -1}, {0x017A, 0x017E, 2, -1},
-        {0x01CE, 0x01DC, 2, -1}, {0x01DF, 0x01EF, 2, -1}, {0x01F9, 0x021F, 2, -1}, {0x0223, 0x0233, 2, -1}, {0x0247, 0x024F, 2, -1},
-        {0x03AC, 0x03AC, 1, 0x386 - 0x3AC}, {0x03AD, 0x03AF, 1, -0x25}, {0x03B1, 0x03C1, 1, -32}, {0x03C2, 0x03C2, 1, 0x3A3 - 0x3C2}, {0x03C3, 0x03CB, 1, -32},
-        {0x03CC, 0x03CC, 1, 0x38C - 0x3CC}, {0x03CD, 0x03CE, 1, -0x3F},
-        {0x0430, 0x044F, 1, -32}, {0x0450, 0x045F, 1, -80}, {0x0461, 0x0481, 2, -1}, {0x048B, 0x04BF, 2, -1}, {0x04C2, 0x04CE, 2, -1}, {0x04CF, 0x04CF, 1, 0x4C0 - 0x4CF},
-        {0x04D1, 0x052F, 2, -1}, {0x0561, 0x0586, 1, -48}, {0x1E01, 0x1E95, 2, -1}, {0x1EA1, 0x1EFF, 2, -1},
-    };
-    for (const CaseRun& r : runs) if (c >= r.lo && c <= r.hi && (c - r.lo) % r.step == 0) return (uint16_t)(c + r.delta);
-    return c;
+    static const std::vector<uint16_t> up = [] {
+        std::vector<uint16_t> t(65536); for (uint32_t i = 0; i < 65536; i++) t[i] = (uint16_t)i;
+        static const uint16_t pairs[][2] = { INFX_UC_UPPER_PAIRS };
+        for (auto& pr : pairs) t[pr[0]] = pr[1];
+        t[0x0131] = 0x0131; t[0x017F] = 0x017F;
+        return t;
+    }();
+    return up[c];
 }
 inline std::u16string folded(const std::string& s) {               // UTF-8 -> folded UTF-16 units
     std::u16string o; o.reserve(s.size());

@@ -2692,6 +2692,10 @@ static int32_t check_filter_prog(infx_index* ix, uint32_t nops, const infx_filte
     }
     return INFX_OK;
 }
+int32_t infx_filter_check(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves, uint32_t ntable_words) {
+    if (!ix || !nops || !ops || (nleaves && !leaves)) return fail(INFX_EINVAL, "null argument%s");
+    return check_filter_prog(ix, nops, ops, nleaves, leaves, ntable_words);
+}
 int32_t infx_filter_create(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves,
                            uint32_t ntable_words, const uint32_t* tables, infx_filter** out) {
     if (!ix || !out || !nops || !ops || (nleaves && (!leaves || !tables))) return fail(INFX_EINVAL, "null argument%s");

@@ -95,34 +95,12 @@ inline bool try_parse_double(const std::string& s0, double& out) {      // doubl
     return end && *end == 0 && end != t.c_str();
 }
 // StringComparison.OrdinalIgnoreCase / RegexOptions.IgnoreCase: both sides are upper-cased per UTF-16 code unit with the invariant SIMPLE case mapping
-// and compared ordinally.  Restated for the scripts the corpora use (Basic Latin, Latin-1, Latin Extended-A/B pairs, Greek, Cyrillic, Armenian);
-// U+0131 and U+017F keep their value (the BCL's ordinal casing does not fold them onto ASCII I / S).  Strings here are UTF-8.
+// and compared ordinally.  The mapping is text.hpp's to_upper_inv (the generated table of unicode_tables.hpp, checked against ICU by
+// tests/test_unicode_second_source.py and tests/test_filter_model.py); U+0131 and U+017F keep their value (the BCL's ordinal casing does not fold them
+// onto ASCII I / S).  Code points beyond the BMP are surrogate pairs to .NET and are not folded.  Strings here are UTF-8.
 inline uint32_t up_cp(uint32_t c) {
-    if (c < 0x80) return (c >= 'a' && c <= 'z') ? c - 32 : c;
-    if (c == 0xB5) return 0x39C;
-    if (c >= 0xE0 && c <= 0xFE && c != 0xF7) return c - 0x20;
-    if (c == 0xFF) return 0x178;
-    if (c >= 0x100 && c <= 0x17F) {
-        if (c == 0x131 || c == 0x138 || c == 0x149 || c == 0x17F) return c;
-        if ((c >= 0x139 && c <= 0x148) || (c >= 0x179 && c <= 0x17E)) return (c & 1) ? c : c - 1;      // upper = odd code point
-        return (c & 1) ? c - 1 : c;                                                                   // upper = even code point
-    }
-    if (c >= 0x180 && c <= 0x24F) {
-        if ((c >= 0x1CD && c <= 0x1DC)) return (c & 1) ? c : c - 1;
-        if ((c >= 0x1DE && c <= 0x1EF) || (c >= 0x1F8 && c <= 0x21F) || (c >= 0x222 && c <= 0x233) || (c >= 0x246 && c <= 0x24F)) return (c & 1) ? c - 1 : c;
-        return c;
-    }
-    if (c == 0x3AC) return 0x386; if (c >= 0x3AD && c <= 0x3AF) return c - 0x25; if (c == 0x3CC) return 0x38C; if (c == 0x3CD || c == 0x3CE) return c - 0x3F;
-    if (c == 0x3C2) return 0x3A3;
-    if (c >= 0x3B1 && c <= 0x3CB) return c - 0x20;
-    if (c >= 0x430 && c <= 0x44F) return c - 0x20;
-    if (c >= 0x450 && c <= 0x45F) return c - 0x50;
-    if ((c >= 0x460 && c <= 0x481) || (c >= 0x48A && c <= 0x4BF) || (c >= 0x4D0 && c <= 0x52F)) return (c & 1) ? c - 1 : c;
-    if (c >= 0x4C1 && c <= 0x4CE) return (c & 1) ? c : c - 1;
-    if (c == 0x4CF) return 0x4C0;
-    if (c >= 0x561 && c <= 0x586) return c - 0x30;
-    if (c >= 0x1E00 && c <= 0x1EFF) { if (c >= 0x1E96 && c <= 0x1E9F) return c; return (c & 1) ? c - 1 : c; }
-    return c;
+    if (c > 0xFFFF || c == 0x17F) return c;
+    return (uint32_t)to_upper_inv((u16)c);
 }
 inline std::vector<uint16_t> up_units(const std::string& s) {       // UTF-8 -> upper-cased UTF-16 code units (invalid bytes pass through as single units)
     std::vector<uint16_t> o; o.reserve(s.size());
@@ -208,7 +186,7 @@ inline std::vector<Tok> tokenize(const std::string& e) {          // FilterParse
         }
         if (isl(c) || c == '_') {
             std::string w; while (i < e.size() && (isl((unsigned char)e[i]) || isdigit((unsigned char)e[i]) || e[i] == '_')) w.push_back(e[i++]);
-            std::string u = w; for (auto& ch : u) ch = (char)up_cp((unsigned char)ch);      // keywords are ASCII
+            std::string u = w; for (auto& ch : u) if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);      // keywords are ASCII
             Tok::T t = Tok::Ident;
             if (u == "AND") t = Tok::And; else if (u == "OR") t = Tok::Or; else if (u == "NOT") t = Tok::Not; else if (u == "BETWEEN") t = Tok::Between;
             else if (u == "IN") t = Tok::In; else if (u == "CONTAINS") t = Tok::Contains; else if (u == "STARTS") t = Tok::Starts; else if (u == "ENDS") t = Tok::Ends;
@@ -340,7 +318,7 @@ inline bool execute(const Compiled& f, const Fields& doc) {          // FilterVM
                 Slot p = pop(), t = pop(); std::string pat = str(p), text = str(t);
                 const std::vector<uint16_t> P = up_units(pat), T = up_units(text);      // StringComparison.OrdinalIgnoreCase
                 bool r;
-                if (in.op == CONTAINS) r = std::search(T.begin(), T.end(), P.begin(), P.end()) != T.end();
+                if (in.op == CONTAINS) r = P.empty() || std::search(T.begin(), T.end(), P.begin(), P.end()) != T.end();      // "".Contains("") is true (FilterVM.cs:234-239)
                 else if (in.op == STARTS_WITH) r = T.size() >= P.size() && std::equal(P.begin(), P.end(), T.begin());
                 else if (in.op == ENDS_WITH) r = T.size() >= P.size() && std::equal(P.begin(), P.end(), T.end() - (long)P.size());
                 else r = like_match(text, pat);

@@ -290,6 +290,8 @@ int32_t orc_filter_eval(const char* expr, int32_t nfields, const char* const* na
     } catch (const flt::ParseError& e) { return std::string(e.what()).find("not restated") != std::string::npos ? -2 : -1; }
       catch (const std::exception&) { return -2; }
 }
+// OrdinalIgnoreCase as the filter VM's restatement folds a UTF-16 code unit (flt::up_cp), for every unit of the BMP
+int32_t orc_filter_fold(uint16_t* out) { for (uint32_t c = 0; c < 65536; c++) out[c] = (uint16_t)flt::up_cp(c); return 65536; }
 int32_t orc_double_to_string(double x, char* out, int32_t cap) { std::string s = flt::dbl_to_string(x); snprintf(out, (size_t)cap, "%s", s.c_str()); return (int32_t)s.size(); }
 // Document.Deleted for every document whose DocumentKey is listed (DocumentCollection.DeleteDocumentsByKey, Core/DocumentCollection.cs:200-212)
 // without the Count bookkeeping: index statistics stay as indexed.  Returns the number of documents newly marked.

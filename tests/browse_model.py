@@ -3,7 +3,11 @@
 the rest is a walk over the documents and plain counting.
 
 Facet order: count descending, then value ascending as the oracle restates `ThenBy(kvp => kvp.Key)` (oracle/filter.hpp: ordinal-ignore-case, then
-ordinal)."""
+ordinal).  order_facets folds with str.lower(), the engine and the oracle with the invariant upper-case table: the two orders differ where a value lies
+between a letter's lower-case and upper-case form ('_' against 'a'; tests/filter_fuzz.py FOLD_ORDER).  The corpora that go through order_facets have no
+such pair — tests/test_filter_model.py::test_order_facets_agrees_on_the_fuzz_corpus holds that for the string column of filter_fuzz.columns — so
+str.lower() stays; the engine's own order on such pairs is pinned by test_facet_and_sort_order_follow_the_folding and, on the GPU, by
+tests/test_gpu_filter_fuzz.py::test_facet_tie_order_and_sort_by_follow_the_folding."""
 import math
 
 import numpy as np

@@ -264,6 +264,13 @@ def case_tables():
     return {"lower": lo, "upper": up, "letter": le}
 
 
+def filter_fold():
+    """OrdinalIgnoreCase of the filter VM's restatement (oracle/filter.hpp up_cp): the folded value of every BMP code unit."""
+    up = np.zeros(65536, np.uint16)
+    lib().orc_filter_fold(_p(up, C.c_uint16))
+    return up
+
+
 def normalize(s, lower=False):
     x = u16(s); out = np.zeros(len(x) + 8, np.uint16)
     n = lib().orc_normalize(_p(x, C.c_uint16), len(x), int(lower), _p(out, C.c_uint16), len(out))
