@@ -388,6 +388,32 @@ int32_t infx_engine_facets_filtered_column(infx_session* s, uint32_t which, uint
 int32_t infx_engine_facets_filtered_total(infx_session* s, uint32_t which, uint32_t* total);
 int32_t infx_engine_facets_filtered_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_facets_filtered_stats(infx_session* s, uint32_t* counted, uint32_t* cached, uint32_t* launches);
+/* ---- list_documents: a filter's documents in the order of a field, by page (not in the reference: the semantics below are this project's) ---------------
+ * Request i lists the SET of documents that are not Deleted and whose OWN fields its Infiscript `filter` accepts — per document, exactly the documents
+ * infx_engine_last_in_prefilter and infx_engine_facets_filtered_total count; filter = NULL: every live document; duplicate keys are not collapsed — in the
+ * ORDER (k(d), d): d the internal document index, k(d) = 1 + the sort rank of the document's value in field `order_by` (the ranks of Query.SortBy: long
+ * numerically; double with NaN lowest, all NaNs equal, -0 == +0; strings OrdinalIgnoreCase then ordinal), mirrored (number of distinct values + 1 - k) when
+ * `ascending` is 0, a constant when order_by = NULL (index order).  Ties go by ascending index in BOTH directions, so the order is total: pages never overlap
+ * or skip, and any page equals the slice [offset, offset + limit) of the whole order.  1 <= limit <= 1024 (INFX_POST_MAX_ROWS, whatever max_post_rows is);
+ * 0 <= offset < 2^31, a deep offset costs what offset 0 costs; offset >= total: an empty page with the total, no error.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_list_error, the others unaffected): a syntax error, an unknown order_by field or
+ * a limit / offset out of range INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests
+ * (INFX_ECAPACITY): one mask slot per distinct filter.  INFX_EHIP on an engine without a GPU (no CPU fallback).  The masks are the session's pre-filter masks:
+ * same slots, same least-recently-used rule, same epoch (deletions, restores, infx_engine_add_column and indexing invalidate them), and the ones a call is
+ * missing are built in ONE launch in front of it; a column's sort rank is built on its first use.  Nothing else is cached.  Works on a sharded engine without
+ * a collective (whole columns and global Deleted flags on every rank).
+ * Readers, for request `which` of the session's last call: infx_engine_list_rows copies up to cap rows (DocumentKey, internal document, code of the
+ * order_by column: its text through infx_engine_column_value) and returns the page's row count, -1 for a refused request or bad arguments;
+ * infx_engine_list_total the size of the set (returning the request's status); infx_engine_list_error the refusal's message (its length; -1 out of range).
+ * infx_engine_last_list_stats: masks built and reused, histogram passes and kernel launches of the session's last call.
+ * infx_engine_set_list_digit_bits: the width of a radix-select digit on this session, 4 .. 11 (default 11) — a tuning knob. */
+typedef struct infx_list_request { const char* filter; const char* order_by; int32_t ascending; uint32_t offset; uint32_t limit; } infx_list_request;
+int32_t infx_engine_list_documents(infx_session* s, uint32_t nreq, const infx_list_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_list_rows(infx_session* s, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap);
+int32_t infx_engine_list_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_list_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_list_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches);
+int32_t infx_engine_set_list_digit_bits(infx_session* s, int32_t bits);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

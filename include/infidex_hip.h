@@ -358,7 +358,8 @@ int32_t infx_last_filter_count_stats(infx_stream* s, uint32_t* counted, uint32_t
  * A query with a pre-filter P returns what it would return on the same index if every document P does not accept carried Document.Deleted: the
  * query reads a MASK — one byte per GLOBAL internal id, mask[g] = Deleted(g) || !accept_P(g) — wherever it would read the index's Deleted flags
  * (Stage-1 emission, the exact replay, the WordMatcher-only candidates).  Index statistics are untouched, as with deletions; the count, browse and
- * whole-corpus facet kernels keep the real flags.  Unsharded indexes only (infx_search_fused).
+ * whole-corpus facet kernels keep the real flags.  Queries read masks on unsharded indexes only (infx_search_fused); a sharded index may build them for
+ * infx_list_ordered, which reads them by global id.
  *   infx_stream_mask_slot   the device buffer of mask slot `slot` (< INFX_MAX_PREFILTERS) of this stream: total_docs bytes padded to a multiple of four,
  *                           allocated on first use, owned by the stream.  What a slot holds is the caller's bookkeeping.
  *   infx_filter_masks       stages the build of k (<= INFX_MAX_PREFILTERS) masks: masks[i] (device, as from infx_stream_mask_slot) receives the mask of
@@ -406,6 +407,25 @@ int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uin
 int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint32_t ncol, const uint32_t* cols,
                              uint32_t* counts_out /* k x sum(num_values), program-major */, uint32_t* totals_out /* k */);
 int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint32_t* launches);
+/* A page of a document set in the order of a column (not in the reference: the order and the paging are this project's; DESIGN.md "list_documents").
+ * Request i: the SET is the documents whose byte in `mask` is 0 — a mask slot of this stream (infx_stream_mask_slot, built by infx_filter_masks: not
+ * Deleted and accepted) — or, mask = NULL, every document that is not Deleted (the index's real flags).  The KEY of a document is 1 + rank[its code] of
+ * uploaded column `col` (infx_upload_sort_rank), or num_values + 1 - that when `ascending` is 0; col = -1: a constant.  The ORDER is (key, global internal
+ * id) ascending — ties go by ascending id in both directions — a total order.  The answer is the rows at positions [offset, min(offset + limit, total))
+ * of it, total = the size of the set: per row the DocumentKey, the global internal id and the column's code (0 without a column), in
+ * keys_out / docs_out / codes_out at [i * INFX_POST_MAX_ROWS ..]; counts_out[i] rows, totals_out[i] = total; the rows from counts_out[i] up to limit read
+ * -1 / -1 / 0, the ones beyond limit are not written.  offset >= total: no rows, no error.
+ * 1 <= limit <= INFX_POST_MAX_ROWS whatever the index's post rows; offset < 2^31 (the kernels launched do not depend on it); digit_bits 4 .. 11 (11 in production: the width of a radix digit);
+ * at most INFX_MAX_PREFILTERS requests (INFX_ECAPACITY).  No document is sorted: a radix select over the keys (ceil(bits(num_values + 1) / digit_bits)
+ * histogram passes, at most three at 11 bits) finds the keys at both ends of the page, an ordered count / prefix / gather collects its <= 1024 rows and one
+ * workgroup sorts those.  A mask build staged with infx_filter_masks is enqueued first, as ONE launch; nothing waits for the host between the kernels.
+ * Exact and deterministic: the same bytes from any stream and grid.  Works on a sharded index (whole columns and global flags on every rank; the masks
+ * of a sharded index serve this call only).  Synchronous.
+ * infx_last_list_stats: histogram passes (summed over the requests) and kernel launches (the mask build included) of the stream's last call. */
+typedef struct infx_list_req { const uint8_t* mask; int32_t col; int32_t ascending; uint32_t offset; uint32_t limit; uint32_t digit_bits; uint32_t reserved; } infx_list_req;
+int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
+                          uint32_t* counts_out /* nreq */, uint32_t* totals_out /* nreq */);
+int32_t infx_last_list_stats(infx_stream* s, uint32_t* hist_passes, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

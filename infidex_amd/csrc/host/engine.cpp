@@ -89,6 +89,8 @@ struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t cou
 // and the number of live documents the expression accepts; valid for the mask epoch it was counted in
 struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists; std::list<std::string>::iterator lru; };
 struct FfAnswer { int32_t status = INFX_OK; std::string err; std::shared_ptr<const FfEntry> r; };
+// One request of the session's last infx_engine_list_documents: its status and message, the size of its set, its page
+struct ListAnswer { int32_t status = INFX_OK; std::string err; uint32_t total = 0; std::vector<int64_t> keys; std::vector<int32_t> docs; std::vector<uint32_t> codes; };
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
@@ -102,6 +104,8 @@ struct infx_session {
     // infx_engine_facets_filtered: the facet columns of the session's last call, one answer per expression of it (its entry of the engine's cache, or why it
     // was refused), and what the call cost: expressions counted on the device, expressions taken from the cache, k_facets_filtered launches
     std::vector<uint32_t> ffCols; std::vector<FfAnswer> ff; uint32_t ffCounted = 0, ffCached = 0, ffLaunches = 0;
+    // infx_engine_list_documents: one answer per request of the session's last call, what the call cost (histogram passes, kernel launches), the digit width
+    std::vector<ListAnswer> lst; uint32_t lstBuilt = 0, lstReused = 0, lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -3109,6 +3113,115 @@ int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counte
     if (counted) *counted = S->ffCounted;
     if (cached) *cached = S->ffCached;
     if (launches) *launches = S->ffLaunches;
+    return INFX_OK;
+}
+
+// ---- list_documents: a filter's documents in the order of a field, by page (not in the reference) ------------------------------------------------------
+// Per request: the filter goes through the filter cache (refusals are the request's own), its mask through the session's mask cache (the slots, the LRU
+// rule and the statistics of a batch's pre-filters; the missing ones staged as ONE build), the field to its column, whose sort rank is built on first use.
+// infx_list_ordered then selects, gathers and sorts every page on the device; the answers stay on the session for the readers.
+int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_list_request* reqs, int32_t* out_status) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->lst.clear(); S->lstBuilt = S->lstReused = S->lstPasses = S->lstLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) listing requests in one call");
+    S->lst.assign(nreq, ListAnswer());
+    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->lst[i].status = rc; S->lst[i].err = msg; if (out_status) out_status[i] = rc; };
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (out_status) out_status[i] = INFX_OK;
+        if (reqs[i].limit < 1 || reqs[i].limit > INFX_POST_MAX_ROWS) refuse(i, INFX_EINVAL, "a listing's limit is 1 .. 1024");
+        else if (reqs[i].offset >= 0x80000000u) refuse(i, INFX_EINVAL, "a listing's offset is below 2^31");
+    }
+    // a call that fails as a whole leaves no answers behind: the readers refuse (the statuses already written to out_status stay)
+    if (!e->dev || !S->stream) { S->lst.clear(); return efail(INFX_EHIP, "no GPU: list_documents runs on the device"); }
+    if (!e->indexed) { S->lst.clear(); return efail(INFX_EINVAL, "list_documents before index_documents"); }
+    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nreq, -1); std::vector<int32_t> col(nreq, -1);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (S->lst[i].status) continue;
+            if (reqs[i].order_by) {
+                uint32_t c = 0xFFFFFFFFu;
+                const int32_t rc = sort_column(e, reqs[i].order_by, &c);
+                if (rc) { refuse(i, rc, g_eerr); continue; }
+                if (c == 0xFFFFFFFFu) { refuse(i, INFX_EINVAL, std::string("list_documents: no field named '") + reqs[i].order_by + "'"); continue; }
+                col[i] = (int32_t)c;
+            }
+            if (!reqs[i].filter) continue;
+            auto it = idx.find(reqs[i].filter);
+            if (it == idx.end()) {
+                CompiledFilter* cf = nullptr;
+                const int32_t rc = compile_filter(e, reqs[i].filter, &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
+                if (rc) { refuse(i, rc, g_eerr); continue; }
+                it = idx.emplace(reqs[i].filter, (int)exprs.size()).first; exprs.push_back(reqs[i].filter);
+            }
+            of[i] = it->second;
+        }
+    }
+    std::vector<int> slots, built;
+    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, slots, built); if (rc) { unstage_prefilters(S, built); S->lst.clear(); return rc; } }
+    else S->preBuilt = S->preReused = S->preLaunches = 0;
+    std::vector<infx_list_req> dr; std::vector<uint32_t> who;
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (S->lst[i].status) continue;
+        infx_list_req R{};
+        if (of[i] >= 0) {
+            uint8_t* p = nullptr;
+            int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[of[i]], &p);
+            if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); S->lst.clear(); return rc; }
+            R.mask = p;
+        }
+        R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
+        dr.push_back(R); who.push_back(i);
+    }
+    const size_t m = dr.size(), rows = INFX_POST_MAX_ROWS;
+    std::vector<int64_t> keys(std::max<size_t>(m, 1) * rows); std::vector<int32_t> docs(std::max<size_t>(m, 1) * rows); std::vector<uint32_t> codes(std::max<size_t>(m, 1) * rows);
+    std::vector<uint32_t> counts(std::max<size_t>(m, 1), 0), totals(std::max<size_t>(m, 1), 0);
+    int32_t rc = infx_list_ordered(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), counts.data(), totals.data());
+    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); S->lst.clear(); return rc; }
+    take_prefilter_counts(S, 0, built);
+    S->lstBuilt = S->preBuilt; S->lstReused = S->preReused;
+    infx_last_list_stats(S->stream, &S->lstPasses, &S->lstLaunches);
+    for (size_t j = 0; j < m; j++) {
+        ListAnswer& A = S->lst[who[j]];
+        const size_t c = std::min<size_t>(counts[j], dr[j].limit);
+        A.total = totals[j];
+        A.keys.assign(keys.begin() + j * rows, keys.begin() + j * rows + c); A.docs.assign(docs.begin() + j * rows, docs.begin() + j * rows + c);
+        A.codes.assign(codes.begin() + j * rows, codes.begin() + j * rows + c);
+    }
+    return INFX_OK;
+}
+// request `which` of the session's last infx_engine_list_documents: up to cap rows; returns the page's row count, -1 on error (also for a refused request)
+int32_t infx_engine_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap) {
+    if (!S || which >= S->lst.size() || S->lst[which].status || (cap > 0 && (!keys || !docs || !codes))) return -1;
+    const ListAnswer& A = S->lst[which];
+    const size_t c = std::min<size_t>(A.keys.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(keys, A.keys.data(), c * 8); std::memcpy(docs, A.docs.data(), c * 4); std::memcpy(codes, A.codes.data(), c * 4); }
+    return (int32_t)A.keys.size();
+}
+// the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_list_total(infx_session* S, uint32_t which, uint32_t* total) {
+    if (!S || !total || which >= S->lst.size()) return efail(INFX_EINVAL, "no such request in the session's last list_documents call");
+    *total = S->lst[which].total;
+    return S->lst[which].status;
+}
+int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
+    if (!S || which >= S->lst.size()) return -1;
+    const std::string& msg = S->lst[which].err;
+    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", msg.c_str());
+    return (int32_t)msg.size();
+}
+int32_t infx_engine_last_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (masks_built) *masks_built = S->lstBuilt;
+    if (masks_reused) *masks_reused = S->lstReused;
+    if (hist_passes) *hist_passes = S->lstPasses;
+    if (launches) *launches = S->lstLaunches;
+    return INFX_OK;
+}
+int32_t infx_engine_set_list_digit_bits(infx_session* S, int32_t bits) {
+    if (!S || bits < 4 || bits > 11) return efail(INFX_EINVAL, "the digit width of list_documents is 4 .. 11 bits");
+    S->lstDigitBits = bits;
     return INFX_OK;
 }
 

@@ -261,6 +261,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "filter.hip.inc"
 #include "browse.hip.inc"
 #include "facets_filtered.hip.inc"
+#include "listing.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -303,6 +304,8 @@ struct infx_stream {
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
     void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
     uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
+    void *dListWs = nullptr, *dListOut = nullptr; size_t capListWs = 0, capListOut = 0;      // infx_list_ordered: select states, histograms, range counts, page composites; the rows
+    uint32_t lastListPasses = 0, lastListLaunches = 0;         // histogram passes and kernel launches of the last infx_list_ordered
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1213,7 +1216,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -3015,6 +3018,86 @@ int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint
     if (launches) *launches = s->lastFfLaunches;
     return INFX_OK;
 }
+// ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
+int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* counts_out, uint32_t* totals_out) {
+    if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !counts_out || !totals_out))) return fail(INFX_EINVAL, "bad listing arguments%s");
+    s->lastListPasses = 0; s->lastListLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) listing requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs || !ix->d.docKeyAll) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    uint32_t passes[INFX_MAX_PREFILTERS] = {}; size_t histOff[INFX_MAX_PREFILTERS] = {}, histWords = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_list_req& Q = reqs[i];
+        if (Q.limit < 1 || Q.limit > INFX_POST_MAX_ROWS) return fail(INFX_EINVAL, "a listing's limit is 1 .. INFX_POST_MAX_ROWS (1024)%s");
+        if (Q.offset >= 0x80000000u) return fail(INFX_EINVAL, "a listing's offset is below 2^31%s");
+        if (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS) return fail(INFX_EINVAL, "a listing's digit width is 4 .. 11 bits%s");
+        if (Q.col >= 0 && (Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col] || !ix->colRankOk[Q.col])) return fail(INFX_EINVAL, "the listing's column or its sort rank was not uploaded%s");
+        if (Q.col >= 0 && (uint64_t)ix->colDocs[Q.col] < (uint64_t)n) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        if (Q.mask) { const int slot = mask_slot_of(s, Q.mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a listing's mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
+        passes[i] = ls_passes(Q.col >= 0 ? ix->colValues[Q.col] : 1u, Q.digit_bits);
+        histOff[i] = histWords; histWords += (size_t)passes[i] * 2u << Q.digit_bits;
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    const uint32_t builds = s->mkStaged && !s->mkProgs.empty() && n > 0 ? 1u : 0u;
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
+    s->lastListLaunches = builds;
+    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    const uint32_t tiles = (uint32_t)(((int64_t)n + LST_TILE - 1) / LST_TILE), nRanges = std::max(1u, std::min(LST_MAXRANGES, tiles));
+    // workspace: [states | histograms] (zeroed), [page composites] (all ones), range counts and prefixes [nreq][2][3][nRanges]
+    const size_t stBytes = (sizeof(DevListState) + 63) & ~(size_t)63;
+    const size_t oHist = (size_t)nreq * stBytes, oPairs = (oHist + histWords * 4 + 63) & ~(size_t)63, oRange = oPairs + (size_t)nreq * INFX_POST_MAX_ROWS * 8;
+    const size_t wsBytes = oRange + (size_t)nreq * 6 * nRanges * 4;
+    const size_t R = INFX_POST_MAX_ROWS, oDocs = (size_t)nreq * R * 8, oCodes = oDocs + (size_t)nreq * R * 4, oCnt = oCodes + (size_t)nreq * R * 4, oTot = oCnt + (size_t)nreq * 4;
+    GROW(s->dListWs, s->capListWs, wsBytes);
+    GROW(s->dListOut, s->capListOut, oTot + (size_t)nreq * 4);
+    char* W = (char*)s->dListWs; char* O = (char*)s->dListOut;
+    HIPCHK(hipMemsetAsync(W, 0, oPairs, s->st));
+    HIPCHK(hipMemsetAsync(W + oPairs, 0xFF, (size_t)nreq * INFX_POST_MAX_ROWS * 8, s->st));
+    s->unsynced = true;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_list_req& Q = reqs[i];
+        DevListReq D{};
+        D.mask = Q.mask ? Q.mask : ix->d.deleted;
+        if (Q.col >= 0) { D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col]; } else D.nvals = 1;
+        D.ascending = Q.ascending ? 1u : 0u; D.offset = Q.offset; D.limit = Q.limit; D.digitBits = Q.digit_bits; D.passes = passes[i];
+        DevListState* st = (DevListState*)(W + (size_t)i * stBytes);
+        uint32_t* hist = (uint32_t*)(W + oHist) + histOff[i];
+        unsigned long long* pairs = (unsigned long long*)(W + oPairs) + (size_t)i * INFX_POST_MAX_ROWS;
+        uint32_t* rangeCnt = (uint32_t*)(W + oRange) + (size_t)i * 6 * nRanges; uint32_t* rangePre = rangeCnt + 3 * (size_t)nRanges;
+        if (n > 0) {
+            const size_t nb = (size_t)1 << Q.digit_bits;
+            const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
+            const int grid = (int)std::min<int64_t>(FCM_MAXGRID, (groups + LST_THREADS - 1) / LST_THREADS);
+            for (uint32_t p = 0; p < passes[i]; p++) {
+                k_list_hist<<<grid, LST_THREADS, 2 * nb * 4, s->st>>>(D, n, p, st, hist + (size_t)p * 2 * nb);
+                k_list_pick<<<1, LST_THREADS, 0, s->st>>>(D, p, st, hist + (size_t)p * 2 * nb);
+            }
+            k_list_count<<<nRanges, LST_THREADS, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt);
+            k_list_prefix<<<3, LST_THREADS, 0, s->st>>>(nRanges, st, rangeCnt, rangePre);
+            k_list_gather<<<nRanges, WAVE, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt, rangePre, pairs);
+            s->lastListPasses += passes[i]; s->lastListLaunches += 2 * passes[i] + 3;
+        }
+        k_list_sort<<<1, LST_SORT_THREADS, 0, s->st>>>(D, n, st, pairs, (const long long*)ix->d.docKeyAll, (long long*)O + (size_t)i * R, (int32_t*)(O + oDocs) + (size_t)i * R,
+                                                     (uint32_t*)(O + oCodes) + (size_t)i * R, (uint32_t*)(O + oCnt) + i, (uint32_t*)(O + oTot) + i);
+        HIPCHK(hipGetLastError());
+        s->lastListLaunches++;
+        DOWN(keys_out + (size_t)i * R, (long long*)O + (size_t)i * R, (size_t)Q.limit * 8);
+        DOWN(docs_out + (size_t)i * R, (int32_t*)(O + oDocs) + (size_t)i * R, (size_t)Q.limit * 4);
+        DOWN(codes_out + (size_t)i * R, (uint32_t*)(O + oCodes) + (size_t)i * R, (size_t)Q.limit * 4);
+    }
+    DOWN(counts_out, O + oCnt, (size_t)nreq * 4);
+    DOWN(totals_out, O + oTot, (size_t)nreq * 4);
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_list_stats(infx_stream* s, uint32_t* hist_passes, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (hist_passes) *hist_passes = s->lastListPasses;
+    if (launches) *launches = s->lastListLaunches;
+    return INFX_OK;
+}
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {
     if (!s || !out || slot >= INFX_MAX_PREFILTERS) return fail(INFX_EINVAL, "bad mask slot%s");
     infx_index* ix = s->ix;
@@ -3039,7 +3122,6 @@ int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* pr
     if (k > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) masks in one build%s");
     infx_index* ix = s->ix;
     if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    if (ix->nranks > 1 || ix->d.docBase != 0) return fail(INFX_EUNSUPPORTED, "document masks need an unsharded index%s");
     for (uint32_t i = 0; i < k; i++) {
         if (mask_slot_of(s, masks[i]) < 0) return fail(INFX_EINVAL, "a mask buffer is not a mask slot of this stream%s");
         for (uint32_t j = 0; j < i; j++) if (masks[j] == masks[i]) return fail(INFX_EINVAL, "two masks of one build share a slot%s");
@@ -3055,6 +3137,8 @@ int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* pr
 int32_t infx_stream_set_doc_masks(infx_stream* s, uint32_t nq, const uint8_t* const* masks) {
     if (!s || (nq && !masks)) return fail(INFX_EINVAL, "null argument%s");
     s->docMasks.clear();
+    // the masks hold one byte per GLOBAL internal id (a sharded index may build them, for infx_list_ordered); a shard's queries read flags by shard-local id
+    for (uint32_t i = 0; i < nq; i++) if (masks[i] && (s->ix->nranks > 1 || s->ix->d.docBase != 0)) return fail(INFX_EUNSUPPORTED, "document masks need an unsharded index%s");
     for (uint32_t i = 0; i < nq; i++) if (masks[i] && mask_slot_of(s, masks[i]) < 0) return fail(INFX_EINVAL, "a document mask is not a mask slot of this stream%s");
     s->docMasks.assign(masks, masks + nq);
     return INFX_OK;

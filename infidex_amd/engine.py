@@ -157,6 +157,27 @@ class FilteredFacets:      # SearchEngine.facets_of_documents: one per expressio
     error: Optional[str] = None                         # why this expression alone was refused (syntax error, MATCHES); None when it was counted
 
 
+@dataclass
+class ListRequest:         # SearchEngine.list_documents: one page of one listing
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    order_by: Optional[str] = None      # field whose values order the documents; None: index order
+    ascending: bool = True              # False: largest value first — documents of equal value still by ascending index
+    offset: int = 0                     # position of the page's first row in the whole order, 0 <= offset < 2**31
+    limit: int = 20                     # rows of the page, 1 .. 1024
+
+
+@dataclass
+class Listing:             # SearchEngine.list_documents: one per request
+    document_ids: list = _dc_field(default_factory=list)      # DocumentKeys of the page's rows, in order
+    values: list = _dc_field(default_factory=list)            # the rows' order_by values as text (ToString()); [] when order_by is None
+    total: int = 0                                            # live documents the filter accepts, whatever the page
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+class _ListReq(C.Structure):
+    _fields_ = [("filter", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
+
+
 class _Cfg(C.Structure):
     _fields_ = [("device", C.c_int32), ("range_docs", C.c_int32), ("max_depth", C.c_int32), ("threads", C.c_int32),
                 ("enable_coverage", C.c_int32), ("word_matcher", C.c_int32), ("stop_term_limit", C.c_int32),
@@ -422,6 +443,25 @@ class SearchEngine:
         """(expressions counted on the device, expressions taken from the engine's cache, k_facets_filtered launches) of the session's last
         facets_of_documents call (or batch with Query.pre_filter_facets)."""
         return _filtered_facet_stats(self, session.h if session is not None else self._default_session())
+
+    def list_documents(self, filter=None, order_by=None, ascending=True, offset=0, limit=20, session=None):
+        """A page of the documents a filter accepts, in the order of a field (not in the reference).  The set: every document that is not Deleted and whose
+        own fields `filter` accepts (None: every live document; exactly the documents total_in_pre_filter counts; duplicate keys are rows of their own).
+        The order: order_by's values as Query.sort_by compares them (None: index order), descending when ascending is False, documents of equal value by
+        ascending internal index in both directions — a total order, so consecutive pages never overlap or skip.  Returns Listing(document_ids, values,
+        total, error) for positions [offset, offset + limit), 1 <= limit <= 1024 whatever max_post_rows is; an offset at or beyond the total gives an
+        empty page.  The device selects the page (a radix select over the sort ranks of the set, no sort of the set; a deep offset costs what offset 0
+        costs) and the session's pre-filter masks are reused across pages.  A sequence of ListRequest as first argument -> a list of Listing, sixteen
+        requests per device call; a request with a syntax error, MATCHES, an unknown field or a limit out of range gets `error` set, alone."""
+        return _list_documents(self, session.h if session is not None else self._default_session(), filter, order_by, ascending, offset, limit)
+
+    def last_list_stats(self, session=None):
+        """(masks built, masks reused, histogram passes, kernel launches) of the session's last list_documents device call."""
+        return _list_stats(self, session.h if session is not None else self._default_session())
+
+    def set_list_digit_bits(self, bits, session=None):
+        """The width of a radix-select digit of list_documents on the session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
+        self._check(self.L.infx_engine_set_list_digit_bits(session.h if session is not None else self._default_session(), int(bits)))
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -715,6 +755,18 @@ class Session:
         """SearchEngine.last_filtered_facet_stats of this session."""
         return _filtered_facet_stats(self.engine, self.h)
 
+    def list_documents(self, filter=None, order_by=None, ascending=True, offset=0, limit=20):
+        """SearchEngine.list_documents on this session (its mask cache holds the filters' masks)."""
+        return _list_documents(self.engine, self.h, filter, order_by, ascending, offset, limit)
+
+    def last_list_stats(self):
+        """SearchEngine.last_list_stats of this session."""
+        return _list_stats(self.engine, self.h)
+
+    def set_list_digit_bits(self, bits):
+        """The width of a radix-select digit of list_documents on this session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
+        self.engine._check(self.engine.L.infx_engine_set_list_digit_bits(self.h, int(bits)))
+
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
         return _prefilter_stats(self.engine, self.h)
@@ -954,6 +1006,64 @@ def _facets_filtered(engine, sh, filters):
                 facets[name] = vals
         out.append(FilteredFacets(facets, int(tot.value), None))
     return out[0] if single else out
+
+
+def _column_index(engine, name):
+    """The engine's column of a field name, or -1."""
+    for col in range(int(engine.L.infx_engine_column_count(engine.h))):
+        nb = C.create_string_buffer(256); engine.L.infx_engine_column_info(engine.h, col, nb, 256, None, None)
+        if nb.value.decode() == name:
+            return col
+    return -1
+
+
+def _list_documents(engine, sh, filter, order_by, ascending, offset, limit):
+    """infx_engine_list_documents on session handle sh: a Listing for one request (given by its parts), a list of them for a sequence of ListRequest."""
+    single = filter is None or isinstance(filter, str)
+    reqs = [ListRequest(filter, order_by, ascending, offset, limit)] if single else list(filter)
+    out = []
+    for r0 in range(0, len(reqs), MAX_PREFILTERS):       # one mask slot per distinct filter: sixteen requests per device call
+        part = reqs[r0:r0 + MAX_PREFILTERS]
+        n = len(part)
+        arr = (_ListReq * n)()
+        for i, r in enumerate(part):
+            off, lim = int(r.offset), int(r.limit)
+            # out of the C fields' range: passed as values the engine refuses for this request alone
+            arr[i] = _ListReq(None if r.filter is None else r.filter.encode(), None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
+                              off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+        st = np.zeros(n, np.int32)
+        engine._check(engine.L.infx_engine_list_documents(sh, n, arr, _p(st, C.c_int32)))
+        cols = {}
+        for i, r in enumerate(part):
+            if st[i] != 0:
+                buf = C.create_string_buffer(512); engine.L.infx_engine_list_error(sh, i, buf, 512)
+                out.append(Listing([], [], 0, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
+                continue
+            tot = C.c_uint32(0)
+            engine._check(engine.L.infx_engine_list_total(sh, i, C.byref(tot)))
+            keys = np.zeros(1024, np.int64); docs = np.zeros(1024, np.int32); codes = np.zeros(1024, np.uint32)
+            m = engine.L.infx_engine_list_rows(sh, i, _p(keys, C.c_int64), _p(docs, C.c_int32), _p(codes, C.c_uint32), 1024)
+            if m < 0:
+                engine._check(1)
+            vals = []
+            if r.order_by is not None:
+                if r.order_by not in cols:
+                    cols[r.order_by] = (_column_index(engine, r.order_by), {})
+                col, text = cols[r.order_by]
+                for c in codes[:m]:
+                    c = int(c)
+                    if c not in text:
+                        vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col, c, vb, 1024)
+                        text[c] = vb.value.decode()
+                    vals.append(text[c])
+            out.append(Listing([int(k) for k in keys[:m]], vals, int(tot.value), None))
+    return out[0] if single else out
+
+
+def _list_stats(engine, sh):
+    a = C.c_uint32(0); b = C.c_uint32(0); c = C.c_uint32(0); d = C.c_uint32(0)
+    engine._check(engine.L.infx_engine_last_list_stats(sh, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return int(a.value), int(b.value), int(c.value), int(d.value)
 
 
 def _filtered_facet_stats(engine, sh):

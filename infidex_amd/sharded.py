@@ -709,6 +709,14 @@ class ShardedSearcher:
     def last_filtered_facet_stats(self):
         return self.sessions[0].s.last_filtered_facet_stats()
 
+    def list_documents(self, filter=None, order_by=None, ascending=True, offset=0, limit=20):
+        """SearchEngine.list_documents: like facets_of_documents, every rank selects the page over the whole columns with the global Deleted flags on its
+        own GPU and gets the same answer — nothing is exchanged."""
+        return self.sessions[0].s.list_documents(filter, order_by, ascending, offset, limit)
+
+    def last_list_stats(self):
+        return self.sessions[0].s.last_list_stats()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
