@@ -17,37 +17,20 @@ struct DevFacetFilt {
     uint32_t ldsOff[INFX_MAX_FACET_COLS];      // 0xFFFFFFFF: global counters
     uint8_t slot[INFX_MAX_FACET_COLS];         // the column's slot among the codes the programs read (DevCountCols), 0xFF: no program reads it
 };
-// four consecutive codes of a column from document d0: one 16-byte load in a full group, one by one in the corpus's partial last group (columns are not padded)
-__device__ __forceinline__ uint4 ffl_load4(const uint32_t* __restrict__ col, int64_t d0, int64_t n, bool have, bool full) {
-    uint4 c = make_uint4(0, 0, 0, 0);
-    if (full) c = *(const uint4*)(col + d0);
-    else if (have) { c.x = col[d0]; if (d0 + 1 < n) c.y = col[d0 + 1]; if (d0 + 2 < n) c.z = col[d0 + 2]; }      // (d0 + 3 >= n in a partial group)
-    return c;
-}
 #define FFL_BIG_THREADS 1024      // launches whose LDS counters exceed 16 KiB: one large workgroup per CU-sized share of LDS (infx_facets_filtered)
 __global__ __launch_bounds__(FFL_BIG_THREADS) void k_facets_filtered(const DevFilter* __restrict__ progs, uint32_t K, DevCountCols cc, DevColumns cols, int32_t n,
                                                                   const uint8_t* __restrict__ deleted, DevFacetFilt F, int ncol, uint32_t ldsWords, uint32_t stride,
                                                                   uint32_t* __restrict__ out, uint32_t* __restrict__ totals) {
     extern __shared__ __attribute__((aligned(16))) uint32_t ffl_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
-    uint32_t* codes = ffl_lds;                               // [(u * 4 + j) * T + tid]: document j of the thread's four, column slot u
+    uint32_t* codes = ffl_lds;                               // the thread's codes (filt_group4)
     uint32_t* cnt = ffl_lds + (size_t)cc.nUsed * 4u * T;     // [K] live accepted documents of this workgroup
     uint32_t* fac = cnt + K;                                 // [ldsWords] facet counters: F.ldsOff[c] + k * nvals[c] + code
     for (uint32_t i = tid; i < K + ldsWords; i += T) cnt[i] = 0;
     __syncthreads();
     const int64_t groups = ((int64_t)n + 3) >> 2;
     for (int64_t gb = (int64_t)blockIdx.x * T; gb < groups; gb += (int64_t)gridDim.x * T) {
-        const int64_t gi = gb + tid, d0 = gi * 4;
-        const bool have = gi < groups, full = have && d0 + 4 <= (int64_t)n;
-        uint32_t dead = 0;                                   // byte j: document d0 + j is Deleted, or lies beyond the corpus
-        if (!have) dead = 0x01010101u;
-        else if (full) { if (deleted) dead = *(const uint32_t*)(deleted + d0); }
-        else for (int j = 0; j < 4; j++) if (d0 + j >= (int64_t)n || (deleted && deleted[d0 + j])) dead |= 1u << (8 * j);
-        for (uint32_t u = 0; u < cc.nUsed; u++) {
-            const uint4 c = ffl_load4(cols.codes[cc.col[u]], d0, n, have, full);
-            uint32_t* cu = codes + (size_t)u * 4u * T + tid;
-            cu[0] = c.x; cu[T] = c.y; cu[2 * T] = c.z; cu[3 * T] = c.w;
-        }
+        const FiltGroup4 g = filt_group4(gb + tid, groups, n, deleted, cc, cols, codes, tid, T);
         uint32_t acc[4] = {0, 0, 0, 0};                      // document j: bit k = program k accepts it and it is live
         for (uint32_t k = 0; k < K; k++) {
             const DevFilter f = progs[k];
@@ -55,7 +38,7 @@ __global__ __launch_bounds__(FFL_BIG_THREADS) void k_facets_filtered(const DevFi
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const bool a = filt_eval_codes(f, [&](uint32_t c) { return codes[((uint32_t)cc.slot[c] * 4u + j) * T + tid]; });
-                const bool hit = a && !((dead >> (8 * j)) & 0xFFu);
+                const bool hit = a && !((g.dead >> (8 * j)) & 0xFFu);
                 hits += (uint32_t)__popcll(__ballot(hit));
                 acc[j] |= (hit ? 1u : 0u) << k;
             }
@@ -66,7 +49,7 @@ __global__ __launch_bounds__(FFL_BIG_THREADS) void k_facets_filtered(const DevFi
             const uint32_t nv = F.nvals[c];
             uint4 v;
             if (F.slot[c] != 0xFFu) { const uint32_t* cu = codes + (size_t)F.slot[c] * 4u * T + tid; v = make_uint4(cu[0], cu[T], cu[2 * T], cu[3 * T]); }
-            else v = ffl_load4(F.codes[c], d0, n, have, full);
+            else v = g.load4(F.codes[c], n);
             const uint32_t vj[4] = {v.x, v.y, v.z, v.w};
             const bool inLds = F.ldsOff[c] != 0xFFFFFFFFu;
             uint32_t* ctr = inLds ? fac + F.ldsOff[c] : out + F.outOff[c];

@@ -86,41 +86,54 @@ __global__ __launch_bounds__(FCM_THREADS) void k_filter_count_multi(const DevFil
 // threads while that stays within 40 KiB (four workgroups per CU), else one wave per workgroup (64 columns: 64 KiB).
 #define FMM_THREADS 256
 struct DevMaskOut { uint8_t* mask[INFX_MAX_PREFILTERS]; };
+// The four-document walk of k_filter_mask_multi and k_facets_filtered: thread tid of T takes group gi = documents [d0, d0 + 4) of n
+struct FiltGroup4 {
+    int64_t d0; bool have, full;       // the group exists; all four of its documents do
+    uint32_t dead;                     // byte j: document d0 + j is Deleted, or lies beyond the corpus
+    // four consecutive codes of a column: one 16-byte load in a full group, one by one in the corpus's partial last group (columns are not padded)
+    __device__ __forceinline__ uint4 load4(const uint32_t* __restrict__ col, int64_t n) const {
+        uint4 c = make_uint4(0, 0, 0, 0);
+        if (full) c = *(const uint4*)(col + d0);
+        else if (have) { c.x = col[d0]; if (d0 + 1 < n) c.y = col[d0 + 1]; if (d0 + 2 < n) c.z = col[d0 + 2]; }      // (d0 + 3 >= n in a partial group)
+        return c;
+    }
+};
+// forms the group and leaves the codes of the columns the programs read in codes[(u * 4 + j) * T + tid]: document j, column slot u — consecutive lanes, consecutive banks
+__device__ __forceinline__ FiltGroup4 filt_group4(int64_t gi, int64_t groups, int64_t n, const uint8_t* __restrict__ deleted, const DevCountCols& cc, const DevColumns& cols,
+                                                  uint32_t* codes, int tid, int T) {
+    FiltGroup4 g; g.d0 = gi * 4; g.have = gi < groups; g.full = g.have && g.d0 + 4 <= n; g.dead = 0;
+    if (!g.have) g.dead = 0x01010101u;
+    else if (g.full) { if (deleted) g.dead = *(const uint32_t*)(deleted + g.d0); }
+    else for (int j = 0; j < 4; j++) if (g.d0 + j >= n || (deleted && deleted[g.d0 + j])) g.dead |= 1u << (8 * j);
+    for (uint32_t u = 0; u < cc.nUsed; u++) {
+        const uint4 c = g.load4(cols.codes[cc.col[u]], n);
+        uint32_t* cu = codes + (size_t)u * 4u * T + tid;
+        cu[0] = c.x; cu[T] = c.y; cu[2 * T] = c.z; cu[3 * T] = c.w;
+    }
+    return g;
+}
 __global__ __launch_bounds__(FMM_THREADS) void k_filter_mask_multi(const DevFilter* __restrict__ progs, uint32_t K, DevCountCols cc, DevColumns cols, int32_t n,
                                                                     const uint8_t* __restrict__ deleted, DevMaskOut out, uint32_t* __restrict__ counts) {
     extern __shared__ __attribute__((aligned(16))) uint32_t fmm_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
-    uint32_t* codes = fmm_lds;                               // [(u * 4 + j) * T + tid]: document j of the thread's four, column slot u — consecutive lanes, consecutive banks
+    uint32_t* codes = fmm_lds;                               // the thread's codes (filt_group4)
     uint32_t* cnt = fmm_lds + (size_t)cc.nUsed * 4u * T;     // per-workgroup count of each program
     for (uint32_t k = tid; k < K; k += T) cnt[k] = 0;
     __syncthreads();
     const int64_t groups = ((int64_t)n + 3) >> 2;
     for (int64_t gb = (int64_t)blockIdx.x * T; gb < groups; gb += (int64_t)gridDim.x * T) {
-        const int64_t gi = gb + tid, d0 = gi * 4;
-        const bool have = gi < groups, full = have && d0 + 4 <= (int64_t)n;
-        uint32_t dead = 0;                                   // byte j: document d0 + j is Deleted, or lies beyond the corpus
-        if (!have) dead = 0x01010101u;
-        else if (full) { if (deleted) dead = *(const uint32_t*)(deleted + d0); }
-        else for (int j = 0; j < 4; j++) if (d0 + j >= (int64_t)n || (deleted && deleted[d0 + j])) dead |= 1u << (8 * j);
-        for (uint32_t u = 0; u < cc.nUsed; u++) {
-            const uint32_t* __restrict__ col = cols.codes[cc.col[u]];
-            uint4 c = make_uint4(0, 0, 0, 0);
-            if (full) c = *(const uint4*)(col + d0);
-            else if (have) { c.x = col[d0]; if (d0 + 1 < (int64_t)n) c.y = col[d0 + 1]; if (d0 + 2 < (int64_t)n) c.z = col[d0 + 2]; }      // (d0 + 3 >= n in a partial group)
-            uint32_t* cu = codes + (size_t)u * 4u * T + tid;
-            cu[0] = c.x; cu[T] = c.y; cu[2 * T] = c.z; cu[3 * T] = c.w;
-        }
+        const FiltGroup4 g = filt_group4(gb + tid, groups, n, deleted, cc, cols, codes, tid, T);
         for (uint32_t k = 0; k < K; k++) {
             const DevFilter f = progs[k];
             uint32_t word = 0, hits = 0;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const bool acc = filt_eval_codes(f, [&](uint32_t c) { return codes[((uint32_t)cc.slot[c] * 4u + j) * T + tid]; });
-                const bool hit = acc && !((dead >> (8 * j)) & 0xFFu);
+                const bool hit = acc && !((g.dead >> (8 * j)) & 0xFFu);
                 hits += (uint32_t)__popcll(__ballot(hit));
                 word |= (hit ? 0u : 1u) << (8 * j);
             }
-            if (have) *(uint32_t*)(out.mask[k] + d0) = word;
+            if (g.have) *(uint32_t*)(out.mask[k] + g.d0) = word;
             if ((tid & (WAVE - 1)) == 0 && hits) atomicAdd(&cnt[k], hits);
         }
     }

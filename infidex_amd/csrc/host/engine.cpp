@@ -145,6 +145,13 @@ struct CompiledFilter {
     uint32_t pins = 0;                      // installs that hold the entry: it is not evicted while > 0
     std::list<std::string>::iterator lru;
 };
+// the program of anything that holds ops, leaves and tables (a CompiledFilter, a copy taken out of the filter cache), as the device library takes it
+template <class F> static infx_filter_prog prog_of(const F& cf) {
+    infx_filter_prog P{};
+    P.ops = cf.ops.data(); P.leaves = cf.leaves.data(); P.tables = cf.tables.data();
+    P.nops = (uint32_t)cf.ops.size(); P.nleaves = (uint32_t)cf.leaves.size(); P.ntable_words = (uint32_t)cf.tables.size();
+    return P;
+}
 // per-query options of the session's batch (infx_engine_set_query_options): query i's MaxNumberOfRecordsToReturn (never above the call's row stride)
 // and EnableCoverage; the call's values for a session without options
 static inline int32_t qo_max(const infx_session* S, size_t i, int32_t mr) {
@@ -166,6 +173,7 @@ static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* ou
 static void clear_query_prefilters(infx_session* S);
 static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, std::vector<int>& builtSlots);
 static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots);
+static int32_t staged_failed(infx_session* S, std::vector<int>& builtSlots, int32_t rc);
 static void take_prefilter_counts(infx_session* S, uint32_t nq, const std::vector<int>& builtSlots);
 static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
@@ -1200,7 +1208,7 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
-    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); return rc; }
+    if (rc) return staged_failed(S, builtSlots, rc);
     take_prefilter_counts(S, nq, builtSlots);
     B.t3 = now_ms();
     // Kernel durations are resolved when somebody asks (infx_engine_session_last_timings): every hipEventElapsedTime is a HIP API call that queues behind the
@@ -2337,6 +2345,31 @@ int32_t infx_engine_restore_documents(infx_engine* e) {
     return e->indexed ? refresh_first_live(e) : INFX_OK;
 }
 
+// the facet columns: the first INFX_MAX_FACET_COLS facetable columns of the engine; *total_values = the sum of their dictionaries' sizes
+static std::vector<uint32_t> facet_columns(const infx_engine* e, size_t* total_values = nullptr) {
+    std::vector<uint32_t> cols; size_t total = 0;
+    for (size_t c = 0; c < e->columns.size() && cols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) { cols.push_back((uint32_t)c); total += e->columns[c].dict.size(); }
+    if (total_values) *total_values = total;
+    return cols;
+}
+typedef std::vector<std::pair<uint32_t, uint32_t>> FacetPairs;      // (code, count)
+// A column's (code, count) pairs as FacetBuilder lists them: empty strings are not facet values (FacetBuilder.cs:95-99, :170-174), count descending, then value
+// ascending (the column's rank), cut to 100
+static void order_facets(const filt::Column& C, FacetPairs& v) {
+    v.erase(std::remove_if(v.begin(), v.end(), [&](auto& x) { return x.first >= C.text.size() || C.text[x.first].empty(); }), v.end());
+    std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
+    if (v.size() > 100) v.resize(100);
+}
+// the readers' copies: up to cap pairs into codes / counts (returns their number); a message into out, cap (returns its length)
+static int32_t copy_pairs(const FacetPairs& v, uint32_t* codes, uint32_t* counts, int32_t cap) {
+    int32_t m = 0; for (auto& x : v) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
+    return m;
+}
+static int32_t copy_message(const std::string& t, char* out, int32_t cap) {
+    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
+    return (int32_t)t.size();
+}
+
 // ---- Infiscript post-filter + facets (config 5): Query.Filter / Query.EnableFacets (SearchEngine.cs:298-316) ------------------------------
 // One non-indexed document field for all documents (DocumentFields / Field.Value), by internal id: kind 1 int64, 2 double, 3 UTF-8 strings
 // (arena + n+1 offsets).  facetable = Field.Facetable.  After infx_engine_index_documents.
@@ -2447,7 +2480,7 @@ int32_t infx_engine_set_filter(infx_session* S, const char* expr, int32_t enable
         }
     }
     S->facetCols.clear();
-    if (enable_facets) for (size_t c = 0; c < e->columns.size() && S->facetCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) S->facetCols.push_back((uint32_t)c);
+    if (enable_facets) S->facetCols = facet_columns(e);
     int32_t rc = infx_stream_set_postfilter(S->stream, dev, (uint32_t)S->facetCols.size(), S->facetCols.data());
     if (rc) { g_eerr = infx_last_error(); return rc; }
     S->swFilter = expr != nullptr || enable_facets;
@@ -2462,22 +2495,18 @@ int32_t infx_engine_last_facets(infx_session* S, uint32_t nq, uint32_t qi, uint3
     std::vector<uint32_t> cd((size_t)S->e->postRows), ct(cd.size()); uint32_t n = 0;      // one (query, column) slice: at most the engine's post rows pairs
     if (infx_last_facets_of(S->stream, nq, qi, k, cd.data(), ct.data(), &n)) { g_eerr = infx_last_error(); return -1; }
     const filt::Column& C = S->e->columns[S->facetCols[k]];
-    std::vector<std::pair<uint32_t, uint32_t>> v;
-    for (uint32_t i = 0; i < n; i++) if (cd[i] < C.text.size() && !C.text[cd[i]].empty()) v.push_back({cd[i], ct[i]});     // empty strings are not facet values (:95-99)
-    std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
-    if (v.size() > 100) v.resize(100);
+    FacetPairs v;
+    for (uint32_t i = 0; i < n; i++) v.push_back({cd[i], ct[i]});
+    order_facets(C, v);
     if (col) *col = (int32_t)S->facetCols[k];
-    int32_t m = 0; for (auto& x : v) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
-    return m;
+    return copy_pairs(v, codes, counts, cap);
 }
 int32_t infx_engine_facet_column_count(infx_session* S) { return S ? (int32_t)S->facetCols.size() : -1; }
-// One column's value counts (one word per distinct value) as a facet list: null and empty values left out, count descending then value ascending in the row
-// facets' rank, cut to 100
-static std::vector<std::pair<uint32_t, uint32_t>> facet_list(const filt::Column& C, const uint32_t* counts) {
-    std::vector<std::pair<uint32_t, uint32_t>> v;
-    for (uint32_t code = 0; code < C.dict.size(); code++) if (counts[code] && !C.text[code].empty()) v.push_back({code, counts[code]});     // empty strings are not facet values (:170-174)
-    std::sort(v.begin(), v.end(), [&](auto& a, auto& b) { if (a.second != b.second) return a.second > b.second; return C.rank[a.first] < C.rank[b.first]; });
-    if (v.size() > 100) v.resize(100);
+// One column's value counts (one word per distinct value) as a facet list: the values that occur, ordered as the row facets are
+static FacetPairs facet_list(const filt::Column& C, const uint32_t* counts) {
+    FacetPairs v;
+    for (uint32_t code = 0; code < C.dict.size(); code++) if (counts[code]) v.push_back({code, counts[code]});
+    order_facets(C, v);
     return v;
 }
 // FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): value counts of every facetable column over all documents that are not
@@ -2490,7 +2519,7 @@ int32_t infx_engine_facets_all(infx_session* S, int32_t* ncols) {
     if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
     S->facAllCols.clear(); S->facAll.clear();
     size_t total = 0;
-    for (size_t c = 0; c < e->columns.size() && S->facAllCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) { S->facAllCols.push_back((uint32_t)c); total += e->columns[c].dict.size(); }
+    S->facAllCols = facet_columns(e, &total);
     if (ncols) *ncols = (int32_t)S->facAllCols.size();
     if (S->facAllCols.empty()) return INFX_OK;
     std::vector<uint32_t> counts(std::max<size_t>(total, 1));
@@ -2509,8 +2538,7 @@ int32_t infx_engine_facets_all(infx_session* S, int32_t* ncols) {
 int32_t infx_engine_facets_all_column(infx_session* S, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap) {
     if (!S || k >= S->facAll.size() || (cap > 0 && (!codes || !counts))) return -1;
     if (col) *col = (int32_t)S->facAllCols[k];
-    int32_t m = 0; for (auto& x : S->facAll[k]) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
-    return m;
+    return copy_pairs(S->facAll[k], codes, counts, cap);
 }
 
 // ---- Query.Boosts / Query.SortBy (SearchEngine.cs:355-359): ResultProcessor.ApplyBoosts / ApplySort on the device after the post-filter -------------
@@ -2572,12 +2600,6 @@ int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascendi
 }
 
 // ---- per-query options (Search(Query) for a batch of Query objects, each with its own options) ---------------------------------------------------
-static infx_filter_prog prog_of(const CompiledFilter& cf) {
-    infx_filter_prog P{};
-    P.ops = cf.ops.data(); P.leaves = cf.leaves.data(); P.tables = cf.tables.data();
-    P.nops = (uint32_t)cf.ops.size(); P.nleaves = (uint32_t)cf.leaves.size(); P.ntable_words = (uint32_t)cf.tables.size();
-    return P;
-}
 static void clear_query_options(infx_session* S) {
     if (!S->qo.on) return;
     { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, S->qo.pinned, -1); S->e->evict_filters(); }
@@ -2596,8 +2618,7 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.reject.assign(nq, 0); Q.facets.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string()); Q.filterExpr.assign(nq, std::string());
     std::vector<infx_query_post> post(nq); std::vector<infx_query_boost> boosts;
     std::vector<const CompiledFilter*> progs; std::unordered_map<std::string, int32_t> progIdx;
-    std::vector<uint32_t> facetCols;
-    for (size_t c = 0; c < e->columns.size() && facetCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) facetCols.push_back((uint32_t)c);
+    std::vector<uint32_t> facetCols = facet_columns(e);
     bool anyFacets = false;
     std::lock_guard<std::mutex> lk(e->filterMu);
     // per query: compile what it uses (a failure rejects that query alone); the table's programs to count come first
@@ -2727,9 +2748,7 @@ int32_t infx_engine_last_browse_stats(infx_session* S, uint32_t* groups, uint32_
 }
 int32_t infx_engine_query_error(infx_session* S, uint32_t qi, char* out, int32_t cap) {
     if (!S || qi >= S->lastErr.size()) return -1;
-    const std::string& t = S->lastErr[qi];
-    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
-    return (int32_t)t.size();
+    return copy_message(S->lastErr[qi], out, cap);
 }
 // ---- CoverageSetup: engine-wide (SearchEngine's coverageSetup: argument) and per query (Query.CoverageSetup) -----------------------------------------
 static const infx_coverage_setup COVERAGE_SETUP_DEFAULT = {2, 20, 2, 3, 7, 1, 0, 5, 0.2, 1, 1, 1, 1, 1, 1, 0, 254};
@@ -2900,18 +2919,26 @@ static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* ou
     }
     clear_query_prefilters(S);
 }
-// The mask slots of `exprs` (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: slots[k] for exprs[k]; the ones that have to be built are staged on
-// the stream as ONE build (infx_filter_masks) and listed in builtSlots — their counts land in S->preCountBuf, in that order, when the stream is next waited for.
-static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<std::string>& exprs, std::vector<int>& slots, std::vector<int>& builtSlots) {
+// a device call of a batch with staged masks failed: its message is kept, nothing stays staged
+static int32_t staged_failed(infx_session* S, std::vector<int>& builtSlots, int32_t rc) {
+    g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear();
+    return rc;
+}
+// The masks of `exprs` (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: masks[k] = the device flags of exprs[k]'s slot; the ones that have to be built
+// are staged on the stream as ONE build (infx_filter_masks) and listed in builtSlots — their counts land in S->preCountBuf, in that order, when the stream is next
+// waited for.  A failure leaves nothing staged.
+static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<std::string>& exprs, std::vector<uint8_t*>& masks, std::vector<int>& builtSlots) {
     const uint64_t ep = e->maskEpoch.load(); const uint64_t tick = ++S->preTick;
-    slots.assign(exprs.size(), -1); builtSlots.clear();
+    std::vector<int> slots(exprs.size(), -1);
+    masks.assign(exprs.size(), nullptr); builtSlots.clear();
+    auto bail = [&](int32_t rc) { unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; };
     S->preBuilt = S->preReused = S->preLaunches = 0;
     for (size_t k = 0; k < exprs.size(); k++)
         for (int i = 0; i < INFX_MAX_PREFILTERS; i++) { PreMask& M = S->preMask[i]; if (M.valid && M.epoch == ep && M.expr == exprs[k]) { slots[k] = i; M.lastUse = tick; S->preReused++; break; } }
     std::vector<infx_filter_prog> progs; std::vector<uint8_t*> ptrs;
     std::lock_guard<std::mutex> lk(e->filterMu);
     for (size_t k = 0; k < exprs.size(); k++) {
-        if (slots[k] >= 0) continue;
+        if (slots[k] >= 0) { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[k], &masks[k]); if (rc) return staged_failed(S, builtSlots, rc); continue; }
         int best = -1;      // a slot of an earlier epoch or an empty one first, else the least recently used that this batch does not use
         for (int i = 0; i < INFX_MAX_PREFILTERS; i++) {
             PreMask& M = S->preMask[i];
@@ -2921,17 +2948,16 @@ static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<
             const PreMask& Bm = S->preMask[best]; const bool bestStale = !Bm.valid || Bm.epoch != ep;
             if (stale != bestStale ? stale : (!stale && M.lastUse < Bm.lastUse)) best = i;
         }
-        if (best < 0) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch");
+        if (best < 0) return bail(efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch"));
         CompiledFilter* cf = nullptr;
-        { int32_t rc = compile_filter(e, exprs[k].c_str(), &cf, false); if (rc) return rc; }
-        uint8_t* p = nullptr;
-        { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &p); if (rc) { g_eerr = infx_last_error(); return rc; } }
+        { int32_t rc = compile_filter(e, exprs[k].c_str(), &cf, false); if (rc) return bail(rc); }
+        { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &masks[k]); if (rc) return staged_failed(S, builtSlots, rc); }
         PreMask& M = S->preMask[best]; M.expr = exprs[k]; M.epoch = ep; M.lastUse = tick; M.count = 0; M.valid = true;
-        slots[k] = best; builtSlots.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(p);
+        builtSlots.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(masks[k]);
     }
     if (!builtSlots.empty()) {
         int32_t rc = infx_filter_masks(S->stream, (uint32_t)progs.size(), progs.data(), ptrs.data(), S->preCountBuf);
-        if (rc) { g_eerr = infx_last_error(); for (int b : builtSlots) S->preMask[b].valid = false; builtSlots.clear(); return rc; }
+        if (rc) return staged_failed(S, builtSlots, rc);
         S->preBuilt = (uint32_t)builtSlots.size();
     }
     return INFX_OK;
@@ -2959,17 +2985,12 @@ static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, st
         of[i] = it->second;
     }
     if (exprs.empty()) return INFX_OK;
-    std::vector<int> slots;
-    { int32_t rc = acquire_masks(e, S, exprs, slots, builtSlots); if (rc) { unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; } }
+    std::vector<uint8_t*> found;
+    { int32_t rc = acquire_masks(e, S, exprs, found, builtSlots); if (rc) return rc; }
     std::vector<const uint8_t*> masks(nq, nullptr);
-    for (uint32_t i = 0; i < nq; i++) if (of[i] >= 0) {
-        uint8_t* p = nullptr;
-        int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[of[i]], &p);
-        if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; }
-        masks[i] = p;
-    }
+    for (uint32_t i = 0; i < nq; i++) if (of[i] >= 0) masks[i] = found[of[i]];
     int32_t rc = infx_stream_set_doc_masks(S->stream, nq, masks.data());
-    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; }
+    if (rc) return staged_failed(S, builtSlots, rc);
     return INFX_OK;
 }
 // After the batch: the counts of the masks it built have landed; each pre-filtered query's count
@@ -3004,14 +3025,12 @@ int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* o
     const uint64_t N = (uint64_t)e->ix.N;
     if (cap < N) return efail(INFX_EINVAL, "the mask holds one byte per indexed document");
     { std::lock_guard<std::mutex> lk(e->filterMu); CompiledFilter* cf = nullptr; int32_t rc = compile_filter(e, expr, &cf, false); if (rc) return rc; }
-    std::vector<int> slots, built;
-    { int32_t rc = acquire_masks(e, S, {std::string(expr)}, slots, built); if (rc) { unstage_prefilters(S, built); return rc; } }
+    std::vector<uint8_t*> masks; std::vector<int> built;
+    { int32_t rc = acquire_masks(e, S, {std::string(expr)}, masks, built); if (rc) return rc; }
     int32_t rc = infx_stream_wait(S->stream);      // builds what was staged
-    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); return rc; }
+    if (rc) return staged_failed(S, built, rc);
     take_prefilter_counts(S, 0, built);
-    uint8_t* p = nullptr;
-    rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[0], &p);
-    if (!rc && N) rc = infx_stream_copy(S->stream, out_bytes, p, N);
+    if (N) rc = infx_stream_copy(S->stream, out_bytes, masks[0], N);
     if (!rc) rc = infx_stream_wait(S->stream);
     if (rc) { g_eerr = infx_last_error(); return rc; }
     return INFX_OK;
@@ -3031,7 +3050,7 @@ int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* con
     if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
     S->ff.assign(k, FfAnswer());
     size_t total = 0;
-    for (size_t c = 0; c < e->columns.size() && S->ffCols.size() < INFX_MAX_FACET_COLS; c++) if (e->columns[c].facetable) { S->ffCols.push_back((uint32_t)c); total += e->columns[c].dict.size(); }
+    S->ffCols = facet_columns(e, &total);
     const uint64_t ep = e->maskEpoch.load();
     // the call's distinct expressions: from the cache, refused, or missing (compiled here; the programs are copied out of the filter cache, which other
     // sessions may evict from while the device counts)
@@ -3059,11 +3078,7 @@ int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* con
     for (size_t m0 = 0; m0 < miss.size(); m0 += INFX_MAX_PREFILTERS) {
         const uint32_t kk = (uint32_t)std::min<size_t>(INFX_MAX_PREFILTERS, miss.size() - m0);
         std::vector<infx_filter_prog> progs(kk);
-        for (uint32_t j = 0; j < kk; j++) {
-            const Missing& M = miss[m0 + j]; infx_filter_prog& P = progs[j]; P = infx_filter_prog{};
-            P.ops = M.ops.data(); P.leaves = M.leaves.data(); P.tables = M.tables.data();
-            P.nops = (uint32_t)M.ops.size(); P.nleaves = (uint32_t)M.leaves.size(); P.ntable_words = (uint32_t)M.tables.size();
-        }
+        for (uint32_t j = 0; j < kk; j++) progs[j] = prog_of(miss[m0 + j]);
         counts.resize(std::max<size_t>((size_t)kk * total, 1));
         int32_t rc = infx_facets_filtered(S->stream, kk, progs.data(), (uint32_t)S->ffCols.size(), S->ffCols.data(), counts.data(), totals.data());
         if (rc) { g_eerr = infx_last_error(); S->ff.clear(); S->ffCols.clear(); return rc; }
@@ -3092,8 +3107,7 @@ int32_t infx_engine_facets_filtered_column_count(infx_session* S) { return S ? (
 int32_t infx_engine_facets_filtered_column(infx_session* S, uint32_t which, uint32_t k, int32_t* col, uint32_t* codes, uint32_t* counts, int32_t cap) {
     if (!S || which >= S->ff.size() || !S->ff[which].r || k >= S->ff[which].r->lists.size() || k >= S->ffCols.size() || (cap > 0 && (!codes || !counts))) return -1;
     if (col) *col = (int32_t)S->ffCols[k];
-    int32_t m = 0; for (auto& x : S->ff[which].r->lists[k]) { if (m >= cap) break; codes[m] = x.first; counts[m] = x.second; m++; }
-    return m;
+    return copy_pairs(S->ff[which].r->lists[k], codes, counts, cap);
 }
 // the live documents expression `which` accepts (0 for a refused one, whose status is returned)
 int32_t infx_engine_facets_filtered_total(infx_session* S, uint32_t which, uint32_t* total) {
@@ -3104,9 +3118,7 @@ int32_t infx_engine_facets_filtered_total(infx_session* S, uint32_t which, uint3
 // the message of expression `which`'s refusal ("" if it was counted); returns its length, -1 out of range
 int32_t infx_engine_facets_filtered_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
     if (!S || which >= S->ff.size()) return -1;
-    const std::string& m = S->ff[which].err;
-    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", m.c_str());
-    return (int32_t)m.size();
+    return copy_message(S->ff[which].err, out, cap);
 }
 int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counted, uint32_t* cached, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
@@ -3158,19 +3170,14 @@ int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_li
             of[i] = it->second;
         }
     }
-    std::vector<int> slots, built;
-    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, slots, built); if (rc) { unstage_prefilters(S, built); S->lst.clear(); return rc; } }
+    std::vector<uint8_t*> masks; std::vector<int> built;
+    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, masks, built); if (rc) { S->lst.clear(); return rc; } }
     else S->preBuilt = S->preReused = S->preLaunches = 0;
     std::vector<infx_list_req> dr; std::vector<uint32_t> who;
     for (uint32_t i = 0; i < nreq; i++) {
         if (S->lst[i].status) continue;
         infx_list_req R{};
-        if (of[i] >= 0) {
-            uint8_t* p = nullptr;
-            int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[of[i]], &p);
-            if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); S->lst.clear(); return rc; }
-            R.mask = p;
-        }
+        if (of[i] >= 0) R.mask = masks[of[i]];
         R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
         dr.push_back(R); who.push_back(i);
     }
@@ -3178,7 +3185,7 @@ int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_li
     std::vector<int64_t> keys(std::max<size_t>(m, 1) * rows); std::vector<int32_t> docs(std::max<size_t>(m, 1) * rows); std::vector<uint32_t> codes(std::max<size_t>(m, 1) * rows);
     std::vector<uint32_t> counts(std::max<size_t>(m, 1), 0), totals(std::max<size_t>(m, 1), 0);
     int32_t rc = infx_list_ordered(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), counts.data(), totals.data());
-    if (rc) { g_eerr = infx_last_error(); unstage_prefilters(S, built); S->lst.clear(); return rc; }
+    if (rc) { S->lst.clear(); return staged_failed(S, built, rc); }
     take_prefilter_counts(S, 0, built);
     S->lstBuilt = S->preBuilt; S->lstReused = S->preReused;
     infx_last_list_stats(S->stream, &S->lstPasses, &S->lstLaunches);
@@ -3207,9 +3214,7 @@ int32_t infx_engine_list_total(infx_session* S, uint32_t which, uint32_t* total)
 }
 int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
     if (!S || which >= S->lst.size()) return -1;
-    const std::string& msg = S->lst[which].err;
-    if (out && cap > 0) snprintf(out, (size_t)cap, "%s", msg.c_str());
-    return (int32_t)msg.size();
+    return copy_message(S->lst[which].err, out, cap);
 }
 int32_t infx_engine_last_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");

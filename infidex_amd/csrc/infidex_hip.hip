@@ -22,7 +22,6 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
-#include <functional>
 #include <unordered_map>
 #include <algorithm>
 #include <map>
@@ -270,6 +269,62 @@ struct infx_filter {
     infx_index* ix; DevFilter d{}; uint32_t nops = 0, nleaves = 0; void *dOps = nullptr, *dLeaves = nullptr, *dTables = nullptr;
     std::vector<infx_filter_leaf> hLeaves;      // host copy of the leaves: the columns k_filter_count_multi loads for it
 };
+static int32_t check_filter_prog(infx_index* ix, uint32_t nops, const infx_filter_op* ops, uint32_t nleaves, const infx_filter_leaf* leaves, uint32_t ntable_words);
+
+// The filter programs of one launch sequence on their way to the device; nothing else knows how they are laid out.  An entry is either
+//   - packed: its ops, leaves and tables lie in `code`, each 16-byte aligned (opsOff / leavesOff / tablesOff: byte offsets into code), or
+//   - resident: an infx_filter, whose device copy is the program and whose hLeaves are its host leaves.
+// On the device a table is DevFilter[size()] and, wherever the caller puts it, the code the packed entries point into.  The usual blob is the table,
+// padded to 16 bytes, then the code (blob_bytes / put_blob, table_upload); the finalize places the two parts inside its own upload (put).
+struct ProgTable {
+    struct Entry { uint32_t nops, nleaves, opsOff, leavesOff, tablesOff; const infx_filter* resident; };
+    std::vector<Entry> progs; std::vector<uint8_t> code;
+    static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+    uint32_t size() const { return (uint32_t)progs.size(); }
+    void clear() { progs.clear(); code.clear(); }
+    void add(const infx_filter* f) { progs.push_back(Entry{0, 0, 0, 0, 0, f}); }
+    // replaces the table by programs [0, n), packed, each validated as infx_filter_create does
+    int32_t pack(infx_index* ix, uint32_t n, const infx_filter_prog* src) {
+        clear();
+        auto put = [&](const void* p, size_t bytes) { const size_t o = al16(code.size()); code.resize(o + bytes); if (bytes) std::memcpy(code.data() + o, p, bytes); return (uint32_t)o; };
+        for (uint32_t i = 0; i < n; i++) {
+            const infx_filter_prog& P = src[i];
+            if (!P.nops || !P.ops || (P.nleaves && (!P.leaves || !P.tables))) return fail(INFX_EINVAL, "null filter program%s");
+            { int32_t rc_ = check_filter_prog(ix, P.nops, P.ops, P.nleaves, P.leaves, P.ntable_words); if (rc_) return rc_; }
+            Entry Q{P.nops, P.nleaves, 0, 0, 0, nullptr};
+            Q.opsOff = put(P.ops, (size_t)P.nops * sizeof(infx_filter_op));
+            Q.leavesOff = put(P.leaves, (size_t)P.nleaves * sizeof(infx_filter_leaf));
+            Q.tablesOff = put(P.tables, (size_t)P.ntable_words * 4);
+            progs.push_back(Q);
+        }
+        if (code.size() > 0xFFFFFFF0ull) return fail(INFX_ECAPACITY, "the batch's filter programs exceed 4 GiB%s");
+        return INFX_OK;
+    }
+    // program p as the kernels read it, the code at dCode on the device
+    DevFilter dev(uint32_t p, const char* dCode) const {
+        const Entry& P = progs[p];
+        if (P.resident) return P.resident->d;
+        return DevFilter{(const infx_filter_op*)(dCode + P.opsOff), P.nops, (const infx_filter_leaf*)(dCode + P.leavesOff), P.nleaves, (const uint32_t*)(dCode + P.tablesOff)};
+    }
+    // adds the columns program p reads to cc, each once, in the order they are met (the kernels load a document's codes of these columns once for all programs)
+    void add_columns(DevCountCols& cc, uint32_t p) const {
+        const Entry& P = progs[p];
+        const infx_filter_leaf* L = P.resident ? P.resident->hLeaves.data() : (const infx_filter_leaf*)(code.data() + P.leavesOff);
+        const uint32_t nl = P.resident ? (uint32_t)P.resident->hLeaves.size() : P.nleaves;
+        for (uint32_t l = 0; l < nl; l++) {
+            const uint32_t c = L[l].col;
+            if (c < FILT_MAXCOL && !(cc.slot[c] < cc.nUsed && cc.col[cc.slot[c]] == c)) { cc.slot[c] = (uint8_t)cc.nUsed; cc.col[cc.nUsed++] = c; }
+        }
+    }
+    DevCountCols columns(uint32_t first, uint32_t n) const { DevCountCols cc{}; for (uint32_t p = 0; p < n; p++) add_columns(cc, first + p); return cc; }
+    size_t table_bytes() const { return progs.size() * sizeof(DevFilter); }
+    void put(uint8_t* hTable, uint8_t* hCode, const char* dCode) const {
+        for (uint32_t p = 0; p < size(); p++) { const DevFilter f = dev(p, dCode); std::memcpy(hTable + (size_t)p * sizeof(DevFilter), &f, sizeof f); }
+        if (!code.empty()) std::memcpy(hCode, code.data(), code.size());
+    }
+    size_t blob_bytes() const { return al16(table_bytes()) + code.size(); }
+    void put_blob(uint8_t* h, const char* d) const { put(h, h + al16(table_bytes()), d + al16(table_bytes())); }
+};
 
 struct infx_stream {
     infx_index* ix;
@@ -281,18 +336,17 @@ struct infx_stream {
     // boosts / sort-by (infx_stream_set_boosts / _set_sort): applied after the post-filter (k_postproc)
     infx_filter* boosts[INFX_MAX_BOOSTS] = {}; int32_t boostStrength[INFX_MAX_BOOSTS] = {}; uint32_t nBoost = 0;
     uint32_t sortCol = 0; bool sortOn = false, sortAsc = false;
-    // per-query post-processing of the NEXT batch (infx_stream_set_query_post), consumed by its finalize: the batch's programs packed into one blob
-    // (opsOff / leavesOff / tablesOff: byte offsets into qpCode), the boost list, one descriptor per query, the programs [0, qpNCount) to count
-    struct QpProg { uint32_t nops, nleaves, opsOff, leavesOff, tablesOff; };
+    // per-query post-processing of the NEXT batch (infx_stream_set_query_post), consumed by its finalize: the batch's programs,
+    // the boost list, one descriptor per query, the programs [0, qpNCount) to count
     bool qpOn = false; uint32_t qpNq = 0, qpNFacet = 0, qpFacetCols[INFX_MAX_FACET_COLS] = {}, qpNCount = 0; uint32_t* qpCountsOut = nullptr;
-    std::vector<QpProg> qpProgs; std::vector<uint8_t> qpCode; std::vector<DevQBoost> qpBoosts; std::vector<DevQPost> qpDesc; DevCountCols qpCols{};
+    ProgTable qpTable; std::vector<DevQBoost> qpBoosts; std::vector<DevQPost> qpDesc;
     uint32_t lastCountK = 0, lastCountLaunches = 0;     // the filter programs the last finalize counted, and its k_filter_count_multi launches
     void* dPostBlob = nullptr; size_t capPostBlob = 0;     // the batch's DevPostBatch + program table + boost list + descriptors (+ packed programs)
     void* dQCount = nullptr; size_t capQCount = 0;
-    // pre-filter masks: the stream's mask slots (infx_stream_mask_slot), a staged build (infx_filter_masks: programs packed as qpCode is, enqueued by the next
+    // pre-filter masks: the stream's mask slots (infx_stream_mask_slot), a staged build (infx_filter_masks, enqueued by the next
     // batch or by infx_stream_wait), the per-query flags of the next batch (infx_stream_set_doc_masks) and their device table (DevIndex::qDeleted while qDelOn)
     uint8_t* dMask[INFX_MAX_PREFILTERS] = {}; size_t capMask[INFX_MAX_PREFILTERS] = {};
-    bool mkStaged = false; std::vector<QpProg> mkProgs; std::vector<uint8_t> mkCode; DevCountCols mkCols{}; DevMaskOut mkOut{}; uint32_t* mkCountsOut = nullptr;
+    bool mkStaged = false; ProgTable mkTable; DevMaskOut mkOut{}; uint32_t* mkCountsOut = nullptr;
     void* dMaskBlob = nullptr; size_t capMaskBlob = 0; void* dMaskCnt = nullptr; size_t capMaskCnt = 0;
     uint32_t lastMaskBuilt = 0, lastMaskLaunches = 0;
     std::vector<const uint8_t*> docMasks; void* dQDel = nullptr; size_t capQDel = 0; bool qDelOn = false;
@@ -558,6 +612,34 @@ struct PlanStream {
 #define UP(dst, src, n) do { int32_t rc_ = up(s, (dst), (src), (n)); if (rc_) return rc_; } while (0)
 #define DOWN(dst, src, n) do { int32_t rc_ = down(s, (dst), (src), (n)); if (rc_) return rc_; } while (0)
 #define SYNC() do { int32_t rc_ = stream_sync(s); if (rc_) return rc_; } while (0)
+// the table as one blob in *buf, grown to fit: one upload
+static int32_t table_upload(infx_stream* s, const ProgTable& T, void** buf, size_t* cap) {
+    const size_t total = T.blob_bytes();
+    { int32_t rc_ = grow(s, buf, cap, total); if (rc_) return rc_; }
+    std::vector<uint8_t> H(total, 0);
+    T.put_blob(H.data(), (const char*)*buf);
+    return up(s, *buf, H.data(), total);
+}
+// Columns are indexed by GLOBAL internal id: whatever reads them by document needs every uploaded column (col < 0), or column col, to hold documents [0, n)
+#define COLS_COVER_CORPUS "a column holds fewer rows than the corpus has documents%s"
+#define COLS_COVER_COUNTED "a column holds fewer rows than the counted documents%s"
+static int32_t columns_cover(const infx_index* ix, int64_t n, const char* msg, int col = -1) {
+    for (int c = std::max(col, 0); c < (col < 0 ? FILT_MAXCOL : col + 1); c++)
+        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max<int64_t>(n, 0)) return fail(INFX_EINVAL, msg);
+    return INFX_OK;
+}
+static DevColumns dev_columns(const infx_index* ix) { DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c]; return cols; }
+// Raises kernel fn's dynamic-LDS limit for a launch of lds bytes on `device`, when that is more than the 64 KiB every kernel may have.  Sessions launch from
+// several threads: the attribute is raised under a lock, and only past its high-water mark — one mark per (device, function), because a function's
+// attributes belong to the device that is current when they are set.
+static hipError_t lds_limit(const void* fn, int device, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    static std::mutex mu; static std::map<std::pair<int, const void*>, size_t> mark;
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& hw = mark[{device, fn}];
+    if (lds > hw) { const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; hw = lds; }
+    return hipSuccess;
+}
 
 template <int R> static void launch_union(infx_stream* s, uint32_t nv, const uint32_t* dBeg, const uint32_t* dEnd, const int32_t* dMembers, uint32_t* dRangeCount,
                                             const unsigned long long* dBase, int32_t* outDocs) {
@@ -1867,33 +1949,21 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
 #define FCM_MAXGRID 2048
 static int32_t count_enqueue(infx_stream* s, const DevFilter* dProgs, uint32_t K, const DevCountCols& cc, int32_t docBase, int32_t n, uint32_t* dCounts) {
     infx_index* ix = s->ix;
-    for (int c = 0; c < FILT_MAXCOL; c++)       // columns are indexed by GLOBAL internal id: every uploaded column must cover the counted range
-        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)docBase + (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the counted documents%s");
+    { int32_t rc_ = columns_cover(ix, (int64_t)docBase + std::max(n, 0), COLS_COVER_COUNTED); if (rc_) return rc_; }
     HIPCHK(hipMemsetAsync(dCounts, 0, (size_t)K * 4, s->st));
     s->lastCountK = K; s->lastCountLaunches = 0;
     if (n <= 0 || !K) return INFX_OK;
-    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+    const DevColumns cols = dev_columns(ix);
     const int grid = (int)std::min<int64_t>(FCM_MAXGRID, ((int64_t)n + FCM_THREADS - 1) / FCM_THREADS);
     for (uint32_t k0 = 0; k0 < K; k0 += FCM_MAXK) {
         const uint32_t k = std::min(FCM_MAXK, K - k0);
         const size_t lds = ((size_t)k + (size_t)cc.nUsed * FCM_THREADS) * 4;
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_filter_count_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(lds_limit((const void*)k_filter_count_multi, ix->cfg.device, lds));
         k_filter_count_multi<<<grid, FCM_THREADS, lds, s->st>>>(dProgs + k0, k, cc, cols, docBase, n, ix->d.deleted, dCounts + k0);
         HIPCHK(hipGetLastError());
         s->lastCountLaunches++;
     }
     return INFX_OK;
-}
-// the columns programs [0, k) read, each once (k_filter_count_multi loads a document's codes of these columns once for all k programs)
-static DevCountCols count_columns(const infx_filter_leaf* const* leaves, const uint32_t* nleaves, uint32_t k) {
-    DevCountCols cc{};
-    for (int c = 0; c < FILT_MAXCOL; c++) cc.slot[c] = 0;
-    bool seen[FILT_MAXCOL] = {};
-    for (uint32_t p = 0; p < k; p++) for (uint32_t l = 0; l < nleaves[p]; l++) {
-        const uint32_t c = leaves[p][l].col;
-        if (c < FILT_MAXCOL && !seen[c]) { seen[c] = true; cc.slot[c] = (uint8_t)cc.nUsed; cc.col[cc.nUsed++] = c; }
-    }
-    return cc;
 }
 
 // ---- pre-filter masks (k_filter_mask_multi) ----
@@ -1904,43 +1974,28 @@ static int32_t mask_flush(infx_stream* s) {
     if (!s->mkStaged) return INFX_OK;
     s->mkStaged = false;
     infx_index* ix = s->ix;
-    const uint32_t K = (uint32_t)s->mkProgs.size();
+    const uint32_t K = s->mkTable.size();
     const int32_t n = ix->d.totalDocs;
     s->lastMaskBuilt = K; s->lastMaskLaunches = 0;
     if (!K) return INFX_OK;
-    for (int c = 0; c < FILT_MAXCOL; c++)
-        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS); if (rc_) return rc_; }
     for (uint32_t k = 0; k < K; k++) {      // the kernel stores whole dwords up to the padded size
         const int slot = mask_slot_of(s, s->mkOut.mask[k]);
         if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a mask buffer is not a mask slot of this stream, or was made for a smaller corpus%s");
     }
-    const size_t oCode = ((size_t)K * sizeof(DevFilter) + 15) & ~(size_t)15, total = oCode + s->mkCode.size();
-    GROW(s->dMaskBlob, s->capMaskBlob, total);
+    { int32_t rc_ = table_upload(s, s->mkTable, &s->dMaskBlob, &s->capMaskBlob); if (rc_) return rc_; }
     GROW(s->dMaskCnt, s->capMaskCnt, (size_t)INFX_MAX_PREFILTERS * 4);
-    char* D = (char*)s->dMaskBlob;
-    std::vector<uint8_t> H(total, 0);
-    for (uint32_t i = 0; i < K; i++) {
-        const auto& P = s->mkProgs[i];
-        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
-        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
-    }
-    if (!s->mkCode.empty()) std::memcpy(H.data() + oCode, s->mkCode.data(), s->mkCode.size());
-    UP(D, H.data(), total);
     HIPCHK(hipMemsetAsync(s->dMaskCnt, 0, (size_t)K * 4, s->st));
     if (n > 0) {
-        DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
-        const DevCountCols& cc = s->mkCols;
+        const DevColumns cols = dev_columns(ix);
+        const DevCountCols cc = s->mkTable.columns(0, K);
         // 256 threads while four workgroups' LDS fit a CU (40 KiB each), else one wave per workgroup (64 columns: 64 KiB)
         const int threads = ((size_t)cc.nUsed * 4 * FMM_THREADS + K) * 4 <= 40 * 1024 ? FMM_THREADS : WAVE;
         const size_t lds = ((size_t)cc.nUsed * 4 * threads + K) * 4;
         const int64_t groups = ((int64_t)n + 3) / 4;
         const int grid = (int)std::min<int64_t>(FCM_MAXGRID, (groups + threads - 1) / threads);
-        {   // sessions launch from several threads: the attribute is raised under a lock, and only past its high-water mark
-            static std::mutex mu; static size_t attr = 0;
-            std::lock_guard<std::mutex> lk(mu);
-            if (lds > 64 * 1024 && lds > attr) { HIPCHK(hipFuncSetAttribute((const void*)k_filter_mask_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr = lds; }
-        }
-        k_filter_mask_multi<<<grid, threads, lds, s->st>>>((const DevFilter*)D, K, cc, cols, n, ix->d.deleted, s->mkOut, (uint32_t*)s->dMaskCnt);
+        HIPCHK(lds_limit((const void*)k_filter_mask_multi, ix->cfg.device, lds));
+        k_filter_mask_multi<<<grid, threads, lds, s->st>>>((const DevFilter*)s->dMaskBlob, K, cc, cols, n, ix->d.deleted, s->mkOut, (uint32_t*)s->dMaskCnt);
         HIPCHK(hipGetLastError());
         s->lastMaskLaunches = 1;
     }
@@ -1971,29 +2026,28 @@ static int32_t stage_doc_masks(infx_stream* s, uint32_t nd, uint32_t nq, const i
 
 // The batch's browse queries (s->browseQ; browse.hip.inc): grouped by filter program, all groups answered by one ordered scan of the corpus, which
 // also counts the ncount programs whose NumberOfDocumentsInFilter the batch needs (into s->dQCount — k_filter_count_multi is not launched for such a
-// batch).  filterOf(q) = the program of query q or -1; leavesOf(p) = host leaves of program p.  Enqueued after k_finalize, before k_postfilter.
+// batch).  T: the batch's program table, its code at dCode; desc[q * descStride].filter = the program of query q or -1.  Enqueued after k_finalize, before k_postfilter.
 #define BRW_MAXG 256u           // groups per k_browse_scan launch: at 256 programs a launch spends ~99 % of its time evaluating, so reading
                                 // the codes again for the next 256 costs nothing measurable, and the per-range counts of a launch stay at 2 MB
 #define BRW_MAXRANGES 2048
-static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& progs, uint32_t ncount, int32_t max_results, bool ties, const std::function<int32_t(uint32_t)>& filterOf,
-                              const std::function<std::pair<const infx_filter_leaf*, uint32_t>(int32_t)>& leavesOf) {
+static int32_t browse_enqueue(infx_stream* s, const ProgTable& T, const char* dCode, const DevQPost* desc, uint32_t descStride, uint32_t ncount, int32_t max_results, bool ties) {
     infx_index* ix = s->ix;
     const int32_t n = ix->d.totalDocs;
-    for (int c = 0; c < FILT_MAXCOL; c++) if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS); if (rc_) return rc_; }
     static const bool earlyStop = [] { const char* e = getenv("INFX_BROWSE_EARLY_STOP"); return !(e && e[0] == '0'); }();
     const uint32_t rowStride = ix->postRows;       // rows a group can hand out: the stride of rowDocs
     std::vector<DevBrowseGroup> groups; std::vector<DevBrowseQuery> bq; std::unordered_map<int32_t, uint32_t> groupOf;
     for (auto& b : s->browseQ) {
-        const int32_t prog = filterOf(b.first);
+        const int32_t prog = desc[(size_t)b.first * descStride].filter;
         auto it = groupOf.find(prog);
-        if (it == groupOf.end()) { it = groupOf.emplace(prog, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{prog >= 0 ? progs[(size_t)prog] : DevFilter{}, prog, 0u, 0u, 0u}); }
+        if (it == groupOf.end()) { it = groupOf.emplace(prog, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{prog >= 0 ? T.dev((uint32_t)prog, dCode) : DevFilter{}, prog, 0u, 0u, 0u}); }
         const uint32_t rows = std::min<uint32_t>(std::min<uint32_t>(b.second, (uint32_t)max_results), rowStride);
         groups[it->second].rows = std::max(groups[it->second].rows, rows);
         bq.push_back(DevBrowseQuery{b.first, it->second, rows, 0u});
     }
     for (uint32_t k = 0; k < ncount; k++) {      // the programs to count: those no browse query uses are groups without rows
         auto it = groupOf.find((int32_t)k);
-        if (it == groupOf.end()) { it = groupOf.emplace((int32_t)k, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{progs[k], (int32_t)k, 0u, 0u, 0u}); }
+        if (it == groupOf.end()) { it = groupOf.emplace((int32_t)k, (uint32_t)groups.size()).first; groups.push_back(DevBrowseGroup{T.dev(k, dCode), (int32_t)k, 0u, 0u, 0u}); }
         groups[it->second].flags |= BRW_COUNT; groups[it->second].countIdx = k;
     }
     const uint32_t G = (uint32_t)groups.size();
@@ -2012,20 +2066,19 @@ static int32_t browse_enqueue(infx_stream* s, const std::vector<DevFilter>& prog
     uint32_t *dCnt = (uint32_t*)W, *dPre = (uint32_t*)(W + oPre), *dTot = (uint32_t*)(W + oTot), *dOwn = (uint32_t*)(W + oOwn); int32_t* dRows = (int32_t*)(W + oRows);
     if (ncount) { GROW(s->dQCount, s->capQCount, (size_t)ncount * 4); HIPCHK(hipMemsetAsync(s->dQCount, 0, (size_t)ncount * 4, s->st)); }
     if (dup) HIPCHK(hipMemsetAsync(dOwn, 0, (size_t)G * 4, s->st));
-    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
+    const DevColumns cols = dev_columns(ix);
     s->lastBrowseGroups = G; s->lastBrowseLaunches = 0;
     for (uint32_t g0 = 0; g0 < G; g0 += BRW_MAXG) {
         const uint32_t g = std::min(BRW_MAXG, G - g0);
-        std::vector<const infx_filter_leaf*> lv; std::vector<uint32_t> nl;
-        for (uint32_t i = 0; i < g; i++) if (groups[g0 + i].prog >= 0) { auto L = leavesOf(groups[g0 + i].prog); lv.push_back(L.first); nl.push_back(L.second); }
-        const DevCountCols cc = count_columns(lv.data(), nl.data(), (uint32_t)lv.size());
+        DevCountCols cc{};
+        for (uint32_t i = 0; i < g; i++) if (groups[g0 + i].prog >= 0) T.add_columns(cc, (uint32_t)groups[g0 + i].prog);
         const size_t lds = ((size_t)g * (dup ? 2 : 1) + (size_t)cc.nUsed * BRW_THREADS * (dup ? 2 : 1)) * 4;
         if (dup) {
-            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_browse_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(lds_limit((const void*)k_browse_scan<true>, ix->cfg.device, lds));
             k_browse_scan<true><<<nRanges, BRW_THREADS, lds, s->st>>>(dGroups + g0, g, cc, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, ix->firstLive, earlyStop ? 1 : 0,
                                                                        dCnt + (size_t)g0 * nRanges, dOwn + g0);
         } else {
-            if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_browse_scan<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(lds_limit((const void*)k_browse_scan<false>, ix->cfg.device, lds));
             k_browse_scan<false><<<nRanges, BRW_THREADS, lds, s->st>>>(dGroups + g0, g, cc, cols, n, (uint32_t)tiles, nRanges, ix->d.deleted, nullptr, earlyStop ? 1 : 0,
                                                                         dCnt + (size_t)g0 * nRanges, nullptr);
         }
@@ -2101,48 +2154,46 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         if (!ix->d.docKeyAll) { s->browseQ.clear(); return fail(INFX_EINVAL, "index not uploaded%s"); }
     }
     if (launchPF || launchPP) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
-    DevColumns cols; for (int c = 0; c < FILT_MAXCOL; c++) cols.codes[c] = ix->colCodes[c];
-    const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr;
-    std::vector<DevFilter> progs;       // the batch's program table (device pointers)
+    const DevColumns cols = dev_columns(ix);
+    const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr; const char* dCode = nullptr;
+    // the batch's program table, boost list and descriptors: the staged per-query ones, or the session-wide filters (resident entries) behind one shared descriptor
+    ProgTable sprogs; std::vector<DevQBoost> sboost; std::vector<DevQPost> sdesc;
+    const ProgTable& T = qp ? s->qpTable : sprogs;
+    const std::vector<DevQBoost>& boosts = qp ? s->qpBoosts : sboost; const std::vector<DevQPost>& desc = qp ? s->qpDesc : sdesc;
+    const uint32_t descStride = qp ? 1u : 0u;
     if (launchPF || launchPP || ncount) {       // the batch's DevPostBatch, program table, boost list and descriptors (+ the packed per-query programs): one upload
-        std::vector<DevQBoost> sboost; std::vector<DevQPost> sdesc;
         if (!qp) {
             DevQPost D{}; D.filter = -1; D.sortCol = 0;
-            if (s->postFilter) { D.filter = (int32_t)progs.size(); progs.push_back(s->postFilter->d); }
+            if (s->postFilter) { D.filter = (int32_t)sprogs.size(); sprogs.add(s->postFilter); }
             if (s->nFacet) D.flags |= QP_FACETS;
             D.boostOff = 0; D.nboost = s->nBoost;
-            for (uint32_t b = 0; b < s->nBoost; b++) { sboost.push_back(DevQBoost{(int32_t)progs.size(), s->boostStrength[b]}); progs.push_back(s->boosts[b]->d); }
+            for (uint32_t b = 0; b < s->nBoost; b++) { sboost.push_back(DevQBoost{(int32_t)sprogs.size(), s->boostStrength[b]}); sprogs.add(s->boosts[b]); }
             if (s->sortOn) { D.flags |= QP_SORT | (s->sortAsc ? QP_ASC : 0u); D.sortCol = s->sortCol; }
             if (wideShared) D.flags |= QP_WIDE;
             sdesc.push_back(D);
         }
-        const std::vector<DevQBoost>& boosts = qp ? s->qpBoosts : sboost; const std::vector<DevQPost>& desc = qp ? s->qpDesc : sdesc;
-        const size_t nprog = qp ? s->qpProgs.size() : progs.size();
-        auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-        const size_t oProgs = al(sizeof(DevPostBatch)), oBoosts = al(oProgs + nprog * sizeof(DevFilter)), oDesc = al(oBoosts + boosts.size() * sizeof(DevQBoost));
-        const size_t oCode = al(oDesc + desc.size() * sizeof(DevQPost)), total = oCode + (qp ? s->qpCode.size() : 0);
+        auto al = ProgTable::al16;
+        const size_t oProgs = al(sizeof(DevPostBatch)), oBoosts = al(oProgs + T.table_bytes()), oDesc = al(oBoosts + boosts.size() * sizeof(DevQBoost));
+        const size_t oCode = al(oDesc + desc.size() * sizeof(DevQPost)), total = oCode + T.code.size();
         GROW(s->dPostBlob, s->capPostBlob, total);
         char* D = (char*)s->dPostBlob;
-        if (qp) for (const auto& P : s->qpProgs)
-            progs.push_back(DevFilter{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)});
         DevPostBatch pb{};
-        pb.progs = (const DevFilter*)(D + oProgs); pb.boosts = (const DevQBoost*)(D + oBoosts); pb.desc = (const DevQPost*)(D + oDesc); pb.descStride = qp ? 1u : 0u;
+        pb.progs = (const DevFilter*)(D + oProgs); pb.boosts = (const DevQBoost*)(D + oBoosts); pb.desc = (const DevQPost*)(D + oDesc); pb.descStride = descStride;
         for (int c = 0; c < FILT_MAXCOL; c++) pb.rank[c] = ix->colRankOk[c] ? ix->colRank[c] : nullptr;
         pb.keys = (long long*)s->dFKeys; pb.scores = (float*)s->dFScores; pb.ties = ties ? (uint8_t*)s->dFTies : nullptr; pb.docs = (int32_t*)s->dFDocs;
         pb.counts = (uint32_t*)s->dFCounts; pb.flags = (uint32_t*)s->dFFlags; pb.stride = max_results;
         pb.fqs = browse ? (const infx_fused_query*)s->dFQ : nullptr;
         std::vector<uint8_t> H(total, 0);
         std::memcpy(H.data(), &pb, sizeof pb);
-        if (nprog) std::memcpy(H.data() + oProgs, progs.data(), nprog * sizeof(DevFilter));
+        T.put(H.data() + oProgs, H.data() + oCode, D + oCode);
         if (!boosts.empty()) std::memcpy(H.data() + oBoosts, boosts.data(), boosts.size() * sizeof(DevQBoost));
         if (!desc.empty()) std::memcpy(H.data() + oDesc, desc.data(), desc.size() * sizeof(DevQPost));
-        if (qp && !s->qpCode.empty()) std::memcpy(H.data() + oCode, s->qpCode.data(), s->qpCode.size());
         UP(D, H.data(), total);
-        dPB = (const DevPostBatch*)D; dProgs = (const DevFilter*)(D + oProgs);
+        dPB = (const DevPostBatch*)D; dProgs = (const DevFilter*)(D + oProgs); dCode = D + oCode;
     }
     if (ncount && !browse) {       // Filter.NumberOfDocumentsInFilter of the expressions this batch uses first, over the whole corpus (every shard holds the whole columns)
         GROW(s->dQCount, s->capQCount, (size_t)ncount * 4);
-        { int32_t rc_ = count_enqueue(s, dProgs, ncount, s->qpCols, 0, ix->d.totalDocs, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+        { int32_t rc_ = count_enqueue(s, dProgs, ncount, T.columns(0, ncount), 0, ix->d.totalDocs, (uint32_t*)s->dQCount); if (rc_) return rc_; }
         DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
     }
     {   // the per-query truncation records (infx_stream_set_coverage, consumed here); the defaults stay on the device from one batch to the next
@@ -2161,11 +2212,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
                                                 (const infx_finalize_setup*)s->dFin);
     HIPCHK(hipGetLastError());
     if (browse) {
-        int32_t rc_;
-        if (qp) rc_ = browse_enqueue(s, progs, ncount, max_results, ties, [&](uint32_t q) { return s->qpDesc[q].filter; },
-                                     [&](int32_t p) { const auto& P = s->qpProgs[(size_t)p]; return std::make_pair((const infx_filter_leaf*)(s->qpCode.data() + P.leavesOff), P.nleaves); });
-        else rc_ = browse_enqueue(s, progs, 0, max_results, ties, [&](uint32_t) { return s->postFilter ? 0 : -1; },
-                                  [&](int32_t) { return std::make_pair((const infx_filter_leaf*)s->postFilter->hLeaves.data(), (uint32_t)s->postFilter->hLeaves.size()); });
+        const int32_t rc_ = browse_enqueue(s, T, dCode, desc.data(), descStride, ncount, max_results, ties);
         s->browseQ.clear();
         if (rc_) return rc_;
         if (ncount) DOWN(s->qpCountsOut, s->dQCount, (size_t)ncount * 4);
@@ -2727,12 +2774,10 @@ int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count) {
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
     // k_filter_count_multi with a one-entry program table (the filter's device copy) over this shard's documents
-    GROW(s->dPostBlob, s->capPostBlob, sizeof(DevFilter));
+    ProgTable T; T.add(f);
+    { int32_t rc_ = table_upload(s, T, &s->dPostBlob, &s->capPostBlob); if (rc_) return rc_; }
     GROW(s->dQCount, s->capQCount, 4);
-    UP(s->dPostBlob, &f->d, sizeof(DevFilter));
-    const infx_filter_leaf* lv = f->hLeaves.data(); const uint32_t nl = (uint32_t)f->hLeaves.size();
-    const DevCountCols cc = count_columns(&lv, &nl, 1);
-    { int32_t rc_ = count_enqueue(s, (const DevFilter*)s->dPostBlob, 1, cc, ix->d.docBase, ix->d.N, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+    { int32_t rc_ = count_enqueue(s, (const DevFilter*)s->dPostBlob, 1, T.columns(0, 1), ix->d.docBase, ix->d.N, (uint32_t*)s->dQCount); if (rc_) return rc_; }
     DOWN(count, s->dQCount, 4);
     SYNC();
     return INFX_OK;
@@ -2740,8 +2785,7 @@ int32_t infx_filter_count(infx_stream* s, infx_filter* f, uint32_t* count) {
 int32_t infx_stream_set_postfilter(infx_stream* s, infx_filter* f, uint32_t nfacet, const uint32_t* facet_cols) {
     if (!s || nfacet > INFX_MAX_FACET_COLS || (nfacet && !facet_cols) || (f && f->ix != s->ix)) return fail(INFX_EINVAL, "bad post-filter arguments%s");
     for (uint32_t c = 0; c < nfacet; c++) if (facet_cols[c] >= FILT_MAXCOL || !s->ix->colCodes[facet_cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
-    for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids: a column shorter than the corpus would be read out of bounds
-        if (s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    { int32_t rc_ = columns_cover(s->ix, s->ix->d.totalDocs, COLS_COVER_CORPUS); if (rc_) return rc_; }      // rows carry GLOBAL internal ids
     if (s->qpOn && (f || nfacet)) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->postFilter = f; s->nFacet = nfacet;
     for (uint32_t c = 0; c < INFX_MAX_FACET_COLS; c++) s->facetCols[c] = c < nfacet ? facet_cols[c] : 0;
@@ -2764,8 +2808,7 @@ int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f
     uint32_t m = 0;
     for (uint32_t i = 0; i < n; i++) if (f[i]) { if (f[i]->ix != s->ix) return fail(INFX_EINVAL, "a boost filter belongs to another index%s"); m++; }
     if (m > INFX_MAX_BOOSTS) return fail(INFX_ECAPACITY, "more than INFX_MAX_BOOSTS boosts with a filter%s");
-    for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids: a column shorter than the corpus would be read out of bounds
-        if (m && s->ix->colCodes[c] && s->ix->colDocs[c] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    if (m) { int32_t rc_ = columns_cover(s->ix, s->ix->d.totalDocs, COLS_COVER_CORPUS); if (rc_) return rc_; }      // rows carry GLOBAL internal ids
     if (s->qpOn && m) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->nBoost = 0;
     for (uint32_t i = 0; i < n; i++) if (f[i]) { s->boosts[s->nBoost] = f[i]; s->boostStrength[s->nBoost] = strengths[i]; s->nBoost++; }
@@ -2776,31 +2819,13 @@ int32_t infx_stream_set_sort(infx_stream* s, uint32_t col, int32_t ascending, in
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (enabled && col != 0xFFFFFFFFu) {
         if (col >= FILT_MAXCOL || !s->ix->colCodes[col] || !s->ix->colRankOk[col]) return fail(INFX_EINVAL, "sort column or its rank was not uploaded%s");
-        if (s->ix->colDocs[col] < (uint32_t)s->ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        { int32_t rc_ = columns_cover(s->ix, s->ix->d.totalDocs, COLS_COVER_CORPUS, (int)col); if (rc_) return rc_; }
     }
     if (s->qpOn && enabled) return fail(INFX_EINVAL, "per-query options are installed on this stream%s");
     s->sortOn = enabled != 0; s->sortCol = enabled ? col : 0; s->sortAsc = enabled && ascending != 0;
     return INFX_OK;
 }
 // ---- per-query post-processing (k_postfilter / k_postproc with one descriptor per query) + k_filter_count_multi ----------------------------------
-// packs programs [0, n) into one blob (ops, leaves, tables of each, 16-byte aligned), validated as infx_filter_create does
-static int32_t pack_progs(infx_index* ix, uint32_t n, const infx_filter_prog* progs, std::vector<infx_stream::QpProg>& out, std::vector<uint8_t>& code) {
-    out.clear(); code.clear();
-    auto put = [&](const void* p, size_t bytes) { const size_t o = (code.size() + 15) & ~(size_t)15; code.resize(o + bytes); if (bytes) std::memcpy(code.data() + o, p, bytes); return (uint32_t)o; };
-    for (uint32_t i = 0; i < n; i++) {
-        const infx_filter_prog& P = progs[i];
-        if (!P.nops || !P.ops || (P.nleaves && (!P.leaves || !P.tables))) return fail(INFX_EINVAL, "null filter program%s");
-        { int32_t rc_ = check_filter_prog(ix, P.nops, P.ops, P.nleaves, P.leaves, P.ntable_words); if (rc_) return rc_; }
-        infx_stream::QpProg Q{};
-        Q.nops = P.nops; Q.nleaves = P.nleaves;
-        Q.opsOff = put(P.ops, (size_t)P.nops * sizeof(infx_filter_op));
-        Q.leavesOff = put(P.leaves, (size_t)P.nleaves * sizeof(infx_filter_leaf));
-        Q.tablesOff = put(P.tables, (size_t)P.ntable_words * 4);
-        out.push_back(Q);
-    }
-    if (code.size() > 0xFFFFFFF0ull) return fail(INFX_ECAPACITY, "the batch's filter programs exceed 4 GiB%s");
-    return INFX_OK;
-}
 int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, const infx_filter_prog* progs, uint32_t nboost, const infx_query_boost* boosts,
                                    const infx_query_post* post, uint32_t nfacet, const uint32_t* facet_cols, uint32_t ncount, uint32_t* counts_out) {
     if (!s) return fail(INFX_EINVAL, "null argument%s");
@@ -2811,8 +2836,7 @@ int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, 
     if (s->postFilter || s->nFacet || s->nBoost || s->sortOn) return fail(INFX_EINVAL, "per-query options and a session-wide post-filter, facets, boosts or sort exclude each other%s");
     infx_index* ix = s->ix;
     for (uint32_t c = 0; c < nfacet; c++) if (facet_cols[c] >= FILT_MAXCOL || !ix->colCodes[facet_cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
-    for (int c = 0; c < FILT_MAXCOL; c++)       // rows carry GLOBAL internal ids and the counts run over the whole corpus: every column covers it
-        if (ix->colCodes[c] && ix->colDocs[c] < (uint32_t)ix->d.totalDocs) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS); if (rc_) return rc_; }      // rows carry GLOBAL internal ids and the counts run over the whole corpus
     for (uint32_t b = 0; b < nboost; b++) if (boosts[b].prog < 0 || (uint32_t)boosts[b].prog >= nprog) return fail(INFX_EINVAL, "boost program index out of range%s");
     for (uint32_t q = 0; q < nq; q++) {
         const infx_query_post& D = post[q];
@@ -2822,16 +2846,13 @@ int32_t infx_stream_set_query_post(infx_stream* s, uint32_t nq, uint32_t nprog, 
             return fail(INFX_EINVAL, "sort column or its rank was not uploaded%s");
         if (D.flags & ~(uint32_t)(INFX_QP_FACETS | INFX_QP_SORT | INFX_QP_ASC)) return fail(INFX_EINVAL, "unknown per-query flag%s");
     }
-    { int32_t rc_ = pack_progs(ix, nprog, progs, s->qpProgs, s->qpCode); if (rc_) return rc_; }
+    { int32_t rc_ = s->qpTable.pack(ix, nprog, progs); if (rc_) return rc_; }
     s->qpBoosts.resize(nboost); for (uint32_t b = 0; b < nboost; b++) s->qpBoosts[b] = DevQBoost{boosts[b].prog, boosts[b].strength};
     s->qpDesc.resize(nq);
     for (uint32_t q = 0; q < nq; q++) {
         const infx_query_post& D = post[q]; DevQPost& E = s->qpDesc[q];
         E = DevQPost{}; E.filter = D.filter < 0 ? -1 : D.filter; E.flags = D.flags; E.sortCol = (D.flags & INFX_QP_SORT) ? D.sort_col : 0u; E.boostOff = D.boost_off; E.nboost = D.nboost;
     }
-    std::vector<const infx_filter_leaf*> lv(ncount); std::vector<uint32_t> nl(ncount);
-    for (uint32_t i = 0; i < ncount; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
-    s->qpCols = count_columns(lv.data(), nl.data(), ncount);
     s->qpNq = nq; s->qpNFacet = nfacet; s->qpNCount = ncount; s->qpCountsOut = counts_out;
     for (uint32_t c = 0; c < INFX_MAX_FACET_COLS; c++) s->qpFacetCols[c] = c < nfacet ? facet_cols[c] : 0;
     s->qpOn = true;
@@ -2844,25 +2865,12 @@ int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_pr
     if (!k) return INFX_OK;
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    std::vector<infx_stream::QpProg> packed; std::vector<uint8_t> code;
-    { int32_t rc_ = pack_progs(ix, k, progs, packed, code); if (rc_) return rc_; }
-    const size_t oCode = ((size_t)k * sizeof(DevFilter) + 15) & ~(size_t)15, total = oCode + code.size();
-    GROW(s->dPostBlob, s->capPostBlob, total);
+    ProgTable T;
+    { int32_t rc_ = T.pack(ix, k, progs); if (rc_) return rc_; }
+    { int32_t rc_ = table_upload(s, T, &s->dPostBlob, &s->capPostBlob); if (rc_) return rc_; }
     GROW(s->dQCount, s->capQCount, (size_t)k * 4);
-    char* D = (char*)s->dPostBlob;
-    std::vector<uint8_t> H(total, 0);
-    for (uint32_t i = 0; i < k; i++) {
-        const auto& P = packed[i];
-        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
-        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
-    }
-    if (!code.empty()) std::memcpy(H.data() + oCode, code.data(), code.size());
-    UP(D, H.data(), total);
-    std::vector<const infx_filter_leaf*> lv(k); std::vector<uint32_t> nl(k);
-    for (uint32_t i = 0; i < k; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
-    const DevCountCols cc = count_columns(lv.data(), nl.data(), k);
     const int32_t base = whole_corpus ? 0 : ix->d.docBase, n = whole_corpus ? ix->d.totalDocs : ix->d.N;
-    { int32_t rc_ = count_enqueue(s, (const DevFilter*)D, k, cc, base, n, (uint32_t*)s->dQCount); if (rc_) return rc_; }
+    { int32_t rc_ = count_enqueue(s, (const DevFilter*)s->dPostBlob, k, T.columns(0, k), base, n, (uint32_t*)s->dQCount); if (rc_) return rc_; }
     DOWN(counts, s->dQCount, (size_t)k * 4);
     SYNC();
     return INFX_OK;
@@ -2883,7 +2891,7 @@ int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uin
     DevFacetAll F{}; size_t total = 0; uint32_t ldsWords = 0;
     for (uint32_t c = 0; c < ncol; c++) {
         if (cols[c] >= FILT_MAXCOL || !ix->colCodes[cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
-        if ((uint64_t)ix->colDocs[cols[c]] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS, (int)cols[c]); if (rc_) return rc_; }
         total += ix->colValues[cols[c]];
     }
     HIPCHK(enter_device(ix->cfg.device));
@@ -2946,38 +2954,25 @@ int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog*
         if (cols[c] >= FILT_MAXCOL || !ix->colCodes[cols[c]]) return fail(INFX_EINVAL, "facet column was not uploaded%s");
         nv[c] = ix->colValues[cols[c]]; total += nv[c];
     }
-    for (int c = 0; c < FILT_MAXCOL; c++)       // the programs may read any uploaded column, by GLOBAL internal id
-        if (ix->colCodes[c] && (uint64_t)ix->colDocs[c] < (uint64_t)std::max(n, 0)) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+    { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS); if (rc_) return rc_; }      // the programs may read any uploaded column
     if (total && !counts_out) return fail(INFX_EINVAL, "bad filtered-facet arguments%s");
     if (total > 0xFFFFFFFFull / INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "the facet columns hold too many distinct values%s");
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    std::vector<infx_stream::QpProg> packed; std::vector<uint8_t> code;
-    { int32_t rc_ = pack_progs(ix, k, progs, packed, code); if (rc_) return rc_; }      // (validates every program against the uploaded columns)
-    const size_t oCode = ((size_t)k * sizeof(DevFilter) + 15) & ~(size_t)15, blob = oCode + code.size();
+    ProgTable T;
+    { int32_t rc_ = T.pack(ix, k, progs); if (rc_) return rc_; }      // (validates every program against the uploaded columns)
     const size_t words = (size_t)k * (size_t)total + k;                                  // counters [k][total], then totals [k]
-    GROW(s->dFfBlob, s->capFfBlob, blob);
+    { int32_t rc_ = table_upload(s, T, &s->dFfBlob, &s->capFfBlob); if (rc_) return rc_; }
     GROW(s->dFfCnt, s->capFfCnt, words * 4);
-    char* D = (char*)s->dFfBlob;
-    std::vector<uint8_t> H(blob, 0);
-    for (uint32_t i = 0; i < k; i++) {
-        const auto& P = packed[i];
-        const DevFilter f{(const infx_filter_op*)(D + oCode + P.opsOff), P.nops, (const infx_filter_leaf*)(D + oCode + P.leavesOff), P.nleaves, (const uint32_t*)(D + oCode + P.tablesOff)};
-        std::memcpy(H.data() + (size_t)i * sizeof(DevFilter), &f, sizeof f);
-    }
-    if (!code.empty()) std::memcpy(H.data() + oCode, code.data(), code.size());
-    UP(D, H.data(), blob);
     HIPCHK(hipMemsetAsync(s->dFfCnt, 0, words * 4, s->st));
     uint32_t* dOut = (uint32_t*)s->dFfCnt; uint32_t* dTot = dOut + (size_t)k * (size_t)total;
     s->lastFfProgs = k;
     if (n > 0) {
-        DevColumns dc; for (int c = 0; c < FILT_MAXCOL; c++) dc.codes[c] = ix->colCodes[c];
+        const DevColumns dc = dev_columns(ix);
         const uint32_t per = ffl_programs_per_launch(k, ncol, nv);
         for (uint32_t k0 = 0; k0 < k; k0 += per) {
             const uint32_t kk = std::min(per, k - k0);
-            std::vector<const infx_filter_leaf*> lv(kk); std::vector<uint32_t> nl(kk);
-            for (uint32_t i = 0; i < kk; i++) { lv[i] = progs[k0 + i].leaves; nl[i] = progs[k0 + i].nleaves; }
-            const DevCountCols cc = count_columns(lv.data(), nl.data(), kk);
+            const DevCountCols cc = T.columns(k0, kk);
             DevFacetFilt F{}; uint32_t o = 0;
             const uint32_t ldsWords = ffl_place(kk, ncol, nv, F.ldsOff);
             for (uint32_t c = 0; c < ncol; c++) {
@@ -2994,14 +2989,8 @@ int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog*
             int64_t maxGrid = FCM_MAXGRID;
             if (big) { int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device)); maxGrid = std::max<int64_t>(1, (int64_t)cus * (int64_t)(FFL_CU_LDS / lds)); }
             const int grid = (int)std::min<int64_t>(maxGrid, (groups + threads - 1) / threads);
-            {   // sessions launch from several threads: the attribute is raised under a lock, and only past its high-water mark — one mark per device (a function's
-                // attributes belong to the device that is current when they are set)
-                static std::mutex mu; static std::map<int, size_t> attr;
-                std::lock_guard<std::mutex> lk(mu);
-                size_t& hw = attr[ix->cfg.device];
-                if (lds > 64 * 1024 && lds > hw) { HIPCHK(hipFuncSetAttribute((const void*)k_facets_filtered, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); hw = lds; }
-            }
-            k_facets_filtered<<<grid, threads, lds, s->st>>>((const DevFilter*)D + k0, kk, cc, dc, n, ix->d.deleted, F, (int)ncol, ldsWords, (uint32_t)total,
+            HIPCHK(lds_limit((const void*)k_facets_filtered, ix->cfg.device, lds));
+            k_facets_filtered<<<grid, threads, lds, s->st>>>((const DevFilter*)s->dFfBlob + k0, kk, cc, dc, n, ix->d.deleted, F, (int)ncol, ldsWords, (uint32_t)total,
                                                             dOut + (size_t)k0 * (size_t)total, dTot + k0);
             HIPCHK(hipGetLastError());
             s->lastFfLaunches++;
@@ -3033,14 +3022,14 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
         if (Q.offset >= 0x80000000u) return fail(INFX_EINVAL, "a listing's offset is below 2^31%s");
         if (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS) return fail(INFX_EINVAL, "a listing's digit width is 4 .. 11 bits%s");
         if (Q.col >= 0 && (Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col] || !ix->colRankOk[Q.col])) return fail(INFX_EINVAL, "the listing's column or its sort rank was not uploaded%s");
-        if (Q.col >= 0 && (uint64_t)ix->colDocs[Q.col] < (uint64_t)n) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        if (Q.col >= 0) { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS, Q.col); if (rc_) return rc_; }
         if (Q.mask) { const int slot = mask_slot_of(s, Q.mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a listing's mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
         passes[i] = ls_passes(Q.col >= 0 ? ix->colValues[Q.col] : 1u, Q.digit_bits);
         histOff[i] = histWords; histWords += (size_t)passes[i] * 2u << Q.digit_bits;
     }
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    const uint32_t builds = s->mkStaged && !s->mkProgs.empty() && n > 0 ? 1u : 0u;
+    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
     { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
     s->lastListLaunches = builds;
     if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
@@ -3117,7 +3106,7 @@ int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {
 }
 int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint8_t* const* masks, uint32_t* counts) {
     if (!s || (k && (!progs || !masks))) return fail(INFX_EINVAL, "null argument%s");
-    s->mkStaged = false; s->mkProgs.clear(); s->mkCode.clear(); s->mkCountsOut = nullptr;
+    s->mkStaged = false; s->mkTable.clear(); s->mkCountsOut = nullptr;
     if (!k) return INFX_OK;
     if (k > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) masks in one build%s");
     infx_index* ix = s->ix;
@@ -3126,10 +3115,7 @@ int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* pr
         if (mask_slot_of(s, masks[i]) < 0) return fail(INFX_EINVAL, "a mask buffer is not a mask slot of this stream%s");
         for (uint32_t j = 0; j < i; j++) if (masks[j] == masks[i]) return fail(INFX_EINVAL, "two masks of one build share a slot%s");
     }
-    { int32_t rc_ = pack_progs(ix, k, progs, s->mkProgs, s->mkCode); if (rc_) { s->mkProgs.clear(); s->mkCode.clear(); return rc_; } }
-    std::vector<const infx_filter_leaf*> lv(k); std::vector<uint32_t> nl(k);
-    for (uint32_t i = 0; i < k; i++) { lv[i] = progs[i].leaves; nl[i] = progs[i].nleaves; }
-    s->mkCols = count_columns(lv.data(), nl.data(), k);
+    { int32_t rc_ = s->mkTable.pack(ix, k, progs); if (rc_) { s->mkTable.clear(); return rc_; } }
     s->mkOut = DevMaskOut{}; for (uint32_t i = 0; i < k; i++) s->mkOut.mask[i] = masks[i];
     s->mkCountsOut = counts; s->mkStaged = true;
     return INFX_OK;

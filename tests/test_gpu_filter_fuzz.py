@@ -12,7 +12,8 @@ check runs a second time with every tenth document deleted.
                      made with expression K must return, bit for bit, what the same call returns with `vK = 1` — a one-leaf program that
                      tests/test_gpu_filter.py and tests/test_gpu_boost_sort.py hold to the oracle.
   refusals           depth 33 and 257 ops are refused per query / per expression with check_filter_prog's message, like a syntax error.
-  many columns       11 and 64 columns read by one expression: the one-wave launches, and at 64 columns the raised dynamic-LDS limit.
+  many columns       11 and 64 columns read by one expression: the one-wave launches, and at 64 columns the raised dynamic-LDS limit — of the mask and
+                     facet kernels, and of k_filter_count_multi and k_browse_scan, whose sixteen programs over 64 columns need 65 600 bytes.
 
 What a wrong kernel would show: reading table word `c >> 6` instead of `c >> 5` moves the chosen codes 32, 33, 63, 64 and 999 to other words, so the
 single-leaf masks fail; a TERN that pops one entry too few leaves its condition under the result, which the enclosing OR of the depth-32 ternary chain then
@@ -292,7 +293,16 @@ def test_many_columns(m, n):
                         if c:
                             facets[name] = order_facets(c)
                 assert fac[k].error is None and fac[k].total == int((want == 0).sum()) and fac[k].facets == facets, (m, n, x[:80], fac[k].total, fac[k].facets, facets)
-            alone = Session(e)                                              # the expression that reads every column, alone in its launch
+            if m == 64 and not deleted:
+                # k_filter_count_multi and k_browse_scan with K = 16 over 64 columns: (16 + 64 * 256) * 4 = 65 600 bytes of LDS, past the 64 KiB default limit
+                cnt = s.search_queries([Query("alpha", 10, filter=x) for x in exprs])
+                assert s.last_count_stats() == (16, 1)
+                brw = s.search_queries([Query("", 10, filter=x, enable_facets=True) for x in exprs])
+                assert e.last_browse_stats(s) == (16, 1)                    # sixteen groups (their counts are cached by now), one scan launch
+                for k, x in enumerate(exprs):
+                    assert cnt[k].error is None and cnt[k].total_in_filter == int(accept[k].sum()), (n, x[:80], cnt[k].total_in_filter)
+                    assert model.check(brw[k], x, 10, (n, x[:80])) == np.flatnonzero(accept[k])[:10].tolist()      # the first ten accepted documents, in internal order
+            alone = Session(e)                                             # the expression that reads every column, alone in its launch
             want = np.where(accept[0] & live, 0, 1).astype(np.uint8)
             assert np.array_equal(alone.prefilter_mask(exprs[0]), want) and alone.last_prefilter_stats() == (1, 0, 1)
             alone.close(); s.close()
