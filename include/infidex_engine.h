@@ -238,7 +238,9 @@ int32_t infx_engine_index_from_host_cache(infx_engine* e, const char* path);
 /* ---- Query.Filter (Infiscript, Api/FilterParser.cs) and Query.EnableFacets (config 5) -------------------------------------------------
  * Non-indexed document fields are given as columns (one value per indexed document, in indexing order); the post-filter of the returned
  * rows (Scoring/ResultProcessor.cs:35-70), Filter.NumberOfDocumentsInFilter and the facet counts (Core/FacetBuilder.cs:19-105) run on the
- * device (include/infidex_hip.h).  kind: 1 int64, 2 double, 3 UTF-8 strings (arena + n+1 offsets). */
+ * device (include/infidex_hip.h).  kind: 1 int64, 2 double, 3 UTF-8 strings (arena + n+1 offsets).  A name the engine already holds REPLACES
+ * that column in its slot (new values, possibly of another kind): compiled filters, filter counts, masks, filtered-facet answers and the column's
+ * sort rank are built again on their next use.  An exclusive call, like indexing: no search is in flight. */
 int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, int32_t facetable, int64_t n, const int64_t* vals_i, const double* vals_d,
                                const char* arena, const uint64_t* offs);
 int32_t infx_engine_column_count(infx_engine* e);
@@ -414,6 +416,34 @@ int32_t infx_engine_list_total(infx_session* s, uint32_t which, uint32_t* total)
 int32_t infx_engine_list_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_list_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches);
 int32_t infx_engine_set_list_digit_bits(infx_session* s, int32_t bits);
+/* ---- range_facets: bucket counts and min / max of a numeric field over a filter (not in the reference: the semantics below are this project's) ----------
+ * Request i asks, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document; duplicate keys are documents of their own — for the values v of `field`, an int64 or a double column:
+ *   counts[j]  documents with e_j <= v < e_(j+1): every bucket is half-open, the last included        below  documents with v < e_0
+ *   above      documents with v >= e_B                                                                  nan    documents whose value is a NaN (double columns)
+ *   total      the size of the set, whatever the edges: nan + below + sum(counts) + above == total
+ *   min, max   the smallest and largest value of the set that is not a NaN (none: kind 0); -0.0 and +0.0 compare equal, either may come back
+ * Values compare as Query.SortBy compares them (long numerically; double numerically with -0 == +0).  A NaN value is in no bucket and not in min / max.
+ * EDGES: nedges = 2 .. 257 (1 .. 256 buckets), strictly increasing under that comparison (so -0.0, 0.0 is not), no NaN, +-inf allowed on a double column.
+ * An int64 column reads edges_i (NULL: INFX_EINVAL, "integer column needs integer edges"), a double column reads edges_d.
+ * No sums, means or percentiles (a percentile is infx_engine_list_documents at offset p * total, limit 1); nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_range_error, the others answered): a syntax error, an unknown field, a string
+ * column or bad edges INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests
+ * (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), the field and edge refusals already in out_status; a call that failed as a
+ * whole leaves nothing for the readers.  The masks are the session's pre-filter masks (slots, least-recently-used rule, epoch and statistics of
+ * infx_engine_list_documents; the ones a call is missing are built in ONE launch in front of it); the column's sort rank is built on its first use; ONE
+ * k_range_counts launch counts all requests of the call.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_range_counts copies up to cap bucket counts and below / above / nan and returns the
+ * number of buckets (-1 for a refused request or bad arguments); infx_engine_range_total the size of the set (returning the request's status);
+ * infx_engine_range_minmax *kind = 1 with lo_i / hi_i, 2 with lo_d / hi_d, 0 when the set holds no value that is not a NaN; infx_engine_range_error the
+ * refusal's message (its length; -1 out of range).  infx_engine_last_range_stats: masks built and reused and k_range_counts launches of the last call. */
+typedef struct infx_range_request { const char* filter; const char* field; uint32_t nedges; const int64_t* edges_i; const double* edges_d; } infx_range_request;
+int32_t infx_engine_range_facets(infx_session* s, uint32_t nreq, const infx_range_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_range_counts(infx_session* s, uint32_t which, uint32_t* counts, int32_t cap, uint32_t* below, uint32_t* above, uint32_t* nan);
+int32_t infx_engine_range_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_range_minmax(infx_session* s, uint32_t which, int32_t* kind, int64_t* lo_i, int64_t* hi_i, double* lo_d, double* hi_d);
+int32_t infx_engine_range_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_range_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

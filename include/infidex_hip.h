@@ -426,6 +426,26 @@ typedef struct infx_list_req { const uint8_t* mask; int32_t col; int32_t ascendi
 int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
                           uint32_t* counts_out /* nreq */, uint32_t* totals_out /* nreq */);
 int32_t infx_last_list_stats(infx_stream* s, uint32_t* hist_passes, uint32_t* launches);
+/* Range facets of a document set over a numeric column (not in the reference: the buckets are this project's; DESIGN.md "range_facets").
+ * Request i: the SET is the documents whose byte in `mask` is 0 — a mask slot of this stream (infx_stream_mask_slot, built by infx_filter_masks: not
+ * Deleted and accepted) — or, mask = NULL, every document that is not Deleted (the index's real flags).  The work is on the dense sort rank of uploaded
+ * column `col` (infx_upload_sort_rank), never on values: the caller turns its nedges (2 .. INFX_RANGE_MAX_EDGES) strictly increasing edges e_0 < .. < e_B
+ * into thr[j] = the number of distinct ranks whose value compares < e_j (non-decreasing; a NaN ranks lowest and is counted under every edge), and
+ * nan_ranks = 1 when the column's value of rank 0 is a NaN, else 0 (nan_ranks <= thr[j] <= num_values).  A document of rank r is counted in
+ * counts_out[i * INFX_RANGE_SLOTS + k]: k = B + 2 (NaN) when r < nan_ranks, else k = #{j : thr[j] <= r} — k = 0 below e_0, k = 1 .. B the half-open
+ * bucket [e_(k-1), e_k), k = B + 1 at or above e_B; B + 3 words are written per request, their sum is the size of the set.  min_rank_out[i] /
+ * max_rank_out[i]: the smallest and largest rank >= nan_ranks in the set; min_rank_out[i] = 0xFFFFFFFF when there is none (max_rank_out[i] is 0 then).
+ * At most 16 requests (INFX_ECAPACITY), all counted by ONE k_range_counts launch that walks the corpus once: the requests are taken in the order
+ * (mask, col), so the ones that share a mask read its bytes once and the ones that share a column too read the codes and ranks once.  A mask build
+ * staged with infx_filter_masks is enqueued first, as ONE launch.  Integer atomics only, none decides a position: the same bytes from any stream
+ * and grid.  Works on a sharded index (whole columns and global flags on every rank; masks by global id).  Synchronous.
+ * infx_last_range_stats: requests and k_range_counts launches (0 or 1) of the stream's last call. */
+#define INFX_RANGE_MAX_EDGES 257
+#define INFX_RANGE_SLOTS 260
+typedef struct infx_range_req { const uint8_t* mask; int32_t col; uint32_t nedges; uint32_t nan_ranks; uint32_t reserved; const uint32_t* thr; } infx_range_req;
+int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* reqs, uint32_t* counts_out /* nreq x INFX_RANGE_SLOTS */,
+                          uint32_t* min_rank_out /* nreq */, uint32_t* max_rank_out /* nreq */);
+int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

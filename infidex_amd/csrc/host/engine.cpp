@@ -91,6 +91,9 @@ struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector
 struct FfAnswer { int32_t status = INFX_OK; std::string err; std::shared_ptr<const FfEntry> r; };
 // One request of the session's last infx_engine_list_documents: its status and message, the size of its set, its page
 struct ListAnswer { int32_t status = INFX_OK; std::string err; uint32_t total = 0; std::vector<int64_t> keys; std::vector<int32_t> docs; std::vector<uint32_t> codes; };
+// One request of the session's last infx_engine_range_facets: its status and message, its counters, the extremes as values (kind 0: none, 1 int64, 2 double)
+struct RangeAnswer { int32_t status = INFX_OK; std::string err; uint32_t total = 0, below = 0, above = 0, nan = 0; std::vector<uint32_t> counts;
+                     int32_t kind = 0; int64_t loI = 0, hiI = 0; double loD = 0, hiD = 0; };
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
@@ -106,6 +109,8 @@ struct infx_session {
     std::vector<uint32_t> ffCols; std::vector<FfAnswer> ff; uint32_t ffCounted = 0, ffCached = 0, ffLaunches = 0;
     // infx_engine_list_documents: one answer per request of the session's last call, what the call cost (histogram passes, kernel launches), the digit width
     std::vector<ListAnswer> lst; uint32_t lstBuilt = 0, lstReused = 0, lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
+    // infx_engine_range_facets: one answer per request of the session's last call; masks built and reused and k_range_counts launches of that call
+    std::vector<RangeAnswer> rng; uint32_t rngBuilt = 0, rngReused = 0, rngLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -225,6 +230,9 @@ struct infx_engine {
     std::vector<filt::Column> columns; std::mutex filterMu; std::unordered_map<std::string, CompiledFilter> filters;
     std::vector<infx_filter*> retiredFilters;     // compiled against an older column set (a session's stream may still point at one): freed with the engine
     std::vector<uint8_t> sortRanked;              // per column: its sort rank is on the device (infx_engine_set_sort, built on first use)
+    // per column, for infx_engine_range_facets (built on first use, under filterMu): the lowest code of every sort rank, in rank order, and whether rank 0 is a NaN
+    struct RangeIndex { bool ok = false; uint32_t nanRanks = 0; std::vector<uint32_t> codeOfRank; };
+    std::vector<RangeIndex> rangeIndex;
     // NumberOfDocumentsInFilter is cached per expression; a Filter parsed after a mutation counts again (the reference keeps the count on the Filter instance)
     void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = kv.second.countedAll = false; }
     void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); filterLru.clear(); }
@@ -2377,17 +2385,25 @@ int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, i
                                const char* arena, const uint64_t* offs) {
     if (!e || !name || n < 0 || (kind == 1 && !vi) || (kind == 2 && !vd) || (kind == 3 && (!arena || !offs)) || kind < 1 || kind > 3) return efail(INFX_EINVAL, "bad column arguments");
     if (!e->indexed || n != e->ix.N) return efail(INFX_EINVAL, "a column needs one value per indexed document");
-    if (e->columns.size() >= 64) return efail(INFX_ECAPACITY, "too many columns");
-    for (auto& c : e->columns) if (c.name == name) return efail(INFX_EINVAL, "column exists");
+    // a name the engine already holds: the column is REPLACED in its slot (new values, possibly of another kind); everything derived from it goes
+    size_t at = e->columns.size();
+    for (size_t i = 0; i < e->columns.size(); i++) if (e->columns[i].name == name) at = i;
+    if (at == e->columns.size() && e->columns.size() >= 64) return efail(INFX_ECAPACITY, "too many columns");
     filt::Column c; c.name = name; c.facetable = facetable != 0;
     if (kind == 1) filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 1; b.i = vi[d]; return b; }, (long long)0);
     else if (kind == 2) filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 2; b.d = vd[d]; return b; }, (uint64_t)0);
     else filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 3; b.s.assign(arena + offs[d], arena + offs[d + 1]); return b; }, std::string());
     if (e->dev) {
-        int32_t rc = infx_upload_column(e->dev, (uint32_t)e->columns.size(), (uint32_t)n, c.codes.data(), (uint32_t)c.dict.size());
+        int32_t rc = infx_upload_column(e->dev, (uint32_t)at, (uint32_t)n, c.codes.data(), (uint32_t)c.dict.size());      // (a re-upload voids the column's sort rank on the device)
         if (rc) { g_eerr = infx_last_error(); return rc; }
     }
-    e->columns.push_back(std::move(c));
+    if (at < e->columns.size()) {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        e->columns[at] = std::move(c);
+        if (at < e->sortRanked.size()) e->sortRanked[at] = 0;
+        if (at < e->rangeIndex.size()) e->rangeIndex[at] = infx_engine::RangeIndex();
+    } else e->columns.push_back(std::move(c));
+    e->invalidate_filter_counts();
     e->maskEpoch++;
     e->retire_filters();      // leaf tables of filters compiled before this field existed treat it as null: compile again on next use
     return INFX_OK;
@@ -3227,6 +3243,168 @@ int32_t infx_engine_last_list_stats(infx_session* S, uint32_t* masks_built, uint
 int32_t infx_engine_set_list_digit_bits(infx_session* S, int32_t bits) {
     if (!S || bits < 4 || bits > 11) return efail(INFX_EINVAL, "the digit width of list_documents is 4 .. 11 bits");
     S->lstDigitBits = bits;
+    return INFX_OK;
+}
+
+// ---- range_facets: bucket counts and min / max of a numeric field over the documents a filter accepts (not in the reference) --------------------------
+// Per request: the field to its column (int64 or double), the edges to thresholds over the column's dense sort rank — thr[i] = the number of distinct ranks
+// whose value compares < e_i under filt::sort_cmp, found by bisection over the ranks' values — the filter through the filter cache and its mask through the
+// session's mask cache, as infx_engine_list_documents.  infx_range_counts then counts every request in one pass; the extreme ranks come back as values.
+// The column's rank order (lowest code of every rank; built with the sort rank's first use).  Caller holds e->filterMu.
+static int32_t range_index(infx_engine* e, uint32_t col, const infx_engine::RangeIndex** out) {
+    if (e->rangeIndex.size() < e->columns.size()) e->rangeIndex.resize(e->columns.size());
+    if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
+    infx_engine::RangeIndex& X = e->rangeIndex[col];
+    if (!X.ok || !e->sortRanked[col]) {
+        const filt::Column& c = e->columns[col];
+        std::vector<uint32_t> rank; filt::sort_rank(c, rank);
+        if (!e->sortRanked[col]) {
+            int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
+            if (rc) { g_eerr = infx_last_error(); return rc; }
+            e->sortRanked[col] = 1;
+        }
+        uint32_t nr = 0; for (uint32_t r : rank) nr = std::max(nr, r + 1u);
+        X.codeOfRank.assign(nr, 0xFFFFFFFFu);
+        for (size_t code = 0; code < rank.size(); code++) if (X.codeOfRank[rank[code]] == 0xFFFFFFFFu) X.codeOfRank[rank[code]] = (uint32_t)code;      // codes ascend: the lowest wins
+        X.nanRanks = nr && c.dict[X.codeOfRank[0]].kind == 2 && std::isnan(c.dict[X.codeOfRank[0]].d) ? 1u : 0u;
+        X.ok = true;
+    }
+    *out = &X;
+    return INFX_OK;
+}
+static int column_kind(const filt::Column& c) { return c.dict.empty() ? 0 : c.dict[0].kind; }
+int32_t infx_engine_range_facets(infx_session* S, uint32_t nreq, const infx_range_request* reqs, int32_t* out_status) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->rng.clear(); S->rngBuilt = S->rngReused = S->rngLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) range requests in one call");
+    S->rng.assign(nreq, RangeAnswer());
+    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->rng[i].status = rc; S->rng[i].err = msg; if (out_status) out_status[i] = rc; };
+    std::vector<int32_t> col(nreq, -1); std::vector<int> kind(nreq, 0);
+    {
+        // what needs no device: the field, its kind and the edges
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            const infx_range_request& Q = reqs[i];
+            if (out_status) out_status[i] = INFX_OK;
+            if (!Q.field) { refuse(i, INFX_EINVAL, "range_facets needs a field"); continue; }
+            for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == Q.field) col[i] = (int32_t)c;      // case sensitive, as the filter's fields
+            if (col[i] < 0) { refuse(i, INFX_EINVAL, std::string("range_facets: no field named '") + Q.field + "'"); continue; }
+            int k = column_kind(e->columns[col[i]]);
+            if (k == 3) { refuse(i, INFX_EINVAL, std::string("range_facets: field '") + Q.field + "' is a string column; ranges need an int64 or a double column"); continue; }
+            if (k == 0) k = Q.edges_i ? 1 : 2;                              // (a column without a value)
+            kind[i] = k;
+            if (Q.nedges < 2 || Q.nedges > INFX_RANGE_MAX_EDGES) { refuse(i, INFX_EINVAL, "range_facets takes 2 to 257 edges (1 to 256 buckets)"); continue; }
+            if (k == 1) {
+                if (!Q.edges_i) { refuse(i, INFX_EINVAL, "integer column needs integer edges"); continue; }
+                for (uint32_t j = 1; j < Q.nedges && !S->rng[i].status; j++) if (!(Q.edges_i[j - 1] < Q.edges_i[j])) refuse(i, INFX_EINVAL, "the edges of range_facets are strictly increasing");
+            } else {
+                if (!Q.edges_d) { refuse(i, INFX_EINVAL, "double column needs double edges"); continue; }
+                for (uint32_t j = 0; j < Q.nedges && !S->rng[i].status; j++) {
+                    if (std::isnan(Q.edges_d[j])) refuse(i, INFX_EINVAL, "an edge of range_facets is not a NaN");
+                    else if (j && !(Q.edges_d[j - 1] < Q.edges_d[j])) refuse(i, INFX_EINVAL, "the edges of range_facets are strictly increasing (-0.0 and 0.0 compare equal)");
+                }
+            }
+        }
+    }
+    // a call that fails as a whole leaves no answers behind: the readers refuse (the statuses already written to out_status stay)
+    if (!e->dev || !S->stream) { S->rng.clear(); return efail(INFX_EHIP, "no GPU: range_facets runs on the device"); }
+    if (!e->indexed) { S->rng.clear(); return efail(INFX_EINVAL, "range_facets before index_documents"); }
+    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nreq, -1);
+    std::vector<std::vector<uint32_t>> thr(nreq); std::vector<uint32_t> nanRanks(nreq, 0);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (S->rng[i].status) continue;
+            const infx_range_request& Q = reqs[i];
+            const infx_engine::RangeIndex* X = nullptr;
+            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }
+            if (Q.filter) {
+                auto it = idx.find(Q.filter);
+                if (it == idx.end()) {
+                    CompiledFilter* cf = nullptr;
+                    const int32_t rc = compile_filter(e, Q.filter, &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
+                    if (rc) { refuse(i, rc, g_eerr); continue; }
+                    it = idx.emplace(Q.filter, (int)exprs.size()).first; exprs.push_back(Q.filter);
+                }
+                of[i] = it->second;
+            }
+            const filt::Column& c = e->columns[col[i]];
+            nanRanks[i] = X->nanRanks;
+            thr[i].resize(Q.nedges);
+            for (uint32_t j = 0; j < Q.nedges; j++) {
+                filt::Boxed edge; edge.kind = kind[i]; if (kind[i] == 1) edge.i = Q.edges_i[j]; else edge.d = Q.edges_d[j];
+                // the ranks' values ascend under sort_cmp: the first rank whose value is not below the edge
+                thr[i][j] = (uint32_t)(std::partition_point(X->codeOfRank.begin(), X->codeOfRank.end(), [&](uint32_t code) { return filt::sort_cmp(c.dict[code], edge) < 0; }) - X->codeOfRank.begin());
+            }
+        }
+    }
+    std::vector<uint8_t*> masks; std::vector<int> built;
+    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, masks, built); if (rc) { S->rng.clear(); return rc; } }
+    else S->preBuilt = S->preReused = S->preLaunches = 0;
+    std::vector<infx_range_req> dr; std::vector<uint32_t> who;
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (S->rng[i].status) continue;
+        infx_range_req R{};
+        if (of[i] >= 0) R.mask = masks[of[i]];
+        R.col = col[i]; R.nedges = reqs[i].nedges; R.nan_ranks = nanRanks[i]; R.thr = thr[i].data();
+        dr.push_back(R); who.push_back(i);
+    }
+    const size_t m = dr.size();
+    std::vector<uint32_t> counts(std::max<size_t>(m, 1) * INFX_RANGE_SLOTS, 0), lo(std::max<size_t>(m, 1), 0xFFFFFFFFu), hi(std::max<size_t>(m, 1), 0);
+    int32_t rc = infx_range_counts(S->stream, (uint32_t)m, dr.data(), counts.data(), lo.data(), hi.data());
+    if (rc) { S->rng.clear(); return staged_failed(S, built, rc); }
+    take_prefilter_counts(S, 0, built);
+    S->rngBuilt = S->preBuilt; S->rngReused = S->preReused;
+    { uint32_t r_ = 0; infx_last_range_stats(S->stream, &r_, &S->rngLaunches); }
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    for (size_t j = 0; j < m; j++) {
+        RangeAnswer& A = S->rng[who[j]];
+        const uint32_t ne = dr[j].nedges; const uint32_t* c = counts.data() + j * INFX_RANGE_SLOTS;
+        A.below = c[0]; A.counts.assign(c + 1, c + ne); A.above = c[ne]; A.nan = c[ne + 1];
+        uint64_t t = 0; for (uint32_t k = 0; k < ne + 2; k++) t += c[k];
+        A.total = (uint32_t)t;
+        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
+        if (lo[j] != 0xFFFFFFFFu && lo[j] < X.codeOfRank.size() && hi[j] < X.codeOfRank.size()) {
+            const filt::Boxed& a = C.dict[X.codeOfRank[lo[j]]]; const filt::Boxed& b = C.dict[X.codeOfRank[hi[j]]];
+            A.kind = a.kind == 1 ? 1 : 2;
+            if (A.kind == 1) { A.loI = a.i; A.hiI = b.i; } else { A.loD = a.d; A.hiD = b.d; }
+        }
+    }
+    return INFX_OK;
+}
+// request `which` of the session's last infx_engine_range_facets: up to cap bucket counts; returns the number of buckets, -1 on error (also for a refused request)
+int32_t infx_engine_range_counts(infx_session* S, uint32_t which, uint32_t* counts, int32_t cap, uint32_t* below, uint32_t* above, uint32_t* nan) {
+    if (!S || which >= S->rng.size() || S->rng[which].status || (cap > 0 && !counts)) return -1;
+    const RangeAnswer& A = S->rng[which];
+    const size_t c = std::min<size_t>(A.counts.size(), (size_t)std::max(cap, 0));
+    if (c) std::memcpy(counts, A.counts.data(), c * 4);
+    if (below) *below = A.below; if (above) *above = A.above; if (nan) *nan = A.nan;
+    return (int32_t)A.counts.size();
+}
+// the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_range_total(infx_session* S, uint32_t which, uint32_t* total) {
+    if (!S || !total || which >= S->rng.size()) return efail(INFX_EINVAL, "no such request in the session's last range_facets call");
+    *total = S->rng[which].total;
+    return S->rng[which].status;
+}
+// the smallest and largest non-NaN value of request `which`'s set: *kind 1 -> lo_i / hi_i, 2 -> lo_d / hi_d, 0 -> there is none
+int32_t infx_engine_range_minmax(infx_session* S, uint32_t which, int32_t* kind, int64_t* lo_i, int64_t* hi_i, double* lo_d, double* hi_d) {
+    if (!S || !kind || which >= S->rng.size()) return efail(INFX_EINVAL, "no such request in the session's last range_facets call");
+    const RangeAnswer& A = S->rng[which];
+    *kind = A.kind;
+    if (lo_i) *lo_i = A.loI; if (hi_i) *hi_i = A.hiI; if (lo_d) *lo_d = A.loD; if (hi_d) *hi_d = A.hiD;
+    return A.status;
+}
+int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
+    if (!S || which >= S->rng.size()) return -1;
+    return copy_message(S->rng[which].err, out, cap);
+}
+int32_t infx_engine_last_range_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (masks_built) *masks_built = S->rngBuilt;
+    if (masks_reused) *masks_reused = S->rngReused;
+    if (launches) *launches = S->rngLaunches;
     return INFX_OK;
 }
 

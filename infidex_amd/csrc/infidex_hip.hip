@@ -261,6 +261,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "browse.hip.inc"
 #include "facets_filtered.hip.inc"
 #include "listing.hip.inc"
+#include "ranges.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -360,6 +361,8 @@ struct infx_stream {
     uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
     void *dListWs = nullptr, *dListOut = nullptr; size_t capListWs = 0, capListOut = 0;      // infx_list_ordered: select states, histograms, range counts, page composites; the rows
     uint32_t lastListPasses = 0, lastListLaunches = 0;         // histogram passes and kernel launches of the last infx_list_ordered
+    void *dRngWs = nullptr, *dRngOut = nullptr; size_t capRngWs = 0, capRngOut = 0;        // infx_range_counts: the requests' thresholds; counters, largest and smallest ranks
+    uint32_t lastRngReqs = 0, lastRngLaunches = 0;             // requests and k_range_counts launches of the last infx_range_counts
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1298,7 +1301,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -3085,6 +3088,77 @@ int32_t infx_last_list_stats(infx_stream* s, uint32_t* hist_passes, uint32_t* la
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (hist_passes) *hist_passes = s->lastListPasses;
     if (launches) *launches = s->lastListLaunches;
+    return INFX_OK;
+}
+// ---- range_facets: bucket counts and the extreme sort ranks of a numeric column over a document set (ranges.hip.inc) ----
+int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* reqs, uint32_t* counts_out, uint32_t* min_rank_out, uint32_t* max_rank_out) {
+    if (!s || (nreq && (!reqs || !counts_out || !min_rank_out || !max_rank_out))) return fail(INFX_EINVAL, "bad range arguments%s");
+    s->lastRngReqs = 0; s->lastRngLaunches = 0;
+    if (nreq > RB_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 range requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    size_t thrWords = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_range_req& Q = reqs[i];
+        if (Q.nedges < RB_MIN_EDGES || Q.nedges > RB_MAX_EDGES || !Q.thr) return fail(INFX_EINVAL, "a range request has 2 .. INFX_RANGE_MAX_EDGES (257) thresholds%s");
+        if (Q.col < 0 || Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col] || !ix->colRankOk[Q.col]) return fail(INFX_EINVAL, "the range request's column or its sort rank was not uploaded%s");
+        if ((uint64_t)ix->colDocs[Q.col] < (uint64_t)n) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
+        for (uint32_t j = 0; j < Q.nedges; j++)
+            if (Q.thr[j] < Q.nan_ranks || Q.thr[j] > ix->colValues[Q.col] || (j && Q.thr[j] < Q.thr[j - 1])) return fail(INFX_EINVAL, "a range request's thresholds are non-decreasing, from nan_ranks to the column's number of values%s");
+        if (Q.mask) { const int slot = mask_slot_of(s, Q.mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a range request's mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
+        thrWords += Q.nedges;
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front
+    s->lastRngReqs = nreq;
+    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    // requests that share a mask follow one another, and among them the ones that share a column: the walk keeps what the request before loaded
+    uint32_t order[RB_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
+    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) { return reqs[a].mask != reqs[b].mask ? std::less<const uint8_t*>()(reqs[a].mask, reqs[b].mask) : reqs[a].col < reqs[b].col; });
+    const size_t oHi = (size_t)nreq * RNG_OUT_STRIDE * 4, oLo = oHi + (size_t)nreq * 4;
+    GROW(s->dRngWs, s->capRngWs, thrWords * 4);
+    GROW(s->dRngOut, s->capRngOut, oLo + (size_t)nreq * 4);
+    char* O = (char*)s->dRngOut;
+    std::vector<uint32_t> thr; thr.reserve(thrWords);
+    DevRangeCall P{}; P.nreq = nreq;
+    uint32_t ldsWords = 0;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_range_req& Q = reqs[order[k]];
+        DevRangeReq& D = P.r[k];
+        D.mask = Q.mask ? Q.mask : ix->d.deleted;
+        D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col];
+        D.thr = (const uint32_t*)s->dRngWs + thr.size(); thr.insert(thr.end(), Q.thr, Q.thr + Q.nedges);
+        D.nedges = Q.nedges; D.nanRanks = Q.nan_ranks; D.ldsOff = ldsWords; ldsWords += rb_lds_words(Q.nedges);
+        if (k) { const infx_range_req& B = reqs[order[k - 1]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+    }
+    UP(s->dRngWs, thr.data(), thrWords * 4);
+    HIPCHK(hipMemsetAsync(O, 0, oLo, s->st));
+    HIPCHK(hipMemsetAsync(O + oLo, 0xFF, (size_t)nreq * 4, s->st));
+    s->unsynced = true;
+    if (n > 0) {
+        const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
+        const int grid = (int)std::min<int64_t>(RNG_MAXGRID, (groups + RNG_THREADS - 1) / RNG_THREADS);
+        k_range_counts<<<grid, RNG_THREADS, (size_t)ldsWords * 4, s->st>>>(P, n, (uint32_t*)O, (uint32_t*)(O + oHi), (uint32_t*)(O + oLo));
+        HIPCHK(hipGetLastError());
+        s->lastRngLaunches = 1;
+    }
+    for (uint32_t k = 0; k < nreq; k++) {
+        const uint32_t i = order[k];
+        DOWN(counts_out + (size_t)i * INFX_RANGE_SLOTS, (uint32_t*)O + (size_t)k * RNG_OUT_STRIDE, (size_t)rb_slots(reqs[i].nedges) * 4);
+        DOWN(max_rank_out + i, (uint32_t*)(O + oHi) + k, 4);
+        DOWN(min_rank_out + i, (uint32_t*)(O + oLo) + k, 4);
+    }
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (requests) *requests = s->lastRngReqs;
+    if (launches) *launches = s->lastRngLaunches;
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

@@ -174,6 +174,30 @@ class Listing:             # SearchEngine.list_documents: one per request
     error: Optional[str] = None                               # why this request alone was refused; None when it was answered
 
 
+@dataclass
+class RangeRequest:        # SearchEngine.range_facets: the buckets of one numeric field over one filter
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    field: str = ""                     # an int64 or a double column
+    edges: tuple = ()                   # 2 .. 257 strictly increasing edges e_0 < .. < e_B: B half-open buckets [e_i, e_i+1); ints for an int column
+
+
+@dataclass
+class RangeFacets:         # SearchEngine.range_facets: one per request
+    edges: tuple = ()                                         # the request's edges
+    counts: list = _dc_field(default_factory=list)            # counts[i]: documents with edges[i] <= value < edges[i + 1]
+    below: int = 0                                            # documents with value < edges[0]
+    above: int = 0                                            # documents with value >= edges[-1]
+    nan: int = 0                                              # documents whose value is a NaN (double columns): in no bucket, not in min / max
+    total: int = 0                                            # live documents the filter accepts: nan + below + sum(counts) + above
+    min: Optional[object] = None                              # smallest / largest non-NaN value of the set (int for an int column, float for a double one);
+    max: Optional[object] = None                              # None when there is none
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+class _RangeReq(C.Structure):
+    _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("nedges", C.c_uint32), ("edges_i", C.POINTER(C.c_int64)), ("edges_d", C.POINTER(C.c_double))]
+
+
 class _ListReq(C.Structure):
     _fields_ = [("filter", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
 
@@ -462,6 +486,22 @@ class SearchEngine:
     def set_list_digit_bits(self, bits, session=None):
         """The width of a radix-select digit of list_documents on the session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
         self._check(self.L.infx_engine_set_list_digit_bits(session.h if session is not None else self._default_session(), int(bits)))
+
+    def range_facets(self, filter=None, field=None, edges=(), session=None):
+        """Range facets (not in the reference): over the documents list_documents(filter) lists — not Deleted, their own fields accepted by `filter`; None:
+        every live document; duplicate keys are documents of their own — the values of `field`, an int64 or a double column, counted into the half-open
+        buckets [edges[i], edges[i + 1]) (the last one too), with the documents below edges[0], at or above edges[-1] and, on a double column, with a NaN
+        value (in no bucket), the size of the set and its smallest and largest non-NaN value.  Returns RangeFacets(edges, counts, below, above, nan, total,
+        min, max, error); always nan + below + sum(counts) + above == total.  2 .. 257 edges, strictly increasing as Query.sort_by compares values (-0.0,
+        0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  A sequence of RangeRequest as first argument -> a list of
+        RangeFacets, sixteen requests per device call, all counted in ONE pass over the corpus (requests of one filter read its mask once); a request
+        with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums, means or percentiles (a percentile is
+        list_documents(order_by=field, offset=p * total, limit=1))."""
+        return _range_facets(self, session.h if session is not None else self._default_session(), filter, field, edges)
+
+    def last_range_stats(self, session=None):
+        """(masks built, masks reused, k_range_counts launches) of the session's last range_facets device call."""
+        return _range_stats(self, session.h if session is not None else self._default_session())
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -767,6 +807,14 @@ class Session:
         """The width of a radix-select digit of list_documents on this session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
         self.engine._check(self.engine.L.infx_engine_set_list_digit_bits(self.h, int(bits)))
 
+    def range_facets(self, filter=None, field=None, edges=()):
+        """SearchEngine.range_facets on this session (its mask cache holds the filters' masks)."""
+        return _range_facets(self.engine, self.h, filter, field, edges)
+
+    def last_range_stats(self):
+        """SearchEngine.last_range_stats of this session."""
+        return _range_stats(self.engine, self.h)
+
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
         return _prefilter_stats(self.engine, self.h)
@@ -1058,6 +1106,58 @@ def _list_documents(engine, sh, filter, order_by, ascending, offset, limit):
                     vals.append(text[c])
             out.append(Listing([int(k) for k in keys[:m]], vals, int(tot.value), None))
     return out[0] if single else out
+
+
+def _range_facets(engine, sh, filter, field, edges):
+    """infx_engine_range_facets on session handle sh: a RangeFacets for one request (given by its parts), a list of them for a sequence of RangeRequest."""
+    single = filter is None or isinstance(filter, str)
+    reqs = [RangeRequest(filter, field, edges)] if single else list(filter)
+    out = []
+    for r0 in range(0, len(reqs), MAX_PREFILTERS):       # one mask slot per distinct filter: sixteen requests per device call
+        part = reqs[r0:r0 + MAX_PREFILTERS]
+        n = len(part)
+        arr = (_RangeReq * n)()
+        keep = []                                        # the edge arrays live until the call returns
+        for i, r in enumerate(part):
+            ed = tuple(r.edges)
+            # integer edges only when every edge is a Python int (not a bool) that an int64 holds; double edges always (what float() refuses is passed as NaN: refused)
+            ei = None
+            if ed and all(isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63 for x in ed):
+                ei = np.asarray(ed, np.int64); keep.append(ei)
+            vals = []
+            for x in ed:
+                try:
+                    vals.append(float(x))
+                except (TypeError, ValueError, OverflowError):
+                    vals.append(float("nan"))
+            edd = np.asarray(vals, np.float64); keep.append(edd)
+            arr[i] = _RangeReq(None if r.filter is None else r.filter.encode(), None if r.field is None else str(r.field).encode(), min(len(ed), 0xFFFFFFFF),
+                               None if ei is None else _p(ei, C.c_int64), _p(edd, C.c_double))
+        st = np.zeros(n, np.int32)
+        engine._check(engine.L.infx_engine_range_facets(sh, n, arr, _p(st, C.c_int32)))
+        for i, r in enumerate(part):
+            ed = tuple(r.edges)
+            if st[i] != 0:
+                buf = C.create_string_buffer(512); engine.L.infx_engine_range_error(sh, i, buf, 512)
+                out.append(RangeFacets(ed, [], 0, 0, 0, 0, None, None, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
+                continue
+            tot = C.c_uint32(0); below = C.c_uint32(0); above = C.c_uint32(0); nan = C.c_uint32(0)
+            engine._check(engine.L.infx_engine_range_total(sh, i, C.byref(tot)))
+            counts = np.zeros(256, np.uint32)
+            m = engine.L.infx_engine_range_counts(sh, i, _p(counts, C.c_uint32), 256, C.byref(below), C.byref(above), C.byref(nan))
+            if m < 0:
+                engine._check(1)
+            kind = C.c_int32(0); li = C.c_int64(0); hi = C.c_int64(0); ld = C.c_double(0); hd = C.c_double(0)
+            engine._check(engine.L.infx_engine_range_minmax(sh, i, C.byref(kind), C.byref(li), C.byref(hi), C.byref(ld), C.byref(hd)))
+            lo, up = (int(li.value), int(hi.value)) if kind.value == 1 else ((float(ld.value), float(hd.value)) if kind.value == 2 else (None, None))
+            out.append(RangeFacets(ed, [int(c) for c in counts[:m]], int(below.value), int(above.value), int(nan.value), int(tot.value), lo, up, None))
+    return out[0] if single else out
+
+
+def _range_stats(engine, sh):
+    a = C.c_uint32(0); b = C.c_uint32(0); c = C.c_uint32(0)
+    engine._check(engine.L.infx_engine_last_range_stats(sh, C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def _list_stats(engine, sh):

@@ -717,6 +717,14 @@ class ShardedSearcher:
     def last_list_stats(self):
         return self.sessions[0].s.last_list_stats()
 
+    def range_facets(self, filter=None, field=None, edges=()):
+        """SearchEngine.range_facets: like list_documents, every rank counts over the whole columns with the global Deleted flags on its own GPU and gets
+        the same answer — nothing is exchanged."""
+        return self.sessions[0].s.range_facets(filter, field, edges)
+
+    def last_range_stats(self):
+        return self.sessions[0].s.last_range_stats()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
