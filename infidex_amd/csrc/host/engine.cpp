@@ -88,12 +88,17 @@ struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t cou
 // The facets of one Infiscript expression (infx_engine_facets_filtered), as the engine caches them: per facet column the ordered (code, count) list, cut to 100,
 // and the number of live documents the expression accepts; valid for the mask epoch it was counted in
 struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists; std::list<std::string>::iterator lru; };
-struct FfAnswer { int32_t status = INFX_OK; std::string err; std::shared_ptr<const FfEntry> r; };
+// What the answer to one request of a per-request call begins with: its status and message (why it was refused) and the size of its set (0 when refused)
+struct Answer { int32_t status = INFX_OK; std::string err; uint32_t total = 0; };
+// answer `which` of a session's last per-request call (null: no session, or no such answer)
+template <class A> static const A* answer_at(const std::vector<A>* v, uint32_t which) { return v && which < v->size() ? &(*v)[which] : nullptr; }
+struct FfAnswer : Answer { std::shared_ptr<const FfEntry> r; };
 // One request of the session's last infx_engine_list_documents: its status and message, the size of its set, its page
-struct ListAnswer { int32_t status = INFX_OK; std::string err; uint32_t total = 0; std::vector<int64_t> keys; std::vector<int32_t> docs; std::vector<uint32_t> codes; };
+struct ListAnswer : Answer { std::vector<int64_t> keys; std::vector<int32_t> docs; std::vector<uint32_t> codes; };
 // One request of the session's last infx_engine_range_facets: its status and message, its counters, the extremes as values (kind 0: none, 1 int64, 2 double)
-struct RangeAnswer { int32_t status = INFX_OK; std::string err; uint32_t total = 0, below = 0, above = 0, nan = 0; std::vector<uint32_t> counts;
+struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vector<uint32_t> counts;
                      int32_t kind = 0; int64_t loI = 0, hiI = 0; double loD = 0, hiD = 0; };
+struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
@@ -108,9 +113,9 @@ struct infx_session {
     // was refused), and what the call cost: expressions counted on the device, expressions taken from the cache, k_facets_filtered launches
     std::vector<uint32_t> ffCols; std::vector<FfAnswer> ff; uint32_t ffCounted = 0, ffCached = 0, ffLaunches = 0;
     // infx_engine_list_documents: one answer per request of the session's last call, what the call cost (histogram passes, kernel launches), the digit width
-    std::vector<ListAnswer> lst; uint32_t lstBuilt = 0, lstReused = 0, lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
+    std::vector<ListAnswer> lst; MaskUse lstMasks; uint32_t lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
     // infx_engine_range_facets: one answer per request of the session's last call; masks built and reused and k_range_counts launches of that call
-    std::vector<RangeAnswer> rng; uint32_t rngBuilt = 0, rngReused = 0, rngLaunches = 0;
+    std::vector<RangeAnswer> rng; MaskUse rngMasks; uint32_t rngLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -176,10 +181,22 @@ static int32_t query_cov_check(infx_session* S, uint32_t nq);
 static int32_t query_pre_check(infx_session* S, uint32_t nq);
 static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static void clear_query_prefilters(infx_session* S);
-static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, std::vector<int>& builtSlots);
-static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots);
-static int32_t staged_failed(infx_session* S, std::vector<int>& builtSlots, int32_t rc);
-static void take_prefilter_counts(infx_session* S, uint32_t nq, const std::vector<int>& builtSlots);
+// The filter and mask part of one call over the documents that filters accept: a batch with pre-filters, infx_engine_prefilter_mask, _list_documents,
+// _range_facets.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
+// the session's mask cache, mask(i) is request i's; the device call that follows ends in failed(rc) or done().  (Defined with the mask cache, below.)
+struct MaskCall {
+    infx_session* S; MaskUse* use;                // use: where the call's kind keeps its masks built / reused, beside the session's pre* counters
+    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of;      // the distinct filters; request i's among them (-1: none)
+    std::vector<uint8_t*> masks; std::vector<int> built;      // exprs[k]'s device flags; the slots the call builds
+    MaskCall(infx_session* S, uint32_t nreq, MaskUse* use = nullptr) : S(S), use(use), of(nreq, -1) {}
+    void add(uint32_t i, const std::string& expr);      // request i has filter expr, which is known to compile
+    int32_t intern(uint32_t i, const char* expr);        // request i has filter expr: compiled on first sight, a failure (message in g_eerr) is the request's.  Caller holds filterMu
+    int32_t acquire();                                   // once per call, nothing holding filterMu; without a filter only zeroes the pre* counters
+    uint8_t* mask(uint32_t i) const { return of[i] >= 0 ? masks[of[i]] : nullptr; }
+    int32_t failed(int32_t rc);                          // the device call failed: its message is kept, nothing stays staged
+    void done(uint32_t nq = 0);                          // it succeeded: the built masks' counts, the statistics (nq: the batch whose queries' counts to take)
+};
+static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, MaskCall& pre);
 static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
 static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len);
@@ -1211,13 +1228,13 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     rc = stage_long_queries(S, FI); if (rc) return rc;
     rc = stage_coverage_setup(S, nq, true); if (rc) return rc;
     // Pre-filters: the masks the batch is missing are staged on the session's stream (one launch in front of the batch, no host wait), each query's flags installed
-    std::vector<int> builtSlots;
-    rc = stage_prefilters(e, S, nq, fq, builtSlots); if (rc) return rc;
+    MaskCall pre(S, nq);
+    rc = stage_prefilters(S, nq, fq, pre); if (rc) return rc;
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
-    if (rc) return staged_failed(S, builtSlots, rc);
-    take_prefilter_counts(S, nq, builtSlots);
+    if (rc) return pre.failed(rc);
+    pre.done(nq);
     B.t3 = now_ms();
     // Kernel durations are resolved when somebody asks (infx_engine_session_last_timings): every hipEventElapsedTime is a HIP API call that queues behind the
     // launches of the other sessions (measured: 2.8-3.3 ms of "post" time per batch on two of three boxes with six sessions).
@@ -2377,6 +2394,22 @@ static int32_t copy_message(const std::string& t, char* out, int32_t cap) {
     if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
     return (int32_t)t.size();
 }
+// The readers of a per-request call, over answer_at(): the answer's message (its length; -1 without an answer), the size of its set with its status
+// (INFX_EINVAL and `none` without an answer)
+static int32_t answer_error(const Answer* a, char* out, int32_t cap) { return a ? copy_message(a->err, out, cap) : -1; }
+static int32_t answer_total(const Answer* a, uint32_t* total, const char* none) {
+    if (!a || !total) return efail(INFX_EINVAL, none);
+    *total = a->total;
+    return a->status;
+}
+// the getters of a call's counters: each value to its destination, where one was given
+static int32_t put_stats(std::initializer_list<std::pair<uint32_t*, uint32_t>> to) { for (auto& p : to) if (p.first) *p.first = p.second; return INFX_OK; }
+// the engine's column of a field name, -1: none (case sensitive, as the filter's fields)
+static int32_t column_named(const infx_engine* e, const char* name) {
+    int32_t col = -1;
+    for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == name) col = (int32_t)c;
+    return col;
+}
 
 // ---- Infiscript post-filter + facets (config 5): Query.Filter / Query.EnableFacets (SearchEngine.cs:298-316) ------------------------------
 // One non-indexed document field for all documents (DocumentFields / Field.Value), by internal id: kind 1 int64, 2 double, 3 UTF-8 strings
@@ -2585,8 +2618,7 @@ int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* e
 }
 // the column of a SortBy field (0xFFFFFFFF: no such field); the first use of a column builds and uploads its sort rank.  Caller holds e->filterMu.
 static int32_t sort_column(infx_engine* e, const char* field, uint32_t* out) {
-    uint32_t col = 0xFFFFFFFFu;
-    for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == field) col = (uint32_t)c;      // case sensitive, as the filter's fields
+    const uint32_t col = (uint32_t)column_named(e, field);
     if (col != 0xFFFFFFFFu) {
         if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
         if (!e->sortRanked[col]) {
@@ -2751,9 +2783,7 @@ int32_t infx_engine_last_in_filter(infx_session* S, uint32_t nq, uint32_t* out) 
 }
 int32_t infx_engine_last_count_stats(infx_session* S, uint32_t* counted, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    if (counted) *counted = S->lastCounted;
-    if (launches) *launches = S->lastCountLaunches;
-    return INFX_OK;
+    return put_stats({{counted, S->lastCounted}, {launches, S->lastCountLaunches}});
 }
 int32_t infx_engine_last_browse_stats(infx_session* S, uint32_t* groups, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
@@ -2935,26 +2965,42 @@ static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* ou
     }
     clear_query_prefilters(S);
 }
-// a device call of a batch with staged masks failed: its message is kept, nothing stays staged
-static int32_t staged_failed(infx_session* S, std::vector<int>& builtSlots, int32_t rc) {
-    g_eerr = infx_last_error(); unstage_prefilters(S, builtSlots); builtSlots.clear();
+static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots) {
+    for (int b : builtSlots) S->preMask[b].valid = false;
+    if (S->stream) { infx_filter_masks(S->stream, 0, nullptr, nullptr, nullptr); infx_stream_set_doc_masks(S->stream, 0, nullptr); }
+}
+void MaskCall::add(uint32_t i, const std::string& expr) {
+    auto it = idx.find(expr);
+    if (it == idx.end()) { it = idx.emplace(expr, (int)exprs.size()).first; exprs.push_back(expr); }
+    of[i] = it->second;
+}
+int32_t MaskCall::intern(uint32_t i, const char* expr) {
+    CompiledFilter* cf = nullptr;
+    if (!idx.count(expr)) { const int32_t rc = compile_filter(S->e, expr, &cf, false); if (rc) return rc; }      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
+    add(i, expr);
+    return INFX_OK;
+}
+int32_t MaskCall::failed(int32_t rc) {
+    g_eerr = infx_last_error(); unstage_prefilters(S, built); built.clear();
     return rc;
 }
-// The masks of `exprs` (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: masks[k] = the device flags of exprs[k]'s slot; the ones that have to be built
-// are staged on the stream as ONE build (infx_filter_masks) and listed in builtSlots — their counts land in S->preCountBuf, in that order, when the stream is next
+// The masks of exprs (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: masks[k] = the device flags of exprs[k]'s slot; the ones that have to be built
+// are staged on the stream as ONE build (infx_filter_masks) and listed in `built` — their counts land in S->preCountBuf, in that order, when the stream is next
 // waited for.  A failure leaves nothing staged.
-static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<std::string>& exprs, std::vector<uint8_t*>& masks, std::vector<int>& builtSlots) {
+int32_t MaskCall::acquire() {
+    infx_engine* e = S->e;
+    S->preBuilt = S->preReused = S->preLaunches = 0;
+    if (exprs.empty()) return INFX_OK;
     const uint64_t ep = e->maskEpoch.load(); const uint64_t tick = ++S->preTick;
     std::vector<int> slots(exprs.size(), -1);
-    masks.assign(exprs.size(), nullptr); builtSlots.clear();
-    auto bail = [&](int32_t rc) { unstage_prefilters(S, builtSlots); builtSlots.clear(); return rc; };
-    S->preBuilt = S->preReused = S->preLaunches = 0;
+    masks.assign(exprs.size(), nullptr); built.clear();
+    auto bail = [&](int32_t rc) { unstage_prefilters(S, built); built.clear(); return rc; };
     for (size_t k = 0; k < exprs.size(); k++)
         for (int i = 0; i < INFX_MAX_PREFILTERS; i++) { PreMask& M = S->preMask[i]; if (M.valid && M.epoch == ep && M.expr == exprs[k]) { slots[k] = i; M.lastUse = tick; S->preReused++; break; } }
     std::vector<infx_filter_prog> progs; std::vector<uint8_t*> ptrs;
     std::lock_guard<std::mutex> lk(e->filterMu);
     for (size_t k = 0; k < exprs.size(); k++) {
-        if (slots[k] >= 0) { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[k], &masks[k]); if (rc) return staged_failed(S, builtSlots, rc); continue; }
+        if (slots[k] >= 0) { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[k], &masks[k]); if (rc) return failed(rc); continue; }
         int best = -1;      // a slot of an earlier epoch or an empty one first, else the least recently used that this batch does not use
         for (int i = 0; i < INFX_MAX_PREFILTERS; i++) {
             PreMask& M = S->preMask[i];
@@ -2967,52 +3013,43 @@ static int32_t acquire_masks(infx_engine* e, infx_session* S, const std::vector<
         if (best < 0) return bail(efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch"));
         CompiledFilter* cf = nullptr;
         { int32_t rc = compile_filter(e, exprs[k].c_str(), &cf, false); if (rc) return bail(rc); }
-        { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &masks[k]); if (rc) return staged_failed(S, builtSlots, rc); }
+        { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &masks[k]); if (rc) return failed(rc); }
         PreMask& M = S->preMask[best]; M.expr = exprs[k]; M.epoch = ep; M.lastUse = tick; M.count = 0; M.valid = true;
-        builtSlots.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(masks[k]);
+        built.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(masks[k]);
     }
-    if (!builtSlots.empty()) {
+    if (!built.empty()) {
         int32_t rc = infx_filter_masks(S->stream, (uint32_t)progs.size(), progs.data(), ptrs.data(), S->preCountBuf);
-        if (rc) return staged_failed(S, builtSlots, rc);
-        S->preBuilt = (uint32_t)builtSlots.size();
+        if (rc) return failed(rc);
+        S->preBuilt = (uint32_t)built.size();
     }
     return INFX_OK;
 }
-static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots) {
-    for (int b : builtSlots) S->preMask[b].valid = false;
-    if (S->stream) { infx_filter_masks(S->stream, 0, nullptr, nullptr, nullptr); infx_stream_set_doc_masks(S->stream, 0, nullptr); }
-}
 // Before the batch's infx_search_fused: refuses a pre-filter on a browse query, finds or stages the masks, installs each query's flags on the stream
-static int32_t stage_prefilters(infx_engine* e, infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, std::vector<int>& builtSlots) {
-    builtSlots.clear();
-    S->lastInPre.assign(nq, 0); S->preBuilt = S->preReused = S->preLaunches = 0;
-    if (!S->qp.on || S->qp.nq != nq) return INFX_OK;
+static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, MaskCall& pre) {
+    S->lastInPre.assign(nq, 0);
     QueryPre& Q = S->qp;
-    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nq, -1);
-    for (uint32_t i = 0; i < nq; i++) {
+    const uint32_t n = Q.on && Q.nq == nq ? nq : 0;      // (the pre-filters were installed for this batch)
+    for (uint32_t i = 0; i < n; i++) {
         if (!Q.has[i] || Q.reject[i]) continue;
         if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: Filter already restricts the scan
             Q.reject[i] = 1; Q.status[i] = INFX_EUNSUPPORTED; Q.err[i] = "a pre-filter does not apply to a browse query (empty text with EnableFacets): its Filter already restricts the scan";
             fq[i].flags &= ~INFX_FQ_BROWSE;
             continue;
         }
-        auto it = idx.find(Q.expr[i]);
-        if (it == idx.end()) { it = idx.emplace(Q.expr[i], (int)exprs.size()).first; exprs.push_back(Q.expr[i]); }
-        of[i] = it->second;
+        pre.add(i, Q.expr[i]);      // (compiled by infx_engine_set_query_prefilters)
     }
-    if (exprs.empty()) return INFX_OK;
-    std::vector<uint8_t*> found;
-    { int32_t rc = acquire_masks(e, S, exprs, found, builtSlots); if (rc) return rc; }
+    { int32_t rc = pre.acquire(); if (rc) return rc; }
+    if (pre.exprs.empty()) return INFX_OK;
     std::vector<const uint8_t*> masks(nq, nullptr);
-    for (uint32_t i = 0; i < nq; i++) if (of[i] >= 0) masks[i] = found[of[i]];
+    for (uint32_t i = 0; i < nq; i++) masks[i] = pre.mask(i);
     int32_t rc = infx_stream_set_doc_masks(S->stream, nq, masks.data());
-    if (rc) return staged_failed(S, builtSlots, rc);
-    return INFX_OK;
+    return rc ? pre.failed(rc) : INFX_OK;
 }
-// After the batch: the counts of the masks it built have landed; each pre-filtered query's count
-static void take_prefilter_counts(infx_session* S, uint32_t nq, const std::vector<int>& builtSlots) {
-    for (size_t k = 0; k < builtSlots.size(); k++) S->preMask[builtSlots[k]].count = S->preCountBuf[k];
-    if (!builtSlots.empty()) { uint32_t b = 0, l = 0; infx_last_filter_mask_stats(S->stream, &b, &l); S->preLaunches = l; }
+// After the call: the counts of the masks it built have landed; what it built and reused; each pre-filtered query's count
+void MaskCall::done(uint32_t nq) {
+    for (size_t k = 0; k < built.size(); k++) S->preMask[built[k]].count = S->preCountBuf[k];
+    if (!built.empty()) { uint32_t b = 0, l = 0; infx_last_filter_mask_stats(S->stream, &b, &l); S->preLaunches = l; }
+    if (use) *use = MaskUse{S->preBuilt, S->preReused};
     if (!S->qp.on || S->qp.nq != nq) return;
     const uint64_t ep = S->e->maskEpoch.load();
     for (uint32_t i = 0; i < nq; i++) {
@@ -3028,10 +3065,7 @@ int32_t infx_engine_last_in_prefilter(infx_session* S, uint32_t nq, uint32_t* ou
 }
 int32_t infx_engine_last_prefilter_stats(infx_session* S, uint32_t* built, uint32_t* reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    if (built) *built = S->preBuilt;
-    if (reused) *reused = S->preReused;
-    if (launches) *launches = S->preLaunches;
-    return INFX_OK;
+    return put_stats({{built, S->preBuilt}, {reused, S->preReused}, {launches, S->preLaunches}});
 }
 int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* out_bytes, uint64_t cap) {
     if (!S || !expr || !out_bytes) return efail(INFX_EINVAL, "null argument");
@@ -3040,13 +3074,13 @@ int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* o
     if (engine_sharded(e)) return efail(INFX_EUNSUPPORTED, "a pre-filter needs an engine that is not sharded");
     const uint64_t N = (uint64_t)e->ix.N;
     if (cap < N) return efail(INFX_EINVAL, "the mask holds one byte per indexed document");
-    { std::lock_guard<std::mutex> lk(e->filterMu); CompiledFilter* cf = nullptr; int32_t rc = compile_filter(e, expr, &cf, false); if (rc) return rc; }
-    std::vector<uint8_t*> masks; std::vector<int> built;
-    { int32_t rc = acquire_masks(e, S, {std::string(expr)}, masks, built); if (rc) return rc; }
+    MaskCall mc(S, 1);
+    { std::lock_guard<std::mutex> lk(e->filterMu); int32_t rc = mc.intern(0, expr); if (rc) return rc; }
+    { int32_t rc = mc.acquire(); if (rc) return rc; }
     int32_t rc = infx_stream_wait(S->stream);      // builds what was staged
-    if (rc) return staged_failed(S, built, rc);
-    take_prefilter_counts(S, 0, built);
-    if (N) rc = infx_stream_copy(S->stream, out_bytes, masks[0], N);
+    if (rc) return mc.failed(rc);
+    mc.done();
+    if (N) rc = infx_stream_copy(S->stream, out_bytes, mc.mask(0), N);
     if (!rc) rc = infx_stream_wait(S->stream);
     if (rc) { g_eerr = infx_last_error(); return rc; }
     return INFX_OK;
@@ -3113,7 +3147,7 @@ int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* con
             while (e->ffCache.size() > e->ffCacheLimit) { e->ffCache.erase(e->ffLru.back()); e->ffLru.pop_back(); }
         }
     }
-    for (uint32_t i = 0; i < k; i++) if (exprs[i]) S->ff[i] = answer[exprs[i]];
+    for (uint32_t i = 0; i < k; i++) if (exprs[i]) { S->ff[i] = answer[exprs[i]]; if (S->ff[i].r) S->ff[i].total = S->ff[i].r->total; }
     if (out_status) for (uint32_t i = 0; i < k; i++) out_status[i] = S->ff[i].status;
     return INFX_OK;
 }
@@ -3127,20 +3161,23 @@ int32_t infx_engine_facets_filtered_column(infx_session* S, uint32_t which, uint
 }
 // the live documents expression `which` accepts (0 for a refused one, whose status is returned)
 int32_t infx_engine_facets_filtered_total(infx_session* S, uint32_t which, uint32_t* total) {
-    if (!S || !total || which >= S->ff.size()) return efail(INFX_EINVAL, "no such expression in the session's last filtered-facet call");
-    *total = S->ff[which].r ? S->ff[which].r->total : 0;
-    return S->ff[which].status;
+    return answer_total(answer_at(S ? &S->ff : nullptr, which), total, "no such expression in the session's last filtered-facet call");
 }
 // the message of expression `which`'s refusal ("" if it was counted); returns its length, -1 out of range
-int32_t infx_engine_facets_filtered_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
-    if (!S || which >= S->ff.size()) return -1;
-    return copy_message(S->ff[which].err, out, cap);
-}
+int32_t infx_engine_facets_filtered_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->ff : nullptr, which), out, cap); }
 int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counted, uint32_t* cached, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    if (counted) *counted = S->ffCounted;
-    if (cached) *cached = S->ffCached;
-    if (launches) *launches = S->ffLaunches;
+    return put_stats({{counted, S->ffCounted}, {cached, S->ffCached}, {launches, S->ffLaunches}});
+}
+
+// ---- requests over the documents a filter accepts: infx_engine_list_documents and infx_engine_range_facets -------------------------------------------
+// Both take up to INFX_MAX_PREFILTERS requests, answer each on its own (a refusal is the request's: its status in out_status[i], its message with the answer)
+// and leave the answers on the session for the readers.  A call that fails as a whole leaves no answers behind — the readers refuse — while the statuses
+// already written to out_status stay.  The filters and their masks are a MaskCall's.
+// what such a call needs of the engine (`what` names the call in the message)
+static int32_t need_indexed_device(const infx_session* S, const char* what) {
+    if (!S->e->dev || !S->stream) return efail(INFX_EHIP, std::string("no GPU: ") + what + " runs on the device");
+    if (!S->e->indexed) return efail(INFX_EINVAL, std::string(what) + " before index_documents");
     return INFX_OK;
 }
 
@@ -3151,7 +3188,7 @@ int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counte
 int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_list_request* reqs, int32_t* out_status) {
     if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    S->lst.clear(); S->lstBuilt = S->lstReused = S->lstPasses = S->lstLaunches = 0;
+    S->lst.clear(); S->lstMasks = MaskUse(); S->lstPasses = S->lstLaunches = 0;
     if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) listing requests in one call");
     S->lst.assign(nreq, ListAnswer());
     auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->lst[i].status = rc; S->lst[i].err = msg; if (out_status) out_status[i] = rc; };
@@ -3160,10 +3197,8 @@ int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_li
         if (reqs[i].limit < 1 || reqs[i].limit > INFX_POST_MAX_ROWS) refuse(i, INFX_EINVAL, "a listing's limit is 1 .. 1024");
         else if (reqs[i].offset >= 0x80000000u) refuse(i, INFX_EINVAL, "a listing's offset is below 2^31");
     }
-    // a call that fails as a whole leaves no answers behind: the readers refuse (the statuses already written to out_status stay)
-    if (!e->dev || !S->stream) { S->lst.clear(); return efail(INFX_EHIP, "no GPU: list_documents runs on the device"); }
-    if (!e->indexed) { S->lst.clear(); return efail(INFX_EINVAL, "list_documents before index_documents"); }
-    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nreq, -1); std::vector<int32_t> col(nreq, -1);
+    { int32_t rc = need_indexed_device(S, "list_documents"); if (rc) { S->lst.clear(); return rc; } }
+    MaskCall mc(S, nreq, &S->lstMasks); std::vector<int32_t> col(nreq, -1);
     {
         std::lock_guard<std::mutex> lk(e->filterMu);
         for (uint32_t i = 0; i < nreq; i++) {
@@ -3175,35 +3210,23 @@ int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_li
                 if (c == 0xFFFFFFFFu) { refuse(i, INFX_EINVAL, std::string("list_documents: no field named '") + reqs[i].order_by + "'"); continue; }
                 col[i] = (int32_t)c;
             }
-            if (!reqs[i].filter) continue;
-            auto it = idx.find(reqs[i].filter);
-            if (it == idx.end()) {
-                CompiledFilter* cf = nullptr;
-                const int32_t rc = compile_filter(e, reqs[i].filter, &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
-                if (rc) { refuse(i, rc, g_eerr); continue; }
-                it = idx.emplace(reqs[i].filter, (int)exprs.size()).first; exprs.push_back(reqs[i].filter);
-            }
-            of[i] = it->second;
+            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) refuse(i, rc, g_eerr); }
         }
     }
-    std::vector<uint8_t*> masks; std::vector<int> built;
-    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, masks, built); if (rc) { S->lst.clear(); return rc; } }
-    else S->preBuilt = S->preReused = S->preLaunches = 0;
+    { int32_t rc = mc.acquire(); if (rc) { S->lst.clear(); return rc; } }
     std::vector<infx_list_req> dr; std::vector<uint32_t> who;
     for (uint32_t i = 0; i < nreq; i++) {
         if (S->lst[i].status) continue;
         infx_list_req R{};
-        if (of[i] >= 0) R.mask = masks[of[i]];
-        R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
+        R.mask = mc.mask(i); R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
         dr.push_back(R); who.push_back(i);
     }
     const size_t m = dr.size(), rows = INFX_POST_MAX_ROWS;
     std::vector<int64_t> keys(std::max<size_t>(m, 1) * rows); std::vector<int32_t> docs(std::max<size_t>(m, 1) * rows); std::vector<uint32_t> codes(std::max<size_t>(m, 1) * rows);
     std::vector<uint32_t> counts(std::max<size_t>(m, 1), 0), totals(std::max<size_t>(m, 1), 0);
     int32_t rc = infx_list_ordered(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), counts.data(), totals.data());
-    if (rc) { S->lst.clear(); return staged_failed(S, built, rc); }
-    take_prefilter_counts(S, 0, built);
-    S->lstBuilt = S->preBuilt; S->lstReused = S->preReused;
+    if (rc) { S->lst.clear(); return mc.failed(rc); }
+    mc.done();
     infx_last_list_stats(S->stream, &S->lstPasses, &S->lstLaunches);
     for (size_t j = 0; j < m; j++) {
         ListAnswer& A = S->lst[who[j]];
@@ -3216,29 +3239,20 @@ int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_li
 }
 // request `which` of the session's last infx_engine_list_documents: up to cap rows; returns the page's row count, -1 on error (also for a refused request)
 int32_t infx_engine_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap) {
-    if (!S || which >= S->lst.size() || S->lst[which].status || (cap > 0 && (!keys || !docs || !codes))) return -1;
-    const ListAnswer& A = S->lst[which];
-    const size_t c = std::min<size_t>(A.keys.size(), (size_t)std::max(cap, 0));
-    if (c) { std::memcpy(keys, A.keys.data(), c * 8); std::memcpy(docs, A.docs.data(), c * 4); std::memcpy(codes, A.codes.data(), c * 4); }
-    return (int32_t)A.keys.size();
+    const ListAnswer* A = answer_at(S ? &S->lst : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!keys || !docs || !codes))) return -1;
+    const size_t c = std::min<size_t>(A->keys.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(keys, A->keys.data(), c * 8); std::memcpy(docs, A->docs.data(), c * 4); std::memcpy(codes, A->codes.data(), c * 4); }
+    return (int32_t)A->keys.size();
 }
 // the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_list_total(infx_session* S, uint32_t which, uint32_t* total) {
-    if (!S || !total || which >= S->lst.size()) return efail(INFX_EINVAL, "no such request in the session's last list_documents call");
-    *total = S->lst[which].total;
-    return S->lst[which].status;
+    return answer_total(answer_at(S ? &S->lst : nullptr, which), total, "no such request in the session's last list_documents call");
 }
-int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
-    if (!S || which >= S->lst.size()) return -1;
-    return copy_message(S->lst[which].err, out, cap);
-}
+int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->lst : nullptr, which), out, cap); }
 int32_t infx_engine_last_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    if (masks_built) *masks_built = S->lstBuilt;
-    if (masks_reused) *masks_reused = S->lstReused;
-    if (hist_passes) *hist_passes = S->lstPasses;
-    if (launches) *launches = S->lstLaunches;
-    return INFX_OK;
+    return put_stats({{masks_built, S->lstMasks.built}, {masks_reused, S->lstMasks.reused}, {hist_passes, S->lstPasses}, {launches, S->lstLaunches}});
 }
 int32_t infx_engine_set_list_digit_bits(infx_session* S, int32_t bits) {
     if (!S || bits < 4 || bits > 11) return efail(INFX_EINVAL, "the digit width of list_documents is 4 .. 11 bits");
@@ -3273,44 +3287,57 @@ static int32_t range_index(infx_engine* e, uint32_t col, const infx_engine::Rang
     return INFX_OK;
 }
 static int column_kind(const filt::Column& c) { return c.dict.empty() ? 0 : c.dict[0].kind; }
+// What is wrong with request Q before anything of it is looked at on the device — the field, its kind, the edges, in this order — as the request's status, the
+// text in *why; INFX_OK with the field's column and the kind of the edges (1 int64, 2 double).  Caller holds e->filterMu.
+static int32_t range_request_check(const infx_engine* e, const infx_range_request& Q, int32_t* col, int* kind, std::string* why) {
+    auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
+    if (!Q.field) return bad("range_facets needs a field");
+    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("range_facets: no field named '") + Q.field + "'");
+    int k = column_kind(e->columns[*col]);
+    if (k == 3) return bad(std::string("range_facets: field '") + Q.field + "' is a string column; ranges need an int64 or a double column");
+    if (k == 0) k = Q.edges_i ? 1 : 2;                              // (a column without a value)
+    *kind = k;
+    if (Q.nedges < 2 || Q.nedges > INFX_RANGE_MAX_EDGES) return bad("range_facets takes 2 to 257 edges (1 to 256 buckets)");
+    if (k == 1) {
+        if (!Q.edges_i) return bad("integer column needs integer edges");
+        for (uint32_t j = 1; j < Q.nedges; j++) if (!(Q.edges_i[j - 1] < Q.edges_i[j])) return bad("the edges of range_facets are strictly increasing");
+    } else {
+        if (!Q.edges_d) return bad("double column needs double edges");
+        for (uint32_t j = 0; j < Q.nedges; j++) {
+            if (std::isnan(Q.edges_d[j])) return bad("an edge of range_facets is not a NaN");
+            if (j && !(Q.edges_d[j - 1] < Q.edges_d[j])) return bad("the edges of range_facets are strictly increasing (-0.0 and 0.0 compare equal)");
+        }
+    }
+    return INFX_OK;
+}
+// The edges of Q as thresholds over column c's ranks: the ranks' values ascend under sort_cmp, thr[j] = the first rank whose value is not below edge j
+static std::vector<uint32_t> range_thresholds(const filt::Column& c, const infx_engine::RangeIndex& X, const infx_range_request& Q, int kind) {
+    std::vector<uint32_t> thr(Q.nedges);
+    for (uint32_t j = 0; j < Q.nedges; j++) {
+        filt::Boxed edge; edge.kind = kind; if (kind == 1) edge.i = Q.edges_i[j]; else edge.d = Q.edges_d[j];
+        thr[j] = (uint32_t)(std::partition_point(X.codeOfRank.begin(), X.codeOfRank.end(), [&](uint32_t code) { return filt::sort_cmp(c.dict[code], edge) < 0; }) - X.codeOfRank.begin());
+    }
+    return thr;
+}
 int32_t infx_engine_range_facets(infx_session* S, uint32_t nreq, const infx_range_request* reqs, int32_t* out_status) {
     if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    S->rng.clear(); S->rngBuilt = S->rngReused = S->rngLaunches = 0;
+    S->rng.clear(); S->rngMasks = MaskUse(); S->rngLaunches = 0;
     if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) range requests in one call");
     S->rng.assign(nreq, RangeAnswer());
     auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->rng[i].status = rc; S->rng[i].err = msg; if (out_status) out_status[i] = rc; };
     std::vector<int32_t> col(nreq, -1); std::vector<int> kind(nreq, 0);
     {
-        // what needs no device: the field, its kind and the edges
         std::lock_guard<std::mutex> lk(e->filterMu);
         for (uint32_t i = 0; i < nreq; i++) {
-            const infx_range_request& Q = reqs[i];
+            std::string why;
             if (out_status) out_status[i] = INFX_OK;
-            if (!Q.field) { refuse(i, INFX_EINVAL, "range_facets needs a field"); continue; }
-            for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == Q.field) col[i] = (int32_t)c;      // case sensitive, as the filter's fields
-            if (col[i] < 0) { refuse(i, INFX_EINVAL, std::string("range_facets: no field named '") + Q.field + "'"); continue; }
-            int k = column_kind(e->columns[col[i]]);
-            if (k == 3) { refuse(i, INFX_EINVAL, std::string("range_facets: field '") + Q.field + "' is a string column; ranges need an int64 or a double column"); continue; }
-            if (k == 0) k = Q.edges_i ? 1 : 2;                              // (a column without a value)
-            kind[i] = k;
-            if (Q.nedges < 2 || Q.nedges > INFX_RANGE_MAX_EDGES) { refuse(i, INFX_EINVAL, "range_facets takes 2 to 257 edges (1 to 256 buckets)"); continue; }
-            if (k == 1) {
-                if (!Q.edges_i) { refuse(i, INFX_EINVAL, "integer column needs integer edges"); continue; }
-                for (uint32_t j = 1; j < Q.nedges && !S->rng[i].status; j++) if (!(Q.edges_i[j - 1] < Q.edges_i[j])) refuse(i, INFX_EINVAL, "the edges of range_facets are strictly increasing");
-            } else {
-                if (!Q.edges_d) { refuse(i, INFX_EINVAL, "double column needs double edges"); continue; }
-                for (uint32_t j = 0; j < Q.nedges && !S->rng[i].status; j++) {
-                    if (std::isnan(Q.edges_d[j])) refuse(i, INFX_EINVAL, "an edge of range_facets is not a NaN");
-                    else if (j && !(Q.edges_d[j - 1] < Q.edges_d[j])) refuse(i, INFX_EINVAL, "the edges of range_facets are strictly increasing (-0.0 and 0.0 compare equal)");
-                }
-            }
+            const int32_t rc = range_request_check(e, reqs[i], &col[i], &kind[i], &why);
+            if (rc) refuse(i, rc, why);
         }
     }
-    // a call that fails as a whole leaves no answers behind: the readers refuse (the statuses already written to out_status stay)
-    if (!e->dev || !S->stream) { S->rng.clear(); return efail(INFX_EHIP, "no GPU: range_facets runs on the device"); }
-    if (!e->indexed) { S->rng.clear(); return efail(INFX_EINVAL, "range_facets before index_documents"); }
-    std::vector<std::string> exprs; std::unordered_map<std::string, int> idx; std::vector<int> of(nreq, -1);
+    { int32_t rc = need_indexed_device(S, "range_facets"); if (rc) { S->rng.clear(); return rc; } }
+    MaskCall mc(S, nreq, &S->rngMasks);
     std::vector<std::vector<uint32_t>> thr(nreq); std::vector<uint32_t> nanRanks(nreq, 0);
     {
         std::lock_guard<std::mutex> lk(e->filterMu);
@@ -3319,43 +3346,24 @@ int32_t infx_engine_range_facets(infx_session* S, uint32_t nreq, const infx_rang
             const infx_range_request& Q = reqs[i];
             const infx_engine::RangeIndex* X = nullptr;
             { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }
-            if (Q.filter) {
-                auto it = idx.find(Q.filter);
-                if (it == idx.end()) {
-                    CompiledFilter* cf = nullptr;
-                    const int32_t rc = compile_filter(e, Q.filter, &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
-                    if (rc) { refuse(i, rc, g_eerr); continue; }
-                    it = idx.emplace(Q.filter, (int)exprs.size()).first; exprs.push_back(Q.filter);
-                }
-                of[i] = it->second;
-            }
-            const filt::Column& c = e->columns[col[i]];
+            if (Q.filter) { const int32_t rc = mc.intern(i, Q.filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
             nanRanks[i] = X->nanRanks;
-            thr[i].resize(Q.nedges);
-            for (uint32_t j = 0; j < Q.nedges; j++) {
-                filt::Boxed edge; edge.kind = kind[i]; if (kind[i] == 1) edge.i = Q.edges_i[j]; else edge.d = Q.edges_d[j];
-                // the ranks' values ascend under sort_cmp: the first rank whose value is not below the edge
-                thr[i][j] = (uint32_t)(std::partition_point(X->codeOfRank.begin(), X->codeOfRank.end(), [&](uint32_t code) { return filt::sort_cmp(c.dict[code], edge) < 0; }) - X->codeOfRank.begin());
-            }
+            thr[i] = range_thresholds(e->columns[col[i]], *X, Q, kind[i]);
         }
     }
-    std::vector<uint8_t*> masks; std::vector<int> built;
-    if (!exprs.empty()) { int32_t rc = acquire_masks(e, S, exprs, masks, built); if (rc) { S->rng.clear(); return rc; } }
-    else S->preBuilt = S->preReused = S->preLaunches = 0;
+    { int32_t rc = mc.acquire(); if (rc) { S->rng.clear(); return rc; } }
     std::vector<infx_range_req> dr; std::vector<uint32_t> who;
     for (uint32_t i = 0; i < nreq; i++) {
         if (S->rng[i].status) continue;
         infx_range_req R{};
-        if (of[i] >= 0) R.mask = masks[of[i]];
-        R.col = col[i]; R.nedges = reqs[i].nedges; R.nan_ranks = nanRanks[i]; R.thr = thr[i].data();
+        R.mask = mc.mask(i); R.col = col[i]; R.nedges = reqs[i].nedges; R.nan_ranks = nanRanks[i]; R.thr = thr[i].data();
         dr.push_back(R); who.push_back(i);
     }
     const size_t m = dr.size();
     std::vector<uint32_t> counts(std::max<size_t>(m, 1) * INFX_RANGE_SLOTS, 0), lo(std::max<size_t>(m, 1), 0xFFFFFFFFu), hi(std::max<size_t>(m, 1), 0);
     int32_t rc = infx_range_counts(S->stream, (uint32_t)m, dr.data(), counts.data(), lo.data(), hi.data());
-    if (rc) { S->rng.clear(); return staged_failed(S, built, rc); }
-    take_prefilter_counts(S, 0, built);
-    S->rngBuilt = S->preBuilt; S->rngReused = S->preReused;
+    if (rc) { S->rng.clear(); return mc.failed(rc); }
+    mc.done();
     { uint32_t r_ = 0; infx_last_range_stats(S->stream, &r_, &S->rngLaunches); }
     std::lock_guard<std::mutex> lk(e->filterMu);
     for (size_t j = 0; j < m; j++) {
@@ -3375,18 +3383,16 @@ int32_t infx_engine_range_facets(infx_session* S, uint32_t nreq, const infx_rang
 }
 // request `which` of the session's last infx_engine_range_facets: up to cap bucket counts; returns the number of buckets, -1 on error (also for a refused request)
 int32_t infx_engine_range_counts(infx_session* S, uint32_t which, uint32_t* counts, int32_t cap, uint32_t* below, uint32_t* above, uint32_t* nan) {
-    if (!S || which >= S->rng.size() || S->rng[which].status || (cap > 0 && !counts)) return -1;
-    const RangeAnswer& A = S->rng[which];
-    const size_t c = std::min<size_t>(A.counts.size(), (size_t)std::max(cap, 0));
-    if (c) std::memcpy(counts, A.counts.data(), c * 4);
-    if (below) *below = A.below; if (above) *above = A.above; if (nan) *nan = A.nan;
-    return (int32_t)A.counts.size();
+    const RangeAnswer* A = answer_at(S ? &S->rng : nullptr, which);
+    if (!A || A->status || (cap > 0 && !counts)) return -1;
+    const size_t c = std::min<size_t>(A->counts.size(), (size_t)std::max(cap, 0));
+    if (c) std::memcpy(counts, A->counts.data(), c * 4);
+    if (below) *below = A->below; if (above) *above = A->above; if (nan) *nan = A->nan;
+    return (int32_t)A->counts.size();
 }
 // the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_range_total(infx_session* S, uint32_t which, uint32_t* total) {
-    if (!S || !total || which >= S->rng.size()) return efail(INFX_EINVAL, "no such request in the session's last range_facets call");
-    *total = S->rng[which].total;
-    return S->rng[which].status;
+    return answer_total(answer_at(S ? &S->rng : nullptr, which), total, "no such request in the session's last range_facets call");
 }
 // the smallest and largest non-NaN value of request `which`'s set: *kind 1 -> lo_i / hi_i, 2 -> lo_d / hi_d, 0 -> there is none
 int32_t infx_engine_range_minmax(infx_session* S, uint32_t which, int32_t* kind, int64_t* lo_i, int64_t* hi_i, double* lo_d, double* hi_d) {
@@ -3396,16 +3402,10 @@ int32_t infx_engine_range_minmax(infx_session* S, uint32_t which, int32_t* kind,
     if (lo_i) *lo_i = A.loI; if (hi_i) *hi_i = A.hiI; if (lo_d) *lo_d = A.loD; if (hi_d) *hi_d = A.hiD;
     return A.status;
 }
-int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int32_t cap) {
-    if (!S || which >= S->rng.size()) return -1;
-    return copy_message(S->rng[which].err, out, cap);
-}
+int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->rng : nullptr, which), out, cap); }
 int32_t infx_engine_last_range_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    if (masks_built) *masks_built = S->rngBuilt;
-    if (masks_reused) *masks_reused = S->rngReused;
-    if (launches) *launches = S->rngLaunches;
-    return INFX_OK;
+    return put_stats({{masks_built, S->rngMasks.built}, {masks_reused, S->rngMasks.reused}, {launches, S->rngLaunches}});
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

@@ -3010,6 +3010,18 @@ int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint
     if (launches) *launches = s->lastFfLaunches;
     return INFX_OK;
 }
+// ---- requests over document sets: a mask (null: every live document) and a column read through its sort rank ----
+// What infx_list_ordered and infx_range_counts ask of one request before anything is enqueued: the column uploaded with its sort rank and covering the corpus
+// (col < 0, a set in document order, only where !needCol), the mask a slot of this stream and large enough.  `what` names the request in the messages.
+static int32_t check_set_request(const infx_stream* s, const uint8_t* mask, int32_t col, bool needCol, const char* what) {
+    const infx_index* ix = s->ix;
+    if (col >= 0 || needCol) {
+        if (col < 0 || col >= FILT_MAXCOL || !ix->colCodes[col] || !ix->colRankOk[col]) return fail(INFX_EINVAL, "the %s's column or its sort rank was not uploaded", what);
+        int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, col); if (rc_) return rc_;
+    }
+    if (mask) { const int slot = mask_slot_of(s, mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a %s's mask is not a mask slot of this stream, or was made for a smaller corpus", what); }
+    return INFX_OK;
+}
 // ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
 int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* counts_out, uint32_t* totals_out) {
     if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !counts_out || !totals_out))) return fail(INFX_EINVAL, "bad listing arguments%s");
@@ -3024,9 +3036,7 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
         if (Q.limit < 1 || Q.limit > INFX_POST_MAX_ROWS) return fail(INFX_EINVAL, "a listing's limit is 1 .. INFX_POST_MAX_ROWS (1024)%s");
         if (Q.offset >= 0x80000000u) return fail(INFX_EINVAL, "a listing's offset is below 2^31%s");
         if (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS) return fail(INFX_EINVAL, "a listing's digit width is 4 .. 11 bits%s");
-        if (Q.col >= 0 && (Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col] || !ix->colRankOk[Q.col])) return fail(INFX_EINVAL, "the listing's column or its sort rank was not uploaded%s");
-        if (Q.col >= 0) { int32_t rc_ = columns_cover(ix, n, COLS_COVER_CORPUS, Q.col); if (rc_) return rc_; }
-        if (Q.mask) { const int slot = mask_slot_of(s, Q.mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a listing's mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "listing"); if (rc_) return rc_; }
         passes[i] = ls_passes(Q.col >= 0 ? ix->colValues[Q.col] : 1u, Q.digit_bits);
         histOff[i] = histWords; histWords += (size_t)passes[i] * 2u << Q.digit_bits;
     }
@@ -3102,12 +3112,10 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_range_req& Q = reqs[i];
         if (Q.nedges < RB_MIN_EDGES || Q.nedges > RB_MAX_EDGES || !Q.thr) return fail(INFX_EINVAL, "a range request has 2 .. INFX_RANGE_MAX_EDGES (257) thresholds%s");
-        if (Q.col < 0 || Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col] || !ix->colRankOk[Q.col]) return fail(INFX_EINVAL, "the range request's column or its sort rank was not uploaded%s");
-        if ((uint64_t)ix->colDocs[Q.col] < (uint64_t)n) return fail(INFX_EINVAL, "a column holds fewer rows than the corpus has documents%s");
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "range request"); if (rc_) return rc_; }
         if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
         for (uint32_t j = 0; j < Q.nedges; j++)
             if (Q.thr[j] < Q.nan_ranks || Q.thr[j] > ix->colValues[Q.col] || (j && Q.thr[j] < Q.thr[j - 1])) return fail(INFX_EINVAL, "a range request's thresholds are non-decreasing, from nan_ranks to the column's number of values%s");
-        if (Q.mask) { const int slot = mask_slot_of(s, Q.mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a range request's mask is not a mask slot of this stream, or was made for a smaller corpus%s"); }
         thrWords += Q.nedges;
     }
     HIPCHK(enter_device(ix->cfg.device));

@@ -435,20 +435,7 @@ class SearchEngine:
     def facets_of(self, sh, nq, i):
         """Facets of query i of the last batch (nq queries) searched on session handle sh with Query.EnableFacets: {field: [(value, count)]}, counts over
         the returned rows, (count desc, value asc) — Core/FacetBuilder.cs:19-105."""
-        facets = {}
-        for k in range(self.L.infx_engine_facet_column_count(sh)):
-            col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
-            m = self.L.infx_engine_last_facets(sh, nq, i, k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
-            if m < 0:
-                self._check(1)
-            if m > 0:
-                nb = C.create_string_buffer(256); self.L.infx_engine_column_info(self.h, col.value, nb, 256, None, None)
-                vals = []
-                for j in range(m):
-                    vb = C.create_string_buffer(1024); self.L.infx_engine_column_value(self.h, col.value, int(codes[j]), vb, 1024)
-                    vals.append((vb.value.decode(), int(cnts[j])))
-                facets[nb.value.decode()] = vals
-        return facets
+        return _facet_columns(self, self.L.infx_engine_facet_column_count(sh), lambda k, *out: self.L.infx_engine_last_facets(sh, nq, i, k, *out))
 
     def facets_of_all_documents(self, session=None):
         """FacetBuilder.BuildFacetsFromAllDocuments (Core/FacetBuilder.cs:110-181): {field: [(value, count)]} over every document that is not Deleted
@@ -466,7 +453,7 @@ class SearchEngine:
     def last_filtered_facet_stats(self, session=None):
         """(expressions counted on the device, expressions taken from the engine's cache, k_facets_filtered launches) of the session's last
         facets_of_documents call (or batch with Query.pre_filter_facets)."""
-        return _filtered_facet_stats(self, session.h if session is not None else self._default_session())
+        return _u32_stats(self, "infx_engine_last_facets_filtered_stats", session.h if session is not None else self._default_session(), 3)
 
     def list_documents(self, filter=None, order_by=None, ascending=True, offset=0, limit=20, session=None):
         """A page of the documents a filter accepts, in the order of a field (not in the reference).  The set: every document that is not Deleted and whose
@@ -481,7 +468,7 @@ class SearchEngine:
 
     def last_list_stats(self, session=None):
         """(masks built, masks reused, histogram passes, kernel launches) of the session's last list_documents device call."""
-        return _list_stats(self, session.h if session is not None else self._default_session())
+        return _u32_stats(self, "infx_engine_last_list_stats", session.h if session is not None else self._default_session(), 4)
 
     def set_list_digit_bits(self, bits, session=None):
         """The width of a radix-select digit of list_documents on the session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
@@ -501,7 +488,7 @@ class SearchEngine:
 
     def last_range_stats(self, session=None):
         """(masks built, masks reused, k_range_counts launches) of the session's last range_facets device call."""
-        return _range_stats(self, session.h if session is not None else self._default_session())
+        return _u32_stats(self, "infx_engine_last_range_stats", session.h if session is not None else self._default_session(), 3)
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -578,11 +565,11 @@ class SearchEngine:
 
     def last_count_stats(self, session=None):
         """(expressions the session's last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
-        return _count_stats(self, session.h if session is not None else self._default_session())
+        return _u32_stats(self, "infx_engine_last_count_stats", session.h if session is not None else self._default_session(), 2)
 
     def last_prefilter_stats(self, session=None):
         """(masks built, masks taken from the session's cache, k_filter_mask_multi launches) of the session's last search (or prefilter_mask call)."""
-        return _prefilter_stats(self, session.h if session is not None else self._default_session())
+        return _u32_stats(self, "infx_engine_last_prefilter_stats", session.h if session is not None else self._default_session(), 3)
 
     def prefilter_mask(self, expr: str, session=None) -> np.ndarray:
         """Parity tooling: the device's mask of a pre-filter expression, one byte per indexed document (1 = Deleted or not accepted) — built, or taken
@@ -793,7 +780,7 @@ class Session:
 
     def last_filtered_facet_stats(self):
         """SearchEngine.last_filtered_facet_stats of this session."""
-        return _filtered_facet_stats(self.engine, self.h)
+        return _u32_stats(self.engine, "infx_engine_last_facets_filtered_stats", self.h, 3)
 
     def list_documents(self, filter=None, order_by=None, ascending=True, offset=0, limit=20):
         """SearchEngine.list_documents on this session (its mask cache holds the filters' masks)."""
@@ -801,7 +788,7 @@ class Session:
 
     def last_list_stats(self):
         """SearchEngine.last_list_stats of this session."""
-        return _list_stats(self.engine, self.h)
+        return _u32_stats(self.engine, "infx_engine_last_list_stats", self.h, 4)
 
     def set_list_digit_bits(self, bits):
         """The width of a radix-select digit of list_documents on this session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
@@ -813,11 +800,11 @@ class Session:
 
     def last_range_stats(self):
         """SearchEngine.last_range_stats of this session."""
-        return _range_stats(self.engine, self.h)
+        return _u32_stats(self.engine, "infx_engine_last_range_stats", self.h, 3)
 
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
-        return _prefilter_stats(self.engine, self.h)
+        return _u32_stats(self.engine, "infx_engine_last_prefilter_stats", self.h, 3)
 
     def prefilter_mask(self, expr: str) -> np.ndarray:
         """SearchEngine.prefilter_mask on this session (its own mask cache)."""
@@ -825,7 +812,7 @@ class Session:
 
     def last_count_stats(self):
         """(expressions the last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
-        return _count_stats(self.engine, self.h)
+        return _u32_stats(self.engine, "infx_engine_last_count_stats", self.h, 2)
 
     def set_sort(self, sort_by=None, ascending=False):
         """Installs Query.SortBy (a field name; None = relevance order) and Query.SortAscending on this session."""
@@ -911,15 +898,21 @@ def _in_prefilter(engine, sh, n):
     return out[:n]
 
 
-def _query_error(engine, sh, j, status):
-    buf = C.create_string_buffer(512); engine.L.infx_engine_query_error(sh, j, buf, 512)
+def _request_error(engine, fn, sh, i, status):
+    """The message the library's reader fn has for request (or query) i of the session's last call; "status <n>" when it has none."""
+    buf = C.create_string_buffer(512); getattr(engine.L, fn)(sh, i, buf, 512)
     return buf.value.decode(errors="replace") or ("status %d" % status)
 
 
-def _prefilter_stats(engine, sh):
-    b = C.c_uint32(0); r = C.c_uint32(0); n = C.c_uint32(0)
-    engine._check(engine.L.infx_engine_last_prefilter_stats(sh, C.byref(b), C.byref(r), C.byref(n)))
-    return int(b.value), int(r.value), int(n.value)
+def _query_error(engine, sh, j, status):
+    return _request_error(engine, "infx_engine_query_error", sh, j, status)
+
+
+def _u32_stats(engine, fn, sh, k):
+    """The k uint32 counters the library's getter fn reports for session handle sh."""
+    v = [C.c_uint32(0) for _ in range(k)]
+    engine._check(getattr(engine.L, fn)(sh, *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
 
 
 def _prefilter_mask(engine, sh, expr):
@@ -1000,20 +993,7 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
 def _facets_all(engine, sh):
     ncols = C.c_int32(0)
     engine._check(engine.L.infx_engine_facets_all(sh, C.byref(ncols)))
-    facets = {}
-    for k in range(int(ncols.value)):
-        col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
-        m = engine.L.infx_engine_facets_all_column(sh, k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
-        if m < 0:
-            engine._check(1)
-        if m > 0:
-            nb = C.create_string_buffer(256); engine.L.infx_engine_column_info(engine.h, col.value, nb, 256, None, None)
-            vals = []
-            for j in range(m):
-                vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col.value, int(codes[j]), vb, 1024)
-                vals.append((vb.value.decode(), int(cnts[j])))
-            facets[nb.value.decode()] = vals
-    return facets
+    return _facet_columns(engine, int(ncols.value), lambda k, *out: engine.L.infx_engine_facets_all_column(sh, k, *out))
 
 
 def _column_facets(engine, col, m, codes, cnts):
@@ -1026,34 +1006,46 @@ def _column_facets(engine, col, m, codes, cnts):
     return nb.value.decode(), vals
 
 
+def _facet_columns(engine, ncols, read):
+    """{field: [(value, count)]} of ncols facet columns; read(k, col, codes, counts, cap) is the library's reader of the k-th: the number of pairs, < 0 for an error."""
+    facets = {}
+    for k in range(ncols):
+        col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
+        m = read(k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
+        if m < 0:
+            engine._check(1)
+        if m > 0:
+            name, vals = _column_facets(engine, col.value, m, codes, cnts)
+            facets[name] = vals
+    return facets
+
+
+def _per_request(engine, sh, fn, error_fn, ctype, reqs, single, pack, read, refused, chunk=MAX_PREFILTERS):
+    """The call pattern of the features that answer each request on its own, on session handle sh: reqs go to the library function fn `chunk` at a time
+    (None: in one call, which the engine splits itself), as an array of ctype made by pack(request).  A request the engine refused becomes refused(request,
+    message), the message from the library's reader error_fn; any other becomes read(i, request), i its place in the call.  One answer for `single`, else their list."""
+    out = []
+    for r0 in range(0, len(reqs), chunk) if chunk else [0]:
+        part = reqs[r0:r0 + chunk] if chunk else reqs
+        n = len(part)
+        arr = (ctype * max(n, 1))(*[pack(r) for r in part])
+        st = np.zeros(max(n, 1), np.int32)
+        engine._check(getattr(engine.L, fn)(sh, n, arr, _p(st, C.c_int32)))
+        for i, r in enumerate(part):
+            out.append(refused(r, _request_error(engine, error_fn, sh, i, int(st[i]))) if st[i] != 0 else read(i, r))
+    return out[0] if single else out
+
+
 def _facets_filtered(engine, sh, filters):
     """infx_engine_facets_filtered on session handle sh: a FilteredFacets for a str, a list of them for a sequence."""
-    single = isinstance(filters, str)
-    exprs = [filters] if single else list(filters)
-    n = len(exprs)
-    arr = (C.c_char_p * max(n, 1))(*[x.encode() for x in exprs])
-    st = np.zeros(max(n, 1), np.int32)
-    engine._check(engine.L.infx_engine_facets_filtered(sh, n, arr, _p(st, C.c_int32)))
-    ncols = int(engine.L.infx_engine_facets_filtered_column_count(sh))
-    out = []
-    for i in range(n):
-        if st[i] != 0:
-            buf = C.create_string_buffer(512); engine.L.infx_engine_facets_filtered_error(sh, i, buf, 512)
-            out.append(FilteredFacets({}, 0, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
-            continue
+    def read(i, _):
         tot = C.c_uint32(0)
         engine._check(engine.L.infx_engine_facets_filtered_total(sh, i, C.byref(tot)))
-        facets = {}
-        for k in range(ncols):
-            col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
-            m = engine.L.infx_engine_facets_filtered_column(sh, i, k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
-            if m < 0:
-                engine._check(1)
-            if m > 0:
-                name, vals = _column_facets(engine, col.value, m, codes, cnts)
-                facets[name] = vals
-        out.append(FilteredFacets(facets, int(tot.value), None))
-    return out[0] if single else out
+        ncols = int(engine.L.infx_engine_facets_filtered_column_count(sh))
+        return FilteredFacets(_facet_columns(engine, ncols, lambda k, *out: engine.L.infx_engine_facets_filtered_column(sh, i, k, *out)), int(tot.value), None)
+    single = isinstance(filters, str)
+    return _per_request(engine, sh, "infx_engine_facets_filtered", "infx_engine_facets_filtered_error", C.c_char_p, [filters] if single else list(filters), single,
+                        lambda x: x.encode(), read, lambda _, msg: FilteredFacets({}, 0, msg), chunk=None)
 
 
 def _column_index(engine, name):
@@ -1067,109 +1059,75 @@ def _column_index(engine, name):
 
 def _list_documents(engine, sh, filter, order_by, ascending, offset, limit):
     """infx_engine_list_documents on session handle sh: a Listing for one request (given by its parts), a list of them for a sequence of ListRequest."""
+    def pack(r):
+        off, lim = int(r.offset), int(r.limit)
+        # out of the C fields' range: passed as values the engine refuses for this request alone
+        return _ListReq(None if r.filter is None else r.filter.encode(), None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
+                        off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+    cols = {}
+
+    def read(i, r):
+        tot = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_list_total(sh, i, C.byref(tot)))
+        keys = np.zeros(1024, np.int64); docs = np.zeros(1024, np.int32); codes = np.zeros(1024, np.uint32)
+        m = engine.L.infx_engine_list_rows(sh, i, _p(keys, C.c_int64), _p(docs, C.c_int32), _p(codes, C.c_uint32), 1024)
+        if m < 0:
+            engine._check(1)
+        vals = []
+        if r.order_by is not None:
+            if r.order_by not in cols:
+                cols[r.order_by] = (_column_index(engine, r.order_by), {})
+            col, text = cols[r.order_by]
+            for c in codes[:m]:
+                c = int(c)
+                if c not in text:
+                    vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col, c, vb, 1024)
+                    text[c] = vb.value.decode()
+                vals.append(text[c])
+        return Listing([int(k) for k in keys[:m]], vals, int(tot.value), None)
     single = filter is None or isinstance(filter, str)
-    reqs = [ListRequest(filter, order_by, ascending, offset, limit)] if single else list(filter)
-    out = []
-    for r0 in range(0, len(reqs), MAX_PREFILTERS):       # one mask slot per distinct filter: sixteen requests per device call
-        part = reqs[r0:r0 + MAX_PREFILTERS]
-        n = len(part)
-        arr = (_ListReq * n)()
-        for i, r in enumerate(part):
-            off, lim = int(r.offset), int(r.limit)
-            # out of the C fields' range: passed as values the engine refuses for this request alone
-            arr[i] = _ListReq(None if r.filter is None else r.filter.encode(), None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
-                              off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
-        st = np.zeros(n, np.int32)
-        engine._check(engine.L.infx_engine_list_documents(sh, n, arr, _p(st, C.c_int32)))
-        cols = {}
-        for i, r in enumerate(part):
-            if st[i] != 0:
-                buf = C.create_string_buffer(512); engine.L.infx_engine_list_error(sh, i, buf, 512)
-                out.append(Listing([], [], 0, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
-                continue
-            tot = C.c_uint32(0)
-            engine._check(engine.L.infx_engine_list_total(sh, i, C.byref(tot)))
-            keys = np.zeros(1024, np.int64); docs = np.zeros(1024, np.int32); codes = np.zeros(1024, np.uint32)
-            m = engine.L.infx_engine_list_rows(sh, i, _p(keys, C.c_int64), _p(docs, C.c_int32), _p(codes, C.c_uint32), 1024)
-            if m < 0:
-                engine._check(1)
-            vals = []
-            if r.order_by is not None:
-                if r.order_by not in cols:
-                    cols[r.order_by] = (_column_index(engine, r.order_by), {})
-                col, text = cols[r.order_by]
-                for c in codes[:m]:
-                    c = int(c)
-                    if c not in text:
-                        vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col, c, vb, 1024)
-                        text[c] = vb.value.decode()
-                    vals.append(text[c])
-            out.append(Listing([int(k) for k in keys[:m]], vals, int(tot.value), None))
-    return out[0] if single else out
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_list_documents", "infx_engine_list_error", _ListReq,
+                        [ListRequest(filter, order_by, ascending, offset, limit)] if single else list(filter), single, pack, read,
+                        lambda _, msg: Listing([], [], 0, msg))
 
 
 def _range_facets(engine, sh, filter, field, edges):
     """infx_engine_range_facets on session handle sh: a RangeFacets for one request (given by its parts), a list of them for a sequence of RangeRequest."""
+    keep = []                                            # the edge arrays live until the calls have returned
+
+    def pack(r):
+        ed = tuple(r.edges)
+        # integer edges only when every edge is a Python int (not a bool) that an int64 holds; double edges always (what float() refuses is passed as NaN: refused)
+        ei = None
+        if ed and all(isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63 for x in ed):
+            ei = np.asarray(ed, np.int64); keep.append(ei)
+        vals = []
+        for x in ed:
+            try:
+                vals.append(float(x))
+            except (TypeError, ValueError, OverflowError):
+                vals.append(float("nan"))
+        edd = np.asarray(vals, np.float64); keep.append(edd)
+        return _RangeReq(None if r.filter is None else r.filter.encode(), None if r.field is None else str(r.field).encode(), min(len(ed), 0xFFFFFFFF),
+                         None if ei is None else _p(ei, C.c_int64), _p(edd, C.c_double))
+
+    def read(i, r):
+        tot = C.c_uint32(0); below = C.c_uint32(0); above = C.c_uint32(0); nan = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_range_total(sh, i, C.byref(tot)))
+        counts = np.zeros(256, np.uint32)
+        m = engine.L.infx_engine_range_counts(sh, i, _p(counts, C.c_uint32), 256, C.byref(below), C.byref(above), C.byref(nan))
+        if m < 0:
+            engine._check(1)
+        kind = C.c_int32(0); li = C.c_int64(0); hi = C.c_int64(0); ld = C.c_double(0); hd = C.c_double(0)
+        engine._check(engine.L.infx_engine_range_minmax(sh, i, C.byref(kind), C.byref(li), C.byref(hi), C.byref(ld), C.byref(hd)))
+        lo, up = (int(li.value), int(hi.value)) if kind.value == 1 else ((float(ld.value), float(hd.value)) if kind.value == 2 else (None, None))
+        return RangeFacets(tuple(r.edges), [int(c) for c in counts[:m]], int(below.value), int(above.value), int(nan.value), int(tot.value), lo, up, None)
     single = filter is None or isinstance(filter, str)
-    reqs = [RangeRequest(filter, field, edges)] if single else list(filter)
-    out = []
-    for r0 in range(0, len(reqs), MAX_PREFILTERS):       # one mask slot per distinct filter: sixteen requests per device call
-        part = reqs[r0:r0 + MAX_PREFILTERS]
-        n = len(part)
-        arr = (_RangeReq * n)()
-        keep = []                                        # the edge arrays live until the call returns
-        for i, r in enumerate(part):
-            ed = tuple(r.edges)
-            # integer edges only when every edge is a Python int (not a bool) that an int64 holds; double edges always (what float() refuses is passed as NaN: refused)
-            ei = None
-            if ed and all(isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63 for x in ed):
-                ei = np.asarray(ed, np.int64); keep.append(ei)
-            vals = []
-            for x in ed:
-                try:
-                    vals.append(float(x))
-                except (TypeError, ValueError, OverflowError):
-                    vals.append(float("nan"))
-            edd = np.asarray(vals, np.float64); keep.append(edd)
-            arr[i] = _RangeReq(None if r.filter is None else r.filter.encode(), None if r.field is None else str(r.field).encode(), min(len(ed), 0xFFFFFFFF),
-                               None if ei is None else _p(ei, C.c_int64), _p(edd, C.c_double))
-        st = np.zeros(n, np.int32)
-        engine._check(engine.L.infx_engine_range_facets(sh, n, arr, _p(st, C.c_int32)))
-        for i, r in enumerate(part):
-            ed = tuple(r.edges)
-            if st[i] != 0:
-                buf = C.create_string_buffer(512); engine.L.infx_engine_range_error(sh, i, buf, 512)
-                out.append(RangeFacets(ed, [], 0, 0, 0, 0, None, None, buf.value.decode(errors="replace") or ("status %d" % int(st[i]))))
-                continue
-            tot = C.c_uint32(0); below = C.c_uint32(0); above = C.c_uint32(0); nan = C.c_uint32(0)
-            engine._check(engine.L.infx_engine_range_total(sh, i, C.byref(tot)))
-            counts = np.zeros(256, np.uint32)
-            m = engine.L.infx_engine_range_counts(sh, i, _p(counts, C.c_uint32), 256, C.byref(below), C.byref(above), C.byref(nan))
-            if m < 0:
-                engine._check(1)
-            kind = C.c_int32(0); li = C.c_int64(0); hi = C.c_int64(0); ld = C.c_double(0); hd = C.c_double(0)
-            engine._check(engine.L.infx_engine_range_minmax(sh, i, C.byref(kind), C.byref(li), C.byref(hi), C.byref(ld), C.byref(hd)))
-            lo, up = (int(li.value), int(hi.value)) if kind.value == 1 else ((float(ld.value), float(hd.value)) if kind.value == 2 else (None, None))
-            out.append(RangeFacets(ed, [int(c) for c in counts[:m]], int(below.value), int(above.value), int(nan.value), int(tot.value), lo, up, None))
-    return out[0] if single else out
-
-
-def _range_stats(engine, sh):
-    a = C.c_uint32(0); b = C.c_uint32(0); c = C.c_uint32(0)
-    engine._check(engine.L.infx_engine_last_range_stats(sh, C.byref(a), C.byref(b), C.byref(c)))
-    return int(a.value), int(b.value), int(c.value)
-
-
-def _list_stats(engine, sh):
-    a = C.c_uint32(0); b = C.c_uint32(0); c = C.c_uint32(0); d = C.c_uint32(0)
-    engine._check(engine.L.infx_engine_last_list_stats(sh, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
-    return int(a.value), int(b.value), int(c.value), int(d.value)
-
-
-def _filtered_facet_stats(engine, sh):
-    a = C.c_uint32(0); b = C.c_uint32(0); n = C.c_uint32(0)
-    engine._check(engine.L.infx_engine_last_facets_filtered_stats(sh, C.byref(a), C.byref(b), C.byref(n)))
-    return int(a.value), int(b.value), int(n.value)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_range_facets", "infx_engine_range_error", _RangeReq,
+                        [RangeRequest(filter, field, edges)] if single else list(filter), single, pack, read,
+                        lambda r, msg: RangeFacets(tuple(r.edges), [], 0, 0, 0, 0, None, None, msg))
 
 
 def _attach_pre_filter_facets(engine, sh, qs, results):
@@ -1185,12 +1143,6 @@ def _attach_pre_filter_facets(engine, sh, qs, results):
     for q, r in zip(qs, results):
         if q.pre_filter_facets and q.pre_filter is not None and r.error is None and got[q.pre_filter].error is None:
             r.pre_filter_facets = got[q.pre_filter].facets
-
-
-def _count_stats(engine, sh):
-    k = C.c_uint32(0); n = C.c_uint32(0)
-    engine._check(engine.L.infx_engine_last_count_stats(sh, C.byref(k), C.byref(n)))
-    return int(k.value), int(n.value)
 
 
 def _set_sort(engine, sh, sort_by, ascending):
