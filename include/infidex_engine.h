@@ -444,6 +444,41 @@ int32_t infx_engine_range_total(infx_session* s, uint32_t which, uint32_t* total
 int32_t infx_engine_range_minmax(infx_session* s, uint32_t which, int32_t* kind, int64_t* lo_i, int64_t* hi_i, double* lo_d, double* hi_d);
 int32_t infx_engine_range_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_range_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
+/* ---- field_stats: counts, min / max and the EXACT sum and mean of a numeric field over a filter, whole or per group (not in the reference: the semantics
+ * below are this project's) ----
+ * Request i asks, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document; duplicate keys are documents of their own — for the values v of `field`, an int64 or a double column:
+ *   nan        members whose value is a NaN; they appear in no other figure            count   the other members; count + nan is the size of the set
+ *   min, max   the smallest and largest value that is not a NaN, as infx_engine_range_minmax returns them (valid when count > 0)
+ *   sum        kind 1 (int64 column): the exact sum as the 128-bit two's complement integer sum_hi : sum_lo, and rounded once in sum_d
+ *              kind 2 (double column): sum_d = the exact real sum of the finite values rounded ONCE to nearest-even (what math.fsum returns); beyond the
+ *              double range +-inf; with +inf members and no -inf member +inf, the mirror case -inf, both a NaN; a zero sum is +0.0; an empty set 0
+ *   mean       valid when count > 0: the exact sum divided by count, rounded once, for both kinds; +-inf / NaN as the sum
+ * and, with `group_by` (any column of any kind, facetable or not, of at most INFX_STATS_MAX_GROUPS = 4096 distinct values; it may be `field` itself), the
+ * same figures for every distinct value of group_by that has a member: ALL such groups (no cut at 100), members descending, then the group column's facet
+ * tie order ascending.  The groups' count and nan add up to the whole's; on an int64 column so do the sums.
+ * The sums do not depend on the order of the additions: the device adds integers only (DESIGN.md "field_stats"), so every run, session, stream and rank
+ * returns the same bytes.  No variance, percentiles, distinct counts or top-N cut; nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_field_stats_error, the others answered): a syntax error, a missing or unknown
+ * field, an unknown group_by, a string field, a group_by of more than 4096 values, or a double column whose finite values span more than 128 binary digits
+ * (it cannot be summed exactly) INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests
+ * (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), every refusal but the filter's already in out_status; a call that failed as
+ * a whole leaves nothing for the readers.  The masks are the session's pre-filter masks (slots, least-recently-used rule, epoch and statistics of
+ * infx_engine_list_documents); the field's sort rank and value table are built on first use and dropped when infx_engine_add_column replaces the column;
+ * ONE k_field_stats launch answers all requests of the call.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_field_stats_whole the whole's figures (returning the request's status);
+ * infx_engine_field_stats_groups copies up to cap groups in the order above — codes[g] the group's code in column *group_col (-1 without group_by; its
+ * text through infx_engine_column_value), figures[g] its figures — and returns the number of groups (-1 for a refused request or bad arguments);
+ * infx_engine_field_stats_total the size of the set (returning the request's status); infx_engine_field_stats_error the refusal's message (its length; -1
+ * out of range).  infx_engine_last_field_stats_stats: masks built and reused and k_field_stats launches of the last call. */
+typedef struct infx_stats_request { const char* filter; const char* field; const char* group_by; } infx_stats_request;
+typedef struct infx_stats_figures { uint32_t count; uint32_t nan; int32_t kind; int32_t reserved; int64_t min_i; int64_t max_i; double min_d; double max_d; double sum_d; uint64_t sum_lo; int64_t sum_hi; double mean; } infx_stats_figures;
+int32_t infx_engine_field_stats(infx_session* s, uint32_t nreq, const infx_stats_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_field_stats_whole(infx_session* s, uint32_t which, infx_stats_figures* out);
+int32_t infx_engine_field_stats_groups(infx_session* s, uint32_t which, int32_t* group_col, uint32_t* codes, infx_stats_figures* figures, int32_t cap);
+int32_t infx_engine_field_stats_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_field_stats_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_field_stats_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

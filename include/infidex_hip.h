@@ -446,6 +446,34 @@ typedef struct infx_range_req { const uint8_t* mask; int32_t col; uint32_t nedge
 int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* reqs, uint32_t* counts_out /* nreq x INFX_RANGE_SLOTS */,
                           uint32_t* min_rank_out /* nreq */, uint32_t* max_rank_out /* nreq */);
 int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* launches);
+/* Field statistics of a document set over a numeric column, whole or per value of a second column (not in the reference: the aggregate is this
+ * project's; DESIGN.md "field_stats").
+ * infx_upload_column_values: the raw values of column col's codes — bits[v] the 8 bytes of distinct value v: an int64 (kind 1) or the bit pattern of a
+ * double (kind 2) — with the scale they are summed at: scale_exp the lowest exponent of a set mantissa bit over the finite values that are not zero
+ * (0 for kind 1 and for a column without such a value), nlimbs = ceil((1 + highest exponent of a set bit - scale_exp) / 32), at least 1, at most 4 (kind 1:
+ * at most 2).  Both are checked against the values (INFX_EINVAL).  8 B per distinct value: the limbs are cut from the value on the device by integer
+ * shifts, so a member costs one 8 B gather, not 16 B of precomputed limbs.  Exclusive call, like infx_upload_sort_rank; a re-upload of the column voids the
+ * table as it voids the sort rank.
+ * infx_field_stats, request i: the SET is the documents whose byte in `mask` is 0 — a mask slot of this stream — or, mask = NULL, every document that is
+ * not Deleted.  `col` needs its sort rank (infx_upload_sort_rank) and its value table; `group_col` is any uploaded column of at most
+ * INFX_STATS_MAX_GROUPS distinct values, or -1.  The request has one SLOT per distinct value of group_col (in code order), one in all without it; the
+ * slots of request i follow those of request i - 1 in slots_out.  A member document adds to the slot of its group code: one of four counters by the class
+ * of its value (finite, NaN, +inf, -inf), its sort rank to min_rank / max_rank unless it is a NaN (min_rank = 0xFFFFFFFF and max_rank = 0: the slot saw no
+ * such value), and, when finite, the nlimbs unsigned 32-bit digits of |v| / 2^scale_exp, with the sign of v, to the signed 64-bit sums sum[0 .. nlimbs)
+ * (the others are 0).  The exact sum of the slot's finite values is 2^scale_exp * (sum[0] + sum[1] * 2^32 + ..); with fewer than 2^31 documents no sum
+ * overflows.  Every accumulation is an integer atomic — no floating-point add, no order: the same bytes from any stream, grid and placement.
+ * At most 16 requests (INFX_ECAPACITY), all answered by ONE k_field_stats launch that walks the corpus once: the requests are taken in the order
+ * (mask, col, group_col), so the ones that share a mask read its bytes once and the ones that share a value column too read its codes, values and ranks
+ * once.  A request's slots lie in LDS while they fit (requests in ascending size, 16 384 words per workgroup), else in global memory.  A mask build
+ * staged with infx_filter_masks is enqueued first, as ONE launch.  Works on a sharded index.  Synchronous.
+ * infx_last_field_stats_info: requests and k_field_stats launches (0 or 1) of the stream's last call. */
+#define INFX_STATS_MAX_GROUPS 4096
+#define INFX_STATS_MAX_LIMBS 4
+typedef struct infx_stats_req { const uint8_t* mask; int32_t col; int32_t group_col; } infx_stats_req;
+typedef struct infx_stats_slot { uint32_t finite; uint32_t nan; uint32_t pinf; uint32_t ninf; uint32_t min_rank; uint32_t max_rank; int64_t sum[INFX_STATS_MAX_LIMBS]; } infx_stats_slot;
+int32_t infx_upload_column_values(infx_index* idx, uint32_t col, uint32_t num_values, const uint64_t* bits, int32_t kind, int32_t scale_exp, uint32_t nlimbs);
+int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out /* sum of the requests' slots */);
+int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -28,7 +28,8 @@ def device_sources():
 def host_sources():
     """What the host object (csrc/host/engine.cpp) is compiled from."""
     host = os.path.join(CSRC, "host")
-    return [os.path.join(host, f) for f in os.listdir(host) if f.endswith((".h", ".cpp"))] + _include_headers()
+    shared = [os.path.join(CSRC, "exact_sum.h")]     # the arithmetic engine.cpp shares with k_field_stats
+    return [os.path.join(host, f) for f in os.listdir(host) if f.endswith((".h", ".cpp"))] + shared + _include_headers()
 
 
 def sources():

@@ -15,6 +15,8 @@
 #include <mutex>
 #include <condition_variable>
 #include "../../../include/infidex_engine.h"
+#define XS_FN static inline
+#include "../exact_sum.h"
 #include <chrono>
 #include <map>
 #include <list>
@@ -98,6 +100,9 @@ struct ListAnswer : Answer { std::vector<int64_t> keys; std::vector<int32_t> doc
 // One request of the session's last infx_engine_range_facets: its status and message, its counters, the extremes as values (kind 0: none, 1 int64, 2 double)
 struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vector<uint32_t> counts;
                      int32_t kind = 0; int64_t loI = 0, hiI = 0; double loD = 0, hiD = 0; };
+// One request of the session's last infx_engine_field_stats: its status and message, the whole's figures, the group column (-1: none) and the groups that have a
+// member, in the contract's order
+struct StatsAnswer : Answer { infx_stats_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_stats_figures> groups; };
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 struct infx_session {
     QueryCov qc;
@@ -116,6 +121,8 @@ struct infx_session {
     std::vector<ListAnswer> lst; MaskUse lstMasks; uint32_t lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
     // infx_engine_range_facets: one answer per request of the session's last call; masks built and reused and k_range_counts launches of that call
     std::vector<RangeAnswer> rng; MaskUse rngMasks; uint32_t rngLaunches = 0;
+    // infx_engine_field_stats: likewise, with the k_field_stats launches of that call
+    std::vector<StatsAnswer> sts; MaskUse stsMasks; uint32_t stsLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -182,7 +189,7 @@ static int32_t query_pre_check(infx_session* S, uint32_t nq);
 static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static void clear_query_prefilters(infx_session* S);
 // The filter and mask part of one call over the documents that filters accept: a batch with pre-filters, infx_engine_prefilter_mask, _list_documents,
-// _range_facets.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
+// _range_facets, _field_stats.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
 // the session's mask cache, mask(i) is request i's; the device call that follows ends in failed(rc) or done().  (Defined with the mask cache, below.)
 struct MaskCall {
     infx_session* S; MaskUse* use;                // use: where the call's kind keeps its masks built / reused, beside the session's pre* counters
@@ -250,6 +257,10 @@ struct infx_engine {
     // per column, for infx_engine_range_facets (built on first use, under filterMu): the lowest code of every sort rank, in rank order, and whether rank 0 is a NaN
     struct RangeIndex { bool ok = false; uint32_t nanRanks = 0; std::vector<uint32_t> codeOfRank; };
     std::vector<RangeIndex> rangeIndex;
+    // per column, for infx_engine_field_stats (built on first use, under filterMu; dropped with the column): the raw values of its codes, the scale and width
+    // they are summed at (exact_sum.h), whether they can be summed exactly, and whether the table is on the device
+    struct StatsIndex { bool ok = false, summable = false, uploaded = false; int32_t kind = 0; XsScale sc = {0, 1, 1}; std::vector<uint64_t> bits; };
+    std::vector<StatsIndex> statsIndex;
     // NumberOfDocumentsInFilter is cached per expression; a Filter parsed after a mutation counts again (the reference keeps the count on the Filter instance)
     void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = kv.second.countedAll = false; }
     void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); filterLru.clear(); }
@@ -2435,6 +2446,7 @@ int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, i
         e->columns[at] = std::move(c);
         if (at < e->sortRanked.size()) e->sortRanked[at] = 0;
         if (at < e->rangeIndex.size()) e->rangeIndex[at] = infx_engine::RangeIndex();
+        if (at < e->statsIndex.size()) e->statsIndex[at] = infx_engine::StatsIndex();
     } else e->columns.push_back(std::move(c));
     e->invalidate_filter_counts();
     e->maskEpoch++;
@@ -3170,8 +3182,8 @@ int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counte
     return put_stats({{counted, S->ffCounted}, {cached, S->ffCached}, {launches, S->ffLaunches}});
 }
 
-// ---- requests over the documents a filter accepts: infx_engine_list_documents and infx_engine_range_facets -------------------------------------------
-// Both take up to INFX_MAX_PREFILTERS requests, answer each on its own (a refusal is the request's: its status in out_status[i], its message with the answer)
+// ---- requests over the documents a filter accepts: infx_engine_list_documents, infx_engine_range_facets and infx_engine_field_stats --------------------
+// Each takes up to INFX_MAX_PREFILTERS requests, answer each on its own (a refusal is the request's: its status in out_status[i], its message with the answer)
 // and leave the answers on the session for the readers.  A call that fails as a whole leaves no answers behind — the readers refuse — while the statuses
 // already written to out_status stay.  The filters and their masks are a MaskCall's.
 // what such a call needs of the engine (`what` names the call in the message)
@@ -3406,6 +3418,160 @@ int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int3
 int32_t infx_engine_last_range_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->rngMasks.built}, {masks_reused, S->rngMasks.reused}, {launches, S->rngLaunches}});
+}
+
+// ---- field_stats: counts, min / max and the exact sum and mean of a numeric field over the documents a filter accepts, whole or per group (not in the reference) ----
+// Per request: the field to its column (int64 or double) and the column to its value table — the raw values of its codes with the power-of-two scale at which
+// every finite one is an integer (exact_sum.h; a double column that spans more than 128 binary digits is refused) — group_by to any column of at most 4096
+// values, the filter through the filter cache and its mask through the session's mask cache, as infx_engine_range_facets.  infx_field_stats then adds integers
+// only, one slot per group code; the engine recombines the limb sums and rounds ONCE, for the sum and for the mean (exact_sum.h).
+// The value table of a column (host part).  Caller holds e->filterMu.
+static infx_engine::StatsIndex& stats_index(infx_engine* e, uint32_t col) {
+    if (e->statsIndex.size() < e->columns.size()) e->statsIndex.resize(e->columns.size());
+    infx_engine::StatsIndex& X = e->statsIndex[col];
+    if (!X.ok) {
+        const filt::Column& c = e->columns[col];
+        X.kind = c.dict.empty() || c.dict[0].kind == 1 ? XS_KIND_INT : XS_KIND_DOUBLE;
+        X.bits.resize(c.dict.size());
+        for (size_t v = 0; v < c.dict.size(); v++) { if (X.kind == XS_KIND_INT) X.bits[v] = (uint64_t)c.dict[v].i; else std::memcpy(&X.bits[v], &c.dict[v].d, 8); }
+        X.summable = xs_column_scale(X.bits.data(), X.bits.size(), X.kind, &X.sc);
+        X.uploaded = false; X.ok = true;
+    }
+    return X;
+}
+// What is wrong with request Q before anything of it is looked at on the device — the field, its kind, group_by, whether the field can be summed exactly — as
+// the request's status, the text in *why; INFX_OK with the columns (gcol -1: no group_by).  Caller holds e->filterMu.
+static int32_t stats_request_check(infx_engine* e, const infx_stats_request& Q, int32_t* col, int32_t* gcol, std::string* why) {
+    auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
+    *gcol = -1;
+    if (!Q.field) return bad("field_stats needs a field");
+    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("field_stats: no field named '") + Q.field + "'");
+    if (column_kind(e->columns[*col]) == 3) return bad(std::string("field_stats: field '") + Q.field + "' is a string column; sums need an int64 or a double column");
+    if (Q.group_by) {
+        if ((*gcol = column_named(e, Q.group_by)) < 0) return bad(std::string("field_stats: no group_by field named '") + Q.group_by + "'");
+        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string("field_stats: group_by field '") + Q.group_by + "' has more than 4096 distinct values");
+    }
+    if (!stats_index(e, (uint32_t)*col).summable)
+        return bad(std::string("field_stats: the finite values of field '") + Q.field + "' span more than 128 binary digits; they cannot be summed exactly");
+    return INFX_OK;
+}
+// The figures of one slot (a group, or the whole): counts, the extremes as values through the rank's lowest code, the limb sums recombined and rounded once
+static infx_stats_figures stats_figures(const infx_stats_slot& S, const infx_engine::StatsIndex& V, const filt::Column& C, const infx_engine::RangeIndex& X) {
+    infx_stats_figures F = {};
+    F.count = S.finite + S.pinf + S.ninf; F.nan = S.nan; F.kind = V.kind;
+    const XsWide W = xs_recombine(S.sum, V.sc.nlimbs);
+    const uint64_t sb = xs_sum_bits(W, V.sc.scale, S.pinf, S.ninf); std::memcpy(&F.sum_d, &sb, 8);
+    if (V.kind == XS_KIND_INT) xs_sum_int128(W, &F.sum_lo, &F.sum_hi);
+    if (F.count) {
+        const uint64_t mb = xs_mean_bits(W, V.sc.scale, F.count, S.pinf, S.ninf); std::memcpy(&F.mean, &mb, 8);
+        if (S.min_rank < X.codeOfRank.size() && S.max_rank < X.codeOfRank.size()) {
+            const filt::Boxed& a = C.dict[X.codeOfRank[S.min_rank]]; const filt::Boxed& b = C.dict[X.codeOfRank[S.max_rank]];
+            if (V.kind == XS_KIND_INT) { F.min_i = a.i; F.max_i = b.i; } else { F.min_d = a.d; F.max_d = b.d; }
+        }
+    }
+    return F;
+}
+int32_t infx_engine_field_stats(infx_session* S, uint32_t nreq, const infx_stats_request* reqs, int32_t* out_status) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->sts.clear(); S->stsMasks = MaskUse(); S->stsLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) field_stats requests in one call");
+    S->sts.assign(nreq, StatsAnswer());
+    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->sts[i].status = rc; S->sts[i].err = msg; if (out_status) out_status[i] = rc; };
+    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            std::string why;
+            if (out_status) out_status[i] = INFX_OK;
+            const int32_t rc = stats_request_check(e, reqs[i], &col[i], &gcol[i], &why);
+            if (rc) refuse(i, rc, why);
+        }
+    }
+    { int32_t rc = need_indexed_device(S, "field_stats"); if (rc) { S->sts.clear(); return rc; } }
+    MaskCall mc(S, nreq, &S->stsMasks);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (S->sts[i].status) continue;
+            const infx_engine::RangeIndex* X = nullptr;
+            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }      // (the sort rank, for min / max)
+            infx_engine::StatsIndex& V = stats_index(e, (uint32_t)col[i]);
+            if (!V.uploaded) {
+                const int32_t rc = infx_upload_column_values(e->dev, (uint32_t)col[i], (uint32_t)V.bits.size(), V.bits.data(), V.kind, V.sc.scale, V.sc.nlimbs);
+                if (rc) { refuse(i, rc, infx_last_error()); continue; }
+                V.uploaded = true;
+            }
+            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
+        }
+    }
+    { int32_t rc = mc.acquire(); if (rc) { S->sts.clear(); return rc; } }
+    std::vector<infx_stats_req> dr; std::vector<uint32_t> who; std::vector<size_t> at; size_t nslots = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (S->sts[i].status) continue;
+        infx_stats_req R{};
+        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i];
+        dr.push_back(R); who.push_back(i); at.push_back(nslots);
+        nslots += gcol[i] >= 0 ? std::max<size_t>(e->columns[gcol[i]].dict.size(), 1) : 1;
+    }
+    const size_t m = dr.size();
+    std::vector<infx_stats_slot> slots(std::max<size_t>(nslots, 1));
+    int32_t rc = infx_field_stats(S->stream, (uint32_t)m, dr.data(), slots.data());
+    if (rc) { S->sts.clear(); return mc.failed(rc); }
+    mc.done();
+    { uint32_t r_ = 0; infx_last_field_stats_info(S->stream, &r_, &S->stsLaunches); }
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    for (size_t j = 0; j < m; j++) {
+        StatsAnswer& A = S->sts[who[j]];
+        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col]; const infx_engine::StatsIndex& V = e->statsIndex[dr[j].col];
+        const infx_stats_slot* sl = slots.data() + at[j];
+        A.groupCol = dr[j].group_col;
+        if (A.groupCol < 0) A.whole = stats_figures(sl[0], V, C, X);
+        else {
+            const filt::Column& G = e->columns[A.groupCol];
+            infx_stats_slot all = {}; all.min_rank = 0xFFFFFFFFu;
+            std::vector<uint32_t> ord;
+            for (uint32_t g = 0; g < G.dict.size(); g++) {
+                const infx_stats_slot& s1 = sl[g];
+                if (!(s1.finite + s1.nan + s1.pinf + s1.ninf)) continue;
+                ord.push_back(g);
+                all.finite += s1.finite; all.nan += s1.nan; all.pinf += s1.pinf; all.ninf += s1.ninf;
+                if (s1.min_rank != 0xFFFFFFFFu) { all.min_rank = std::min(all.min_rank, s1.min_rank); all.max_rank = std::max(all.max_rank, s1.max_rank); }
+                for (int k = 0; k < INFX_STATS_MAX_LIMBS; k++) all.sum[k] += s1.sum[k];      // (fewer than 2^31 members in all: no limb sum overflows)
+            }
+            auto members = [&](uint32_t g) { return (uint64_t)sl[g].finite + sl[g].nan + sl[g].pinf + sl[g].ninf; };
+            std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return members(a) != members(b) ? members(a) > members(b) : G.rank[a] < G.rank[b]; });
+            A.whole = stats_figures(all, V, C, X);
+            for (uint32_t g : ord) { A.codes.push_back(g); A.groups.push_back(stats_figures(sl[g], V, C, X)); }
+        }
+        A.total = A.whole.count + A.whole.nan;
+    }
+    return INFX_OK;
+}
+// request `which` of the session's last infx_engine_field_stats: the whole's figures (returns the request's status; INFX_EINVAL without such an answer)
+int32_t infx_engine_field_stats_whole(infx_session* S, uint32_t which, infx_stats_figures* out) {
+    const StatsAnswer* A = answer_at(S ? &S->sts : nullptr, which);
+    if (!A || !out) return efail(INFX_EINVAL, "no such request in the session's last field_stats call");
+    *out = A->whole;
+    return A->status;
+}
+// its groups, in the contract's order: up to cap codes (of column *group_col, -1 without group_by) and figures; returns the number of groups, -1 on error (also for a refused request)
+int32_t infx_engine_field_stats_groups(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, infx_stats_figures* figures, int32_t cap) {
+    const StatsAnswer* A = answer_at(S ? &S->sts : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!codes || !figures))) return -1;
+    const size_t c = std::min<size_t>(A->groups.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(figures, A->groups.data(), c * sizeof(infx_stats_figures)); }
+    if (group_col) *group_col = A->groupCol;
+    return (int32_t)A->groups.size();
+}
+// the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_field_stats_total(infx_session* S, uint32_t which, uint32_t* total) {
+    return answer_total(answer_at(S ? &S->sts : nullptr, which), total, "no such request in the session's last field_stats call");
+}
+int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->sts : nullptr, which), out, cap); }
+int32_t infx_engine_last_field_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->stsMasks.built}, {masks_reused, S->stsMasks.reused}, {launches, S->stsLaunches}});
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

@@ -99,6 +99,8 @@ struct infx_index {
     int32_t* dFirstLive = nullptr; uint32_t firstLiveCap = 0; const int32_t* firstLive = nullptr;      // first live document of each document's key, by GLOBAL internal id (infx_set_first_live; nullptr: keys are unique)
     const uint32_t* colCodes[FILT_MAXCOL] = {}; uint32_t colValues[FILT_MAXCOL] = {}; uint32_t colDocs[FILT_MAXCOL] = {}; uint32_t colCap[FILT_MAXCOL] = {};   // device-resident columns (infx_upload_column)
     const uint32_t* colRank[FILT_MAXCOL] = {}; uint32_t colRankCap[FILT_MAXCOL] = {}; bool colRankOk[FILT_MAXCOL] = {};     // sort ranks of their codes (infx_upload_sort_rank); a column re-upload voids its rank
+    // raw values of their codes with the scale field_stats sums them at (infx_upload_column_values); a column re-upload voids them too
+    const uint64_t* colBits[FILT_MAXCOL] = {}; uint32_t colBitsCap[FILT_MAXCOL] = {}; bool colBitsOk[FILT_MAXCOL] = {}; int32_t colKind[FILT_MAXCOL] = {}, colScale[FILT_MAXCOL] = {}; uint32_t colLimbs[FILT_MAXCOL] = {};
     std::vector<uint64_t> hPsOff;
     int rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;         // infx_set_shard_comm
@@ -262,6 +264,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "facets_filtered.hip.inc"
 #include "listing.hip.inc"
 #include "ranges.hip.inc"
+#include "stats.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -363,6 +366,8 @@ struct infx_stream {
     uint32_t lastListPasses = 0, lastListLaunches = 0;         // histogram passes and kernel launches of the last infx_list_ordered
     void *dRngWs = nullptr, *dRngOut = nullptr; size_t capRngWs = 0, capRngOut = 0;        // infx_range_counts: the requests' thresholds; counters, largest and smallest ranks
     uint32_t lastRngReqs = 0, lastRngLaunches = 0;             // requests and k_range_counts launches of the last infx_range_counts
+    void* dStsOut = nullptr; size_t capStsOut = 0; std::vector<uint32_t> hStsRaw;      // infx_field_stats: the requests' slots and smallest ranks; their host copy
+    uint32_t lastStsReqs = 0, lastStsLaunches = 0;             // requests and k_field_stats launches of the last infx_field_stats
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1301,7 +1306,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -2720,7 +2725,7 @@ int32_t infx_upload_column(infx_index* ix, uint32_t col, uint32_t total_docs, co
     uint32_t* d = const_cast<uint32_t*>(ix->colCodes[col]);
     if (!d || ix->colCap[col] < total_docs) { HIPCHK(dalloc(ix, &d, (size_t)total_docs + 1)); ix->colCap[col] = total_docs; }     // a re-upload reuses the column's buffer
     if (total_docs) HIPCHK(hipMemcpy(d, codes, (size_t)total_docs * 4, hipMemcpyHostToDevice));
-    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false;
+    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false; ix->colBitsOk[col] = false;
     return INFX_OK;
 }
 // a program must be a well-formed postfix expression whose stack fits the kernels' 32 slots, over uploaded columns, with its leaf tables in range
@@ -2804,6 +2809,24 @@ int32_t infx_upload_sort_rank(infx_index* ix, uint32_t col, uint32_t num_values,
     if (!d || ix->colRankCap[col] < num_values) { HIPCHK(dalloc(ix, &d, (size_t)num_values)); ix->colRankCap[col] = num_values; }
     if (num_values) HIPCHK(hipMemcpy(d, rank, (size_t)num_values * 4, hipMemcpyHostToDevice));
     ix->colRank[col] = d; ix->colRankOk[col] = true;
+    return INFX_OK;
+}
+// the raw values of a column's codes for infx_field_stats, with the scale and width the caller found for them (exact_sum.h)
+int32_t infx_upload_column_values(infx_index* ix, uint32_t col, uint32_t num_values, const uint64_t* bits, int32_t kind, int32_t scale_exp, uint32_t nlimbs) {
+    if (!ix || col >= FILT_MAXCOL || (num_values && !bits)) return fail(INFX_EINVAL, "bad column-value arguments%s");
+    if (!ix->colCodes[col] || num_values != ix->colValues[col]) return fail(INFX_EINVAL, "a value table needs one entry per distinct value of an uploaded column%s");
+    if ((kind != XS_KIND_INT && kind != XS_KIND_DOUBLE) || nlimbs < 1 || nlimbs > (kind == XS_KIND_INT ? 2u : (uint32_t)XS_MAX_LIMBS) || (kind == XS_KIND_INT && scale_exp != 0) || scale_exp < -1074 || scale_exp > 1023)
+        return fail(INFX_EINVAL, "a value table is int64 (kind 1, scale 0, 1 .. 2 limbs) or double (kind 2, scale -1074 .. 1023, 1 .. 4 limbs)%s");
+    {   // the scale and width must be the table's own: the kernel relies on no value shifting a set bit out of nlimbs limbs
+        XsScale sc; const bool ok = xs_column_scale(bits, num_values, kind, &sc);
+        if (!ok || sc.scale != scale_exp || sc.nlimbs != nlimbs) return fail(INFX_EINVAL, "scale_exp and nlimbs are not the scale and width of the values%s");
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());                      // exclusive call, as infx_upload_column
+    uint64_t* d = const_cast<uint64_t*>(ix->colBits[col]);
+    if (!d || ix->colBitsCap[col] < num_values) { HIPCHK(dalloc(ix, &d, (size_t)num_values)); ix->colBitsCap[col] = num_values; }
+    if (num_values) HIPCHK(hipMemcpy(d, bits, (size_t)num_values * 8, hipMemcpyHostToDevice));
+    ix->colBits[col] = d; ix->colKind[col] = kind; ix->colScale[col] = scale_exp; ix->colLimbs[col] = nlimbs; ix->colBitsOk[col] = true;
     return INFX_OK;
 }
 int32_t infx_stream_set_boosts(infx_stream* s, uint32_t n, infx_filter* const* f, const int32_t* strengths) {
@@ -3167,6 +3190,114 @@ int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* laun
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (requests) *requests = s->lastRngReqs;
     if (launches) *launches = s->lastRngLaunches;
+    return INFX_OK;
+}
+// ---- field_stats: counts, extreme sort ranks and exact limb sums of a numeric column over a document set, whole or per group (stats.hip.inc) ----
+// Where the slots of a call's requests live: in ascending size (slots x words) while they fit `budget` words of LDS per workgroup, the others in global
+// memory.  words[k] = request k's slots x stride; ldsOff[k] = its first LDS word or STS_GLOBAL; *inGlobal the requests left out.  Returns the LDS words in use.
+static uint32_t sts_place(uint32_t nreq, const uint32_t* words, uint32_t budget, uint32_t* ldsOff, uint32_t* inGlobal) {
+    uint32_t by[STS_MAX_REQS], used = 0; *inGlobal = 0;
+    for (uint32_t k = 0; k < nreq; k++) by[k] = k;
+    std::stable_sort(by, by + nreq, [&](uint32_t a, uint32_t b) { return words[a] < words[b]; });
+    for (uint32_t j = 0; j < nreq; j++) {
+        const uint32_t k = by[j];
+        if (used + words[k] <= budget) { ldsOff[k] = used; used += words[k]; } else { ldsOff[k] = STS_GLOBAL; ++*inGlobal; }
+    }
+    return used;
+}
+int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out) {
+    if (!s || (nreq && (!reqs || !slots_out))) return fail(INFX_EINVAL, "bad field-stats arguments%s");
+    s->lastStsReqs = 0; s->lastStsLaunches = 0;
+    if (nreq > STS_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-stats requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_stats_req& Q = reqs[i];
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "field-stats request"); if (rc_) return rc_; }
+        if (!ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the field-stats request's value table was not uploaded%s");
+        if (Q.group_col >= 0) {
+            if (Q.group_col >= FILT_MAXCOL || !ix->colCodes[Q.group_col]) return fail(INFX_EINVAL, "the field-stats request's group column was not uploaded%s");
+            { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.group_col); if (rc_) return rc_; }
+            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
+        }
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front
+    s->lastStsReqs = nreq;
+    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    // requests that share a mask follow one another, among them the ones that share a value column, among those the ones that share a group column
+    uint32_t order[STS_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
+    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
+        const infx_stats_req &A = reqs[a], &B = reqs[b];
+        if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
+        return A.col != B.col ? A.col < B.col : A.group_col < B.group_col; });
+    // the output: per request (in device order) its slots, then every request's smallest ranks
+    uint32_t nslots[STS_MAX_REQS], words[STS_MAX_REQS], ldsOff[STS_MAX_REQS]; size_t off[STS_MAX_REQS], loOff[STS_MAX_REQS], outWords = 0, totalSlots = 0;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_stats_req& Q = reqs[order[k]];
+        nslots[k] = Q.group_col >= 0 ? std::max(ix->colValues[Q.group_col], 1u) : 1u;
+        words[k] = nslots[k] * sts_stride(ix->colLimbs[Q.col]);
+        off[k] = outWords; outWords += words[k]; loOff[k] = totalSlots; totalSlots += nslots[k];
+    }
+    // 256 threads and k_facets_all's LDS budget; a call that leaves slots in global memory which the whole LDS of a CU would hold runs as one workgroup of 1024
+    // threads per CU instead: the same sixteen waves per CU, and LDS atomics where every member would be global atomics (INFX_STATS_NO_BIG_LDS=1: never, for measurements)
+    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();
+    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal); int threads = STS_THREADS;
+    if (inGlobal && !noBig) {
+        uint32_t bigOff[STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
+        if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; threads = STS_BIG_THREADS; }
+    }
+    GROW(s->dStsOut, s->capStsOut, (outWords + totalSlots) * 4);
+    uint32_t* O = (uint32_t*)s->dStsOut;
+    DevStatsCall P{}; P.nreq = nreq;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_stats_req& Q = reqs[order[k]];
+        DevStatsReq& D = P.r[k];
+        D.mask = Q.mask ? Q.mask : ix->d.deleted;
+        D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.bits = ix->colBits[Q.col]; D.nvals = ix->colValues[Q.col];
+        D.kind = ix->colKind[Q.col]; D.scale = ix->colScale[Q.col]; D.nlimbs = ix->colLimbs[Q.col];
+        D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = nslots[k];
+        D.out = O + off[k]; D.lo = O + outWords + loOff[k]; D.ldsOff = ldsOff[k];
+        if (k) { const infx_stats_req& B = reqs[order[k - 1]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+    }
+    HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
+    HIPCHK(hipMemsetAsync(O + outWords, 0xFF, totalSlots * 4, s->st));
+    s->unsynced = true;
+    if (n > 0) {
+        const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
+        // every workgroup merges its LDS slots once: no more workgroups than are resident (LDS of a CU: FFL_CU_LDS; 2048 threads)
+        int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device));
+        const int64_t perCu = std::min<int64_t>(2048 / threads, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)ldsWords * 4, 1)));
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + threads - 1) / threads));
+        HIPCHK(lds_limit((const void*)k_field_stats, ix->cfg.device, (size_t)ldsWords * 4));
+        k_field_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
+        HIPCHK(hipGetLastError());
+        s->lastStsLaunches = 1;
+    }
+    s->hStsRaw.assign(outWords + totalSlots, 0u);
+    DOWN(s->hStsRaw.data(), O, (outWords + totalSlots) * 4);
+    SYNC();
+    // the caller's order: request i's slots follow request i - 1's
+    size_t at[STS_MAX_REQS], sum = 0;
+    for (uint32_t i = 0; i < nreq; i++) { at[i] = sum; sum += reqs[i].group_col >= 0 ? std::max(ix->colValues[reqs[i].group_col], 1u) : 1u; }
+    for (uint32_t k = 0; k < nreq; k++) {
+        const uint32_t nl = ix->colLimbs[reqs[order[k]].col], W = sts_stride(nl);
+        for (uint32_t g = 0; g < nslots[k]; g++) {
+            const uint32_t* w = s->hStsRaw.data() + off[k] + (size_t)g * W;
+            infx_stats_slot& S = slots_out[at[order[k]] + g];
+            S.finite = w[0]; S.nan = w[1]; S.pinf = w[2]; S.ninf = w[3]; S.max_rank = w[4]; S.min_rank = s->hStsRaw[outWords + loOff[k] + g];
+            for (uint32_t i = 0; i < INFX_STATS_MAX_LIMBS; i++) { int64_t v = 0; if (i < nl) std::memcpy(&v, w + STS_HEAD + 2 * i, 8); S.sum[i] = v; }
+        }
+    }
+    return INFX_OK;
+}
+int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (requests) *requests = s->lastStsReqs;
+    if (launches) *launches = s->lastStsLaunches;
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

@@ -194,6 +194,47 @@ class RangeFacets:         # SearchEngine.range_facets: one per request
     error: Optional[str] = None                               # why this request alone was refused; None when it was answered
 
 
+@dataclass
+class StatsRequest:        # SearchEngine.field_stats: the statistics of one numeric field over one filter, whole or per group
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    field: Optional[str] = None         # an int64 or a double column
+    group_by: Optional[str] = None      # any column of at most 4096 distinct values; None: the whole only
+
+
+@dataclass
+class GroupStats:          # SearchEngine.field_stats: one group of one request
+    value: str = ""                                           # the group's value of the group_by field as text (ToString(), the facet key)
+    count: int = 0                                            # members whose value is not a NaN
+    nan: int = 0                                              # members whose value is a NaN: in no other figure
+    min: Optional[object] = None                              # smallest / largest non-NaN value (int for an int column, float for a double one); None when
+    max: Optional[object] = None                              # count == 0
+    sum: object = 0                                           # int column: the exact sum, a Python int; double column: the exact real sum rounded once
+    mean: Optional[float] = None                              # the exact sum / count rounded once; None when count == 0
+
+
+@dataclass
+class FieldStats:          # SearchEngine.field_stats: one per request
+    count: int = 0                                            # members whose value is not a NaN
+    nan: int = 0                                              # members whose value is a NaN (double columns): in no other figure
+    total: int = 0                                            # live documents the filter accepts: count + nan (Listing.total of the same filter)
+    min: Optional[object] = None                              # smallest / largest non-NaN value of the set, as RangeFacets.min / max; None when count == 0
+    max: Optional[object] = None
+    sum: object = 0                                           # int column: the exact sum, a Python int (it may exceed 64 bits); double column: the exact real sum
+    #                                                           of the finite values rounded once (math.fsum's), +-inf / NaN with infinite members
+    mean: Optional[float] = None                              # the exact sum / count rounded once; None when count == 0
+    groups: list = _dc_field(default_factory=list)            # [GroupStats] of every group with a member: members descending, then value ascending; [] without group_by
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+class _StatsReq(C.Structure):          # infx_stats_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("group_by", C.c_char_p)]
+
+
+class _StatsFigures(C.Structure):      # infx_stats_figures (include/infidex_engine.h)
+    _fields_ = [("count", C.c_uint32), ("nan", C.c_uint32), ("kind", C.c_int32), ("reserved", C.c_int32), ("min_i", C.c_int64), ("max_i", C.c_int64),
+                ("min_d", C.c_double), ("max_d", C.c_double), ("sum_d", C.c_double), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("mean", C.c_double)]
+
+
 class _RangeReq(C.Structure):
     _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("nedges", C.c_uint32), ("edges_i", C.POINTER(C.c_int64)), ("edges_d", C.POINTER(C.c_double))]
 
@@ -480,7 +521,7 @@ class SearchEngine:
         buckets [edges[i], edges[i + 1]) (the last one too), with the documents below edges[0], at or above edges[-1] and, on a double column, with a NaN
         value (in no bucket), the size of the set and its smallest and largest non-NaN value.  Returns RangeFacets(edges, counts, below, above, nan, total,
         min, max, error); always nan + below + sum(counts) + above == total.  2 .. 257 edges, strictly increasing as Query.sort_by compares values (-0.0,
-        0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  A sequence of RangeRequest as first argument -> a list of
+        0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  Sums and means: field_stats.  A sequence of RangeRequest as first argument -> a list of
         RangeFacets, sixteen requests per device call, all counted in ONE pass over the corpus (requests of one filter read its mask once); a request
         with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums, means or percentiles (a percentile is
         list_documents(order_by=field, offset=p * total, limit=1))."""
@@ -489,6 +530,22 @@ class SearchEngine:
     def last_range_stats(self, session=None):
         """(masks built, masks reused, k_range_counts launches) of the session's last range_facets device call."""
         return _u32_stats(self, "infx_engine_last_range_stats", session.h if session is not None else self._default_session(), 3)
+
+    def field_stats(self, filter=None, field=None, group_by=None, session=None):
+        """Field statistics (not in the reference): over the documents list_documents(filter) lists — not Deleted, their own fields accepted by `filter`; None:
+        every live document; duplicate keys are documents of their own — the number of values of the int64 or double column `field` that are not a NaN, the
+        NaNs, the smallest and largest value, and the EXACT sum and mean: an int column's sum is a Python int (it may exceed 64 bits), a double column's the
+        exact real sum of the finite values rounded once to nearest-even (what math.fsum returns; beyond the double range +-inf; +inf / -inf / NaN with
+        infinite members), the mean the exact sum / count rounded once.  The device adds integers only, so every run returns the same bytes.  With `group_by`
+        (any column of at most 4096 distinct values, `field` itself included) the same figures for every group that has a member, members descending then value
+        ascending, all of them.  Returns FieldStats(count, nan, total, min, max, sum, mean, groups, error).  A sequence of StatsRequest as first argument ->
+        a list of FieldStats, sixteen requests per device call, all answered in ONE pass over the corpus; a request with a syntax error, MATCHES, a missing,
+        unknown or string field, an unknown or too large group_by, or a double column that spans more than 128 binary digits gets `error` set, alone."""
+        return _field_stats(self, session.h if session is not None else self._default_session(), filter, field, group_by)
+
+    def last_field_stats_stats(self, session=None):
+        """(masks built, masks reused, k_field_stats launches) of the session's last field_stats device call."""
+        return _u32_stats(self, "infx_engine_last_field_stats_stats", session.h if session is not None else self._default_session(), 3)
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -801,6 +858,14 @@ class Session:
     def last_range_stats(self):
         """SearchEngine.last_range_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_range_stats", self.h, 3)
+
+    def field_stats(self, filter=None, field=None, group_by=None):
+        """SearchEngine.field_stats on this session (its mask cache holds the filters' masks)."""
+        return _field_stats(self.engine, self.h, filter, field, group_by)
+
+    def last_field_stats_stats(self):
+        """SearchEngine.last_field_stats_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_field_stats_stats", self.h, 3)
 
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
@@ -1128,6 +1193,46 @@ def _range_facets(engine, sh, filter, field, edges):
     return _per_request(engine, sh, "infx_engine_range_facets", "infx_engine_range_error", _RangeReq,
                         [RangeRequest(filter, field, edges)] if single else list(filter), single, pack, read,
                         lambda r, msg: RangeFacets(tuple(r.edges), [], 0, 0, 0, 0, None, None, msg))
+
+
+_STATS_FIGURES = np.dtype([(name, {C.c_uint32: "<u4", C.c_int32: "<i4", C.c_int64: "<i8", C.c_uint64: "<u8", C.c_double: "<f8"}[ty]) for name, ty in _StatsFigures._fields_])
+
+
+def _stats_figures(f):
+    """(count, nan, min, max, sum, mean) of an infx_stats_figures given as the tuple of its fields; the int column's sum is composed here from its two halves."""
+    count, nan, kind, _, min_i, max_i, min_d, max_d, sum_d, sum_lo, sum_hi, mean = f
+    lo, up = ((min_i, max_i) if kind == 1 else (min_d, max_d)) if count else (None, None)
+    return count, nan, lo, up, (sum_hi << 64) + sum_lo if kind == 1 else sum_d, mean if count else None
+
+
+def _field_stats(engine, sh, filter, field, group_by):
+    """infx_engine_field_stats on session handle sh: a FieldStats for one request (given by its parts), a list of them for a sequence of StatsRequest."""
+    def pack(r):
+        return _StatsReq(*[None if x is None else str(x).encode() for x in (r.filter, r.field, r.group_by)])
+
+    def read(i, r):
+        tot = C.c_uint32(0); whole = _StatsFigures()
+        engine._check(engine.L.infx_engine_field_stats_total(sh, i, C.byref(tot)))
+        engine._check(engine.L.infx_engine_field_stats_whole(sh, i, C.byref(whole)))
+        col = C.c_int32(-1)
+        m = engine.L.infx_engine_field_stats_groups(sh, i, C.byref(col), None, None, 0)
+        if m < 0:
+            engine._check(1)
+        groups = []
+        if m > 0:
+            codes = np.zeros(m, np.uint32); figs = (_StatsFigures * m)()
+            engine.L.infx_engine_field_stats_groups(sh, i, C.byref(col), _p(codes, C.c_uint32), figs, m)
+            vb = C.create_string_buffer(1024)
+            for code, f in zip(codes.tolist(), np.frombuffer(figs, _STATS_FIGURES).tolist()):      # (one conversion for all groups: thousands of them are common)
+                engine.L.infx_engine_column_value(engine.h, col.value, code, vb, 1024)
+                groups.append(GroupStats(vb.value.decode(), *_stats_figures(f)))
+        count, nan, lo, up, total, mean = _stats_figures(np.frombuffer(whole, _STATS_FIGURES)[0].tolist())
+        return FieldStats(count, nan, int(tot.value), lo, up, total, mean, groups, None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_field_stats", "infx_engine_field_stats_error", _StatsReq,
+                        [StatsRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
+                        lambda r, msg: FieldStats(error=msg))
 
 
 def _attach_pre_filter_facets(engine, sh, qs, results):

@@ -725,6 +725,14 @@ class ShardedSearcher:
     def last_range_stats(self):
         return self.sessions[0].s.last_range_stats()
 
+    def field_stats(self, filter=None, field=None, group_by=None):
+        """SearchEngine.field_stats: like range_facets, every rank adds over the whole columns with the global Deleted flags on its own GPU and gets the same
+        answer — nothing is exchanged."""
+        return self.sessions[0].s.field_stats(filter, field, group_by)
+
+    def last_field_stats_stats(self):
+        return self.sessions[0].s.last_field_stats_stats()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
