@@ -479,6 +479,36 @@ int32_t infx_engine_field_stats_groups(infx_session* s, uint32_t which, int32_t*
 int32_t infx_engine_field_stats_total(infx_session* s, uint32_t which, uint32_t* total);
 int32_t infx_engine_field_stats_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_field_stats_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
+/* ---- list_groups: one row per value of a field, in the order of a field, by page (not in the reference: the semantics below are this project's) -----------
+ * Request i lists, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document; duplicate keys are documents of their own — and in its ORDER (k(d), d) for `order_by` and `ascending` (ties by ascending
+ * index in both directions; order_by = NULL: index order):
+ *   GROUP   one dictionary code of field `group_by`, exactly as infx_engine_field_stats forms and names groups (the text of infx_engine_column_value): any
+ *           column of any kind, facetable or not, of any number of distinct values; it may be order_by itself
+ *   HEAD    of a group with a member: its member that comes first in the ORDER — "the cheapest offer of every product", "the newest post of every author"
+ *   ANSWER  the rows at [offset, min(offset + limit, total_groups)) of the heads in the ORDER, i.e. infx_engine_list_documents over the SET restricted to
+ *           the heads: pages never overlap or skip.  Per row the DocumentKey, the internal document, the code of the order_by column, the code of the
+ *           group_by column and the number of members of that group in the SET
+ *   total_groups   the number of groups with a member: the exact distinct count of group_by over the filter       total   the size of the SET
+ * 1 <= limit <= 1024, 0 <= offset < 2^31; offset >= total_groups: an empty page with both totals, no error.  No more than one row per group, no order by
+ * size; nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_group_list_error, the others answered): a syntax error, a missing or unknown
+ * group_by, an unknown order_by or a limit / offset out of range INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most
+ * INFX_MAX_PREFILTERS (16) requests (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), every refusal but the filter's already in
+ * out_status; a call that failed as a whole leaves nothing for the readers.  The masks are the session's pre-filter masks (slots, least-recently-used rule,
+ * epoch and statistics of infx_engine_list_documents; the ones a call is missing are built in ONE launch in front of it); order_by's sort rank is built on
+ * its first use.  Requests that share filter, group_by, order_by and direction — the pages of one listing — share one head pass.  Exact and deterministic:
+ * the same bytes from any session, stream and rank.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_group_list_rows copies up to cap rows and returns the page's row count (-1 for a
+ * refused request or bad arguments); infx_engine_group_list_totals both totals (returning the request's status); infx_engine_group_list_error the refusal's
+ * message (its length; -1 out of range).  infx_engine_last_group_list_stats: masks built and reused, head passes, histogram passes and kernel launches of
+ * the session's last call.  infx_engine_set_list_digit_bits governs the pages' select here too. */
+typedef struct infx_group_list_request { const char* filter; const char* group_by; const char* order_by; int32_t ascending; uint32_t offset; uint32_t limit; } infx_group_list_request;
+int32_t infx_engine_list_groups(infx_session* s, uint32_t nreq, const infx_group_list_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_group_list_rows(infx_session* s, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, uint32_t* group_codes, uint32_t* sizes, int32_t cap);
+int32_t infx_engine_group_list_totals(infx_session* s, uint32_t which, uint32_t* total_groups, uint32_t* total);
+int32_t infx_engine_group_list_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_group_list_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

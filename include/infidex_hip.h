@@ -474,6 +474,35 @@ typedef struct infx_stats_slot { uint32_t finite; uint32_t nan; uint32_t pinf; u
 int32_t infx_upload_column_values(infx_index* idx, uint32_t col, uint32_t num_values, const uint64_t* bits, int32_t kind, int32_t scale_exp, uint32_t nlimbs);
 int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out /* sum of the requests' slots */);
 int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches);
+/* A page of the HEADS of a document set's groups, in the order of a column, with the groups' sizes (not in the reference: the collapsed listing is this
+ * project's; DESIGN.md "list_groups").
+ * Request i: the SET, the KEY and the ORDER (key, global internal id) are infx_list_ordered's, over `mask` (a mask slot of this stream, or NULL: every
+ * document that is not Deleted), column `col` (-1: a constant key) and `ascending`.  A GROUP is one code of uploaded column `group_col` (any kind, any
+ * number of values; it may be `col`); the HEAD of a group with a member is its member that comes first in the ORDER.  The answer is the rows at positions
+ * [offset, min(offset + limit, groups)) of the heads in the ORDER — infx_list_ordered over the SET restricted to the heads: per row the DocumentKey, the
+ * global internal id, the code of `col` (0 without a column), the group's code and the number of members of that group in the SET, in keys_out / docs_out /
+ * codes_out / gcodes_out / sizes_out at [i * INFX_POST_MAX_ROWS ..]; counts_out[i] rows, group_totals_out[i] = the number of groups with a member (the exact
+ * distinct count of group_col over the set), totals_out[i] = the size of the SET.  Rows from counts_out[i] up to limit read -1 / -1 / 0 / 0 / 0.
+ * offset >= groups: no rows, no error.  limit, offset, digit_bits and the number of requests as in infx_list_ordered.
+ * A SPEC is (mask, group_col, col, ascending); the requests of a call are taken in spec order and the specs run one after another on the stream:
+ *   k_group_heads       one walk over the corpus per spec: every member takes the 64-bit minimum of (key << 32 | id) into the entry of its group code in the
+ *                       head table (8 B per value of group_col), asked of the memory only when a plain read shows a larger entry.  Tables of at most 8 191
+ *                       values lie in LDS per workgroup, up to 20 479 values in the whole LDS of a CU under one workgroup of 1024 threads, and are merged
+ *                       with one global minimum per entry that saw a member; larger tables are hit in global memory.  The walk also counts the set.
+ *   k_group_heads_mask  byte d = 0 exactly when d is a member and the low word of its group's entry is d: the heads as a mask.
+ *   the page            infx_list_ordered's select / count / prefix / gather / sort over the heads mask, per request.
+ *   k_group_page, k_group_sizes   the group codes of every page's rows, sorted; ONE further walk over the SET for all requests of the spec looks every member's
+ *                       code up among them and adds to the row's counter.
+ * A minimum has no order and the adds are integer adds, none decides a position: the same bytes from any stream, grid and placement.  A mask build staged
+ * with infx_filter_masks is enqueued first, as ONE launch; nothing waits for the host between the kernels.  Works on a sharded index (whole columns and
+ * global flags on every rank).  Synchronous.
+ * infx_last_group_list_stats: head passes (= specs), histogram passes (summed over the requests) and kernel launches (the mask build included) of the
+ * stream's last call. */
+typedef struct infx_group_list_req { const uint8_t* mask; int32_t col; int32_t ascending; uint32_t offset; uint32_t limit; uint32_t digit_bits; uint32_t reserved; int32_t group_col; int32_t reserved2; } infx_group_list_req;
+int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
+                          uint32_t* gcodes_out, uint32_t* sizes_out, uint32_t* counts_out /* nreq */, uint32_t* group_totals_out /* nreq */,
+                          uint32_t* totals_out /* nreq */);
+int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -103,6 +103,9 @@ struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vecto
 // One request of the session's last infx_engine_field_stats: its status and message, the whole's figures, the group column (-1: none) and the groups that have a
 // member, in the contract's order
 struct StatsAnswer : Answer { infx_stats_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_stats_figures> groups; };
+// One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
+// row what a ListAnswer holds, the group's code and its size
+struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 struct infx_session {
     QueryCov qc;
@@ -123,6 +126,8 @@ struct infx_session {
     std::vector<RangeAnswer> rng; MaskUse rngMasks; uint32_t rngLaunches = 0;
     // infx_engine_field_stats: likewise, with the k_field_stats launches of that call
     std::vector<StatsAnswer> sts; MaskUse stsMasks; uint32_t stsLaunches = 0;
+    // infx_engine_list_groups: likewise, with the head passes, histogram passes and kernel launches of that call (the digit width is lstDigitBits)
+    std::vector<GroupListAnswer> grp; MaskUse grpMasks; uint32_t grpHeads = 0, grpPasses = 0, grpLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -3182,7 +3187,7 @@ int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counte
     return put_stats({{counted, S->ffCounted}, {cached, S->ffCached}, {launches, S->ffLaunches}});
 }
 
-// ---- requests over the documents a filter accepts: infx_engine_list_documents, infx_engine_range_facets and infx_engine_field_stats --------------------
+// ---- requests over the documents a filter accepts: infx_engine_list_documents, _range_facets, _field_stats and _list_groups -----------------------------
 // Each takes up to INFX_MAX_PREFILTERS requests, answer each on its own (a refusal is the request's: its status in out_status[i], its message with the answer)
 // and leave the answers on the session for the readers.  A call that fails as a whole leaves no answers behind — the readers refuse — while the statuses
 // already written to out_status stay.  The filters and their masks are a MaskCall's.
@@ -3572,6 +3577,95 @@ int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out
 int32_t infx_engine_last_field_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->stsMasks.built}, {masks_reused, S->stsMasks.reused}, {launches, S->stsLaunches}});
+}
+
+// ---- list_groups: one row per value of a field — the group's first document in the order of a field — by page (not in the reference) ---------------------
+// Per request, as infx_engine_list_documents: the filter through the filter cache, its mask through the session's mask cache, order_by to its column, whose
+// sort rank is built on first use; group_by to its column (any kind: the group is the dictionary code).  infx_list_grouped then finds the heads of every
+// (mask, group column, order column, direction) once and pages over them; the answers stay on the session for the readers.
+int32_t infx_engine_list_groups(infx_session* S, uint32_t nreq, const infx_group_list_request* reqs, int32_t* out_status) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->grp.clear(); S->grpMasks = MaskUse(); S->grpHeads = S->grpPasses = S->grpLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) list_groups requests in one call");
+    S->grp.assign(nreq, GroupListAnswer());
+    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->grp[i].status = rc; S->grp[i].err = msg; if (out_status) out_status[i] = rc; };
+    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (out_status) out_status[i] = INFX_OK;
+            if (reqs[i].limit < 1 || reqs[i].limit > INFX_POST_MAX_ROWS) refuse(i, INFX_EINVAL, "a listing's limit is 1 .. 1024");
+            else if (reqs[i].offset >= 0x80000000u) refuse(i, INFX_EINVAL, "a listing's offset is below 2^31");
+            else if (!reqs[i].group_by) refuse(i, INFX_EINVAL, "list_groups needs a group_by field");
+            else if ((gcol[i] = column_named(e, reqs[i].group_by)) < 0) refuse(i, INFX_EINVAL, std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'");
+            else if (reqs[i].order_by && column_named(e, reqs[i].order_by) < 0) refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'");
+        }
+    }
+    { int32_t rc = need_indexed_device(S, "list_groups"); if (rc) { S->grp.clear(); return rc; } }
+    MaskCall mc(S, nreq, &S->grpMasks);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (S->grp[i].status) continue;
+            if ((gcol[i] = column_named(e, reqs[i].group_by)) < 0) { refuse(i, INFX_EINVAL, std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'"); continue; }
+            if (reqs[i].order_by) {
+                uint32_t c = 0xFFFFFFFFu;
+                const int32_t rc = sort_column(e, reqs[i].order_by, &c);
+                if (rc) { refuse(i, rc, g_eerr); continue; }
+                if (c == 0xFFFFFFFFu) { refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'"); continue; }
+                col[i] = (int32_t)c;
+            }
+            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) refuse(i, rc, g_eerr); }
+        }
+    }
+    { int32_t rc = mc.acquire(); if (rc) { S->grp.clear(); return rc; } }
+    std::vector<infx_group_list_req> dr; std::vector<uint32_t> who;
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (S->grp[i].status) continue;
+        infx_group_list_req R{};
+        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit;
+        R.digit_bits = (uint32_t)S->lstDigitBits;
+        dr.push_back(R); who.push_back(i);
+    }
+    const size_t m = dr.size(), rows = INFX_POST_MAX_ROWS, cap = std::max<size_t>(m, 1);
+    std::vector<int64_t> keys(cap * rows); std::vector<int32_t> docs(cap * rows); std::vector<uint32_t> codes(cap * rows), gcodes(cap * rows), sizes(cap * rows);
+    std::vector<uint32_t> counts(cap, 0), groups(cap, 0), totals(cap, 0);
+    int32_t rc = infx_list_grouped(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), gcodes.data(), sizes.data(), counts.data(), groups.data(), totals.data());
+    if (rc) { S->grp.clear(); return mc.failed(rc); }
+    mc.done();
+    infx_last_group_list_stats(S->stream, &S->grpHeads, &S->grpPasses, &S->grpLaunches);
+    for (size_t j = 0; j < m; j++) {
+        GroupListAnswer& A = S->grp[who[j]];
+        const size_t c = std::min<size_t>(counts[j], dr[j].limit), at = j * rows;
+        A.total = totals[j]; A.totalGroups = groups[j];
+        A.keys.assign(keys.begin() + at, keys.begin() + at + c); A.docs.assign(docs.begin() + at, docs.begin() + at + c);
+        A.codes.assign(codes.begin() + at, codes.begin() + at + c); A.gcodes.assign(gcodes.begin() + at, gcodes.begin() + at + c);
+        A.sizes.assign(sizes.begin() + at, sizes.begin() + at + c);
+    }
+    return INFX_OK;
+}
+// request `which` of the session's last infx_engine_list_groups: up to cap rows; returns the page's row count, -1 on error (also for a refused request)
+int32_t infx_engine_group_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, uint32_t* group_codes, uint32_t* sizes, int32_t cap) {
+    const GroupListAnswer* A = answer_at(S ? &S->grp : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!keys || !docs || !codes || !group_codes || !sizes))) return -1;
+    const size_t c = std::min<size_t>(A->keys.size(), (size_t)std::max(cap, 0));
+    if (c) {
+        std::memcpy(keys, A->keys.data(), c * 8); std::memcpy(docs, A->docs.data(), c * 4); std::memcpy(codes, A->codes.data(), c * 4);
+        std::memcpy(group_codes, A->gcodes.data(), c * 4); std::memcpy(sizes, A->sizes.data(), c * 4);
+    }
+    return (int32_t)A->keys.size();
+}
+// the number of groups with a member and the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_group_list_totals(infx_session* S, uint32_t which, uint32_t* total_groups, uint32_t* total) {
+    const GroupListAnswer* A = answer_at(S ? &S->grp : nullptr, which);
+    if (A && total_groups) *total_groups = A->totalGroups;
+    return answer_total(total_groups ? A : nullptr, total, "no such request in the session's last list_groups call");
+}
+int32_t infx_engine_group_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->grp : nullptr, which), out, cap); }
+int32_t infx_engine_last_group_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->grpMasks.built}, {masks_reused, S->grpMasks.reused}, {head_passes, S->grpHeads}, {hist_passes, S->grpPasses}, {launches, S->grpLaunches}});
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

@@ -265,6 +265,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "listing.hip.inc"
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
+#include "groups.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -368,6 +369,8 @@ struct infx_stream {
     uint32_t lastRngReqs = 0, lastRngLaunches = 0;             // requests and k_range_counts launches of the last infx_range_counts
     void* dStsOut = nullptr; size_t capStsOut = 0; std::vector<uint32_t> hStsRaw;      // infx_field_stats: the requests' slots and smallest ranks; their host copy
     uint32_t lastStsReqs = 0, lastStsLaunches = 0;             // requests and k_field_stats launches of the last infx_field_stats
+    void* dGrpWs = nullptr; size_t capGrpWs = 0;               // infx_list_grouped: a spec's head table and heads mask; per request the page's sorted codes, rows, group codes and sizes
+    uint32_t lastGrpHeads = 0, lastGrpPasses = 0, lastGrpLaunches = 0;      // head passes, histogram passes and kernel launches of the last infx_list_grouped
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1306,7 +1309,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -3046,6 +3049,83 @@ static int32_t check_set_request(const infx_stream* s, const uint8_t* mask, int3
     return INFX_OK;
 }
 // ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
+// The enqueue part of a listing call, shared by infx_list_ordered and infx_list_grouped.  Where the nreq requests of a call lie in the stream's listing
+// workspace W ([states | histograms] zeroed, [page composites] all ones, range counts and prefixes [nreq][2][3][nRanges]) and in its rows O
+// ([keys | docs | codes | counts | totals], INFX_POST_MAX_ROWS rows per request).
+struct ListLayout {
+    int32_t n; uint32_t nreq, tiles, nRanges;
+    size_t stBytes, oHist, oPairs, oRange, oDocs, oCodes, oCnt, oTot, histOff[INFX_MAX_PREFILTERS];
+    char *W, *O;
+    int32_t* docs(uint32_t i) const { return (int32_t*)(O + oDocs) + (size_t)i * INFX_POST_MAX_ROWS; }
+    uint32_t* count(uint32_t i) const { return (uint32_t*)(O + oCnt) + i; }
+    uint32_t* total(uint32_t i) const { return (uint32_t*)(O + oTot) + i; }
+};
+// what a request reads of the index: the set (mask or the Deleted flags), the ordered column with its sort rank, the passes of its select
+static DevListReq list_dev_req(const infx_index* ix, const uint8_t* mask, int32_t col, bool ascending, uint32_t offset, uint32_t limit, uint32_t digitBits) {
+    DevListReq D{};
+    D.mask = mask ? mask : ix->d.deleted;
+    if (col >= 0) { D.codes = ix->colCodes[col]; D.rank = ix->colRank[col]; D.nvals = ix->colValues[col]; } else D.nvals = 1;
+    D.ascending = ascending ? 1u : 0u; D.offset = offset; D.limit = limit; D.digitBits = digitBits; D.passes = ls_passes(D.nvals, digitBits);
+    return D;
+}
+// the workspace of nreq requests, grown and initialised on the stream
+static int32_t list_prepare(infx_stream* s, int32_t n, uint32_t nreq, const DevListReq* D, ListLayout* L) {
+    L->n = n; L->nreq = nreq;
+    size_t histWords = 0;
+    for (uint32_t i = 0; i < nreq; i++) { L->histOff[i] = histWords; histWords += (size_t)D[i].passes * 2u << D[i].digitBits; }
+    L->tiles = (uint32_t)(((int64_t)n + LST_TILE - 1) / LST_TILE); L->nRanges = std::max(1u, std::min(LST_MAXRANGES, L->tiles));
+    L->stBytes = (sizeof(DevListState) + 63) & ~(size_t)63;
+    L->oHist = (size_t)nreq * L->stBytes; L->oPairs = (L->oHist + histWords * 4 + 63) & ~(size_t)63; L->oRange = L->oPairs + (size_t)nreq * INFX_POST_MAX_ROWS * 8;
+    const size_t wsBytes = L->oRange + (size_t)nreq * 6 * L->nRanges * 4;
+    const size_t R = INFX_POST_MAX_ROWS;
+    L->oDocs = (size_t)nreq * R * 8; L->oCodes = L->oDocs + (size_t)nreq * R * 4; L->oCnt = L->oCodes + (size_t)nreq * R * 4; L->oTot = L->oCnt + (size_t)nreq * 4;
+    GROW(s->dListWs, s->capListWs, wsBytes);
+    GROW(s->dListOut, s->capListOut, L->oTot + (size_t)nreq * 4);
+    L->W = (char*)s->dListWs; L->O = (char*)s->dListOut;
+    HIPCHK(hipMemsetAsync(L->W, 0, L->oPairs, s->st));
+    HIPCHK(hipMemsetAsync(L->W + L->oPairs, 0xFF, (size_t)nreq * INFX_POST_MAX_ROWS * 8, s->st));
+    s->unsynced = true;
+    return INFX_OK;
+}
+// request i of the layout: select, count, prefix, gather and sort on the stream, and its rows' way back to the caller's keys / docs / codes (the request's own
+// rows: D.limit of each).  *histPasses / *launches grow by what was enqueued.
+static int32_t list_enqueue(infx_stream* s, const ListLayout& L, uint32_t i, const DevListReq& D, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
+                            uint32_t* histPasses, uint32_t* launches) {
+    const int32_t n = L.n; const uint32_t nRanges = L.nRanges, tiles = L.tiles; const size_t R = INFX_POST_MAX_ROWS;
+    char* W = L.W; char* O = L.O;
+    DevListState* st = (DevListState*)(W + (size_t)i * L.stBytes);
+    uint32_t* hist = (uint32_t*)(W + L.oHist) + L.histOff[i];
+    unsigned long long* pairs = (unsigned long long*)(W + L.oPairs) + (size_t)i * INFX_POST_MAX_ROWS;
+    uint32_t* rangeCnt = (uint32_t*)(W + L.oRange) + (size_t)i * 6 * nRanges; uint32_t* rangePre = rangeCnt + 3 * (size_t)nRanges;
+    if (n > 0) {
+        const size_t nb = (size_t)1 << D.digitBits;
+        const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
+        const int grid = (int)std::min<int64_t>(FCM_MAXGRID, (groups + LST_THREADS - 1) / LST_THREADS);
+        for (uint32_t p = 0; p < D.passes; p++) {
+            k_list_hist<<<grid, LST_THREADS, 2 * nb * 4, s->st>>>(D, n, p, st, hist + (size_t)p * 2 * nb);
+            k_list_pick<<<1, LST_THREADS, 0, s->st>>>(D, p, st, hist + (size_t)p * 2 * nb);
+        }
+        k_list_count<<<nRanges, LST_THREADS, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt);
+        k_list_prefix<<<3, LST_THREADS, 0, s->st>>>(nRanges, st, rangeCnt, rangePre);
+        k_list_gather<<<nRanges, WAVE, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt, rangePre, pairs);
+        *histPasses += D.passes; *launches += 2 * D.passes + 3;
+    }
+    k_list_sort<<<1, LST_SORT_THREADS, 0, s->st>>>(D, n, st, pairs, (const long long*)s->ix->d.docKeyAll, (long long*)O + (size_t)i * R, L.docs(i),
+                                                 (uint32_t*)(O + L.oCodes) + (size_t)i * R, L.count(i), L.total(i));
+    HIPCHK(hipGetLastError());
+    ++*launches;
+    DOWN(keys_out, (long long*)O + (size_t)i * R, (size_t)D.limit * 8);
+    DOWN(docs_out, L.docs(i), (size_t)D.limit * 4);
+    DOWN(codes_out, (uint32_t*)(O + L.oCodes) + (size_t)i * R, (size_t)D.limit * 4);
+    return INFX_OK;
+}
+// a request's page: limit, offset and digit width in range
+static int32_t check_page_request(uint32_t limit, uint32_t offset, uint32_t digitBits) {
+    if (limit < 1 || limit > INFX_POST_MAX_ROWS) return fail(INFX_EINVAL, "a listing's limit is 1 .. INFX_POST_MAX_ROWS (1024)%s");
+    if (offset >= 0x80000000u) return fail(INFX_EINVAL, "a listing's offset is below 2^31%s");
+    if (digitBits < LS_MIN_DIGIT_BITS || digitBits > LS_MAX_DIGIT_BITS) return fail(INFX_EINVAL, "a listing's digit width is 4 .. 11 bits%s");
+    return INFX_OK;
+}
 int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* counts_out, uint32_t* totals_out) {
     if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !counts_out || !totals_out))) return fail(INFX_EINVAL, "bad listing arguments%s");
     s->lastListPasses = 0; s->lastListLaunches = 0;
@@ -3053,15 +3133,12 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
     infx_index* ix = s->ix;
     if (!ix->haveDocs || !ix->d.docKeyAll) return fail(INFX_EINVAL, "index not uploaded%s");
     const int32_t n = std::max(ix->d.totalDocs, 0);
-    uint32_t passes[INFX_MAX_PREFILTERS] = {}; size_t histOff[INFX_MAX_PREFILTERS] = {}, histWords = 0;
+    DevListReq D[INFX_MAX_PREFILTERS];
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_list_req& Q = reqs[i];
-        if (Q.limit < 1 || Q.limit > INFX_POST_MAX_ROWS) return fail(INFX_EINVAL, "a listing's limit is 1 .. INFX_POST_MAX_ROWS (1024)%s");
-        if (Q.offset >= 0x80000000u) return fail(INFX_EINVAL, "a listing's offset is below 2^31%s");
-        if (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS) return fail(INFX_EINVAL, "a listing's digit width is 4 .. 11 bits%s");
+        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "listing"); if (rc_) return rc_; }
-        passes[i] = ls_passes(Q.col >= 0 ? ix->colValues[Q.col] : 1u, Q.digit_bits);
-        histOff[i] = histWords; histWords += (size_t)passes[i] * 2u << Q.digit_bits;
+        D[i] = list_dev_req(ix, Q.mask, Q.col, Q.ascending != 0, Q.offset, Q.limit, Q.digit_bits);
     }
     HIPCHK(enter_device(ix->cfg.device));
     { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
@@ -3069,51 +3146,14 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
     { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
     s->lastListLaunches = builds;
     if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
-    const uint32_t tiles = (uint32_t)(((int64_t)n + LST_TILE - 1) / LST_TILE), nRanges = std::max(1u, std::min(LST_MAXRANGES, tiles));
-    // workspace: [states | histograms] (zeroed), [page composites] (all ones), range counts and prefixes [nreq][2][3][nRanges]
-    const size_t stBytes = (sizeof(DevListState) + 63) & ~(size_t)63;
-    const size_t oHist = (size_t)nreq * stBytes, oPairs = (oHist + histWords * 4 + 63) & ~(size_t)63, oRange = oPairs + (size_t)nreq * INFX_POST_MAX_ROWS * 8;
-    const size_t wsBytes = oRange + (size_t)nreq * 6 * nRanges * 4;
-    const size_t R = INFX_POST_MAX_ROWS, oDocs = (size_t)nreq * R * 8, oCodes = oDocs + (size_t)nreq * R * 4, oCnt = oCodes + (size_t)nreq * R * 4, oTot = oCnt + (size_t)nreq * 4;
-    GROW(s->dListWs, s->capListWs, wsBytes);
-    GROW(s->dListOut, s->capListOut, oTot + (size_t)nreq * 4);
-    char* W = (char*)s->dListWs; char* O = (char*)s->dListOut;
-    HIPCHK(hipMemsetAsync(W, 0, oPairs, s->st));
-    HIPCHK(hipMemsetAsync(W + oPairs, 0xFF, (size_t)nreq * INFX_POST_MAX_ROWS * 8, s->st));
-    s->unsynced = true;
+    ListLayout L;
+    { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
     for (uint32_t i = 0; i < nreq; i++) {
-        const infx_list_req& Q = reqs[i];
-        DevListReq D{};
-        D.mask = Q.mask ? Q.mask : ix->d.deleted;
-        if (Q.col >= 0) { D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col]; } else D.nvals = 1;
-        D.ascending = Q.ascending ? 1u : 0u; D.offset = Q.offset; D.limit = Q.limit; D.digitBits = Q.digit_bits; D.passes = passes[i];
-        DevListState* st = (DevListState*)(W + (size_t)i * stBytes);
-        uint32_t* hist = (uint32_t*)(W + oHist) + histOff[i];
-        unsigned long long* pairs = (unsigned long long*)(W + oPairs) + (size_t)i * INFX_POST_MAX_ROWS;
-        uint32_t* rangeCnt = (uint32_t*)(W + oRange) + (size_t)i * 6 * nRanges; uint32_t* rangePre = rangeCnt + 3 * (size_t)nRanges;
-        if (n > 0) {
-            const size_t nb = (size_t)1 << Q.digit_bits;
-            const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
-            const int grid = (int)std::min<int64_t>(FCM_MAXGRID, (groups + LST_THREADS - 1) / LST_THREADS);
-            for (uint32_t p = 0; p < passes[i]; p++) {
-                k_list_hist<<<grid, LST_THREADS, 2 * nb * 4, s->st>>>(D, n, p, st, hist + (size_t)p * 2 * nb);
-                k_list_pick<<<1, LST_THREADS, 0, s->st>>>(D, p, st, hist + (size_t)p * 2 * nb);
-            }
-            k_list_count<<<nRanges, LST_THREADS, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt);
-            k_list_prefix<<<3, LST_THREADS, 0, s->st>>>(nRanges, st, rangeCnt, rangePre);
-            k_list_gather<<<nRanges, WAVE, 0, s->st>>>(D, n, tiles, nRanges, st, rangeCnt, rangePre, pairs);
-            s->lastListPasses += passes[i]; s->lastListLaunches += 2 * passes[i] + 3;
-        }
-        k_list_sort<<<1, LST_SORT_THREADS, 0, s->st>>>(D, n, st, pairs, (const long long*)ix->d.docKeyAll, (long long*)O + (size_t)i * R, (int32_t*)(O + oDocs) + (size_t)i * R,
-                                                     (uint32_t*)(O + oCodes) + (size_t)i * R, (uint32_t*)(O + oCnt) + i, (uint32_t*)(O + oTot) + i);
-        HIPCHK(hipGetLastError());
-        s->lastListLaunches++;
-        DOWN(keys_out + (size_t)i * R, (long long*)O + (size_t)i * R, (size_t)Q.limit * 8);
-        DOWN(docs_out + (size_t)i * R, (int32_t*)(O + oDocs) + (size_t)i * R, (size_t)Q.limit * 4);
-        DOWN(codes_out + (size_t)i * R, (uint32_t*)(O + oCodes) + (size_t)i * R, (size_t)Q.limit * 4);
+        const size_t at = (size_t)i * INFX_POST_MAX_ROWS;
+        int32_t rc_ = list_enqueue(s, L, i, D[i], keys_out + at, docs_out + at, codes_out + at, &s->lastListPasses, &s->lastListLaunches); if (rc_) return rc_;
     }
-    DOWN(counts_out, O + oCnt, (size_t)nreq * 4);
-    DOWN(totals_out, O + oTot, (size_t)nreq * 4);
+    DOWN(counts_out, L.count(0), (size_t)nreq * 4);
+    DOWN(totals_out, L.total(0), (size_t)nreq * 4);
     SYNC();
     return INFX_OK;
 }
@@ -3298,6 +3338,131 @@ int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t*
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (requests) *requests = s->lastStsReqs;
     if (launches) *launches = s->lastStsLaunches;
+    return INFX_OK;
+}
+// ---- list_groups: a page of the heads of a document set's groups, in the order of a column, with the groups' sizes (groups.hip.inc) ----
+int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* gcodes_out,
+                          uint32_t* sizes_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
+    if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !gcodes_out || !sizes_out || !counts_out || !group_totals_out || !totals_out)))
+        return fail(INFX_EINVAL, "bad grouped-listing arguments%s");
+    s->lastGrpHeads = 0; s->lastGrpPasses = 0; s->lastGrpLaunches = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) grouped-listing requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs || !ix->d.docKeyAll) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    uint32_t gvMax = 1;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_group_list_req& Q = reqs[i];
+        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "grouped listing"); if (rc_) return rc_; }
+        if (Q.group_col < 0 || Q.group_col >= FILT_MAXCOL || !ix->colCodes[Q.group_col]) return fail(INFX_EINVAL, "the grouped listing's group column was not uploaded%s");
+        { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.group_col); if (rc_) return rc_; }
+        gvMax = std::max(gvMax, ix->colValues[Q.group_col]);
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
+    s->lastGrpLaunches = builds;
+    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    // requests of one spec — (mask, group column, order column, direction) — follow one another: they share the head pass, the heads mask and the size walk
+    uint32_t order[INFX_MAX_PREFILTERS];
+    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
+    auto same_spec = [&](const infx_group_list_req& A, const infx_group_list_req& B) { return A.mask == B.mask && A.group_col == B.group_col && A.col == B.col && (A.ascending != 0) == (B.ascending != 0); };
+    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
+        const infx_group_list_req &A = reqs[a], &B = reqs[b];
+        if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
+        if (A.group_col != B.group_col) return A.group_col < B.group_col;
+        return A.col != B.col ? A.col < B.col : (A.ascending != 0) < (B.ascending != 0); });
+    // workspace, one spec at a time: [head table | heads mask (whole groups of 16 bytes)]; then per spec its set's size, per request [sorted codes | rows | group codes | sizes]
+    const size_t R = INFX_POST_MAX_ROWS, groups16 = ((size_t)n + LST_GROUP - 1) / LST_GROUP;
+    const size_t oHeads = ((size_t)gvMax * 8 + 63) & ~(size_t)63, oTot = (oHeads + groups16 * LST_GROUP + 63) & ~(size_t)63, oSorted = oTot + INFX_MAX_PREFILTERS * 4;
+    const size_t oPerm = oSorted + (size_t)nreq * R * 4, oGc = oPerm + (size_t)nreq * R * 4, oSizes = oGc + (size_t)nreq * R * 4;
+    GROW(s->dGrpWs, s->capGrpWs, oSizes + (size_t)nreq * R * 4);
+    char* G0 = (char*)s->dGrpWs;
+    uint32_t* dTot = (uint32_t*)(G0 + oTot); uint32_t* dSorted = (uint32_t*)(G0 + oSorted); uint32_t* dPerm = (uint32_t*)(G0 + oPerm);
+    uint32_t* dGc = (uint32_t*)(G0 + oGc); uint32_t* dSizes = (uint32_t*)(G0 + oSizes);
+    HIPCHK(hipMemsetAsync(dTot, 0, INFX_MAX_PREFILTERS * 4, s->st));
+    s->unsynced = true;
+    // the pages are listings over the heads mask
+    DevListReq D[INFX_MAX_PREFILTERS];
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_group_list_req& Q = reqs[order[k]];
+        D[k] = list_dev_req(ix, (const uint8_t*)(G0 + oHeads), Q.col, Q.ascending != 0, Q.offset, Q.limit, Q.digit_bits);
+    }
+    ListLayout L;
+    { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
+    int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device)); cus = std::max(cus, 1);
+    const int64_t groups = (int64_t)groups16;
+    // a walk with `words` words of LDS per workgroup: 256 threads while they fit k_field_stats' budget, else one workgroup of 1024 per CU; never more workgroups than are
+    // resident (each merges its LDS once)
+    auto walk_shape = [&](uint32_t words, int* threads, int* grid) {
+        *threads = words <= GRP_LDS_WORDS ? GRP_THREADS : GRP_BIG_THREADS;
+        const int64_t perCu = std::min<int64_t>(2048 / *threads, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)words * 4, 1)));
+        *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * std::max<int64_t>(perCu, 1), (groups + *threads - 1) / *threads));
+    };
+    uint32_t spec = 0;
+    for (uint32_t k0 = 0; k0 < nreq; spec++) {
+        uint32_t k1 = k0 + 1;
+        while (k1 < nreq && same_spec(reqs[order[k0]], reqs[order[k1]])) k1++;
+        const infx_group_list_req& Q = reqs[order[k0]];
+        DevGroupSpec G{};
+        G.mask = Q.mask ? Q.mask : ix->d.deleted; G.gcodes = ix->colCodes[Q.group_col]; G.gvals = ix->colValues[Q.group_col];
+        G.ocodes = D[k0].codes; G.orank = D[k0].rank; G.onvals = D[k0].nvals; G.ascending = D[k0].ascending;
+        G.table = (unsigned long long*)G0; G.heads = (uint8_t*)(G0 + oHeads); G.total = dTot + spec;
+        if (n > 0) {
+            HIPCHK(hipMemsetAsync(G.table, 0xFF, (size_t)std::max(G.gvals, 1u) * 8, s->st));
+            // the table and the workgroup's member counter (two words) in LDS while they fit one of the two budgets
+            const uint32_t words = 2u * G.gvals + 2u;
+            G.inLds = words <= GRP_BIG_LDS_WORDS ? 1u : 0u;
+            int threads, grid; walk_shape(G.inLds ? words : 2u, &threads, &grid);
+            const size_t lds = (size_t)(G.inLds ? words : 2u) * 4;
+            HIPCHK(lds_limit((const void*)k_group_heads, ix->cfg.device, lds));
+            k_group_heads<<<grid, threads, lds, s->st>>>(G, n);
+            k_group_heads_mask<<<(int)std::min<int64_t>(FCM_MAXGRID, (groups + GRP_THREADS - 1) / GRP_THREADS), GRP_THREADS, 0, s->st>>>(G, n);
+            HIPCHK(hipGetLastError());
+            s->lastGrpHeads++; s->lastGrpLaunches += 2;
+        }
+        for (uint32_t k = k0; k < k1; k++) {
+            const size_t at = (size_t)order[k] * R;
+            int32_t rc_ = list_enqueue(s, L, k, D[k], keys_out + at, docs_out + at, codes_out + at, &s->lastGrpPasses, &s->lastGrpLaunches); if (rc_) return rc_;
+        }
+        k_group_page<<<k1 - k0, LST_SORT_THREADS, 0, s->st>>>(G.gcodes, n, L.docs(k0), L.count(k0), dGc + (size_t)k0 * R, dSorted + (size_t)k0 * R, dPerm + (size_t)k0 * R, dSizes + (size_t)k0 * R);
+        HIPCHK(hipGetLastError());
+        s->lastGrpLaunches++;
+        if (n > 0) {
+            DevGroupSizes Z{};
+            Z.mask = G.mask; Z.gcodes = G.gcodes; Z.nreq = k1 - k0;
+            uint32_t words = 0;
+            for (uint32_t k = k0; k < k1; k++) {
+                const uint32_t q = k - k0;
+                Z.cnt[q] = L.count(k); Z.sorted[q] = dSorted + (size_t)k * R; Z.perm[q] = dPerm + (size_t)k * R; Z.sizes[q] = dSizes + (size_t)k * R;
+                Z.ldsOff[q] = words; Z.limit[q] = D[k].limit; words += 2u * D[k].limit;
+            }
+            int threads, grid; walk_shape(words, &threads, &grid);
+            HIPCHK(lds_limit((const void*)k_group_sizes, ix->cfg.device, (size_t)words * 4));
+            k_group_sizes<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
+            HIPCHK(hipGetLastError());
+            s->lastGrpLaunches++;
+        }
+        for (uint32_t k = k0; k < k1; k++) {
+            const uint32_t i = order[k];
+            DOWN(gcodes_out + (size_t)i * R, dGc + (size_t)k * R, (size_t)D[k].limit * 4);
+            DOWN(sizes_out + (size_t)i * R, dSizes + (size_t)k * R, (size_t)D[k].limit * 4);
+            DOWN(counts_out + i, L.count(k), 4);
+            DOWN(group_totals_out + i, L.total(k), 4);
+            DOWN(totals_out + i, dTot + spec, 4);
+        }
+        k0 = k1;
+    }
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (head_passes) *head_passes = s->lastGrpHeads;
+    if (hist_passes) *hist_passes = s->lastGrpPasses;
+    if (launches) *launches = s->lastGrpLaunches;
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

@@ -175,6 +175,27 @@ class Listing:             # SearchEngine.list_documents: one per request
 
 
 @dataclass
+class GroupListRequest:    # SearchEngine.list_groups: one page of one collapsed listing
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    group_by: Optional[str] = None      # field whose values form the groups: any column, any number of distinct values (required)
+    order_by: Optional[str] = None      # field whose values order the documents; None: index order
+    ascending: bool = True              # False: largest value first — documents of equal value still by ascending index
+    offset: int = 0                     # position of the page's first row among the groups' heads, 0 <= offset < 2**31
+    limit: int = 20                     # rows of the page, 1 .. 1024
+
+
+@dataclass
+class GroupListing:        # SearchEngine.list_groups: one per request
+    document_ids: list = _dc_field(default_factory=list)      # DocumentKeys of the page's rows: each the head of its group, the member first in the order
+    values: list = _dc_field(default_factory=list)            # the rows' order_by values as text (ToString()); [] when order_by is None
+    group_values: list = _dc_field(default_factory=list)      # the rows' group_by values as text (the facet key, GroupStats.value)
+    group_sizes: list = _dc_field(default_factory=list)       # members of each row's group among the documents the filter accepts
+    total_groups: int = 0                                     # groups with a member: the exact distinct count of group_by over the filter
+    total: int = 0                                            # live documents the filter accepts (Listing.total of the same filter)
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+@dataclass
 class RangeRequest:        # SearchEngine.range_facets: the buckets of one numeric field over one filter
     filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
     field: str = ""                     # an int64 or a double column
@@ -241,6 +262,10 @@ class _RangeReq(C.Structure):
 
 class _ListReq(C.Structure):
     _fields_ = [("filter", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class _GroupListReq(C.Structure):     # infx_group_list_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
 
 
 class _Cfg(C.Structure):
@@ -514,6 +539,22 @@ class SearchEngine:
     def set_list_digit_bits(self, bits, session=None):
         """The width of a radix-select digit of list_documents on the session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
         self._check(self.L.infx_engine_set_list_digit_bits(session.h if session is not None else self._default_session(), int(bits)))
+
+    def list_groups(self, filter=None, group_by=None, order_by=None, ascending=True, offset=0, limit=20, session=None):
+        """A collapsed listing (not in the reference): over the documents list_documents(filter) lists and in its order (order_by, ascending; ties by ascending
+        internal index in both directions), one row per value of `group_by` — the group's head, its member that comes first in that order ("the cheapest
+        offer of every product", "the newest post of every author") — and of those rows the page [offset, offset + limit).  A group is one dictionary code
+        of group_by, exactly as field_stats(group_by=...) forms and names groups; any column of any kind and any number of values, group_by == order_by
+        included.  The answer equals list_documents over the filter's documents restricted to the heads, so pages never overlap or skip.  Returns
+        GroupListing(document_ids, values, group_values, group_sizes, total_groups, total, error): group_sizes the members of each row's group, total_groups
+        the exact distinct count of group_by over the filter, total = Listing.total.  1 <= limit <= 1024; offset >= total_groups is an empty page.  A
+        sequence of GroupListRequest as first argument -> a list of GroupListing, sixteen requests per device call; the pages of one listing in one call
+        share one pass over the corpus.  Exact and deterministic; nothing is cached but the session's pre-filter masks.  Needs a GPU."""
+        return _list_groups(self, session.h if session is not None else self._default_session(), filter, group_by, order_by, ascending, offset, limit)
+
+    def last_group_list_stats(self, session=None):
+        """(masks built, masks reused, head passes, histogram passes, kernel launches) of the session's last list_groups device call."""
+        return _u32_stats(self, "infx_engine_last_group_list_stats", session.h if session is not None else self._default_session(), 5)
 
     def range_facets(self, filter=None, field=None, edges=(), session=None):
         """Range facets (not in the reference): over the documents list_documents(filter) lists — not Deleted, their own fields accepted by `filter`; None:
@@ -851,6 +892,14 @@ class Session:
         """The width of a radix-select digit of list_documents on this session, 4 .. 11 (default 11): a tuning knob, the pages do not depend on it."""
         self.engine._check(self.engine.L.infx_engine_set_list_digit_bits(self.h, int(bits)))
 
+    def list_groups(self, filter=None, group_by=None, order_by=None, ascending=True, offset=0, limit=20):
+        """SearchEngine.list_groups on this session (its mask cache holds the filters' masks)."""
+        return _list_groups(self.engine, self.h, filter, group_by, order_by, ascending, offset, limit)
+
+    def last_group_list_stats(self):
+        """SearchEngine.last_group_list_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_group_list_stats", self.h, 5)
+
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets on this session (its mask cache holds the filters' masks)."""
         return _range_facets(self.engine, self.h, filter, field, edges)
@@ -1155,6 +1204,46 @@ def _list_documents(engine, sh, filter, order_by, ascending, offset, limit):
     return _per_request(engine, sh, "infx_engine_list_documents", "infx_engine_list_error", _ListReq,
                         [ListRequest(filter, order_by, ascending, offset, limit)] if single else list(filter), single, pack, read,
                         lambda _, msg: Listing([], [], 0, msg))
+
+
+def _list_groups(engine, sh, filter, group_by, order_by, ascending, offset, limit):
+    """infx_engine_list_groups on session handle sh: a GroupListing for one request (given by its parts), a list of them for a sequence of GroupListRequest."""
+    def pack(r):
+        off, lim = int(r.offset), int(r.limit)
+        # out of the C fields' range: passed as values the engine refuses for this request alone
+        return _GroupListReq(None if r.filter is None else r.filter.encode(), None if r.group_by is None else str(r.group_by).encode(),
+                             None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
+                             off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+    cols = {}
+
+    def texts(name, codes):
+        """the values of column `name` at codes, as list_documents fetches them"""
+        if name not in cols:
+            cols[name] = (_column_index(engine, name), {})
+        col, text = cols[name]
+        out = []
+        for c in codes:
+            c = int(c)
+            if c not in text:
+                vb = C.create_string_buffer(1024); engine.L.infx_engine_column_value(engine.h, col, c, vb, 1024)
+                text[c] = vb.value.decode()
+            out.append(text[c])
+        return out
+
+    def read(i, r):
+        groups = C.c_uint32(0); tot = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_group_list_totals(sh, i, C.byref(groups), C.byref(tot)))
+        keys = np.zeros(1024, np.int64); docs = np.zeros(1024, np.int32); codes = np.zeros(1024, np.uint32); gcodes = np.zeros(1024, np.uint32); sizes = np.zeros(1024, np.uint32)
+        m = engine.L.infx_engine_group_list_rows(sh, i, _p(keys, C.c_int64), _p(docs, C.c_int32), _p(codes, C.c_uint32), _p(gcodes, C.c_uint32), _p(sizes, C.c_uint32), 1024)
+        if m < 0:
+            engine._check(1)
+        vals = [] if r.order_by is None else texts(r.order_by, codes[:m])
+        return GroupListing([int(k) for k in keys[:m]], vals, texts(str(r.group_by), gcodes[:m]), [int(x) for x in sizes[:m]], int(groups.value), int(tot.value), None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_list_groups", "infx_engine_group_list_error", _GroupListReq,
+                        [GroupListRequest(filter, group_by, order_by, ascending, offset, limit)] if single else list(filter), single, pack, read,
+                        lambda _, msg: GroupListing(error=msg))
 
 
 def _range_facets(engine, sh, filter, field, edges):

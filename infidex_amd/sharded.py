@@ -717,6 +717,14 @@ class ShardedSearcher:
     def last_list_stats(self):
         return self.sessions[0].s.last_list_stats()
 
+    def list_groups(self, filter=None, group_by=None, order_by=None, ascending=True, offset=0, limit=20):
+        """SearchEngine.list_groups: like list_documents, every rank finds the heads and selects the page over the whole columns with the global Deleted
+        flags on its own GPU and gets the same answer — nothing is exchanged."""
+        return self.sessions[0].s.list_groups(filter, group_by, order_by, ascending, offset, limit)
+
+    def last_group_list_stats(self):
+        return self.sessions[0].s.last_group_list_stats()
+
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets: like list_documents, every rank counts over the whole columns with the global Deleted flags on its own GPU and gets
         the same answer — nothing is exchanged."""
