@@ -4,9 +4,7 @@
 //
 // The set is a byte per document, 0 = in the set, as in listing.hip.inc.  A SPEC is (mask, group column, order column, direction): its heads are found once,
 // whatever the pages asked of it.  A member's composite is (listing key << 32) | document (group_heads.h): the head of a group is its smallest composite.
-//   k_group_heads       ONE walk over the corpus, k_field_stats' shape: a thread takes 16 consecutive documents, their flags are one 16-byte load
-//                       (grp_mask16), a group of four without a member loads no codes (sts_codes16), the corpus's partial last group is read one by one, a
-//                       null mask loads no flag.  The head table holds 8 B per value of the group column, all ones = no member: a member takes the 64-bit
+//   k_group_heads       ONE walk over the corpus, k_field_stats' shape: a thread takes 16 consecutive documents (set_walk.h).  The head table holds 8 B per value of the group column, all ones = no member: a member takes the 64-bit
 //                       minimum of its composite into the entry of its group code, and only when the composite is below what a plain read of the entry
 //                       shows — the entry only ever decreases, so a stale read skips no update that matters.  Tables that fit lie in LDS per workgroup
 //                       (GRP_LDS_WORDS under 256 threads, else GRP_BIG_LDS_WORDS under one workgroup of 1024 per CU) and are merged once, one global
@@ -20,6 +18,7 @@
 //                       not zero at the end.
 // A minimum has no order and the adds are integer adds: any grid, stream and placement give the same bytes.  No atomic decides a position.
 #include "group_heads.h"
+#include "set_walk.h"
 #define GRP_THREADS 256
 #define GRP_BIG_THREADS 1024                // with GRP_BIG_LDS_WORDS: one workgroup per CU, the same sixteen waves
 #define GRP_LDS_WORDS STS_LDS_WORDS         // k_field_stats' two budgets
@@ -42,31 +41,6 @@ struct DevGroupSizes {
     uint32_t* sizes[INFX_MAX_PREFILTERS];               // per row (zeroed)
     uint32_t ldsOff[INFX_MAX_PREFILTERS], limit[INFX_MAX_PREFILTERS];      // request q's LDS words: [limit codes | limit counters] from ldsOff
 };
-// rng_mask16's bytes — byte j of m[q]: document d0 + 4q + j (d0 a multiple of 16) is outside the set — with the corpus's partial last group built from
-// values, not from conditional updates of m: every byte is read at an address clamped into the corpus (n > 0 here) and or-ed into its word.  Compiled
-// into these kernels, rng_mask16's own loop lost the flag of a word's first byte when the other three were clear (12 documents, flags 1111 1000 0000:
-// document 4 came out a member); tests/test_gpu_list_groups.py walks those shapes.
-__device__ __forceinline__ void grp_mask16(const uint8_t* __restrict__ mask, int32_t n, int64_t d0, uint32_t (&m)[4]) {
-    if (d0 + LST_GROUP <= (int64_t)n) {
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (mask) v = *(const uint4*)(mask + d0);
-        m[0] = v.x; m[1] = v.y; m[2] = v.z; m[3] = v.w;
-        return;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int64_t d = d0 + 4 * q + t;
-            const uint32_t flag = mask ? mask[d < (int64_t)n ? d : (int64_t)n - 1] : 0u;
-            const uint32_t out = (d >= (int64_t)n ? 1u : 0u) | (flag ? 1u : 0u);
-            w |= out << (8 * t);
-        }
-        m[q] = w;
-    }
-}
-__device__ __forceinline__ bool grp_member(const uint32_t (&m)[4], int j) { return !((m[j >> 2] >> (8 * (j & 3))) & 0xFFu); }
 // entry <- min(entry, comp), asked of the memory only when a plain read shows a larger entry (one aligned 8-byte load: it is never torn)
 __device__ __forceinline__ void grp_take_min(unsigned long long* entry, unsigned long long comp) {
     if (comp < __hip_atomic_load(entry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(entry, comp);
@@ -85,17 +59,15 @@ __global__ __launch_bounds__(GRP_BIG_THREADS) void k_group_heads(DevGroupSpec G,
     for (int64_t g = (int64_t)blockIdx.x * T + tid; g < groups; g += (int64_t)gridDim.x * T) {
         const int64_t d0 = g * LST_GROUP;
         uint32_t m[4], gc[LST_GROUP], oc[LST_GROUP];
-        grp_mask16(G.mask, n, d0, m);
-        if (!sts_codes16(G.gcodes, n, d0, m, gc)) continue;
-        if (G.ocodes) sts_codes16(G.ocodes, n, d0, m, oc);
+        sw_flags16(G.mask, n, d0, m);
+        if (!sw_codes16(G.gcodes, n, d0, m, gc)) continue;
+        sw_codes16(G.ocodes, n, d0, m, oc);
 #pragma unroll
         for (int j = 0; j < LST_GROUP; j++) {
-            if (!grp_member(m, j)) continue;
+            if (!sw_member(m, j)) continue;
             mine++;
             if (gc[j] >= G.gvals) continue;
-            uint32_t k = 1u;
-            if (G.ocodes) k = ls_mirror(1u + (oc[j] < G.onvals ? G.orank[oc[j]] : 0u), G.onvals, G.ascending != 0);      // lst_keys16's key
-            const unsigned long long comp = gh_composite(k, (uint32_t)(d0 + j));
+            const unsigned long long comp = gh_composite(ls_key(G.orank, oc[j], G.onvals, G.ascending != 0), (uint32_t)(d0 + j));
             if (G.inLds) grp_take_min(grp_tab + gc[j], comp); else grp_take_min(G.table + gc[j], comp);      // (two inlined copies: ds_min_u64 / global_atomic_umin_x2)
         }
     }
@@ -111,11 +83,11 @@ __global__ __launch_bounds__(GRP_THREADS) void k_group_heads_mask(DevGroupSpec G
     for (int64_t g = (int64_t)blockIdx.x * GRP_THREADS + threadIdx.x; g < groups; g += (int64_t)gridDim.x * GRP_THREADS) {
         const int64_t d0 = g * LST_GROUP;
         uint32_t m[4], gc[LST_GROUP], out[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
-        grp_mask16(G.mask, n, d0, m);
-        if (sts_codes16(G.gcodes, n, d0, m, gc)) {
+        sw_flags16(G.mask, n, d0, m);
+        if (sw_codes16(G.gcodes, n, d0, m, gc)) {
 #pragma unroll
             for (int j = 0; j < LST_GROUP; j++) {
-                if (!grp_member(m, j) || gc[j] >= G.gvals) continue;
+                if (!sw_member(m, j) || gc[j] >= G.gvals) continue;
                 if (gh_is_head(G.table[gc[j]], (uint32_t)(d0 + j))) out[j >> 2] &= ~(0xFFu << (8 * (j & 3)));
             }
         }
@@ -164,15 +136,15 @@ __global__ __launch_bounds__(GRP_BIG_THREADS) void k_group_sizes(DevGroupSizes Z
     for (int64_t g = (int64_t)blockIdx.x * T + tid; g < groups; g += (int64_t)gridDim.x * T) {
         const int64_t d0 = g * LST_GROUP;
         uint32_t m[4], gc[LST_GROUP];
-        grp_mask16(Z.mask, n, d0, m);
-        if (!sts_codes16(Z.gcodes, n, d0, m, gc)) continue;
+        sw_flags16(Z.mask, n, d0, m);
+        if (!sw_codes16(Z.gcodes, n, d0, m, gc)) continue;
         for (uint32_t q = 0; q < Z.nreq; q++) {
             const uint32_t r = rows[q];
             if (!r) continue;
             uint32_t* L = grp_lds + Z.ldsOff[q];
 #pragma unroll
             for (int j = 0; j < LST_GROUP; j++) {
-                if (!grp_member(m, j)) continue;
+                if (!sw_member(m, j)) continue;
                 const uint32_t pos = gh_find(L, r, gc[j]);
                 if (pos != GH_NONE) atomicAdd(L + Z.limit[q] + pos, 1u);
             }

@@ -3048,6 +3048,32 @@ static int32_t check_set_request(const infx_stream* s, const uint8_t* mask, int3
     if (mask) { const int slot = mask_slot_of(s, mask); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a %s's mask is not a mask slot of this stream, or was made for a smaller corpus", what); }
     return INFX_OK;
 }
+// a group column (field_stats, list_groups): uploaded and covering the corpus
+static int32_t check_group_column(const infx_index* ix, int32_t col, const char* what) {
+    if (col < 0 || col >= FILT_MAXCOL || !ix->colCodes[col]) return fail(INFX_EINVAL, "the %s's group column was not uploaded", what);
+    return columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, col);
+}
+// The start of a set call, its requests checked: the device, the staging of the call before consumed, the masks the call is missing built (infx_filter_masks:
+// one launch in front of the rest; *launches, where the entry point counts its launches, starts from it).  A call without requests ends here, synchronised.
+static int32_t set_call_begin(infx_stream* s, int32_t n, uint32_t nreq, uint32_t* launches) {
+    HIPCHK(enter_device(s->ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }
+    if (launches) *launches = builds;
+    if (!nreq && s->unsynced) SYNC();
+    return INFX_OK;
+}
+// Threads and grid of a set walk (set_walk.h: 16 documents per thread and step) whose workgroups keep ldsWords words of LDS and merge them once at the end:
+// STS_THREADS while the words fit STS_LDS_WORDS, else one workgroup of STS_BIG_THREADS per CU (the same sixteen waves); no more workgroups than are resident
+// (LDS of a CU: FFL_CU_LDS; 2048 threads), at least one.
+static int32_t merge_once_shape(const infx_index* ix, int32_t n, uint32_t ldsWords, int* threads, int* grid) {
+    int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device));
+    const int64_t groups = ((int64_t)n + SW_GROUP - 1) / SW_GROUP, T = ldsWords <= STS_LDS_WORDS ? STS_THREADS : STS_BIG_THREADS;
+    const int64_t perCu = std::min<int64_t>(2048 / T, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)ldsWords * 4, 1)));      // (at least one: ldsWords <= STS_BIG_LDS_WORDS)
+    *threads = (int)T; *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + T - 1) / T));
+    return INFX_OK;
+}
 // ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
 // The enqueue part of a listing call, shared by infx_list_ordered and infx_list_grouped.  Where the nreq requests of a call lie in the stream's listing
 // workspace W ([states | histograms] zeroed, [page composites] all ones, range counts and prefixes [nreq][2][3][nRanges]) and in its rows O
@@ -3140,12 +3166,8 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "listing"); if (rc_) return rc_; }
         D[i] = list_dev_req(ix, Q.mask, Q.col, Q.ascending != 0, Q.offset, Q.limit, Q.digit_bits);
     }
-    HIPCHK(enter_device(ix->cfg.device));
-    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
-    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
-    s->lastListLaunches = builds;
-    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastListLaunches); if (rc_) return rc_; }
+    if (!nreq) return INFX_OK;
     ListLayout L;
     { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
     for (uint32_t i = 0; i < nreq; i++) {
@@ -3181,11 +3203,9 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
             if (Q.thr[j] < Q.nan_ranks || Q.thr[j] > ix->colValues[Q.col] || (j && Q.thr[j] < Q.thr[j - 1])) return fail(INFX_EINVAL, "a range request's thresholds are non-decreasing, from nan_ranks to the column's number of values%s");
         thrWords += Q.nedges;
     }
-    HIPCHK(enter_device(ix->cfg.device));
-    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front
+    { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
     s->lastRngReqs = nreq;
-    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    if (!nreq) return INFX_OK;
     // requests that share a mask follow one another, and among them the ones that share a column: the walk keeps what the request before loaded
     uint32_t order[RB_MAX_REQS];
     for (uint32_t i = 0; i < nreq; i++) order[i] = i;
@@ -3257,16 +3277,13 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "field-stats request"); if (rc_) return rc_; }
         if (!ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the field-stats request's value table was not uploaded%s");
         if (Q.group_col >= 0) {
-            if (Q.group_col >= FILT_MAXCOL || !ix->colCodes[Q.group_col]) return fail(INFX_EINVAL, "the field-stats request's group column was not uploaded%s");
-            { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.group_col); if (rc_) return rc_; }
+            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-stats request"); if (rc_) return rc_; }
             if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
         }
     }
-    HIPCHK(enter_device(ix->cfg.device));
-    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front
+    { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
     s->lastStsReqs = nreq;
-    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    if (!nreq) return INFX_OK;
     // requests that share a mask follow one another, among them the ones that share a value column, among those the ones that share a group column
     uint32_t order[STS_MAX_REQS];
     for (uint32_t i = 0; i < nreq; i++) order[i] = i;
@@ -3285,10 +3302,10 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
     // 256 threads and k_facets_all's LDS budget; a call that leaves slots in global memory which the whole LDS of a CU would hold runs as one workgroup of 1024
     // threads per CU instead: the same sixteen waves per CU, and LDS atomics where every member would be global atomics (INFX_STATS_NO_BIG_LDS=1: never, for measurements)
     static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();
-    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal); int threads = STS_THREADS;
+    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
     if (inGlobal && !noBig) {
         uint32_t bigOff[STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
-        if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; threads = STS_BIG_THREADS; }
+        if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; }      // (more than STS_LDS_WORDS now: merge_once_shape takes 1024 threads)
     }
     GROW(s->dStsOut, s->capStsOut, (outWords + totalSlots) * 4);
     uint32_t* O = (uint32_t*)s->dStsOut;
@@ -3307,11 +3324,7 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
     HIPCHK(hipMemsetAsync(O + outWords, 0xFF, totalSlots * 4, s->st));
     s->unsynced = true;
     if (n > 0) {
-        const int64_t groups = ((int64_t)n + LST_GROUP - 1) / LST_GROUP;
-        // every workgroup merges its LDS slots once: no more workgroups than are resident (LDS of a CU: FFL_CU_LDS; 2048 threads)
-        int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device));
-        const int64_t perCu = std::min<int64_t>(2048 / threads, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)ldsWords * 4, 1)));
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + threads - 1) / threads));
+        int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
         HIPCHK(lds_limit((const void*)k_field_stats, ix->cfg.device, (size_t)ldsWords * 4));
         k_field_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
         HIPCHK(hipGetLastError());
@@ -3355,16 +3368,11 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
         const infx_group_list_req& Q = reqs[i];
         { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "grouped listing"); if (rc_) return rc_; }
-        if (Q.group_col < 0 || Q.group_col >= FILT_MAXCOL || !ix->colCodes[Q.group_col]) return fail(INFX_EINVAL, "the grouped listing's group column was not uploaded%s");
-        { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.group_col); if (rc_) return rc_; }
+        { int32_t rc_ = check_group_column(ix, Q.group_col, "grouped listing"); if (rc_) return rc_; }
         gvMax = std::max(gvMax, ix->colValues[Q.group_col]);
     }
-    HIPCHK(enter_device(ix->cfg.device));
-    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
-    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }      // the masks the call is missing (infx_filter_masks): one launch in front of the rest
-    s->lastGrpLaunches = builds;
-    if (!nreq) { if (s->unsynced) SYNC(); return INFX_OK; }
+    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastGrpLaunches); if (rc_) return rc_; }
+    if (!nreq) return INFX_OK;
     // requests of one spec — (mask, group column, order column, direction) — follow one another: they share the head pass, the heads mask and the size walk
     uint32_t order[INFX_MAX_PREFILTERS];
     for (uint32_t i = 0; i < nreq; i++) order[i] = i;
@@ -3392,15 +3400,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
     }
     ListLayout L;
     { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
-    int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device)); cus = std::max(cus, 1);
     const int64_t groups = (int64_t)groups16;
-    // a walk with `words` words of LDS per workgroup: 256 threads while they fit k_field_stats' budget, else one workgroup of 1024 per CU; never more workgroups than are
-    // resident (each merges its LDS once)
-    auto walk_shape = [&](uint32_t words, int* threads, int* grid) {
-        *threads = words <= GRP_LDS_WORDS ? GRP_THREADS : GRP_BIG_THREADS;
-        const int64_t perCu = std::min<int64_t>(2048 / *threads, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)words * 4, 1)));
-        *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)cus * std::max<int64_t>(perCu, 1), (groups + *threads - 1) / *threads));
-    };
     uint32_t spec = 0;
     for (uint32_t k0 = 0; k0 < nreq; spec++) {
         uint32_t k1 = k0 + 1;
@@ -3415,7 +3415,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             // the table and the workgroup's member counter (two words) in LDS while they fit one of the two budgets
             const uint32_t words = 2u * G.gvals + 2u;
             G.inLds = words <= GRP_BIG_LDS_WORDS ? 1u : 0u;
-            int threads, grid; walk_shape(G.inLds ? words : 2u, &threads, &grid);
+            int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, G.inLds ? words : 2u, &threads, &grid); if (rc_) return rc_; }
             const size_t lds = (size_t)(G.inLds ? words : 2u) * 4;
             HIPCHK(lds_limit((const void*)k_group_heads, ix->cfg.device, lds));
             k_group_heads<<<grid, threads, lds, s->st>>>(G, n);
@@ -3439,7 +3439,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
                 Z.cnt[q] = L.count(k); Z.sorted[q] = dSorted + (size_t)k * R; Z.perm[q] = dPerm + (size_t)k * R; Z.sizes[q] = dSizes + (size_t)k * R;
                 Z.ldsOff[q] = words; Z.limit[q] = D[k].limit; words += 2u * D[k].limit;
             }
-            int threads, grid; walk_shape(words, &threads, &grid);
+            int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, words, &threads, &grid); if (rc_) return rc_; }
             HIPCHK(lds_limit((const void*)k_group_sizes, ix->cfg.device, (size_t)words * 4));
             k_group_sizes<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
             HIPCHK(hipGetLastError());

@@ -6,8 +6,7 @@
 // is a set of documents and every step below may find it in any order.  The arithmetic is listing_select.h's, shared with the host model.
 //   k_list_hist    one pass of a radix select from the most significant digit, for the page's first and last position at once: per-workgroup LDS histograms
 //                  (2 x 2^digit_bits words) of the current digit over the documents under each target's prefix, merged with one global atomic per bin
-//                  that is not zero.  A thread takes 16 consecutive documents: their flags are one 16-byte load, and a group of four without a member
-//                  loads no codes.
+//                  that is not zero.  A thread takes 16 consecutive documents (set_walk.h).
 //   k_list_pick    one workgroup, between the passes, on the stream: scans each target's bins, extends its prefix by the digit that holds its position and
 //                  keeps the position inside that bin.  The first pass's histogram also gives the size of the set, hence the last position.  After the
 //                  last pass: the thresholds T_lo / T_hi and the tie indices (ls_page).
@@ -21,8 +20,9 @@
 //                  DocumentKey, document and the column's code per row.
 // Integer atomics add to histogram bins and range counters; no position is decided by one.
 #include "listing_select.h"
+#include "set_walk.h"
 #define LST_THREADS 256
-#define LST_GROUP 16                        // documents per thread and step
+#define LST_GROUP SW_GROUP                  // documents per thread and step
 #define LST_TILE (WAVE * LST_GROUP)         // a wave's step; ranges are runs of whole tiles
 #define LST_MAXRANGES 2048u
 struct DevListReq {
@@ -32,39 +32,13 @@ struct DevListReq {
 };
 struct DevListState { ls_target t[2]; uint32_t total, last, live, pad; ls_page page; uint32_t classTotal[3]; };      // zeroed before the first pass
 
-// keys of the 16 documents from d0 (a multiple of 16) into kk, 0 = not in the set.  Flags and codes of full groups arrive as 16-byte loads; the corpus's partial last
-// group is read one by one (neither the columns nor the Deleted flags are padded).
+// keys of the 16 documents from d0 (a multiple of 16) into kk, 0 = not in the set; false: no member among them.  The walk is set_walk.h's.
 __device__ __forceinline__ bool lst_keys16(const DevListReq& R, int32_t n, int64_t d0, uint32_t (&kk)[LST_GROUP]) {
-    uint32_t m[4] = {0, 0, 0, 0};           // byte j of m[q]: document d0 + 4q + j is outside the set
-    const bool full = d0 + LST_GROUP <= (int64_t)n;
-    if (full) { if (R.mask) { const uint4 v = *(const uint4*)(R.mask + d0); m[0] = v.x; m[1] = v.y; m[2] = v.z; m[3] = v.w; } }
-    else {
+    uint32_t m[4], cc[LST_GROUP];
+    sw_flags16(R.mask, n, d0, m);
+    const bool any = sw_codes16(R.codes, n, d0, m, cc);
 #pragma unroll
-        for (int j = 0; j < LST_GROUP; j++) if (d0 + j >= (int64_t)n || (R.mask && R.mask[d0 + j])) m[j >> 2] |= 1u << (8 * (j & 3));
-    }
-    bool any = false;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t w = m[q];
-        const bool some = ((w - 0x01010101u) & ~w & 0x80808080u) != 0;      // a zero byte: a member among the four
-        uint4 c = make_uint4(0, 0, 0, 0);
-        if (some && R.codes) {
-            const int64_t dq = d0 + 4 * q;
-            if (dq + 4 <= (int64_t)n) c = *(const uint4*)(R.codes + dq);
-            else { if (dq < n) c.x = R.codes[dq]; if (dq + 1 < n) c.y = R.codes[dq + 1]; if (dq + 2 < n) c.z = R.codes[dq + 2]; }
-        }
-        const uint32_t cj[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint32_t k = 0;
-            if (some && !((w >> (8 * j)) & 0xFFu)) {
-                k = 1u;
-                if (R.codes) k = ls_mirror(1u + (cj[j] < R.nvals ? R.rank[cj[j]] : 0u), R.nvals, R.ascending != 0);
-            }
-            kk[4 * q + j] = k;
-        }
-        any = any || some;
-    }
+    for (int j = 0; j < LST_GROUP; j++) kk[j] = sw_member(m, j) ? ls_key(R.rank, cc[j], R.nvals, R.ascending != 0) : 0u;
     return any;
 }
 __device__ __forceinline__ int32_t lst_range_start(uint32_t r, uint32_t tiles, uint32_t nRanges, int32_t n) {

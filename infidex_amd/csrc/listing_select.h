@@ -26,6 +26,11 @@ struct ls_page { uint32_t tLo, tHi, tieLo, tieHi, count; };
 
 // descending order is ascending order of the mirrored key; ties stay in document order in both
 LS_FN uint32_t ls_mirror(uint32_t k, uint32_t nvals, bool ascending) { return ascending ? k : (uint32_t)((uint64_t)nvals + 1u - k); }
+// the listing key of a member whose value has dictionary code `code`: 1 + rank[code] (0 for a code beyond the table), mirrored when descending; 1 without a
+// column (rank == nullptr: document order)
+LS_FN uint32_t ls_key(const uint32_t* rank, uint32_t code, uint32_t nvals, bool ascending) {
+    return rank ? ls_mirror(1u + (code < nvals ? rank[code] : 0u), nvals, ascending) : 1u;
+}
 // B: the bits of nvals + 1 (keys are 1 .. nvals)
 LS_FN uint32_t ls_key_bits(uint32_t nvals) { uint32_t b = 0; for (uint64_t v = (uint64_t)nvals + 1u; v; v >>= 1) b++; return b; }
 LS_FN uint32_t ls_passes(uint32_t nvals, uint32_t digitBits) { return (ls_key_bits(nvals) + digitBits - 1) / digitBits; }

@@ -4,8 +4,7 @@
 // The set is a byte per document, 0 = in the set: a pre-filter mask (k_filter_mask_multi) or the index's Deleted flags (nullptr: every document).  The work is
 // on sort ranks, never on values: the host turns a request's edges into thresholds over the column's dense sort rank (range_buckets.h) and a document of
 // rank r = rank[code] goes to the counter rb_slot names.  The arithmetic is range_buckets.h's, shared with the host model.
-//   k_range_counts   ONE launch for all requests of a call (at most RB_MAX_REQS).  The walk is lst_keys16's: a thread takes 16 consecutive documents, their
-//                    flags are one 16-byte load, a group of four without a member loads no codes, the corpus's partial last group is read one by one.
+//   k_range_counts   ONE launch for all requests of a call (at most RB_MAX_REQS).  A thread takes 16 consecutive documents (set_walk.h).
 //                    Inside the walk the requests run one after another (the loop and every reuse decision are uniform over the grid): a request that shares
 //                    its predecessor's mask keeps the group's flag bytes, one that shares mask and column keeps the ranks too — the host orders a call's
 //                    requests by (mask, column).  Per workgroup the thresholds and B + 3 counters of every request lie in LDS with the smallest and largest
@@ -13,6 +12,7 @@
 //                    that is not zero, the ranks with one atomicMin and one atomicMax per request and workgroup.
 // Integer atomics add to counters and take a minimum and a maximum; no position is decided by one: any grid and any stream give the same bytes.
 #include "range_buckets.h"
+#include "set_walk.h"
 #define RNG_THREADS 256
 #define RNG_OUT_STRIDE 260                  // words per request in the global counters (RB_MAX_SLOTS rounded up to four)
 #define RNG_MAXGRID 1024                    // four workgroups per CU, what sixteen requests of 256 buckets leave room for in LDS: every workgroup is resident and merges once
@@ -25,37 +25,12 @@ struct DevRangeReq {
 };
 struct DevRangeCall { uint32_t nreq, pad; DevRangeReq r[RB_MAX_REQS]; };
 
-// byte j of m[q]: document d0 + 4q + j (d0 a multiple of 16) is outside the set
-__device__ __forceinline__ void rng_mask16(const uint8_t* __restrict__ mask, int32_t n, int64_t d0, uint32_t (&m)[4]) {
-    m[0] = m[1] = m[2] = m[3] = 0;
-    if (d0 + LST_GROUP <= (int64_t)n) { if (mask) { const uint4 v = *(const uint4*)(mask + d0); m[0] = v.x; m[1] = v.y; m[2] = v.z; m[3] = v.w; } }
-    else {
-#pragma unroll
-        for (int j = 0; j < LST_GROUP; j++) if (d0 + j >= (int64_t)n || (mask && mask[d0 + j])) m[j >> 2] |= 1u << (8 * (j & 3));
-    }
-}
-// sort ranks of the 16 documents from d0 into rr, RB_NO_RANK = not in the set; false: no member among them
+// sort ranks of the 16 documents from d0 into rr (m: their flags, sw_flags16), RB_NO_RANK = not in the set; false: no member among them
 __device__ __forceinline__ bool rng_ranks16(const DevRangeReq& R, int32_t n, int64_t d0, const uint32_t (&m)[4], uint32_t (&rr)[LST_GROUP]) {
-    bool any = false;
+    uint32_t cc[LST_GROUP];
+    const bool any = sw_codes16(R.codes, n, d0, m, cc);
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t w = m[q];
-        const bool some = ((w - 0x01010101u) & ~w & 0x80808080u) != 0;      // a zero byte: a member among the four
-        uint4 c = make_uint4(0, 0, 0, 0);
-        if (some) {
-            const int64_t dq = d0 + 4 * q;
-            if (dq + 4 <= (int64_t)n) c = *(const uint4*)(R.codes + dq);
-            else { if (dq < n) c.x = R.codes[dq]; if (dq + 1 < n) c.y = R.codes[dq + 1]; if (dq + 2 < n) c.z = R.codes[dq + 2]; }
-        }
-        const uint32_t cj[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint32_t r = RB_NO_RANK;
-            if (some && !((w >> (8 * j)) & 0xFFu)) r = cj[j] < R.nvals ? R.rank[cj[j]] : 0u;
-            rr[4 * q + j] = r;
-        }
-        any = any || some;
-    }
+    for (int j = 0; j < LST_GROUP; j++) rr[j] = sw_member(m, j) ? (cc[j] < R.nvals ? R.rank[cc[j]] : 0u) : RB_NO_RANK;
     return any;
 }
 
@@ -77,7 +52,7 @@ __global__ __launch_bounds__(RNG_THREADS) void k_range_counts(DevRangeCall P, in
         bool any = false;
         for (uint32_t q = 0; q < P.nreq; q++) {
             const DevRangeReq& R = P.r[q];
-            if (!(R.reuse & 1u)) rng_mask16(R.mask, n, d0, m);
+            if (!(R.reuse & 1u)) sw_flags16(R.mask, n, d0, m);
             if (!(R.reuse & 2u)) any = rng_ranks16(R, n, d0, m, rr);
             if (!any) continue;
             const uint32_t ne = R.nedges, nanRanks = R.nanRanks;

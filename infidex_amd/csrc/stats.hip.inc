@@ -5,9 +5,7 @@
 // exact_sum.h turns the bytes into a class (finite, NaN, +inf, -inf), a sign and L unsigned 32-bit limbs of |v| / 2^scale by integer shifts.  A SLOT —
 // one per value of the group column, one in all without it — is STS_HEAD + 2 L words: four counters by class, the largest and the smallest non-NaN rank,
 // L signed 64-bit limb sums.  Every accumulation is an integer atomic (add, min, max): no floating-point instruction, no order, the same bytes on any grid.
-//   k_field_stats    ONE launch for all requests of a call (at most STS_MAX_REQS).  The walk is k_range_counts': a thread takes 16 consecutive documents,
-//                    their flags are one 16-byte load (rng_mask16), a group of four without a member loads no codes, the corpus's partial last group is
-//                    read one by one, a null mask loads no flag.  Inside the walk the requests run one after another (uniform over the grid): one that
+//   k_field_stats    ONE launch for all requests of a call (at most STS_MAX_REQS).  A thread takes 16 consecutive documents (set_walk.h).  Inside the walk the requests run one after another (uniform over the grid): one that
 //                    shares its predecessor's mask keeps the flag bytes, one that shares mask and value column keeps the decoded values — the host orders
 //                    a call's requests by (mask, value column, group column).
 //                    The host places a request's slots in LDS while they fit (requests in ascending size, STS_LDS_WORDS per workgroup of STS_THREADS;
@@ -18,6 +16,7 @@
 //                    shuffles, and ONE lane updates the slot per wave and step.  With one, every member is a handful of LDS (or global) atomics on the
 //                    slot of its group code.
 #include "exact_sum.h"
+#include "set_walk.h"
 #define STS_THREADS 256
 #define STS_BIG_THREADS 1024                // with STS_BIG_LDS_WORDS: one workgroup per CU, the same sixteen waves
 #define STS_MAX_REQS 16
@@ -38,31 +37,13 @@ struct DevStatsReq {
 struct DevStatsCall { uint32_t nreq, pad; DevStatsReq r[STS_MAX_REQS]; };
 __host__ __device__ __forceinline__ uint32_t sts_stride(uint32_t nlimbs) { return STS_HEAD + 2u * nlimbs; }
 
-// codes of the 16 documents from d0 in column col; a group of four without a member (m: rng_mask16's bytes) is not loaded
-__device__ __forceinline__ bool sts_codes16(const uint32_t* __restrict__ col, int32_t n, int64_t d0, const uint32_t (&m)[4], uint32_t (&cc)[LST_GROUP]) {
-    bool any = false;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t w = m[q];
-        const bool some = ((w - 0x01010101u) & ~w & 0x80808080u) != 0;      // a zero byte: a member among the four
-        uint4 c = make_uint4(0, 0, 0, 0);
-        if (some) {
-            const int64_t dq = d0 + 4 * q;
-            if (dq + 4 <= (int64_t)n) c = *(const uint4*)(col + dq);
-            else { if (dq < n) c.x = col[dq]; if (dq + 1 < n) c.y = col[dq + 1]; if (dq + 2 < n) c.z = col[dq + 2]; }
-        }
-        cc[4 * q] = c.x; cc[4 * q + 1] = c.y; cc[4 * q + 2] = c.z; cc[4 * q + 3] = c.w;
-        any = any || some;
-    }
-    return any;
-}
-// raw values and sort ranks of the 16 documents from d0: vr = RB_NO_RANK marks a document outside the set; false: no member among them
+// raw values and sort ranks of the 16 documents from d0 (m: their flags, sw_flags16): vr = RB_NO_RANK marks a document outside the set; false: no member among them
 __device__ __forceinline__ bool sts_values16(const DevStatsReq& R, int32_t n, int64_t d0, const uint32_t (&m)[4], uint64_t (&vb)[LST_GROUP], uint32_t (&vr)[LST_GROUP]) {
     uint32_t cc[LST_GROUP];
-    const bool any = sts_codes16(R.codes, n, d0, m, cc);
+    const bool any = sw_codes16(R.codes, n, d0, m, cc);
 #pragma unroll
     for (int j = 0; j < LST_GROUP; j++) {
-        const bool in = any && !((m[j >> 2] >> (8 * (j & 3))) & 0xFFu) && cc[j] < R.nvals;
+        const bool in = any && sw_member(m, j) && cc[j] < R.nvals;
         vb[j] = in ? R.bits[cc[j]] : 0ull;
         vr[j] = in ? R.rank[cc[j]] : RB_NO_RANK;
     }
@@ -100,7 +81,7 @@ __global__ __launch_bounds__(STS_BIG_THREADS) void k_field_stats(DevStatsCall P,
         bool any = false;
         for (uint32_t q = 0; q < P.nreq; q++) {
             const DevStatsReq& R = P.r[q];
-            if (!(R.reuse & 1u)) rng_mask16(R.mask, n, d0, m);
+            if (!(R.reuse & 1u)) sw_flags16(R.mask, n, d0, m);
             if (!(R.reuse & 2u)) any = sts_values16(R, n, d0, m, vb, vr);
             const uint32_t nl = R.nlimbs, W = sts_stride(nl);
             const bool inLds = R.ldsOff != STS_GLOBAL;
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(STS_BIG_THREADS) void k_field_stats(DevStatsCall P,
             }
             if (!any) continue;
             uint32_t gc[LST_GROUP];
-            sts_codes16(R.gcodes, n, d0, m, gc);
+            sw_codes16(R.gcodes, n, d0, m, gc);
 #pragma unroll
             for (int j = 0; j < LST_GROUP; j++) {
                 if (vr[j] == RB_NO_RANK || gc[j] >= R.gvals) continue;
