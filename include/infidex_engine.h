@@ -458,7 +458,7 @@ int32_t infx_engine_last_range_stats(infx_session* s, uint32_t* masks_built, uin
  * same figures for every distinct value of group_by that has a member: ALL such groups (no cut at 100), members descending, then the group column's facet
  * tie order ascending.  The groups' count and nan add up to the whole's; on an int64 column so do the sums.
  * The sums do not depend on the order of the additions: the device adds integers only (DESIGN.md "field_stats"), so every run, session, stream and rank
- * returns the same bytes.  No variance, percentiles, distinct counts or top-N cut; nothing is cached but the masks.
+ * returns the same bytes.  No variance, distinct counts or top-N cut (percentiles: infx_engine_field_quantiles); nothing is cached but the masks.
  * A request is refused ON ITS OWN (out_status[i], message from infx_engine_field_stats_error, the others answered): a syntax error, a missing or unknown
  * field, an unknown group_by, a string field, a group_by of more than 4096 values, or a double column whose finite values span more than 128 binary digits
  * (it cannot be summed exactly) INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests
@@ -479,6 +479,45 @@ int32_t infx_engine_field_stats_groups(infx_session* s, uint32_t which, int32_t*
 int32_t infx_engine_field_stats_total(infx_session* s, uint32_t which, uint32_t* total);
 int32_t infx_engine_field_stats_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_field_stats_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
+/* ---- field_quantiles: exact medians and percentiles of a numeric field over a filter, whole and per group (not in the reference: the semantics below are
+ * this project's) ----
+ * Request i asks, over the SET of infx_engine_field_stats (what infx_engine_list_total and infx_engine_field_stats_total count), for nq quantiles q[0 .. nq)
+ * of `field`, an int64 or a double column — 1 <= nq <= INFX_QUANT_MAX (16), every q[t] a number in [0, 1], in any order, duplicates allowed:
+ *   nan        members whose value is a NaN; they are in no quantile                    count   the other members; count + nan is the size of the set
+ *   value t    the value at 0-based position floor((count - 1) * q[t]) of the non-NaN members in ascending order of infx_engine_set_sort's comparison —
+ *              the product ONE IEEE double multiplication: the element numpy.quantile(method="lower") picks.  No interpolation: always a value some
+ *              member has, returned as min / max are (through the rank's lowest code; v_i for kind 1, v_d for kind 2); +-inf are ordinary values.  Valid
+ *              when count > 0.  q = 0 is infx_engine_field_stats' min, q = 1 its max; infx_engine_list_documents at order_by = field, ascending,
+ *              offset = nan + position, limit = 1 lists a document of that value (NaNs hold the lowest ranks).
+ * and, with `group_by` (infx_engine_field_stats' rule: any column of at most 4096 distinct values, `field` itself included), the same figures for every
+ * distinct value of group_by that has a member, each at the positions of its OWN count, in infx_engine_field_stats' order of groups.
+ * Exact and deterministic: the device selects on sort ranks with integer adds (DESIGN.md "field_quantiles"), so every run, session, stream and rank returns
+ * the same bytes.  Nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_field_quantiles_error, the others answered): a syntax error, a missing, unknown
+ * or string field, an unknown group_by or one of more than 4096 values, nq = 0 or q = NULL, nq > 16, a q[t] outside [0, 1] or a NaN INFX_EINVAL, MATCHES
+ * INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests (INFX_ECAPACITY).  INFX_EHIP on an engine without a
+ * GPU (no CPU fallback), every refusal but the filter's already in out_status; a call that failed as a whole leaves nothing for the readers.  The masks are
+ * the session's pre-filter masks; every pass of the select is one k_quant_hist and one k_quant_pick launch for all requests of the call.  Works on a
+ * sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_field_quantiles_whole the whole's figures (returning the request's status);
+ * infx_engine_field_quantiles_groups copies up to cap groups — codes[g] the group's code in column *group_col (-1 without group_by), figures[g] its
+ * figures — and returns the number of groups (-1 for a refused request or bad arguments); infx_engine_field_quantiles_total the size of the set (returning
+ * the request's status); infx_engine_field_quantiles_error the refusal's message (its length; -1 out of range).
+ * infx_engine_last_field_quantiles_stats: masks built and reused, histogram passes (k_quant_hist launches) and kernel launches of the last call.
+ * infx_engine_last_field_quantiles_placement: the digit width the last call chose (the cap under which every request's width lies) and how many of its
+ * (request, pass) pairs had their bins in LDS / in global memory (infx_last_field_quantiles_info).
+ * infx_engine_set_quantile_digit_bits: the width of the select's radix digit on this session, 4 .. 11, or 0 (the default): the engine chooses per call.  It
+ * changes the number of passes, never an answer. */
+typedef struct infx_quantile_request { const char* filter; const char* field; const char* group_by; const double* q; uint32_t nq; } infx_quantile_request;
+typedef struct infx_quantile_figures { uint32_t count; uint32_t nan; int32_t kind; uint32_t nq; int64_t v_i[16]; double v_d[16]; } infx_quantile_figures;
+int32_t infx_engine_field_quantiles(infx_session* s, uint32_t nreq, const infx_quantile_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_field_quantiles_whole(infx_session* s, uint32_t which, infx_quantile_figures* out);
+int32_t infx_engine_field_quantiles_groups(infx_session* s, uint32_t which, int32_t* group_col, uint32_t* codes, infx_quantile_figures* figures, int32_t cap);
+int32_t infx_engine_field_quantiles_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_field_quantiles_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_field_quantiles_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches);
+int32_t infx_engine_last_field_quantiles_placement(infx_session* s, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows);
+int32_t infx_engine_set_quantile_digit_bits(infx_session* s, int32_t bits);
 /* ---- list_groups: one row per value of a field, in the order of a field, by page (not in the reference: the semantics below are this project's) -----------
  * Request i lists, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
  * filter = NULL: every live document; duplicate keys are documents of their own — and in its ORDER (k(d), d) for `order_by` and `ascending` (ties by ascending

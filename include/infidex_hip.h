@@ -474,6 +474,32 @@ typedef struct infx_stats_slot { uint32_t finite; uint32_t nan; uint32_t pinf; u
 int32_t infx_upload_column_values(infx_index* idx, uint32_t col, uint32_t num_values, const uint64_t* bits, int32_t kind, int32_t scale_exp, uint32_t nlimbs);
 int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out /* sum of the requests' slots */);
 int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches);
+/* Quantiles of a document set over a numeric column, whole and per value of a second column (not in the reference: the aggregate is this project's;
+ * DESIGN.md "field_quantiles").
+ * Request i: the SET is infx_field_stats': the documents whose byte in `mask` is 0 — a mask slot of this stream — or, mask = NULL, every document that is
+ * not Deleted.  The work is on the dense sort rank of uploaded column `col` (infx_upload_sort_rank), never on values; nan_ranks = 1 when the column's
+ * value of rank 0 is a NaN, else 0: a member whose rank is below it is counted as a NaN and is in no quantile.  `group_col` is any uploaded column of at
+ * most INFX_STATS_MAX_GROUPS distinct values, or -1.  The request has one SLOT per distinct value of group_col (in code order) and, BEHIND them, one for the
+ * whole set — that one alone without group_col; the slots of request i follow those of request i - 1 in slots_out: count = the slot's members that are
+ * not NaNs, nan = the others.  ranks_out holds nq words per slot, in the same order: word t is the sort rank at 0-based position
+ * floor((count - 1) * q[t]) of the slot's non-NaN members in ascending rank order — the product one IEEE double multiplication — or 0xFFFFFFFF when count
+ * is 0.  1 <= nq <= INFX_QUANT_MAX, every q[t] in [0, 1] (no NaN), in any order, duplicates allowed.
+ * No document is sorted: a radix select over the keys 1 + rank, most significant digit first, for ALL targets (slot, t) of ALL requests at once.  A pass is
+ * ONE k_quant_hist launch — a walk over the corpus that takes the requests in the order (mask, col, group_col), so the ones that share a mask read its bytes
+ * once and the ones that share a column too read its codes and ranks once — and ONE k_quant_pick launch, on the stream.  digit_bits: the width of a radix digit, 4 .. 11, or
+ * 0: the call chooses — the widest at which the bins of one pass of the whole call take at most 64 MiB, per request narrowed to the least width of the same
+ * number of passes, ceil(bits(num_values + 1) / width); a width given here is lowered to that bound too.  The width changes the number of passes, never the
+ * answer.  Bins lie in LDS while they fit (as infx_field_stats' slots; a request's groups' bins and the whole set's are placed apart), else in global memory.  Integer atomics only, none decides a position:
+ * the same bytes from any stream, grid, width and placement.  At most 16 requests (INFX_ECAPACITY).  A mask build staged with infx_filter_masks is
+ * enqueued first, as ONE launch; nothing waits for the host between the kernels.  Works on a sharded index.  Synchronous.
+ * infx_last_field_quantiles_info, of the stream's last call: requests, k_quant_hist launches (= passes), kernel launches (the mask build included), the
+ * call's digit width, and how many (request, pass) pairs had their bins — the groups', without group_col the whole set's — in LDS / in global memory. */
+#define INFX_QUANT_MAX 16
+typedef struct infx_quant_req { const uint8_t* mask; int32_t col; int32_t group_col; uint32_t nq; uint32_t digit_bits; uint32_t nan_ranks; uint32_t reserved; double q[INFX_QUANT_MAX]; } infx_quant_req;
+typedef struct infx_quant_slot { uint32_t count; uint32_t nan; } infx_quant_slot;
+int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req* reqs, infx_quant_slot* slots_out /* sum of the requests' slots */,
+                             uint32_t* ranks_out /* sum of the requests' slots x nq */);
+int32_t infx_last_field_quantiles_info(infx_stream* s, uint32_t* requests, uint32_t* hist_passes, uint32_t* launches, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows);
 /* A page of the HEADS of a document set's groups, in the order of a column, with the groups' sizes (not in the reference: the collapsed listing is this
  * project's; DESIGN.md "list_groups").
  * Request i: the SET, the KEY and the ORDER (key, global internal id) are infx_list_ordered's, over `mask` (a mask slot of this stream, or NULL: every

@@ -103,6 +103,8 @@ struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vecto
 // One request of the session's last infx_engine_field_stats: its status and message, the whole's figures, the group column (-1: none) and the groups that have a
 // member, in the contract's order
 struct StatsAnswer : Answer { infx_stats_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_stats_figures> groups; };
+// One request of the session's last infx_engine_field_quantiles: likewise, with the figures of infx_quantile_figures
+struct QuantAnswer : Answer { infx_quantile_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_quantile_figures> groups; };
 // One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
 // row what a ListAnswer holds, the group's code and its size
 struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
@@ -126,6 +128,8 @@ struct infx_session {
     std::vector<RangeAnswer> rng; MaskUse rngMasks; uint32_t rngLaunches = 0;
     // infx_engine_field_stats: likewise, with the k_field_stats launches of that call
     std::vector<StatsAnswer> sts; MaskUse stsMasks; uint32_t stsLaunches = 0;
+    // infx_engine_field_quantiles: likewise, with the histogram passes and kernel launches of that call; the digit width (0: chosen per call)
+    std::vector<QuantAnswer> qnt; MaskUse qntMasks; uint32_t qntPasses = 0, qntLaunches = 0, qntPlace[3] = {0, 0, 0}; int32_t qntDigitBits = 0;      // qntPlace: the call's digit width, (request, pass) pairs with bins in LDS / in global memory
     // infx_engine_list_groups: likewise, with the head passes, histogram passes and kernel launches of that call (the digit width is lstDigitBits)
     std::vector<GroupListAnswer> grp; MaskUse grpMasks; uint32_t grpHeads = 0, grpPasses = 0, grpLaunches = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
@@ -3577,6 +3581,139 @@ int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out
 int32_t infx_engine_last_field_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->stsMasks.built}, {masks_reused, S->stsMasks.reused}, {launches, S->stsLaunches}});
+}
+
+// ---- field_quantiles: the values at the quantiles' positions of a numeric field over the documents a filter accepts, whole and per group (not in the reference) ----
+// Per request: the field to its column (int64 or double) and the column to its sort rank, group_by to any column of at most 4096 values, the filter through
+// the filter cache and its mask through the session's mask cache, as infx_engine_field_stats.  infx_field_quantiles then selects every (slot, quantile) of the
+// call on sort ranks; the engine maps each answered rank to a value through the rank's lowest code, as stats_figures does for min / max.
+// What is wrong with request Q before anything of it is looked at on the device, as the request's status, the text in *why; INFX_OK with the columns
+// (gcol -1: no group_by).  Caller holds e->filterMu.
+static int32_t quant_request_check(infx_engine* e, const infx_quantile_request& Q, int32_t* col, int32_t* gcol, std::string* why) {
+    auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
+    *gcol = -1;
+    if (!Q.field) return bad("field_quantiles needs a field");
+    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("field_quantiles: no field named '") + Q.field + "'");
+    if (column_kind(e->columns[*col]) == 3) return bad(std::string("field_quantiles: field '") + Q.field + "' is a string column; quantiles need an int64 or a double column");
+    if (Q.group_by) {
+        if ((*gcol = column_named(e, Q.group_by)) < 0) return bad(std::string("field_quantiles: no group_by field named '") + Q.group_by + "'");
+        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string("field_quantiles: group_by field '") + Q.group_by + "' has more than 4096 distinct values");
+    }
+    if (!Q.nq || !Q.q) return bad("field_quantiles needs at least one quantile");
+    if (Q.nq > INFX_QUANT_MAX) return bad("field_quantiles: more than 16 quantiles in one request");
+    for (uint32_t t = 0; t < Q.nq; t++) if (!(Q.q[t] >= 0.0 && Q.q[t] <= 1.0)) return bad("field_quantiles: every quantile is a number in [0, 1]");
+    return INFX_OK;
+}
+// The figures of one slot: its counts and the values of its nq answered ranks through the rank's lowest code
+static infx_quantile_figures quant_figures(const infx_quant_slot& S, const uint32_t* ranks, uint32_t nq, const filt::Column& C, const infx_engine::RangeIndex& X) {
+    infx_quantile_figures F = {};
+    F.count = S.count; F.nan = S.nan; F.kind = C.dict.empty() || C.dict[0].kind == 1 ? 1 : 2; F.nq = nq;
+    for (uint32_t t = 0; t < nq && S.count; t++) {
+        if (ranks[t] >= X.codeOfRank.size()) continue;
+        const filt::Boxed& v = C.dict[X.codeOfRank[ranks[t]]];
+        if (F.kind == 1) F.v_i[t] = v.i; else F.v_d[t] = v.d;
+    }
+    return F;
+}
+int32_t infx_engine_field_quantiles(infx_session* S, uint32_t nreq, const infx_quantile_request* reqs, int32_t* out_status) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    S->qnt.clear(); S->qntMasks = MaskUse(); S->qntPasses = S->qntLaunches = 0; S->qntPlace[0] = S->qntPlace[1] = S->qntPlace[2] = 0;
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) field_quantiles requests in one call");
+    S->qnt.assign(nreq, QuantAnswer());
+    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->qnt[i].status = rc; S->qnt[i].err = msg; if (out_status) out_status[i] = rc; };
+    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            std::string why;
+            if (out_status) out_status[i] = INFX_OK;
+            const int32_t rc = quant_request_check(e, reqs[i], &col[i], &gcol[i], &why);
+            if (rc) refuse(i, rc, why);
+        }
+    }
+    { int32_t rc = need_indexed_device(S, "field_quantiles"); if (rc) { S->qnt.clear(); return rc; } }
+    MaskCall mc(S, nreq, &S->qntMasks);
+    std::vector<uint32_t> nanRanks(nreq, 0);
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nreq; i++) {
+            if (S->qnt[i].status) continue;
+            const infx_engine::RangeIndex* X = nullptr;
+            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }
+            nanRanks[i] = X->nanRanks;
+            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
+        }
+    }
+    { int32_t rc = mc.acquire(); if (rc) { S->qnt.clear(); return rc; } }
+    std::vector<infx_quant_req> dr; std::vector<uint32_t> who; std::vector<size_t> atSlot, atRank; size_t nslots = 0, nranks = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        if (S->qnt[i].status) continue;
+        infx_quant_req R{};
+        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.nq = reqs[i].nq; R.digit_bits = (uint32_t)S->qntDigitBits; R.nan_ranks = nanRanks[i];
+        std::copy(reqs[i].q, reqs[i].q + reqs[i].nq, R.q);
+        dr.push_back(R); who.push_back(i); atSlot.push_back(nslots); atRank.push_back(nranks);
+        const size_t sl = gcol[i] >= 0 ? e->columns[gcol[i]].dict.size() + 1 : 1;
+        nslots += sl; nranks += sl * reqs[i].nq;
+    }
+    const size_t m = dr.size();
+    std::vector<infx_quant_slot> slots(std::max<size_t>(nslots, 1)); std::vector<uint32_t> ranks(std::max<size_t>(nranks, 1));
+    int32_t rc = infx_field_quantiles(S->stream, (uint32_t)m, dr.data(), slots.data(), ranks.data());
+    if (rc) { S->qnt.clear(); return mc.failed(rc); }
+    mc.done();
+    infx_last_field_quantiles_info(S->stream, nullptr, &S->qntPasses, &S->qntLaunches, &S->qntPlace[0], &S->qntPlace[1], &S->qntPlace[2]);
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    for (size_t j = 0; j < m; j++) {
+        QuantAnswer& A = S->qnt[who[j]];
+        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
+        const infx_quant_slot* sl = slots.data() + atSlot[j]; const uint32_t* rk = ranks.data() + atRank[j]; const uint32_t nq = dr[j].nq;
+        A.groupCol = dr[j].group_col;
+        const size_t ng = A.groupCol >= 0 ? e->columns[A.groupCol].dict.size() : 0;      // (the whole set's slot lies behind the groups')
+        A.whole = quant_figures(sl[ng], rk + ng * nq, nq, C, X);
+        if (A.groupCol >= 0) {
+            const filt::Column& G = e->columns[A.groupCol];
+            std::vector<uint32_t> ord;
+            for (uint32_t g = 0; g < ng; g++) if (sl[g].count + sl[g].nan) ord.push_back(g);
+            auto members = [&](uint32_t g) { return (uint64_t)sl[g].count + sl[g].nan; };
+            std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return members(a) != members(b) ? members(a) > members(b) : G.rank[a] < G.rank[b]; });
+            for (uint32_t g : ord) { A.codes.push_back(g); A.groups.push_back(quant_figures(sl[g], rk + (size_t)g * nq, nq, C, X)); }
+        }
+        A.total = A.whole.count + A.whole.nan;
+    }
+    return INFX_OK;
+}
+// request `which` of the session's last infx_engine_field_quantiles: the whole's figures (returns the request's status; INFX_EINVAL without such an answer)
+int32_t infx_engine_field_quantiles_whole(infx_session* S, uint32_t which, infx_quantile_figures* out) {
+    const QuantAnswer* A = answer_at(S ? &S->qnt : nullptr, which);
+    if (!A || !out) return efail(INFX_EINVAL, "no such request in the session's last field_quantiles call");
+    *out = A->whole;
+    return A->status;
+}
+// its groups, in the contract's order: up to cap codes (of column *group_col, -1 without group_by) and figures; returns the number of groups, -1 on error (also for a refused request)
+int32_t infx_engine_field_quantiles_groups(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, infx_quantile_figures* figures, int32_t cap) {
+    const QuantAnswer* A = answer_at(S ? &S->qnt : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!codes || !figures))) return -1;
+    const size_t c = std::min<size_t>(A->groups.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(figures, A->groups.data(), c * sizeof(infx_quantile_figures)); }
+    if (group_col) *group_col = A->groupCol;
+    return (int32_t)A->groups.size();
+}
+int32_t infx_engine_field_quantiles_total(infx_session* S, uint32_t which, uint32_t* total) {
+    return answer_total(answer_at(S ? &S->qnt : nullptr, which), total, "no such request in the session's last field_quantiles call");
+}
+int32_t infx_engine_field_quantiles_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->qnt : nullptr, which), out, cap); }
+int32_t infx_engine_last_field_quantiles_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->qntMasks.built}, {masks_reused, S->qntMasks.reused}, {hist_passes, S->qntPasses}, {launches, S->qntLaunches}});
+}
+int32_t infx_engine_last_field_quantiles_placement(infx_session* S, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{digit_bits, S->qntPlace[0]}, {lds_rows, S->qntPlace[1]}, {global_rows, S->qntPlace[2]}});
+}
+int32_t infx_engine_set_quantile_digit_bits(infx_session* S, int32_t bits) {
+    if (!S || (bits != 0 && (bits < 4 || bits > 11))) return efail(INFX_EINVAL, "the digit width of field_quantiles is 4 .. 11 bits, or 0: chosen per call");
+    S->qntDigitBits = bits;
+    return INFX_OK;
 }
 
 // ---- list_groups: one row per value of a field — the group's first document in the order of a field — by page (not in the reference) ---------------------

@@ -266,6 +266,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
 #include "groups.hip.inc"
+#include "quantiles.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 
@@ -369,6 +370,8 @@ struct infx_stream {
     uint32_t lastRngReqs = 0, lastRngLaunches = 0;             // requests and k_range_counts launches of the last infx_range_counts
     void* dStsOut = nullptr; size_t capStsOut = 0; std::vector<uint32_t> hStsRaw;      // infx_field_stats: the requests' slots and smallest ranks; their host copy
     uint32_t lastStsReqs = 0, lastStsLaunches = 0;             // requests and k_field_stats launches of the last infx_field_stats
+    void *dQntWs = nullptr, *dQntOut = nullptr; size_t capQntWs = 0, capQntOut = 0; std::vector<uint32_t> hQntRaw;      // infx_field_quantiles: quantiles, targets and one pass's rows; counts and ranks; their host copy
+    uint32_t lastQntInfo[6] = {0, 0, 0, 0, 0, 0};              // of the last infx_field_quantiles: requests, histogram passes, launches, digit width, request-passes with rows in LDS / in global memory
     void* dGrpWs = nullptr; size_t capGrpWs = 0;               // infx_list_grouped: a spec's head table and heads mask; per request the page's sorted codes, rows, group codes and sizes
     uint32_t lastGrpHeads = 0, lastGrpPasses = 0, lastGrpLaunches = 0;      // head passes, histogram passes and kernel launches of the last infx_list_grouped
     hipStream_t st = nullptr;
@@ -1309,7 +1312,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -3256,7 +3259,7 @@ int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* laun
 // Where the slots of a call's requests live: in ascending size (slots x words) while they fit `budget` words of LDS per workgroup, the others in global
 // memory.  words[k] = request k's slots x stride; ldsOff[k] = its first LDS word or STS_GLOBAL; *inGlobal the requests left out.  Returns the LDS words in use.
 static uint32_t sts_place(uint32_t nreq, const uint32_t* words, uint32_t budget, uint32_t* ldsOff, uint32_t* inGlobal) {
-    uint32_t by[STS_MAX_REQS], used = 0; *inGlobal = 0;
+    uint32_t by[2 * STS_MAX_REQS], used = 0; *inGlobal = 0;      // (nreq <= 2 x STS_MAX_REQS: infx_field_quantiles places two sets of rows per request)
     for (uint32_t k = 0; k < nreq; k++) by[k] = k;
     std::stable_sort(by, by + nreq, [&](uint32_t a, uint32_t b) { return words[a] < words[b]; });
     for (uint32_t j = 0; j < nreq; j++) {
@@ -3351,6 +3354,135 @@ int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t*
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (requests) *requests = s->lastStsReqs;
     if (launches) *launches = s->lastStsLaunches;
+    return INFX_OK;
+}
+// ---- field_quantiles: the sort ranks at the quantiles' positions of a numeric column over a document set, whole and per group (quantiles.hip.inc) ----
+// The digit width of request Q under the call's cap: its own digit_bits (never above the cap), else the narrowest width that takes no more passes than the cap
+static uint32_t qnt_width(const infx_quant_req& Q, uint32_t nvals, uint32_t cap) { return Q.digit_bits ? std::min(Q.digit_bits, cap) : qs_narrow(nvals, cap); }
+int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req* reqs, infx_quant_slot* slots_out, uint32_t* ranks_out) {
+    if (!s || (nreq && (!reqs || !slots_out || !ranks_out))) return fail(INFX_EINVAL, "bad field-quantiles arguments%s");
+    std::fill(s->lastQntInfo, s->lastQntInfo + 6, 0u);
+    if (nreq > QNT_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-quantiles requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_quant_req& Q = reqs[i];
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "field-quantiles request"); if (rc_) return rc_; }
+        if (Q.group_col >= 0) {
+            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-quantiles request"); if (rc_) return rc_; }
+            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
+        }
+        if (Q.nq < 1 || Q.nq > QS_MAX_Q) return fail(INFX_EINVAL, "a field-quantiles request has 1 .. INFX_QUANT_MAX (16) quantiles%s");
+        for (uint32_t t = 0; t < Q.nq; t++) if (!(Q.q[t] >= 0.0 && Q.q[t] <= 1.0)) return fail(INFX_EINVAL, "a quantile is a number in [0, 1]%s");
+        if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
+        if (Q.digit_bits && (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS)) return fail(INFX_EINVAL, "a field-quantiles request's digit width is 0 (chosen by the call) or 4 .. 11 bits%s");
+    }
+    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastQntInfo[2]); if (rc_) return rc_; }
+    s->lastQntInfo[0] = nreq;
+    if (!nreq) return INFX_OK;
+    // requests that share a mask follow one another, among them the ones that share a value column, among those the ones that share a group column
+    uint32_t order[QNT_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
+    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
+        const infx_quant_req &A = reqs[a], &B = reqs[b];
+        if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
+        return A.col != B.col ? A.col < B.col : A.group_col < B.group_col; });
+    uint32_t slots[QNT_MAX_REQS], width[QNT_MAX_REQS], passes[QNT_MAX_REQS]; size_t slot0[QNT_MAX_REQS], tgt0[QNT_MAX_REQS], q0[QNT_MAX_REQS], totalSlots = 0, totalTgts = 0, totalQ = 0;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_quant_req& Q = reqs[order[k]];
+        slots[k] = Q.group_col >= 0 ? ix->colValues[Q.group_col] + 1u : 1u;
+        slot0[k] = totalSlots; tgt0[k] = totalTgts; q0[k] = totalQ;
+        totalSlots += slots[k]; totalTgts += (size_t)slots[k] * Q.nq; totalQ += Q.nq;
+    }
+    // The digit width: the widest (fewest passes) at which the rows of one pass of the whole call stay inside QNT_SCRATCH_WORDS.  At 4 bits they always do:
+    // 16 requests x 4097 slots x 16 quantiles x 16 bins.
+    uint32_t cap = LS_MAX_DIGIT_BITS; size_t tabWords = 0;
+    for (;; cap--) {
+        size_t first = 0, later = 0;
+        for (uint32_t k = 0; k < nreq; k++) {
+            const infx_quant_req& Q = reqs[order[k]];
+            width[k] = qnt_width(Q, ix->colValues[Q.col], cap); passes[k] = ls_passes(ix->colValues[Q.col], width[k]);
+            first += (size_t)slots[k] * qs_slot_words(0, Q.nq, width[k]);
+            if (passes[k] > 1) later += (size_t)slots[k] * qs_slot_words(1, Q.nq, width[k]);
+        }
+        tabWords = std::max(first, later);
+        if (tabWords <= QNT_SCRATCH_WORDS || cap == LS_MIN_DIGIT_BITS) break;
+    }
+    s->lastQntInfo[3] = cap;
+    const size_t oTgt = (totalQ * 8 + 63) & ~(size_t)63, oTab = (oTgt + totalTgts * sizeof(ls_target) + 63) & ~(size_t)63;
+    GROW(s->dQntWs, s->capQntWs, oTab + tabWords * 4);
+    GROW(s->dQntOut, s->capQntOut, (2 * totalSlots + totalTgts) * 4);
+    char* W = (char*)s->dQntWs; uint32_t* O = (uint32_t*)s->dQntOut;
+    {
+        std::vector<double> qs; qs.reserve(totalQ);
+        for (uint32_t k = 0; k < nreq; k++) qs.insert(qs.end(), reqs[order[k]].q, reqs[order[k]].q + reqs[order[k]].nq);
+        UP(W, qs.data(), totalQ * 8);
+    }
+    // without a pass (an empty corpus) every slot reads count 0 and every target no rank
+    HIPCHK(hipMemsetAsync(O, 0, 2 * totalSlots * 4, s->st));
+    HIPCHK(hipMemsetAsync(O + 2 * totalSlots, 0xFF, totalTgts * 4, s->st));
+    s->unsynced = true;
+    const uint32_t maxPasses = *std::max_element(passes, passes + nreq);
+    for (uint32_t p = 0; n > 0 && p < maxPasses; p++) {
+        // the requests that still have a pass to go, in the call's order: what one keeps of the one before it holds among them
+        // words / ldsOff: per request its groups' rows (none without a group column), then the whole set's
+        DevQuantCall P{}; uint32_t words[2 * QNT_MAX_REQS], ldsOff[2 * QNT_MAX_REQS]; size_t used = 0; int32_t before = -1;
+        for (uint32_t k = 0; k < nreq; k++) {
+            if (passes[k] <= p) continue;
+            const infx_quant_req& Q = reqs[order[k]];
+            DevQuantReq& D = P.r[P.nreq];
+            D.mask = Q.mask ? Q.mask : ix->d.deleted;
+            D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col];
+            D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = slots[k] - 1u; D.slots = slots[k]; D.nq = Q.nq;
+            D.q = (const double*)W + q0[k]; D.tgt = (ls_target*)(W + oTgt) + tgt0[k]; D.tab = (uint32_t*)(W + oTab) + used;
+            D.slotOut = O + 2 * slot0[k]; D.rankOut = O + 2 * totalSlots + tgt0[k];
+            D.digitBits = width[k]; D.passes = passes[k]; D.nanRanks = Q.nan_ranks; D.slot0 = P.slots;
+            if (before >= 0) { const infx_quant_req& B = reqs[order[before]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+            words[2 * P.nreq + 1] = qs_slot_words(p, Q.nq, width[k]); words[2 * P.nreq] = D.gvals * words[2 * P.nreq + 1];
+            used += (size_t)slots[k] * words[2 * P.nreq + 1]; P.slots += slots[k]; P.nreq++; before = (int32_t)k;
+        }
+        // the rows' places: k_field_stats' rule and its two launch shapes
+        uint32_t inGlobal = 0, ldsWords = sts_place(2 * P.nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
+        if (inGlobal) {
+            uint32_t bigOff[2 * QNT_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(2 * P.nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
+            if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + 2 * P.nreq, ldsOff); ldsWords = bigWords; }
+        }
+        for (uint32_t k = 0; k < P.nreq; k++) {
+            P.r[k].ldsOff = ldsOff[2 * k]; P.r[k].ldsOffWhole = ldsOff[2 * k + 1];
+            // counted by where the rows that make the request large lie: its groups', the whole set's without a group column
+            const bool inLds = (P.r[k].gvals ? P.r[k].ldsOff : P.r[k].ldsOffWhole) != STS_GLOBAL;
+            s->lastQntInfo[inLds ? 4 : 5]++;
+        }
+        HIPCHK(hipMemsetAsync(W + oTab, 0, used * 4, s->st));
+        int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
+        HIPCHK(lds_limit((const void*)k_quant_hist, ix->cfg.device, (size_t)ldsWords * 4));
+        k_quant_hist<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n, p);
+        const uint32_t perBlock = QNT_PICK_THREADS / WAVE;
+        k_quant_pick<<<(P.slots + perBlock - 1) / perBlock, QNT_PICK_THREADS, 0, s->st>>>(P, p);
+        HIPCHK(hipGetLastError());
+        s->lastQntInfo[1]++; s->lastQntInfo[2] += 2;
+    }
+    s->hQntRaw.assign(2 * totalSlots + totalTgts, 0u);
+    DOWN(s->hQntRaw.data(), O, (2 * totalSlots + totalTgts) * 4);
+    SYNC();
+    // the caller's order: request i's slots and ranks follow request i - 1's
+    size_t atSlot[QNT_MAX_REQS], atTgt[QNT_MAX_REQS], ns = 0, nt = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const uint32_t sl = reqs[i].group_col >= 0 ? ix->colValues[reqs[i].group_col] + 1u : 1u;
+        atSlot[i] = ns; atTgt[i] = nt; ns += sl; nt += (size_t)sl * reqs[i].nq;
+    }
+    for (uint32_t k = 0; k < nreq; k++) {
+        const uint32_t i = order[k];
+        for (uint32_t g = 0; g < slots[k]; g++) { slots_out[atSlot[i] + g].count = s->hQntRaw[2 * (slot0[k] + g)]; slots_out[atSlot[i] + g].nan = s->hQntRaw[2 * (slot0[k] + g) + 1]; }
+        std::copy(s->hQntRaw.begin() + 2 * totalSlots + tgt0[k], s->hQntRaw.begin() + 2 * totalSlots + tgt0[k] + (size_t)slots[k] * reqs[i].nq, ranks_out + atTgt[i]);
+    }
+    return INFX_OK;
+}
+int32_t infx_last_field_quantiles_info(infx_stream* s, uint32_t* requests, uint32_t* hist_passes, uint32_t* launches, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    uint32_t* out[6] = {requests, hist_passes, launches, digit_bits, lds_rows, global_rows};
+    for (int i = 0; i < 6; i++) if (out[i]) *out[i] = s->lastQntInfo[i];
     return INFX_OK;
 }
 // ---- list_groups: a page of the heads of a document set's groups, in the order of a column, with the groups' sizes (groups.hip.inc) ----

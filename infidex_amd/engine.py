@@ -247,6 +247,42 @@ class FieldStats:          # SearchEngine.field_stats: one per request
     error: Optional[str] = None                               # why this request alone was refused; None when it was answered
 
 
+@dataclass
+class QuantileRequest:     # SearchEngine.field_quantiles: the quantiles of one numeric field over one filter, whole and per group
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    field: Optional[str] = None         # an int64 or a double column
+    q: tuple = (0.5,)                   # 1 .. 16 numbers in [0, 1], in any order, duplicates allowed
+    group_by: Optional[str] = None      # any column of at most 4096 distinct values; None: the whole only
+
+
+@dataclass
+class GroupQuantiles:      # SearchEngine.field_quantiles: one group of one request
+    value: str = ""                                           # the group's value of the group_by field as text (GroupStats.value)
+    count: int = 0                                            # members whose value is not a NaN
+    nan: int = 0                                              # members whose value is a NaN: in no quantile
+    values: list = _dc_field(default_factory=list)            # values[i]: the group's value at position floor((count - 1) * q[i]); None when count == 0
+
+
+@dataclass
+class FieldQuantiles:      # SearchEngine.field_quantiles: one per request
+    q: tuple = ()                                             # the request's quantiles, as floats
+    values: list = _dc_field(default_factory=list)            # values[i]: the value at 0-based position floor((count - 1) * q[i]) of the non-NaN members in
+    #                                                           ascending order (int for an int column, float for a double one); None when count == 0
+    count: int = 0                                            # members whose value is not a NaN
+    nan: int = 0                                              # members whose value is a NaN (double columns): in no quantile
+    total: int = 0                                            # live documents the filter accepts: count + nan (Listing.total, FieldStats.total)
+    groups: list = _dc_field(default_factory=list)            # [GroupQuantiles] of every group with a member, in FieldStats.groups' order; [] without group_by
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+class _QuantReq(C.Structure):          # infx_quantile_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("group_by", C.c_char_p), ("q", C.POINTER(C.c_double)), ("nq", C.c_uint32)]
+
+
+class _QuantFigures(C.Structure):      # infx_quantile_figures (include/infidex_engine.h)
+    _fields_ = [("count", C.c_uint32), ("nan", C.c_uint32), ("kind", C.c_int32), ("nq", C.c_uint32), ("v_i", C.c_int64 * 16), ("v_d", C.c_double * 16)]
+
+
 class _StatsReq(C.Structure):          # infx_stats_request (include/infidex_engine.h)
     _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("group_by", C.c_char_p)]
 
@@ -564,8 +600,8 @@ class SearchEngine:
         min, max, error); always nan + below + sum(counts) + above == total.  2 .. 257 edges, strictly increasing as Query.sort_by compares values (-0.0,
         0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  Sums and means: field_stats.  A sequence of RangeRequest as first argument -> a list of
         RangeFacets, sixteen requests per device call, all counted in ONE pass over the corpus (requests of one filter read its mask once); a request
-        with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums, means or percentiles (a percentile is
-        list_documents(order_by=field, offset=p * total, limit=1))."""
+        with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums or means (field_stats) and no
+        percentiles (field_quantiles)."""
         return _range_facets(self, session.h if session is not None else self._default_session(), filter, field, edges)
 
     def last_range_stats(self, session=None):
@@ -587,6 +623,33 @@ class SearchEngine:
     def last_field_stats_stats(self, session=None):
         """(masks built, masks reused, k_field_stats launches) of the session's last field_stats device call."""
         return _u32_stats(self, "infx_engine_last_field_stats_stats", session.h if session is not None else self._default_session(), 3)
+
+    def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None, session=None):
+        """Exact medians and percentiles (not in the reference): over the documents field_stats(filter) counts — not Deleted, their own fields accepted by
+        `filter`; None: every live document; duplicate keys are documents of their own — for every q[i] (1 .. 16 numbers in [0, 1], any order, duplicates
+        allowed) the value at 0-based position floor((count - 1) * q[i]) of the non-NaN values of the int64 or double column `field` in ascending order: what
+        numpy.quantile(method="lower") picks, never interpolated, always a value some member has (int for an int column, float for a double one; None when
+        count == 0).  q = 0 is FieldStats.min, q = 1 FieldStats.max, and list_documents(filter, order_by=field, offset=nan + position, limit=1) lists a
+        document of that value.  With `group_by` (any column of at most 4096 distinct values, `field` itself included) the same for every group that has a
+        member, each at the positions of its own count, in FieldStats.groups' order.  Returns FieldQuantiles(q, values, count, nan, total, groups, error).
+        The device selects on sort ranks with integer adds — all quantiles of all groups of all requests in the same few passes — so every run returns the
+        same bytes.  A sequence of QuantileRequest as first argument -> a list of FieldQuantiles, sixteen requests per device call; a request with a syntax
+        error, MATCHES, a missing, unknown or string field, an unknown or too large group_by, or no, more than 16 or out-of-range quantiles gets `error`
+        set, alone.  Needs a GPU."""
+        return _field_quantiles(self, session.h if session is not None else self._default_session(), filter, field, q, group_by)
+
+    def last_field_quantiles_stats(self, session=None):
+        """(masks built, masks reused, histogram passes, kernel launches) of the session's last field_quantiles device call."""
+        return _u32_stats(self, "infx_engine_last_field_quantiles_stats", session.h if session is not None else self._default_session(), 4)
+
+    def last_field_quantiles_placement(self, session=None):
+        """(digit width, (request, pass) pairs with bins in LDS, pairs with bins in global memory) of the session's last field_quantiles device call."""
+        return _u32_stats(self, "infx_engine_last_field_quantiles_placement", session.h if session is not None else self._default_session(), 3)
+
+    def set_quantile_digit_bits(self, bits, session=None):
+        """The width of a radix-select digit of field_quantiles on the session, 4 .. 11, or 0 (the default): chosen per call.  A tuning knob: it changes the
+        number of passes, never an answer."""
+        self._check(self.L.infx_engine_set_quantile_digit_bits(session.h if session is not None else self._default_session(), int(bits)))
 
     def _default_session(self):
         h = C.c_void_p(); self._check(self.L.infx_engine_default_session(self.h, C.byref(h))); return h
@@ -915,6 +978,22 @@ class Session:
     def last_field_stats_stats(self):
         """SearchEngine.last_field_stats_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_field_stats_stats", self.h, 3)
+
+    def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None):
+        """SearchEngine.field_quantiles on this session (its mask cache holds the filters' masks)."""
+        return _field_quantiles(self.engine, self.h, filter, field, q, group_by)
+
+    def last_field_quantiles_stats(self):
+        """SearchEngine.last_field_quantiles_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_field_quantiles_stats", self.h, 4)
+
+    def last_field_quantiles_placement(self):
+        """SearchEngine.last_field_quantiles_placement of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_field_quantiles_placement", self.h, 3)
+
+    def set_quantile_digit_bits(self, bits):
+        """SearchEngine.set_quantile_digit_bits of this session."""
+        self.engine._check(self.engine.L.infx_engine_set_quantile_digit_bits(self.h, int(bits)))
 
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
@@ -1322,6 +1401,58 @@ def _field_stats(engine, sh, filter, field, group_by):
     return _per_request(engine, sh, "infx_engine_field_stats", "infx_engine_field_stats_error", _StatsReq,
                         [StatsRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
                         lambda r, msg: FieldStats(error=msg))
+
+
+def _quantile_tuple(q):
+    """The quantiles of a request as a tuple of floats: a number alone is one quantile; what float() refuses becomes a NaN, which the engine refuses."""
+    out = []
+    for x in (q if isinstance(q, (tuple, list, np.ndarray)) else (q,)):
+        try:
+            out.append(float(x))
+        except (TypeError, ValueError, OverflowError):
+            out.append(float("nan"))
+    return tuple(out)
+
+
+def _quantile_figures(f):
+    """(count, nan, values) of an infx_quantile_figures: None for every quantile of a slot without a non-NaN member."""
+    nq, count = int(f.nq), int(f.count)
+    vals = [None] * nq if not count else ([int(f.v_i[t]) for t in range(nq)] if f.kind == 1 else [float(f.v_d[t]) for t in range(nq)])
+    return count, int(f.nan), vals
+
+
+def _field_quantiles(engine, sh, filter, field, q, group_by):
+    """infx_engine_field_quantiles on session handle sh: a FieldQuantiles for one request (given by its parts), a list of them for a sequence of QuantileRequest."""
+    keep = []                                            # the quantile arrays live until the calls have returned
+
+    def pack(r):
+        qs = np.asarray(_quantile_tuple(r.q), np.float64); keep.append(qs)
+        text = [None if x is None else str(x).encode() for x in (r.filter, r.field, r.group_by)]
+        return _QuantReq(text[0], text[1], text[2], _p(qs, C.c_double) if len(qs) else None, min(len(qs), 0xFFFFFFFF))
+
+    def read(i, r):
+        tot = C.c_uint32(0); whole = _QuantFigures()
+        engine._check(engine.L.infx_engine_field_quantiles_total(sh, i, C.byref(tot)))
+        engine._check(engine.L.infx_engine_field_quantiles_whole(sh, i, C.byref(whole)))
+        col = C.c_int32(-1)
+        m = engine.L.infx_engine_field_quantiles_groups(sh, i, C.byref(col), None, None, 0)
+        if m < 0:
+            engine._check(1)
+        groups = []
+        if m > 0:
+            codes = np.zeros(m, np.uint32); figs = (_QuantFigures * m)()
+            engine.L.infx_engine_field_quantiles_groups(sh, i, C.byref(col), _p(codes, C.c_uint32), figs, m)
+            vb = C.create_string_buffer(1024)
+            for code, f in zip(codes.tolist(), figs):
+                engine.L.infx_engine_column_value(engine.h, col.value, code, vb, 1024)
+                groups.append(GroupQuantiles(vb.value.decode(), *_quantile_figures(f)))
+        count, nan, vals = _quantile_figures(whole)
+        return FieldQuantiles(_quantile_tuple(r.q), vals, count, nan, int(tot.value), groups, None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_field_quantiles", "infx_engine_field_quantiles_error", _QuantReq,
+                        [QuantileRequest(filter, field, q, group_by)] if single else list(filter), single, pack, read,
+                        lambda r, msg: FieldQuantiles(q=_quantile_tuple(r.q), error=msg))
 
 
 def _attach_pre_filter_facets(engine, sh, qs, results):

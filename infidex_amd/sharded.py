@@ -741,6 +741,14 @@ class ShardedSearcher:
     def last_field_stats_stats(self):
         return self.sessions[0].s.last_field_stats_stats()
 
+    def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None):
+        """SearchEngine.field_quantiles: like field_stats, every rank selects over the whole columns with the global Deleted flags on its own GPU and gets the
+        same answer — no collective."""
+        return self.sessions[0].s.field_quantiles(filter, field, q, group_by)
+
+    def last_field_quantiles_stats(self):
+        return self.sessions[0].s.last_field_quantiles_stats()
+
     def last_timings(self):
         return self.last.s.last_timings()
 
