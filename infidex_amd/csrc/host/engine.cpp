@@ -12,6 +12,7 @@
 #include "infdx2_verify.h"
 #include "infs.h"
 #include "hostcache.h"
+#include <array>
 #include <mutex>
 #include <condition_variable>
 #include "../../../include/infidex_engine.h"
@@ -100,15 +101,16 @@ struct ListAnswer : Answer { std::vector<int64_t> keys; std::vector<int32_t> doc
 // One request of the session's last infx_engine_range_facets: its status and message, its counters, the extremes as values (kind 0: none, 1 int64, 2 double)
 struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vector<uint32_t> counts;
                      int32_t kind = 0; int64_t loI = 0, hiI = 0; double loD = 0, hiD = 0; };
-// One request of the session's last infx_engine_field_stats: its status and message, the whole's figures, the group column (-1: none) and the groups that have a
-// member, in the contract's order
-struct StatsAnswer : Answer { infx_stats_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_stats_figures> groups; };
-// One request of the session's last infx_engine_field_quantiles: likewise, with the figures of infx_quantile_figures
-struct QuantAnswer : Answer { infx_quantile_figures whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<infx_quantile_figures> groups; };
+// One request of the session's last infx_engine_field_stats (F: infx_stats_figures) or infx_engine_field_quantiles (infx_quantile_figures): its status and
+// message, the whole's figures, the group column (-1: none) and the groups that have a member, in the contract's order
+template <class F> struct FiguresAnswer : Answer { F whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<F> groups; };
+typedef FiguresAnswer<infx_stats_figures> StatsAnswer;
+typedef FiguresAnswer<infx_quantile_figures> QuantAnswer;
 // One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
 // row what a ListAnswer holds, the group's code and its size
 struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
+template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskUse masks; };
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
@@ -122,16 +124,16 @@ struct infx_session {
     // infx_engine_facets_filtered: the facet columns of the session's last call, one answer per expression of it (its entry of the engine's cache, or why it
     // was refused), and what the call cost: expressions counted on the device, expressions taken from the cache, k_facets_filtered launches
     std::vector<uint32_t> ffCols; std::vector<FfAnswer> ff; uint32_t ffCounted = 0, ffCached = 0, ffLaunches = 0;
-    // infx_engine_list_documents: one answer per request of the session's last call, what the call cost (histogram passes, kernel launches), the digit width
-    std::vector<ListAnswer> lst; MaskUse lstMasks; uint32_t lstPasses = 0, lstLaunches = 0; int32_t lstDigitBits = 11;
-    // infx_engine_range_facets: one answer per request of the session's last call; masks built and reused and k_range_counts launches of that call
-    std::vector<RangeAnswer> rng; MaskUse rngMasks; uint32_t rngLaunches = 0;
-    // infx_engine_field_stats: likewise, with the k_field_stats launches of that call
-    std::vector<StatsAnswer> sts; MaskUse stsMasks; uint32_t stsLaunches = 0;
-    // infx_engine_field_quantiles: likewise, with the histogram passes and kernel launches of that call; the digit width (0: chosen per call)
-    std::vector<QuantAnswer> qnt; MaskUse qntMasks; uint32_t qntPasses = 0, qntLaunches = 0, qntPlace[3] = {0, 0, 0}; int32_t qntDigitBits = 0;      // qntPlace: the call's digit width, (request, pass) pairs with bins in LDS / in global memory
-    // infx_engine_list_groups: likewise, with the head passes, histogram passes and kernel launches of that call (the digit width is lstDigitBits)
-    std::vector<GroupListAnswer> grp; MaskUse grpMasks; uint32_t grpHeads = 0, grpPasses = 0, grpLaunches = 0;
+    // What the session keeps of its last call of each per-request kind (set_call): one answer per request, the masks built / reused, what else the call cost
+    // infx_engine_list_documents: histogram passes, kernel launches; lstDigitBits: the digit width
+    struct Lst : LastCall<ListAnswer> { uint32_t passes = 0, launches = 0; } lst; int32_t lstDigitBits = 11;
+    struct Rng : LastCall<RangeAnswer> { uint32_t launches = 0; } rng;      // infx_engine_range_facets: k_range_counts launches
+    struct Sts : LastCall<StatsAnswer> { uint32_t launches = 0; } sts;      // infx_engine_field_stats: k_field_stats launches
+    // infx_engine_field_quantiles: histogram passes, kernel launches; place: the call's digit width, (request, pass) pairs with bins in LDS / in global memory;
+    // qntDigitBits: the digit width asked for (0: chosen per call)
+    struct Qnt : LastCall<QuantAnswer> { uint32_t passes = 0, launches = 0, place[3] = {0, 0, 0}; } qnt; int32_t qntDigitBits = 0;
+    // infx_engine_list_groups: head passes, histogram passes, kernel launches (the digit width is lstDigitBits)
+    struct Grp : LastCall<GroupListAnswer> { uint32_t heads = 0, passes = 0, launches = 0; } grp;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -2637,20 +2639,22 @@ int32_t infx_engine_set_boosts(infx_session* S, uint32_t n, const char* const* e
     { std::lock_guard<std::mutex> lk(e->filterMu); set_session_pins(S, S->swPinBoosts, keep); }
     return INFX_OK;
 }
-// the column of a SortBy field (0xFFFFFFFF: no such field); the first use of a column builds and uploads its sort rank.  Caller holds e->filterMu.
-static int32_t sort_column(infx_engine* e, const char* field, uint32_t* out) {
-    const uint32_t col = (uint32_t)column_named(e, field);
-    if (col != 0xFFFFFFFFu) {
-        if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
-        if (!e->sortRanked[col]) {
-            std::vector<uint32_t> rank; filt::sort_rank(e->columns[col], rank);
-            int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
-            if (rc) { g_eerr = infx_last_error(); return rc; }
-            e->sortRanked[col] = 1;
-        }
-    }
-    *out = col;
+// Column col's sort rank is on the device: built and uploaded on its first use, which leaves the rank in *built where the caller asks for it.
+// Caller holds e->filterMu.
+static int32_t sort_rank_on_device(infx_engine* e, uint32_t col, std::vector<uint32_t>* built = nullptr) {
+    if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
+    if (e->sortRanked[col]) return INFX_OK;
+    std::vector<uint32_t> rank; filt::sort_rank(e->columns[col], rank);
+    int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    e->sortRanked[col] = 1;
+    if (built) built->swap(rank);
     return INFX_OK;
+}
+// the column of a SortBy field (0xFFFFFFFF: no such field), its sort rank on the device.  Caller holds e->filterMu.
+static int32_t sort_column(infx_engine* e, const char* field, uint32_t* out) {
+    *out = (uint32_t)column_named(e, field);
+    return *out != 0xFFFFFFFFu ? sort_rank_on_device(e, *out) : INFX_OK;
 }
 int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascending) {
     if (!S) return efail(INFX_EINVAL, "null session");
@@ -3191,7 +3195,7 @@ int32_t infx_engine_last_facets_filtered_stats(infx_session* S, uint32_t* counte
     return put_stats({{counted, S->ffCounted}, {cached, S->ffCached}, {launches, S->ffLaunches}});
 }
 
-// ---- requests over the documents a filter accepts: infx_engine_list_documents, _range_facets, _field_stats and _list_groups -----------------------------
+// ---- requests over the documents a filter accepts: infx_engine_list_documents, _range_facets, _field_stats, _field_quantiles and _list_groups -----------
 // Each takes up to INFX_MAX_PREFILTERS requests, answer each on its own (a refusal is the request's: its status in out_status[i], its message with the answer)
 // and leave the answers on the session for the readers.  A call that fails as a whole leaves no answers behind — the readers refuse — while the statuses
 // already written to out_status stay.  The filters and their masks are a MaskCall's.
@@ -3201,79 +3205,150 @@ static int32_t need_indexed_device(const infx_session* S, const char* what) {
     if (!S->e->indexed) return efail(INFX_EINVAL, std::string(what) + " before index_documents");
     return INFX_OK;
 }
+extern "C++" {
+// One such call while it runs, as its kind's steps see it: `last` is where the session keeps the kind's answers, who[j] the request behind the j-th live one
+template <class K> struct SetCall {
+    infx_session* S; K& last; int32_t* out; MaskCall mc; std::vector<uint32_t> who;
+    void refuse(uint32_t i, int32_t rc, const std::string& msg) { last.ans[i].status = rc; last.ans[i].err = msg; if (out) out[i] = rc; }
+    // request i's filter (null: none) through the filter cache; false: refused.  Caller holds filterMu
+    bool filter(uint32_t i, const char* expr) { const int32_t rc = expr ? mc.intern(i, expr) : INFX_OK; if (rc) refuse(i, rc, g_eerr); return !rc; }
+    template <class Fn> void each(bool locked, Fn fn) {      // fn(*this, i) for every request not refused so far, under filterMu if `locked`
+        std::unique_lock<std::mutex> lk(S->e->filterMu, std::defer_lock);
+        if (locked) lk.lock();
+        for (uint32_t i = 0; i < last.ans.size(); i++) if (!last.ans[i].status) fn(*this, i);
+    }
+    int32_t fail(int32_t rc, bool staged) { last.ans.clear(); return staged ? mc.failed(rc) : rc; }      // the call fails as a whole (staged: a build may be)
+};
+// The frame of every such call.  `kind` is what the session keeps of the kind's last call (reset here), `name` the call's name and `plural` its requests in
+// the messages.  The kind's own steps: check(F, i) looks at what of request i needs no device (under filterMu where lockedCheck), resolve(F, i) at its columns
+// and its filter under filterMu — both refuse on the request's behalf and see only requests not refused so far; run(F) packs the live requests F.who, makes
+// the device call and returns its status; unpack(F) fetches the device's counters and fills the answers of F.who.
+template <class K, class Q, class Check, class Resolve, class Run, class Unpack>
+static int32_t set_call(infx_session* S, K infx_session::*kind, const char* name, const char* plural, bool lockedCheck, uint32_t nreq, const Q* reqs,
+                        int32_t* out_status, Check check, Resolve resolve, Run run, Unpack unpack) {
+    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
+    S->*kind = K();
+    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, std::string("more than INFX_MAX_PREFILTERS (16) ") + plural + " in one call");
+    SetCall<K> F{S, S->*kind, out_status, MaskCall(S, nreq, &(S->*kind).masks), {}};
+    F.last.ans.assign(nreq, typename K::answer());
+    if (out_status) std::fill(out_status, out_status + nreq, (int32_t)INFX_OK);
+    F.each(lockedCheck, check);
+    { const int32_t rc = need_indexed_device(S, name); if (rc) return F.fail(rc, false); }
+    F.each(true, resolve);
+    { const int32_t rc = F.mc.acquire(); if (rc) return F.fail(rc, false); }
+    for (uint32_t i = 0; i < nreq; i++) if (!F.last.ans[i].status) F.who.push_back(i);
+    { const int32_t rc = run(F); if (rc) return F.fail(rc, true); }
+    F.mc.done();
+    unpack(F);
+    return INFX_OK;
+}
+// The groups of G that have a member — members(g) of them — in the contract's order: members descending, then the group column's rank ascending
+template <class M> static std::vector<uint32_t> groups_in_order(const filt::Column& G, M members) {
+    std::vector<uint32_t> ord;
+    for (uint32_t g = 0; g < G.dict.size(); g++) if (members(g)) ord.push_back(g);
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return members(a) != members(b) ? members(a) > members(b) : G.rank[a] < G.rank[b]; });
+    return ord;
+}
+// page j of a listing call's rows (INFX_POST_MAX_ROWS per request), its first c
+template <class T> static void page_of(std::vector<T>& to, const std::vector<T>& rows, size_t j, size_t c) {
+    to.assign(rows.begin() + j * INFX_POST_MAX_ROWS, rows.begin() + j * INFX_POST_MAX_ROWS + c);
+}
+// The two readers of a FiguresAnswer (null: no such answer).  The whole's figures: returns the request's status, INFX_EINVAL (message `none`) without an answer
+template <class F> static int32_t figures_whole(const FiguresAnswer<F>* A, F* out, const char* none) {
+    if (!A || !out) return efail(INFX_EINVAL, none);
+    *out = A->whole;
+    return A->status;
+}
+// its groups, in the contract's order: up to cap codes (of column *group_col, -1 without group_by) and figures; returns the number of groups, -1 on error
+// (also for a refused request)
+template <class F> static int32_t figures_groups(const FiguresAnswer<F>* A, int32_t* group_col, uint32_t* codes, F* figures, int32_t cap) {
+    if (!A || A->status || (cap > 0 && (!codes || !figures))) return -1;
+    const size_t c = std::min<size_t>(A->groups.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(figures, A->groups.data(), c * sizeof(F)); }
+    if (group_col) *group_col = A->groupCol;
+    return (int32_t)A->groups.size();
+}
+} // extern "C++"
 
 // ---- list_documents: a filter's documents in the order of a field, by page (not in the reference) ------------------------------------------------------
 // Per request: the filter goes through the filter cache (refusals are the request's own), its mask through the session's mask cache (the slots, the LRU
 // rule and the statistics of a batch's pre-filters; the missing ones staged as ONE build), the field to its column, whose sort rank is built on first use.
 // infx_list_ordered then selects, gathers and sorts every page on the device; the answers stay on the session for the readers.
-int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_list_request* reqs, int32_t* out_status) {
-    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
-    infx_engine* e = S->e;
-    S->lst.clear(); S->lstMasks = MaskUse(); S->lstPasses = S->lstLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) listing requests in one call");
-    S->lst.assign(nreq, ListAnswer());
-    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->lst[i].status = rc; S->lst[i].err = msg; if (out_status) out_status[i] = rc; };
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (out_status) out_status[i] = INFX_OK;
-        if (reqs[i].limit < 1 || reqs[i].limit > INFX_POST_MAX_ROWS) refuse(i, INFX_EINVAL, "a listing's limit is 1 .. 1024");
-        else if (reqs[i].offset >= 0x80000000u) refuse(i, INFX_EINVAL, "a listing's offset is below 2^31");
-    }
-    { int32_t rc = need_indexed_device(S, "list_documents"); if (rc) { S->lst.clear(); return rc; } }
-    MaskCall mc(S, nreq, &S->lstMasks); std::vector<int32_t> col(nreq, -1);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (S->lst[i].status) continue;
-            if (reqs[i].order_by) {
-                uint32_t c = 0xFFFFFFFFu;
-                const int32_t rc = sort_column(e, reqs[i].order_by, &c);
-                if (rc) { refuse(i, rc, g_eerr); continue; }
-                if (c == 0xFFFFFFFFu) { refuse(i, INFX_EINVAL, std::string("list_documents: no field named '") + reqs[i].order_by + "'"); continue; }
-                col[i] = (int32_t)c;
-            }
-            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) refuse(i, rc, g_eerr); }
-        }
-    }
-    { int32_t rc = mc.acquire(); if (rc) { S->lst.clear(); return rc; } }
-    std::vector<infx_list_req> dr; std::vector<uint32_t> who;
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (S->lst[i].status) continue;
-        infx_list_req R{};
-        R.mask = mc.mask(i); R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
-        dr.push_back(R); who.push_back(i);
-    }
-    const size_t m = dr.size(), rows = INFX_POST_MAX_ROWS;
-    std::vector<int64_t> keys(std::max<size_t>(m, 1) * rows); std::vector<int32_t> docs(std::max<size_t>(m, 1) * rows); std::vector<uint32_t> codes(std::max<size_t>(m, 1) * rows);
-    std::vector<uint32_t> counts(std::max<size_t>(m, 1), 0), totals(std::max<size_t>(m, 1), 0);
-    int32_t rc = infx_list_ordered(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), counts.data(), totals.data());
-    if (rc) { S->lst.clear(); return mc.failed(rc); }
-    mc.done();
-    infx_last_list_stats(S->stream, &S->lstPasses, &S->lstLaunches);
-    for (size_t j = 0; j < m; j++) {
-        ListAnswer& A = S->lst[who[j]];
-        const size_t c = std::min<size_t>(counts[j], dr[j].limit);
-        A.total = totals[j];
-        A.keys.assign(keys.begin() + j * rows, keys.begin() + j * rows + c); A.docs.assign(docs.begin() + j * rows, docs.begin() + j * rows + c);
-        A.codes.assign(codes.begin() + j * rows, codes.begin() + j * rows + c);
-    }
+// what is wrong with a page's limit or offset (null: nothing)
+static const char* page_problem(uint32_t limit, uint32_t offset) {
+    if (limit < 1 || limit > INFX_POST_MAX_ROWS) return "a listing's limit is 1 .. 1024";
+    return offset >= 0x80000000u ? "a listing's offset is below 2^31" : nullptr;
+}
+// order_by (null: document order, *col stays -1) to its column, whose sort rank is built on first use; a failure is the request's: its status, the text in
+// *why (`what` names the call).  Caller holds e->filterMu.
+static int32_t order_column(infx_engine* e, const char* what, const char* order_by, int32_t* col, std::string* why) {
+    if (!order_by) return INFX_OK;
+    uint32_t c = 0xFFFFFFFFu;
+    const int32_t rc = sort_column(e, order_by, &c);
+    if (rc) { *why = g_eerr; return rc; }
+    if (c == 0xFFFFFFFFu) { *why = std::string(what) + ": no field named '" + order_by + "'"; return INFX_EINVAL; }
+    *col = (int32_t)c;
     return INFX_OK;
 }
-// request `which` of the session's last infx_engine_list_documents: up to cap rows; returns the page's row count, -1 on error (also for a refused request)
-int32_t infx_engine_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap) {
-    const ListAnswer* A = answer_at(S ? &S->lst : nullptr, which);
-    if (!A || A->status || (cap > 0 && (!keys || !docs || !codes))) return -1;
+// The pages of a listing call's m live requests as the device library writes them: INFX_POST_MAX_ROWS rows per request, its page's row count, its set's size
+struct PageRows {
+    std::vector<int64_t> keys; std::vector<int32_t> docs; std::vector<uint32_t> codes, counts, totals;
+    void pages(size_t m) {
+        const size_t rows = std::max<size_t>(m, 1) * INFX_POST_MAX_ROWS;
+        keys.resize(rows); docs.resize(rows); codes.resize(rows); counts.assign(std::max<size_t>(m, 1), 0); totals.assign(std::max<size_t>(m, 1), 0);
+    }
+    // answer A takes page j, cut to the request's limit, and the size of the set; returns the page's rows
+    size_t take(ListAnswer& A, size_t j, uint32_t limit) const {
+        const size_t c = std::min<size_t>(counts[j], limit);
+        A.total = totals[j]; page_of(A.keys, keys, j, c); page_of(A.docs, docs, j, c); page_of(A.codes, codes, j, c);
+        return c;
+    }
+};
+int32_t infx_engine_list_documents(infx_session* S, uint32_t nreq, const infx_list_request* reqs, int32_t* out_status) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col; col.fill(-1); std::vector<infx_list_req> dr; PageRows P;
+    return set_call(S, &infx_session::lst, "list_documents", "listing requests", false, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) { if (const char* bad = page_problem(reqs[i].limit, reqs[i].offset)) F.refuse(i, INFX_EINVAL, bad); },
+        [&](auto& F, uint32_t i) {
+            std::string why;
+            const int32_t rc = order_column(S->e, "list_documents", reqs[i].order_by, &col[i], &why);
+            if (rc) F.refuse(i, rc, why); else F.filter(i, reqs[i].filter);
+        },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_list_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit;
+                R.digit_bits = (uint32_t)S->lstDigitBits;
+                dr.push_back(R);
+            }
+            P.pages(dr.size());
+            return infx_list_ordered(S->stream, (uint32_t)dr.size(), dr.data(), P.keys.data(), P.docs.data(), P.codes.data(), P.counts.data(), P.totals.data());
+        },
+        [&](auto& F) {
+            infx_last_list_stats(S->stream, &S->lst.passes, &S->lst.launches);
+            for (size_t j = 0; j < dr.size(); j++) P.take(S->lst.ans[F.who[j]], j, dr[j].limit);
+        });
+}
+// The rows reader of a page: up to cap rows; returns the page's row count (*copied: how many it copied), -1 on error (also for a refused request).  A reader
+// with further arrays passes whether they are there in `more`.
+static int32_t page_rows(const ListAnswer* A, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap, bool more = true, size_t* copied = nullptr) {
+    if (!A || A->status || (cap > 0 && (!keys || !docs || !codes || !more))) return -1;
     const size_t c = std::min<size_t>(A->keys.size(), (size_t)std::max(cap, 0));
     if (c) { std::memcpy(keys, A->keys.data(), c * 8); std::memcpy(docs, A->docs.data(), c * 4); std::memcpy(codes, A->codes.data(), c * 4); }
+    if (copied) *copied = c;
     return (int32_t)A->keys.size();
+}
+// request `which` of the session's last infx_engine_list_documents: its page, as page_rows
+int32_t infx_engine_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap) {
+    return page_rows(answer_at(S ? &S->lst.ans : nullptr, which), keys, docs, codes, cap);
 }
 // the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_list_total(infx_session* S, uint32_t which, uint32_t* total) {
-    return answer_total(answer_at(S ? &S->lst : nullptr, which), total, "no such request in the session's last list_documents call");
+    return answer_total(answer_at(S ? &S->lst.ans : nullptr, which), total, "no such request in the session's last list_documents call");
 }
-int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->lst : nullptr, which), out, cap); }
+int32_t infx_engine_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->lst.ans : nullptr, which), out, cap); }
 int32_t infx_engine_last_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{masks_built, S->lstMasks.built}, {masks_reused, S->lstMasks.reused}, {hist_passes, S->lstPasses}, {launches, S->lstLaunches}});
+    return put_stats({{masks_built, S->lst.masks.built}, {masks_reused, S->lst.masks.reused}, {hist_passes, S->lst.passes}, {launches, S->lst.launches}});
 }
 int32_t infx_engine_set_list_digit_bits(infx_session* S, int32_t bits) {
     if (!S || bits < 4 || bits > 11) return efail(INFX_EINVAL, "the digit width of list_documents is 4 .. 11 bits");
@@ -3288,16 +3363,12 @@ int32_t infx_engine_set_list_digit_bits(infx_session* S, int32_t bits) {
 // The column's rank order (lowest code of every rank; built with the sort rank's first use).  Caller holds e->filterMu.
 static int32_t range_index(infx_engine* e, uint32_t col, const infx_engine::RangeIndex** out) {
     if (e->rangeIndex.size() < e->columns.size()) e->rangeIndex.resize(e->columns.size());
-    if (e->sortRanked.size() < e->columns.size()) e->sortRanked.resize(e->columns.size(), 0);
     infx_engine::RangeIndex& X = e->rangeIndex[col];
-    if (!X.ok || !e->sortRanked[col]) {
+    std::vector<uint32_t> rank;
+    { const int32_t rc = sort_rank_on_device(e, col, &rank); if (rc) return rc; }
+    if (!X.ok) {
         const filt::Column& c = e->columns[col];
-        std::vector<uint32_t> rank; filt::sort_rank(c, rank);
-        if (!e->sortRanked[col]) {
-            int32_t rc = infx_upload_sort_rank(e->dev, col, (uint32_t)rank.size(), rank.data());
-            if (rc) { g_eerr = infx_last_error(); return rc; }
-            e->sortRanked[col] = 1;
-        }
+        if (rank.empty()) filt::sort_rank(c, rank);
         uint32_t nr = 0; for (uint32_t r : rank) nr = std::max(nr, r + 1u);
         X.codeOfRank.assign(nr, 0xFFFFFFFFu);
         for (size_t code = 0; code < rank.size(); code++) if (X.codeOfRank[rank[code]] == 0xFFFFFFFFu) X.codeOfRank[rank[code]] = (uint32_t)code;      // codes ascend: the lowest wins
@@ -3306,6 +3377,10 @@ static int32_t range_index(infx_engine* e, uint32_t col, const infx_engine::Rang
     }
     *out = &X;
     return INFX_OK;
+}
+// the value of a rank of column C: its lowest code's (null: no such rank, as the ranks of an empty set)
+static const filt::Boxed* value_of_rank(const filt::Column& C, const infx_engine::RangeIndex& X, uint32_t rank) {
+    return rank < X.codeOfRank.size() ? &C.dict[X.codeOfRank[rank]] : nullptr;
 }
 static int column_kind(const filt::Column& c) { return c.dict.empty() ? 0 : c.dict[0].kind; }
 // What is wrong with request Q before anything of it is looked at on the device — the field, its kind, the edges, in this order — as the request's status, the
@@ -3341,70 +3416,53 @@ static std::vector<uint32_t> range_thresholds(const filt::Column& c, const infx_
     return thr;
 }
 int32_t infx_engine_range_facets(infx_session* S, uint32_t nreq, const infx_range_request* reqs, int32_t* out_status) {
-    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
-    infx_engine* e = S->e;
-    S->rng.clear(); S->rngMasks = MaskUse(); S->rngLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) range requests in one call");
-    S->rng.assign(nreq, RangeAnswer());
-    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->rng[i].status = rc; S->rng[i].err = msg; if (out_status) out_status[i] = rc; };
-    std::vector<int32_t> col(nreq, -1); std::vector<int> kind(nreq, 0);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
+    struct Req { int32_t col = -1; int kind = 0; uint32_t nanRanks = 0; std::vector<uint32_t> thr; } rq[INFX_MAX_PREFILTERS];
+    std::vector<infx_range_req> dr; std::vector<uint32_t> counts, lo, hi;
+    return set_call(S, &infx_session::rng, "range_facets", "range requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
             std::string why;
-            if (out_status) out_status[i] = INFX_OK;
-            const int32_t rc = range_request_check(e, reqs[i], &col[i], &kind[i], &why);
-            if (rc) refuse(i, rc, why);
-        }
-    }
-    { int32_t rc = need_indexed_device(S, "range_facets"); if (rc) { S->rng.clear(); return rc; } }
-    MaskCall mc(S, nreq, &S->rngMasks);
-    std::vector<std::vector<uint32_t>> thr(nreq); std::vector<uint32_t> nanRanks(nreq, 0);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (S->rng[i].status) continue;
-            const infx_range_request& Q = reqs[i];
+            const int32_t rc = range_request_check(S->e, reqs[i], &rq[i].col, &rq[i].kind, &why);
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) {
             const infx_engine::RangeIndex* X = nullptr;
-            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }
-            if (Q.filter) { const int32_t rc = mc.intern(i, Q.filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
-            nanRanks[i] = X->nanRanks;
-            thr[i] = range_thresholds(e->columns[col[i]], *X, Q, kind[i]);
-        }
-    }
-    { int32_t rc = mc.acquire(); if (rc) { S->rng.clear(); return rc; } }
-    std::vector<infx_range_req> dr; std::vector<uint32_t> who;
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (S->rng[i].status) continue;
-        infx_range_req R{};
-        R.mask = mc.mask(i); R.col = col[i]; R.nedges = reqs[i].nedges; R.nan_ranks = nanRanks[i]; R.thr = thr[i].data();
-        dr.push_back(R); who.push_back(i);
-    }
-    const size_t m = dr.size();
-    std::vector<uint32_t> counts(std::max<size_t>(m, 1) * INFX_RANGE_SLOTS, 0), lo(std::max<size_t>(m, 1), 0xFFFFFFFFu), hi(std::max<size_t>(m, 1), 0);
-    int32_t rc = infx_range_counts(S->stream, (uint32_t)m, dr.data(), counts.data(), lo.data(), hi.data());
-    if (rc) { S->rng.clear(); return mc.failed(rc); }
-    mc.done();
-    { uint32_t r_ = 0; infx_last_range_stats(S->stream, &r_, &S->rngLaunches); }
-    std::lock_guard<std::mutex> lk(e->filterMu);
-    for (size_t j = 0; j < m; j++) {
-        RangeAnswer& A = S->rng[who[j]];
-        const uint32_t ne = dr[j].nedges; const uint32_t* c = counts.data() + j * INFX_RANGE_SLOTS;
-        A.below = c[0]; A.counts.assign(c + 1, c + ne); A.above = c[ne]; A.nan = c[ne + 1];
-        uint64_t t = 0; for (uint32_t k = 0; k < ne + 2; k++) t += c[k];
-        A.total = (uint32_t)t;
-        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
-        if (lo[j] != 0xFFFFFFFFu && lo[j] < X.codeOfRank.size() && hi[j] < X.codeOfRank.size()) {
-            const filt::Boxed& a = C.dict[X.codeOfRank[lo[j]]]; const filt::Boxed& b = C.dict[X.codeOfRank[hi[j]]];
-            A.kind = a.kind == 1 ? 1 : 2;
-            if (A.kind == 1) { A.loI = a.i; A.hiI = b.i; } else { A.loD = a.d; A.hiD = b.d; }
-        }
-    }
-    return INFX_OK;
+            const int32_t rc = range_index(S->e, (uint32_t)rq[i].col, &X);
+            if (rc) return F.refuse(i, rc, g_eerr);
+            if (!F.filter(i, reqs[i].filter)) return;
+            rq[i].nanRanks = X->nanRanks;
+            rq[i].thr = range_thresholds(S->e->columns[rq[i].col], *X, reqs[i], rq[i].kind);
+        },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_range_req R{};
+                R.mask = F.mc.mask(i); R.col = rq[i].col; R.nedges = reqs[i].nedges; R.nan_ranks = rq[i].nanRanks; R.thr = rq[i].thr.data();
+                dr.push_back(R);
+            }
+            const size_t m = std::max<size_t>(dr.size(), 1);
+            counts.assign(m * INFX_RANGE_SLOTS, 0); lo.assign(m, 0xFFFFFFFFu); hi.assign(m, 0);
+            return infx_range_counts(S->stream, (uint32_t)dr.size(), dr.data(), counts.data(), lo.data(), hi.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_range_stats(S->stream, nullptr, &S->rng.launches);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                RangeAnswer& A = S->rng.ans[F.who[j]];
+                const uint32_t ne = dr[j].nedges; const uint32_t* c = counts.data() + j * INFX_RANGE_SLOTS;
+                A.below = c[0]; A.counts.assign(c + 1, c + ne); A.above = c[ne]; A.nan = c[ne + 1];
+                uint64_t t = 0; for (uint32_t k = 0; k < ne + 2; k++) t += c[k];
+                A.total = (uint32_t)t;
+                const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
+                const filt::Boxed *a = value_of_rank(C, X, lo[j]), *b = value_of_rank(C, X, hi[j]);
+                if (!a || !b) continue;
+                A.kind = a->kind == 1 ? 1 : 2;
+                if (A.kind == 1) { A.loI = a->i; A.hiI = b->i; } else { A.loD = a->d; A.hiD = b->d; }
+            }
+        });
 }
 // request `which` of the session's last infx_engine_range_facets: up to cap bucket counts; returns the number of buckets, -1 on error (also for a refused request)
 int32_t infx_engine_range_counts(infx_session* S, uint32_t which, uint32_t* counts, int32_t cap, uint32_t* below, uint32_t* above, uint32_t* nan) {
-    const RangeAnswer* A = answer_at(S ? &S->rng : nullptr, which);
+    const RangeAnswer* A = answer_at(S ? &S->rng.ans : nullptr, which);
     if (!A || A->status || (cap > 0 && !counts)) return -1;
     const size_t c = std::min<size_t>(A->counts.size(), (size_t)std::max(cap, 0));
     if (c) std::memcpy(counts, A->counts.data(), c * 4);
@@ -3413,20 +3471,20 @@ int32_t infx_engine_range_counts(infx_session* S, uint32_t which, uint32_t* coun
 }
 // the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_range_total(infx_session* S, uint32_t which, uint32_t* total) {
-    return answer_total(answer_at(S ? &S->rng : nullptr, which), total, "no such request in the session's last range_facets call");
+    return answer_total(answer_at(S ? &S->rng.ans : nullptr, which), total, "no such request in the session's last range_facets call");
 }
 // the smallest and largest non-NaN value of request `which`'s set: *kind 1 -> lo_i / hi_i, 2 -> lo_d / hi_d, 0 -> there is none
 int32_t infx_engine_range_minmax(infx_session* S, uint32_t which, int32_t* kind, int64_t* lo_i, int64_t* hi_i, double* lo_d, double* hi_d) {
-    if (!S || !kind || which >= S->rng.size()) return efail(INFX_EINVAL, "no such request in the session's last range_facets call");
-    const RangeAnswer& A = S->rng[which];
+    if (!S || !kind || which >= S->rng.ans.size()) return efail(INFX_EINVAL, "no such request in the session's last range_facets call");
+    const RangeAnswer& A = S->rng.ans[which];
     *kind = A.kind;
     if (lo_i) *lo_i = A.loI; if (hi_i) *hi_i = A.hiI; if (lo_d) *lo_d = A.loD; if (hi_d) *hi_d = A.hiD;
     return A.status;
 }
-int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->rng : nullptr, which), out, cap); }
+int32_t infx_engine_range_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->rng.ans : nullptr, which), out, cap); }
 int32_t infx_engine_last_range_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{masks_built, S->rngMasks.built}, {masks_reused, S->rngMasks.reused}, {launches, S->rngLaunches}});
+    return put_stats({{masks_built, S->rng.masks.built}, {masks_reused, S->rng.masks.reused}, {launches, S->rng.launches}});
 }
 
 // ---- field_stats: counts, min / max and the exact sum and mean of a numeric field over the documents a filter accepts, whole or per group (not in the reference) ----
@@ -3448,20 +3506,20 @@ static infx_engine::StatsIndex& stats_index(infx_engine* e, uint32_t col) {
     }
     return X;
 }
-// What is wrong with request Q before anything of it is looked at on the device — the field, its kind, group_by, whether the field can be summed exactly — as
-// the request's status, the text in *why; INFX_OK with the columns (gcol -1: no group_by).  Caller holds e->filterMu.
-static int32_t stats_request_check(infx_engine* e, const infx_stats_request& Q, int32_t* col, int32_t* gcol, std::string* why) {
-    auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
+// What is wrong with the field and the group_by of a field_stats or field_quantiles request (`what`; its `figures` need a numeric column) before anything of
+// it is looked at on the device — the field, its kind, group_by, in this order — as the request's status, the text in *why; INFX_OK with the columns (gcol -1:
+// no group_by).  Caller holds e->filterMu.
+static int32_t numeric_field_check(const infx_engine* e, const std::string& what, const char* figures, const char* field, const char* group_by, int32_t* col,
+                                   int32_t* gcol, std::string* why) {
+    auto bad = [&](const std::string& msg) { *why = what + msg; return (int32_t)INFX_EINVAL; };
     *gcol = -1;
-    if (!Q.field) return bad("field_stats needs a field");
-    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("field_stats: no field named '") + Q.field + "'");
-    if (column_kind(e->columns[*col]) == 3) return bad(std::string("field_stats: field '") + Q.field + "' is a string column; sums need an int64 or a double column");
-    if (Q.group_by) {
-        if ((*gcol = column_named(e, Q.group_by)) < 0) return bad(std::string("field_stats: no group_by field named '") + Q.group_by + "'");
-        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string("field_stats: group_by field '") + Q.group_by + "' has more than 4096 distinct values");
+    if (!field) return bad(" needs a field");
+    if ((*col = column_named(e, field)) < 0) return bad(std::string(": no field named '") + field + "'");
+    if (column_kind(e->columns[*col]) == 3) return bad(std::string(": field '") + field + "' is a string column; " + figures + " need an int64 or a double column");
+    if (group_by) {
+        if ((*gcol = column_named(e, group_by)) < 0) return bad(std::string(": no group_by field named '") + group_by + "'");
+        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string(": group_by field '") + group_by + "' has more than 4096 distinct values");
     }
-    if (!stats_index(e, (uint32_t)*col).summable)
-        return bad(std::string("field_stats: the finite values of field '") + Q.field + "' span more than 128 binary digits; they cannot be summed exactly");
     return INFX_OK;
 }
 // The figures of one slot (a group, or the whole): counts, the extremes as values through the rank's lowest code, the limb sums recombined and rounded once
@@ -3473,132 +3531,98 @@ static infx_stats_figures stats_figures(const infx_stats_slot& S, const infx_eng
     if (V.kind == XS_KIND_INT) xs_sum_int128(W, &F.sum_lo, &F.sum_hi);
     if (F.count) {
         const uint64_t mb = xs_mean_bits(W, V.sc.scale, F.count, S.pinf, S.ninf); std::memcpy(&F.mean, &mb, 8);
-        if (S.min_rank < X.codeOfRank.size() && S.max_rank < X.codeOfRank.size()) {
-            const filt::Boxed& a = C.dict[X.codeOfRank[S.min_rank]]; const filt::Boxed& b = C.dict[X.codeOfRank[S.max_rank]];
-            if (V.kind == XS_KIND_INT) { F.min_i = a.i; F.max_i = b.i; } else { F.min_d = a.d; F.max_d = b.d; }
-        }
+        const filt::Boxed *a = value_of_rank(C, X, S.min_rank), *b = value_of_rank(C, X, S.max_rank);
+        if (a && b) { if (V.kind == XS_KIND_INT) { F.min_i = a->i; F.max_i = b->i; } else { F.min_d = a->d; F.max_d = b->d; } }
     }
     return F;
 }
 int32_t infx_engine_field_stats(infx_session* S, uint32_t nreq, const infx_stats_request* reqs, int32_t* out_status) {
-    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
-    infx_engine* e = S->e;
-    S->sts.clear(); S->stsMasks = MaskUse(); S->stsLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) field_stats requests in one call");
-    S->sts.assign(nreq, StatsAnswer());
-    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->sts[i].status = rc; S->sts[i].err = msg; if (out_status) out_status[i] = rc; };
-    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; std::vector<infx_stats_req> dr; std::vector<size_t> at; std::vector<infx_stats_slot> slots;
+    return set_call(S, &infx_session::sts, "field_stats", "field_stats requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
             std::string why;
-            if (out_status) out_status[i] = INFX_OK;
-            const int32_t rc = stats_request_check(e, reqs[i], &col[i], &gcol[i], &why);
-            if (rc) refuse(i, rc, why);
-        }
-    }
-    { int32_t rc = need_indexed_device(S, "field_stats"); if (rc) { S->sts.clear(); return rc; } }
-    MaskCall mc(S, nreq, &S->stsMasks);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (S->sts[i].status) continue;
+            int32_t rc = numeric_field_check(S->e, "field_stats", "sums", reqs[i].field, reqs[i].group_by, &col[i], &gcol[i], &why);
+            if (!rc && !stats_index(S->e, (uint32_t)col[i]).summable) {
+                rc = INFX_EINVAL;
+                why = std::string("field_stats: the finite values of field '") + reqs[i].field + "' span more than 128 binary digits; they cannot be summed exactly";
+            }
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) {
+            infx_engine* e = S->e;
             const infx_engine::RangeIndex* X = nullptr;
-            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }      // (the sort rank, for min / max)
+            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) return F.refuse(i, rc, g_eerr); }      // (the sort rank, for min / max)
             infx_engine::StatsIndex& V = stats_index(e, (uint32_t)col[i]);
             if (!V.uploaded) {
                 const int32_t rc = infx_upload_column_values(e->dev, (uint32_t)col[i], (uint32_t)V.bits.size(), V.bits.data(), V.kind, V.sc.scale, V.sc.nlimbs);
-                if (rc) { refuse(i, rc, infx_last_error()); continue; }
+                if (rc) return F.refuse(i, rc, infx_last_error());
                 V.uploaded = true;
             }
-            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
-        }
-    }
-    { int32_t rc = mc.acquire(); if (rc) { S->sts.clear(); return rc; } }
-    std::vector<infx_stats_req> dr; std::vector<uint32_t> who; std::vector<size_t> at; size_t nslots = 0;
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (S->sts[i].status) continue;
-        infx_stats_req R{};
-        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i];
-        dr.push_back(R); who.push_back(i); at.push_back(nslots);
-        nslots += gcol[i] >= 0 ? std::max<size_t>(e->columns[gcol[i]].dict.size(), 1) : 1;
-    }
-    const size_t m = dr.size();
-    std::vector<infx_stats_slot> slots(std::max<size_t>(nslots, 1));
-    int32_t rc = infx_field_stats(S->stream, (uint32_t)m, dr.data(), slots.data());
-    if (rc) { S->sts.clear(); return mc.failed(rc); }
-    mc.done();
-    { uint32_t r_ = 0; infx_last_field_stats_info(S->stream, &r_, &S->stsLaunches); }
-    std::lock_guard<std::mutex> lk(e->filterMu);
-    for (size_t j = 0; j < m; j++) {
-        StatsAnswer& A = S->sts[who[j]];
-        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col]; const infx_engine::StatsIndex& V = e->statsIndex[dr[j].col];
-        const infx_stats_slot* sl = slots.data() + at[j];
-        A.groupCol = dr[j].group_col;
-        if (A.groupCol < 0) A.whole = stats_figures(sl[0], V, C, X);
-        else {
-            const filt::Column& G = e->columns[A.groupCol];
-            infx_stats_slot all = {}; all.min_rank = 0xFFFFFFFFu;
-            std::vector<uint32_t> ord;
-            for (uint32_t g = 0; g < G.dict.size(); g++) {
-                const infx_stats_slot& s1 = sl[g];
-                if (!(s1.finite + s1.nan + s1.pinf + s1.ninf)) continue;
-                ord.push_back(g);
-                all.finite += s1.finite; all.nan += s1.nan; all.pinf += s1.pinf; all.ninf += s1.ninf;
-                if (s1.min_rank != 0xFFFFFFFFu) { all.min_rank = std::min(all.min_rank, s1.min_rank); all.max_rank = std::max(all.max_rank, s1.max_rank); }
-                for (int k = 0; k < INFX_STATS_MAX_LIMBS; k++) all.sum[k] += s1.sum[k];      // (fewer than 2^31 members in all: no limb sum overflows)
+            F.filter(i, reqs[i].filter);
+        },
+        [&](auto& F) {
+            size_t nslots = 0;
+            for (uint32_t i : F.who) {
+                infx_stats_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.group_col = gcol[i];
+                dr.push_back(R); at.push_back(nslots);
+                nslots += gcol[i] >= 0 ? std::max<size_t>(S->e->columns[gcol[i]].dict.size(), 1) : 1;
             }
-            auto members = [&](uint32_t g) { return (uint64_t)sl[g].finite + sl[g].nan + sl[g].pinf + sl[g].ninf; };
-            std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return members(a) != members(b) ? members(a) > members(b) : G.rank[a] < G.rank[b]; });
-            A.whole = stats_figures(all, V, C, X);
-            for (uint32_t g : ord) { A.codes.push_back(g); A.groups.push_back(stats_figures(sl[g], V, C, X)); }
-        }
-        A.total = A.whole.count + A.whole.nan;
-    }
-    return INFX_OK;
+            slots.resize(std::max<size_t>(nslots, 1));
+            return infx_field_stats(S->stream, (uint32_t)dr.size(), dr.data(), slots.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_field_stats_info(S->stream, nullptr, &S->sts.launches);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                StatsAnswer& A = S->sts.ans[F.who[j]];
+                const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col]; const infx_engine::StatsIndex& V = e->statsIndex[dr[j].col];
+                const infx_stats_slot* sl = slots.data() + at[j];
+                A.groupCol = dr[j].group_col;
+                if (A.groupCol < 0) A.whole = stats_figures(sl[0], V, C, X);
+                else {
+                    infx_stats_slot all = {}; all.min_rank = 0xFFFFFFFFu;
+                    A.codes = groups_in_order(e->columns[A.groupCol], [&](uint32_t g) { return (uint64_t)sl[g].finite + sl[g].nan + sl[g].pinf + sl[g].ninf; });
+                    for (uint32_t g : A.codes) {
+                        const infx_stats_slot& s1 = sl[g];
+                        all.finite += s1.finite; all.nan += s1.nan; all.pinf += s1.pinf; all.ninf += s1.ninf;
+                        if (s1.min_rank != 0xFFFFFFFFu) { all.min_rank = std::min(all.min_rank, s1.min_rank); all.max_rank = std::max(all.max_rank, s1.max_rank); }
+                        for (int k = 0; k < INFX_STATS_MAX_LIMBS; k++) all.sum[k] += s1.sum[k];      // (fewer than 2^31 members in all: no limb sum overflows)
+                        A.groups.push_back(stats_figures(s1, V, C, X));
+                    }
+                    A.whole = stats_figures(all, V, C, X);
+                }
+                A.total = A.whole.count + A.whole.nan;
+            }
+        });
 }
-// request `which` of the session's last infx_engine_field_stats: the whole's figures (returns the request's status; INFX_EINVAL without such an answer)
+// request `which` of the session's last infx_engine_field_stats: the whole's figures and the groups', as figures_whole and figures_groups
 int32_t infx_engine_field_stats_whole(infx_session* S, uint32_t which, infx_stats_figures* out) {
-    const StatsAnswer* A = answer_at(S ? &S->sts : nullptr, which);
-    if (!A || !out) return efail(INFX_EINVAL, "no such request in the session's last field_stats call");
-    *out = A->whole;
-    return A->status;
+    return figures_whole(answer_at(S ? &S->sts.ans : nullptr, which), out, "no such request in the session's last field_stats call");
 }
-// its groups, in the contract's order: up to cap codes (of column *group_col, -1 without group_by) and figures; returns the number of groups, -1 on error (also for a refused request)
 int32_t infx_engine_field_stats_groups(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, infx_stats_figures* figures, int32_t cap) {
-    const StatsAnswer* A = answer_at(S ? &S->sts : nullptr, which);
-    if (!A || A->status || (cap > 0 && (!codes || !figures))) return -1;
-    const size_t c = std::min<size_t>(A->groups.size(), (size_t)std::max(cap, 0));
-    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(figures, A->groups.data(), c * sizeof(infx_stats_figures)); }
-    if (group_col) *group_col = A->groupCol;
-    return (int32_t)A->groups.size();
+    return figures_groups(answer_at(S ? &S->sts.ans : nullptr, which), group_col, codes, figures, cap);
 }
 // the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_field_stats_total(infx_session* S, uint32_t which, uint32_t* total) {
-    return answer_total(answer_at(S ? &S->sts : nullptr, which), total, "no such request in the session's last field_stats call");
+    return answer_total(answer_at(S ? &S->sts.ans : nullptr, which), total, "no such request in the session's last field_stats call");
 }
-int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->sts : nullptr, which), out, cap); }
+int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->sts.ans : nullptr, which), out, cap); }
 int32_t infx_engine_last_field_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{masks_built, S->stsMasks.built}, {masks_reused, S->stsMasks.reused}, {launches, S->stsLaunches}});
+    return put_stats({{masks_built, S->sts.masks.built}, {masks_reused, S->sts.masks.reused}, {launches, S->sts.launches}});
 }
 
 // ---- field_quantiles: the values at the quantiles' positions of a numeric field over the documents a filter accepts, whole and per group (not in the reference) ----
 // Per request: the field to its column (int64 or double) and the column to its sort rank, group_by to any column of at most 4096 values, the filter through
 // the filter cache and its mask through the session's mask cache, as infx_engine_field_stats.  infx_field_quantiles then selects every (slot, quantile) of the
 // call on sort ranks; the engine maps each answered rank to a value through the rank's lowest code, as stats_figures does for min / max.
-// What is wrong with request Q before anything of it is looked at on the device, as the request's status, the text in *why; INFX_OK with the columns
-// (gcol -1: no group_by).  Caller holds e->filterMu.
-static int32_t quant_request_check(infx_engine* e, const infx_quantile_request& Q, int32_t* col, int32_t* gcol, std::string* why) {
-    auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
-    *gcol = -1;
-    if (!Q.field) return bad("field_quantiles needs a field");
-    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("field_quantiles: no field named '") + Q.field + "'");
-    if (column_kind(e->columns[*col]) == 3) return bad(std::string("field_quantiles: field '") + Q.field + "' is a string column; quantiles need an int64 or a double column");
-    if (Q.group_by) {
-        if ((*gcol = column_named(e, Q.group_by)) < 0) return bad(std::string("field_quantiles: no group_by field named '") + Q.group_by + "'");
-        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string("field_quantiles: group_by field '") + Q.group_by + "' has more than 4096 distinct values");
-    }
+// What is wrong with request Q before anything of it is looked at on the device — field and group_by as numeric_field_check, then the quantiles — as the
+// request's status, the text in *why; INFX_OK with the columns (gcol -1: no group_by).  Caller holds e->filterMu.
+static int32_t quant_request_check(const infx_engine* e, const infx_quantile_request& Q, int32_t* col, int32_t* gcol, std::string* why) {
+    auto bad = [&](const char* msg) { *why = msg; return (int32_t)INFX_EINVAL; };
+    { const int32_t rc = numeric_field_check(e, "field_quantiles", "quantiles", Q.field, Q.group_by, col, gcol, why); if (rc) return rc; }
     if (!Q.nq || !Q.q) return bad("field_quantiles needs at least one quantile");
     if (Q.nq > INFX_QUANT_MAX) return bad("field_quantiles: more than 16 quantiles in one request");
     for (uint32_t t = 0; t < Q.nq; t++) if (!(Q.q[t] >= 0.0 && Q.q[t] <= 1.0)) return bad("field_quantiles: every quantile is a number in [0, 1]");
@@ -3608,107 +3632,76 @@ static int32_t quant_request_check(infx_engine* e, const infx_quantile_request& 
 static infx_quantile_figures quant_figures(const infx_quant_slot& S, const uint32_t* ranks, uint32_t nq, const filt::Column& C, const infx_engine::RangeIndex& X) {
     infx_quantile_figures F = {};
     F.count = S.count; F.nan = S.nan; F.kind = C.dict.empty() || C.dict[0].kind == 1 ? 1 : 2; F.nq = nq;
-    for (uint32_t t = 0; t < nq && S.count; t++) {
-        if (ranks[t] >= X.codeOfRank.size()) continue;
-        const filt::Boxed& v = C.dict[X.codeOfRank[ranks[t]]];
-        if (F.kind == 1) F.v_i[t] = v.i; else F.v_d[t] = v.d;
-    }
+    for (uint32_t t = 0; t < nq && S.count; t++)
+        if (const filt::Boxed* v = value_of_rank(C, X, ranks[t])) { if (F.kind == 1) F.v_i[t] = v->i; else F.v_d[t] = v->d; }
     return F;
 }
 int32_t infx_engine_field_quantiles(infx_session* S, uint32_t nreq, const infx_quantile_request* reqs, int32_t* out_status) {
-    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
-    infx_engine* e = S->e;
-    S->qnt.clear(); S->qntMasks = MaskUse(); S->qntPasses = S->qntLaunches = 0; S->qntPlace[0] = S->qntPlace[1] = S->qntPlace[2] = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) field_quantiles requests in one call");
-    S->qnt.assign(nreq, QuantAnswer());
-    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->qnt[i].status = rc; S->qnt[i].err = msg; if (out_status) out_status[i] = rc; };
-    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; std::array<uint32_t, INFX_MAX_PREFILTERS> nanRanks;
+    std::vector<infx_quant_req> dr; std::vector<size_t> atSlot, atRank; std::vector<infx_quant_slot> slots; std::vector<uint32_t> ranks;
+    return set_call(S, &infx_session::qnt, "field_quantiles", "field_quantiles requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
             std::string why;
-            if (out_status) out_status[i] = INFX_OK;
-            const int32_t rc = quant_request_check(e, reqs[i], &col[i], &gcol[i], &why);
-            if (rc) refuse(i, rc, why);
-        }
-    }
-    { int32_t rc = need_indexed_device(S, "field_quantiles"); if (rc) { S->qnt.clear(); return rc; } }
-    MaskCall mc(S, nreq, &S->qntMasks);
-    std::vector<uint32_t> nanRanks(nreq, 0);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (S->qnt[i].status) continue;
+            const int32_t rc = quant_request_check(S->e, reqs[i], &col[i], &gcol[i], &why);
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) {
             const infx_engine::RangeIndex* X = nullptr;
-            { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) { refuse(i, rc, g_eerr); continue; } }
+            const int32_t rc = range_index(S->e, (uint32_t)col[i], &X);
+            if (rc) return F.refuse(i, rc, g_eerr);
             nanRanks[i] = X->nanRanks;
-            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) { refuse(i, rc, g_eerr); continue; } }
-        }
-    }
-    { int32_t rc = mc.acquire(); if (rc) { S->qnt.clear(); return rc; } }
-    std::vector<infx_quant_req> dr; std::vector<uint32_t> who; std::vector<size_t> atSlot, atRank; size_t nslots = 0, nranks = 0;
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (S->qnt[i].status) continue;
-        infx_quant_req R{};
-        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.nq = reqs[i].nq; R.digit_bits = (uint32_t)S->qntDigitBits; R.nan_ranks = nanRanks[i];
-        std::copy(reqs[i].q, reqs[i].q + reqs[i].nq, R.q);
-        dr.push_back(R); who.push_back(i); atSlot.push_back(nslots); atRank.push_back(nranks);
-        const size_t sl = gcol[i] >= 0 ? e->columns[gcol[i]].dict.size() + 1 : 1;
-        nslots += sl; nranks += sl * reqs[i].nq;
-    }
-    const size_t m = dr.size();
-    std::vector<infx_quant_slot> slots(std::max<size_t>(nslots, 1)); std::vector<uint32_t> ranks(std::max<size_t>(nranks, 1));
-    int32_t rc = infx_field_quantiles(S->stream, (uint32_t)m, dr.data(), slots.data(), ranks.data());
-    if (rc) { S->qnt.clear(); return mc.failed(rc); }
-    mc.done();
-    infx_last_field_quantiles_info(S->stream, nullptr, &S->qntPasses, &S->qntLaunches, &S->qntPlace[0], &S->qntPlace[1], &S->qntPlace[2]);
-    std::lock_guard<std::mutex> lk(e->filterMu);
-    for (size_t j = 0; j < m; j++) {
-        QuantAnswer& A = S->qnt[who[j]];
-        const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
-        const infx_quant_slot* sl = slots.data() + atSlot[j]; const uint32_t* rk = ranks.data() + atRank[j]; const uint32_t nq = dr[j].nq;
-        A.groupCol = dr[j].group_col;
-        const size_t ng = A.groupCol >= 0 ? e->columns[A.groupCol].dict.size() : 0;      // (the whole set's slot lies behind the groups')
-        A.whole = quant_figures(sl[ng], rk + ng * nq, nq, C, X);
-        if (A.groupCol >= 0) {
-            const filt::Column& G = e->columns[A.groupCol];
-            std::vector<uint32_t> ord;
-            for (uint32_t g = 0; g < ng; g++) if (sl[g].count + sl[g].nan) ord.push_back(g);
-            auto members = [&](uint32_t g) { return (uint64_t)sl[g].count + sl[g].nan; };
-            std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return members(a) != members(b) ? members(a) > members(b) : G.rank[a] < G.rank[b]; });
-            for (uint32_t g : ord) { A.codes.push_back(g); A.groups.push_back(quant_figures(sl[g], rk + (size_t)g * nq, nq, C, X)); }
-        }
-        A.total = A.whole.count + A.whole.nan;
-    }
-    return INFX_OK;
+            F.filter(i, reqs[i].filter);
+        },
+        [&](auto& F) {
+            size_t nslots = 0, nranks = 0;
+            for (uint32_t i : F.who) {
+                infx_quant_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.digit_bits = (uint32_t)S->qntDigitBits; R.nan_ranks = nanRanks[i];
+                R.nq = reqs[i].nq; std::copy(reqs[i].q, reqs[i].q + reqs[i].nq, R.q);
+                dr.push_back(R); atSlot.push_back(nslots); atRank.push_back(nranks);
+                const size_t sl = gcol[i] >= 0 ? S->e->columns[gcol[i]].dict.size() + 1 : 1;
+                nslots += sl; nranks += sl * reqs[i].nq;
+            }
+            slots.resize(std::max<size_t>(nslots, 1)); ranks.resize(std::max<size_t>(nranks, 1));
+            return infx_field_quantiles(S->stream, (uint32_t)dr.size(), dr.data(), slots.data(), ranks.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_field_quantiles_info(S->stream, nullptr, &S->qnt.passes, &S->qnt.launches, &S->qnt.place[0], &S->qnt.place[1], &S->qnt.place[2]);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                QuantAnswer& A = S->qnt.ans[F.who[j]];
+                const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col];
+                const infx_quant_slot* sl = slots.data() + atSlot[j]; const uint32_t* rk = ranks.data() + atRank[j]; const uint32_t nq = dr[j].nq;
+                A.groupCol = dr[j].group_col;
+                const size_t ng = A.groupCol >= 0 ? e->columns[A.groupCol].dict.size() : 0;      // (the whole set's slot lies behind the groups')
+                A.whole = quant_figures(sl[ng], rk + ng * nq, nq, C, X);
+                if (A.groupCol >= 0) {
+                    A.codes = groups_in_order(e->columns[A.groupCol], [&](uint32_t g) { return (uint64_t)sl[g].count + sl[g].nan; });
+                    for (uint32_t g : A.codes) A.groups.push_back(quant_figures(sl[g], rk + (size_t)g * nq, nq, C, X));
+                }
+                A.total = A.whole.count + A.whole.nan;
+            }
+        });
 }
-// request `which` of the session's last infx_engine_field_quantiles: the whole's figures (returns the request's status; INFX_EINVAL without such an answer)
+// request `which` of the session's last infx_engine_field_quantiles: the whole's figures and the groups', as figures_whole and figures_groups
 int32_t infx_engine_field_quantiles_whole(infx_session* S, uint32_t which, infx_quantile_figures* out) {
-    const QuantAnswer* A = answer_at(S ? &S->qnt : nullptr, which);
-    if (!A || !out) return efail(INFX_EINVAL, "no such request in the session's last field_quantiles call");
-    *out = A->whole;
-    return A->status;
+    return figures_whole(answer_at(S ? &S->qnt.ans : nullptr, which), out, "no such request in the session's last field_quantiles call");
 }
-// its groups, in the contract's order: up to cap codes (of column *group_col, -1 without group_by) and figures; returns the number of groups, -1 on error (also for a refused request)
 int32_t infx_engine_field_quantiles_groups(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, infx_quantile_figures* figures, int32_t cap) {
-    const QuantAnswer* A = answer_at(S ? &S->qnt : nullptr, which);
-    if (!A || A->status || (cap > 0 && (!codes || !figures))) return -1;
-    const size_t c = std::min<size_t>(A->groups.size(), (size_t)std::max(cap, 0));
-    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(figures, A->groups.data(), c * sizeof(infx_quantile_figures)); }
-    if (group_col) *group_col = A->groupCol;
-    return (int32_t)A->groups.size();
+    return figures_groups(answer_at(S ? &S->qnt.ans : nullptr, which), group_col, codes, figures, cap);
 }
 int32_t infx_engine_field_quantiles_total(infx_session* S, uint32_t which, uint32_t* total) {
-    return answer_total(answer_at(S ? &S->qnt : nullptr, which), total, "no such request in the session's last field_quantiles call");
+    return answer_total(answer_at(S ? &S->qnt.ans : nullptr, which), total, "no such request in the session's last field_quantiles call");
 }
-int32_t infx_engine_field_quantiles_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->qnt : nullptr, which), out, cap); }
+int32_t infx_engine_field_quantiles_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->qnt.ans : nullptr, which), out, cap); }
 int32_t infx_engine_last_field_quantiles_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{masks_built, S->qntMasks.built}, {masks_reused, S->qntMasks.reused}, {hist_passes, S->qntPasses}, {launches, S->qntLaunches}});
+    return put_stats({{masks_built, S->qnt.masks.built}, {masks_reused, S->qnt.masks.reused}, {hist_passes, S->qnt.passes}, {launches, S->qnt.launches}});
 }
 int32_t infx_engine_last_field_quantiles_placement(infx_session* S, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{digit_bits, S->qntPlace[0]}, {lds_rows, S->qntPlace[1]}, {global_rows, S->qntPlace[2]}});
+    return put_stats({{digit_bits, S->qnt.place[0]}, {lds_rows, S->qnt.place[1]}, {global_rows, S->qnt.place[2]}});
 }
 int32_t infx_engine_set_quantile_digit_bits(infx_session* S, int32_t bits) {
     if (!S || (bits != 0 && (bits < 4 || bits > 11))) return efail(INFX_EINVAL, "the digit width of field_quantiles is 4 .. 11 bits, or 0: chosen per call");
@@ -3721,88 +3714,62 @@ int32_t infx_engine_set_quantile_digit_bits(infx_session* S, int32_t bits) {
 // sort rank is built on first use; group_by to its column (any kind: the group is the dictionary code).  infx_list_grouped then finds the heads of every
 // (mask, group column, order column, direction) once and pages over them; the answers stay on the session for the readers.
 int32_t infx_engine_list_groups(infx_session* S, uint32_t nreq, const infx_group_list_request* reqs, int32_t* out_status) {
-    if (!S || (nreq && !reqs)) return efail(INFX_EINVAL, "null argument");
-    infx_engine* e = S->e;
-    S->grp.clear(); S->grpMasks = MaskUse(); S->grpHeads = S->grpPasses = S->grpLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) list_groups requests in one call");
-    S->grp.assign(nreq, GroupListAnswer());
-    auto refuse = [&](uint32_t i, int32_t rc, const std::string& msg) { S->grp[i].status = rc; S->grp[i].err = msg; if (out_status) out_status[i] = rc; };
-    std::vector<int32_t> col(nreq, -1), gcol(nreq, -1);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (out_status) out_status[i] = INFX_OK;
-            if (reqs[i].limit < 1 || reqs[i].limit > INFX_POST_MAX_ROWS) refuse(i, INFX_EINVAL, "a listing's limit is 1 .. 1024");
-            else if (reqs[i].offset >= 0x80000000u) refuse(i, INFX_EINVAL, "a listing's offset is below 2^31");
-            else if (!reqs[i].group_by) refuse(i, INFX_EINVAL, "list_groups needs a group_by field");
-            else if ((gcol[i] = column_named(e, reqs[i].group_by)) < 0) refuse(i, INFX_EINVAL, std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'");
-            else if (reqs[i].order_by && column_named(e, reqs[i].order_by) < 0) refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'");
-        }
-    }
-    { int32_t rc = need_indexed_device(S, "list_groups"); if (rc) { S->grp.clear(); return rc; } }
-    MaskCall mc(S, nreq, &S->grpMasks);
-    {
-        std::lock_guard<std::mutex> lk(e->filterMu);
-        for (uint32_t i = 0; i < nreq; i++) {
-            if (S->grp[i].status) continue;
-            if ((gcol[i] = column_named(e, reqs[i].group_by)) < 0) { refuse(i, INFX_EINVAL, std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'"); continue; }
-            if (reqs[i].order_by) {
-                uint32_t c = 0xFFFFFFFFu;
-                const int32_t rc = sort_column(e, reqs[i].order_by, &c);
-                if (rc) { refuse(i, rc, g_eerr); continue; }
-                if (c == 0xFFFFFFFFu) { refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'"); continue; }
-                col[i] = (int32_t)c;
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; col.fill(-1);
+    std::vector<infx_group_list_req> dr; PageRows P; std::vector<uint32_t> gcodes, sizes, groups;
+    auto no_group = [&](uint32_t i) { return std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'"; };
+    return set_call(S, &infx_session::grp, "list_groups", "list_groups requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
+            if (const char* bad = page_problem(reqs[i].limit, reqs[i].offset)) F.refuse(i, INFX_EINVAL, bad);
+            else if (!reqs[i].group_by) F.refuse(i, INFX_EINVAL, "list_groups needs a group_by field");
+            else if (column_named(S->e, reqs[i].group_by) < 0) F.refuse(i, INFX_EINVAL, no_group(i));
+            else if (reqs[i].order_by && column_named(S->e, reqs[i].order_by) < 0)
+                F.refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'");
+        },
+        [&](auto& F, uint32_t i) {
+            std::string why;
+            if ((gcol[i] = column_named(S->e, reqs[i].group_by)) < 0) return F.refuse(i, INFX_EINVAL, no_group(i));
+            const int32_t rc = order_column(S->e, "list_groups", reqs[i].order_by, &col[i], &why);
+            if (rc) F.refuse(i, rc, why); else F.filter(i, reqs[i].filter);
+        },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_group_list_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset;
+                R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
+                dr.push_back(R);
             }
-            if (reqs[i].filter) { const int32_t rc = mc.intern(i, reqs[i].filter); if (rc) refuse(i, rc, g_eerr); }
-        }
-    }
-    { int32_t rc = mc.acquire(); if (rc) { S->grp.clear(); return rc; } }
-    std::vector<infx_group_list_req> dr; std::vector<uint32_t> who;
-    for (uint32_t i = 0; i < nreq; i++) {
-        if (S->grp[i].status) continue;
-        infx_group_list_req R{};
-        R.mask = mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.ascending = reqs[i].ascending ? 1 : 0; R.offset = reqs[i].offset; R.limit = reqs[i].limit;
-        R.digit_bits = (uint32_t)S->lstDigitBits;
-        dr.push_back(R); who.push_back(i);
-    }
-    const size_t m = dr.size(), rows = INFX_POST_MAX_ROWS, cap = std::max<size_t>(m, 1);
-    std::vector<int64_t> keys(cap * rows); std::vector<int32_t> docs(cap * rows); std::vector<uint32_t> codes(cap * rows), gcodes(cap * rows), sizes(cap * rows);
-    std::vector<uint32_t> counts(cap, 0), groups(cap, 0), totals(cap, 0);
-    int32_t rc = infx_list_grouped(S->stream, (uint32_t)m, dr.data(), keys.data(), docs.data(), codes.data(), gcodes.data(), sizes.data(), counts.data(), groups.data(), totals.data());
-    if (rc) { S->grp.clear(); return mc.failed(rc); }
-    mc.done();
-    infx_last_group_list_stats(S->stream, &S->grpHeads, &S->grpPasses, &S->grpLaunches);
-    for (size_t j = 0; j < m; j++) {
-        GroupListAnswer& A = S->grp[who[j]];
-        const size_t c = std::min<size_t>(counts[j], dr[j].limit), at = j * rows;
-        A.total = totals[j]; A.totalGroups = groups[j];
-        A.keys.assign(keys.begin() + at, keys.begin() + at + c); A.docs.assign(docs.begin() + at, docs.begin() + at + c);
-        A.codes.assign(codes.begin() + at, codes.begin() + at + c); A.gcodes.assign(gcodes.begin() + at, gcodes.begin() + at + c);
-        A.sizes.assign(sizes.begin() + at, sizes.begin() + at + c);
-    }
-    return INFX_OK;
+            P.pages(dr.size());
+            gcodes.resize(P.codes.size()); sizes.resize(P.codes.size()); groups.assign(P.counts.size(), 0);
+            return infx_list_grouped(S->stream, (uint32_t)dr.size(), dr.data(), P.keys.data(), P.docs.data(), P.codes.data(), gcodes.data(), sizes.data(),
+                                     P.counts.data(), groups.data(), P.totals.data());
+        },
+        [&](auto& F) {
+            infx_last_group_list_stats(S->stream, &S->grp.heads, &S->grp.passes, &S->grp.launches);
+            for (size_t j = 0; j < dr.size(); j++) {
+                GroupListAnswer& A = S->grp.ans[F.who[j]];
+                const size_t c = P.take(A, j, dr[j].limit);
+                A.totalGroups = groups[j]; page_of(A.gcodes, gcodes, j, c); page_of(A.sizes, sizes, j, c);
+            }
+        });
 }
-// request `which` of the session's last infx_engine_list_groups: up to cap rows; returns the page's row count, -1 on error (also for a refused request)
+// request `which` of the session's last infx_engine_list_groups: its page as page_rows, with every row's group code and group size
 int32_t infx_engine_group_list_rows(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, uint32_t* group_codes, uint32_t* sizes, int32_t cap) {
-    const GroupListAnswer* A = answer_at(S ? &S->grp : nullptr, which);
-    if (!A || A->status || (cap > 0 && (!keys || !docs || !codes || !group_codes || !sizes))) return -1;
-    const size_t c = std::min<size_t>(A->keys.size(), (size_t)std::max(cap, 0));
-    if (c) {
-        std::memcpy(keys, A->keys.data(), c * 8); std::memcpy(docs, A->docs.data(), c * 4); std::memcpy(codes, A->codes.data(), c * 4);
-        std::memcpy(group_codes, A->gcodes.data(), c * 4); std::memcpy(sizes, A->sizes.data(), c * 4);
-    }
-    return (int32_t)A->keys.size();
+    const GroupListAnswer* A = answer_at(S ? &S->grp.ans : nullptr, which);
+    size_t c = 0;
+    const int32_t n = page_rows(A, keys, docs, codes, cap, group_codes && sizes, &c);
+    if (c) { std::memcpy(group_codes, A->gcodes.data(), c * 4); std::memcpy(sizes, A->sizes.data(), c * 4); }
+    return n;
 }
 // the number of groups with a member and the size of request `which`'s set (0 for a refused one, whose status is returned)
 int32_t infx_engine_group_list_totals(infx_session* S, uint32_t which, uint32_t* total_groups, uint32_t* total) {
-    const GroupListAnswer* A = answer_at(S ? &S->grp : nullptr, which);
+    const GroupListAnswer* A = answer_at(S ? &S->grp.ans : nullptr, which);
     if (A && total_groups) *total_groups = A->totalGroups;
     return answer_total(total_groups ? A : nullptr, total, "no such request in the session's last list_groups call");
 }
-int32_t infx_engine_group_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->grp : nullptr, which), out, cap); }
+int32_t infx_engine_group_list_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->grp.ans : nullptr, which), out, cap); }
 int32_t infx_engine_last_group_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
-    return put_stats({{masks_built, S->grpMasks.built}, {masks_reused, S->grpMasks.reused}, {head_passes, S->grpHeads}, {hist_passes, S->grpPasses}, {launches, S->grpLaunches}});
+    return put_stats({{masks_built, S->grp.masks.built}, {masks_reused, S->grp.masks.reused}, {head_passes, S->grp.heads}, {hist_passes, S->grp.passes}, {launches, S->grp.launches}});
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

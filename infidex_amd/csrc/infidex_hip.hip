@@ -3077,6 +3077,17 @@ static int32_t merge_once_shape(const infx_index* ix, int32_t n, uint32_t ldsWor
     *threads = (int)T; *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + T - 1) / T));
     return INFX_OK;
 }
+struct SetKey { const uint8_t* mask; int32_t col, gcol; };      // what the device's order of a call's requests looks at (gcol: -1 throughout a call without groups)
+// order[]: the requests so that the ones that share a mask follow one another, among them the ones that share a value column, among those the ones that share
+// a group column — the walk keeps what the request before loaded — and the others in the caller's order
+static void set_order(uint32_t nreq, const SetKey* key, uint32_t* order) {
+    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
+    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
+        const SetKey &A = key[a], &B = key[b];
+        return A.mask != B.mask ? std::less<const uint8_t*>()(A.mask, B.mask) : A.col != B.col ? A.col < B.col : A.gcol < B.gcol; });
+}
+// what request Q keeps of B, the one before it in that order: 1 the mask's flags, 3 the value column's ranks as well
+static uint32_t set_reuse(const SetKey& B, const SetKey& Q) { return B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
 // ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
 // The enqueue part of a listing call, shared by infx_list_ordered and infx_list_grouped.  Where the nreq requests of a call lie in the stream's listing
 // workspace W ([states | histograms] zeroed, [page composites] all ones, range counts and prefixes [nreq][2][3][nRanges]) and in its rows O
@@ -3209,10 +3220,9 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
     { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
     s->lastRngReqs = nreq;
     if (!nreq) return INFX_OK;
-    // requests that share a mask follow one another, and among them the ones that share a column: the walk keeps what the request before loaded
-    uint32_t order[RB_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
-    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) { return reqs[a].mask != reqs[b].mask ? std::less<const uint8_t*>()(reqs[a].mask, reqs[b].mask) : reqs[a].col < reqs[b].col; });
+    uint32_t order[RB_MAX_REQS]; SetKey key[RB_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, -1};
+    set_order(nreq, key, order);
     const size_t oHi = (size_t)nreq * RNG_OUT_STRIDE * 4, oLo = oHi + (size_t)nreq * 4;
     GROW(s->dRngWs, s->capRngWs, thrWords * 4);
     GROW(s->dRngOut, s->capRngOut, oLo + (size_t)nreq * 4);
@@ -3227,7 +3237,7 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
         D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col];
         D.thr = (const uint32_t*)s->dRngWs + thr.size(); thr.insert(thr.end(), Q.thr, Q.thr + Q.nedges);
         D.nedges = Q.nedges; D.nanRanks = Q.nan_ranks; D.ldsOff = ldsWords; ldsWords += rb_lds_words(Q.nedges);
-        if (k) { const infx_range_req& B = reqs[order[k - 1]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+        if (k) D.reuse = set_reuse(key[order[k - 1]], key[order[k]]);
     }
     UP(s->dRngWs, thr.data(), thrWords * 4);
     HIPCHK(hipMemsetAsync(O, 0, oLo, s->st));
@@ -3268,6 +3278,16 @@ static uint32_t sts_place(uint32_t nreq, const uint32_t* words, uint32_t budget,
     }
     return used;
 }
+// sts_place under the two budgets: k_facets_all's (STS_LDS_WORDS, 256 threads); where that leaves requests in global memory and the whole LDS of a CU would
+// hold more of them, that (STS_BIG_LDS_WORDS, if `big` allows it): merge_once_shape then takes one workgroup of 1024 threads per CU, LDS atomics for global ones
+static uint32_t sts_place_best(uint32_t nreq, const uint32_t* words, bool big, uint32_t* ldsOff) {
+    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
+    if (inGlobal && big) {
+        uint32_t bigOff[2 * STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
+        if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; }
+    }
+    return ldsWords;
+}
 int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out) {
     if (!s || (nreq && (!reqs || !slots_out))) return fail(INFX_EINVAL, "bad field-stats arguments%s");
     s->lastStsReqs = 0; s->lastStsLaunches = 0;
@@ -3287,29 +3307,21 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
     { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
     s->lastStsReqs = nreq;
     if (!nreq) return INFX_OK;
-    // requests that share a mask follow one another, among them the ones that share a value column, among those the ones that share a group column
-    uint32_t order[STS_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
-    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
-        const infx_stats_req &A = reqs[a], &B = reqs[b];
-        if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
-        return A.col != B.col ? A.col < B.col : A.group_col < B.group_col; });
+    uint32_t order[STS_MAX_REQS]; SetKey key[STS_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
+    set_order(nreq, key, order);
+    // a request's slots: one per value of its group column (at least one), one without; in the caller's order request i's follow request i - 1's, at at[i]
+    uint32_t slotsOf[STS_MAX_REQS]; size_t at[STS_MAX_REQS], totalSlots = 0;
+    for (uint32_t i = 0; i < nreq; i++) { const int32_t g = reqs[i].group_col; slotsOf[i] = g >= 0 ? std::max(ix->colValues[g], 1u) : 1u; at[i] = totalSlots; totalSlots += slotsOf[i]; }
     // the output: per request (in device order) its slots, then every request's smallest ranks
-    uint32_t nslots[STS_MAX_REQS], words[STS_MAX_REQS], ldsOff[STS_MAX_REQS]; size_t off[STS_MAX_REQS], loOff[STS_MAX_REQS], outWords = 0, totalSlots = 0;
+    uint32_t words[STS_MAX_REQS], ldsOff[STS_MAX_REQS]; size_t off[STS_MAX_REQS], loOff[STS_MAX_REQS], outWords = 0, loSlots = 0;
     for (uint32_t k = 0; k < nreq; k++) {
         const infx_stats_req& Q = reqs[order[k]];
-        nslots[k] = Q.group_col >= 0 ? std::max(ix->colValues[Q.group_col], 1u) : 1u;
-        words[k] = nslots[k] * sts_stride(ix->colLimbs[Q.col]);
-        off[k] = outWords; outWords += words[k]; loOff[k] = totalSlots; totalSlots += nslots[k];
+        words[k] = slotsOf[order[k]] * sts_stride(ix->colLimbs[Q.col]);
+        off[k] = outWords; outWords += words[k]; loOff[k] = loSlots; loSlots += slotsOf[order[k]];
     }
-    // 256 threads and k_facets_all's LDS budget; a call that leaves slots in global memory which the whole LDS of a CU would hold runs as one workgroup of 1024
-    // threads per CU instead: the same sixteen waves per CU, and LDS atomics where every member would be global atomics (INFX_STATS_NO_BIG_LDS=1: never, for measurements)
-    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();
-    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
-    if (inGlobal && !noBig) {
-        uint32_t bigOff[STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
-        if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; }      // (more than STS_LDS_WORDS now: merge_once_shape takes 1024 threads)
-    }
+    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (=1: never 1024 threads, for measurements)
+    const uint32_t ldsWords = sts_place_best(nreq, words, !noBig, ldsOff);
     GROW(s->dStsOut, s->capStsOut, (outWords + totalSlots) * 4);
     uint32_t* O = (uint32_t*)s->dStsOut;
     DevStatsCall P{}; P.nreq = nreq;
@@ -3319,9 +3331,9 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
         D.mask = Q.mask ? Q.mask : ix->d.deleted;
         D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.bits = ix->colBits[Q.col]; D.nvals = ix->colValues[Q.col];
         D.kind = ix->colKind[Q.col]; D.scale = ix->colScale[Q.col]; D.nlimbs = ix->colLimbs[Q.col];
-        D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = nslots[k];
+        D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = slotsOf[order[k]];
         D.out = O + off[k]; D.lo = O + outWords + loOff[k]; D.ldsOff = ldsOff[k];
-        if (k) { const infx_stats_req& B = reqs[order[k - 1]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+        if (k) D.reuse = set_reuse(key[order[k - 1]], key[order[k]]);
     }
     HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
     HIPCHK(hipMemsetAsync(O + outWords, 0xFF, totalSlots * 4, s->st));
@@ -3336,12 +3348,9 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
     s->hStsRaw.assign(outWords + totalSlots, 0u);
     DOWN(s->hStsRaw.data(), O, (outWords + totalSlots) * 4);
     SYNC();
-    // the caller's order: request i's slots follow request i - 1's
-    size_t at[STS_MAX_REQS], sum = 0;
-    for (uint32_t i = 0; i < nreq; i++) { at[i] = sum; sum += reqs[i].group_col >= 0 ? std::max(ix->colValues[reqs[i].group_col], 1u) : 1u; }
     for (uint32_t k = 0; k < nreq; k++) {
         const uint32_t nl = ix->colLimbs[reqs[order[k]].col], W = sts_stride(nl);
-        for (uint32_t g = 0; g < nslots[k]; g++) {
+        for (uint32_t g = 0; g < slotsOf[order[k]]; g++) {
             const uint32_t* w = s->hStsRaw.data() + off[k] + (size_t)g * W;
             infx_stats_slot& S = slots_out[at[order[k]] + g];
             S.finite = w[0]; S.nan = w[1]; S.pinf = w[2]; S.ninf = w[3]; S.max_rank = w[4]; S.min_rank = s->hStsRaw[outWords + loOff[k] + g];
@@ -3381,17 +3390,19 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
     { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastQntInfo[2]); if (rc_) return rc_; }
     s->lastQntInfo[0] = nreq;
     if (!nreq) return INFX_OK;
-    // requests that share a mask follow one another, among them the ones that share a value column, among those the ones that share a group column
-    uint32_t order[QNT_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) order[i] = i;
-    std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
-        const infx_quant_req &A = reqs[a], &B = reqs[b];
-        if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
-        return A.col != B.col ? A.col < B.col : A.group_col < B.group_col; });
+    uint32_t order[QNT_MAX_REQS]; SetKey key[QNT_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
+    set_order(nreq, key, order);
+    // a request's slots: one per value of its group column, then the whole set's; in the caller's order request i's slots and ranks follow request i - 1's
+    uint32_t slotsOf[QNT_MAX_REQS]; size_t atSlot[QNT_MAX_REQS], atTgt[QNT_MAX_REQS], ns = 0, nt = 0;
+    for (uint32_t i = 0; i < nreq; i++) {
+        slotsOf[i] = reqs[i].group_col >= 0 ? ix->colValues[reqs[i].group_col] + 1u : 1u;
+        atSlot[i] = ns; atTgt[i] = nt; ns += slotsOf[i]; nt += (size_t)slotsOf[i] * reqs[i].nq;
+    }
     uint32_t slots[QNT_MAX_REQS], width[QNT_MAX_REQS], passes[QNT_MAX_REQS]; size_t slot0[QNT_MAX_REQS], tgt0[QNT_MAX_REQS], q0[QNT_MAX_REQS], totalSlots = 0, totalTgts = 0, totalQ = 0;
     for (uint32_t k = 0; k < nreq; k++) {
         const infx_quant_req& Q = reqs[order[k]];
-        slots[k] = Q.group_col >= 0 ? ix->colValues[Q.group_col] + 1u : 1u;
+        slots[k] = slotsOf[order[k]];
         slot0[k] = totalSlots; tgt0[k] = totalTgts; q0[k] = totalQ;
         totalSlots += slots[k]; totalTgts += (size_t)slots[k] * Q.nq; totalQ += Q.nq;
     }
@@ -3438,16 +3449,11 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
             D.q = (const double*)W + q0[k]; D.tgt = (ls_target*)(W + oTgt) + tgt0[k]; D.tab = (uint32_t*)(W + oTab) + used;
             D.slotOut = O + 2 * slot0[k]; D.rankOut = O + 2 * totalSlots + tgt0[k];
             D.digitBits = width[k]; D.passes = passes[k]; D.nanRanks = Q.nan_ranks; D.slot0 = P.slots;
-            if (before >= 0) { const infx_quant_req& B = reqs[order[before]]; D.reuse = B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+            if (before >= 0) D.reuse = set_reuse(key[order[before]], key[order[k]]);
             words[2 * P.nreq + 1] = qs_slot_words(p, Q.nq, width[k]); words[2 * P.nreq] = D.gvals * words[2 * P.nreq + 1];
             used += (size_t)slots[k] * words[2 * P.nreq + 1]; P.slots += slots[k]; P.nreq++; before = (int32_t)k;
         }
-        // the rows' places: k_field_stats' rule and its two launch shapes
-        uint32_t inGlobal = 0, ldsWords = sts_place(2 * P.nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
-        if (inGlobal) {
-            uint32_t bigOff[2 * QNT_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(2 * P.nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
-            if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + 2 * P.nreq, ldsOff); ldsWords = bigWords; }
-        }
+        const uint32_t ldsWords = sts_place_best(2 * P.nreq, words, true, ldsOff);      // the rows' places: k_field_stats' rule and its two launch shapes
         for (uint32_t k = 0; k < P.nreq; k++) {
             P.r[k].ldsOff = ldsOff[2 * k]; P.r[k].ldsOffWhole = ldsOff[2 * k + 1];
             // counted by where the rows that make the request large lie: its groups', the whole set's without a group column
@@ -3466,12 +3472,6 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
     s->hQntRaw.assign(2 * totalSlots + totalTgts, 0u);
     DOWN(s->hQntRaw.data(), O, (2 * totalSlots + totalTgts) * 4);
     SYNC();
-    // the caller's order: request i's slots and ranks follow request i - 1's
-    size_t atSlot[QNT_MAX_REQS], atTgt[QNT_MAX_REQS], ns = 0, nt = 0;
-    for (uint32_t i = 0; i < nreq; i++) {
-        const uint32_t sl = reqs[i].group_col >= 0 ? ix->colValues[reqs[i].group_col] + 1u : 1u;
-        atSlot[i] = ns; atTgt[i] = nt; ns += sl; nt += (size_t)sl * reqs[i].nq;
-    }
     for (uint32_t k = 0; k < nreq; k++) {
         const uint32_t i = order[k];
         for (uint32_t g = 0; g < slots[k]; g++) { slots_out[atSlot[i] + g].count = s->hQntRaw[2 * (slot0[k] + g)]; slots_out[atSlot[i] + g].nan = s->hQntRaw[2 * (slot0[k] + g) + 1]; }
