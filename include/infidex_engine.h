@@ -548,6 +548,41 @@ int32_t infx_engine_group_list_rows(infx_session* s, uint32_t which, int64_t* ke
 int32_t infx_engine_group_list_totals(infx_session* s, uint32_t which, uint32_t* total_groups, uint32_t* total);
 int32_t infx_engine_group_list_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_group_list_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
+/* ---- top_groups: a field's groups ranked by size, count, min, max, sum or mean, by page (not in the reference: the semantics below are this project's) ------
+ * Request i ranks, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document:
+ *   GROUP   one dictionary code of field `group_by`, formed and named exactly as in infx_engine_field_stats and infx_engine_list_groups: any column of any
+ *           kind and ANY number of distinct values, a unique column and `field` itself included
+ *   FIELD   an int64 or a double column infx_engine_field_stats can sum (at most 128 binary digits); NULL only with by = "size"
+ *   FIGURE  of a group, by `by`: "size" its members in the SET; "count" those whose value is not a NaN; "min" / "max" infx_stats_figures' min / max, compared
+ *           by the column's sort rank (-0.0 and 0.0 tie); "sum" its sum — an int column's exact integer compared exactly, a double column's exact real sum
+ *           rounded once compared as a double, -inf < finite < +inf; "mean" its mean as a double.  A group whose figure is none or a NaN — min / max / mean
+ *           with count == 0, a sum or mean over both infinities — has NO figure
+ *   ORDER   the groups with a figure by the figure, ascending or descending; then, in BOTH directions, the groups without one; every tie by the group
+ *           column's facet tie order (infx_engine_field_stats' order of equal groups), ascending in both directions.  The order is total
+ *   ANSWER  the rows at [offset, min(offset + limit, total_groups)): per row the group's code, its members and — with a field — the figures
+ *           infx_engine_field_stats returns for that group, from the same functions; only groups with a member are rows
+ *   total_groups   the number of groups with a member (infx_engine_group_list_totals')       total   the size of the SET
+ * 1 <= limit <= 1024, 0 <= offset < 2^31; offset >= total_groups: an empty page with both totals, no error.  Nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_top_groups_error, the others answered): a syntax error, a missing or unknown
+ * group_by, an unknown `by`, a `by` other than "size" without a field, an unknown or string field, a field that is not exactly summable or a limit / offset
+ * out of range INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests (INFX_ECAPACITY).
+ * INFX_EHIP on an engine without a GPU (no CPU fallback), every refusal but the filter's already in out_status; a call that failed as a whole leaves nothing
+ * for the readers.  The masks are the session's pre-filter masks, as for infx_engine_list_documents.  Requests that share filter, field and group_by — pages,
+ * directions and `by`s of one table — share one accumulate pass.  Exact and deterministic: integer adds, minima and maxima only; the same bytes from any
+ * session, stream and rank.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_top_groups_rows copies up to cap rows (figures[r].kind is 0 throughout a request
+ * without a field) and returns the page's row count (-1 for a refused request or bad arguments); infx_engine_top_groups_totals both totals (returning the
+ * request's status); infx_engine_top_groups_error the refusal's message (its length; -1 out of range).  infx_engine_last_top_groups_stats: masks built and
+ * reused, accumulate passes, select passes (histogram launches) and kernel launches of the session's last call; infx_engine_last_top_groups_placement: the
+ * tables it accumulated in a workgroup's LDS, in a CU's whole LDS and in global memory.  infx_engine_set_list_digit_bits governs the select here too. */
+typedef struct infx_top_request { const char* filter; const char* group_by; const char* by; const char* field; int32_t ascending; uint32_t offset; uint32_t limit; } infx_top_request;
+int32_t infx_engine_top_groups(infx_session* s, uint32_t nreq, const infx_top_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_top_groups_rows(infx_session* s, uint32_t which, int32_t* group_col, uint32_t* codes, uint32_t* sizes, infx_stats_figures* figures, int32_t cap);
+int32_t infx_engine_top_groups_totals(infx_session* s, uint32_t which, uint32_t* total_groups, uint32_t* total);
+int32_t infx_engine_top_groups_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_top_groups_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches);
+int32_t infx_engine_last_top_groups_placement(infx_session* s, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

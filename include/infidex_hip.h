@@ -529,6 +529,41 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
                           uint32_t* gcodes_out, uint32_t* sizes_out, uint32_t* counts_out /* nreq */, uint32_t* group_totals_out /* nreq */,
                           uint32_t* totals_out /* nreq */);
 int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
+/* A page of a document set's GROUPS ranked by a figure of the group (not in the reference: the ranking is this project's; DESIGN.md "top_groups").
+ * Request i: the SET is infx_field_stats' — the documents whose byte in `mask` is 0 (a mask slot of this stream), or, mask = NULL, every document that is not
+ * Deleted.  A GROUP is one code of uploaded column `group_col`: any kind, ANY number of values, its facet tie order uploaded with infx_upload_group_rank (a
+ * permutation of the codes; a column re-upload voids it).  `col` is a value column with its sort rank and value table uploaded as for infx_field_stats, or
+ * -1, which allows by = INFX_TOP_BY_SIZE only.  The FIGURE of a group is, by `by`: its members in the SET (SIZE), those whose value is not a NaN (COUNT),
+ * the smallest / largest sort rank of those (MIN / MAX), the exact sum (SUM: an int column's 128-bit integer, a double column's real sum rounded once, as a
+ * double), the exact mean rounded once (MEAN).  A group whose figure is none (MIN / MAX / MEAN without a value that is not a NaN) or a NaN (+inf and -inf
+ * among its members) has NO figure.  ORDER: the groups with a member and a figure by the figure, ascending or descending, then the groups with a member and
+ * no figure, in both directions; every tie by the group rank, ascending in both directions.  The answer is the rows [offset, min(offset + limit, groups)):
+ * per row the group's code and its slot — infx_field_stats' slot of that group; without a value column `finite` holds the members, min_rank is all ones and
+ * the rest zero — in codes_out / slots_out at [i * INFX_POST_MAX_ROWS ..]; counts_out[i] rows, group_totals_out[i] the groups with a member,
+ * totals_out[i] the size of the SET.  offset >= groups: no rows, no error.  limit, offset, digit_bits and the number of requests as in infx_list_ordered.
+ * A TABLE is (mask, col, group_col); the requests of a call are taken in table order and the tables run one after another on the stream:
+ *   accumulate     one walk per table: k_field_stats with the table as its one request (infx_field_stats' slots and placement: a workgroup's LDS, a CU's
+ *                  whole LDS under 1024 threads, else global atomics; no cap on the slots), or k_top_sizes (one member counter per code) without a column
+ *   k_top_keys     per request and code the composite [class | figure | group rank] of top_select.h; counts the groups with a member and the SET
+ *   k_top_hist / k_top_pick   radix select over the composites, most significant digit first, for positions offset and offset + rows - 1 at once; the
+ *                  requests of a table advance in the same launches, each for the passes its figure's width needs
+ *   k_top_gather / k_top_page   the codes between the two composites found (composites are distinct: exactly the page), sorted in LDS, with their slots
+ * Integer adds, minima and maxima only, none decides an answer's bytes: the same bytes from any stream, grid and placement.  A mask build staged with
+ * infx_filter_masks is enqueued first, as ONE launch; one copy brings all pages back.  Works on a sharded index.  Synchronous.
+ * infx_last_top_groups_info: requests, accumulate passes (= tables walked), select passes (k_top_hist launches), kernel launches (the mask build
+ * included), and the tables accumulated in a workgroup's LDS / a CU's whole LDS / global memory of the stream's last call. */
+#define INFX_TOP_BY_SIZE 0
+#define INFX_TOP_BY_COUNT 1
+#define INFX_TOP_BY_MIN 2
+#define INFX_TOP_BY_MAX 3
+#define INFX_TOP_BY_SUM 4
+#define INFX_TOP_BY_MEAN 5
+typedef struct infx_top_req { const uint8_t* mask; int32_t col; int32_t group_col; uint32_t by; int32_t ascending; uint32_t offset; uint32_t limit; uint32_t digit_bits; uint32_t reserved; } infx_top_req;
+int32_t infx_upload_group_rank(infx_index* ix, uint32_t col, uint32_t num_values, const uint32_t* rank);
+int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs, uint32_t* codes_out, infx_stats_slot* slots_out, uint32_t* counts_out /* nreq */,
+                        uint32_t* group_totals_out /* nreq */, uint32_t* totals_out /* nreq */);
+int32_t infx_last_top_groups_info(infx_stream* s, uint32_t* requests, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches,
+                                  uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -18,6 +18,7 @@
 #include "../../../include/infidex_engine.h"
 #define XS_FN static inline
 #include "../exact_sum.h"
+#define TS_BYS 6                            // the figures infx_top_groups ranks by (INFX_TOP_BY_*), in the order of their names
 #include <chrono>
 #include <map>
 #include <list>
@@ -109,6 +110,9 @@ typedef FiguresAnswer<infx_quantile_figures> QuantAnswer;
 // One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
 // row what a ListAnswer holds, the group's code and its size
 struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
+// One request of the session's last infx_engine_top_groups: its status and message, the size of its set (total), the groups with a member, the group column,
+// whether it had a field, its page: per row the group's code, its members and — with a field — its figures
+struct TopAnswer : Answer { uint32_t totalGroups = 0; int32_t groupCol = -1; bool hasField = false; std::vector<uint32_t> codes, sizes; std::vector<infx_stats_figures> figures; };
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskUse masks; };
 struct infx_session {
@@ -134,6 +138,9 @@ struct infx_session {
     struct Qnt : LastCall<QuantAnswer> { uint32_t passes = 0, launches = 0, place[3] = {0, 0, 0}; } qnt; int32_t qntDigitBits = 0;
     // infx_engine_list_groups: head passes, histogram passes, kernel launches (the digit width is lstDigitBits)
     struct Grp : LastCall<GroupListAnswer> { uint32_t heads = 0, passes = 0, launches = 0; } grp;
+    // infx_engine_top_groups: accumulate passes, select passes, kernel launches, tables accumulated in a workgroup's LDS / a CU's whole LDS / global memory
+    // (the digit width is lstDigitBits)
+    struct Top : LastCall<TopAnswer> { uint32_t accumulates = 0, passes = 0, launches = 0, place[3] = {0, 0, 0}; } top;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -264,6 +271,7 @@ struct infx_engine {
     // non-indexed document fields (DocumentFields) as dictionary-encoded columns + compiled Infiscript filters (config 5)
     std::vector<filt::Column> columns; std::mutex filterMu; std::unordered_map<std::string, CompiledFilter> filters;
     std::vector<infx_filter*> retiredFilters;     // compiled against an older column set (a session's stream may still point at one): freed with the engine
+    std::vector<uint8_t> tieRanked;               // per column: its facet tie order (Column.rank) is on the device (infx_engine_top_groups, uploaded on first use)
     std::vector<uint8_t> sortRanked;              // per column: its sort rank is on the device (infx_engine_set_sort, built on first use)
     // per column, for infx_engine_range_facets (built on first use, under filterMu): the lowest code of every sort rank, in rank order, and whether rank 0 is a NaN
     struct RangeIndex { bool ok = false; uint32_t nanRanks = 0; std::vector<uint32_t> codeOfRank; };
@@ -2456,6 +2464,7 @@ int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, i
         std::lock_guard<std::mutex> lk(e->filterMu);
         e->columns[at] = std::move(c);
         if (at < e->sortRanked.size()) e->sortRanked[at] = 0;
+        if (at < e->tieRanked.size()) e->tieRanked[at] = 0;
         if (at < e->rangeIndex.size()) e->rangeIndex[at] = infx_engine::RangeIndex();
         if (at < e->statsIndex.size()) e->statsIndex[at] = infx_engine::StatsIndex();
     } else e->columns.push_back(std::move(c));
@@ -3770,6 +3779,114 @@ int32_t infx_engine_group_list_error(infx_session* S, uint32_t which, char* out,
 int32_t infx_engine_last_group_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->grp.masks.built}, {masks_reused, S->grp.masks.reused}, {head_passes, S->grp.heads}, {hist_passes, S->grp.passes}, {launches, S->grp.launches}});
+}
+
+// ---- top_groups: the groups of a field ranked by their size or by the count, min, max, sum or mean of a second field, by page (not in the reference) --------
+// Per request, as infx_engine_field_stats: the field (if any) to its column, its sort rank and its value table; group_by to its column — any kind, any number
+// of values — whose facet tie order (Column.rank) is uploaded on first use; the filter through the filter cache and its mask through the session's mask cache.
+// infx_top_groups then accumulates one slot per group code, ranks the slots by order-preserving composites and selects the page; the engine turns the page's
+// slots into figures with stats_figures, the reader of infx_engine_field_stats.
+static const char* const TOP_BY_NAMES[TS_BYS] = {"size", "count", "min", "max", "sum", "mean"};
+// Column col's facet tie order is on the device.  Caller holds e->filterMu.
+static int32_t group_rank_on_device(infx_engine* e, uint32_t col) {
+    if (e->tieRanked.size() < e->columns.size()) e->tieRanked.resize(e->columns.size(), 0);
+    if (e->tieRanked[col]) return INFX_OK;
+    const filt::Column& c = e->columns[col];
+    int32_t rc = infx_upload_group_rank(e->dev, col, (uint32_t)c.rank.size(), c.rank.data());
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    e->tieRanked[col] = 1;
+    return INFX_OK;
+}
+int32_t infx_engine_top_groups(infx_session* S, uint32_t nreq, const infx_top_request* reqs, int32_t* out_status) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol, by; col.fill(-1); gcol.fill(-1); by.fill(-1);
+    std::vector<infx_top_req> dr; std::vector<uint32_t> codes, counts, groups, totals; std::vector<infx_stats_slot> slots;
+    return set_call(S, &infx_session::top, "top_groups", "top_groups requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
+            const infx_top_request& Q = reqs[i];
+            if (const char* bad = page_problem(Q.limit, Q.offset)) return F.refuse(i, INFX_EINVAL, bad);
+            if (!Q.group_by) return F.refuse(i, INFX_EINVAL, "top_groups needs a group_by field");
+            if ((gcol[i] = column_named(S->e, Q.group_by)) < 0) return F.refuse(i, INFX_EINVAL, std::string("top_groups: no group_by field named '") + Q.group_by + "'");
+            for (int b = 0; Q.by && b < TS_BYS; b++) if (!std::strcmp(Q.by, TOP_BY_NAMES[b])) by[i] = b;
+            if (by[i] < 0) return F.refuse(i, INFX_EINVAL, std::string("top_groups: by is one of size, count, min, max, sum, mean, not '") + (Q.by ? Q.by : "") + "'");
+            if (!Q.field) {
+                if (by[i] != INFX_TOP_BY_SIZE) F.refuse(i, INFX_EINVAL, std::string("top_groups: by = '") + Q.by + "' needs a field");
+                return;
+            }
+            std::string why; int32_t g = -1;
+            int32_t rc = numeric_field_check(S->e, "top_groups", "figures", Q.field, nullptr, &col[i], &g, &why);
+            if (!rc && !stats_index(S->e, (uint32_t)col[i]).summable) {
+                rc = INFX_EINVAL;
+                why = std::string("top_groups: the finite values of field '") + Q.field + "' span more than 128 binary digits; they cannot be summed exactly";
+            }
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) {
+            infx_engine* e = S->e;
+            if (col[i] >= 0) {
+                const infx_engine::RangeIndex* X = nullptr;
+                { const int32_t rc = range_index(e, (uint32_t)col[i], &X); if (rc) return F.refuse(i, rc, g_eerr); }      // (the sort rank, for min / max)
+                infx_engine::StatsIndex& V = stats_index(e, (uint32_t)col[i]);
+                if (!V.uploaded) {
+                    const int32_t rc = infx_upload_column_values(e->dev, (uint32_t)col[i], (uint32_t)V.bits.size(), V.bits.data(), V.kind, V.sc.scale, V.sc.nlimbs);
+                    if (rc) return F.refuse(i, rc, infx_last_error());
+                    V.uploaded = true;
+                }
+            }
+            { const int32_t rc = group_rank_on_device(e, (uint32_t)gcol[i]); if (rc) return F.refuse(i, rc, g_eerr); }
+            F.filter(i, reqs[i].filter);
+        },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_top_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.by = (uint32_t)by[i]; R.ascending = reqs[i].ascending ? 1 : 0;
+                R.offset = reqs[i].offset; R.limit = reqs[i].limit; R.digit_bits = (uint32_t)S->lstDigitBits;
+                dr.push_back(R);
+            }
+            const size_t m = std::max<size_t>(dr.size(), 1);
+            codes.assign(m * INFX_POST_MAX_ROWS, 0); slots.assign(m * INFX_POST_MAX_ROWS, infx_stats_slot()); counts.assign(m, 0); groups.assign(m, 0); totals.assign(m, 0);
+            return infx_top_groups(S->stream, (uint32_t)dr.size(), dr.data(), codes.data(), slots.data(), counts.data(), groups.data(), totals.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_top_groups_info(S->stream, nullptr, &S->top.accumulates, &S->top.passes, &S->top.launches, &S->top.place[0], &S->top.place[1], &S->top.place[2]);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                TopAnswer& A = S->top.ans[F.who[j]];
+                const size_t c = std::min<size_t>(counts[j], dr[j].limit), at = j * INFX_POST_MAX_ROWS;
+                A.total = totals[j]; A.totalGroups = groups[j]; A.groupCol = dr[j].group_col; A.hasField = dr[j].col >= 0;
+                A.codes.assign(codes.begin() + at, codes.begin() + at + c);
+                for (size_t r = 0; r < c; r++) {
+                    const infx_stats_slot& sl = slots[at + r];
+                    A.sizes.push_back(sl.finite + sl.nan + sl.pinf + sl.ninf);
+                    A.figures.push_back(A.hasField ? stats_figures(sl, e->statsIndex[dr[j].col], e->columns[dr[j].col], e->rangeIndex[dr[j].col]) : infx_stats_figures());
+                }
+            }
+        });
+}
+// request `which` of the session's last infx_engine_top_groups: up to cap rows — the group's code in column *group_col, its members, its figures (kind 0
+// throughout a request without a field); returns the page's row count, -1 on error (also for a refused request)
+int32_t infx_engine_top_groups_rows(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, uint32_t* sizes, infx_stats_figures* figures, int32_t cap) {
+    const TopAnswer* A = answer_at(S ? &S->top.ans : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!codes || !sizes || !figures))) return -1;
+    const size_t c = std::min<size_t>(A->codes.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(codes, A->codes.data(), c * 4); std::memcpy(sizes, A->sizes.data(), c * 4); std::memcpy(figures, A->figures.data(), c * sizeof(infx_stats_figures)); }
+    if (group_col) *group_col = A->groupCol;
+    return (int32_t)A->codes.size();
+}
+// the number of groups with a member and the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_top_groups_totals(infx_session* S, uint32_t which, uint32_t* total_groups, uint32_t* total) {
+    const TopAnswer* A = answer_at(S ? &S->top.ans : nullptr, which);
+    if (A && total_groups) *total_groups = A->totalGroups;
+    return answer_total(total_groups ? A : nullptr, total, "no such request in the session's last top_groups call");
+}
+int32_t infx_engine_top_groups_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->top.ans : nullptr, which), out, cap); }
+int32_t infx_engine_last_top_groups_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->top.masks.built}, {masks_reused, S->top.masks.reused}, {accumulate_passes, S->top.accumulates}, {select_passes, S->top.passes}, {launches, S->top.launches}});
+}
+int32_t infx_engine_last_top_groups_placement(infx_session* S, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{small_lds, S->top.place[0]}, {big_lds, S->top.place[1]}, {in_global, S->top.place[2]}});
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

@@ -99,6 +99,7 @@ struct infx_index {
     int32_t* dFirstLive = nullptr; uint32_t firstLiveCap = 0; const int32_t* firstLive = nullptr;      // first live document of each document's key, by GLOBAL internal id (infx_set_first_live; nullptr: keys are unique)
     const uint32_t* colCodes[FILT_MAXCOL] = {}; uint32_t colValues[FILT_MAXCOL] = {}; uint32_t colDocs[FILT_MAXCOL] = {}; uint32_t colCap[FILT_MAXCOL] = {};   // device-resident columns (infx_upload_column)
     const uint32_t* colRank[FILT_MAXCOL] = {}; uint32_t colRankCap[FILT_MAXCOL] = {}; bool colRankOk[FILT_MAXCOL] = {};     // sort ranks of their codes (infx_upload_sort_rank); a column re-upload voids its rank
+    const uint32_t* colTie[FILT_MAXCOL] = {}; uint32_t colTieCap[FILT_MAXCOL] = {}; bool colTieOk[FILT_MAXCOL] = {};        // facet tie order of their codes (infx_upload_group_rank, for infx_top_groups); a column re-upload voids it
     // raw values of their codes with the scale field_stats sums them at (infx_upload_column_values); a column re-upload voids them too
     const uint64_t* colBits[FILT_MAXCOL] = {}; uint32_t colBitsCap[FILT_MAXCOL] = {}; bool colBitsOk[FILT_MAXCOL] = {}; int32_t colKind[FILT_MAXCOL] = {}, colScale[FILT_MAXCOL] = {}; uint32_t colLimbs[FILT_MAXCOL] = {};
     std::vector<uint64_t> hPsOff;
@@ -266,6 +267,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
 #include "groups.hip.inc"
+#include "top_groups.hip.inc"
 #include "quantiles.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
@@ -373,6 +375,9 @@ struct infx_stream {
     void *dQntWs = nullptr, *dQntOut = nullptr; size_t capQntWs = 0, capQntOut = 0; std::vector<uint32_t> hQntRaw;      // infx_field_quantiles: quantiles, targets and one pass's rows; counts and ranks; their host copy
     uint32_t lastQntInfo[6] = {0, 0, 0, 0, 0, 0};              // of the last infx_field_quantiles: requests, histogram passes, launches, digit width, request-passes with rows in LDS / in global memory
     void* dGrpWs = nullptr; size_t capGrpWs = 0;               // infx_list_grouped: a spec's head table and heads mask; per request the page's sorted codes, rows, group codes and sizes
+    // infx_top_groups: [a table's slots and smallest ranks | its requests' composites | histograms | select states], the requests' pages, their host copy
+    void* dTopWs = nullptr; size_t capTopWs = 0; void* dTopOut = nullptr; size_t capTopOut = 0; std::vector<uint32_t> hTopRaw;
+    uint32_t lastTopInfo[7] = {0, 0, 0, 0, 0, 0, 0};          // of the last infx_top_groups: requests, accumulate passes, select passes, launches, tables in a workgroup's LDS / a CU's whole LDS / global memory
     uint32_t lastGrpHeads = 0, lastGrpPasses = 0, lastGrpLaunches = 0;      // head passes, histogram passes and kernel launches of the last infx_list_grouped
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
@@ -1312,7 +1317,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut, s->dTopWs, s->dTopOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -2731,7 +2736,7 @@ int32_t infx_upload_column(infx_index* ix, uint32_t col, uint32_t total_docs, co
     uint32_t* d = const_cast<uint32_t*>(ix->colCodes[col]);
     if (!d || ix->colCap[col] < total_docs) { HIPCHK(dalloc(ix, &d, (size_t)total_docs + 1)); ix->colCap[col] = total_docs; }     // a re-upload reuses the column's buffer
     if (total_docs) HIPCHK(hipMemcpy(d, codes, (size_t)total_docs * 4, hipMemcpyHostToDevice));
-    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false; ix->colBitsOk[col] = false;
+    ix->colCodes[col] = d; ix->colValues[col] = num_values; ix->colDocs[col] = total_docs; ix->colRankOk[col] = false; ix->colBitsOk[col] = false; ix->colTieOk[col] = false;
     return INFX_OK;
 }
 // a program must be a well-formed postfix expression whose stack fits the kernels' 32 slots, over uploaded columns, with its leaf tables in range
@@ -2815,6 +2820,22 @@ int32_t infx_upload_sort_rank(infx_index* ix, uint32_t col, uint32_t num_values,
     if (!d || ix->colRankCap[col] < num_values) { HIPCHK(dalloc(ix, &d, (size_t)num_values)); ix->colRankCap[col] = num_values; }
     if (num_values) HIPCHK(hipMemcpy(d, rank, (size_t)num_values * 4, hipMemcpyHostToDevice));
     ix->colRank[col] = d; ix->colRankOk[col] = true;
+    return INFX_OK;
+}
+// the facet tie order of a column's codes — a permutation of them — for infx_top_groups
+int32_t infx_upload_group_rank(infx_index* ix, uint32_t col, uint32_t num_values, const uint32_t* rank) {
+    if (!ix || col >= FILT_MAXCOL || (num_values && !rank)) return fail(INFX_EINVAL, "bad group-rank arguments%s");
+    if (!ix->colCodes[col] || num_values != ix->colValues[col]) return fail(INFX_EINVAL, "a group rank needs one entry per distinct value of an uploaded column%s");
+    {   // the select relies on distinct composites: every rank below num_values, none twice
+        std::vector<uint8_t> seen(num_values, 0);
+        for (uint32_t i = 0; i < num_values; i++) { if (rank[i] >= num_values || seen[rank[i]]) return fail(INFX_EINVAL, "a group rank is a permutation of the column's codes%s"); seen[rank[i]] = 1; }
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());                      // exclusive call, as infx_upload_column
+    uint32_t* d = const_cast<uint32_t*>(ix->colTie[col]);
+    if (!d || ix->colTieCap[col] < num_values) { HIPCHK(dalloc(ix, &d, (size_t)num_values)); ix->colTieCap[col] = num_values; }
+    if (num_values) HIPCHK(hipMemcpy(d, rank, (size_t)num_values * 4, hipMemcpyHostToDevice));
+    ix->colTie[col] = d; ix->colTieOk[col] = true;
     return INFX_OK;
 }
 // the raw values of a column's codes for infx_field_stats, with the scale and width the caller found for them (exact_sum.h)
@@ -3595,6 +3616,135 @@ int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32
     if (head_passes) *head_passes = s->lastGrpHeads;
     if (hist_passes) *hist_passes = s->lastGrpPasses;
     if (launches) *launches = s->lastGrpLaunches;
+    return INFX_OK;
+}
+// ---- top_groups: a page of a document set's groups, ranked by a figure of the group (top_groups.hip.inc) ----
+int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs, uint32_t* codes_out, infx_stats_slot* slots_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
+    if (!s || (nreq && (!reqs || !codes_out || !slots_out || !counts_out || !group_totals_out || !totals_out))) return fail(INFX_EINVAL, "bad top-groups arguments%s");
+    std::fill(s->lastTopInfo, s->lastTopInfo + 7, 0u);
+    if (nreq > TOP_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 top-groups requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_top_req& Q = reqs[i];
+        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "top-groups request"); if (rc_) return rc_; }
+        { int32_t rc_ = check_group_column(ix, Q.group_col, "top-groups request"); if (rc_) return rc_; }
+        if (!ix->colTieOk[Q.group_col]) return fail(INFX_EINVAL, "the top-groups request's group rank was not uploaded%s");
+        if (Q.by >= TS_BYS) return fail(INFX_EINVAL, "a top-groups request ranks by size, count, min, max, sum or mean (0 .. 5)%s");
+        if (Q.col < 0 && Q.by != TS_BY_SIZE) return fail(INFX_EINVAL, "without a value column a top-groups request ranks by size%s");
+        if (Q.col >= 0 && !ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the top-groups request's value table was not uploaded%s");
+    }
+    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastTopInfo[3]); if (rc_) return rc_; }
+    s->lastTopInfo[0] = nreq;
+    if (!nreq) return INFX_OK;
+    uint32_t order[TOP_MAX_REQS]; SetKey key[TOP_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
+    set_order(nreq, key, order);
+    auto same_table = [&](uint32_t a, uint32_t b) { return key[a].mask == key[b].mask && key[a].col == key[b].col && key[a].gcol == key[b].gcol; };
+    // per request (device order) what its select needs; per table the words of its slots and smallest ranks and of its requests' composites
+    uint32_t figWords[TOP_MAX_REQS], passes[TOP_MAX_REQS]; size_t keyOff[TOP_MAX_REQS], tabWords = 0, keyWords = 0;
+    for (uint32_t k0 = 0; k0 < nreq;) {
+        const infx_top_req& Q = reqs[order[k0]];
+        const size_t gv = ix->colValues[Q.group_col];
+        tabWords = std::max(tabWords, Q.col >= 0 ? gv * (sts_stride(ix->colLimbs[Q.col]) + 1u) : gv);
+        size_t kw = 0; uint32_t k1 = k0;
+        for (; k1 < nreq && same_table(order[k0], order[k1]); k1++) {
+            const infx_top_req& R = reqs[order[k1]];
+            figWords[k1] = ts_fig_words(R.by, R.col >= 0 ? ix->colKind[R.col] : XS_KIND_INT); passes[k1] = ts_passes(figWords[k1], R.digit_bits);
+            keyOff[k1] = kw; kw += gv * ts_key_words(figWords[k1]);
+        }
+        keyWords = std::max(keyWords, kw); k0 = k1;
+    }
+    const size_t stBytes = (sizeof(DevTopState) + 63) & ~(size_t)63;
+    const size_t oKeys = (tabWords * 4 + 63) & ~(size_t)63, oHist = (oKeys + keyWords * 4 + 63) & ~(size_t)63, oState = oHist + (size_t)nreq * 2 * LS_MAX_BINS * 4;
+    GROW(s->dTopWs, s->capTopWs, oState + nreq * stBytes);
+    GROW(s->dTopOut, s->capTopOut, (size_t)nreq * TOP_OUT_WORDS * 4);
+    char* W = (char*)s->dTopWs; uint32_t* O = (uint32_t*)s->dTopOut;
+    HIPCHK(hipMemsetAsync(W + oHist, 0, oState + nreq * stBytes - oHist, s->st));
+    HIPCHK(hipMemsetAsync(O, 0, (size_t)nreq * TOP_OUT_WORDS * 4, s->st));
+    s->unsynced = true;
+    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (as infx_field_stats)
+    for (uint32_t k0 = 0; k0 < nreq;) {
+        uint32_t k1 = k0; while (k1 < nreq && same_table(order[k0], order[k1])) k1++;
+        const infx_top_req& Q = reqs[order[k0]];
+        const uint32_t gv = ix->colValues[Q.group_col], nl = Q.col >= 0 ? ix->colLimbs[Q.col] : 0u, stride = Q.col >= 0 ? sts_stride(nl) : 1u;
+        uint32_t* slots = (uint32_t*)W; uint32_t* lo = slots + (size_t)gv * stride;
+        const uint8_t* mask = Q.mask ? Q.mask : ix->d.deleted;
+        // 1. accumulate: the table's slots, placed as field_stats places one request's
+        if (gv) HIPCHK(hipMemsetAsync(slots, 0, (size_t)gv * stride * 4, s->st));
+        if (gv && Q.col >= 0) HIPCHK(hipMemsetAsync(lo, 0xFF, (size_t)gv * 4, s->st));
+        if (n > 0 && gv) {
+            const uint32_t words = gv * stride; uint32_t ldsOff = 0;
+            const uint32_t ldsWords = (uint64_t)gv * stride > STS_BIG_LDS_WORDS ? (ldsOff = STS_GLOBAL, 0u) : sts_place_best(1, &words, !noBig, &ldsOff);
+            int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
+            if (Q.col >= 0) {
+                DevStatsCall P{}; P.nreq = 1;
+                DevStatsReq& D = P.r[0];
+                D.mask = mask; D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.bits = ix->colBits[Q.col]; D.nvals = ix->colValues[Q.col];
+                D.kind = ix->colKind[Q.col]; D.scale = ix->colScale[Q.col]; D.nlimbs = nl;
+                D.gcodes = ix->colCodes[Q.group_col]; D.gvals = gv; D.out = slots; D.lo = lo; D.ldsOff = ldsOff;
+                HIPCHK(lds_limit((const void*)k_field_stats, ix->cfg.device, (size_t)ldsWords * 4));
+                k_field_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
+            } else {
+                HIPCHK(lds_limit((const void*)k_top_sizes, ix->cfg.device, (size_t)ldsWords * 4));
+                k_top_sizes<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(mask, ix->colCodes[Q.group_col], gv, slots, ldsOff != STS_GLOBAL ? 1u : 0u, n);
+            }
+            HIPCHK(hipGetLastError());
+            s->lastTopInfo[1]++; s->lastTopInfo[3]++;
+            s->lastTopInfo[ldsOff == STS_GLOBAL ? 6 : ldsWords <= STS_LDS_WORDS ? 4 : 5]++;
+        }
+        // 2. keys; 3. select: the requests that still have a pass, in one launch each for histogram and pick; 4. the pages
+        DevTopCall P{}; P.nreq = k1 - k0;
+        uint32_t maxPasses = 0;
+        for (uint32_t k = k0; k < k1; k++) {
+            const infx_top_req& R = reqs[order[k]];
+            DevTopReq& D = P.r[k - k0];
+            D.slots = slots; D.lo = Q.col >= 0 ? lo : nullptr; D.tie = ix->colTie[Q.group_col];
+            D.keys = (uint32_t*)(W + oKeys) + keyOff[k]; D.hist = (uint32_t*)(W + oHist) + (size_t)k * 2 * LS_MAX_BINS; D.st = (DevTopState*)(W + oState + k * stBytes);
+            D.out = O + (size_t)k * TOP_OUT_WORDS;
+            D.gvals = gv; D.stride = stride; D.nlimbs = nl; D.by = R.by; D.kind = Q.col >= 0 ? ix->colKind[Q.col] : XS_KIND_INT; D.scale = Q.col >= 0 ? ix->colScale[Q.col] : 0;
+            D.ascending = R.ascending ? 1u : 0u; D.offset = R.offset; D.limit = R.limit; D.digitBits = R.digit_bits; D.figWords = figWords[k]; D.passes = passes[k];
+            maxPasses = std::max(maxPasses, passes[k]);
+        }
+        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(FCM_MAXGRID, ((int64_t)gv + TOP_THREADS - 1) / TOP_THREADS));
+        k_top_keys<<<dim3(blocks, P.nreq), TOP_THREADS, 0, s->st>>>(P);
+        s->lastTopInfo[3]++;
+        for (uint32_t p = 0; p < maxPasses; p++) {
+            DevTopCall A{}; uint32_t bits = LS_MIN_DIGIT_BITS;
+            for (uint32_t q = 0; q < P.nreq; q++) if (P.r[q].passes > p) { A.r[A.nreq++] = P.r[q]; bits = std::max(bits, P.r[q].digitBits); }
+            k_top_hist<<<dim3(blocks, A.nreq), TOP_THREADS, ((size_t)2 << bits) * 4, s->st>>>(A, p);
+            k_top_pick<<<A.nreq, TOP_THREADS, 0, s->st>>>(A, p);
+            s->lastTopInfo[2]++; s->lastTopInfo[3] += 2;
+        }
+        k_top_gather<<<dim3(blocks, P.nreq), TOP_THREADS, 0, s->st>>>(P);
+        k_top_page<<<P.nreq, LST_SORT_THREADS, 0, s->st>>>(P);
+        HIPCHK(hipGetLastError());
+        s->lastTopInfo[3] += 2;
+        k0 = k1;
+    }
+    s->hTopRaw.assign((size_t)nreq * TOP_OUT_WORDS, 0u);
+    DOWN(s->hTopRaw.data(), O, (size_t)nreq * TOP_OUT_WORDS * 4);
+    SYNC();
+    for (uint32_t k = 0; k < nreq; k++) {
+        const uint32_t i = order[k]; const uint32_t* w = s->hTopRaw.data() + (size_t)k * TOP_OUT_WORDS;
+        const uint32_t rows = std::min<uint32_t>(w[0], INFX_POST_MAX_ROWS);
+        counts_out[i] = rows; group_totals_out[i] = w[1]; totals_out[i] = w[2];
+        for (uint32_t r = 0; r < rows; r++) {
+            codes_out[(size_t)i * INFX_POST_MAX_ROWS + r] = w[TOP_OUT_HEAD + r];
+            const uint32_t* v = w + TOP_OUT_HEAD + INFX_POST_MAX_ROWS + (size_t)r * TOP_SLOT_WORDS;
+            infx_stats_slot& S = slots_out[(size_t)i * INFX_POST_MAX_ROWS + r];
+            S.finite = v[0]; S.nan = v[1]; S.pinf = v[2]; S.ninf = v[3]; S.max_rank = v[4]; S.min_rank = v[5];
+            for (uint32_t j = 0; j < INFX_STATS_MAX_LIMBS; j++) std::memcpy(&S.sum[j], v + STS_HEAD + 2 * j, 8);
+        }
+    }
+    return INFX_OK;
+}
+int32_t infx_last_top_groups_info(infx_stream* s, uint32_t* requests, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    uint32_t* out[7] = {requests, accumulate_passes, select_passes, launches, small_lds, big_lds, in_global};
+    for (int i = 0; i < 7; i++) if (out[i]) *out[i] = s->lastTopInfo[i];
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

@@ -196,6 +196,37 @@ class GroupListing:        # SearchEngine.list_groups: one per request
 
 
 @dataclass
+class TopGroupsRequest:    # SearchEngine.top_groups: one page of one ranking of a field's groups
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    group_by: Optional[str] = None      # field whose values form the groups: any column, any number of distinct values (required)
+    by: str = "size"                    # the figure that ranks the groups: "size", "count", "min", "max", "sum" or "mean"
+    field: Optional[str] = None         # an int64 or a double column field_stats can sum; None only with by="size"
+    ascending: bool = False             # False: largest figure first; groups without a figure come last and ties go by the group's value in both directions
+    offset: int = 0                     # position of the page's first row in the ranking, 0 <= offset < 2**31
+    limit: int = 20                     # rows of the page, 1 .. 1024
+
+
+@dataclass
+class GroupRow:            # SearchEngine.top_groups: one group of one page
+    value: str = ""                                           # the group's value of the group_by field as text (GroupStats.value)
+    size: int = 0                                             # members of the group among the documents the filter accepts
+    count: Optional[int] = None                               # GroupStats' figures of the group for the request's field, from the same functions;
+    nan: Optional[int] = None                                 # None without a field
+    min: Optional[object] = None
+    max: Optional[object] = None
+    sum: Optional[object] = None
+    mean: Optional[float] = None
+
+
+@dataclass
+class TopGroups:           # SearchEngine.top_groups: one per request
+    groups: list = _dc_field(default_factory=list)            # [GroupRow] of the page, in ranking order
+    total_groups: int = 0                                     # groups with a member (GroupListing.total_groups of the same filter and group_by)
+    total: int = 0                                            # live documents the filter accepts (Listing.total of the same filter)
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+@dataclass
 class RangeRequest:        # SearchEngine.range_facets: the buckets of one numeric field over one filter
     filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
     field: str = ""                     # an int64 or a double column
@@ -302,6 +333,10 @@ class _ListReq(C.Structure):
 
 class _GroupListReq(C.Structure):     # infx_group_list_request (include/infidex_engine.h)
     _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class _TopReq(C.Structure):           # infx_top_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("by", C.c_char_p), ("field", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
 
 
 class _Cfg(C.Structure):
@@ -591,6 +626,27 @@ class SearchEngine:
     def last_group_list_stats(self, session=None):
         """(masks built, masks reused, head passes, histogram passes, kernel launches) of the session's last list_groups device call."""
         return _u32_stats(self, "infx_engine_last_group_list_stats", session.h if session is not None else self._default_session(), 5)
+
+    def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20, session=None):
+        """A field's groups ranked by a figure and cut to a page (not in the reference): over the documents list_documents(filter) lists, one row per value
+        of group_by (any column, any number of distinct values — field_stats stops at 4096 — a unique column and `field` itself included) that has a member,
+        ranked by `by`: "size" the group's members, or for `field` (an int64 or double column field_stats can sum) "count", "min", "max", "sum" or "mean" —
+        GroupStats' figures, compared as the caller sees them (an int sum exactly, min / max as Query.sort_by compares values).  Groups without a figure (min /
+        max / mean with count == 0, a sum or mean over both infinities) come after all others in BOTH directions; every tie goes by the group's value
+        ascending (field_stats' order of equal groups) in both directions, so pages never overlap or skip.  1 <= limit <= 1024, 0 <= offset < 2**31.  Returns
+        TopGroups(groups, total_groups, total, error): groups the GroupRow(value, size, count, nan, min, max, sum, mean) of rows [offset, offset + limit) —
+        the six figures exactly what field_stats returns for that group, None without a field.  A sequence of TopGroupsRequest as first argument -> a list of
+        TopGroups, sixteen requests per device call; pages, directions and `by`s of one (filter, field, group_by) in one call share one pass over the
+        documents.  A refused request gets `error` set, alone.  Exact and deterministic; needs a GPU."""
+        return _top_groups(self, session.h if session is not None else self._default_session(), filter, group_by, by, field, ascending, offset, limit)
+
+    def last_top_groups_stats(self, session=None):
+        """(masks built, masks reused, accumulate passes, select passes, kernel launches) of the session's last top_groups device call."""
+        return _u32_stats(self, "infx_engine_last_top_groups_stats", session.h if session is not None else self._default_session(), 5)
+
+    def last_top_groups_placement(self, session=None):
+        """(tables accumulated in a workgroup's LDS, in a CU's whole LDS, in global memory) of the session's last top_groups device call."""
+        return _u32_stats(self, "infx_engine_last_top_groups_placement", session.h if session is not None else self._default_session(), 3)
 
     def range_facets(self, filter=None, field=None, edges=(), session=None):
         """Range facets (not in the reference): over the documents list_documents(filter) lists — not Deleted, their own fields accepted by `filter`; None:
@@ -962,6 +1018,18 @@ class Session:
     def last_group_list_stats(self):
         """SearchEngine.last_group_list_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_group_list_stats", self.h, 5)
+
+    def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20):
+        """SearchEngine.top_groups on this session (its mask cache holds the filters' masks)."""
+        return _top_groups(self.engine, self.h, filter, group_by, by, field, ascending, offset, limit)
+
+    def last_top_groups_stats(self):
+        """SearchEngine.last_top_groups_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_top_groups_stats", self.h, 5)
+
+    def last_top_groups_placement(self):
+        """SearchEngine.last_top_groups_placement of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_top_groups_placement", self.h, 3)
 
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets on this session (its mask cache holds the filters' masks)."""
@@ -1401,6 +1469,35 @@ def _field_stats(engine, sh, filter, field, group_by):
     return _per_request(engine, sh, "infx_engine_field_stats", "infx_engine_field_stats_error", _StatsReq,
                         [StatsRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
                         lambda r, msg: FieldStats(error=msg))
+
+
+def _top_groups(engine, sh, filter, group_by, by, field, ascending, offset, limit):
+    """infx_engine_top_groups on session handle sh: a TopGroups for one request (given by its parts), a list of them for a sequence of TopGroupsRequest."""
+    def pack(r):
+        off, lim = int(r.offset), int(r.limit)
+        # out of the C fields' range: passed as values the engine refuses for this request alone
+        return _TopReq(*[None if x is None else str(x).encode() for x in (r.filter, r.group_by, r.by, r.field)], 1 if r.ascending else 0,
+                       off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+
+    def read(i, r):
+        groups = C.c_uint32(0); tot = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_top_groups_totals(sh, i, C.byref(groups), C.byref(tot)))
+        cap = max(1, min(int(r.limit), 1024))                # (an answered request's limit is in range)
+        col = C.c_int32(-1); codes = np.zeros(cap, np.uint32); sizes = np.zeros(cap, np.uint32); figs = (_StatsFigures * cap)()
+        m = engine.L.infx_engine_top_groups_rows(sh, i, C.byref(col), _p(codes, C.c_uint32), _p(sizes, C.c_uint32), figs, cap)
+        if m < 0:
+            engine._check(1)
+        rows = []
+        vb = C.create_string_buffer(1024)
+        for code, size, f in zip(codes[:m].tolist(), sizes[:m].tolist(), np.frombuffer(figs, _STATS_FIGURES)[:m].tolist()):
+            engine.L.infx_engine_column_value(engine.h, col.value, code, vb, 1024)
+            rows.append(GroupRow(vb.value.decode(), size, *(_stats_figures(f) if r.field is not None else ())))
+        return TopGroups(rows, int(groups.value), int(tot.value), None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_top_groups", "infx_engine_top_groups_error", _TopReq,
+                        [TopGroupsRequest(filter, group_by, by, field, ascending, offset, limit)] if single else list(filter), single, pack, read,
+                        lambda r, msg: TopGroups(error=msg))
 
 
 def _quantile_tuple(q):

@@ -725,6 +725,14 @@ class ShardedSearcher:
     def last_group_list_stats(self):
         return self.sessions[0].s.last_group_list_stats()
 
+    def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20):
+        """SearchEngine.top_groups: like list_groups, every rank accumulates, ranks and selects the page over the whole columns with the global Deleted
+        flags on its own GPU and gets the same answer — nothing is exchanged."""
+        return self.sessions[0].s.top_groups(filter, group_by, by, field, ascending, offset, limit)
+
+    def last_top_groups_stats(self):
+        return self.sessions[0].s.last_top_groups_stats()
+
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets: like list_documents, every rank counts over the whole columns with the global Deleted flags on its own GPU and gets
         the same answer — nothing is exchanged."""
