@@ -163,7 +163,18 @@ typedef struct infx_query {
 
 typedef struct infx_hit { int32_t doc; float score; } infx_hit;   /* doc = global internal id; key via infx_upload_docs */
 
-/* Per-query class counts of the candidate tiers on THIS shard (sum over shards before infx_stage1_select when sharded). */
+/* Per-query class counts of the candidate tiers on THIS shard (sum over shards before infx_stage1_select when sharded).
+ * A document is counted when a candidate-generating list of the query holds it and its accumulated score is > 0 (a term with idf <= 0 adds nothing; a
+ * document hit by such terms alone is no row and is not counted).  Deleted documents ARE counted: the reference's tiers see them.  c[] by infx_query.mode:
+ *   INFX_MODE_AND     c[0..15], index = bit 0: the document holds every INFX_ROLE_AND term and the INFX_ROLE_LOWEST one (Tier 0)
+ *                                     | bit 1: it holds every INFX_ROLE_AND term and n_and >= 3 (Tier 1; contains Tier 0)
+ *                                     | bit 2: it is in the list of INFX_ROLE_S1 | bit 3: ... of INFX_ROLE_S2.
+ *                     Only documents of S1 u S2 are counted (index >= 4): Tier 0 and Tier 1 lie inside S1, the term of the highest idf.
+ *   INFX_MODE_DISJ    c[r], r < 128: documents whose smallest infx_term.rank among the INFX_ROLE_ELIGIBLE / INFX_ROLE_LOWQ terms that hold them is r
+ *                     (localCount of SelectCandidatesDisjunctive per term).  Documents of the query's pre-"seen" set (prefix_set) are not counted.
+ *   INFX_MODE_PREFIX  c[1]: documents of the prefix DocSet with a score > 0.
+ * Every other entry is 0 (c[128..135] are reserved).  infx_stage1_select reads the tier rules off these counts: which tiers the reference would have
+ * unioned (AND), up to which rank its walk would have gone (DISJ). */
 #define INFX_NCLASS 136
 typedef struct infx_counts { uint32_t c[INFX_NCLASS]; } infx_counts;
 
