@@ -583,6 +583,36 @@ int32_t infx_engine_top_groups_totals(infx_session* s, uint32_t which, uint32_t*
 int32_t infx_engine_top_groups_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_top_groups_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches);
 int32_t infx_engine_last_top_groups_placement(infx_session* s, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
+/* ---- field_distinct: the exact number of distinct values of a field, whole and per group (not in the reference: the semantics below are this project's) ------
+ * Request i counts, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document:
+ *   VALUE   one dictionary code of `field`, exactly the groups infx_engine_list_groups forms of it: `distinct` of a request without group_by IS that call's
+ *           total_groups.  Codes are given by the stored bytes — an int64 by its number, a string by its bytes, a double by its BIT PATTERN: -0.0 and 0.0 are
+ *           two values, a NaN is a value, and NaNs of different payloads are different values
+ *   FIELD   any column of any kind and any number of values, a string column and a unique column included
+ *   GROUP   with `group_by` (any column of at most INFX_STATS_MAX_GROUPS = 4096 values, checked as infx_engine_field_stats checks it; it may be `field`
+ *           itself — every group then holds one value): per group with a member its members (size) and the values of `field` among them (distinct), in
+ *           infx_engine_field_stats' order of groups
+ *   whole   distinct: the values of `field` in the SET, with or without group_by; size: the SET's size (also infx_engine_field_distinct_total)
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_field_distinct_error, the others answered): a syntax error, a missing or unknown
+ * field, an unknown group_by or one of more than 4096 values INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most
+ * INFX_MAX_PREFILTERS (16) requests (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), every refusal but the filter's already in
+ * out_status; a call that failed as a whole leaves nothing for the readers.  Nothing is cached but the masks, the session's pre-filter masks.  Requests that
+ * share filter, field and group_by share one pass.  Exact and deterministic — bit ORs, compare-and-swap installs counted once and integer adds only: the same
+ * bytes from any session, stream, placement and rank.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: _whole, _groups, _total and _error as infx_engine_field_stats'.
+ * infx_engine_last_field_distinct_stats: masks built and reused, the passes that marked in LDS, in a global bitmap and in a hash set, and kernel launches of
+ * the session's last call.  infx_engine_set_distinct_placement: where this session's passes mark — 0 automatic (default), 1 LDS, 2 global bitmap, 3 hash set;
+ * a forced placement that does not fit falls to the next larger one.  For tests and measurements: the answer does not depend on it. */
+typedef struct infx_distinct_request { const char* filter; const char* field; const char* group_by; } infx_distinct_request;
+typedef struct infx_distinct_figures { uint32_t size; uint32_t distinct; } infx_distinct_figures;
+int32_t infx_engine_field_distinct(infx_session* s, uint32_t nreq, const infx_distinct_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_field_distinct_whole(infx_session* s, uint32_t which, infx_distinct_figures* out);
+int32_t infx_engine_field_distinct_groups(infx_session* s, uint32_t which, int32_t* group_col, uint32_t* codes, infx_distinct_figures* figures, int32_t cap);
+int32_t infx_engine_field_distinct_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_field_distinct_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_field_distinct_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* lds_passes, uint32_t* bitmap_passes, uint32_t* hash_passes, uint32_t* launches);
+int32_t infx_engine_set_distinct_placement(infx_session* s, int32_t mode);
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit);
 int64_t infx_engine_filter_cache_size(infx_engine* e);
 /* The infx_cov_query (CoverageEngine.PrepareQuery) the engine would hand to the device for this raw query text: lets a caller of the device ABI

@@ -575,6 +575,29 @@ int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs,
                         uint32_t* group_totals_out /* nreq */, uint32_t* totals_out /* nreq */);
 int32_t infx_last_top_groups_info(infx_stream* s, uint32_t* requests, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches,
                                   uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
+/* The exact number of distinct codes of a column over a document set, whole and per group (not in the reference: DESIGN.md "field_distinct").
+ * Request i: the SET is infx_field_stats' — the documents whose byte in `mask` is 0 (a mask slot of this stream), or, mask = NULL, every document that is not
+ * Deleted.  `col` is any uploaded column (no sort rank or value table needed), `group_col` any uploaded column of at most INFX_STATS_MAX_GROUPS values, or
+ * -1.  A member's PAIR is (its code in group_col, 0 without one; its code in col).  distinct_out[i]: the codes of col among the members; totals_out[i]: the
+ * members; with a group column, by group code at [i * INFX_STATS_MAX_GROUPS ..]: group_sizes_out the members of the group, group_distinct_out the codes of
+ * col among them (without one those entries are not written).
+ * A SPEC is (mask, col, group_col, placement); the requests of a call are taken in spec order, each spec is marked in ONE set walk and the specs run one after
+ * another on the stream, in one workspace.  G = the group column's values (1 without), V = col's:
+ *   1 LDS      G rows of V bits (rows padded to 32-bit words) and G size counters in a workgroup's LDS, by k_field_stats' two budgets; merged once
+ *   2 bitmap   the rows in global memory, at most 2^32 bits: a member's atomicOr only where a plain read shows its bit clear; sizes in LDS
+ *   3 hash     an open-addressing set of 64-bit keys (pair index + 1), capacity the power of two >= 2 x min(documents, G x V): it cannot fill.  A probe
+ *              visits at most `capacity` slots, then raises a flag that fails the call (INFX_ECAPACITY); installs are counted per group in LDS; with more
+ *              than one group a V-bit side row gives the whole set's count
+ *   k_distinct_count   popcounts the rows of placements 1 and 2 per group; k_distinct_union ORs them into a union row, whose popcount is the whole set's count
+ * placement 0: LDS when it fits, else the smaller of bitmap and hash workspace.  1 / 2 / 3 force one; one that does not fit falls to the next larger.
+ * Bit ORs, compare-and-swap installs counted once and integer adds only: the same bytes from any stream, grid and placement.  A mask build staged with
+ * infx_filter_masks is enqueued first, as ONE launch; one copy brings all counters back.  Works on a sharded index.  Synchronous.
+ * infx_last_field_distinct_info: requests, kernel launches (the mask build included), and the specs marked in LDS / a global bitmap / a hash set of the
+ * stream's last call. */
+typedef struct infx_distinct_req { const uint8_t* mask; int32_t col; int32_t group_col; uint32_t placement; uint32_t reserved; } infx_distinct_req;
+int32_t infx_field_distinct(infx_stream* s, uint32_t nreq, const infx_distinct_req* reqs, uint32_t* distinct_out /* nreq */, uint32_t* totals_out /* nreq */,
+                            uint32_t* group_sizes_out /* nreq x INFX_STATS_MAX_GROUPS */, uint32_t* group_distinct_out /* nreq x INFX_STATS_MAX_GROUPS */);
+int32_t infx_last_field_distinct_info(infx_stream* s, uint32_t* requests, uint32_t* launches, uint32_t* lds_passes, uint32_t* bitmap_passes, uint32_t* hash_passes);
 
 /* ---- measurement hooks (bench.py) ------------------------------------------------------------------------------ */
 /* Durations (ms) of the last Stage-1 accumulate / select / Stage-2 launches on this stream, from HIP events recorded on

@@ -107,6 +107,7 @@ struct RangeAnswer : Answer { uint32_t below = 0, above = 0, nan = 0; std::vecto
 template <class F> struct FiguresAnswer : Answer { F whole = {}; int32_t groupCol = -1; std::vector<uint32_t> codes; std::vector<F> groups; };
 typedef FiguresAnswer<infx_stats_figures> StatsAnswer;
 typedef FiguresAnswer<infx_quantile_figures> QuantAnswer;
+typedef FiguresAnswer<infx_distinct_figures> DistinctAnswer;      // (whole: the set's size and the field's values in it)
 // One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
 // row what a ListAnswer holds, the group's code and its size
 struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
@@ -141,6 +142,8 @@ struct infx_session {
     // infx_engine_top_groups: accumulate passes, select passes, kernel launches, tables accumulated in a workgroup's LDS / a CU's whole LDS / global memory
     // (the digit width is lstDigitBits)
     struct Top : LastCall<TopAnswer> { uint32_t accumulates = 0, passes = 0, launches = 0, place[3] = {0, 0, 0}; } top;
+    // infx_engine_field_distinct: kernel launches, passes that marked in LDS / in a global bitmap / in a hash set; dstPlacement: the placement asked of the device
+    struct Dst : LastCall<DistinctAnswer> { uint32_t launches = 0, place[3] = {0, 0, 0}; } dst; int32_t dstPlacement = 0;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -3515,6 +3518,17 @@ static infx_engine::StatsIndex& stats_index(infx_engine* e, uint32_t col) {
     }
     return X;
 }
+// What is wrong with the group_by of a request of `what` (null: none, *gcol = -1): an unknown column or one of more than INFX_STATS_MAX_GROUPS values.
+// Caller holds e->filterMu.
+static int32_t group_by_check(const infx_engine* e, const std::string& what, const char* group_by, int32_t* gcol, std::string* why) {
+    auto bad = [&](const std::string& msg) { *why = what + msg; return (int32_t)INFX_EINVAL; };
+    *gcol = -1;
+    if (group_by) {
+        if ((*gcol = column_named(e, group_by)) < 0) return bad(std::string(": no group_by field named '") + group_by + "'");
+        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string(": group_by field '") + group_by + "' has more than 4096 distinct values");
+    }
+    return INFX_OK;
+}
 // What is wrong with the field and the group_by of a field_stats or field_quantiles request (`what`; its `figures` need a numeric column) before anything of
 // it is looked at on the device — the field, its kind, group_by, in this order — as the request's status, the text in *why; INFX_OK with the columns (gcol -1:
 // no group_by).  Caller holds e->filterMu.
@@ -3525,11 +3539,7 @@ static int32_t numeric_field_check(const infx_engine* e, const std::string& what
     if (!field) return bad(" needs a field");
     if ((*col = column_named(e, field)) < 0) return bad(std::string(": no field named '") + field + "'");
     if (column_kind(e->columns[*col]) == 3) return bad(std::string(": field '") + field + "' is a string column; " + figures + " need an int64 or a double column");
-    if (group_by) {
-        if ((*gcol = column_named(e, group_by)) < 0) return bad(std::string(": no group_by field named '") + group_by + "'");
-        if (e->columns[*gcol].dict.size() > INFX_STATS_MAX_GROUPS) return bad(std::string(": group_by field '") + group_by + "' has more than 4096 distinct values");
-    }
-    return INFX_OK;
+    return group_by_check(e, what, group_by, gcol, why);
 }
 // The figures of one slot (a group, or the whole): counts, the extremes as values through the rank's lowest code, the limb sums recombined and rounded once
 static infx_stats_figures stats_figures(const infx_stats_slot& S, const infx_engine::StatsIndex& V, const filt::Column& C, const infx_engine::RangeIndex& X) {
@@ -3887,6 +3897,69 @@ int32_t infx_engine_last_top_groups_stats(infx_session* S, uint32_t* masks_built
 int32_t infx_engine_last_top_groups_placement(infx_session* S, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{small_lds, S->top.place[0]}, {big_lds, S->top.place[1]}, {in_global, S->top.place[2]}});
+}
+
+// ---- field_distinct: the exact number of distinct values of a field over the documents a filter accepts, whole and per group (not in the reference) --------
+// Per request: the field to its column — any kind, any number of values; nothing of it but its codes is needed — group_by as infx_engine_field_stats checks
+// it, the filter through the filter cache and its mask through the session's mask cache.  infx_field_distinct marks the (group code, field code) pairs of the
+// set and counts them; the engine orders the groups with a member as field_stats does.
+int32_t infx_engine_field_distinct(infx_session* S, uint32_t nreq, const infx_distinct_request* reqs, int32_t* out_status) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; col.fill(-1); gcol.fill(-1);
+    std::vector<infx_distinct_req> dr; std::vector<uint32_t> distinct, totals, gsizes, gdistinct;
+    return set_call(S, &infx_session::dst, "field_distinct", "field_distinct requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
+            const infx_distinct_request& Q = reqs[i];
+            if (!Q.field) return F.refuse(i, INFX_EINVAL, "field_distinct needs a field");
+            if ((col[i] = column_named(S->e, Q.field)) < 0) return F.refuse(i, INFX_EINVAL, std::string("field_distinct: no field named '") + Q.field + "'");
+            std::string why;
+            const int32_t rc = group_by_check(S->e, "field_distinct", Q.group_by, &gcol[i], &why);
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) { F.filter(i, reqs[i].filter); },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_distinct_req R{};
+                R.mask = F.mc.mask(i); R.col = col[i]; R.group_col = gcol[i]; R.placement = (uint32_t)S->dstPlacement;
+                dr.push_back(R);
+            }
+            const size_t m = std::max<size_t>(dr.size(), 1);
+            distinct.assign(m, 0); totals.assign(m, 0); gsizes.assign(m * INFX_STATS_MAX_GROUPS, 0); gdistinct.assign(m * INFX_STATS_MAX_GROUPS, 0);
+            return infx_field_distinct(S->stream, (uint32_t)dr.size(), dr.data(), distinct.data(), totals.data(), gsizes.data(), gdistinct.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_field_distinct_info(S->stream, nullptr, &S->dst.launches, &S->dst.place[0], &S->dst.place[1], &S->dst.place[2]);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                DistinctAnswer& A = S->dst.ans[F.who[j]];
+                A.groupCol = dr[j].group_col; A.total = totals[j]; A.whole.size = totals[j]; A.whole.distinct = distinct[j];
+                if (A.groupCol < 0) continue;
+                const uint32_t *sz = gsizes.data() + j * INFX_STATS_MAX_GROUPS, *dc = gdistinct.data() + j * INFX_STATS_MAX_GROUPS;
+                A.codes = groups_in_order(e->columns[A.groupCol], [&](uint32_t g) { return (uint64_t)sz[g]; });
+                for (uint32_t g : A.codes) A.groups.push_back(infx_distinct_figures{sz[g], dc[g]});
+            }
+        });
+}
+// request `which` of the session's last infx_engine_field_distinct: the whole's figures and the groups', as figures_whole and figures_groups
+int32_t infx_engine_field_distinct_whole(infx_session* S, uint32_t which, infx_distinct_figures* out) {
+    return figures_whole(answer_at(S ? &S->dst.ans : nullptr, which), out, "no such request in the session's last field_distinct call");
+}
+int32_t infx_engine_field_distinct_groups(infx_session* S, uint32_t which, int32_t* group_col, uint32_t* codes, infx_distinct_figures* figures, int32_t cap) {
+    return figures_groups(answer_at(S ? &S->dst.ans : nullptr, which), group_col, codes, figures, cap);
+}
+// the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_field_distinct_total(infx_session* S, uint32_t which, uint32_t* total) {
+    return answer_total(answer_at(S ? &S->dst.ans : nullptr, which), total, "no such request in the session's last field_distinct call");
+}
+int32_t infx_engine_field_distinct_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->dst.ans : nullptr, which), out, cap); }
+int32_t infx_engine_last_field_distinct_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* lds_passes, uint32_t* bitmap_passes, uint32_t* hash_passes, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->dst.masks.built}, {masks_reused, S->dst.masks.reused}, {lds_passes, S->dst.place[0]}, {bitmap_passes, S->dst.place[1]}, {hash_passes, S->dst.place[2]}, {launches, S->dst.launches}});
+}
+int32_t infx_engine_set_distinct_placement(infx_session* S, int32_t mode) {
+    if (!S || mode < 0 || mode > 3) return efail(INFX_EINVAL, "a distinct placement is 0 (automatic), 1 (LDS), 2 (global bitmap) or 3 (hash set)");
+    S->dstPlacement = mode;
+    return INFX_OK;
 }
 
 int32_t infx_engine_set_filter_cache_limit(infx_engine* e, uint64_t limit) {

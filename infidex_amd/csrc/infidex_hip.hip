@@ -268,6 +268,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "stats.hip.inc"
 #include "groups.hip.inc"
 #include "top_groups.hip.inc"
+#include "distinct.hip.inc"
 #include "quantiles.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
@@ -378,6 +379,9 @@ struct infx_stream {
     // infx_top_groups: [a table's slots and smallest ranks | its requests' composites | histograms | select states], the requests' pages, their host copy
     void* dTopWs = nullptr; size_t capTopWs = 0; void* dTopOut = nullptr; size_t capTopOut = 0; std::vector<uint32_t> hTopRaw;
     uint32_t lastTopInfo[7] = {0, 0, 0, 0, 0, 0, 0};          // of the last infx_top_groups: requests, accumulate passes, select passes, launches, tables in a workgroup's LDS / a CU's whole LDS / global memory
+    // infx_field_distinct: one spec's pair set at a time — [rows | union row] or [hash set | side row]; every spec's [sizes | distinct | whole | overflow]; their host copy
+    void* dDstWs = nullptr; size_t capDstWs = 0; void* dDstOut = nullptr; size_t capDstOut = 0; std::vector<uint32_t> hDstRaw;
+    uint32_t lastDstInfo[5] = {0, 0, 0, 0, 0};               // of the last infx_field_distinct: requests, kernel launches, specs marked in LDS / in a global bitmap / in a hash set
     uint32_t lastGrpHeads = 0, lastGrpPasses = 0, lastGrpLaunches = 0;      // head passes, histogram passes and kernel launches of the last infx_list_grouped
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
@@ -1317,7 +1321,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut, s->dTopWs, s->dTopOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut, s->dTopWs, s->dTopOut, s->dDstWs, s->dDstOut};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
@@ -3745,6 +3749,141 @@ int32_t infx_last_top_groups_info(infx_stream* s, uint32_t* requests, uint32_t* 
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     uint32_t* out[7] = {requests, accumulate_passes, select_passes, launches, small_lds, big_lds, in_global};
     for (int i = 0; i < 7; i++) if (out[i]) *out[i] = s->lastTopInfo[i];
+    return INFX_OK;
+}
+// ---- field_distinct: the distinct values of a column over a document set, whole and per group (distinct.hip.inc) ----
+// Where a spec's pairs are marked (DST_PLACE_*) under `mode`, and — for LDS — the words of the workgroup: k_field_stats' two budgets decide whether the rows
+// and their size counters fit; between the global bitmap and the hash set the smaller workspace wins (profiles/field_distinct.md).  A forced placement that
+// does not fit falls to the next larger one.
+static uint32_t dst_place(uint32_t mode, uint32_t gv, uint32_t fv, uint64_t docs, bool big, uint32_t* ldsWords) {
+    const uint64_t rows = ds_bitmap_words(gv, fv);
+    *ldsWords = 0;
+    if (mode <= DST_PLACE_LDS && rows + gv <= STS_BIG_LDS_WORDS) {
+        const uint32_t words = (uint32_t)rows + gv; uint32_t off = 0;
+        const uint32_t used = sts_place_best(1, &words, big, &off);
+        if (off != STS_GLOBAL) { *ldsWords = used; return DST_PLACE_LDS; }
+    }
+    if (mode == DST_PLACE_HASH || !ds_bitmap_fits(gv, fv)) return DST_PLACE_HASH;
+    if (mode != DST_PLACE_AUTO) return DST_PLACE_BITMAP;
+    return (rows + (gv > 1 ? ds_row_words(fv) : 0u)) * 4u <= ds_capacity(ds_max_pairs(docs, gv, fv)) * 8u ? DST_PLACE_BITMAP : DST_PLACE_HASH;
+}
+static int dst_count_grid(uint32_t words) { return (int)std::max<int64_t>(1, std::min<int64_t>(DST_COUNT_GRID, ((int64_t)words + DST_COUNT_THREADS - 1) / DST_COUNT_THREADS)); }
+int32_t infx_field_distinct(infx_stream* s, uint32_t nreq, const infx_distinct_req* reqs, uint32_t* distinct_out, uint32_t* totals_out, uint32_t* group_sizes_out, uint32_t* group_distinct_out) {
+    if (!s || (nreq && (!reqs || !distinct_out || !totals_out || !group_sizes_out || !group_distinct_out))) return fail(INFX_EINVAL, "bad field-distinct arguments%s");
+    std::fill(s->lastDstInfo, s->lastDstInfo + 5, 0u);
+    if (nreq > DST_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-distinct requests in one call%s");
+    infx_index* ix = s->ix;
+    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
+    const int32_t n = std::max(ix->d.totalDocs, 0);
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_distinct_req& Q = reqs[i];
+        { int32_t rc_ = check_set_request(s, Q.mask, -1, false, "field-distinct request"); if (rc_) return rc_; }
+        if (Q.col < 0 || Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col]) return fail(INFX_EINVAL, "the field-distinct request's column was not uploaded%s");
+        { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.col); if (rc_) return rc_; }
+        if (Q.group_col >= 0) {
+            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-distinct request"); if (rc_) return rc_; }
+            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
+        }
+        if (Q.placement > DST_PLACE_HASH) return fail(INFX_EINVAL, "a field-distinct request's placement is 0 (automatic), 1 (LDS), 2 (global bitmap) or 3 (hash set)%s");
+    }
+    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastDstInfo[1]); if (rc_) return rc_; }
+    s->lastDstInfo[0] = nreq;
+    if (!nreq) return INFX_OK;
+    uint32_t order[DST_MAX_REQS]; SetKey key[DST_MAX_REQS];
+    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col >= 0 ? reqs[i].group_col : -1};
+    set_order(nreq, key, order);
+    auto same_spec = [&](uint32_t a, uint32_t b) { return key[a].mask == key[b].mask && key[a].col == key[b].col && key[a].gcol == key[b].gcol && reqs[a].placement == reqs[b].placement; };
+    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (as infx_field_stats)
+    // per spec (device order): its placement, its words of LDS, its bytes of workspace and where its counters lie in the output
+    uint32_t place[DST_MAX_REQS] = {}, ldsWords[DST_MAX_REQS] = {}; size_t outOff[DST_MAX_REQS] = {}, wsBytes = 64, outWords = 0;
+    for (uint32_t k0 = 0; k0 < nreq;) {
+        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+        const infx_distinct_req& Q = reqs[order[k0]];
+        const uint32_t gv = Q.group_col >= 0 ? ix->colValues[Q.group_col] : 1u, fv = ix->colValues[Q.col], row = ds_row_words(fv);
+        place[k0] = dst_place(Q.placement, gv, fv, (uint64_t)n, !noBig, &ldsWords[k0]);
+        wsBytes = std::max(wsBytes, place[k0] == DST_PLACE_HASH ? (size_t)ds_capacity(ds_max_pairs((uint64_t)n, gv, fv)) * 8 + (size_t)row * 4
+                                                                : ((size_t)ds_bitmap_words(gv, fv) + row) * 4);
+        outOff[k0] = outWords; outWords += 2 * (size_t)gv + 2;
+        k0 = k1;
+    }
+    GROW(s->dDstWs, s->capDstWs, wsBytes);
+    GROW(s->dDstOut, s->capDstOut, outWords * 4);
+    uint32_t* O = (uint32_t*)s->dDstOut;
+    HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
+    s->unsynced = true;
+    for (uint32_t k0 = 0; k0 < nreq;) {
+        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+        const infx_distinct_req& Q = reqs[order[k0]];
+        const bool grouped = Q.group_col >= 0;
+        const uint32_t gv = grouped ? ix->colValues[Q.group_col] : 1u, fv = ix->colValues[Q.col], row = ds_row_words(fv);
+        if (n > 0 && gv && fv) {
+            DevDistinct D{};
+            D.mask = Q.mask ? Q.mask : ix->d.deleted; D.fcodes = ix->colCodes[Q.col]; D.gcodes = grouped ? ix->colCodes[Q.group_col] : nullptr;
+            D.gvals = gv; D.fvals = fv; D.rowWords = row;
+            D.sizes = O + outOff[k0]; D.distinct = D.sizes + gv; uint32_t* whole = D.distinct + gv; D.overflow = whole + 1;
+            const uint32_t rows = gv * row;                    // (placements 1 and 2: below 2^27)
+            uint32_t* uni = nullptr;                           // the row whose bits are the whole set's values, where it is not the spec's one row
+            int threads, grid;
+            if (place[k0] == DST_PLACE_HASH) {
+                D.capacity = ds_capacity(ds_max_pairs((uint64_t)n, gv, fv)); D.table = (unsigned long long*)s->dDstWs;
+                if (gv > 1) D.side = uni = (uint32_t*)(D.table + D.capacity);
+                HIPCHK(hipMemsetAsync(D.table, 0, (size_t)D.capacity * 8 + (gv > 1 ? (size_t)row * 4 : 0), s->st));
+                { int32_t rc_ = merge_once_shape(ix, n, 2u * gv, &threads, &grid); if (rc_) return rc_; }
+                k_distinct_hash<<<grid, threads, (size_t)2 * gv * 4, s->st>>>(D, n);
+            } else {
+                D.bits = (uint32_t*)s->dDstWs;
+                if (gv > 1) uni = D.bits + rows;
+                HIPCHK(hipMemsetAsync(D.bits, 0, ((size_t)rows + (gv > 1 ? row : 0u)) * 4, s->st));
+                if (place[k0] == DST_PLACE_LDS) {
+                    { int32_t rc_ = merge_once_shape(ix, n, ldsWords[k0], &threads, &grid); if (rc_) return rc_; }
+                    HIPCHK(lds_limit((const void*)k_distinct_lds, ix->cfg.device, (size_t)ldsWords[k0] * 4));
+                    k_distinct_lds<<<grid, threads, (size_t)ldsWords[k0] * 4, s->st>>>(D, n);
+                } else {
+                    { int32_t rc_ = merge_once_shape(ix, n, gv, &threads, &grid); if (rc_) return rc_; }
+                    k_distinct_bitmap<<<grid, threads, (size_t)gv * 4, s->st>>>(D, n);
+                }
+                k_distinct_count<<<dst_count_grid(rows), DST_COUNT_THREADS, 0, s->st>>>(D.bits, rows, row, D.distinct);
+                s->lastDstInfo[1]++;
+                if (uni) {
+                    const dim3 ug((unsigned)std::min<int64_t>(FCM_MAXGRID, ((int64_t)row + DST_COUNT_THREADS - 1) / DST_COUNT_THREADS), (gv + DST_UNION_ROWS - 1) / DST_UNION_ROWS);
+                    k_distinct_union<<<ug, DST_COUNT_THREADS, 0, s->st>>>(D.bits, gv, row, DST_UNION_ROWS, uni);
+                    s->lastDstInfo[1]++;
+                }
+            }
+            // the whole set's figure: the bits of the union (side) row; with one row the host takes that row's counter
+            if (uni) { k_distinct_count<<<dst_count_grid(row), DST_COUNT_THREADS, 0, s->st>>>(uni, row, row, whole); s->lastDstInfo[1]++; }
+            HIPCHK(hipGetLastError());
+            s->lastDstInfo[1]++; s->lastDstInfo[1 + place[k0]]++;
+        }
+        k0 = k1;
+    }
+    s->hDstRaw.assign(outWords, 0u);
+    DOWN(s->hDstRaw.data(), O, outWords * 4);
+    SYNC();
+    for (uint32_t k0 = 0; k0 < nreq;) {
+        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+        const infx_distinct_req& Q = reqs[order[k0]];
+        const bool grouped = Q.group_col >= 0;
+        const uint32_t gv = grouped ? ix->colValues[Q.group_col] : 1u;
+        const uint32_t *sizes = s->hDstRaw.data() + outOff[k0], *distinct = sizes + gv;
+        if (distinct[gv + 1]) return fail(INFX_ECAPACITY, "field-distinct: the hash set of a request overflowed%s");      // (sized never to: a broken table, not a large request)
+        uint32_t total = 0; for (uint32_t g = 0; g < gv; g++) total += sizes[g];
+        for (uint32_t k = k0; k < k1; k++) {
+            const uint32_t i = order[k];
+            distinct_out[i] = gv > 1 ? distinct[gv] : (gv ? distinct[0] : 0u); totals_out[i] = total;      // (one row: that row is the whole)
+            if (grouped && gv) {
+                std::memcpy(group_sizes_out + (size_t)i * INFX_STATS_MAX_GROUPS, sizes, (size_t)gv * 4);
+                std::memcpy(group_distinct_out + (size_t)i * INFX_STATS_MAX_GROUPS, distinct, (size_t)gv * 4);
+            }
+        }
+        k0 = k1;
+    }
+    return INFX_OK;
+}
+int32_t infx_last_field_distinct_info(infx_stream* s, uint32_t* requests, uint32_t* launches, uint32_t* lds_passes, uint32_t* bitmap_passes, uint32_t* hash_passes) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    uint32_t* out[5] = {requests, launches, lds_passes, bitmap_passes, hash_passes};
+    for (int i = 0; i < 5; i++) if (out[i]) *out[i] = s->lastDstInfo[i];
     return INFX_OK;
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {

@@ -227,6 +227,29 @@ class TopGroups:           # SearchEngine.top_groups: one per request
 
 
 @dataclass
+class DistinctRequest:     # SearchEngine.field_distinct: the distinct values of one field over one filter, whole and per group
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    field: Optional[str] = None         # any column: int64, double or string, of any number of distinct values
+    group_by: Optional[str] = None      # any column of at most 4096 distinct values; None: the whole only
+
+
+@dataclass
+class GroupDistinct:       # SearchEngine.field_distinct: one group of one request
+    value: str = ""                                           # the group's value of the group_by field as text (GroupStats.value)
+    size: int = 0                                             # members of the group among the documents the filter accepts
+    distinct: int = 0                                         # distinct values of the field among them
+
+
+@dataclass
+class FieldDistinct:       # SearchEngine.field_distinct: one per request
+    distinct: int = 0                                         # distinct values of the field among the documents the filter accepts (GroupListing.total_groups of
+    #                                                           the same filter with group_by=field), with or without group_by
+    total: int = 0                                            # live documents the filter accepts (Listing.total of the same filter)
+    groups: list = _dc_field(default_factory=list)            # [GroupDistinct] of every group with a member, in FieldStats.groups' order; [] without group_by
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+@dataclass
 class RangeRequest:        # SearchEngine.range_facets: the buckets of one numeric field over one filter
     filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
     field: str = ""                     # an int64 or a double column
@@ -337,6 +360,14 @@ class _GroupListReq(C.Structure):     # infx_group_list_request (include/infidex
 
 class _TopReq(C.Structure):           # infx_top_request (include/infidex_engine.h)
     _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("by", C.c_char_p), ("field", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class _DistinctReq(C.Structure):       # infx_distinct_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("group_by", C.c_char_p)]
+
+
+class _DistinctFigures(C.Structure):   # infx_distinct_figures (include/infidex_engine.h)
+    _fields_ = [("size", C.c_uint32), ("distinct", C.c_uint32)]
 
 
 class _Cfg(C.Structure):
@@ -647,6 +678,28 @@ class SearchEngine:
     def last_top_groups_placement(self, session=None):
         """(tables accumulated in a workgroup's LDS, in a CU's whole LDS, in global memory) of the session's last top_groups device call."""
         return _u32_stats(self, "infx_engine_last_top_groups_placement", session.h if session is not None else self._default_session(), 3)
+
+    def field_distinct(self, filter=None, field=None, group_by=None, session=None):
+        """Exact distinct counts (not in the reference): over the documents list_documents(filter) lists, the number of distinct values of `field` — any
+        column of any kind and any number of values, a string column and a unique column included — whole and, with group_by (any column of at most 4096
+        values, checked as field_stats checks it; it may be `field` itself), per group.  A value is one dictionary code of the field, exactly the groups
+        list_groups(group_by=field) forms: `distinct` equals that call's total_groups.  Values are told apart by their stored bytes: a double by its bit
+        pattern, so -0.0 and 0.0 are two values, a NaN is a value and NaNs of different payloads differ.  Returns FieldDistinct(distinct, total, groups,
+        error): groups the GroupDistinct(value, size, distinct) of every group with a member in FieldStats.groups' order, [] without group_by; the whole
+        set's distinct is filled either way.  A sequence of DistinctRequest as first argument -> a list of FieldDistinct, sixteen requests per device call;
+        requests that share filter, field and group_by share one pass.  A refused request gets `error` set, alone.  Exact and deterministic — no sketch;
+        needs a GPU."""
+        return _field_distinct(self, session.h if session is not None else self._default_session(), filter, field, group_by)
+
+    def last_field_distinct_stats(self, session=None):
+        """(masks built, masks reused, passes that marked in LDS, in a global bitmap, in a hash set, kernel launches) of the session's last field_distinct
+        device call."""
+        return _u32_stats(self, "infx_engine_last_field_distinct_stats", session.h if session is not None else self._default_session(), 6)
+
+    def set_distinct_placement(self, mode, session=None):
+        """Where field_distinct marks on this session: 0 automatic (default), 1 LDS, 2 global bitmap, 3 hash set; a forced placement that does not fit falls
+        to the next larger one.  The answers do not depend on it — for tests and measurements."""
+        self._check(self.L.infx_engine_set_distinct_placement(session.h if session is not None else self._default_session(), int(mode)))
 
     def range_facets(self, filter=None, field=None, edges=(), session=None):
         """Range facets (not in the reference): over the documents list_documents(filter) lists — not Deleted, their own fields accepted by `filter`; None:
@@ -1030,6 +1083,18 @@ class Session:
     def last_top_groups_placement(self):
         """SearchEngine.last_top_groups_placement of this session."""
         return _u32_stats(self.engine, "infx_engine_last_top_groups_placement", self.h, 3)
+
+    def field_distinct(self, filter=None, field=None, group_by=None):
+        """SearchEngine.field_distinct on this session (its mask cache holds the filters' masks)."""
+        return _field_distinct(self.engine, self.h, filter, field, group_by)
+
+    def last_field_distinct_stats(self):
+        """SearchEngine.last_field_distinct_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_field_distinct_stats", self.h, 6)
+
+    def set_distinct_placement(self, mode):
+        """SearchEngine.set_distinct_placement of this session."""
+        self.engine._check(self.engine.L.infx_engine_set_distinct_placement(self.h, int(mode)))
 
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets on this session (its mask cache holds the filters' masks)."""
@@ -1469,6 +1534,37 @@ def _field_stats(engine, sh, filter, field, group_by):
     return _per_request(engine, sh, "infx_engine_field_stats", "infx_engine_field_stats_error", _StatsReq,
                         [StatsRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
                         lambda r, msg: FieldStats(error=msg))
+
+
+_DISTINCT_FIGURES = np.dtype([("size", "<u4"), ("distinct", "<u4")])
+
+
+def _field_distinct(engine, sh, filter, field, group_by):
+    """infx_engine_field_distinct on session handle sh: a FieldDistinct for one request (given by its parts), a list of them for a sequence of DistinctRequest."""
+    def pack(r):
+        return _DistinctReq(*[None if x is None else str(x).encode() for x in (r.filter, r.field, r.group_by)])
+
+    def read(i, r):
+        whole = _DistinctFigures()
+        engine._check(engine.L.infx_engine_field_distinct_whole(sh, i, C.byref(whole)))
+        col = C.c_int32(-1)
+        m = engine.L.infx_engine_field_distinct_groups(sh, i, C.byref(col), None, None, 0)
+        if m < 0:
+            engine._check(1)
+        groups = []
+        if m > 0:
+            codes = np.zeros(m, np.uint32); figs = (_DistinctFigures * m)()
+            engine.L.infx_engine_field_distinct_groups(sh, i, C.byref(col), _p(codes, C.c_uint32), figs, m)
+            vb = C.create_string_buffer(1024)
+            for code, (size, distinct) in zip(codes.tolist(), np.frombuffer(figs, _DISTINCT_FIGURES).tolist()):
+                engine.L.infx_engine_column_value(engine.h, col.value, code, vb, 1024)
+                groups.append(GroupDistinct(vb.value.decode(), size, distinct))
+        return FieldDistinct(int(whole.distinct), int(whole.size), groups, None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_field_distinct", "infx_engine_field_distinct_error", _DistinctReq,
+                        [DistinctRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
+                        lambda r, msg: FieldDistinct(error=msg))
 
 
 def _top_groups(engine, sh, filter, group_by, by, field, ascending, offset, limit):

@@ -733,6 +733,14 @@ class ShardedSearcher:
     def last_top_groups_stats(self):
         return self.sessions[0].s.last_top_groups_stats()
 
+    def field_distinct(self, filter=None, field=None, group_by=None):
+        """SearchEngine.field_distinct: like field_stats, every rank marks and counts over the whole columns with the global Deleted flags on its own GPU
+        and gets the same answer — nothing is exchanged."""
+        return self.sessions[0].s.field_distinct(filter, field, group_by)
+
+    def last_field_distinct_stats(self):
+        return self.sessions[0].s.last_field_distinct_stats()
+
     def range_facets(self, filter=None, field=None, edges=()):
         """SearchEngine.range_facets: like list_documents, every rank counts over the whole columns with the global Deleted flags on its own GPU and gets
         the same answer — nothing is exchanged."""
