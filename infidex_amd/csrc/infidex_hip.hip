@@ -335,6 +335,27 @@ struct ProgTable {
     void put_blob(uint8_t* h, const char* d) const { put(h, h + al16(table_bytes()), d + al16(table_bytes())); }
 };
 
+// The kinds of calls over document sets ("requests over document sets" below), what a stream keeps of each (ws | out | raw) and what info[] counts of the last call:
+enum SetKind {
+    SK_LIST,          // infx_list_ordered: select states, histograms, range counts, page composites | the rows.  Histogram passes, kernel launches
+    SK_RANGE,         // infx_range_counts: the requests' thresholds | counters, largest and smallest ranks.  Requests, k_range_counts launches
+    SK_STATS,         // infx_field_stats: - | the requests' slots and smallest ranks | their host copy.  Requests, k_field_stats launches
+    SK_QUANT,         // infx_field_quantiles: quantiles, targets and one pass's rows | counts and ranks | their host copy.  Requests, histogram passes, launches, digit width,
+                      // request-passes with rows in LDS / in global memory
+    SK_GROUPED,       // infx_list_grouped (its pages in SK_LIST's buffers): a spec's head table and heads mask; per request the page's sorted codes, rows, group codes and sizes | -.
+                      // Head passes, histogram passes, kernel launches
+    SK_TOP,           // infx_top_groups: [a table's slots and smallest ranks | its requests' composites | histograms | select states] | the requests' pages | their host copy.
+                      // Requests, accumulate passes, select passes, launches, tables in a workgroup's LDS / a CU's whole LDS / global memory
+    SK_DISTINCT,      // infx_field_distinct: one spec's pair set at a time — [rows | union row] or [hash set | side row] | every spec's [sizes | distinct | whole | overflow] |
+                      // their host copy.  Requests, kernel launches, specs marked in LDS / in a global bitmap / in a hash set
+    SK_KINDS
+};
+struct SetKindState {
+    void *ws = nullptr, *out = nullptr; size_t capWs = 0, capOut = 0;      // the workspace and the output on the device
+    std::vector<uint32_t> raw;                                             // the output as the host unpacks it
+    uint32_t info[7] = {0, 0, 0, 0, 0, 0, 0};                              // the counters of the kind's last call, in the order of its infx_last_* reader
+};
+
 struct infx_stream {
     infx_index* ix;
     // post-filter / facets (infx_stream_set_postfilter): applied to the rows of every fused / sharded finalize on this stream
@@ -367,22 +388,7 @@ struct infx_stream {
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
     void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
     uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
-    void *dListWs = nullptr, *dListOut = nullptr; size_t capListWs = 0, capListOut = 0;      // infx_list_ordered: select states, histograms, range counts, page composites; the rows
-    uint32_t lastListPasses = 0, lastListLaunches = 0;         // histogram passes and kernel launches of the last infx_list_ordered
-    void *dRngWs = nullptr, *dRngOut = nullptr; size_t capRngWs = 0, capRngOut = 0;        // infx_range_counts: the requests' thresholds; counters, largest and smallest ranks
-    uint32_t lastRngReqs = 0, lastRngLaunches = 0;             // requests and k_range_counts launches of the last infx_range_counts
-    void* dStsOut = nullptr; size_t capStsOut = 0; std::vector<uint32_t> hStsRaw;      // infx_field_stats: the requests' slots and smallest ranks; their host copy
-    uint32_t lastStsReqs = 0, lastStsLaunches = 0;             // requests and k_field_stats launches of the last infx_field_stats
-    void *dQntWs = nullptr, *dQntOut = nullptr; size_t capQntWs = 0, capQntOut = 0; std::vector<uint32_t> hQntRaw;      // infx_field_quantiles: quantiles, targets and one pass's rows; counts and ranks; their host copy
-    uint32_t lastQntInfo[6] = {0, 0, 0, 0, 0, 0};              // of the last infx_field_quantiles: requests, histogram passes, launches, digit width, request-passes with rows in LDS / in global memory
-    void* dGrpWs = nullptr; size_t capGrpWs = 0;               // infx_list_grouped: a spec's head table and heads mask; per request the page's sorted codes, rows, group codes and sizes
-    // infx_top_groups: [a table's slots and smallest ranks | its requests' composites | histograms | select states], the requests' pages, their host copy
-    void* dTopWs = nullptr; size_t capTopWs = 0; void* dTopOut = nullptr; size_t capTopOut = 0; std::vector<uint32_t> hTopRaw;
-    uint32_t lastTopInfo[7] = {0, 0, 0, 0, 0, 0, 0};          // of the last infx_top_groups: requests, accumulate passes, select passes, launches, tables in a workgroup's LDS / a CU's whole LDS / global memory
-    // infx_field_distinct: one spec's pair set at a time — [rows | union row] or [hash set | side row]; every spec's [sizes | distinct | whole | overflow]; their host copy
-    void* dDstWs = nullptr; size_t capDstWs = 0; void* dDstOut = nullptr; size_t capDstOut = 0; std::vector<uint32_t> hDstRaw;
-    uint32_t lastDstInfo[5] = {0, 0, 0, 0, 0};               // of the last infx_field_distinct: requests, kernel launches, specs marked in LDS / in a global bitmap / in a hash set
-    uint32_t lastGrpHeads = 0, lastGrpPasses = 0, lastGrpLaunches = 0;      // head passes, histogram passes and kernel launches of the last infx_list_grouped
+    SetKindState kind[SK_KINDS];                               // the set calls (infx_list_ordered .. infx_field_distinct): per kind its buffers, raw host copy and counters
     hipStream_t st = nullptr;
     // Planning kernels (k_ld1, k_union count pass) are tiny and the host WAITS for their results (idf needs the union cardinalities): queued behind the
     // streaming kernels of the other batches in flight they came back after 10-15 ms (measured: plan_ms 14.9 per batch of which ~2 ms host work).  They
@@ -1321,8 +1327,9 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dListWs, s->dListOut, s->dRngWs, s->dRngOut, s->dStsOut, s->dGrpWs, s->dQntWs, s->dQntOut, s->dTopWs, s->dTopOut, s->dDstWs, s->dDstOut};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel};
     for (void* p : s->dMask) if (p) hipFree(p);
+    for (const SetKindState& K : s->kind) { if (K.ws) hipFree(K.ws); if (K.out) hipFree(K.out); }
     for (void* p : ps) if (p) hipFree(p);
     for (void* p : s->scratch) if (p) hipFree(p);
     for (void* p : s->parked) hipFree(p);
@@ -3081,25 +3088,10 @@ static int32_t check_group_column(const infx_index* ix, int32_t col, const char*
     if (col < 0 || col >= FILT_MAXCOL || !ix->colCodes[col]) return fail(INFX_EINVAL, "the %s's group column was not uploaded", what);
     return columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, col);
 }
-// The start of a set call, its requests checked: the device, the staging of the call before consumed, the masks the call is missing built (infx_filter_masks:
-// one launch in front of the rest; *launches, where the entry point counts its launches, starts from it).  A call without requests ends here, synchronised.
-static int32_t set_call_begin(infx_stream* s, int32_t n, uint32_t nreq, uint32_t* launches) {
-    HIPCHK(enter_device(s->ix->cfg.device));
-    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
-    const uint32_t builds = s->mkStaged && s->mkTable.size() && n > 0 ? 1u : 0u;
-    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }
-    if (launches) *launches = builds;
-    if (!nreq && s->unsynced) SYNC();
-    return INFX_OK;
-}
-// Threads and grid of a set walk (set_walk.h: 16 documents per thread and step) whose workgroups keep ldsWords words of LDS and merge them once at the end:
-// STS_THREADS while the words fit STS_LDS_WORDS, else one workgroup of STS_BIG_THREADS per CU (the same sixteen waves); no more workgroups than are resident
-// (LDS of a CU: FFL_CU_LDS; 2048 threads), at least one.
-static int32_t merge_once_shape(const infx_index* ix, int32_t n, uint32_t ldsWords, int* threads, int* grid) {
-    int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device));
-    const int64_t groups = ((int64_t)n + SW_GROUP - 1) / SW_GROUP, T = ldsWords <= STS_LDS_WORDS ? STS_THREADS : STS_BIG_THREADS;
-    const int64_t perCu = std::min<int64_t>(2048 / T, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)ldsWords * 4, 1)));      // (at least one: ldsWords <= STS_BIG_LDS_WORDS)
-    *threads = (int)T; *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + T - 1) / T));
+// the group column of a call that keeps one slot per group: as above, with at most STS_MAX_GROUPS values
+static int32_t check_group_slots(const infx_index* ix, int32_t col, const char* what) {
+    { int32_t rc_ = check_group_column(ix, col, what); if (rc_) return rc_; }
+    if (ix->colValues[col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
     return INFX_OK;
 }
 struct SetKey { const uint8_t* mask; int32_t col, gcol; };      // what the device's order of a call's requests looks at (gcol: -1 throughout a call without groups)
@@ -3113,6 +3105,107 @@ static void set_order(uint32_t nreq, const SetKey* key, uint32_t* order) {
 }
 // what request Q keeps of B, the one before it in that order: 1 the mask's flags, 3 the value column's ranks as well
 static uint32_t set_reuse(const SetKey& B, const SetKey& Q) { return B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
+// The frame of a set call.  What the seven kinds' starts differ in: the two refusals' words; whether the rows need the documents' keys (the listings); where
+// info[] counts requests and launches (-1: not at all; the mask build is the first launch of a kind that counts them); whether the device takes the requests
+// in set_order's order (infx_list_grouped keeps one of its own, infx_list_ordered the caller's).
+struct SetKindSpec { const char *badArgs, *tooMany; bool needKeys; int requestsAt, launchesAt; bool ordered; };
+static const SetKindSpec SET_KINDS[SK_KINDS] = {
+    {"bad listing arguments%s", "more than INFX_MAX_PREFILTERS (16) listing requests in one call%s", true, -1, 1, false},
+    {"bad range arguments%s", "more than 16 range requests in one call%s", false, 0, -1, true},
+    {"bad field-stats arguments%s", "more than 16 field-stats requests in one call%s", false, 0, -1, true},
+    {"bad field-quantiles arguments%s", "more than 16 field-quantiles requests in one call%s", false, 0, 2, true},
+    {"bad grouped-listing arguments%s", "more than INFX_MAX_PREFILTERS (16) grouped-listing requests in one call%s", true, -1, 2, false},
+    {"bad top-groups arguments%s", "more than 16 top-groups requests in one call%s", false, 0, 3, true},
+    {"bad field-distinct arguments%s", "more than 16 field-distinct requests in one call%s", false, 0, 1, true},
+};
+static_assert(RB_MAX_REQS == INFX_MAX_PREFILTERS && STS_MAX_REQS == INFX_MAX_PREFILTERS && QNT_MAX_REQS == INFX_MAX_PREFILTERS && TOP_MAX_REQS == INFX_MAX_PREFILTERS &&
+              DST_MAX_REQS == INFX_MAX_PREFILTERS, "every set call takes as many requests as a mask build takes filters");
+struct SetCall {
+    infx_stream* s; infx_index* ix; SetKindState* K; const SetKindSpec* spec;
+    int32_t n; uint32_t nreq;                                            // the corpus (never negative), the call's requests
+    SetKey key[INFX_MAX_PREFILTERS]; uint32_t order[INFX_MAX_PREFILTERS];      // key[i]: request i's, filled by the checks of an ordered kind; order[k]: the k-th request of the device
+};
+// The start of a set call, in front of its per-request checks: null arguments refused (badArgs: what the entry point found of its own), the kind's counters
+// reset, then too many requests and an index without documents refused.  Nothing is consumed or enqueued.
+static int32_t set_call_open(SetCall* c, infx_stream* s, SetKind kind, bool badArgs, uint32_t nreq) {
+    const SetKindSpec& spec = SET_KINDS[kind];
+    if (!s || badArgs) return fail(INFX_EINVAL, spec.badArgs);
+    c->s = s; c->ix = s->ix; c->K = &s->kind[kind]; c->spec = &spec; c->nreq = nreq;
+    std::fill(c->K->info, c->K->info + 7, 0u);
+    if (nreq > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, spec.tooMany);
+    if (!c->ix->haveDocs || (spec.needKeys && !c->ix->d.docKeyAll)) return fail(INFX_EINVAL, "index not uploaded%s");
+    c->n = std::max(c->ix->d.totalDocs, 0);
+    return INFX_OK;
+}
+// The rest of the start, the requests checked: the device, the staging of the call before consumed, the masks the call is missing built (infx_filter_masks:
+// one launch in front of the rest; a kind that counts its launches starts from it), the requests counted and put into the device's order.  A call without
+// requests ends here, synchronised.
+static int32_t set_call_begin(SetCall* c) {
+    infx_stream* s = c->s;
+    HIPCHK(enter_device(c->ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    const uint32_t builds = s->mkStaged && s->mkTable.size() && c->n > 0 ? 1u : 0u;
+    { int32_t rc_ = mask_flush(s); if (rc_) return rc_; }
+    if (c->spec->launchesAt >= 0) c->K->info[c->spec->launchesAt] = builds;
+    if (!c->nreq && s->unsynced) SYNC();
+    if (c->spec->requestsAt >= 0) c->K->info[c->spec->requestsAt] = c->nreq;
+    if (c->spec->ordered) set_order(c->nreq, c->key, c->order);
+    return INFX_OK;
+}
+// the flags a request's set is read from: its mask, or every live document
+static const uint8_t* set_flags(const infx_index* ix, const uint8_t* mask) { return mask ? mask : ix->d.deleted; }
+extern "C++" {      // (the two templates of this section)
+// a value column as a device request (DevListReq, DevRangeReq, DevStatsReq, DevQuantReq) reads it: codes, sort rank, number of values
+template <class Dev> static void put_column(const infx_index* ix, int32_t col, Dev* D) { D->codes = ix->colCodes[col]; D->rank = ix->colRank[col]; D->nvals = ix->colValues[col]; }
+// Runs of requests that share a spec, in the device's order: the position behind the run that starts at k0 (same: of two requests, by the caller's numbering)
+template <class Same> static uint32_t run_end(const uint32_t* order, uint32_t k0, uint32_t nreq, Same same) {
+    uint32_t k1 = k0 + 1;
+    while (k1 < nreq && same(order[k0], order[k1])) k1++;
+    return k1;
+}
+}
+// k_field_stats' request: the set, the summed column with its value table, the group column (gcol < 0: none) with `slots` slots at out, their smallest ranks at lo
+static DevStatsReq stats_dev_req(const infx_index* ix, const uint8_t* mask, int32_t col, int32_t gcol, uint32_t slots, uint32_t* out, uint32_t* lo, uint32_t ldsOff) {
+    DevStatsReq D{};
+    D.mask = set_flags(ix, mask); put_column(ix, col, &D);
+    D.bits = ix->colBits[col]; D.kind = ix->colKind[col]; D.scale = ix->colScale[col]; D.nlimbs = ix->colLimbs[col];
+    D.gcodes = gcol >= 0 ? ix->colCodes[gcol] : nullptr; D.gvals = slots; D.out = out; D.lo = lo; D.ldsOff = ldsOff;
+    return D;
+}
+// a slot as k_field_stats leaves it (w: five counters and ranks, then limbs from STS_HEAD), its first nl limbs read and the others zero, with its smallest rank
+static infx_stats_slot stats_slot(const uint32_t* w, uint32_t nl, uint32_t minRank) {
+    infx_stats_slot S{};
+    S.finite = w[0]; S.nan = w[1]; S.pinf = w[2]; S.ninf = w[3]; S.max_rank = w[4]; S.min_rank = minRank;
+    for (uint32_t i = 0; i < nl; i++) std::memcpy(&S.sum[i], w + STS_HEAD + 2 * i, 8);
+    return S;
+}
+// whether a placement may take the whole LDS of a CU (one workgroup of 1024 threads): not with INFX_STATS_NO_BIG_LDS=1, for measurements
+static bool stats_big_lds() { static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }(); return !noBig; }
+// the kind's output, `words` words of it, copied to its raw host copy: the call's last download and its synchronisation
+static int32_t set_fetch_raw(const SetCall& c, size_t words) {
+    infx_stream* s = c.s;
+    c.K->raw.assign(words, 0u);
+    DOWN(c.K->raw.data(), c.K->out, words * 4);
+    SYNC();
+    return INFX_OK;
+}
+// one reader behind the seven infx_last_*: out[i] (where not null) takes counter i of the kind's last call
+static int32_t put_info(const infx_stream* s, SetKind kind, std::initializer_list<uint32_t*> out) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    const uint32_t* v = s->kind[kind].info;
+    for (uint32_t* p : out) { if (p) *p = *v; v++; }
+    return INFX_OK;
+}
+// Threads and grid of a set walk (set_walk.h: 16 documents per thread and step) whose workgroups keep ldsWords words of LDS and merge them once at the end:
+// STS_THREADS while the words fit STS_LDS_WORDS, else one workgroup of STS_BIG_THREADS per CU (the same sixteen waves); no more workgroups than are resident
+// (LDS of a CU: FFL_CU_LDS; 2048 threads), at least one.
+static int32_t merge_once_shape(const infx_index* ix, int32_t n, uint32_t ldsWords, int* threads, int* grid) {
+    int cus = 0; HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->cfg.device));
+    const int64_t groups = ((int64_t)n + SW_GROUP - 1) / SW_GROUP, T = ldsWords <= STS_LDS_WORDS ? STS_THREADS : STS_BIG_THREADS;
+    const int64_t perCu = std::min<int64_t>(2048 / T, (int64_t)(FFL_CU_LDS / std::max<size_t>((size_t)ldsWords * 4, 1)));      // (at least one: ldsWords <= STS_BIG_LDS_WORDS)
+    *threads = (int)T; *grid = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(cus, 1) * perCu, (groups + T - 1) / T));
+    return INFX_OK;
+}
 // ---- list_documents: a page of the documents a filter accepts, in the order of a column (listing.hip.inc) ----
 // The enqueue part of a listing call, shared by infx_list_ordered and infx_list_grouped.  Where the nreq requests of a call lie in the stream's listing
 // workspace W ([states | histograms] zeroed, [page composites] all ones, range counts and prefixes [nreq][2][3][nRanges]) and in its rows O
@@ -3128,8 +3221,8 @@ struct ListLayout {
 // what a request reads of the index: the set (mask or the Deleted flags), the ordered column with its sort rank, the passes of its select
 static DevListReq list_dev_req(const infx_index* ix, const uint8_t* mask, int32_t col, bool ascending, uint32_t offset, uint32_t limit, uint32_t digitBits) {
     DevListReq D{};
-    D.mask = mask ? mask : ix->d.deleted;
-    if (col >= 0) { D.codes = ix->colCodes[col]; D.rank = ix->colRank[col]; D.nvals = ix->colValues[col]; } else D.nvals = 1;
+    D.mask = set_flags(ix, mask);
+    if (col >= 0) put_column(ix, col, &D); else D.nvals = 1;
     D.ascending = ascending ? 1u : 0u; D.offset = offset; D.limit = limit; D.digitBits = digitBits; D.passes = ls_passes(D.nvals, digitBits);
     return D;
 }
@@ -3144,9 +3237,10 @@ static int32_t list_prepare(infx_stream* s, int32_t n, uint32_t nreq, const DevL
     const size_t wsBytes = L->oRange + (size_t)nreq * 6 * L->nRanges * 4;
     const size_t R = INFX_POST_MAX_ROWS;
     L->oDocs = (size_t)nreq * R * 8; L->oCodes = L->oDocs + (size_t)nreq * R * 4; L->oCnt = L->oCodes + (size_t)nreq * R * 4; L->oTot = L->oCnt + (size_t)nreq * 4;
-    GROW(s->dListWs, s->capListWs, wsBytes);
-    GROW(s->dListOut, s->capListOut, L->oTot + (size_t)nreq * 4);
-    L->W = (char*)s->dListWs; L->O = (char*)s->dListOut;
+    SetKindState& K = s->kind[SK_LIST];
+    GROW(K.ws, K.capWs, wsBytes);
+    GROW(K.out, K.capOut, L->oTot + (size_t)nreq * 4);
+    L->W = (char*)K.ws; L->O = (char*)K.out;
     HIPCHK(hipMemsetAsync(L->W, 0, L->oPairs, s->st));
     HIPCHK(hipMemsetAsync(L->W + L->oPairs, 0xFF, (size_t)nreq * INFX_POST_MAX_ROWS * 8, s->st));
     s->unsynced = true;
@@ -3192,12 +3286,9 @@ static int32_t check_page_request(uint32_t limit, uint32_t offset, uint32_t digi
     return INFX_OK;
 }
 int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* counts_out, uint32_t* totals_out) {
-    if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !counts_out || !totals_out))) return fail(INFX_EINVAL, "bad listing arguments%s");
-    s->lastListPasses = 0; s->lastListLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) listing requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs || !ix->d.docKeyAll) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_LIST, nreq && (!reqs || !keys_out || !docs_out || !codes_out || !counts_out || !totals_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; const int32_t n = c.n; uint32_t* info = c.K->info;
     DevListReq D[INFX_MAX_PREFILTERS];
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_list_req& Q = reqs[i];
@@ -3205,13 +3296,13 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "listing"); if (rc_) return rc_; }
         D[i] = list_dev_req(ix, Q.mask, Q.col, Q.ascending != 0, Q.offset, Q.limit, Q.digit_bits);
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastListLaunches); if (rc_) return rc_; }
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
     ListLayout L;
     { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
     for (uint32_t i = 0; i < nreq; i++) {
         const size_t at = (size_t)i * INFX_POST_MAX_ROWS;
-        int32_t rc_ = list_enqueue(s, L, i, D[i], keys_out + at, docs_out + at, codes_out + at, &s->lastListPasses, &s->lastListLaunches); if (rc_) return rc_;
+        int32_t rc_ = list_enqueue(s, L, i, D[i], keys_out + at, docs_out + at, codes_out + at, &info[0], &info[1]); if (rc_) return rc_;
     }
     DOWN(counts_out, L.count(0), (size_t)nreq * 4);
     DOWN(totals_out, L.total(0), (size_t)nreq * 4);
@@ -3219,19 +3310,13 @@ int32_t infx_list_ordered(infx_stream* s, uint32_t nreq, const infx_list_req* re
     return INFX_OK;
 }
 int32_t infx_last_list_stats(infx_stream* s, uint32_t* hist_passes, uint32_t* launches) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    if (hist_passes) *hist_passes = s->lastListPasses;
-    if (launches) *launches = s->lastListLaunches;
-    return INFX_OK;
+    return put_info(s, SK_LIST, {hist_passes, launches});
 }
 // ---- range_facets: bucket counts and the extreme sort ranks of a numeric column over a document set (ranges.hip.inc) ----
 int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* reqs, uint32_t* counts_out, uint32_t* min_rank_out, uint32_t* max_rank_out) {
-    if (!s || (nreq && (!reqs || !counts_out || !min_rank_out || !max_rank_out))) return fail(INFX_EINVAL, "bad range arguments%s");
-    s->lastRngReqs = 0; s->lastRngLaunches = 0;
-    if (nreq > RB_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 range requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_RANGE, nreq && (!reqs || !counts_out || !min_rank_out || !max_rank_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
     size_t thrWords = 0;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_range_req& Q = reqs[i];
@@ -3240,31 +3325,26 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
         if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
         for (uint32_t j = 0; j < Q.nedges; j++)
             if (Q.thr[j] < Q.nan_ranks || Q.thr[j] > ix->colValues[Q.col] || (j && Q.thr[j] < Q.thr[j - 1])) return fail(INFX_EINVAL, "a range request's thresholds are non-decreasing, from nan_ranks to the column's number of values%s");
-        thrWords += Q.nedges;
+        thrWords += Q.nedges; c.key[i] = SetKey{Q.mask, Q.col, -1};
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
-    s->lastRngReqs = nreq;
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
-    uint32_t order[RB_MAX_REQS]; SetKey key[RB_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, -1};
-    set_order(nreq, key, order);
     const size_t oHi = (size_t)nreq * RNG_OUT_STRIDE * 4, oLo = oHi + (size_t)nreq * 4;
-    GROW(s->dRngWs, s->capRngWs, thrWords * 4);
-    GROW(s->dRngOut, s->capRngOut, oLo + (size_t)nreq * 4);
-    char* O = (char*)s->dRngOut;
+    GROW(K.ws, K.capWs, thrWords * 4);
+    GROW(K.out, K.capOut, oLo + (size_t)nreq * 4);
+    char* O = (char*)K.out;
     std::vector<uint32_t> thr; thr.reserve(thrWords);
     DevRangeCall P{}; P.nreq = nreq;
     uint32_t ldsWords = 0;
     for (uint32_t k = 0; k < nreq; k++) {
         const infx_range_req& Q = reqs[order[k]];
         DevRangeReq& D = P.r[k];
-        D.mask = Q.mask ? Q.mask : ix->d.deleted;
-        D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col];
-        D.thr = (const uint32_t*)s->dRngWs + thr.size(); thr.insert(thr.end(), Q.thr, Q.thr + Q.nedges);
+        D.mask = set_flags(ix, Q.mask); put_column(ix, Q.col, &D);
+        D.thr = (const uint32_t*)K.ws + thr.size(); thr.insert(thr.end(), Q.thr, Q.thr + Q.nedges);
         D.nedges = Q.nedges; D.nanRanks = Q.nan_ranks; D.ldsOff = ldsWords; ldsWords += rb_lds_words(Q.nedges);
         if (k) D.reuse = set_reuse(key[order[k - 1]], key[order[k]]);
     }
-    UP(s->dRngWs, thr.data(), thrWords * 4);
+    UP(K.ws, thr.data(), thrWords * 4);
     HIPCHK(hipMemsetAsync(O, 0, oLo, s->st));
     HIPCHK(hipMemsetAsync(O + oLo, 0xFF, (size_t)nreq * 4, s->st));
     s->unsynced = true;
@@ -3273,7 +3353,7 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
         const int grid = (int)std::min<int64_t>(RNG_MAXGRID, (groups + RNG_THREADS - 1) / RNG_THREADS);
         k_range_counts<<<grid, RNG_THREADS, (size_t)ldsWords * 4, s->st>>>(P, n, (uint32_t*)O, (uint32_t*)(O + oHi), (uint32_t*)(O + oLo));
         HIPCHK(hipGetLastError());
-        s->lastRngLaunches = 1;
+        K.info[1] = 1;
     }
     for (uint32_t k = 0; k < nreq; k++) {
         const uint32_t i = order[k];
@@ -3285,10 +3365,7 @@ int32_t infx_range_counts(infx_stream* s, uint32_t nreq, const infx_range_req* r
     return INFX_OK;
 }
 int32_t infx_last_range_stats(infx_stream* s, uint32_t* requests, uint32_t* launches) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    if (requests) *requests = s->lastRngReqs;
-    if (launches) *launches = s->lastRngLaunches;
-    return INFX_OK;
+    return put_info(s, SK_RANGE, {requests, launches});
 }
 // ---- field_stats: counts, extreme sort ranks and exact limb sums of a numeric column over a document set, whole or per group (stats.hip.inc) ----
 // Where the slots of a call's requests live: in ascending size (slots x words) while they fit `budget` words of LDS per workgroup, the others in global
@@ -3314,27 +3391,18 @@ static uint32_t sts_place_best(uint32_t nreq, const uint32_t* words, bool big, u
     return ldsWords;
 }
 int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out) {
-    if (!s || (nreq && (!reqs || !slots_out))) return fail(INFX_EINVAL, "bad field-stats arguments%s");
-    s->lastStsReqs = 0; s->lastStsLaunches = 0;
-    if (nreq > STS_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-stats requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_STATS, nreq && (!reqs || !slots_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_stats_req& Q = reqs[i];
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "field-stats request"); if (rc_) return rc_; }
         if (!ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the field-stats request's value table was not uploaded%s");
-        if (Q.group_col >= 0) {
-            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-stats request"); if (rc_) return rc_; }
-            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
-        }
+        if (Q.group_col >= 0) { int32_t rc_ = check_group_slots(ix, Q.group_col, "field-stats request"); if (rc_) return rc_; }
+        c.key[i] = SetKey{Q.mask, Q.col, Q.group_col};
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, nullptr); if (rc_) return rc_; }
-    s->lastStsReqs = nreq;
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
-    uint32_t order[STS_MAX_REQS]; SetKey key[STS_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
-    set_order(nreq, key, order);
     // a request's slots: one per value of its group column (at least one), one without; in the caller's order request i's follow request i - 1's, at at[i]
     uint32_t slotsOf[STS_MAX_REQS]; size_t at[STS_MAX_REQS], totalSlots = 0;
     for (uint32_t i = 0; i < nreq; i++) { const int32_t g = reqs[i].group_col; slotsOf[i] = g >= 0 ? std::max(ix->colValues[g], 1u) : 1u; at[i] = totalSlots; totalSlots += slotsOf[i]; }
@@ -3345,20 +3413,14 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
         words[k] = slotsOf[order[k]] * sts_stride(ix->colLimbs[Q.col]);
         off[k] = outWords; outWords += words[k]; loOff[k] = loSlots; loSlots += slotsOf[order[k]];
     }
-    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (=1: never 1024 threads, for measurements)
-    const uint32_t ldsWords = sts_place_best(nreq, words, !noBig, ldsOff);
-    GROW(s->dStsOut, s->capStsOut, (outWords + totalSlots) * 4);
-    uint32_t* O = (uint32_t*)s->dStsOut;
+    const uint32_t ldsWords = sts_place_best(nreq, words, stats_big_lds(), ldsOff);
+    GROW(K.out, K.capOut, (outWords + totalSlots) * 4);
+    uint32_t* O = (uint32_t*)K.out;
     DevStatsCall P{}; P.nreq = nreq;
     for (uint32_t k = 0; k < nreq; k++) {
         const infx_stats_req& Q = reqs[order[k]];
-        DevStatsReq& D = P.r[k];
-        D.mask = Q.mask ? Q.mask : ix->d.deleted;
-        D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.bits = ix->colBits[Q.col]; D.nvals = ix->colValues[Q.col];
-        D.kind = ix->colKind[Q.col]; D.scale = ix->colScale[Q.col]; D.nlimbs = ix->colLimbs[Q.col];
-        D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = slotsOf[order[k]];
-        D.out = O + off[k]; D.lo = O + outWords + loOff[k]; D.ldsOff = ldsOff[k];
-        if (k) D.reuse = set_reuse(key[order[k - 1]], key[order[k]]);
+        P.r[k] = stats_dev_req(ix, Q.mask, Q.col, Q.group_col, slotsOf[order[k]], O + off[k], O + outWords + loOff[k], ldsOff[k]);
+        if (k) P.r[k].reuse = set_reuse(key[order[k - 1]], key[order[k]]);
     }
     HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
     HIPCHK(hipMemsetAsync(O + outWords, 0xFF, totalSlots * 4, s->st));
@@ -3368,56 +3430,38 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
         HIPCHK(lds_limit((const void*)k_field_stats, ix->cfg.device, (size_t)ldsWords * 4));
         k_field_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
         HIPCHK(hipGetLastError());
-        s->lastStsLaunches = 1;
+        K.info[1] = 1;
     }
-    s->hStsRaw.assign(outWords + totalSlots, 0u);
-    DOWN(s->hStsRaw.data(), O, (outWords + totalSlots) * 4);
-    SYNC();
+    { int32_t rc_ = set_fetch_raw(c, outWords + totalSlots); if (rc_) return rc_; }
     for (uint32_t k = 0; k < nreq; k++) {
         const uint32_t nl = ix->colLimbs[reqs[order[k]].col], W = sts_stride(nl);
-        for (uint32_t g = 0; g < slotsOf[order[k]]; g++) {
-            const uint32_t* w = s->hStsRaw.data() + off[k] + (size_t)g * W;
-            infx_stats_slot& S = slots_out[at[order[k]] + g];
-            S.finite = w[0]; S.nan = w[1]; S.pinf = w[2]; S.ninf = w[3]; S.max_rank = w[4]; S.min_rank = s->hStsRaw[outWords + loOff[k] + g];
-            for (uint32_t i = 0; i < INFX_STATS_MAX_LIMBS; i++) { int64_t v = 0; if (i < nl) std::memcpy(&v, w + STS_HEAD + 2 * i, 8); S.sum[i] = v; }
-        }
+        for (uint32_t g = 0; g < slotsOf[order[k]]; g++)
+            slots_out[at[order[k]] + g] = stats_slot(K.raw.data() + off[k] + (size_t)g * W, nl, K.raw[outWords + loOff[k] + g]);
     }
     return INFX_OK;
 }
 int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    if (requests) *requests = s->lastStsReqs;
-    if (launches) *launches = s->lastStsLaunches;
-    return INFX_OK;
+    return put_info(s, SK_STATS, {requests, launches});
 }
 // ---- field_quantiles: the sort ranks at the quantiles' positions of a numeric column over a document set, whole and per group (quantiles.hip.inc) ----
 // The digit width of request Q under the call's cap: its own digit_bits (never above the cap), else the narrowest width that takes no more passes than the cap
 static uint32_t qnt_width(const infx_quant_req& Q, uint32_t nvals, uint32_t cap) { return Q.digit_bits ? std::min(Q.digit_bits, cap) : qs_narrow(nvals, cap); }
 int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req* reqs, infx_quant_slot* slots_out, uint32_t* ranks_out) {
-    if (!s || (nreq && (!reqs || !slots_out || !ranks_out))) return fail(INFX_EINVAL, "bad field-quantiles arguments%s");
-    std::fill(s->lastQntInfo, s->lastQntInfo + 6, 0u);
-    if (nreq > QNT_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-quantiles requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_QUANT, nreq && (!reqs || !slots_out || !ranks_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_quant_req& Q = reqs[i];
         { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "field-quantiles request"); if (rc_) return rc_; }
-        if (Q.group_col >= 0) {
-            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-quantiles request"); if (rc_) return rc_; }
-            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
-        }
+        if (Q.group_col >= 0) { int32_t rc_ = check_group_slots(ix, Q.group_col, "field-quantiles request"); if (rc_) return rc_; }
+        c.key[i] = SetKey{Q.mask, Q.col, Q.group_col};
         if (Q.nq < 1 || Q.nq > QS_MAX_Q) return fail(INFX_EINVAL, "a field-quantiles request has 1 .. INFX_QUANT_MAX (16) quantiles%s");
         for (uint32_t t = 0; t < Q.nq; t++) if (!(Q.q[t] >= 0.0 && Q.q[t] <= 1.0)) return fail(INFX_EINVAL, "a quantile is a number in [0, 1]%s");
         if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
         if (Q.digit_bits && (Q.digit_bits < LS_MIN_DIGIT_BITS || Q.digit_bits > LS_MAX_DIGIT_BITS)) return fail(INFX_EINVAL, "a field-quantiles request's digit width is 0 (chosen by the call) or 4 .. 11 bits%s");
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastQntInfo[2]); if (rc_) return rc_; }
-    s->lastQntInfo[0] = nreq;
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
-    uint32_t order[QNT_MAX_REQS]; SetKey key[QNT_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
-    set_order(nreq, key, order);
     // a request's slots: one per value of its group column, then the whole set's; in the caller's order request i's slots and ranks follow request i - 1's
     uint32_t slotsOf[QNT_MAX_REQS]; size_t atSlot[QNT_MAX_REQS], atTgt[QNT_MAX_REQS], ns = 0, nt = 0;
     for (uint32_t i = 0; i < nreq; i++) {
@@ -3445,11 +3489,11 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
         tabWords = std::max(first, later);
         if (tabWords <= QNT_SCRATCH_WORDS || cap == LS_MIN_DIGIT_BITS) break;
     }
-    s->lastQntInfo[3] = cap;
+    K.info[3] = cap;
     const size_t oTgt = (totalQ * 8 + 63) & ~(size_t)63, oTab = (oTgt + totalTgts * sizeof(ls_target) + 63) & ~(size_t)63;
-    GROW(s->dQntWs, s->capQntWs, oTab + tabWords * 4);
-    GROW(s->dQntOut, s->capQntOut, (2 * totalSlots + totalTgts) * 4);
-    char* W = (char*)s->dQntWs; uint32_t* O = (uint32_t*)s->dQntOut;
+    GROW(K.ws, K.capWs, oTab + tabWords * 4);
+    GROW(K.out, K.capOut, (2 * totalSlots + totalTgts) * 4);
+    char* W = (char*)K.ws; uint32_t* O = (uint32_t*)K.out;
     {
         std::vector<double> qs; qs.reserve(totalQ);
         for (uint32_t k = 0; k < nreq; k++) qs.insert(qs.end(), reqs[order[k]].q, reqs[order[k]].q + reqs[order[k]].nq);
@@ -3468,8 +3512,7 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
             if (passes[k] <= p) continue;
             const infx_quant_req& Q = reqs[order[k]];
             DevQuantReq& D = P.r[P.nreq];
-            D.mask = Q.mask ? Q.mask : ix->d.deleted;
-            D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.nvals = ix->colValues[Q.col];
+            D.mask = set_flags(ix, Q.mask); put_column(ix, Q.col, &D);
             D.gcodes = Q.group_col >= 0 ? ix->colCodes[Q.group_col] : nullptr; D.gvals = slots[k] - 1u; D.slots = slots[k]; D.nq = Q.nq;
             D.q = (const double*)W + q0[k]; D.tgt = (ls_target*)(W + oTgt) + tgt0[k]; D.tab = (uint32_t*)(W + oTab) + used;
             D.slotOut = O + 2 * slot0[k]; D.rankOut = O + 2 * totalSlots + tgt0[k];
@@ -3483,7 +3526,7 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
             P.r[k].ldsOff = ldsOff[2 * k]; P.r[k].ldsOffWhole = ldsOff[2 * k + 1];
             // counted by where the rows that make the request large lie: its groups', the whole set's without a group column
             const bool inLds = (P.r[k].gvals ? P.r[k].ldsOff : P.r[k].ldsOffWhole) != STS_GLOBAL;
-            s->lastQntInfo[inLds ? 4 : 5]++;
+            K.info[inLds ? 4 : 5]++;
         }
         HIPCHK(hipMemsetAsync(W + oTab, 0, used * 4, s->st));
         int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
@@ -3492,34 +3535,26 @@ int32_t infx_field_quantiles(infx_stream* s, uint32_t nreq, const infx_quant_req
         const uint32_t perBlock = QNT_PICK_THREADS / WAVE;
         k_quant_pick<<<(P.slots + perBlock - 1) / perBlock, QNT_PICK_THREADS, 0, s->st>>>(P, p);
         HIPCHK(hipGetLastError());
-        s->lastQntInfo[1]++; s->lastQntInfo[2] += 2;
+        K.info[1]++; K.info[2] += 2;
     }
-    s->hQntRaw.assign(2 * totalSlots + totalTgts, 0u);
-    DOWN(s->hQntRaw.data(), O, (2 * totalSlots + totalTgts) * 4);
-    SYNC();
+    { int32_t rc_ = set_fetch_raw(c, 2 * totalSlots + totalTgts); if (rc_) return rc_; }
     for (uint32_t k = 0; k < nreq; k++) {
         const uint32_t i = order[k];
-        for (uint32_t g = 0; g < slots[k]; g++) { slots_out[atSlot[i] + g].count = s->hQntRaw[2 * (slot0[k] + g)]; slots_out[atSlot[i] + g].nan = s->hQntRaw[2 * (slot0[k] + g) + 1]; }
-        std::copy(s->hQntRaw.begin() + 2 * totalSlots + tgt0[k], s->hQntRaw.begin() + 2 * totalSlots + tgt0[k] + (size_t)slots[k] * reqs[i].nq, ranks_out + atTgt[i]);
+        for (uint32_t g = 0; g < slots[k]; g++) { slots_out[atSlot[i] + g].count = K.raw[2 * (slot0[k] + g)]; slots_out[atSlot[i] + g].nan = K.raw[2 * (slot0[k] + g) + 1]; }
+        std::copy(K.raw.begin() + 2 * totalSlots + tgt0[k], K.raw.begin() + 2 * totalSlots + tgt0[k] + (size_t)slots[k] * reqs[i].nq, ranks_out + atTgt[i]);
     }
     return INFX_OK;
 }
 int32_t infx_last_field_quantiles_info(infx_stream* s, uint32_t* requests, uint32_t* hist_passes, uint32_t* launches, uint32_t* digit_bits, uint32_t* lds_rows, uint32_t* global_rows) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    uint32_t* out[6] = {requests, hist_passes, launches, digit_bits, lds_rows, global_rows};
-    for (int i = 0; i < 6; i++) if (out[i]) *out[i] = s->lastQntInfo[i];
-    return INFX_OK;
+    return put_info(s, SK_QUANT, {requests, hist_passes, launches, digit_bits, lds_rows, global_rows});
 }
 // ---- list_groups: a page of the heads of a document set's groups, in the order of a column, with the groups' sizes (groups.hip.inc) ----
 int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* gcodes_out,
                           uint32_t* sizes_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
-    if (!s || (nreq && (!reqs || !keys_out || !docs_out || !codes_out || !gcodes_out || !sizes_out || !counts_out || !group_totals_out || !totals_out)))
-        return fail(INFX_EINVAL, "bad grouped-listing arguments%s");
-    s->lastGrpHeads = 0; s->lastGrpPasses = 0; s->lastGrpLaunches = 0;
-    if (nreq > INFX_MAX_PREFILTERS) return fail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) grouped-listing requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs || !ix->d.docKeyAll) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    const bool badArgs = nreq && (!reqs || !keys_out || !docs_out || !codes_out || !gcodes_out || !sizes_out || !counts_out || !group_totals_out || !totals_out);
+    { int32_t rc_ = set_call_open(&c, s, SK_GROUPED, badArgs, nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; uint32_t* order = c.order;
     uint32_t gvMax = 1;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_group_list_req& Q = reqs[i];
@@ -3528,12 +3563,11 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
         { int32_t rc_ = check_group_column(ix, Q.group_col, "grouped listing"); if (rc_) return rc_; }
         gvMax = std::max(gvMax, ix->colValues[Q.group_col]);
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastGrpLaunches); if (rc_) return rc_; }
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
     // requests of one spec — (mask, group column, order column, direction) — follow one another: they share the head pass, the heads mask and the size walk
-    uint32_t order[INFX_MAX_PREFILTERS];
     for (uint32_t i = 0; i < nreq; i++) order[i] = i;
-    auto same_spec = [&](const infx_group_list_req& A, const infx_group_list_req& B) { return A.mask == B.mask && A.group_col == B.group_col && A.col == B.col && (A.ascending != 0) == (B.ascending != 0); };
+    auto same_spec = [&](uint32_t a, uint32_t b) { const infx_group_list_req &A = reqs[a], &B = reqs[b]; return A.mask == B.mask && A.group_col == B.group_col && A.col == B.col && (A.ascending != 0) == (B.ascending != 0); };
     std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
         const infx_group_list_req &A = reqs[a], &B = reqs[b];
         if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
@@ -3543,8 +3577,8 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
     const size_t R = INFX_POST_MAX_ROWS, groups16 = ((size_t)n + LST_GROUP - 1) / LST_GROUP;
     const size_t oHeads = ((size_t)gvMax * 8 + 63) & ~(size_t)63, oTot = (oHeads + groups16 * LST_GROUP + 63) & ~(size_t)63, oSorted = oTot + INFX_MAX_PREFILTERS * 4;
     const size_t oPerm = oSorted + (size_t)nreq * R * 4, oGc = oPerm + (size_t)nreq * R * 4, oSizes = oGc + (size_t)nreq * R * 4;
-    GROW(s->dGrpWs, s->capGrpWs, oSizes + (size_t)nreq * R * 4);
-    char* G0 = (char*)s->dGrpWs;
+    GROW(K.ws, K.capWs, oSizes + (size_t)nreq * R * 4);
+    char* G0 = (char*)K.ws;
     uint32_t* dTot = (uint32_t*)(G0 + oTot); uint32_t* dSorted = (uint32_t*)(G0 + oSorted); uint32_t* dPerm = (uint32_t*)(G0 + oPerm);
     uint32_t* dGc = (uint32_t*)(G0 + oGc); uint32_t* dSizes = (uint32_t*)(G0 + oSizes);
     HIPCHK(hipMemsetAsync(dTot, 0, INFX_MAX_PREFILTERS * 4, s->st));
@@ -3559,12 +3593,11 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
     { int32_t rc_ = list_prepare(s, n, nreq, D, &L); if (rc_) return rc_; }
     const int64_t groups = (int64_t)groups16;
     uint32_t spec = 0;
-    for (uint32_t k0 = 0; k0 < nreq; spec++) {
-        uint32_t k1 = k0 + 1;
-        while (k1 < nreq && same_spec(reqs[order[k0]], reqs[order[k1]])) k1++;
+    for (uint32_t k0 = 0, k1; k0 < nreq; k0 = k1, spec++) {
+        k1 = run_end(order, k0, nreq, same_spec);
         const infx_group_list_req& Q = reqs[order[k0]];
         DevGroupSpec G{};
-        G.mask = Q.mask ? Q.mask : ix->d.deleted; G.gcodes = ix->colCodes[Q.group_col]; G.gvals = ix->colValues[Q.group_col];
+        G.mask = set_flags(ix, Q.mask); G.gcodes = ix->colCodes[Q.group_col]; G.gvals = ix->colValues[Q.group_col];
         G.ocodes = D[k0].codes; G.orank = D[k0].rank; G.onvals = D[k0].nvals; G.ascending = D[k0].ascending;
         G.table = (unsigned long long*)G0; G.heads = (uint8_t*)(G0 + oHeads); G.total = dTot + spec;
         if (n > 0) {
@@ -3578,15 +3611,15 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             k_group_heads<<<grid, threads, lds, s->st>>>(G, n);
             k_group_heads_mask<<<(int)std::min<int64_t>(FCM_MAXGRID, (groups + GRP_THREADS - 1) / GRP_THREADS), GRP_THREADS, 0, s->st>>>(G, n);
             HIPCHK(hipGetLastError());
-            s->lastGrpHeads++; s->lastGrpLaunches += 2;
+            K.info[0]++; K.info[2] += 2;
         }
         for (uint32_t k = k0; k < k1; k++) {
             const size_t at = (size_t)order[k] * R;
-            int32_t rc_ = list_enqueue(s, L, k, D[k], keys_out + at, docs_out + at, codes_out + at, &s->lastGrpPasses, &s->lastGrpLaunches); if (rc_) return rc_;
+            int32_t rc_ = list_enqueue(s, L, k, D[k], keys_out + at, docs_out + at, codes_out + at, &K.info[1], &K.info[2]); if (rc_) return rc_;
         }
         k_group_page<<<k1 - k0, LST_SORT_THREADS, 0, s->st>>>(G.gcodes, n, L.docs(k0), L.count(k0), dGc + (size_t)k0 * R, dSorted + (size_t)k0 * R, dPerm + (size_t)k0 * R, dSizes + (size_t)k0 * R);
         HIPCHK(hipGetLastError());
-        s->lastGrpLaunches++;
+        K.info[2]++;
         if (n > 0) {
             DevGroupSizes Z{};
             Z.mask = G.mask; Z.gcodes = G.gcodes; Z.nreq = k1 - k0;
@@ -3600,7 +3633,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             HIPCHK(lds_limit((const void*)k_group_sizes, ix->cfg.device, (size_t)words * 4));
             k_group_sizes<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
             HIPCHK(hipGetLastError());
-            s->lastGrpLaunches++;
+            K.info[2]++;
         }
         for (uint32_t k = k0; k < k1; k++) {
             const uint32_t i = order[k];
@@ -3610,26 +3643,18 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             DOWN(group_totals_out + i, L.total(k), 4);
             DOWN(totals_out + i, dTot + spec, 4);
         }
-        k0 = k1;
     }
     SYNC();
     return INFX_OK;
 }
 int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    if (head_passes) *head_passes = s->lastGrpHeads;
-    if (hist_passes) *hist_passes = s->lastGrpPasses;
-    if (launches) *launches = s->lastGrpLaunches;
-    return INFX_OK;
+    return put_info(s, SK_GROUPED, {head_passes, hist_passes, launches});
 }
 // ---- top_groups: a page of a document set's groups, ranked by a figure of the group (top_groups.hip.inc) ----
 int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs, uint32_t* codes_out, infx_stats_slot* slots_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
-    if (!s || (nreq && (!reqs || !codes_out || !slots_out || !counts_out || !group_totals_out || !totals_out))) return fail(INFX_EINVAL, "bad top-groups arguments%s");
-    std::fill(s->lastTopInfo, s->lastTopInfo + 7, 0u);
-    if (nreq > TOP_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 top-groups requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_TOP, nreq && (!reqs || !codes_out || !slots_out || !counts_out || !group_totals_out || !totals_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_top_req& Q = reqs[i];
         { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
@@ -3639,65 +3664,58 @@ int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs,
         if (Q.by >= TS_BYS) return fail(INFX_EINVAL, "a top-groups request ranks by size, count, min, max, sum or mean (0 .. 5)%s");
         if (Q.col < 0 && Q.by != TS_BY_SIZE) return fail(INFX_EINVAL, "without a value column a top-groups request ranks by size%s");
         if (Q.col >= 0 && !ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the top-groups request's value table was not uploaded%s");
+        c.key[i] = SetKey{Q.mask, Q.col, Q.group_col};
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastTopInfo[3]); if (rc_) return rc_; }
-    s->lastTopInfo[0] = nreq;
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
-    uint32_t order[TOP_MAX_REQS]; SetKey key[TOP_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col};
-    set_order(nreq, key, order);
     auto same_table = [&](uint32_t a, uint32_t b) { return key[a].mask == key[b].mask && key[a].col == key[b].col && key[a].gcol == key[b].gcol; };
     // per request (device order) what its select needs; per table the words of its slots and smallest ranks and of its requests' composites
     uint32_t figWords[TOP_MAX_REQS], passes[TOP_MAX_REQS]; size_t keyOff[TOP_MAX_REQS], tabWords = 0, keyWords = 0;
-    for (uint32_t k0 = 0; k0 < nreq;) {
+    for (uint32_t k0 = 0, k1; k0 < nreq; k0 = k1) {
+        k1 = run_end(order, k0, nreq, same_table);
         const infx_top_req& Q = reqs[order[k0]];
         const size_t gv = ix->colValues[Q.group_col];
         tabWords = std::max(tabWords, Q.col >= 0 ? gv * (sts_stride(ix->colLimbs[Q.col]) + 1u) : gv);
-        size_t kw = 0; uint32_t k1 = k0;
-        for (; k1 < nreq && same_table(order[k0], order[k1]); k1++) {
-            const infx_top_req& R = reqs[order[k1]];
-            figWords[k1] = ts_fig_words(R.by, R.col >= 0 ? ix->colKind[R.col] : XS_KIND_INT); passes[k1] = ts_passes(figWords[k1], R.digit_bits);
-            keyOff[k1] = kw; kw += gv * ts_key_words(figWords[k1]);
+        size_t kw = 0;
+        for (uint32_t k = k0; k < k1; k++) {
+            const infx_top_req& R = reqs[order[k]];
+            figWords[k] = ts_fig_words(R.by, R.col >= 0 ? ix->colKind[R.col] : XS_KIND_INT); passes[k] = ts_passes(figWords[k], R.digit_bits);
+            keyOff[k] = kw; kw += gv * ts_key_words(figWords[k]);
         }
-        keyWords = std::max(keyWords, kw); k0 = k1;
+        keyWords = std::max(keyWords, kw);
     }
     const size_t stBytes = (sizeof(DevTopState) + 63) & ~(size_t)63;
     const size_t oKeys = (tabWords * 4 + 63) & ~(size_t)63, oHist = (oKeys + keyWords * 4 + 63) & ~(size_t)63, oState = oHist + (size_t)nreq * 2 * LS_MAX_BINS * 4;
-    GROW(s->dTopWs, s->capTopWs, oState + nreq * stBytes);
-    GROW(s->dTopOut, s->capTopOut, (size_t)nreq * TOP_OUT_WORDS * 4);
-    char* W = (char*)s->dTopWs; uint32_t* O = (uint32_t*)s->dTopOut;
+    GROW(K.ws, K.capWs, oState + nreq * stBytes);
+    GROW(K.out, K.capOut, (size_t)nreq * TOP_OUT_WORDS * 4);
+    char* W = (char*)K.ws; uint32_t* O = (uint32_t*)K.out;
     HIPCHK(hipMemsetAsync(W + oHist, 0, oState + nreq * stBytes - oHist, s->st));
     HIPCHK(hipMemsetAsync(O, 0, (size_t)nreq * TOP_OUT_WORDS * 4, s->st));
     s->unsynced = true;
-    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (as infx_field_stats)
-    for (uint32_t k0 = 0; k0 < nreq;) {
-        uint32_t k1 = k0; while (k1 < nreq && same_table(order[k0], order[k1])) k1++;
+    for (uint32_t k0 = 0, k1; k0 < nreq; k0 = k1) {
+        k1 = run_end(order, k0, nreq, same_table);
         const infx_top_req& Q = reqs[order[k0]];
         const uint32_t gv = ix->colValues[Q.group_col], nl = Q.col >= 0 ? ix->colLimbs[Q.col] : 0u, stride = Q.col >= 0 ? sts_stride(nl) : 1u;
         uint32_t* slots = (uint32_t*)W; uint32_t* lo = slots + (size_t)gv * stride;
-        const uint8_t* mask = Q.mask ? Q.mask : ix->d.deleted;
         // 1. accumulate: the table's slots, placed as field_stats places one request's
         if (gv) HIPCHK(hipMemsetAsync(slots, 0, (size_t)gv * stride * 4, s->st));
         if (gv && Q.col >= 0) HIPCHK(hipMemsetAsync(lo, 0xFF, (size_t)gv * 4, s->st));
         if (n > 0 && gv) {
             const uint32_t words = gv * stride; uint32_t ldsOff = 0;
-            const uint32_t ldsWords = (uint64_t)gv * stride > STS_BIG_LDS_WORDS ? (ldsOff = STS_GLOBAL, 0u) : sts_place_best(1, &words, !noBig, &ldsOff);
+            const uint32_t ldsWords = (uint64_t)gv * stride > STS_BIG_LDS_WORDS ? (ldsOff = STS_GLOBAL, 0u) : sts_place_best(1, &words, stats_big_lds(), &ldsOff);
             int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
             if (Q.col >= 0) {
                 DevStatsCall P{}; P.nreq = 1;
-                DevStatsReq& D = P.r[0];
-                D.mask = mask; D.codes = ix->colCodes[Q.col]; D.rank = ix->colRank[Q.col]; D.bits = ix->colBits[Q.col]; D.nvals = ix->colValues[Q.col];
-                D.kind = ix->colKind[Q.col]; D.scale = ix->colScale[Q.col]; D.nlimbs = nl;
-                D.gcodes = ix->colCodes[Q.group_col]; D.gvals = gv; D.out = slots; D.lo = lo; D.ldsOff = ldsOff;
+                P.r[0] = stats_dev_req(ix, Q.mask, Q.col, Q.group_col, gv, slots, lo, ldsOff);
                 HIPCHK(lds_limit((const void*)k_field_stats, ix->cfg.device, (size_t)ldsWords * 4));
                 k_field_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
             } else {
                 HIPCHK(lds_limit((const void*)k_top_sizes, ix->cfg.device, (size_t)ldsWords * 4));
-                k_top_sizes<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(mask, ix->colCodes[Q.group_col], gv, slots, ldsOff != STS_GLOBAL ? 1u : 0u, n);
+                k_top_sizes<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(set_flags(ix, Q.mask), ix->colCodes[Q.group_col], gv, slots, ldsOff != STS_GLOBAL ? 1u : 0u, n);
             }
             HIPCHK(hipGetLastError());
-            s->lastTopInfo[1]++; s->lastTopInfo[3]++;
-            s->lastTopInfo[ldsOff == STS_GLOBAL ? 6 : ldsWords <= STS_LDS_WORDS ? 4 : 5]++;
+            K.info[1]++; K.info[3]++;
+            K.info[ldsOff == STS_GLOBAL ? 6 : ldsWords <= STS_LDS_WORDS ? 4 : 5]++;
         }
         // 2. keys; 3. select: the requests that still have a pass, in one launch each for histogram and pick; 4. the pages
         DevTopCall P{}; P.nreq = k1 - k0;
@@ -3714,42 +3732,34 @@ int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs,
         }
         const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(FCM_MAXGRID, ((int64_t)gv + TOP_THREADS - 1) / TOP_THREADS));
         k_top_keys<<<dim3(blocks, P.nreq), TOP_THREADS, 0, s->st>>>(P);
-        s->lastTopInfo[3]++;
+        K.info[3]++;
         for (uint32_t p = 0; p < maxPasses; p++) {
             DevTopCall A{}; uint32_t bits = LS_MIN_DIGIT_BITS;
             for (uint32_t q = 0; q < P.nreq; q++) if (P.r[q].passes > p) { A.r[A.nreq++] = P.r[q]; bits = std::max(bits, P.r[q].digitBits); }
             k_top_hist<<<dim3(blocks, A.nreq), TOP_THREADS, ((size_t)2 << bits) * 4, s->st>>>(A, p);
             k_top_pick<<<A.nreq, TOP_THREADS, 0, s->st>>>(A, p);
-            s->lastTopInfo[2]++; s->lastTopInfo[3] += 2;
+            K.info[2]++; K.info[3] += 2;
         }
         k_top_gather<<<dim3(blocks, P.nreq), TOP_THREADS, 0, s->st>>>(P);
         k_top_page<<<P.nreq, LST_SORT_THREADS, 0, s->st>>>(P);
         HIPCHK(hipGetLastError());
-        s->lastTopInfo[3] += 2;
-        k0 = k1;
+        K.info[3] += 2;
     }
-    s->hTopRaw.assign((size_t)nreq * TOP_OUT_WORDS, 0u);
-    DOWN(s->hTopRaw.data(), O, (size_t)nreq * TOP_OUT_WORDS * 4);
-    SYNC();
+    { int32_t rc_ = set_fetch_raw(c, (size_t)nreq * TOP_OUT_WORDS); if (rc_) return rc_; }
     for (uint32_t k = 0; k < nreq; k++) {
-        const uint32_t i = order[k]; const uint32_t* w = s->hTopRaw.data() + (size_t)k * TOP_OUT_WORDS;
+        const uint32_t i = order[k]; const uint32_t* w = K.raw.data() + (size_t)k * TOP_OUT_WORDS;
         const uint32_t rows = std::min<uint32_t>(w[0], INFX_POST_MAX_ROWS);
         counts_out[i] = rows; group_totals_out[i] = w[1]; totals_out[i] = w[2];
         for (uint32_t r = 0; r < rows; r++) {
             codes_out[(size_t)i * INFX_POST_MAX_ROWS + r] = w[TOP_OUT_HEAD + r];
             const uint32_t* v = w + TOP_OUT_HEAD + INFX_POST_MAX_ROWS + (size_t)r * TOP_SLOT_WORDS;
-            infx_stats_slot& S = slots_out[(size_t)i * INFX_POST_MAX_ROWS + r];
-            S.finite = v[0]; S.nan = v[1]; S.pinf = v[2]; S.ninf = v[3]; S.max_rank = v[4]; S.min_rank = v[5];
-            for (uint32_t j = 0; j < INFX_STATS_MAX_LIMBS; j++) std::memcpy(&S.sum[j], v + STS_HEAD + 2 * j, 8);
+            slots_out[(size_t)i * INFX_POST_MAX_ROWS + r] = stats_slot(v, INFX_STATS_MAX_LIMBS, v[5]);      // (a page's slot: every limb, the smallest rank in word 5)
         }
     }
     return INFX_OK;
 }
 int32_t infx_last_top_groups_info(infx_stream* s, uint32_t* requests, uint32_t* accumulate_passes, uint32_t* select_passes, uint32_t* launches, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    uint32_t* out[7] = {requests, accumulate_passes, select_passes, launches, small_lds, big_lds, in_global};
-    for (int i = 0; i < 7; i++) if (out[i]) *out[i] = s->lastTopInfo[i];
-    return INFX_OK;
+    return put_info(s, SK_TOP, {requests, accumulate_passes, select_passes, launches, small_lds, big_lds, in_global});
 }
 // ---- field_distinct: the distinct values of a column over a document set, whole and per group (distinct.hip.inc) ----
 // Where a spec's pairs are marked (DST_PLACE_*) under `mode`, and — for LDS — the words of the workgroup: k_field_stats' two budgets decide whether the rows
@@ -3769,69 +3779,56 @@ static uint32_t dst_place(uint32_t mode, uint32_t gv, uint32_t fv, uint64_t docs
 }
 static int dst_count_grid(uint32_t words) { return (int)std::max<int64_t>(1, std::min<int64_t>(DST_COUNT_GRID, ((int64_t)words + DST_COUNT_THREADS - 1) / DST_COUNT_THREADS)); }
 int32_t infx_field_distinct(infx_stream* s, uint32_t nreq, const infx_distinct_req* reqs, uint32_t* distinct_out, uint32_t* totals_out, uint32_t* group_sizes_out, uint32_t* group_distinct_out) {
-    if (!s || (nreq && (!reqs || !distinct_out || !totals_out || !group_sizes_out || !group_distinct_out))) return fail(INFX_EINVAL, "bad field-distinct arguments%s");
-    std::fill(s->lastDstInfo, s->lastDstInfo + 5, 0u);
-    if (nreq > DST_MAX_REQS) return fail(INFX_ECAPACITY, "more than 16 field-distinct requests in one call%s");
-    infx_index* ix = s->ix;
-    if (!ix->haveDocs) return fail(INFX_EINVAL, "index not uploaded%s");
-    const int32_t n = std::max(ix->d.totalDocs, 0);
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_DISTINCT, nreq && (!reqs || !distinct_out || !totals_out || !group_sizes_out || !group_distinct_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
     for (uint32_t i = 0; i < nreq; i++) {
         const infx_distinct_req& Q = reqs[i];
         { int32_t rc_ = check_set_request(s, Q.mask, -1, false, "field-distinct request"); if (rc_) return rc_; }
         if (Q.col < 0 || Q.col >= FILT_MAXCOL || !ix->colCodes[Q.col]) return fail(INFX_EINVAL, "the field-distinct request's column was not uploaded%s");
         { int32_t rc_ = columns_cover(ix, ix->d.totalDocs, COLS_COVER_CORPUS, Q.col); if (rc_) return rc_; }
-        if (Q.group_col >= 0) {
-            { int32_t rc_ = check_group_column(ix, Q.group_col, "field-distinct request"); if (rc_) return rc_; }
-            if (ix->colValues[Q.group_col] > STS_MAX_GROUPS) return fail(INFX_EINVAL, "a group column has at most INFX_STATS_MAX_GROUPS (4096) values%s");
-        }
+        if (Q.group_col >= 0) { int32_t rc_ = check_group_slots(ix, Q.group_col, "field-distinct request"); if (rc_) return rc_; }
         if (Q.placement > DST_PLACE_HASH) return fail(INFX_EINVAL, "a field-distinct request's placement is 0 (automatic), 1 (LDS), 2 (global bitmap) or 3 (hash set)%s");
+        c.key[i] = SetKey{Q.mask, Q.col, Q.group_col >= 0 ? Q.group_col : -1};
     }
-    { int32_t rc_ = set_call_begin(s, n, nreq, &s->lastDstInfo[1]); if (rc_) return rc_; }
-    s->lastDstInfo[0] = nreq;
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
     if (!nreq) return INFX_OK;
-    uint32_t order[DST_MAX_REQS]; SetKey key[DST_MAX_REQS];
-    for (uint32_t i = 0; i < nreq; i++) key[i] = SetKey{reqs[i].mask, reqs[i].col, reqs[i].group_col >= 0 ? reqs[i].group_col : -1};
-    set_order(nreq, key, order);
     auto same_spec = [&](uint32_t a, uint32_t b) { return key[a].mask == key[b].mask && key[a].col == key[b].col && key[a].gcol == key[b].gcol && reqs[a].placement == reqs[b].placement; };
-    static const bool noBig = [] { const char* v = getenv("INFX_STATS_NO_BIG_LDS"); return v && v[0] == '1'; }();      // (as infx_field_stats)
     // per spec (device order): its placement, its words of LDS, its bytes of workspace and where its counters lie in the output
     uint32_t place[DST_MAX_REQS] = {}, ldsWords[DST_MAX_REQS] = {}; size_t outOff[DST_MAX_REQS] = {}, wsBytes = 64, outWords = 0;
-    for (uint32_t k0 = 0; k0 < nreq;) {
-        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+    for (uint32_t k0 = 0; k0 < nreq; k0 = run_end(order, k0, nreq, same_spec)) {
         const infx_distinct_req& Q = reqs[order[k0]];
         const uint32_t gv = Q.group_col >= 0 ? ix->colValues[Q.group_col] : 1u, fv = ix->colValues[Q.col], row = ds_row_words(fv);
-        place[k0] = dst_place(Q.placement, gv, fv, (uint64_t)n, !noBig, &ldsWords[k0]);
+        place[k0] = dst_place(Q.placement, gv, fv, (uint64_t)n, stats_big_lds(), &ldsWords[k0]);
         wsBytes = std::max(wsBytes, place[k0] == DST_PLACE_HASH ? (size_t)ds_capacity(ds_max_pairs((uint64_t)n, gv, fv)) * 8 + (size_t)row * 4
                                                                 : ((size_t)ds_bitmap_words(gv, fv) + row) * 4);
         outOff[k0] = outWords; outWords += 2 * (size_t)gv + 2;
-        k0 = k1;
     }
-    GROW(s->dDstWs, s->capDstWs, wsBytes);
-    GROW(s->dDstOut, s->capDstOut, outWords * 4);
-    uint32_t* O = (uint32_t*)s->dDstOut;
+    GROW(K.ws, K.capWs, wsBytes);
+    GROW(K.out, K.capOut, outWords * 4);
+    uint32_t* O = (uint32_t*)K.out;
     HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
     s->unsynced = true;
-    for (uint32_t k0 = 0; k0 < nreq;) {
-        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+    for (uint32_t k0 = 0; k0 < nreq; k0 = run_end(order, k0, nreq, same_spec)) {
         const infx_distinct_req& Q = reqs[order[k0]];
         const bool grouped = Q.group_col >= 0;
         const uint32_t gv = grouped ? ix->colValues[Q.group_col] : 1u, fv = ix->colValues[Q.col], row = ds_row_words(fv);
         if (n > 0 && gv && fv) {
             DevDistinct D{};
-            D.mask = Q.mask ? Q.mask : ix->d.deleted; D.fcodes = ix->colCodes[Q.col]; D.gcodes = grouped ? ix->colCodes[Q.group_col] : nullptr;
+            D.mask = set_flags(ix, Q.mask); D.fcodes = ix->colCodes[Q.col]; D.gcodes = grouped ? ix->colCodes[Q.group_col] : nullptr;
             D.gvals = gv; D.fvals = fv; D.rowWords = row;
             D.sizes = O + outOff[k0]; D.distinct = D.sizes + gv; uint32_t* whole = D.distinct + gv; D.overflow = whole + 1;
             const uint32_t rows = gv * row;                    // (placements 1 and 2: below 2^27)
             uint32_t* uni = nullptr;                           // the row whose bits are the whole set's values, where it is not the spec's one row
             int threads, grid;
             if (place[k0] == DST_PLACE_HASH) {
-                D.capacity = ds_capacity(ds_max_pairs((uint64_t)n, gv, fv)); D.table = (unsigned long long*)s->dDstWs;
+                D.capacity = ds_capacity(ds_max_pairs((uint64_t)n, gv, fv)); D.table = (unsigned long long*)K.ws;
                 if (gv > 1) D.side = uni = (uint32_t*)(D.table + D.capacity);
                 HIPCHK(hipMemsetAsync(D.table, 0, (size_t)D.capacity * 8 + (gv > 1 ? (size_t)row * 4 : 0), s->st));
                 { int32_t rc_ = merge_once_shape(ix, n, 2u * gv, &threads, &grid); if (rc_) return rc_; }
                 k_distinct_hash<<<grid, threads, (size_t)2 * gv * 4, s->st>>>(D, n);
             } else {
-                D.bits = (uint32_t*)s->dDstWs;
+                D.bits = (uint32_t*)K.ws;
                 if (gv > 1) uni = D.bits + rows;
                 HIPCHK(hipMemsetAsync(D.bits, 0, ((size_t)rows + (gv > 1 ? row : 0u)) * 4, s->st));
                 if (place[k0] == DST_PLACE_LDS) {
@@ -3843,29 +3840,26 @@ int32_t infx_field_distinct(infx_stream* s, uint32_t nreq, const infx_distinct_r
                     k_distinct_bitmap<<<grid, threads, (size_t)gv * 4, s->st>>>(D, n);
                 }
                 k_distinct_count<<<dst_count_grid(rows), DST_COUNT_THREADS, 0, s->st>>>(D.bits, rows, row, D.distinct);
-                s->lastDstInfo[1]++;
+                K.info[1]++;
                 if (uni) {
                     const dim3 ug((unsigned)std::min<int64_t>(FCM_MAXGRID, ((int64_t)row + DST_COUNT_THREADS - 1) / DST_COUNT_THREADS), (gv + DST_UNION_ROWS - 1) / DST_UNION_ROWS);
                     k_distinct_union<<<ug, DST_COUNT_THREADS, 0, s->st>>>(D.bits, gv, row, DST_UNION_ROWS, uni);
-                    s->lastDstInfo[1]++;
+                    K.info[1]++;
                 }
             }
             // the whole set's figure: the bits of the union (side) row; with one row the host takes that row's counter
-            if (uni) { k_distinct_count<<<dst_count_grid(row), DST_COUNT_THREADS, 0, s->st>>>(uni, row, row, whole); s->lastDstInfo[1]++; }
+            if (uni) { k_distinct_count<<<dst_count_grid(row), DST_COUNT_THREADS, 0, s->st>>>(uni, row, row, whole); K.info[1]++; }
             HIPCHK(hipGetLastError());
-            s->lastDstInfo[1]++; s->lastDstInfo[1 + place[k0]]++;
+            K.info[1]++; K.info[1 + place[k0]]++;
         }
-        k0 = k1;
     }
-    s->hDstRaw.assign(outWords, 0u);
-    DOWN(s->hDstRaw.data(), O, outWords * 4);
-    SYNC();
-    for (uint32_t k0 = 0; k0 < nreq;) {
-        uint32_t k1 = k0; while (k1 < nreq && same_spec(order[k0], order[k1])) k1++;
+    { int32_t rc_ = set_fetch_raw(c, outWords); if (rc_) return rc_; }
+    for (uint32_t k0 = 0, k1; k0 < nreq; k0 = k1) {
+        k1 = run_end(order, k0, nreq, same_spec);
         const infx_distinct_req& Q = reqs[order[k0]];
         const bool grouped = Q.group_col >= 0;
         const uint32_t gv = grouped ? ix->colValues[Q.group_col] : 1u;
-        const uint32_t *sizes = s->hDstRaw.data() + outOff[k0], *distinct = sizes + gv;
+        const uint32_t *sizes = K.raw.data() + outOff[k0], *distinct = sizes + gv;
         if (distinct[gv + 1]) return fail(INFX_ECAPACITY, "field-distinct: the hash set of a request overflowed%s");      // (sized never to: a broken table, not a large request)
         uint32_t total = 0; for (uint32_t g = 0; g < gv; g++) total += sizes[g];
         for (uint32_t k = k0; k < k1; k++) {
@@ -3876,15 +3870,11 @@ int32_t infx_field_distinct(infx_stream* s, uint32_t nreq, const infx_distinct_r
                 std::memcpy(group_distinct_out + (size_t)i * INFX_STATS_MAX_GROUPS, distinct, (size_t)gv * 4);
             }
         }
-        k0 = k1;
     }
     return INFX_OK;
 }
 int32_t infx_last_field_distinct_info(infx_stream* s, uint32_t* requests, uint32_t* launches, uint32_t* lds_passes, uint32_t* bitmap_passes, uint32_t* hash_passes) {
-    if (!s) return fail(INFX_EINVAL, "null argument%s");
-    uint32_t* out[5] = {requests, launches, lds_passes, bitmap_passes, hash_passes};
-    for (int i = 0; i < 5; i++) if (out[i]) *out[i] = s->lastDstInfo[i];
-    return INFX_OK;
+    return put_info(s, SK_DISTINCT, {requests, launches, lds_passes, bitmap_passes, hash_passes});
 }
 int32_t infx_stream_mask_slot(infx_stream* s, uint32_t slot, uint8_t** out) {
     if (!s || !out || slot >= INFX_MAX_PREFILTERS) return fail(INFX_EINVAL, "bad mask slot%s");

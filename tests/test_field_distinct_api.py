@@ -72,8 +72,11 @@ def test_symbols_are_exported_with_the_documented_signatures_and_struct_layouts(
 def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 8)()
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_field_distinct(None, 0, None, None, None, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad field-distinct arguments"
     assert L.infx_last_field_distinct_info(None, buf, buf, buf, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_engine_field_distinct(None, 0, None, None) == EINVAL
     assert L.infx_engine_field_distinct_whole(None, 0, None) == EINVAL
     assert L.infx_engine_field_distinct_groups(None, 0, None, None, None, 0) == -1

@@ -82,8 +82,11 @@ def test_symbols_are_exported_with_the_documented_signatures():
 def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 4)(); fig = E._QuantFigures()
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_field_quantiles(None, 0, None, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad field-quantiles arguments"
     assert L.infx_last_field_quantiles_info(None, buf, buf, buf, buf, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_engine_field_quantiles(None, 0, None, None) == EINVAL
     assert L.infx_engine_field_quantiles_whole(None, 0, C.byref(fig)) == EINVAL
     assert L.infx_engine_field_quantiles_groups(None, 0, None, None, None, 0) == -1

@@ -76,8 +76,11 @@ def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 4)(); fig = E._StatsFigures()
     assert L.infx_upload_column_values(None, 0, 0, None, 1, 0, 1) == EINVAL
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_field_stats(None, 0, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad field-stats arguments"
     assert L.infx_last_field_stats_info(None, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_engine_field_stats(None, 0, None, None) == EINVAL
     assert L.infx_engine_field_stats_whole(None, 0, C.byref(fig)) == EINVAL
     assert L.infx_engine_field_stats_groups(None, 0, None, None, None, 0) == -1

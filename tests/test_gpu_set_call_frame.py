@@ -1,5 +1,5 @@
-"""The frame of the engine's per-request calls (set_call, infidex_amd/csrc/host/engine.cpp) on the GPU, across the five features it carries: list_documents,
-list_groups, range_facets, field_stats and field_quantiles.
+"""The frame of the engine's per-request calls (set_call, infidex_amd/csrc/host/engine.cpp) on the GPU, across the seven features it carries: list_documents,
+list_groups, range_facets, field_stats, field_quantiles, top_groups and field_distinct.
 
 One corpus of 37 documents (two whole groups of sixteen and a partial one, four of them deleted) with an int64 column, a double column with a NaN, a string
 column and two group columns.  Per feature ONE call of sixteen requests: refused ones at the first, a middle and the last position (an unknown field, a
@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from infidex_amd import SearchEngine, Document, ListRequest
-from infidex_amd.engine import Session, GroupListRequest, RangeRequest, StatsRequest, QuantileRequest
+from infidex_amd.engine import Session, GroupListRequest, RangeRequest, StatsRequest, QuantileRequest, TopGroupsRequest, DistinctRequest
 
 pytestmark = pytest.mark.gpu
 
@@ -96,3 +96,22 @@ def test_field_quantiles(engine, sessions):
             Q(B, "size", Q3), Q(BAD, "size", Q3, "shade"), Q(C3, "price", (0.9,)), Q(A, "size", (1.0, 0.0), "shape"), Q(None, "price", Q3, "name"), Q(B, "price", Q3, "shade"),
             Q(A, "size", ()), Q(C3, "size", Q3, "size"), Q(A, "price", (0.5, 0.5)), Q(B, "size", (1.5,))]
     held(lambda r, k: sessions[k].field_quantiles(r), lambda k: sessions[k].last_field_quantiles_stats(), reqs, {0: "nosuch", 7: "syntax", 12: "quantile", 15: "[0, 1]"}, 3)
+
+
+def test_top_groups(engine, sessions):
+    # (A, "size", "shade") is one table behind requests 1, 4, 8 and 11: several figures, both directions, three pages; 3 and 12 rank by size without a field
+    T = TopGroupsRequest
+    reqs = [T(A, "shade", "size", None, False, 0, 0), T(A, "shade", "sum", "size", False, 0, 5), T(B, "shape", "mean", "price", True, 0, 40), T(None, "shape", "size", None, False, 0, 10),
+            T(A, "shade", "max", "size", True, 1, 1), T(C3, "name", "count", "price", False, 0, 40), T(A, "nosuch", "sum", "size"), T(B, "shade", "min", "size", False, 0, 40),
+            T(A, "shade", "sum", "size", True, 0, 2), T(C3, "shape", "sum", "size", False, 2, 3), T(BAD, "shade", "sum", "size"), T(A, "shade", "mean", "size", False, 2, 5),
+            T(None, "name", "size", None, True, 3, 7), T(B, "shape", "max", "price", False, 0, 1), T(A, "size", "min", "price", False, 0, 40), T(B, "shade", "sum", "nosuch")]
+    held(lambda r, k: sessions[k].top_groups(r), lambda k: sessions[k].last_top_groups_stats(), reqs, {0: "limit", 6: "nosuch", 10: "syntax", 15: "nosuch"}, 3)
+
+
+def test_field_distinct(engine, sessions):
+    # 1 and 9 are one spec, apart; 10 and 13 are grouped by their own field; 2, 8 and 14 count the string column
+    D = DistinctRequest
+    reqs = [D(A, "nosuch"), D(A, "size", "shade"), D(B, "name", "shape"), D(None, "size"), D(A, "price", "shade"), D(C3, "size", "shape"), D(B, "size"),
+            D(A, "size", "nosuch"), D(C3, "name"), D(A, "size", "shade"), D(None, "shade", "shade"), D(B, "price", "shade"), D(BAD, "size", "shade"),
+            D(C3, "size", "size"), D(A, "name"), D(BAD, "name")]
+    held(lambda r, k: sessions[k].field_distinct(r), lambda k: sessions[k].last_field_distinct_stats(), reqs, {0: "nosuch", 7: "nosuch", 12: "syntax", 15: "syntax"}, 3)

@@ -58,8 +58,11 @@ def test_symbols_are_exported_with_the_documented_signatures():
 def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 4)()
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_list_ordered(None, 0, None, None, None, None, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad listing arguments"
     assert L.infx_last_list_stats(None, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_engine_list_documents(None, 0, None, None) == EINVAL
     assert L.infx_engine_list_rows(None, 0, None, None, None, 0) == -1
     assert L.infx_engine_list_total(None, 0, buf) == EINVAL

@@ -71,8 +71,11 @@ def test_symbols_are_exported_with_the_documented_signatures():
 def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 4)(); k = C.c_int32(0)
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_range_counts(None, 0, None, None, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad range arguments"
     assert L.infx_last_range_stats(None, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_engine_range_facets(None, 0, None, None) == EINVAL
     assert L.infx_engine_range_counts(None, 0, None, 0, None, None, None) == -1
     assert L.infx_engine_range_total(None, 0, buf) == EINVAL

@@ -75,8 +75,11 @@ def test_symbols_are_exported_with_the_documented_signatures_and_struct_sizes():
 def test_null_and_bad_arguments_are_status_codes():
     L = C.CDLL(LIB_PATH)
     buf = (C.c_uint32 * 8)()
+    L.infx_last_error.restype = C.c_char_p
     assert L.infx_top_groups(None, 0, None, None, None, None, None, None) == EINVAL
+    assert L.infx_last_error() == b"bad top-groups arguments"
     assert L.infx_last_top_groups_info(None, buf, buf, buf, buf, buf, buf, buf) == EINVAL
+    assert L.infx_last_error() == b"null argument"
     assert L.infx_upload_group_rank(None, 0, 0, None) == EINVAL
     assert L.infx_engine_top_groups(None, 0, None, None) == EINVAL
     assert L.infx_engine_top_groups_rows(None, 0, None, None, None, None, 0) == -1
