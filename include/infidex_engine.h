@@ -548,6 +548,29 @@ int32_t infx_engine_group_list_rows(infx_session* s, uint32_t which, int64_t* ke
 int32_t infx_engine_group_list_totals(infx_session* s, uint32_t which, uint32_t* total_groups, uint32_t* total);
 int32_t infx_engine_group_list_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_group_list_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
+/* ---- list_group_members: the first N documents of every group, by page (not in the reference: the semantics below are this project's) --------------------
+ * Request i is infx_engine_list_groups' request plus `per_group`.  Its SET, ORDER, GROUPS and HEADS are that call's; its ROWS are exactly the rows of
+ * infx_engine_list_groups for the same filter, group_by, order_by, ascending, offset and limit, in the same order — by each group's head — with the same
+ * sizes, total_groups and total.  Every row carries the MEMBERS of its group: the first min(per_group, size) members of the group in the ORDER (key, internal
+ * index; ties by ascending index in both directions; duplicate DocumentKeys are members of their own), the head first.  "The three cheapest offers of every
+ * product family, page 7" in one call instead of one listing per row: the members are kept in the walk that counts the groups' sizes.
+ * 1 <= per_group <= 16, 1 <= limit <= 1024 and limit * per_group <= 4096 (INFX_GROUP_MEMBERS_MAX); the other limits and every refusal are
+ * infx_engine_list_groups', per request (out_status[i], message from infx_engine_group_members_error).  At most 16 requests (INFX_ECAPACITY); INFX_EHIP on an
+ * engine without a GPU, every refusal but the filter's already in out_status.  Masks, sort ranks and the sharing of head passes as there.  The members are
+ * ordered by one field only, the groups' own; nothing is cached but the masks.  Exact and deterministic: the same bytes from any session, stream and rank.
+ * Readers, for request `which` of the session's last call.  infx_engine_group_members_rows: up to cap rows — the group's code, its size and the number of
+ * members it carries — returning the page's row count (-1 for a refused request or bad arguments).  infx_engine_group_members_members: the members of ALL
+ * rows, row after row (row r's are the member_counts[r] entries behind those of the rows before it): up to cap members' DocumentKeys, internal documents and
+ * codes of the order_by column (0 without one), returning the page's member count (-1 as above) — two readers, because the rows are at most 1024 and
+ * the members at most 4096.  infx_engine_group_members_totals, _error and infx_engine_last_group_members_stats (masks built and reused, head passes,
+ * histogram passes, member walks, kernel launches) as infx_engine_list_groups' readers. */
+typedef struct infx_group_members_request { const char* filter; const char* group_by; const char* order_by; int32_t ascending; uint32_t offset; uint32_t limit; uint32_t per_group; } infx_group_members_request;
+int32_t infx_engine_list_group_members(infx_session* s, uint32_t nreq, const infx_group_members_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_group_members_rows(infx_session* s, uint32_t which, uint32_t* group_codes, uint32_t* sizes, uint32_t* member_counts, int32_t cap);
+int32_t infx_engine_group_members_members(infx_session* s, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap);
+int32_t infx_engine_group_members_totals(infx_session* s, uint32_t which, uint32_t* total_groups, uint32_t* total);
+int32_t infx_engine_group_members_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_group_members_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* member_walks, uint32_t* launches);
 /* ---- top_groups: a field's groups ranked by size, count, min, max, sum or mean, by page (not in the reference: the semantics below are this project's) ------
  * Request i ranks, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
  * filter = NULL: every live document:

@@ -540,6 +540,30 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
                           uint32_t* gcodes_out, uint32_t* sizes_out, uint32_t* counts_out /* nreq */, uint32_t* group_totals_out /* nreq */,
                           uint32_t* totals_out /* nreq */);
 int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches);
+/* infx_list_grouped's page with the first `per_group` MEMBERS of every listed group (not in the reference; DESIGN.md "list_group_members").
+ * Request i is infx_list_grouped's, field for field, plus per_group: 1 .. INFX_GROUP_MEMBERS_MAX_PER_GROUP (16), and limit * per_group <=
+ * INFX_GROUP_MEMBERS_MAX (4096).  The rows, their group codes, sizes and the three totals are exactly infx_list_grouped's of the same request, in rows_out
+ * (the heads' global internal ids) / gcodes_out / sizes_out at [i * INFX_POST_MAX_ROWS ..] and counts_out / group_totals_out / totals_out at [i].  The members
+ * of row r are the first min(per_group, size) members of its group in the ORDER (key, global internal id), the head first: per (row r, place p) the
+ * DocumentKey, the global internal id and the code of `col` (0 without a column) in member_keys_out / member_docs_out / member_codes_out at
+ * [i * INFX_GROUP_MEMBERS_MAX + r * per_group + p]; places without a member, and every place of the rows from counts_out[i] up to limit, read -1 / -1 / 0.
+ * member_counts_out[i * INFX_POST_MAX_ROWS + r]: the places of row r that hold a member.
+ * The front half is infx_list_grouped's: k_group_heads, k_group_heads_mask, the page, k_group_page.  Then, per spec:
+ *   k_group_members      takes k_group_sizes' place, one walk over the SET for as many consecutive requests of the spec as fit the whole LDS of a CU together
+ *                        (per request 2 * limit + 2 * limit * per_group words: one always fits a workgroup's): a member whose group code is among the page's
+ *                        adds to the row's LDS counter and enters (key << 32 | id) into the row's per_group LDS slots, which keep the smallest composites in
+ *                        ascending order under any interleaving (group_members.h); the LDS slots then enter the row's global slots the same way.
+ *   k_group_member_rows  the slots as documents, keys and codes.
+ * Minima and integer adds only: the same bytes from any stream, grid, placement and packing.  Works on a sharded index.  Synchronous.
+ * infx_last_group_members_stats: head passes (= specs), histogram passes, member walks (k_group_members launches) and kernel launches (the mask build
+ * included) of the stream's last call. */
+#define INFX_GROUP_MEMBERS_MAX_PER_GROUP 16
+#define INFX_GROUP_MEMBERS_MAX 4096      /* limit * per_group of a request */
+typedef struct infx_group_members_req { const uint8_t* mask; int32_t col; int32_t ascending; uint32_t offset; uint32_t limit; uint32_t digit_bits; uint32_t reserved; int32_t group_col; int32_t reserved2; uint32_t per_group; uint32_t reserved3; } infx_group_members_req;
+int32_t infx_list_group_members(infx_stream* s, uint32_t nreq, const infx_group_members_req* reqs, int32_t* rows_out, uint32_t* gcodes_out, uint32_t* sizes_out,
+                                uint32_t* member_counts_out, int64_t* member_keys_out, int32_t* member_docs_out, uint32_t* member_codes_out,
+                                uint32_t* counts_out /* nreq */, uint32_t* group_totals_out /* nreq */, uint32_t* totals_out /* nreq */);
+int32_t infx_last_group_members_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* member_walks, uint32_t* launches);
 /* A page of a document set's GROUPS ranked by a figure of the group (not in the reference: the ranking is this project's; DESIGN.md "top_groups").
  * Request i: the SET is infx_field_stats' — the documents whose byte in `mask` is 0 (a mask slot of this stream), or, mask = NULL, every document that is not
  * Deleted.  A GROUP is one code of uploaded column `group_col`: any kind, ANY number of values, its facet tie order uploaded with infx_upload_group_rank (a

@@ -1,7 +1,7 @@
 // The arithmetic of list_groups' passes (groups.hip.inc): the number whose minimum over a group is the group's head, and where a member's group code lies
 // among the sorted codes of a page.  Not in the reference: the collapsed listing is this project's ("list_groups").
 //
-// Plain C++ behind GH_FN, no HIP types: compiled into k_group_heads / k_group_heads_mask / k_group_sizes and, unchanged, into a host model that holds the
+// Plain C++ behind GH_FN, no HIP types: compiled into k_group_heads / k_group_heads_mask / k_group_sizes / k_group_members and, unchanged, into a host model that holds the
 // lookup to a linear scan and the composite to a comparison of (key, document) pairs (tests/models/group_model.cpp, tests/test_group_model.py).
 //   composite  (k << 32) | d: k the member's listing key (listing_select.h: 1 + sort rank, mirrored when descending, 1 without a column), d its document.
 //              Composites compare as the listing's order (k, d) does, so the smallest composite of a group is its head — the member that comes first in the

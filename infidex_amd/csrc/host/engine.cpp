@@ -111,6 +111,9 @@ typedef FiguresAnswer<infx_distinct_figures> DistinctAnswer;      // (whole: the
 // One request of the session's last infx_engine_list_groups: its status and message, the size of its set (total), the groups with a member, its page: per
 // row what a ListAnswer holds, the group's code and its size
 struct GroupListAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes; };
+// One request of the session's last infx_engine_list_group_members: its status and message, both totals, per row of its page the group's code, its size and
+// the number of members it carries; keys / docs / codes: the members of all rows, row after row (what a ListAnswer holds of a row, per member)
+struct GroupMembersAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<uint32_t> gcodes, sizes, held; };
 // One request of the session's last infx_engine_top_groups: its status and message, the size of its set (total), the groups with a member, the group column,
 // whether it had a field, its page: per row the group's code, its members and — with a field — its figures
 struct TopAnswer : Answer { uint32_t totalGroups = 0; int32_t groupCol = -1; bool hasField = false; std::vector<uint32_t> codes, sizes; std::vector<infx_stats_figures> figures; };
@@ -139,6 +142,8 @@ struct infx_session {
     struct Qnt : LastCall<QuantAnswer> { uint32_t passes = 0, launches = 0, place[3] = {0, 0, 0}; } qnt; int32_t qntDigitBits = 0;
     // infx_engine_list_groups: head passes, histogram passes, kernel launches (the digit width is lstDigitBits)
     struct Grp : LastCall<GroupListAnswer> { uint32_t heads = 0, passes = 0, launches = 0; } grp;
+    // infx_engine_list_group_members: head passes, histogram passes, member walks, kernel launches (the digit width is lstDigitBits)
+    struct Mem : LastCall<GroupMembersAnswer> { uint32_t heads = 0, passes = 0, walks = 0, launches = 0; } mem;
     // infx_engine_top_groups: accumulate passes, select passes, kernel launches, tables accumulated in a workgroup's LDS / a CU's whole LDS / global memory
     // (the digit width is lstDigitBits)
     struct Top : LastCall<TopAnswer> { uint32_t accumulates = 0, passes = 0, launches = 0, place[3] = {0, 0, 0}; } top;
@@ -3732,24 +3737,30 @@ int32_t infx_engine_set_quantile_digit_bits(infx_session* S, int32_t bits) {
 // Per request, as infx_engine_list_documents: the filter through the filter cache, its mask through the session's mask cache, order_by to its column, whose
 // sort rank is built on first use; group_by to its column (any kind: the group is the dictionary code).  infx_list_grouped then finds the heads of every
 // (mask, group column, order column, direction) once and pages over them; the answers stay on the session for the readers.
+extern "C++" {
+// The two per-request steps list_groups and list_group_members (`name`) share, for a request R with their common fields.  What needs no device — the page,
+// group_by, order_by — wrong: the refusal's message, else "".  Caller holds e->filterMu.
+template <class Q> static std::string group_request_problem(infx_engine* e, const char* name, const Q& R) {
+    if (const char* bad = page_problem(R.limit, R.offset)) return bad;
+    if (!R.group_by) return std::string(name) + " needs a group_by field";
+    if (column_named(e, R.group_by) < 0) return std::string(name) + ": no group_by field named '" + R.group_by + "'";
+    if (R.order_by && column_named(e, R.order_by) < 0) return std::string(name) + ": no field named '" + R.order_by + "'";
+    return "";
+}
+// its columns and its filter: group_by to *gcol, order_by to *col (its sort rank built on first use), the filter through the filter cache; refusals are F's
+template <class F, class Q> static void group_request_resolve(F& call, const char* name, uint32_t i, const Q& R, int32_t* col, int32_t* gcol) {
+    std::string why;
+    if ((*gcol = column_named(call.S->e, R.group_by)) < 0) return call.refuse(i, INFX_EINVAL, std::string(name) + ": no group_by field named '" + R.group_by + "'");
+    const int32_t rc = order_column(call.S->e, name, R.order_by, col, &why);
+    if (rc) call.refuse(i, rc, why); else call.filter(i, R.filter);
+}
+}
 int32_t infx_engine_list_groups(infx_session* S, uint32_t nreq, const infx_group_list_request* reqs, int32_t* out_status) {
     std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; col.fill(-1);
     std::vector<infx_group_list_req> dr; PageRows P; std::vector<uint32_t> gcodes, sizes, groups;
-    auto no_group = [&](uint32_t i) { return std::string("list_groups: no group_by field named '") + reqs[i].group_by + "'"; };
     return set_call(S, &infx_session::grp, "list_groups", "list_groups requests", true, nreq, reqs, out_status,
-        [&](auto& F, uint32_t i) {
-            if (const char* bad = page_problem(reqs[i].limit, reqs[i].offset)) F.refuse(i, INFX_EINVAL, bad);
-            else if (!reqs[i].group_by) F.refuse(i, INFX_EINVAL, "list_groups needs a group_by field");
-            else if (column_named(S->e, reqs[i].group_by) < 0) F.refuse(i, INFX_EINVAL, no_group(i));
-            else if (reqs[i].order_by && column_named(S->e, reqs[i].order_by) < 0)
-                F.refuse(i, INFX_EINVAL, std::string("list_groups: no field named '") + reqs[i].order_by + "'");
-        },
-        [&](auto& F, uint32_t i) {
-            std::string why;
-            if ((gcol[i] = column_named(S->e, reqs[i].group_by)) < 0) return F.refuse(i, INFX_EINVAL, no_group(i));
-            const int32_t rc = order_column(S->e, "list_groups", reqs[i].order_by, &col[i], &why);
-            if (rc) F.refuse(i, rc, why); else F.filter(i, reqs[i].filter);
-        },
+        [&](auto& F, uint32_t i) { const std::string bad = group_request_problem(S->e, "list_groups", reqs[i]); if (!bad.empty()) F.refuse(i, INFX_EINVAL, bad); },
+        [&](auto& F, uint32_t i) { group_request_resolve(F, "list_groups", i, reqs[i], &col[i], &gcol[i]); },
         [&](auto& F) {
             for (uint32_t i : F.who) {
                 infx_group_list_req R{};
@@ -3789,6 +3800,74 @@ int32_t infx_engine_group_list_error(infx_session* S, uint32_t which, char* out,
 int32_t infx_engine_last_group_list_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->grp.masks.built}, {masks_reused, S->grp.masks.reused}, {head_passes, S->grp.heads}, {hist_passes, S->grp.passes}, {launches, S->grp.launches}});
+}
+
+// ---- list_group_members: list_groups' rows, each with the first per_group members of its group (not in the reference) -----------------------------------
+// Per request as infx_engine_list_groups, through the same two steps; per_group is checked with the page.  infx_list_group_members then returns every page
+// with its rows' members; the answers stay on the session for the readers, the members of a page row after row.
+int32_t infx_engine_list_group_members(infx_session* S, uint32_t nreq, const infx_group_members_request* reqs, int32_t* out_status) {
+    std::array<int32_t, INFX_MAX_PREFILTERS> col, gcol; col.fill(-1);
+    std::vector<infx_group_members_req> dr;
+    std::vector<int32_t> rows, mdocs; std::vector<int64_t> mkeys; std::vector<uint32_t> gcodes, sizes, held, mcodes, counts, groups, totals;
+    const size_t R = INFX_POST_MAX_ROWS, M = INFX_GROUP_MEMBERS_MAX;
+    return set_call(S, &infx_session::mem, "list_group_members", "list_group_members requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
+            const std::string bad = group_request_problem(S->e, "list_group_members", reqs[i]);
+            if (!bad.empty()) F.refuse(i, INFX_EINVAL, bad);
+            else if (reqs[i].per_group < 1 || reqs[i].per_group > INFX_GROUP_MEMBERS_MAX_PER_GROUP) F.refuse(i, INFX_EINVAL, "list_group_members: per_group is 1 .. 16");
+            else if ((uint64_t)reqs[i].limit * reqs[i].per_group > INFX_GROUP_MEMBERS_MAX) F.refuse(i, INFX_EINVAL, "list_group_members: limit * per_group is at most 4096");
+        },
+        [&](auto& F, uint32_t i) { group_request_resolve(F, "list_group_members", i, reqs[i], &col[i], &gcol[i]); },
+        [&](auto& F) {
+            for (uint32_t i : F.who) {
+                infx_group_members_req Q{};
+                Q.mask = F.mc.mask(i); Q.col = col[i]; Q.group_col = gcol[i]; Q.ascending = reqs[i].ascending ? 1 : 0; Q.offset = reqs[i].offset;
+                Q.limit = reqs[i].limit; Q.digit_bits = (uint32_t)S->lstDigitBits; Q.per_group = reqs[i].per_group;
+                dr.push_back(Q);
+            }
+            const size_t m = std::max<size_t>(dr.size(), 1);
+            rows.resize(m * R); gcodes.resize(m * R); sizes.resize(m * R); held.resize(m * R); mkeys.resize(m * M); mdocs.resize(m * M); mcodes.resize(m * M);
+            counts.assign(m, 0); groups.assign(m, 0); totals.assign(m, 0);
+            return infx_list_group_members(S->stream, (uint32_t)dr.size(), dr.data(), rows.data(), gcodes.data(), sizes.data(), held.data(), mkeys.data(), mdocs.data(),
+                                           mcodes.data(), counts.data(), groups.data(), totals.data());
+        },
+        [&](auto& F) {
+            infx_last_group_members_stats(S->stream, &S->mem.heads, &S->mem.passes, &S->mem.walks, &S->mem.launches);
+            for (size_t j = 0; j < dr.size(); j++) {
+                GroupMembersAnswer& A = S->mem.ans[F.who[j]];
+                const size_t c = std::min<size_t>(counts[j], dr[j].limit), pg = dr[j].per_group;
+                A.total = totals[j]; A.totalGroups = groups[j]; page_of(A.gcodes, gcodes, j, c); page_of(A.sizes, sizes, j, c); page_of(A.held, held, j, c);
+                for (size_t r = 0; r < c; r++) {
+                    const size_t at = j * M + r * pg, h = std::min<size_t>(A.held[r], pg);
+                    A.keys.insert(A.keys.end(), mkeys.begin() + at, mkeys.begin() + at + h); A.docs.insert(A.docs.end(), mdocs.begin() + at, mdocs.begin() + at + h);
+                    A.codes.insert(A.codes.end(), mcodes.begin() + at, mcodes.begin() + at + h);
+                }
+            }
+        });
+}
+// request `which` of the session's last infx_engine_list_group_members: per row of its page the group's code, its size and the members it carries; returns
+// the page's row count, -1 on error (also for a refused request)
+int32_t infx_engine_group_members_rows(infx_session* S, uint32_t which, uint32_t* group_codes, uint32_t* sizes, uint32_t* member_counts, int32_t cap) {
+    const GroupMembersAnswer* A = answer_at(S ? &S->mem.ans : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!group_codes || !sizes || !member_counts))) return -1;
+    const size_t c = std::min<size_t>(A->gcodes.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(group_codes, A->gcodes.data(), c * 4); std::memcpy(sizes, A->sizes.data(), c * 4); std::memcpy(member_counts, A->held.data(), c * 4); }
+    return (int32_t)A->gcodes.size();
+}
+// the members of all its rows, row after row, as page_rows: returns the page's member count
+int32_t infx_engine_group_members_members(infx_session* S, uint32_t which, int64_t* keys, int32_t* docs, uint32_t* codes, int32_t cap) {
+    return page_rows(answer_at(S ? &S->mem.ans : nullptr, which), keys, docs, codes, cap);
+}
+int32_t infx_engine_group_members_totals(infx_session* S, uint32_t which, uint32_t* total_groups, uint32_t* total) {
+    const GroupMembersAnswer* A = answer_at(S ? &S->mem.ans : nullptr, which);
+    if (A && total_groups) *total_groups = A->totalGroups;
+    return answer_total(total_groups ? A : nullptr, total, "no such request in the session's last list_group_members call");
+}
+int32_t infx_engine_group_members_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->mem.ans : nullptr, which), out, cap); }
+int32_t infx_engine_last_group_members_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* member_walks, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->mem.masks.built}, {masks_reused, S->mem.masks.reused}, {head_passes, S->mem.heads}, {hist_passes, S->mem.passes}, {member_walks, S->mem.walks},
+                      {launches, S->mem.launches}});
 }
 
 // ---- top_groups: the groups of a field ranked by their size or by the count, min, max, sum or mean of a second field, by page (not in the reference) --------

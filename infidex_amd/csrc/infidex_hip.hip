@@ -267,6 +267,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
 #include "groups.hip.inc"
+#include "group_members.hip.inc"
 #include "top_groups.hip.inc"
 #include "distinct.hip.inc"
 #include "quantiles.hip.inc"
@@ -348,6 +349,8 @@ enum SetKind {
                       // Requests, accumulate passes, select passes, launches, tables in a workgroup's LDS / a CU's whole LDS / global memory
     SK_DISTINCT,      // infx_field_distinct: one spec's pair set at a time — [rows | union row] or [hash set | side row] | every spec's [sizes | distinct | whole | overflow] |
                       // their host copy.  Requests, kernel launches, specs marked in LDS / in a global bitmap / in a hash set
+    SK_MEMBERS,       // infx_list_group_members (its pages in SK_LIST's buffers): SK_GROUPED's workspace | per request its slots, limit and per_group, the members'
+                      // keys, documents and codes, the rows' member counts.  Head passes, histogram passes, member walks, kernel launches
     SK_KINDS
 };
 struct SetKindState {
@@ -3105,9 +3108,9 @@ static void set_order(uint32_t nreq, const SetKey* key, uint32_t* order) {
 }
 // what request Q keeps of B, the one before it in that order: 1 the mask's flags, 3 the value column's ranks as well
 static uint32_t set_reuse(const SetKey& B, const SetKey& Q) { return B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
-// The frame of a set call.  What the seven kinds' starts differ in: the two refusals' words; whether the rows need the documents' keys (the listings); where
+// The frame of a set call.  What the eight kinds' starts differ in: the two refusals' words; whether the rows need the documents' keys (the listings); where
 // info[] counts requests and launches (-1: not at all; the mask build is the first launch of a kind that counts them); whether the device takes the requests
-// in set_order's order (infx_list_grouped keeps one of its own, infx_list_ordered the caller's).
+// in set_order's order (infx_list_grouped and infx_list_group_members keep one of their own, infx_list_ordered the caller's).
 struct SetKindSpec { const char *badArgs, *tooMany; bool needKeys; int requestsAt, launchesAt; bool ordered; };
 static const SetKindSpec SET_KINDS[SK_KINDS] = {
     {"bad listing arguments%s", "more than INFX_MAX_PREFILTERS (16) listing requests in one call%s", true, -1, 1, false},
@@ -3117,6 +3120,7 @@ static const SetKindSpec SET_KINDS[SK_KINDS] = {
     {"bad grouped-listing arguments%s", "more than INFX_MAX_PREFILTERS (16) grouped-listing requests in one call%s", true, -1, 2, false},
     {"bad top-groups arguments%s", "more than 16 top-groups requests in one call%s", false, 0, 3, true},
     {"bad field-distinct arguments%s", "more than 16 field-distinct requests in one call%s", false, 0, 1, true},
+    {"bad group-members arguments%s", "more than INFX_MAX_PREFILTERS (16) group-members requests in one call%s", true, -1, 3, false},
 };
 static_assert(RB_MAX_REQS == INFX_MAX_PREFILTERS && STS_MAX_REQS == INFX_MAX_PREFILTERS && QNT_MAX_REQS == INFX_MAX_PREFILTERS && TOP_MAX_REQS == INFX_MAX_PREFILTERS &&
               DST_MAX_REQS == INFX_MAX_PREFILTERS, "every set call takes as many requests as a mask build takes filters");
@@ -3189,7 +3193,7 @@ static int32_t set_fetch_raw(const SetCall& c, size_t words) {
     SYNC();
     return INFX_OK;
 }
-// one reader behind the seven infx_last_*: out[i] (where not null) takes counter i of the kind's last call
+// one reader behind the eight infx_last_*: out[i] (where not null) takes counter i of the kind's last call
 static int32_t put_info(const infx_stream* s, SetKind kind, std::initializer_list<uint32_t*> out) {
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     const uint32_t* v = s->kind[kind].info;
@@ -3247,7 +3251,7 @@ static int32_t list_prepare(infx_stream* s, int32_t n, uint32_t nreq, const DevL
     return INFX_OK;
 }
 // request i of the layout: select, count, prefix, gather and sort on the stream, and its rows' way back to the caller's keys / docs / codes (the request's own
-// rows: D.limit of each).  *histPasses / *launches grow by what was enqueued.
+// rows: D.limit of each; an array that is null is not fetched).  *histPasses / *launches grow by what was enqueued.
 static int32_t list_enqueue(infx_stream* s, const ListLayout& L, uint32_t i, const DevListReq& D, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
                             uint32_t* histPasses, uint32_t* launches) {
     const int32_t n = L.n; const uint32_t nRanges = L.nRanges, tiles = L.tiles; const size_t R = INFX_POST_MAX_ROWS;
@@ -3273,9 +3277,9 @@ static int32_t list_enqueue(infx_stream* s, const ListLayout& L, uint32_t i, con
                                                  (uint32_t*)(O + L.oCodes) + (size_t)i * R, L.count(i), L.total(i));
     HIPCHK(hipGetLastError());
     ++*launches;
-    DOWN(keys_out, (long long*)O + (size_t)i * R, (size_t)D.limit * 8);
-    DOWN(docs_out, L.docs(i), (size_t)D.limit * 4);
-    DOWN(codes_out, (uint32_t*)(O + L.oCodes) + (size_t)i * R, (size_t)D.limit * 4);
+    if (keys_out) DOWN(keys_out, (long long*)O + (size_t)i * R, (size_t)D.limit * 8);
+    if (docs_out) DOWN(docs_out, L.docs(i), (size_t)D.limit * 4);
+    if (codes_out) DOWN(codes_out, (uint32_t*)(O + L.oCodes) + (size_t)i * R, (size_t)D.limit * 4);
     return INFX_OK;
 }
 // a request's page: limit, offset and digit width in range
@@ -3549,27 +3553,29 @@ int32_t infx_last_field_quantiles_info(infx_stream* s, uint32_t* requests, uint3
     return put_info(s, SK_QUANT, {requests, hist_passes, launches, digit_bits, lds_rows, global_rows});
 }
 // ---- list_groups: a page of the heads of a document set's groups, in the order of a column, with the groups' sizes (groups.hip.inc) ----
-int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* gcodes_out,
-                          uint32_t* sizes_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
-    SetCall c;
-    const bool badArgs = nreq && (!reqs || !keys_out || !docs_out || !codes_out || !gcodes_out || !sizes_out || !counts_out || !group_totals_out || !totals_out);
-    { int32_t rc_ = set_call_open(&c, s, SK_GROUPED, badArgs, nreq); if (rc_) return rc_; }
-    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; uint32_t* order = c.order;
+// The part infx_list_grouped and infx_list_group_members share: everything but the walk that follows a spec's pages.  What that walk finds enqueued on the
+// stream, for the requests [k0, k1) of one spec in the device's order (request k is the caller's order[k]):
+struct GroupPages {
+    DevGroupSpec G;                         // the spec: its set, columns and head table
+    uint32_t k0, k1; const uint32_t* order; const DevListReq* D; const ListLayout* L;      // D[k]: the page as a listing over the heads mask; L->count(k): its rows
+    uint32_t *sorted, *perm, *sizes;        // at [k * INFX_POST_MAX_ROWS ..]: the page's group codes ascending, the row of each, the rows' sizes (zeroed)
+};
+extern "C++" {
+// Req: infx_group_list_req, or a struct that begins with its fields.  The requests are checked and the call begun (c); info[]: where the call counts its head
+// passes, histogram passes and kernel launches.  Per spec: head pass, heads mask, the pages (their rows to keys_out / docs_out / codes_out, each skipped
+// where null), k_group_page, then walk(P) — which fills P.sizes and enqueues what else the call returns — and the way back of the group codes, the sizes and
+// the totals.  Not synchronised.
+template <class Req, class Walk>
+static int32_t grouped_pages(SetCall& c, const Req* reqs, uint32_t* heads, uint32_t* histPasses, uint32_t* launches, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out,
+                             uint32_t* gcodes_out, uint32_t* sizes_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out, Walk walk) {
+    infx_stream* s = c.s; infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const uint32_t nreq = c.nreq; uint32_t* order = c.order;
     uint32_t gvMax = 1;
-    for (uint32_t i = 0; i < nreq; i++) {
-        const infx_group_list_req& Q = reqs[i];
-        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
-        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "grouped listing"); if (rc_) return rc_; }
-        { int32_t rc_ = check_group_column(ix, Q.group_col, "grouped listing"); if (rc_) return rc_; }
-        gvMax = std::max(gvMax, ix->colValues[Q.group_col]);
-    }
-    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
-    if (!nreq) return INFX_OK;
+    for (uint32_t i = 0; i < nreq; i++) gvMax = std::max(gvMax, ix->colValues[reqs[i].group_col]);
     // requests of one spec — (mask, group column, order column, direction) — follow one another: they share the head pass, the heads mask and the size walk
     for (uint32_t i = 0; i < nreq; i++) order[i] = i;
-    auto same_spec = [&](uint32_t a, uint32_t b) { const infx_group_list_req &A = reqs[a], &B = reqs[b]; return A.mask == B.mask && A.group_col == B.group_col && A.col == B.col && (A.ascending != 0) == (B.ascending != 0); };
+    auto same_spec = [&](uint32_t a, uint32_t b) { const Req &A = reqs[a], &B = reqs[b]; return A.mask == B.mask && A.group_col == B.group_col && A.col == B.col && (A.ascending != 0) == (B.ascending != 0); };
     std::stable_sort(order, order + nreq, [&](uint32_t a, uint32_t b) {
-        const infx_group_list_req &A = reqs[a], &B = reqs[b];
+        const Req &A = reqs[a], &B = reqs[b];
         if (A.mask != B.mask) return std::less<const uint8_t*>()(A.mask, B.mask);
         if (A.group_col != B.group_col) return A.group_col < B.group_col;
         return A.col != B.col ? A.col < B.col : (A.ascending != 0) < (B.ascending != 0); });
@@ -3586,7 +3592,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
     // the pages are listings over the heads mask
     DevListReq D[INFX_MAX_PREFILTERS];
     for (uint32_t k = 0; k < nreq; k++) {
-        const infx_group_list_req& Q = reqs[order[k]];
+        const Req& Q = reqs[order[k]];
         D[k] = list_dev_req(ix, (const uint8_t*)(G0 + oHeads), Q.col, Q.ascending != 0, Q.offset, Q.limit, Q.digit_bits);
     }
     ListLayout L;
@@ -3595,7 +3601,7 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
     uint32_t spec = 0;
     for (uint32_t k0 = 0, k1; k0 < nreq; k0 = k1, spec++) {
         k1 = run_end(order, k0, nreq, same_spec);
-        const infx_group_list_req& Q = reqs[order[k0]];
+        const Req& Q = reqs[order[k0]];
         DevGroupSpec G{};
         G.mask = set_flags(ix, Q.mask); G.gcodes = ix->colCodes[Q.group_col]; G.gvals = ix->colValues[Q.group_col];
         G.ocodes = D[k0].codes; G.orank = D[k0].rank; G.onvals = D[k0].nvals; G.ascending = D[k0].ascending;
@@ -3611,30 +3617,17 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             k_group_heads<<<grid, threads, lds, s->st>>>(G, n);
             k_group_heads_mask<<<(int)std::min<int64_t>(FCM_MAXGRID, (groups + GRP_THREADS - 1) / GRP_THREADS), GRP_THREADS, 0, s->st>>>(G, n);
             HIPCHK(hipGetLastError());
-            K.info[0]++; K.info[2] += 2;
+            ++*heads; *launches += 2;
         }
         for (uint32_t k = k0; k < k1; k++) {
             const size_t at = (size_t)order[k] * R;
-            int32_t rc_ = list_enqueue(s, L, k, D[k], keys_out + at, docs_out + at, codes_out + at, &K.info[1], &K.info[2]); if (rc_) return rc_;
+            int32_t rc_ = list_enqueue(s, L, k, D[k], keys_out ? keys_out + at : nullptr, docs_out ? docs_out + at : nullptr, codes_out ? codes_out + at : nullptr, histPasses, launches);
+            if (rc_) return rc_;
         }
         k_group_page<<<k1 - k0, LST_SORT_THREADS, 0, s->st>>>(G.gcodes, n, L.docs(k0), L.count(k0), dGc + (size_t)k0 * R, dSorted + (size_t)k0 * R, dPerm + (size_t)k0 * R, dSizes + (size_t)k0 * R);
         HIPCHK(hipGetLastError());
-        K.info[2]++;
-        if (n > 0) {
-            DevGroupSizes Z{};
-            Z.mask = G.mask; Z.gcodes = G.gcodes; Z.nreq = k1 - k0;
-            uint32_t words = 0;
-            for (uint32_t k = k0; k < k1; k++) {
-                const uint32_t q = k - k0;
-                Z.cnt[q] = L.count(k); Z.sorted[q] = dSorted + (size_t)k * R; Z.perm[q] = dPerm + (size_t)k * R; Z.sizes[q] = dSizes + (size_t)k * R;
-                Z.ldsOff[q] = words; Z.limit[q] = D[k].limit; words += 2u * D[k].limit;
-            }
-            int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, words, &threads, &grid); if (rc_) return rc_; }
-            HIPCHK(lds_limit((const void*)k_group_sizes, ix->cfg.device, (size_t)words * 4));
-            k_group_sizes<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
-            HIPCHK(hipGetLastError());
-            K.info[2]++;
-        }
+        ++*launches;
+        { const GroupPages P{G, k0, k1, order, D, &L, dSorted, dPerm, dSizes}; int32_t rc_ = walk(P); if (rc_) return rc_; }
         for (uint32_t k = k0; k < k1; k++) {
             const uint32_t i = order[k];
             DOWN(gcodes_out + (size_t)i * R, dGc + (size_t)k * R, (size_t)D[k].limit * 4);
@@ -3644,11 +3637,124 @@ int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_r
             DOWN(totals_out + i, dTot + spec, 4);
         }
     }
+    return INFX_OK;
+}
+}
+int32_t infx_list_grouped(infx_stream* s, uint32_t nreq, const infx_group_list_req* reqs, int64_t* keys_out, int32_t* docs_out, uint32_t* codes_out, uint32_t* gcodes_out,
+                          uint32_t* sizes_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
+    SetCall c;
+    const bool badArgs = nreq && (!reqs || !keys_out || !docs_out || !codes_out || !gcodes_out || !sizes_out || !counts_out || !group_totals_out || !totals_out);
+    { int32_t rc_ = set_call_open(&c, s, SK_GROUPED, badArgs, nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_group_list_req& Q = reqs[i];
+        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "grouped listing"); if (rc_) return rc_; }
+        { int32_t rc_ = check_group_column(ix, Q.group_col, "grouped listing"); if (rc_) return rc_; }
+    }
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
+    if (!nreq) return INFX_OK;
+    // the walk behind a spec's pages: the sizes of the listed groups
+    auto sizes_walk = [&](const GroupPages& P) -> int32_t {
+        if (n <= 0) return INFX_OK;
+        const size_t R = INFX_POST_MAX_ROWS;
+        DevGroupSizes Z{};
+        Z.mask = P.G.mask; Z.gcodes = P.G.gcodes; Z.nreq = P.k1 - P.k0;
+        uint32_t words = 0;
+        for (uint32_t k = P.k0; k < P.k1; k++) {
+            const uint32_t q = k - P.k0;
+            Z.cnt[q] = P.L->count(k); Z.sorted[q] = P.sorted + (size_t)k * R; Z.perm[q] = P.perm + (size_t)k * R; Z.sizes[q] = P.sizes + (size_t)k * R;
+            Z.ldsOff[q] = words; Z.limit[q] = P.D[k].limit; words += 2u * P.D[k].limit;
+        }
+        int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, words, &threads, &grid); if (rc_) return rc_; }
+        HIPCHK(lds_limit((const void*)k_group_sizes, ix->cfg.device, (size_t)words * 4));
+        k_group_sizes<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
+        HIPCHK(hipGetLastError());
+        K.info[2]++;
+        return INFX_OK;
+    };
+    { int32_t rc_ = grouped_pages(c, reqs, &K.info[0], &K.info[1], &K.info[2], keys_out, docs_out, codes_out, gcodes_out, sizes_out, counts_out, group_totals_out, totals_out, sizes_walk);
+      if (rc_) return rc_; }
     SYNC();
     return INFX_OK;
 }
 int32_t infx_last_group_list_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* launches) {
     return put_info(s, SK_GROUPED, {head_passes, hist_passes, launches});
+}
+// ---- list_group_members: list_groups' page with the first per_group members of every listed group (group_members.hip.inc) ----
+static_assert(GM_MAX_PER_GROUP == INFX_GROUP_MEMBERS_MAX_PER_GROUP && GM_MAX_SLOTS == INFX_GROUP_MEMBERS_MAX && GH_MAX_CODES == INFX_POST_MAX_ROWS, "group_members.h's limits are the interface's");
+static_assert(gm_lds_words(INFX_POST_MAX_ROWS, INFX_GROUP_MEMBERS_MAX / INFX_POST_MAX_ROWS) <= STS_LDS_WORDS && gm_lds_words(INFX_GROUP_MEMBERS_MAX / INFX_GROUP_MEMBERS_MAX_PER_GROUP, INFX_GROUP_MEMBERS_MAX_PER_GROUP) <= STS_LDS_WORDS,
+              "one request always fits a workgroup's LDS");
+int32_t infx_list_group_members(infx_stream* s, uint32_t nreq, const infx_group_members_req* reqs, int32_t* rows_out, uint32_t* gcodes_out, uint32_t* sizes_out,
+                                uint32_t* member_counts_out, int64_t* member_keys_out, int32_t* member_docs_out, uint32_t* member_codes_out,
+                                uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {
+    SetCall c;
+    const bool badArgs = nreq && (!reqs || !rows_out || !gcodes_out || !sizes_out || !member_counts_out || !member_keys_out || !member_docs_out || !member_codes_out ||
+                                  !counts_out || !group_totals_out || !totals_out);
+    { int32_t rc_ = set_call_open(&c, s, SK_MEMBERS, badArgs, nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_group_members_req& Q = reqs[i];
+        { int32_t rc_ = check_page_request(Q.limit, Q.offset, Q.digit_bits); if (rc_) return rc_; }
+        if (Q.per_group < 1 || Q.per_group > INFX_GROUP_MEMBERS_MAX_PER_GROUP) return fail(INFX_EINVAL, "a group-members request keeps 1 .. INFX_GROUP_MEMBERS_MAX_PER_GROUP (16) members per group%s");
+        if (Q.limit * Q.per_group > INFX_GROUP_MEMBERS_MAX) return fail(INFX_EINVAL, "a group-members request's limit * per_group is at most INFX_GROUP_MEMBERS_MAX (4096)%s");
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, false, "group-members request"); if (rc_) return rc_; }
+        { int32_t rc_ = check_group_column(ix, Q.group_col, "group-members request"); if (rc_) return rc_; }
+    }
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
+    if (!nreq) return INFX_OK;
+    // output, request k of the device's order at [k * M ..]: [slots (all ones) | member keys | member documents | member codes], then R member counts each
+    const size_t R = INFX_POST_MAX_ROWS, M = INFX_GROUP_MEMBERS_MAX;
+    const size_t oKeys = (size_t)nreq * M * 8, oDocs = oKeys + (size_t)nreq * M * 8, oCodes = oDocs + (size_t)nreq * M * 4, oHeld = oCodes + (size_t)nreq * M * 4;
+    GROW(K.out, K.capOut, oHeld + (size_t)nreq * R * 4);
+    char* O = (char*)K.out;
+    unsigned long long* dSlots = (unsigned long long*)O; long long* dKeys = (long long*)(O + oKeys); int32_t* dDocs = (int32_t*)(O + oDocs);
+    uint32_t* dCodes = (uint32_t*)(O + oCodes); uint32_t* dHeld = (uint32_t*)(O + oHeld);
+    HIPCHK(hipMemsetAsync(dSlots, 0xFF, (size_t)nreq * M * 8, s->st));
+    s->unsynced = true;
+    // the walk behind a spec's pages: the sizes of the listed groups and their first members, for as many consecutive requests per launch as the LDS of a CU holds
+    auto members_walk = [&](const GroupPages& P) -> int32_t {
+        DevMemberRows W{};
+        for (uint32_t k0 = P.k0, k1; k0 < P.k1; k0 = k1) {
+            DevGroupMembers Z{};
+            Z.mask = P.G.mask; Z.gcodes = P.G.gcodes; Z.gvals = P.G.gvals; Z.ocodes = P.G.ocodes; Z.orank = P.G.orank; Z.onvals = P.G.onvals; Z.ascending = P.G.ascending;
+            uint32_t words = 0;
+            for (k1 = k0; k1 < P.k1; k1++) {
+                const infx_group_members_req& Q = reqs[P.order[k1]];
+                const uint32_t w = gm_lds_words(Q.limit, Q.per_group), q = k1 - k0;
+                if (q && words + w > GM_PACK_LDS_WORDS) break;
+                Z.cnt[q] = P.L->count(k1); Z.sorted[q] = P.sorted + (size_t)k1 * R; Z.perm[q] = P.perm + (size_t)k1 * R; Z.sizes[q] = P.sizes + (size_t)k1 * R;
+                Z.slots[q] = dSlots + (size_t)k1 * M; Z.ldsOff[q] = words; Z.limit[q] = Q.limit; Z.perGroup[q] = Q.per_group; words += w;
+                W.limit[k1 - P.k0] = Q.limit; W.perGroup[k1 - P.k0] = Q.per_group;
+            }
+            Z.nreq = k1 - k0;
+            if (n <= 0) continue;
+            int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, words + GM_STATIC_LDS_WORDS, &threads, &grid); if (rc_) return rc_; }
+            HIPCHK(lds_limit((const void*)k_group_members, ix->cfg.device, (size_t)words * 4));
+            k_group_members<<<grid, threads, (size_t)words * 4, s->st>>>(Z, n);
+            HIPCHK(hipGetLastError());
+            K.info[2]++; K.info[3]++;
+        }
+        k_group_member_rows<<<P.k1 - P.k0, LST_SORT_THREADS, 0, s->st>>>(dSlots + (size_t)P.k0 * M, W, P.G.ocodes, n, (const long long*)ix->d.docKeyAll, dKeys + (size_t)P.k0 * M,
+                                                                        dDocs + (size_t)P.k0 * M, dCodes + (size_t)P.k0 * M, dHeld + (size_t)P.k0 * R);
+        HIPCHK(hipGetLastError());
+        K.info[3]++;
+        for (uint32_t k = P.k0; k < P.k1; k++) {
+            const uint32_t i = P.order[k]; const size_t places = (size_t)reqs[i].limit * reqs[i].per_group;
+            DOWN(member_keys_out + (size_t)i * M, dKeys + (size_t)k * M, places * 8);
+            DOWN(member_docs_out + (size_t)i * M, dDocs + (size_t)k * M, places * 4);
+            DOWN(member_codes_out + (size_t)i * M, dCodes + (size_t)k * M, places * 4);
+            DOWN(member_counts_out + (size_t)i * R, dHeld + (size_t)k * R, (size_t)reqs[i].limit * 4);
+        }
+        return INFX_OK;
+    };
+    { int32_t rc_ = grouped_pages(c, reqs, &K.info[0], &K.info[1], &K.info[3], nullptr, rows_out, nullptr, gcodes_out, sizes_out, counts_out, group_totals_out, totals_out, members_walk);
+      if (rc_) return rc_; }
+    SYNC();
+    return INFX_OK;
+}
+int32_t infx_last_group_members_stats(infx_stream* s, uint32_t* head_passes, uint32_t* hist_passes, uint32_t* member_walks, uint32_t* launches) {
+    return put_info(s, SK_MEMBERS, {head_passes, hist_passes, member_walks, launches});
 }
 // ---- top_groups: a page of a document set's groups, ranked by a figure of the group (top_groups.hip.inc) ----
 int32_t infx_top_groups(infx_stream* s, uint32_t nreq, const infx_top_req* reqs, uint32_t* codes_out, infx_stats_slot* slots_out, uint32_t* counts_out, uint32_t* group_totals_out, uint32_t* totals_out) {

@@ -1,9 +1,9 @@
 // The set walk: how a thread reads the 16 consecutive documents it takes from a document set.  The one reader behind list_documents (listing.hip.inc),
-// range_facets (ranges.hip.inc), field_stats (stats.hip.inc) and list_groups (groups.hip.inc).  Not in the reference: these features are this project's
+// range_facets (ranges.hip.inc), field_stats (stats.hip.inc), list_groups (groups.hip.inc) and list_group_members (group_members.hip.inc).  Not in the reference: these features are this project's
 // ("The set walk").
 //
 // Plain C++ behind SW_FN, no HIP types: compiled into k_list_hist / k_list_count / k_list_gather / k_range_counts / k_field_stats / k_group_heads /
-// k_group_heads_mask / k_group_sizes and, unchanged, into a host model that holds every function to a definition written byte by byte, on heap blocks of
+// k_group_heads_mask / k_group_sizes / k_group_members and, unchanged, into a host model that holds every function to a definition written byte by byte, on heap blocks of
 // exactly n elements under the address sanitizer (tests/models/set_walk_model.cpp, tests/test_set_walk_model.py).
 //   set        a byte per document, 0 = in the set (a pre-filter mask or the index's Deleted flags); a null pointer: every document.  Neither the flags nor
 //              the columns are padded: nothing is read at or beyond n.

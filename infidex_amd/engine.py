@@ -196,6 +196,33 @@ class GroupListing:        # SearchEngine.list_groups: one per request
 
 
 @dataclass
+class GroupMembersRequest:  # SearchEngine.list_group_members: one page of one collapsed listing, with the first members of every group
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    group_by: Optional[str] = None      # field whose values form the groups: any column, any number of distinct values (required)
+    order_by: Optional[str] = None      # field whose values order the groups' heads AND the members of every group; None: index order
+    ascending: bool = True              # False: largest value first — documents of equal value still by ascending index
+    per_group: int = 3                  # members listed per group, 1 .. 16; limit * per_group <= 4096
+    offset: int = 0                     # position of the page's first group among the groups' heads, 0 <= offset < 2**31
+    limit: int = 20                     # groups of the page, 1 .. 1024
+
+
+@dataclass
+class GroupMembers:        # SearchEngine.list_group_members: one group of one page
+    group_value: str = ""                                     # the group's value of the group_by field as text (GroupListing.group_values)
+    size: int = 0                                             # members of the group among the documents the filter accepts (GroupListing.group_sizes)
+    document_ids: list = _dc_field(default_factory=list)      # DocumentKeys of its first min(per_group, size) members in the listing's order, the head first
+    values: list = _dc_field(default_factory=list)            # the members' order_by values as text (ToString()); [] when order_by is None
+
+
+@dataclass
+class GroupMembersListing:  # SearchEngine.list_group_members: one per request
+    groups: list = _dc_field(default_factory=list)            # [GroupMembers] of the page: the rows of list_groups for the same request, in its order
+    total_groups: int = 0                                     # groups with a member (GroupListing.total_groups)
+    total: int = 0                                            # live documents the filter accepts (Listing.total of the same filter)
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+@dataclass
 class TopGroupsRequest:    # SearchEngine.top_groups: one page of one ranking of a field's groups
     filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
     group_by: Optional[str] = None      # field whose values form the groups: any column, any number of distinct values (required)
@@ -356,6 +383,11 @@ class _ListReq(C.Structure):
 
 class _GroupListReq(C.Structure):     # infx_group_list_request (include/infidex_engine.h)
     _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class _GroupMembersReq(C.Structure):  # infx_group_members_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("group_by", C.c_char_p), ("order_by", C.c_char_p), ("ascending", C.c_int32), ("offset", C.c_uint32), ("limit", C.c_uint32),
+                ("per_group", C.c_uint32)]
 
 
 class _TopReq(C.Structure):           # infx_top_request (include/infidex_engine.h)
@@ -657,6 +689,22 @@ class SearchEngine:
     def last_group_list_stats(self, session=None):
         """(masks built, masks reused, head passes, histogram passes, kernel launches) of the session's last list_groups device call."""
         return _u32_stats(self, "infx_engine_last_group_list_stats", session.h if session is not None else self._default_session(), 5)
+
+    def list_group_members(self, filter=None, group_by=None, order_by=None, ascending=True, per_group=3, offset=0, limit=20, session=None):
+        """The first members of every group, by page (not in the reference): the groups are exactly the rows of list_groups(filter, group_by, order_by,
+        ascending, offset, limit), in its order — by each group's head — and every group carries its first min(per_group, size) members in
+        list_documents(filter, order_by, ascending)'s order (ties by ascending internal index in both directions; duplicate DocumentKeys are members of their
+        own): "the three cheapest offers of every product family, page 7".  Returns GroupMembersListing(groups, total_groups, total, error), groups the
+        GroupMembers(group_value, size, document_ids, values) of the page: document_ids[0] is list_groups' head, size, total_groups and total are
+        list_groups'; values is [] without order_by.  1 <= per_group <= 16, 1 <= limit <= 1024, limit * per_group <= 4096; offset >= total_groups is an
+        empty page.  A sequence of GroupMembersRequest as first argument -> a list of GroupMembersListing, sixteen requests per device call.  One call
+        in place of one list_documents per row: the members are kept in the walk that counts the sizes (profiles/group_members.md).  Exact and deterministic; nothing is cached but the session's
+        pre-filter masks.  Needs a GPU."""
+        return _list_group_members(self, session.h if session is not None else self._default_session(), filter, group_by, order_by, ascending, per_group, offset, limit)
+
+    def last_group_members_stats(self, session=None):
+        """(masks built, masks reused, head passes, histogram passes, member walks, kernel launches) of the session's last list_group_members device call."""
+        return _u32_stats(self, "infx_engine_last_group_members_stats", session.h if session is not None else self._default_session(), 6)
 
     def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20, session=None):
         """A field's groups ranked by a figure and cut to a page (not in the reference): over the documents list_documents(filter) lists, one row per value
@@ -1072,6 +1120,14 @@ class Session:
         """SearchEngine.last_group_list_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_group_list_stats", self.h, 5)
 
+    def list_group_members(self, filter=None, group_by=None, order_by=None, ascending=True, per_group=3, offset=0, limit=20):
+        """SearchEngine.list_group_members on this session (its mask cache holds the filters' masks)."""
+        return _list_group_members(self.engine, self.h, filter, group_by, order_by, ascending, per_group, offset, limit)
+
+    def last_group_members_stats(self):
+        """SearchEngine.last_group_members_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_group_members_stats", self.h, 6)
+
     def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20):
         """SearchEngine.top_groups on this session (its mask cache holds the filters' masks)."""
         return _top_groups(self.engine, self.h, filter, group_by, by, field, ascending, offset, limit)
@@ -1418,18 +1474,11 @@ def _list_documents(engine, sh, filter, order_by, ascending, offset, limit):
                         lambda _, msg: Listing([], [], 0, msg))
 
 
-def _list_groups(engine, sh, filter, group_by, order_by, ascending, offset, limit):
-    """infx_engine_list_groups on session handle sh: a GroupListing for one request (given by its parts), a list of them for a sequence of GroupListRequest."""
-    def pack(r):
-        off, lim = int(r.offset), int(r.limit)
-        # out of the C fields' range: passed as values the engine refuses for this request alone
-        return _GroupListReq(None if r.filter is None else r.filter.encode(), None if r.group_by is None else str(r.group_by).encode(),
-                             None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
-                             off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+def _value_texts(engine):
+    """texts(name, codes): the values of column `name` at codes, as list_documents fetches them; every (column, code) is fetched once per call of this."""
     cols = {}
 
     def texts(name, codes):
-        """the values of column `name` at codes, as list_documents fetches them"""
         if name not in cols:
             cols[name] = (_column_index(engine, name), {})
         col, text = cols[name]
@@ -1441,6 +1490,18 @@ def _list_groups(engine, sh, filter, group_by, order_by, ascending, offset, limi
                 text[c] = vb.value.decode()
             out.append(text[c])
         return out
+    return texts
+
+
+def _list_groups(engine, sh, filter, group_by, order_by, ascending, offset, limit):
+    """infx_engine_list_groups on session handle sh: a GroupListing for one request (given by its parts), a list of them for a sequence of GroupListRequest."""
+    def pack(r):
+        off, lim = int(r.offset), int(r.limit)
+        # out of the C fields' range: passed as values the engine refuses for this request alone
+        return _GroupListReq(None if r.filter is None else r.filter.encode(), None if r.group_by is None else str(r.group_by).encode(),
+                             None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
+                             off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0)
+    texts = _value_texts(engine)
 
     def read(i, r):
         groups = C.c_uint32(0); tot = C.c_uint32(0)
@@ -1456,6 +1517,41 @@ def _list_groups(engine, sh, filter, group_by, order_by, ascending, offset, limi
     return _per_request(engine, sh, "infx_engine_list_groups", "infx_engine_group_list_error", _GroupListReq,
                         [GroupListRequest(filter, group_by, order_by, ascending, offset, limit)] if single else list(filter), single, pack, read,
                         lambda _, msg: GroupListing(error=msg))
+
+
+def _list_group_members(engine, sh, filter, group_by, order_by, ascending, per_group, offset, limit):
+    """infx_engine_list_group_members on session handle sh: a GroupMembersListing for one request (given by its parts), a list of them for a sequence of
+    GroupMembersRequest."""
+    def pack(r):
+        off, lim, per = int(r.offset), int(r.limit), int(r.per_group)
+        # out of the C fields' range: passed as values the engine refuses for this request alone
+        return _GroupMembersReq(None if r.filter is None else r.filter.encode(), None if r.group_by is None else str(r.group_by).encode(),
+                                None if r.order_by is None else r.order_by.encode(), 1 if r.ascending else 0,
+                                off if 0 <= off < 2 ** 32 else 0xFFFFFFFF, lim if 0 <= lim < 2 ** 32 else 0, per if 0 <= per < 2 ** 32 else 0)
+    texts = _value_texts(engine)
+
+    def read(i, r):
+        groups = C.c_uint32(0); tot = C.c_uint32(0)
+        engine._check(engine.L.infx_engine_group_members_totals(sh, i, C.byref(groups), C.byref(tot)))
+        gcodes = np.zeros(1024, np.uint32); sizes = np.zeros(1024, np.uint32); held = np.zeros(1024, np.uint32)
+        keys = np.zeros(4096, np.int64); docs = np.zeros(4096, np.int32); codes = np.zeros(4096, np.uint32)
+        m = engine.L.infx_engine_group_members_rows(sh, i, _p(gcodes, C.c_uint32), _p(sizes, C.c_uint32), _p(held, C.c_uint32), 1024)
+        k = engine.L.infx_engine_group_members_members(sh, i, _p(keys, C.c_int64), _p(docs, C.c_int32), _p(codes, C.c_uint32), 4096)
+        if m < 0 or k < 0 or k != int(held[:m].sum()):
+            engine._check(1)
+        names = texts(str(r.group_by), gcodes[:m])
+        vals = None if r.order_by is None else texts(r.order_by, codes[:k])
+        rows, at = [], 0
+        for j in range(m):
+            h = int(held[j])
+            rows.append(GroupMembers(names[j], int(sizes[j]), [int(x) for x in keys[at:at + h]], [] if vals is None else vals[at:at + h]))
+            at += h
+        return GroupMembersListing(rows, int(groups.value), int(tot.value), None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_list_group_members", "infx_engine_group_members_error", _GroupMembersReq,
+                        [GroupMembersRequest(filter, group_by, order_by, ascending, per_group, offset, limit)] if single else list(filter), single, pack, read,
+                        lambda _, msg: GroupMembersListing(error=msg))
 
 
 def _range_facets(engine, sh, filter, field, edges):

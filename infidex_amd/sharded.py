@@ -725,6 +725,14 @@ class ShardedSearcher:
     def last_group_list_stats(self):
         return self.sessions[0].s.last_group_list_stats()
 
+    def list_group_members(self, filter=None, group_by=None, order_by=None, ascending=True, per_group=3, offset=0, limit=20):
+        """SearchEngine.list_group_members: like list_groups, every rank walks the whole columns with the global Deleted flags on its own GPU and gets the
+        same answer — nothing is exchanged."""
+        return self.sessions[0].s.list_group_members(filter, group_by, order_by, ascending, per_group, offset, limit)
+
+    def last_group_members_stats(self):
+        return self.sessions[0].s.last_group_members_stats()
+
     def top_groups(self, filter=None, group_by=None, by="size", field=None, ascending=False, offset=0, limit=20):
         """SearchEngine.top_groups: like list_groups, every rank accumulates, ranks and selects the page over the whole columns with the global Deleted
         flags on its own GPU and gets the same answer — nothing is exchanged."""
