@@ -426,7 +426,7 @@ int32_t infx_engine_set_list_digit_bits(infx_session* s, int32_t bits);
  * Values compare as Query.SortBy compares them (long numerically; double numerically with -0 == +0).  A NaN value is in no bucket and not in min / max.
  * EDGES: nedges = 2 .. 257 (1 .. 256 buckets), strictly increasing under that comparison (so -0.0, 0.0 is not), no NaN, +-inf allowed on a double column.
  * An int64 column reads edges_i (NULL: INFX_EINVAL, "integer column needs integer edges"), a double column reads edges_d.
- * No sums, means or percentiles (a percentile is infx_engine_list_documents at offset p * total, limit 1); nothing is cached but the masks.
+ * No sums or means (per bucket: infx_engine_bucket_stats) and no percentiles (a percentile is infx_engine_list_documents at offset p * total, limit 1); nothing is cached but the masks.
  * A request is refused ON ITS OWN (out_status[i], message from infx_engine_range_error, the others answered): a syntax error, an unknown field, a string
  * column or bad edges INFX_EINVAL, MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most INFX_MAX_PREFILTERS (16) requests
  * (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), the field and edge refusals already in out_status; a call that failed as a
@@ -479,6 +479,44 @@ int32_t infx_engine_field_stats_groups(infx_session* s, uint32_t which, int32_t*
 int32_t infx_engine_field_stats_total(infx_session* s, uint32_t which, uint32_t* total);
 int32_t infx_engine_field_stats_error(infx_session* s, uint32_t which, char* out, int32_t cap);
 int32_t infx_engine_last_field_stats_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
+/* ---- bucket_stats: the EXACT sums and means of a numeric field per range bucket of a second numeric field over a filter (not in the reference: the
+ * semantics below are this project's) ----
+ * Request i asks, over the SET of infx_engine_list_documents — every document that is not Deleted and whose OWN fields its Infiscript `filter` accepts;
+ * filter = NULL: every live document — for infx_engine_field_stats' figures of `field` over the members of every bucket of `bucket_by`:
+ *   bucket_by, edges   infx_engine_range_facets' field and edges, under the same rules: an int64 or a double column; nedges = 2 .. 257 strictly increasing edges
+ *              e_0 < .. < e_B as Query.SortBy compares values, no NaN, +-inf allowed on a double column; an int64 column reads edges_i, a double column edges_d
+ *   field      infx_engine_field_stats' field: an int64 or a double column whose finite values span at most 128 binary digits; it may be bucket_by itself
+ *   rows       B + 3 of them, in the order [below | B buckets | above | nan]: the members whose bucket_by value is below e_0, in [e_j, e_(j+1)), at or above
+ *              e_B, or a NaN.  Per row its size (its members) and the six figures of `field` over them — count, nan, min, max, sum, mean exactly as
+ *              infx_engine_field_stats defines and computes them (the same functions); size == count + nan; an empty row reads as infx_engine_field_stats
+ *              on an empty set
+ *   whole      the figures of `field` over the whole set, equal figure for figure to infx_engine_field_stats(filter, field): the host adds the rows' slots
+ *              as integers, as a grouped infx_engine_field_stats does;  total  the size of the set
+ * The rows' sizes are infx_engine_range_facets' counts, below, above and nan for the same filter, field = bucket_by and edges; nan.size + below.size + the
+ * buckets' sizes + above.size == total == whole.count + whole.nan; the rows' count and nan add up to the whole's, and on an int64 `field` so do the sums.
+ * The device adds integers only (DESIGN.md "bucket_stats"), so every run, session, stream, placement and rank returns the same bytes.  Left out on purpose:
+ * a group_by beside the buckets, quantiles per bucket, automatic edges, a Query option; nothing is cached but the masks.
+ * A request is refused ON ITS OWN (out_status[i], message from infx_engine_bucket_stats_error, the others answered): a syntax error, a missing, unknown or
+ * string field, a field that cannot be summed exactly, a missing, unknown or string bucket_by or bad edges INFX_EINVAL (the messages of
+ * infx_engine_field_stats and infx_engine_range_facets, naming bucket_stats), MATCHES INFX_EUNSUPPORTED; the call itself then returns INFX_OK.  At most
+ * INFX_MAX_PREFILTERS (16) requests (INFX_ECAPACITY).  INFX_EHIP on an engine without a GPU (no CPU fallback), every refusal but the filter's already in
+ * out_status; a call that failed as a whole leaves nothing for the readers.  The masks are the session's pre-filter masks; both columns' sort ranks and the
+ * field's value table are built on first use and dropped when infx_engine_add_column replaces the column; ONE k_bucket_stats launch answers all requests of
+ * the call.  Works on a sharded engine without a collective.
+ * Readers, for request `which` of the session's last call: infx_engine_bucket_stats_rows copies up to cap rows in the order above — sizes[k] and figures[k]
+ * of row k — and returns the number of rows, B + 3 (-1 for a refused request or bad arguments); infx_engine_bucket_stats_whole the whole's figures and
+ * infx_engine_bucket_stats_total the size of the set (both returning the request's status); infx_engine_bucket_stats_error the refusal's message (its
+ * length; -1 out of range).  infx_engine_last_bucket_stats_stats: masks built and reused and k_bucket_stats launches of the last call;
+ * infx_engine_last_bucket_stats_placement: its requests whose slots lay in a workgroup's LDS, in a CU's whole LDS and in global memory
+ * (infx_last_bucket_stats_info). */
+typedef struct infx_bucket_stats_request { const char* filter; const char* field; const char* bucket_by; uint32_t nedges; const int64_t* edges_i; const double* edges_d; } infx_bucket_stats_request;
+int32_t infx_engine_bucket_stats(infx_session* s, uint32_t nreq, const infx_bucket_stats_request* reqs, int32_t* out_status /* nreq, may be NULL */);
+int32_t infx_engine_bucket_stats_rows(infx_session* s, uint32_t which, uint32_t* sizes, infx_stats_figures* figures, int32_t cap);
+int32_t infx_engine_bucket_stats_whole(infx_session* s, uint32_t which, infx_stats_figures* out);
+int32_t infx_engine_bucket_stats_total(infx_session* s, uint32_t which, uint32_t* total);
+int32_t infx_engine_bucket_stats_error(infx_session* s, uint32_t which, char* out, int32_t cap);
+int32_t infx_engine_last_bucket_stats_stats(infx_session* s, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches);
+int32_t infx_engine_last_bucket_stats_placement(infx_session* s, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
 /* ---- field_quantiles: exact medians and percentiles of a numeric field over a filter, whole and per group (not in the reference: the semantics below are
  * this project's) ----
  * Request i asks, over the SET of infx_engine_field_stats (what infx_engine_list_total and infx_engine_field_stats_total count), for nq quantiles q[0 .. nq)

@@ -485,6 +485,28 @@ typedef struct infx_stats_slot { uint32_t finite; uint32_t nan; uint32_t pinf; u
 int32_t infx_upload_column_values(infx_index* idx, uint32_t col, uint32_t num_values, const uint64_t* bits, int32_t kind, int32_t scale_exp, uint32_t nlimbs);
 int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* reqs, infx_stats_slot* slots_out /* sum of the requests' slots */);
 int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches);
+/* Field statistics of a document set per RANGE BUCKET of a second numeric column (not in the reference: the aggregate is this project's; DESIGN.md
+ * "bucket_stats").
+ * Request i: the SET is infx_field_stats' — the documents whose byte in `mask` is 0 (a mask slot of this stream), or, mask = NULL, every document that is not
+ * Deleted.  `col` is the summed column, with its sort rank and its value table uploaded as for infx_field_stats; `bucket_col` is the column the buckets cut,
+ * with its sort rank uploaded; nedges, thr and nan_ranks are infx_range_counts' over bucket_col (2 .. INFX_RANGE_MAX_EDGES thresholds, non-decreasing,
+ * nan_ranks <= thr[j] <= bucket_col's num_values; nan_ranks 0 or 1); reserved is 0.  col == bucket_col is allowed.  The request has B + 3 = nedges + 2 SLOTS
+ * in infx_range_counts' order of counters — slot 0 below e_0, 1 .. B the half-open buckets, B + 1 at or above e_B, B + 2 the members whose bucket_col value is
+ * a NaN — and the slots of request i follow those of request i - 1 in slots_out.  A member document of bucket rank r adds to slot k (k = B + 2 when
+ * r < nan_ranks, else k = #{j : thr[j] <= r}) exactly what infx_field_stats adds to the slot of a group code: one of four counters by the class of its
+ * VALUE, the value's sort rank to min_rank / max_rank unless it is a NaN, its limbs to the signed sums.  finite + nan + pinf + ninf of slot k is what
+ * infx_range_counts counts in counter k.  Every accumulation is an integer atomic — no floating-point add, no order: the same bytes from any stream, grid
+ * and placement.
+ * At most 16 requests (INFX_ECAPACITY), all answered by ONE k_bucket_stats launch that walks the corpus once: the requests are taken in the order
+ * (mask, col, bucket_col), so the ones that share a mask read its bytes once and the ones that share a value column too read its codes, values and ranks
+ * once.  Every request's thresholds lie in LDS; its slots lie there too while they fit (infx_field_stats' rule and its two launch shapes, each budget less
+ * the thresholds), else in global memory.  A mask build staged with infx_filter_masks is enqueued first, as ONE launch.  Works on a sharded index.
+ * Synchronous.
+ * infx_last_bucket_stats_info: requests and k_bucket_stats launches (0 or 1) of the stream's last call, and its requests whose slots lay in a workgroup's
+ * LDS (256 threads), in a CU's whole LDS (1024 threads) and in global memory. */
+typedef struct infx_bucket_stats_req { const uint8_t* mask; int32_t col; int32_t bucket_col; uint32_t nedges; uint32_t nan_ranks; uint32_t reserved; const uint32_t* thr; } infx_bucket_stats_req;
+int32_t infx_bucket_stats(infx_stream* s, uint32_t nreq, const infx_bucket_stats_req* reqs, infx_stats_slot* slots_out /* sum of the requests' nedges + 2 */);
+int32_t infx_last_bucket_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global);
 /* Quantiles of a document set over a numeric column, whole and per value of a second column (not in the reference: the aggregate is this project's;
  * DESIGN.md "field_quantiles").
  * Request i: the SET is infx_field_stats': the documents whose byte in `mask` is 0 — a mask slot of this stream — or, mask = NULL, every document that is

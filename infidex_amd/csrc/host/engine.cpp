@@ -117,6 +117,9 @@ struct GroupMembersAnswer : ListAnswer { uint32_t totalGroups = 0; std::vector<u
 // One request of the session's last infx_engine_top_groups: its status and message, the size of its set (total), the groups with a member, the group column,
 // whether it had a field, its page: per row the group's code, its members and — with a field — its figures
 struct TopAnswer : Answer { uint32_t totalGroups = 0; int32_t groupCol = -1; bool hasField = false; std::vector<uint32_t> codes, sizes; std::vector<infx_stats_figures> figures; };
+// One request of the session's last infx_engine_bucket_stats: its status and message, the size of its set, per slot [below | B buckets | above | nan] the
+// members and the figures of the field over them, the figures over the whole set
+struct BucketAnswer : Answer { std::vector<uint32_t> sizes; std::vector<infx_stats_figures> rows; infx_stats_figures whole = {}; };
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskUse masks; };
 struct infx_session {
@@ -149,6 +152,8 @@ struct infx_session {
     struct Top : LastCall<TopAnswer> { uint32_t accumulates = 0, passes = 0, launches = 0, place[3] = {0, 0, 0}; } top;
     // infx_engine_field_distinct: kernel launches, passes that marked in LDS / in a global bitmap / in a hash set; dstPlacement: the placement asked of the device
     struct Dst : LastCall<DistinctAnswer> { uint32_t launches = 0, place[3] = {0, 0, 0}; } dst; int32_t dstPlacement = 0;
+    // infx_engine_bucket_stats: k_bucket_stats launches, requests whose slots lay in a workgroup's LDS / a CU's whole LDS / global memory
+    struct Bks : LastCall<BucketAnswer> { uint32_t launches = 0, place[3] = {0, 0, 0}; } bks;
     std::vector<uint32_t> lastInFilter; std::vector<std::string> lastErr; uint32_t lastCounted = 0, lastCountLaunches = 0;     // of the last per-query batch
     infx_engine* e = nullptr;
     Batch* batch = nullptr;
@@ -3401,24 +3406,26 @@ static const filt::Boxed* value_of_rank(const filt::Column& C, const infx_engine
 }
 static int column_kind(const filt::Column& c) { return c.dict.empty() ? 0 : c.dict[0].kind; }
 // What is wrong with request Q before anything of it is looked at on the device — the field, its kind, the edges, in this order — as the request's status, the
-// text in *why; INFX_OK with the field's column and the kind of the edges (1 int64, 2 double).  Caller holds e->filterMu.
-static int32_t range_request_check(const infx_engine* e, const infx_range_request& Q, int32_t* col, int* kind, std::string* why) {
+// text in *why; INFX_OK with the field's column and the kind of the edges (1 int64, 2 double).  `what` names the call and `role` the field in the messages
+// (infx_engine_bucket_stats: its bucket_by).  Caller holds e->filterMu.
+static int32_t range_request_check(const infx_engine* e, const infx_range_request& Q, int32_t* col, int* kind, std::string* why, const std::string& what = "range_facets",
+                                   const std::string& role = "field") {
     auto bad = [&](const std::string& msg) { *why = msg; return (int32_t)INFX_EINVAL; };
-    if (!Q.field) return bad("range_facets needs a field");
-    if ((*col = column_named(e, Q.field)) < 0) return bad(std::string("range_facets: no field named '") + Q.field + "'");
+    if (!Q.field) return bad(what + " needs a " + role);
+    if ((*col = column_named(e, Q.field)) < 0) return bad(what + ": no " + role + " named '" + Q.field + "'");
     int k = column_kind(e->columns[*col]);
-    if (k == 3) return bad(std::string("range_facets: field '") + Q.field + "' is a string column; ranges need an int64 or a double column");
+    if (k == 3) return bad(what + ": " + role + " '" + Q.field + "' is a string column; ranges need an int64 or a double column");
     if (k == 0) k = Q.edges_i ? 1 : 2;                              // (a column without a value)
     *kind = k;
-    if (Q.nedges < 2 || Q.nedges > INFX_RANGE_MAX_EDGES) return bad("range_facets takes 2 to 257 edges (1 to 256 buckets)");
+    if (Q.nedges < 2 || Q.nedges > INFX_RANGE_MAX_EDGES) return bad(what + " takes 2 to 257 edges (1 to 256 buckets)");
     if (k == 1) {
         if (!Q.edges_i) return bad("integer column needs integer edges");
-        for (uint32_t j = 1; j < Q.nedges; j++) if (!(Q.edges_i[j - 1] < Q.edges_i[j])) return bad("the edges of range_facets are strictly increasing");
+        for (uint32_t j = 1; j < Q.nedges; j++) if (!(Q.edges_i[j - 1] < Q.edges_i[j])) return bad("the edges of " + what + " are strictly increasing");
     } else {
         if (!Q.edges_d) return bad("double column needs double edges");
         for (uint32_t j = 0; j < Q.nedges; j++) {
-            if (std::isnan(Q.edges_d[j])) return bad("an edge of range_facets is not a NaN");
-            if (j && !(Q.edges_d[j - 1] < Q.edges_d[j])) return bad("the edges of range_facets are strictly increasing (-0.0 and 0.0 compare equal)");
+            if (std::isnan(Q.edges_d[j])) return bad("an edge of " + what + " is not a NaN");
+            if (j && !(Q.edges_d[j - 1] < Q.edges_d[j])) return bad("the edges of " + what + " are strictly increasing (-0.0 and 0.0 compare equal)");
         }
     }
     return INFX_OK;
@@ -3636,6 +3643,107 @@ int32_t infx_engine_field_stats_error(infx_session* S, uint32_t which, char* out
 int32_t infx_engine_last_field_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
     if (!S) return efail(INFX_EINVAL, "null session");
     return put_stats({{masks_built, S->sts.masks.built}, {masks_reused, S->sts.masks.reused}, {launches, S->sts.launches}});
+}
+
+// ---- bucket_stats: field_stats' figures of a numeric field per range bucket of a second numeric field over the documents a filter accepts (not in the reference) ----
+// Per request: `field` as infx_engine_field_stats resolves it (numeric_field_check, the value table, summable or refused), `bucket_by` and the edges as
+// infx_engine_range_facets resolves its field and edges (range_request_check, range_thresholds over the column's dense sort rank), the filter through the
+// filter cache and its mask through the session's mask cache.  infx_bucket_stats then adds integers only, one slot per bucket; the engine turns every slot
+// into figures with stats_figures and adds the slots as integers for the whole, as a grouped field_stats does.
+int32_t infx_engine_bucket_stats(infx_session* S, uint32_t nreq, const infx_bucket_stats_request* reqs, int32_t* out_status) {
+    struct Req { int32_t col = -1, bcol = -1; int kind = 0; uint32_t nanRanks = 0; std::vector<uint32_t> thr; } rq[INFX_MAX_PREFILTERS];
+    std::vector<infx_bucket_stats_req> dr; std::vector<size_t> at; std::vector<infx_stats_slot> slots;
+    auto as_range = [&](uint32_t i) { return infx_range_request{reqs[i].filter, reqs[i].bucket_by, reqs[i].nedges, reqs[i].edges_i, reqs[i].edges_d}; };
+    return set_call(S, &infx_session::bks, "bucket_stats", "bucket_stats requests", true, nreq, reqs, out_status,
+        [&](auto& F, uint32_t i) {
+            std::string why; int32_t g = -1;
+            int32_t rc = numeric_field_check(S->e, "bucket_stats", "sums", reqs[i].field, nullptr, &rq[i].col, &g, &why);
+            if (!rc && !stats_index(S->e, (uint32_t)rq[i].col).summable) {
+                rc = INFX_EINVAL;
+                why = std::string("bucket_stats: the finite values of field '") + reqs[i].field + "' span more than 128 binary digits; they cannot be summed exactly";
+            }
+            if (!rc) {
+                rc = range_request_check(S->e, as_range(i), &rq[i].bcol, &rq[i].kind, &why, "bucket_stats", "bucket_by field");
+                if (rc && why.compare(0, 12, "bucket_stats")) why = "bucket_stats: " + why;
+            }
+            if (rc) F.refuse(i, rc, why);
+        },
+        [&](auto& F, uint32_t i) {
+            infx_engine* e = S->e;
+            const infx_engine::RangeIndex *X = nullptr, *B = nullptr;
+            { const int32_t rc = range_index(e, (uint32_t)rq[i].col, &X); if (rc) return F.refuse(i, rc, g_eerr); }      // (the sort rank, for min / max)
+            { const int32_t rc = range_index(e, (uint32_t)rq[i].bcol, &B); if (rc) return F.refuse(i, rc, g_eerr); }
+            infx_engine::StatsIndex& V = stats_index(e, (uint32_t)rq[i].col);
+            if (!V.uploaded) {
+                const int32_t rc = infx_upload_column_values(e->dev, (uint32_t)rq[i].col, (uint32_t)V.bits.size(), V.bits.data(), V.kind, V.sc.scale, V.sc.nlimbs);
+                if (rc) return F.refuse(i, rc, infx_last_error());
+                V.uploaded = true;
+            }
+            if (!F.filter(i, reqs[i].filter)) return;
+            rq[i].nanRanks = B->nanRanks;
+            rq[i].thr = range_thresholds(e->columns[rq[i].bcol], *B, as_range(i), rq[i].kind);
+        },
+        [&](auto& F) {
+            size_t nslots = 0;
+            for (uint32_t i : F.who) {
+                infx_bucket_stats_req R{};
+                R.mask = F.mc.mask(i); R.col = rq[i].col; R.bucket_col = rq[i].bcol; R.nedges = reqs[i].nedges; R.nan_ranks = rq[i].nanRanks; R.thr = rq[i].thr.data();
+                dr.push_back(R); at.push_back(nslots);
+                nslots += (size_t)reqs[i].nedges + 2;
+            }
+            slots.resize(std::max<size_t>(nslots, 1));
+            return infx_bucket_stats(S->stream, (uint32_t)dr.size(), dr.data(), slots.data());
+        },
+        [&](auto& F) {
+            infx_engine* e = S->e;
+            infx_last_bucket_stats_info(S->stream, nullptr, &S->bks.launches, &S->bks.place[0], &S->bks.place[1], &S->bks.place[2]);
+            std::lock_guard<std::mutex> lk(e->filterMu);
+            for (size_t j = 0; j < dr.size(); j++) {
+                BucketAnswer& A = S->bks.ans[F.who[j]];
+                const filt::Column& C = e->columns[dr[j].col]; const infx_engine::RangeIndex& X = e->rangeIndex[dr[j].col]; const infx_engine::StatsIndex& V = e->statsIndex[dr[j].col];
+                const infx_stats_slot* sl = slots.data() + at[j];
+                infx_stats_slot all = {}; all.min_rank = 0xFFFFFFFFu;
+                for (uint32_t g = 0; g < dr[j].nedges + 2; g++) {
+                    const infx_stats_slot& s1 = sl[g];
+                    all.finite += s1.finite; all.nan += s1.nan; all.pinf += s1.pinf; all.ninf += s1.ninf;
+                    if (s1.min_rank != 0xFFFFFFFFu) { all.min_rank = std::min(all.min_rank, s1.min_rank); all.max_rank = std::max(all.max_rank, s1.max_rank); }
+                    for (int k = 0; k < INFX_STATS_MAX_LIMBS; k++) all.sum[k] += s1.sum[k];      // (fewer than 2^31 members in all: no limb sum overflows)
+                    A.sizes.push_back(s1.finite + s1.nan + s1.pinf + s1.ninf);
+                    A.rows.push_back(stats_figures(s1, V, C, X));
+                }
+                A.whole = stats_figures(all, V, C, X);
+                A.total = A.whole.count + A.whole.nan;
+            }
+        });
+}
+// request `which` of the session's last infx_engine_bucket_stats: up to cap rows in slot order [below | B buckets | above | nan] — sizes[k] the members of row k,
+// figures[k] the field's figures over them; returns the number of rows (B + 3), -1 on error (also for a refused request)
+int32_t infx_engine_bucket_stats_rows(infx_session* S, uint32_t which, uint32_t* sizes, infx_stats_figures* figures, int32_t cap) {
+    const BucketAnswer* A = answer_at(S ? &S->bks.ans : nullptr, which);
+    if (!A || A->status || (cap > 0 && (!sizes || !figures))) return -1;
+    const size_t c = std::min<size_t>(A->rows.size(), (size_t)std::max(cap, 0));
+    if (c) { std::memcpy(sizes, A->sizes.data(), c * 4); std::memcpy(figures, A->rows.data(), c * sizeof(infx_stats_figures)); }
+    return (int32_t)A->rows.size();
+}
+// the figures over the whole set (returning the request's status)
+int32_t infx_engine_bucket_stats_whole(infx_session* S, uint32_t which, infx_stats_figures* out) {
+    const BucketAnswer* A = answer_at(S ? &S->bks.ans : nullptr, which);
+    if (!A || !out) return efail(INFX_EINVAL, "no such request in the session's last bucket_stats call");
+    *out = A->whole;
+    return A->status;
+}
+// the size of request `which`'s set (0 for a refused one, whose status is returned)
+int32_t infx_engine_bucket_stats_total(infx_session* S, uint32_t which, uint32_t* total) {
+    return answer_total(answer_at(S ? &S->bks.ans : nullptr, which), total, "no such request in the session's last bucket_stats call");
+}
+int32_t infx_engine_bucket_stats_error(infx_session* S, uint32_t which, char* out, int32_t cap) { return answer_error(answer_at(S ? &S->bks.ans : nullptr, which), out, cap); }
+int32_t infx_engine_last_bucket_stats_stats(infx_session* S, uint32_t* masks_built, uint32_t* masks_reused, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{masks_built, S->bks.masks.built}, {masks_reused, S->bks.masks.reused}, {launches, S->bks.launches}});
+}
+int32_t infx_engine_last_bucket_stats_placement(infx_session* S, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    return put_stats({{small_lds, S->bks.place[0]}, {big_lds, S->bks.place[1]}, {in_global, S->bks.place[2]}});
 }
 
 // ---- field_quantiles: the values at the quantiles' positions of a numeric field over the documents a filter accepts, whole and per group (not in the reference) ----

@@ -266,6 +266,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "listing.hip.inc"
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
+#include "bucket_stats.hip.inc"
 #include "groups.hip.inc"
 #include "group_members.hip.inc"
 #include "top_groups.hip.inc"
@@ -351,6 +352,8 @@ enum SetKind {
                       // their host copy.  Requests, kernel launches, specs marked in LDS / in a global bitmap / in a hash set
     SK_MEMBERS,       // infx_list_group_members (its pages in SK_LIST's buffers): SK_GROUPED's workspace | per request its slots, limit and per_group, the members'
                       // keys, documents and codes, the rows' member counts.  Head passes, histogram passes, member walks, kernel launches
+    SK_BUCKETS,       // infx_bucket_stats: the requests' thresholds | the requests' slots and smallest ranks | their host copy.  Requests, k_bucket_stats launches, requests
+                      // with slots in a workgroup's LDS / a CU's whole LDS / global memory
     SK_KINDS
 };
 struct SetKindState {
@@ -3108,7 +3111,7 @@ static void set_order(uint32_t nreq, const SetKey* key, uint32_t* order) {
 }
 // what request Q keeps of B, the one before it in that order: 1 the mask's flags, 3 the value column's ranks as well
 static uint32_t set_reuse(const SetKey& B, const SetKey& Q) { return B.mask == Q.mask ? (B.col == Q.col ? 3u : 1u) : 0u; }
-// The frame of a set call.  What the eight kinds' starts differ in: the two refusals' words; whether the rows need the documents' keys (the listings); where
+// The frame of a set call.  What the nine kinds' starts differ in: the two refusals' words; whether the rows need the documents' keys (the listings); where
 // info[] counts requests and launches (-1: not at all; the mask build is the first launch of a kind that counts them); whether the device takes the requests
 // in set_order's order (infx_list_grouped and infx_list_group_members keep one of their own, infx_list_ordered the caller's).
 struct SetKindSpec { const char *badArgs, *tooMany; bool needKeys; int requestsAt, launchesAt; bool ordered; };
@@ -3121,9 +3124,10 @@ static const SetKindSpec SET_KINDS[SK_KINDS] = {
     {"bad top-groups arguments%s", "more than 16 top-groups requests in one call%s", false, 0, 3, true},
     {"bad field-distinct arguments%s", "more than 16 field-distinct requests in one call%s", false, 0, 1, true},
     {"bad group-members arguments%s", "more than INFX_MAX_PREFILTERS (16) group-members requests in one call%s", true, -1, 3, false},
+    {"bad bucket-stats arguments%s", "more than 16 bucket-stats requests in one call%s", false, 0, -1, true},
 };
 static_assert(RB_MAX_REQS == INFX_MAX_PREFILTERS && STS_MAX_REQS == INFX_MAX_PREFILTERS && QNT_MAX_REQS == INFX_MAX_PREFILTERS && TOP_MAX_REQS == INFX_MAX_PREFILTERS &&
-              DST_MAX_REQS == INFX_MAX_PREFILTERS, "every set call takes as many requests as a mask build takes filters");
+              DST_MAX_REQS == INFX_MAX_PREFILTERS && BKS_MAX_REQS == INFX_MAX_PREFILTERS, "every set call takes as many requests as a mask build takes filters");
 struct SetCall {
     infx_stream* s; infx_index* ix; SetKindState* K; const SetKindSpec* spec;
     int32_t n; uint32_t nreq;                                            // the corpus (never negative), the call's requests
@@ -3193,7 +3197,7 @@ static int32_t set_fetch_raw(const SetCall& c, size_t words) {
     SYNC();
     return INFX_OK;
 }
-// one reader behind the eight infx_last_*: out[i] (where not null) takes counter i of the kind's last call
+// one reader behind the nine infx_last_*: out[i] (where not null) takes counter i of the kind's last call
 static int32_t put_info(const infx_stream* s, SetKind kind, std::initializer_list<uint32_t*> out) {
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     const uint32_t* v = s->kind[kind].info;
@@ -3386,10 +3390,11 @@ static uint32_t sts_place(uint32_t nreq, const uint32_t* words, uint32_t budget,
 }
 // sts_place under the two budgets: k_facets_all's (STS_LDS_WORDS, 256 threads); where that leaves requests in global memory and the whole LDS of a CU would
 // hold more of them, that (STS_BIG_LDS_WORDS, if `big` allows it): merge_once_shape then takes one workgroup of 1024 threads per CU, LDS atomics for global ones
-static uint32_t sts_place_best(uint32_t nreq, const uint32_t* words, bool big, uint32_t* ldsOff) {
-    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS, ldsOff, &inGlobal);
+// `reserve`: words of both budgets the caller keeps for itself (infx_bucket_stats: the thresholds), at most STS_LDS_WORDS
+static uint32_t sts_place_best(uint32_t nreq, const uint32_t* words, bool big, uint32_t* ldsOff, uint32_t reserve = 0) {
+    uint32_t inGlobal = 0, ldsWords = sts_place(nreq, words, STS_LDS_WORDS - reserve, ldsOff, &inGlobal);
     if (inGlobal && big) {
-        uint32_t bigOff[2 * STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS, bigOff, &bigGlobal);
+        uint32_t bigOff[2 * STS_MAX_REQS], bigGlobal = 0; const uint32_t bigWords = sts_place(nreq, words, STS_BIG_LDS_WORDS - reserve, bigOff, &bigGlobal);
         if (bigGlobal < inGlobal) { std::copy(bigOff, bigOff + nreq, ldsOff); ldsWords = bigWords; }
     }
     return ldsWords;
@@ -3446,6 +3451,79 @@ int32_t infx_field_stats(infx_stream* s, uint32_t nreq, const infx_stats_req* re
 }
 int32_t infx_last_field_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches) {
     return put_info(s, SK_STATS, {requests, launches});
+}
+// ---- bucket_stats: field_stats' slots per range bucket of a second numeric column over a document set (bucket_stats.hip.inc) ----
+static_assert(BKS_MAX_THR_WORDS <= STS_LDS_WORDS && INFX_RANGE_MAX_EDGES == RB_MAX_EDGES, "a call's thresholds fit the small budget");
+int32_t infx_bucket_stats(infx_stream* s, uint32_t nreq, const infx_bucket_stats_req* reqs, infx_stats_slot* slots_out) {
+    SetCall c;
+    { int32_t rc_ = set_call_open(&c, s, SK_BUCKETS, nreq && (!reqs || !slots_out), nreq); if (rc_) return rc_; }
+    infx_index* ix = c.ix; SetKindState& K = *c.K; const int32_t n = c.n; const SetKey* key = c.key; const uint32_t* order = c.order;
+    for (uint32_t i = 0; i < nreq; i++) {
+        const infx_bucket_stats_req& Q = reqs[i];
+        if (Q.nedges < RB_MIN_EDGES || Q.nedges > RB_MAX_EDGES || !Q.thr) return fail(INFX_EINVAL, "a bucket-stats request has 2 .. INFX_RANGE_MAX_EDGES (257) thresholds%s");
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.col, true, "bucket-stats request"); if (rc_) return rc_; }
+        if (!ix->colBitsOk[Q.col]) return fail(INFX_EINVAL, "the bucket-stats request's value table was not uploaded%s");
+        { int32_t rc_ = check_set_request(s, Q.mask, Q.bucket_col, true, "bucket-stats request"); if (rc_) return rc_; }
+        if (Q.nan_ranks > 1u) return fail(INFX_EINVAL, "nan_ranks is 0 or 1%s");
+        for (uint32_t j = 0; j < Q.nedges; j++)
+            if (Q.thr[j] < Q.nan_ranks || Q.thr[j] > ix->colValues[Q.bucket_col] || (j && Q.thr[j] < Q.thr[j - 1]))
+                return fail(INFX_EINVAL, "a bucket-stats request's thresholds are non-decreasing, from nan_ranks to the bucket column's number of values%s");
+        c.key[i] = SetKey{Q.mask, Q.col, Q.bucket_col};
+    }
+    { int32_t rc_ = set_call_begin(&c); if (rc_) return rc_; }
+    if (!nreq) return INFX_OK;
+    // a request's slots: B + 3, in rb_slot's order; in the caller's order request i's follow request i - 1's, at at[i]
+    size_t at[BKS_MAX_REQS], totalSlots = 0;
+    for (uint32_t i = 0; i < nreq; i++) { at[i] = totalSlots; totalSlots += bks_slots(reqs[i].nedges); }
+    // the output: per request (in device order) its slots, then every request's smallest ranks; LDS: every request's thresholds, then the slots placed there
+    uint32_t words[BKS_MAX_REQS], ldsOff[BKS_MAX_REQS], thrOff[BKS_MAX_REQS], thrWords = 0; size_t off[BKS_MAX_REQS], loOff[BKS_MAX_REQS], outWords = 0, loSlots = 0;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_bucket_stats_req& Q = reqs[order[k]];
+        words[k] = bks_slot_words(Q.nedges, ix->colLimbs[Q.col]);
+        off[k] = outWords; outWords += words[k]; loOff[k] = loSlots; loSlots += bks_slots(Q.nedges);
+        thrOff[k] = thrWords; thrWords += bks_thr_words(Q.nedges);
+    }
+    const uint32_t slotWords = sts_place_best(nreq, words, stats_big_lds(), ldsOff, thrWords), ldsWords = thrWords + slotWords;
+    uint32_t* info = K.info;
+    for (uint32_t k = 0; k < nreq; k++) {
+        if (ldsOff[k] == STS_GLOBAL) info[4]++;
+        else { ldsOff[k] += thrWords; info[ldsWords <= STS_LDS_WORDS ? 2 : 3]++; }
+    }
+    GROW(K.ws, K.capWs, (size_t)thrWords * 4);
+    GROW(K.out, K.capOut, (outWords + totalSlots) * 4);
+    uint32_t* O = (uint32_t*)K.out;
+    std::vector<uint32_t> thr(thrWords, 0u);
+    DevBucketCall P{}; P.nreq = nreq;
+    for (uint32_t k = 0; k < nreq; k++) {
+        const infx_bucket_stats_req& Q = reqs[order[k]];
+        DevBucketReq& D = P.r[k];
+        D.s = stats_dev_req(ix, Q.mask, Q.col, Q.bucket_col, bks_slots(Q.nedges), O + off[k], O + outWords + loOff[k], ldsOff[k]);
+        if (k) D.s.reuse = set_reuse(key[order[k - 1]], key[order[k]]);
+        D.brank = ix->colRank[Q.bucket_col]; D.bvals = ix->colValues[Q.bucket_col];
+        D.thr = (const uint32_t*)K.ws + thrOff[k]; std::copy(Q.thr, Q.thr + Q.nedges, thr.begin() + thrOff[k]);
+        D.nedges = Q.nedges; D.nanRanks = Q.nan_ranks; D.thrOff = thrOff[k];
+    }
+    UP(K.ws, thr.data(), (size_t)thrWords * 4);
+    HIPCHK(hipMemsetAsync(O, 0, outWords * 4, s->st));
+    HIPCHK(hipMemsetAsync(O + outWords, 0xFF, totalSlots * 4, s->st));
+    s->unsynced = true;
+    if (n > 0) {
+        int threads, grid; { int32_t rc_ = merge_once_shape(ix, n, ldsWords, &threads, &grid); if (rc_) return rc_; }
+        HIPCHK(lds_limit((const void*)k_bucket_stats, ix->cfg.device, (size_t)ldsWords * 4));
+        k_bucket_stats<<<grid, threads, (size_t)ldsWords * 4, s->st>>>(P, n);
+        HIPCHK(hipGetLastError());
+        info[1] = 1;
+    }
+    { int32_t rc_ = set_fetch_raw(c, outWords + totalSlots); if (rc_) return rc_; }
+    for (uint32_t k = 0; k < nreq; k++) {
+        const uint32_t nl = ix->colLimbs[reqs[order[k]].col], W = sts_stride(nl);
+        for (uint32_t g = 0; g < bks_slots(reqs[order[k]].nedges); g++)
+            slots_out[at[order[k]] + g] = stats_slot(K.raw.data() + off[k] + (size_t)g * W, nl, K.raw[outWords + loOff[k] + g]);
+    }
+    return INFX_OK;
+}
+int32_t infx_last_bucket_stats_info(infx_stream* s, uint32_t* requests, uint32_t* launches, uint32_t* small_lds, uint32_t* big_lds, uint32_t* in_global) {
+    return put_info(s, SK_BUCKETS, {requests, launches, small_lds, big_lds, in_global});
 }
 // ---- field_quantiles: the sort ranks at the quantiles' positions of a numeric column over a document set, whole and per group (quantiles.hip.inc) ----
 // The digit width of request Q under the call's cap: its own digit_bits (never above the cap), else the narrowest width that takes no more passes than the cap

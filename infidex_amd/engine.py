@@ -329,6 +329,37 @@ class FieldStats:          # SearchEngine.field_stats: one per request
 
 
 @dataclass
+class BucketStatsRequest:  # SearchEngine.bucket_stats: the statistics of one numeric field per range bucket of a second one, over one filter
+    filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
+    field: Optional[str] = None         # the summed field: an int64 or a double column field_stats can sum
+    bucket_by: Optional[str] = None     # the field the buckets cut: an int64 or a double column; it may be `field`
+    edges: tuple = ()                   # 2 .. 257 strictly increasing edges e_0 < .. < e_B over bucket_by, as RangeRequest.edges
+
+
+@dataclass
+class BucketRow:           # SearchEngine.bucket_stats: one bucket (or below / above / nan, or the whole) of one request
+    size: int = 0                                             # members of the row: count + nan
+    count: int = 0                                            # members whose value of `field` is not a NaN
+    nan: int = 0                                              # members whose value of `field` is a NaN: in no other figure
+    min: Optional[object] = None                              # smallest / largest non-NaN value of `field` (int for an int column, float for a double one); None
+    max: Optional[object] = None                              # when count == 0
+    sum: object = 0                                           # int column: the exact sum, a Python int; double column: the exact real sum rounded once
+    mean: Optional[float] = None                              # the exact sum / count rounded once; None when count == 0
+
+
+@dataclass
+class BucketStats:         # SearchEngine.bucket_stats: one per request
+    edges: tuple = ()                                         # the request's edges
+    buckets: list = _dc_field(default_factory=list)           # [BucketRow]: buckets[i] the members with edges[i] <= bucket_by < edges[i + 1]
+    below: BucketRow = _dc_field(default_factory=BucketRow)   # the members with bucket_by < edges[0]
+    above: BucketRow = _dc_field(default_factory=BucketRow)   # the members with bucket_by >= edges[-1]
+    nan: BucketRow = _dc_field(default_factory=BucketRow)     # the members whose bucket_by value is a NaN (double columns): in no bucket
+    whole: BucketRow = _dc_field(default_factory=BucketRow)   # the whole set: field_stats(filter, field)'s figures
+    total: int = 0                                            # live documents the filter accepts: nan.size + below.size + the buckets' sizes + above.size
+    error: Optional[str] = None                               # why this request alone was refused; None when it was answered
+
+
+@dataclass
 class QuantileRequest:     # SearchEngine.field_quantiles: the quantiles of one numeric field over one filter, whole and per group
     filter: Optional[str] = None        # Infiscript expression over the documents' own fields; None: every live document
     field: Optional[str] = None         # an int64 or a double column
@@ -371,6 +402,11 @@ class _StatsReq(C.Structure):          # infx_stats_request (include/infidex_eng
 class _StatsFigures(C.Structure):      # infx_stats_figures (include/infidex_engine.h)
     _fields_ = [("count", C.c_uint32), ("nan", C.c_uint32), ("kind", C.c_int32), ("reserved", C.c_int32), ("min_i", C.c_int64), ("max_i", C.c_int64),
                 ("min_d", C.c_double), ("max_d", C.c_double), ("sum_d", C.c_double), ("sum_lo", C.c_uint64), ("sum_hi", C.c_int64), ("mean", C.c_double)]
+
+
+class _BucketStatsReq(C.Structure):    # infx_bucket_stats_request (include/infidex_engine.h)
+    _fields_ = [("filter", C.c_char_p), ("field", C.c_char_p), ("bucket_by", C.c_char_p), ("nedges", C.c_uint32), ("edges_i", C.POINTER(C.c_int64)),
+                ("edges_d", C.POINTER(C.c_double))]
 
 
 class _RangeReq(C.Structure):
@@ -755,10 +791,10 @@ class SearchEngine:
         buckets [edges[i], edges[i + 1]) (the last one too), with the documents below edges[0], at or above edges[-1] and, on a double column, with a NaN
         value (in no bucket), the size of the set and its smallest and largest non-NaN value.  Returns RangeFacets(edges, counts, below, above, nan, total,
         min, max, error); always nan + below + sum(counts) + above == total.  2 .. 257 edges, strictly increasing as Query.sort_by compares values (-0.0,
-        0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  Sums and means: field_stats.  A sequence of RangeRequest as first argument -> a list of
+        0.0 is not), no NaN, +-inf allowed on a double column; an int column takes Python ints.  A sequence of RangeRequest as first argument -> a list of
         RangeFacets, sixteen requests per device call, all counted in ONE pass over the corpus (requests of one filter read its mask once); a request
-        with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums or means (field_stats) and no
-        percentiles (field_quantiles)."""
+        with a syntax error, MATCHES, an unknown or string field or bad edges gets `error` set, alone.  No sums or means (per bucket: bucket_stats; of the
+        whole set: field_stats) and no percentiles (field_quantiles)."""
         return _range_facets(self, session.h if session is not None else self._default_session(), filter, field, edges)
 
     def last_range_stats(self, session=None):
@@ -780,6 +816,28 @@ class SearchEngine:
     def last_field_stats_stats(self, session=None):
         """(masks built, masks reused, k_field_stats launches) of the session's last field_stats device call."""
         return _u32_stats(self, "infx_engine_last_field_stats_stats", session.h if session is not None else self._default_session(), 3)
+
+    def bucket_stats(self, filter=None, field=None, bucket_by=None, edges=(), session=None):
+        """Field statistics per range bucket (not in the reference): over the documents list_documents(filter) lists, the members are cut by their value of
+        `bucket_by` into range_facets' half-open buckets [edges[i], edges[i + 1]), below edges[0], at or above edges[-1] and NaN — bucket_by and edges are
+        range_facets' field and edges, under its rules — and every row carries field_stats' figures of `field` over its members: BucketRow(size, count, nan,
+        min, max, sum, mean), size == count + nan, sum and mean EXACT as in field_stats (field_stats' `field`: an int64 or a double column of at most 128
+        binary digits; it may be bucket_by itself); an empty row reads as field_stats on an empty set.  Returns BucketStats(edges, buckets, below, above, nan,
+        whole, total, error): whole equals field_stats(filter, field) figure for figure, the rows' sizes are range_facets(filter, bucket_by, edges)' counts,
+        nan.size + below.size + the buckets' sizes + above.size == total == whole.size, the rows' count / nan add up to whole's and on an int column so do
+        the sums.  The device adds integers only: every run, session and rank returns the same bytes.  A sequence of BucketStatsRequest as first argument
+        -> a list of BucketStats, sixteen requests per device call, all answered in ONE pass over the corpus; a request with a syntax error, MATCHES, a
+        missing, unknown or string field, a field that cannot be summed exactly, a missing, unknown or string bucket_by or bad edges gets `error` set,
+        alone.  Left out on purpose: a group_by beside the buckets, quantiles per bucket, automatic edges, a Query option."""
+        return _bucket_stats(self, session.h if session is not None else self._default_session(), filter, field, bucket_by, edges)
+
+    def last_bucket_stats_stats(self, session=None):
+        """(masks built, masks reused, k_bucket_stats launches) of the session's last bucket_stats device call."""
+        return _u32_stats(self, "infx_engine_last_bucket_stats_stats", session.h if session is not None else self._default_session(), 3)
+
+    def last_bucket_stats_placement(self, session=None):
+        """(requests with slots in a workgroup's LDS, in a CU's whole LDS, in global memory) of the session's last bucket_stats device call."""
+        return _u32_stats(self, "infx_engine_last_bucket_stats_placement", session.h if session is not None else self._default_session(), 3)
 
     def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None, session=None):
         """Exact medians and percentiles (not in the reference): over the documents field_stats(filter) counts — not Deleted, their own fields accepted by
@@ -1168,6 +1226,18 @@ class Session:
         """SearchEngine.last_field_stats_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_field_stats_stats", self.h, 3)
 
+    def bucket_stats(self, filter=None, field=None, bucket_by=None, edges=()):
+        """SearchEngine.bucket_stats on this session (its mask cache holds the filters' masks)."""
+        return _bucket_stats(self.engine, self.h, filter, field, bucket_by, edges)
+
+    def last_bucket_stats_stats(self):
+        """SearchEngine.last_bucket_stats_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_bucket_stats_stats", self.h, 3)
+
+    def last_bucket_stats_placement(self):
+        """SearchEngine.last_bucket_stats_placement of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_bucket_stats_placement", self.h, 3)
+
     def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None):
         """SearchEngine.field_quantiles on this session (its mask cache holds the filters' masks)."""
         return _field_quantiles(self.engine, self.h, filter, field, q, group_by)
@@ -1554,25 +1624,29 @@ def _list_group_members(engine, sh, filter, group_by, order_by, ascending, per_g
                         lambda _, msg: GroupMembersListing(error=msg))
 
 
+def _edge_arrays(edges, keep):
+    """(number of edges, int64 pointer or None, double pointer) of a request's edges; the arrays are appended to keep, which must outlive the call.  Integer
+    edges only when every edge is a Python int (not a bool) that an int64 holds; double edges always (what float() refuses is passed as NaN: refused)."""
+    ed = tuple(edges)
+    ei = None
+    if ed and all(isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63 for x in ed):
+        ei = np.asarray(ed, np.int64); keep.append(ei)
+    vals = []
+    for x in ed:
+        try:
+            vals.append(float(x))
+        except (TypeError, ValueError, OverflowError):
+            vals.append(float("nan"))
+    edd = np.asarray(vals, np.float64); keep.append(edd)
+    return min(len(ed), 0xFFFFFFFF), None if ei is None else _p(ei, C.c_int64), _p(edd, C.c_double)
+
+
 def _range_facets(engine, sh, filter, field, edges):
     """infx_engine_range_facets on session handle sh: a RangeFacets for one request (given by its parts), a list of them for a sequence of RangeRequest."""
     keep = []                                            # the edge arrays live until the calls have returned
 
     def pack(r):
-        ed = tuple(r.edges)
-        # integer edges only when every edge is a Python int (not a bool) that an int64 holds; double edges always (what float() refuses is passed as NaN: refused)
-        ei = None
-        if ed and all(isinstance(x, int) and not isinstance(x, bool) and -2 ** 63 <= x < 2 ** 63 for x in ed):
-            ei = np.asarray(ed, np.int64); keep.append(ei)
-        vals = []
-        for x in ed:
-            try:
-                vals.append(float(x))
-            except (TypeError, ValueError, OverflowError):
-                vals.append(float("nan"))
-        edd = np.asarray(vals, np.float64); keep.append(edd)
-        return _RangeReq(None if r.filter is None else r.filter.encode(), None if r.field is None else str(r.field).encode(), min(len(ed), 0xFFFFFFFF),
-                         None if ei is None else _p(ei, C.c_int64), _p(edd, C.c_double))
+        return _RangeReq(None if r.filter is None else r.filter.encode(), None if r.field is None else str(r.field).encode(), *_edge_arrays(r.edges, keep))
 
     def read(i, r):
         tot = C.c_uint32(0); below = C.c_uint32(0); above = C.c_uint32(0); nan = C.c_uint32(0)
@@ -1630,6 +1704,35 @@ def _field_stats(engine, sh, filter, field, group_by):
     return _per_request(engine, sh, "infx_engine_field_stats", "infx_engine_field_stats_error", _StatsReq,
                         [StatsRequest(filter, field, group_by)] if single else list(filter), single, pack, read,
                         lambda r, msg: FieldStats(error=msg))
+
+
+def _bucket_stats(engine, sh, filter, field, bucket_by, edges):
+    """infx_engine_bucket_stats on session handle sh: a BucketStats for one request (given by its parts), a list of them for a sequence of BucketStatsRequest."""
+    keep = []                                            # the edge arrays live until the calls have returned
+
+    def pack(r):
+        return _BucketStatsReq(*[None if x is None else str(x).encode() for x in (r.filter, r.field, r.bucket_by)], *_edge_arrays(r.edges, keep))
+
+    def row(size, f):
+        return BucketRow(size, *_stats_figures(f))
+
+    def read(i, r):
+        tot = C.c_uint32(0); whole = _StatsFigures()
+        engine._check(engine.L.infx_engine_bucket_stats_total(sh, i, C.byref(tot)))
+        engine._check(engine.L.infx_engine_bucket_stats_whole(sh, i, C.byref(whole)))
+        m = engine.L.infx_engine_bucket_stats_rows(sh, i, None, None, 0)
+        if m < 3:
+            engine._check(1)
+        sizes = np.zeros(m, np.uint32); figs = (_StatsFigures * m)()
+        engine.L.infx_engine_bucket_stats_rows(sh, i, _p(sizes, C.c_uint32), figs, m)
+        rows = [row(s, f) for s, f in zip(sizes.tolist(), np.frombuffer(figs, _STATS_FIGURES).tolist())]      # [below | B buckets | above | nan]
+        w = np.frombuffer(whole, _STATS_FIGURES)[0].tolist()
+        return BucketStats(tuple(r.edges), rows[1:m - 2], rows[0], rows[m - 2], rows[m - 1], row(w[0] + w[1], w), int(tot.value), None)
+    single = filter is None or isinstance(filter, str)
+    # (one mask slot per distinct filter: sixteen requests per device call)
+    return _per_request(engine, sh, "infx_engine_bucket_stats", "infx_engine_bucket_stats_error", _BucketStatsReq,
+                        [BucketStatsRequest(filter, field, bucket_by, edges)] if single else list(filter), single, pack, read,
+                        lambda r, msg: BucketStats(edges=tuple(r.edges), error=msg))
 
 
 _DISTINCT_FIGURES = np.dtype([("size", "<u4"), ("distinct", "<u4")])

@@ -765,6 +765,17 @@ class ShardedSearcher:
     def last_field_stats_stats(self):
         return self.sessions[0].s.last_field_stats_stats()
 
+    def bucket_stats(self, filter=None, field=None, bucket_by=None, edges=()):
+        """SearchEngine.bucket_stats: like field_stats, every rank adds over the whole columns with the global Deleted flags on its own GPU and gets the same
+        answer — nothing is exchanged."""
+        return self.sessions[0].s.bucket_stats(filter, field, bucket_by, edges)
+
+    def last_bucket_stats_stats(self):
+        return self.sessions[0].s.last_bucket_stats_stats()
+
+    def last_bucket_stats_placement(self):
+        return self.sessions[0].s.last_bucket_stats_placement()
+
     def field_quantiles(self, filter=None, field=None, q=(0.5,), group_by=None):
         """SearchEngine.field_quantiles: like field_stats, every rank selects over the whole columns with the global Deleted flags on its own GPU and gets the
         same answer — no collective."""
