@@ -368,6 +368,35 @@ int32_t infx_engine_last_prefilter_stats(infx_session* s, uint32_t* built, uint3
 /* Parity tooling: the mask of one expression as the device holds it — built, or taken from the session's cache — one byte per indexed document in
  * out_bytes (cap >= the number of documents): 1 = Deleted or not accepted. */
 int32_t infx_engine_prefilter_mask(infx_session* s, const char* expr, uint8_t* out_bytes, uint64_t cap);
+/* ---- Query.collapse_by: the best N ranked rows of every group (not in the reference; DESIGN.md "collapse_by") ----------------------------------------
+ * What Elasticsearch calls collapse, Solr field collapsing and Algolia distinct: "at most one hit per product family", "no more than three results per shop".
+ * For a query Q with collapse field F and keep N, let Q0 be Q without collapsing, Filter, EnableFacets, Boosts and SortBy and with MaxNumberOfRecordsToReturn =
+ * CoverageDepth, and L the rows Q0 returns: the whole ranked list the pipeline has for the query (at most CoverageDepth <= 1024 rows, consolidated per key, cut
+ * at the truncation index, the Stage-1 fallback rows where coverage returned nothing; with a pre-filter, of the documents it accepts).  A row's group is the
+ * dictionary code, in column F, of the document whose score it carries — one code one group, as in infx_engine_list_groups; any column will do.  A row is kept
+ * when fewer than N earlier rows of L have its group; kept rows stay in L's order with their scores and tiebreakers.  Q returns the first
+ * MaxNumberOfRecordsToReturn kept rows with Q0's result flags; Filter, facets, Boosts and SortBy then work on those rows as they do on any query's, and the
+ * post-rows limit is held against MaxNumberOfRecordsToReturn, not against L.  Truncation is decided on L, before anything is collapsed.
+ * infx_engine_set_query_collapse installs fields[i] (a column name, UTF-8; NULL: query i is not collapsed; fields == NULL: none is) and keeps[i] (1 ..
+ * INFX_COLLAPSE_MAX_KEEP) for the session's NEXT search of nq queries: consumed by that search like infx_engine_set_query_prefilters, usable with or without
+ * infx_engine_set_query_options, nq = 0 clears, a search of another nq fails with INFX_EINVAL and clears them.  The caller's row stride and output arrays do not
+ * grow: L lives in scratch of the session.  A query is rejected on its own — empty result, result flag bit 4, its status in out_status[i], its message from
+ * infx_engine_query_error, neighbours unaffected — for an unknown column or a keep outside 1 .. 16 (INFX_EINVAL), an empty text with EnableFacets (a browse
+ * query ranks nothing; known when the batch runs: the status then shows in the result flag and the message only), the host phases (INFX_PHASED) and a sharded
+ * engine (INFX_EUNSUPPORTED each), an engine without a GPU (INFX_EHIP).  An empty text without facets stays an empty result without error.
+ * A batch without a collapsing query launches the kernels it launched before with the arguments it passed before.
+ *   infx_engine_last_collapse        per query of the session's last search (nq: its size) the distinct groups of L and the rows of L; 0 where none was folded
+ *   infx_engine_collapse_rows        query qi's rows as returned (after Filter and SortBy): *col the collapse column, per row its group's code in that column
+ *                                    (infx_engine_column_value gives the text) and the rows of L in its group, itself included; returns the rows written (at most
+ *                                    cap), -1 on error or for a query that was not collapsed
+ *   infx_engine_last_collapse_stats  collapsing queries and k_collapse launches of the session's last search: (k, 1) with k collapsing queries, (0, 0) without */
+#define INFX_COLLAPSE_MAX_KEEP 16
+int32_t infx_engine_set_query_collapse(infx_session* s, uint32_t nq, const char* const* fields /* NULL: none */, const int32_t* keeps, int32_t* out_status /* nq, may be NULL */);
+int32_t infx_engine_last_collapse(infx_session* s, uint32_t nq, uint32_t* total_groups, uint32_t* total_ranked);
+int32_t infx_engine_collapse_rows(infx_session* s, uint32_t qi, int32_t* col, uint32_t* codes, uint32_t* sizes, int32_t cap); /* rows written, -1 on error */
+int32_t infx_engine_last_collapse_stats(infx_session* s, uint32_t* queries, uint32_t* launches);
+/* ms2[0] k_finalize's and ms2[1] k_collapse's duration in the session's last search (HIP events on its stream; zeros when nothing was collapsed) */
+int32_t infx_engine_last_collapse_timings(infx_session* s, float* ms2);
 /* ---- facets of the documents a filter accepts (not in the reference: the facet side of Query.pre_filter) --------------------------------------------------
  * The facets of an Infiscript expression P: the value counts of every facetable column (the first INFX_MAX_FACET_COLS) over the documents that are not Deleted
  * and whose OWN fields P accepts — per document, as NumberOfDocumentsInFilter counts and as the pre-filter masks are built, not through the key's first live

@@ -386,6 +386,28 @@ int32_t infx_filter_masks(infx_stream* s, uint32_t k, const infx_filter_prog* pr
 int32_t infx_stream_set_doc_masks(infx_stream* s, uint32_t nq, const uint8_t* const* masks);
 int32_t infx_last_filter_mask_stats(infx_stream* s, uint32_t* built, uint32_t* launches);
 
+/* ---- collapsing: at most `keep` ranked rows per group (not in the reference; DESIGN.md "collapse_by") ------------------------------------------------
+ * infx_stream_set_query_collapse installs one request per query of the stream's NEXT finalize of nq queries (infx_search_fused): col < 0 = the query is not
+ * collapsed, else the column whose dictionary code is a row's group (uploaded, covering the corpus) and keep in 1 .. INFX_COLLAPSE_MAX_KEEP.  Consumed by that
+ * batch, whatever its outcome; nq = 0 clears; a batch of another size fails with INFX_EINVAL.  The depth of such a batch is at most 1024.
+ * A collapsing query's ranked list L is what the same query returns with max_results = depth and nothing else installed (consolidated, cut at the truncation
+ * index, the Stage-1 rows where coverage returned nothing).  A row of L is kept when fewer than `keep` earlier rows of L carry the code of its document; the
+ * query returns the first max_results kept rows, in L's order, and the post-filter, facets, boosts and sort-by run on those.  k_finalize writes L into a window
+ * of the stream's scratch, ONE k_collapse launch (a workgroup per collapsing query) writes the kept rows at the caller's stride: the caller's buffers do not
+ * grow.  A batch without a request launches exactly what it launched before.  Positions and integer adds only: the same bytes from any stream and placement.
+ *   infx_last_collapse        per query of the last batch (nq: its size) the distinct groups of L and the rows of L; 0 for a query that was not collapsed
+ *   infx_collapse_rows        query qi's returned rows, as the post-processing left them: each row's group code and the size of its group in L; returns the
+ *                             rows written (at most cap), -1 on error
+ *   infx_last_collapse_stats  collapsing queries and k_collapse launches of the stream's last finalize
+ *   infx_last_collapse_timings  ms2[0] k_finalize's and ms2[1] k_collapse's duration in that finalize (HIP events; zeros when nothing was collapsed) */
+#define INFX_COLLAPSE_MAX_KEEP 16
+typedef struct infx_collapse_req { int32_t col; int32_t keep; } infx_collapse_req;
+int32_t infx_stream_set_query_collapse(infx_stream* s, uint32_t nq, const infx_collapse_req* reqs);
+int32_t infx_last_collapse(infx_stream* s, uint32_t nq, uint32_t* total_groups, uint32_t* total_ranked);
+int32_t infx_collapse_rows(infx_stream* s, uint32_t qi, uint32_t* codes, uint32_t* sizes, int32_t cap);
+int32_t infx_last_collapse_stats(infx_stream* s, uint32_t* queries, uint32_t* launches);
+int32_t infx_last_collapse_timings(infx_stream* s, float* ms2);
+
 /* ---- browse rows: a query with no text and EnableFacets (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346) -------------------------
  * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= the index's post rows, else INFX_EUNSUPPORTED) documents in
  * internal order that are not Deleted and that its filter accepts — the filter of its infx_query_post descriptor (which must carry INFX_QP_FACETS) or

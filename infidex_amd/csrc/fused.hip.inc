@@ -311,12 +311,16 @@ __global__ __launch_bounds__(P2_THREADS) void k_prep2(DevIndex ix, const infx_hi
 // ---- k_finalize: one workgroup per query ------------------------------------------------------------------------------------
 // dynamic LDS (Cp = power of two >= 2 * depth): sKey[Cp] i64 | sBits[Cp] u32 (score bits) | sPos[Cp] u32 | sIdx[Cp] u16 | sTie[Cp] u8 |
 //                                               sFlag[Cp] u8 | part[257] u32
-__global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx_fused_query* __restrict__ fqs, const FusedMeta* __restrict__ metas,
+// WIN (k_finalize_win, a batch with a collapsing query): a query with a window (winSlot[qi] >= 0) gets a budget of `depth` rows — its whole ranked list — and
+// writes them, documents included, into its window instead of its rows of the batch buffers (collapse.hip.inc).  The other queries of the batch, and every
+// query of k_finalize, are written as ever.
+struct FinalizeWindows { const int32_t* slot; long long* keys; float* scores; uint8_t* ties; int32_t* docs; };
+template <bool WIN> __device__ __forceinline__ void finalize_rows(const DevIndex& ix, const infx_fused_query* __restrict__ fqs, const FusedMeta* __restrict__ metas,
                                                           const infx_cov_cand* __restrict__ cands, const infx_cov_out* __restrict__ outs,
                                                           const infx_hit* __restrict__ s1, int depth, int Cp, int maxResults,
                                                           long long* __restrict__ outKeys, float* __restrict__ outScores, uint8_t* __restrict__ outTies,
                                                           uint32_t* __restrict__ outCounts, uint32_t* __restrict__ outFlags, uint32_t* __restrict__ errFlag,
-                                                          int32_t* __restrict__ outDocs, const infx_finalize_setup* __restrict__ fins) {
+                                                          int32_t* __restrict__ outDocs, const infx_finalize_setup* __restrict__ fins, const FinalizeWindows& win) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     long long* sKey = (long long*)smem;
     uint32_t* sBits = (uint32_t*)(sKey + Cp);
@@ -330,10 +334,12 @@ __global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx
     const int qi = blockIdx.x, tid = threadIdx.x;
     const infx_fused_query FQ = fqs[qi];
     const FusedMeta M = metas[qi];
-    const int mr = min(FQ.max_results, maxResults);
+    const int32_t ws = WIN ? win.slot[qi] : -1;
+    const int mr = ws >= 0 ? depth : min(FQ.max_results, maxResults);
     uint32_t flags = (FQ.flags & FQ_UNSUPPORTED) ? 1u : 0u;
     long long* oK = outKeys + (size_t)qi * maxResults; float* oS = outScores + (size_t)qi * maxResults; uint8_t* oT = outTies ? outTies + (size_t)qi * maxResults : nullptr;
     int32_t* oD = outDocs ? outDocs + (size_t)qi * maxResults : nullptr;       // global internal ids of the rows (post-filter / facets)
+    if (ws >= 0) { const size_t w = (size_t)ws * depth; oK = win.keys + w; oS = win.scores + w; oT = win.ties + w; oD = win.docs + w; }
     bool useStage1 = true;
     uint32_t nOut = 0;
     if (M.runCov) {
@@ -416,3 +422,10 @@ __global__ __launch_bounds__(P2_THREADS) void k_finalize(DevIndex ix, const infx
     }
     if (tid == 0) { outCounts[qi] = nOut; if (outFlags) outFlags[qi] = flags; }
 }
+#define FINALIZE_PARAMS DevIndex ix, const infx_fused_query* __restrict__ fqs, const FusedMeta* __restrict__ metas, const infx_cov_cand* __restrict__ cands,                       \
+                        const infx_cov_out* __restrict__ outs, const infx_hit* __restrict__ s1, int depth, int Cp, int maxResults, long long* __restrict__ outKeys,                 \
+                        float* __restrict__ outScores, uint8_t* __restrict__ outTies, uint32_t* __restrict__ outCounts, uint32_t* __restrict__ outFlags,                            \
+                        uint32_t* __restrict__ errFlag, int32_t* __restrict__ outDocs, const infx_finalize_setup* __restrict__ fins
+#define FINALIZE_ARGS ix, fqs, metas, cands, outs, s1, depth, Cp, maxResults, outKeys, outScores, outTies, outCounts, outFlags, errFlag, outDocs, fins
+__global__ __launch_bounds__(P2_THREADS) void k_finalize(FINALIZE_PARAMS) { finalize_rows<false>(FINALIZE_ARGS, FinalizeWindows{}); }
+__global__ __launch_bounds__(P2_THREADS) void k_finalize_win(FINALIZE_PARAMS, FinalizeWindows win) { finalize_rows<true>(FINALIZE_ARGS, win); }

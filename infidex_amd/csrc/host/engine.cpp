@@ -86,6 +86,12 @@ struct QueryPre {
     std::vector<uint8_t> has, reject; std::vector<int32_t> status; std::vector<std::string> err;      // has: the query asked for one
     std::vector<std::string> pinned;           // cache entries the batch holds
 };
+// Query.collapse_by of the session's next batch (infx_engine_set_query_collapse): consumed by that batch like QueryPre, with or without QueryOpts.
+struct QueryClp {
+    bool on = false, bound = false; uint32_t nq = 0;
+    std::vector<int32_t> col, keep;            // per query: its column (-1: none, or refused) and the rows kept per group
+    std::vector<uint8_t> has, reject; std::vector<int32_t> status; std::vector<std::string> err;      // has: the query asked for it
+};
 // One mask of the session's cache (mask slot i of its stream): the expression it was built from, the engine's mask epoch at that time, the live documents
 // it accepts, when it was last used (least recently used first out)
 struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t count = 0; bool valid = false; };
@@ -125,6 +131,7 @@ template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskU
 struct infx_session {
     QueryCov qc;
     QueryPre qp;
+    QueryClp qk; std::vector<int32_t> lastClpCol;      // lastClpCol: per query of the last batch the column it was collapsed by (-1: it was not)
     PreMask preMask[INFX_MAX_PREFILTERS]; uint64_t preTick = 0; uint32_t preCountBuf[INFX_MAX_PREFILTERS] = {};      // preCountBuf: where a build's counts land
     std::vector<uint32_t> lastInPre; uint32_t preBuilt = 0, preReused = 0, preLaunches = 0;      // of the last batch (or infx_engine_prefilter_mask)
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
@@ -219,6 +226,10 @@ static int32_t query_cov_check(infx_session* S, uint32_t nq);
 static int32_t query_pre_check(infx_session* S, uint32_t nq);
 static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static void clear_query_prefilters(infx_session* S);
+static int32_t query_clp_check(infx_session* S, uint32_t nq);
+static void query_clp_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq);
+static void clear_query_collapse(infx_session* S);
 // The filter and mask part of one call over the documents that filters accept: a batch with pre-filters, infx_engine_prefilter_mask, _list_documents,
 // _range_facets, _field_stats.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
 // the session's mask cache, mask(i) is request i's; the device call that follows ends in failed(rc) or done().  (Defined with the mask cache, below.)
@@ -1273,10 +1284,11 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     // Pre-filters: the masks the batch is missing are staged on the session's stream (one launch in front of the batch, no host wait), each query's flags installed
     MaskCall pre(S, nq);
     rc = stage_prefilters(S, nq, fq, pre); if (rc) return rc;
+    rc = stage_collapse(S, nq, fq); if (rc) return pre.failed(rc);
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
-    if (rc) return pre.failed(rc);
+    if (rc) { if (S->qk.on) infx_stream_set_query_collapse(S->stream, 0, nullptr); return pre.failed(rc); }
     pre.done(nq);
     B.t3 = now_ms();
     // Kernel durations are resolved when somebody asks (infx_engine_session_last_timings): every hipEventElapsedTime is a HIP API call that queues behind the
@@ -1330,13 +1342,14 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
                                  int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                  uint32_t* out_counts, uint32_t* out_flags) {
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (!rc) rc = query_clp_check(S, nq); if (rc) return rc; }
     e->searched.store(true, std::memory_order_relaxed);
     S->lastInPre.assign(nq, 0);
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     query_cov_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     query_pre_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
+    query_clp_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     return rc ? rc : rc2;
 }
 static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
@@ -1413,8 +1426,9 @@ int32_t infx_session_phase0(infx_session* S, uint32_t nq, const uint16_t* q_aren
     if (S->qo.on && S->qo.bound) clear_query_options(S);        // left by a sharded batch that failed between its phase 0 and phase 4
     if (S->qc.on && S->qc.bound) S->qc = QueryCov();
     if (S->qp.on && S->qp.bound) clear_query_prefilters(S);
-    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (rc) return rc; }
-    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on; S->qp.bound = S->qp.on; S->lastInPre.assign(nq, 0);
+    if (S->qk.on && S->qk.bound) clear_query_collapse(S);
+    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (!rc) rc = query_clp_check(S, nq); if (rc) return rc; }
+    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on; S->qp.bound = S->qp.on; S->qk.bound = S->qk.on; S->lastInPre.assign(nq, 0);
     PlanGateHold hold(S->e->gate);
     int32_t rc = ph_plan(S->e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     if (nunions) *nunions = (uint32_t)S->batch->pending.size();
@@ -1886,7 +1900,7 @@ int32_t infx_session_coll_stats(infx_session* S, uint64_t* out4) {      // all-r
 }
 int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits, const uint32_t* all_counts, int32_t max_results, int32_t enable_coverage, uint64_t* ncand) {
     if (!S || W < 1 || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (!rc) rc = query_clp_check(S, S->batch->nq); if (rc) return rc; }
     static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
     if (hostPhases) {
         int32_t rc = ph_stage2(S->e, S, W, all_hits, all_counts, max_results, enable_coverage); if (rc) return rc;
@@ -1931,7 +1945,7 @@ int32_t infx_session_phase2x(infx_session* S, const uint32_t* global_counts, voi
 }
 int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, const void* all_counts, int32_t max_results, int32_t enable_coverage, void* outs) {
     if (!S || W < 1 || max_results < 1 || !outs) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (rc) return rc; }
+    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (!rc) rc = query_clp_check(S, S->batch->nq); if (rc) return rc; }
     infx_engine* e = S->e; Batch& B = *S->batch;
     B.maxResults = max_results;
     std::shared_ptr<FusedIn> FIp; int32_t rc = fused_inputs_for_phase3(e, S, max_results, enable_coverage, FIp); if (rc) return rc;
@@ -1962,15 +1976,17 @@ int32_t infx_session_phase4(infx_session* S, const int32_t* merged_outs3, int64_
         const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK);
         query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
         query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
+        query_clp_finish(S, out_counts, out_flags, rc == INFX_OK);
         return rc ? rc : rc2;
     }
     Batch& B = *S->batch;
     if (B.nq) {
         int32_t rc = infx_shard_finalize(S->stream, B.nq, (const infx_cov_out*)merged_outs3, B.depth, B.maxResults, out_keys, out_scores, out_ties, out_counts, out_flags);
-        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); query_pre_finish(S, out_counts, out_flags, false); return rc; }
+        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); query_pre_finish(S, out_counts, out_flags, false); query_clp_finish(S, out_counts, out_flags, false); return rc; }
         rc = query_options_finish(S, out_counts, out_flags, true);
         query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
         query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
+        query_clp_finish(S, out_counts, out_flags, rc == INFX_OK);
         if (rc) return rc;
         float ms5[5] = {0, 0, 0, 0, 0}; infx_last_fused_timings(S->stream, ms5); S->msFin = ms5[4];
     }
@@ -3011,6 +3027,108 @@ static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* ou
         if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
     }
     clear_query_prefilters(S);
+}
+// ---- Query.collapse_by: at most collapse_keep ranked rows per group ------------------------------------------------------------------------------------
+// (include/infidex_engine.h, "collapse_by"; the step itself is the device library's: include/infidex_hip.h, "collapsing")
+static void clear_query_collapse(infx_session* S) { S->qk = QueryClp(); }
+int32_t infx_engine_set_query_collapse(infx_session* S, uint32_t nq, const char* const* fields, const int32_t* keeps, int32_t* out_status) {
+    if (!S || (nq && fields && !keeps)) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    clear_query_collapse(S);
+    if (nq == 0 || !fields) return INFX_OK;
+    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
+    QueryClp Q; Q.nq = nq;
+    Q.col.assign(nq, -1); Q.keep.assign(nq, 1); Q.has.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
+    {
+        std::lock_guard<std::mutex> lk(e->filterMu);
+        for (uint32_t i = 0; i < nq; i++) {
+            if (!fields[i]) continue;
+            Q.has[i] = 1;
+            auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
+            const int32_t col = column_named(e, fields[i]);
+            if (col < 0) { reject(INFX_EINVAL, std::string("collapse_by: no field named '") + fields[i] + "'"); continue; }
+            if (keeps[i] < 1 || keeps[i] > INFX_COLLAPSE_MAX_KEEP) { reject(INFX_EINVAL, "collapse_keep is 1 .. 16 rows per group"); continue; }
+            if (engine_sharded(e)) { reject(INFX_EUNSUPPORTED, "collapse_by needs an engine that is not sharded: the ranked list is folded on one device"); continue; }
+            if (hostPhases) { reject(INFX_EUNSUPPORTED, "collapse_by runs in the device pipeline: the host phases (INFX_PHASED) do not fold the ranked list"); continue; }
+            if (!e->dev || !S->stream) { reject(INFX_EHIP, "no GPU: the ranked list is folded on the device"); continue; }
+            Q.col[i] = col; Q.keep[i] = keeps[i];
+        }
+    }
+    const bool sameBatch = (S->qo.on && S->qo.nq == nq) || (S->qc.on && S->qc.nq == nq) || (S->qp.on && S->qp.nq == nq);
+    if (!sameBatch || S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
+    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
+    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
+    Q.on = true;
+    S->qk = std::move(Q);
+    return INFX_OK;
+}
+static int32_t query_clp_check(infx_session* S, uint32_t nq) {
+    if (!S->qk.on) return INFX_OK;
+    if (nq != S->qk.nq) { clear_query_collapse(S); return efail(INFX_EINVAL, "the per-query collapse requests were installed for a batch of another size"); }
+    return INFX_OK;
+}
+// Before the batch's infx_search_fused: refuses collapse_by on a browse query, installs each query's request on the stream
+static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq) {
+    QueryClp& Q = S->qk;
+    if (!Q.on || Q.nq != nq) return INFX_OK;
+    std::vector<infx_collapse_req> reqs(nq, infx_collapse_req{-1, 1}); bool any = false;
+    for (uint32_t i = 0; i < nq; i++) {
+        if (!Q.has[i] || Q.reject[i]) continue;
+        if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: nothing is ranked
+            Q.reject[i] = 1; Q.status[i] = INFX_EUNSUPPORTED; Q.err[i] = "collapse_by does not apply to a browse query (empty text with EnableFacets): nothing is ranked; list_groups lists one row per group";
+            fq[i].flags &= ~INFX_FQ_BROWSE;
+            continue;
+        }
+        reqs[i] = infx_collapse_req{Q.col[i], Q.keep[i]}; any = true;
+    }
+    if (!any) return INFX_OK;
+    const int32_t rc = infx_stream_set_query_collapse(S->stream, nq, reqs.data());
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+// The batch is done: a query whose request was refused comes back empty with result flag bit 4; which queries were collapsed, by which column; consumed
+static void query_clp_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
+    if (!S->qk.on) { S->lastClpCol.clear(); return; }
+    const QueryClp& Q = S->qk;
+    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
+    S->lastClpCol.assign(Q.nq, -1);
+    for (uint32_t i = 0; i < Q.nq; i++) {
+        if (Q.reject[i]) {
+            if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
+            if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
+        } else if (ok && Q.has[i] && !(out_flags && (out_flags[i] & INFX_RESULT_REJECTED))) S->lastClpCol[i] = Q.col[i];
+    }
+    clear_query_collapse(S);
+}
+int32_t infx_engine_last_collapse(infx_session* S, uint32_t nq, uint32_t* total_groups, uint32_t* total_ranked) {
+    if (!S || (nq && (!total_groups || !total_ranked))) return efail(INFX_EINVAL, "null argument");
+    if (nq != S->lastClpCol.size()) return efail(INFX_EINVAL, "no batch of this size with collapse requests on the session");
+    bool any = false; for (int32_t c : S->lastClpCol) any |= c >= 0;
+    if (any) { const int32_t rc = infx_last_collapse(S->stream, nq, total_groups, total_ranked); if (rc) { g_eerr = infx_last_error(); return rc; } }
+    for (uint32_t i = 0; i < nq; i++) if (S->lastClpCol[i] < 0) total_groups[i] = total_ranked[i] = 0;
+    return INFX_OK;
+}
+int32_t infx_engine_collapse_rows(infx_session* S, uint32_t qi, int32_t* col, uint32_t* codes, uint32_t* sizes, int32_t cap) {
+    if (!S || qi >= S->lastClpCol.size() || S->lastClpCol[qi] < 0 || !S->stream) { efail(INFX_EINVAL, "no collapsed query of this index in the session's last batch"); return -1; }
+    if (col) *col = S->lastClpCol[qi];
+    const int32_t n = infx_collapse_rows(S->stream, qi, codes, sizes, cap);
+    if (n < 0) g_eerr = infx_last_error();
+    return n;
+}
+int32_t infx_engine_last_collapse_stats(infx_session* S, uint32_t* queries, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (!S->stream) return put_stats({{queries, 0u}, {launches, 0u}});
+    const int32_t rc = infx_last_collapse_stats(S->stream, queries, launches);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+int32_t infx_engine_last_collapse_timings(infx_session* S, float* ms2) {
+    if (!S || !ms2) return efail(INFX_EINVAL, "null argument");
+    ms2[0] = ms2[1] = 0.f;
+    if (!S->stream) return INFX_OK;
+    const int32_t rc = infx_last_collapse_timings(S->stream, ms2);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
 }
 static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots) {
     for (int b : builtSlots) S->preMask[b].valid = false;

@@ -274,6 +274,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "quantiles.hip.inc"
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
+#include "collapse.hip.inc"
 
 // ---------------------------------------------------------------------------------------------------------------
 struct infx_filter {
@@ -391,6 +392,13 @@ struct infx_stream {
     std::vector<int32_t> qpRows;      // max_results of each fused query of the batch, kept only by an index with more than INFX_FILTER_MAX_ROWS post rows
     void *dBrwBlob = nullptr, *dBrwWork = nullptr; size_t capBrwBlob = 0, capBrwWork = 0;
     uint32_t lastBrowseGroups = 0, lastBrowseLaunches = 0;      // groups and k_browse_scan launches of the last finalize
+    // Query.collapse_by of the NEXT batch (infx_stream_set_query_collapse), consumed by its finalize; the windows and what k_collapse keeps (dClp: one blob);
+    // of the last batch: each query's slot (-1: none), the stride, per slot the groups and rows of its list and the rows k_collapse wrote, per such row its document, code and size
+    bool clpOn = false; std::vector<infx_collapse_req> clpReq;
+    void* dClp = nullptr; size_t capClp = 0;
+    std::vector<int32_t> clpSlot, clpDocs, clpFinalDocs; std::vector<uint32_t> clpCodes, clpSizes, clpGroups, clpRanked, clpReturned, clpCounts; uint32_t clpStride = 0; bool clpPosted = false;
+    uint32_t lastClpQueries = 0, lastClpLaunches = 0;
+    hipEvent_t evK0 = nullptr, evK1 = nullptr; bool timedClp = false;      // around k_collapse (created by the first batch that collapses): evF0 .. evK0 is k_finalize_win
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
     void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
     uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
@@ -1333,7 +1341,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dClp};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (const SetKindState& K : s->kind) { if (K.ws) hipFree(K.ws); if (K.out) hipFree(K.out); }
     for (void* p : ps) if (p) hipFree(p);
@@ -1347,6 +1355,8 @@ void infx_stream_destroy(infx_stream* s) {
     hipEventDestroy(s->evSync);
     if (s->evPlan) hipEventDestroy(s->evPlan);
     if (s->evJoin) hipEventDestroy(s->evJoin);
+    if (s->evK0) hipEventDestroy(s->evK0);
+    if (s->evK1) hipEventDestroy(s->evK1);
     { std::lock_guard<std::mutex> lk(s->ix->turnMu); if (s->ix->turnEvent == s->evTurn) s->ix->turnEvent = nullptr; }
     if (s->evTurn) hipEventDestroy(s->evTurn);
     if (s->stAux) { hipStreamSynchronize(s->stAux); hipStreamDestroy(s->stAux); }
@@ -2139,6 +2149,47 @@ static int32_t browse_enqueue(infx_stream* s, const ProgTable& T, const char* dC
     return INFX_OK;
 }
 
+static int32_t check_group_column(const infx_index* ix, int32_t col, const char* what);
+// The finalize of a batch with collapsing queries (list, in batch order): k_finalize_win — every query as k_finalize writes it, but the listed ones into their
+// windows with a budget of `depth` rows — then ONE k_collapse launch of list.size() workgroups.  One blob holds the list, the slots, the windows and what
+// k_collapse keeps for the host; the kept part is downloaded with the batch's other outputs (no host wait here).
+static int32_t collapse_enqueue(infx_stream* s, const std::vector<DevCollapse>& list, uint32_t nq, int32_t depth, int Cp, size_t lds, int32_t max_results, bool ties) {
+    const size_t k = list.size(), rows = k * (size_t)depth, out = k * (size_t)max_results;
+    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    const size_t oList = 0, oSlot = al(oList + k * sizeof(DevCollapse)), oWK = al(oSlot + (size_t)nq * 4), oWS = al(oWK + rows * 8), oWD = al(oWS + rows * 4), oWT = al(oWD + rows * 4);
+    const size_t oRD = al(oWT + rows), oRC = oRD + out * 4, oRS = oRC + out * 4, oG = oRS + out * 4, oR = oG + k * 4, oN = oR + k * 4, total = oN + k * 4;
+    GROW(s->dClp, s->capClp, total);
+    char* D = (char*)s->dClp;
+    s->clpSlot.assign(nq, -1);
+    for (size_t i = 0; i < k; i++) s->clpSlot[list[i].qi] = (int32_t)i;
+    std::vector<uint8_t> H(oWK, 0);
+    std::memcpy(H.data() + oList, list.data(), k * sizeof(DevCollapse)); std::memcpy(H.data() + oSlot, s->clpSlot.data(), (size_t)nq * 4);
+    UP(D, H.data(), oWK);
+    FinalizeWindows win{(const int32_t*)(D + oSlot), (long long*)(D + oWK), (float*)(D + oWS), (uint8_t*)(D + oWT), (int32_t*)(D + oWD)};
+    k_finalize_win<<<nq, P2_THREADS, lds, s->st>>>(dev_index(s), (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
+                                                    (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, Cp, max_results,
+                                                    (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
+                                                    (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, (int32_t*)s->dFDocs,
+                                                    (const infx_finalize_setup*)s->dFin, win);
+    HIPCHK(hipGetLastError());
+    if (!s->evK0) { HIPCHK(hipEventCreate(&s->evK0)); HIPCHK(hipEventCreate(&s->evK1)); }
+    HIPCHK(hipEventRecord(s->evK0, s->st));
+    DevCollapseIo io{};
+    io.wKeys = win.keys; io.wScores = win.scores; io.wTies = win.ties; io.wDocs = win.docs; io.depth = (uint32_t)depth;
+    io.keys = (long long*)s->dFKeys; io.scores = (float*)s->dFScores; io.ties = ties ? (uint8_t*)s->dFTies : nullptr; io.docs = (int32_t*)s->dFDocs;
+    io.counts = (uint32_t*)s->dFCounts; io.stride = (uint32_t)max_results;
+    io.rDocs = (int32_t*)(D + oRD); io.rCodes = (uint32_t*)(D + oRC); io.rSizes = (uint32_t*)(D + oRS); io.groups = (uint32_t*)(D + oG); io.ranked = (uint32_t*)(D + oR); io.returned = (uint32_t*)(D + oN);
+    k_collapse<<<(uint32_t)k, CLP_THREADS, 0, s->st>>>((const DevCollapse*)(D + oList), (const infx_fused_query*)s->dFQ, io);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->evK1, s->st)); s->timedClp = true;
+    s->clpStride = (uint32_t)max_results; s->lastClpQueries = (uint32_t)k; s->lastClpLaunches = 1;
+    s->clpDocs.resize(out); s->clpCodes.resize(out); s->clpSizes.resize(out); s->clpGroups.resize(k); s->clpRanked.resize(k); s->clpReturned.resize(k);
+    // (rows past a query's count are never read: infx_collapse_rows stops at the count; the blob's tail is downloaded as it is)
+    DOWN(s->clpDocs.data(), D + oRD, out * 4); DOWN(s->clpCodes.data(), D + oRC, out * 4); DOWN(s->clpSizes.data(), D + oRS, out * 4);
+    DOWN(s->clpGroups.data(), D + oG, k * 4); DOWN(s->clpRanked.data(), D + oR, k * 4); DOWN(s->clpReturned.data(), D + oN, k * 4);
+    return INFX_OK;
+}
+
 // k_finalize over s->dCovC / s->dCovO / s->dFMeta / s->dFS1 -> result rows in s->dFKeys ...
 static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth, int32_t max_results, bool ties) {
     infx_index* ix = s->ix;
@@ -2155,6 +2206,21 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     // facets / boosts / sort, staged as one descriptor that every query shares.  Nothing is staged or launched for a batch without either.
     const bool qp = s->qpOn;
     s->qpOn = false; s->lastCountK = 0; s->lastCountLaunches = 0;
+    // Query.collapse_by: the collapsing queries of this batch, in batch order (nothing below differs from a batch without one while the list is empty)
+    const bool clp = s->clpOn; s->clpOn = false;
+    s->lastClpQueries = s->lastClpLaunches = 0; s->clpSlot.clear(); s->clpPosted = false; s->timedClp = false;
+    std::vector<DevCollapse> clpList;
+    if (clp) {
+        if (s->clpReq.size() != nq) return fail(INFX_EINVAL, "the per-query collapse requests were installed for a batch of another size%s");
+        for (uint32_t q = 0; q < nq; q++) {
+            const infx_collapse_req& R = s->clpReq[q];
+            if (R.col < 0) continue;
+            { int32_t rc_ = check_group_column(ix, R.col, "collapse request"); if (rc_) return rc_; }
+            if (R.keep < 1 || R.keep > (int32_t)CLP_MAX_KEEP) return fail(INFX_EINVAL, "a collapse request keeps 1 .. INFX_COLLAPSE_MAX_KEEP (16) rows per group%s");
+            clpList.push_back(DevCollapse{ix->colCodes[R.col], q, (uint32_t)R.keep});
+        }
+        if (!clpList.empty() && depth > (int32_t)CLP_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "collapsing works on a ranked list of at most 1024 rows (the depth)%s");
+    }
     if (qp && s->qpNq != nq) return fail(INFX_EINVAL, "the per-query options were installed for a batch of another size%s");
     const bool post = !qp && (s->postFilter != nullptr || s->nFacet > 0);
     if (post && max_results > (int32_t)ix->postRows) return fail(INFX_EUNSUPPORTED, "post-filter / facets run on at most %s returned rows per query (infx_set_post_rows)", post_rows_text(ix).c_str());
@@ -2189,7 +2255,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         if (qp) for (auto& b : s->browseQ) if (!(s->qpDesc[b.first].flags & QP_FACETS)) { s->browseQ.clear(); return fail(INFX_EINVAL, "a browse query needs INFX_QP_FACETS in its descriptor%s"); }
         if (!ix->d.docKeyAll) { s->browseQ.clear(); return fail(INFX_EINVAL, "index not uploaded%s"); }
     }
-    if (launchPF || launchPP) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
+    if (launchPF || launchPP || !clpList.empty()) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
     const DevColumns cols = dev_columns(ix);
     const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr; const char* dCode = nullptr;
     // the batch's program table, boost list and descriptors: the staged per-query ones, or the session-wide filters (resident entries) behind one shared descriptor
@@ -2241,11 +2307,13 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         else if (s->finDefaultN < nq) { std::vector<infx_finalize_setup> d(nq, FIN_DEFAULT_SETUP); UP(s->dFin, d.data(), (size_t)nq * sizeof(infx_finalize_setup)); s->finDefaultN = nq; }
     }
     HIPCHK(hipEventRecord(s->evF0, s->st));
+    if (clpList.empty())
     k_finalize<<<nq, P2_THREADS, lds, s->st>>>(dev_index(s), (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
                                                 (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr,
                                                 (const infx_finalize_setup*)s->dFin);
+    else { int32_t rc_ = collapse_enqueue(s, clpList, nq, depth, (int)Cp, lds, max_results, ties); if (rc_) return rc_; }
     HIPCHK(hipGetLastError());
     if (browse) {
         const int32_t rc_ = browse_enqueue(s, T, dCode, desc.data(), descStride, ncount, max_results, ties);
@@ -2281,6 +2349,11 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         k_postproc<<<nq, WAVE, 0, s->st>>>(dPB, cols);
         if (widePP) k_postproc_wide<<<nq, PW_THREADS, 0, s->st>>>(dPB, cols, ix->postRows);
         HIPCHK(hipGetLastError());
+    }
+    if (!clpList.empty()) {      // the rows as the post-processing left them: their number and, where it ran, their documents, which find each row's group again (infx_collapse_rows)
+        s->clpCounts.resize(nq);
+        DOWN(s->clpCounts.data(), s->dFCounts, (size_t)nq * 4);
+        if (launchPF || launchPP) { s->clpFinalDocs.resize((size_t)nq * max_results); s->clpPosted = true; DOWN(s->clpFinalDocs.data(), s->dFDocs, (size_t)nq * max_results * 4); }
     }
     HIPCHK(hipEventRecord(s->evF1, s->st));
     s->timedFused = true;
@@ -2943,6 +3016,49 @@ int32_t infx_filter_count_progs(infx_stream* s, uint32_t k, const infx_filter_pr
     { int32_t rc_ = count_enqueue(s, (const DevFilter*)s->dPostBlob, k, T.columns(0, k), base, n, (uint32_t*)s->dQCount); if (rc_) return rc_; }
     DOWN(counts, s->dQCount, (size_t)k * 4);
     SYNC();
+    return INFX_OK;
+}
+// ---- Query.collapse_by (k_collapse) --------------------------------------------------------------------------------------------------------------------
+int32_t infx_stream_set_query_collapse(infx_stream* s, uint32_t nq, const infx_collapse_req* reqs) {
+    if (!s || (nq && !reqs)) return fail(INFX_EINVAL, "null argument%s");
+    s->clpOn = nq > 0; s->clpReq.assign(reqs, reqs + nq);
+    return INFX_OK;
+}
+int32_t infx_last_collapse(infx_stream* s, uint32_t nq, uint32_t* total_groups, uint32_t* total_ranked) {
+    if (!s || (nq && (!total_groups || !total_ranked))) return fail(INFX_EINVAL, "null argument%s");
+    if (nq != s->clpSlot.size()) return fail(INFX_EINVAL, "no batch of this size with a collapsing query on the stream%s");
+    for (uint32_t q = 0; q < nq; q++) { const int32_t k = s->clpSlot[q]; total_groups[q] = k < 0 ? 0 : s->clpGroups[k]; total_ranked[q] = k < 0 ? 0 : s->clpRanked[k]; }
+    return INFX_OK;
+}
+// The rows of query qi as the batch returned them: each row's group code and the size of its group in the ranked list; returns the rows written, -1 on error.
+// k_postfilter only drops rows and k_postproc only reorders them, and the documents of a consolidated list are distinct: a returned row is the row k_collapse
+// wrote with the same document.
+int32_t infx_collapse_rows(infx_stream* s, uint32_t qi, uint32_t* codes, uint32_t* sizes, int32_t cap) {
+    if (!s || qi >= s->clpSlot.size() || s->clpSlot[qi] < 0 || cap < 0 || (cap && (!codes || !sizes))) { fail(INFX_EINVAL, "no collapsing query of this index in the stream's last batch%s"); return -1; }
+    const size_t r = (size_t)s->clpSlot[qi] * s->clpStride, o = (size_t)qi * s->clpStride;
+    const uint32_t n = std::min(std::min(s->clpCounts[qi], s->clpStride), (uint32_t)cap);
+    if (!s->clpPosted) { for (uint32_t i = 0; i < n; i++) { codes[i] = s->clpCodes[r + i]; sizes[i] = s->clpSizes[r + i]; } return (int32_t)n; }
+    const uint32_t wrote = std::min(s->clpReturned[s->clpSlot[qi]], s->clpStride);
+    std::vector<std::pair<int32_t, uint32_t>> byDoc(wrote);      // (document, row k_collapse wrote)
+    for (uint32_t i = 0; i < wrote; i++) byDoc[i] = {s->clpDocs[r + i], i};
+    std::sort(byDoc.begin(), byDoc.end());
+    for (uint32_t i = 0; i < n; i++) {
+        const int32_t d = s->clpFinalDocs[o + i];
+        auto it = std::lower_bound(byDoc.begin(), byDoc.end(), std::make_pair(d, 0u));
+        if (it == byDoc.end() || it->first != d) { fail(INFX_EINVAL, "a returned row is not one the collapse step wrote%s"); return -1; }
+        codes[i] = s->clpCodes[r + it->second]; sizes[i] = s->clpSizes[r + it->second];
+    }
+    return (int32_t)n;
+}
+int32_t infx_last_collapse_stats(infx_stream* s, uint32_t* queries, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (queries) *queries = s->lastClpQueries; if (launches) *launches = s->lastClpLaunches;
+    return INFX_OK;
+}
+int32_t infx_last_collapse_timings(infx_stream* s, float* ms2) {
+    if (!s || !ms2) return fail(INFX_EINVAL, "null argument%s");
+    ms2[0] = ms2[1] = 0.f;
+    if (s->timedClp) { hipEventElapsedTime(&ms2[0], s->evF0, s->evK0); hipEventElapsedTime(&ms2[1], s->evK0, s->evK1); }
     return INFX_OK;
 }
 int32_t infx_last_browse_stats(infx_stream* s, uint32_t* groups, uint32_t* launches) {

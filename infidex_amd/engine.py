@@ -105,6 +105,11 @@ class Query:       # Api/Query.cs:9-45
     # ... and the facets of that set: Result.pre_filter_facets = the facets of every live document pre_filter accepts (SearchEngine.facets_of_documents),
     # what a drill-down sidebar shows beside the ranked rows.  Ignored without a pre_filter.
     pre_filter_facets: bool = False
+    # Not in the reference: at most collapse_keep rows per value of the field collapse_by ("one hit per product family", "three results per shop").  The rows
+    # kept are the first of each group in the query's whole ranked list (up to coverage_depth rows), in rank order; filter, facets, boosts and sort_by then work
+    # on the returned rows.  Result.group_values / group_sizes / total_groups / total_ranked describe the fold.  None = no collapsing.
+    collapse_by: Optional[str] = None
+    collapse_keep: int = 1                 # rows kept per group, 1 .. 16
 
     @property
     def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
@@ -135,6 +140,12 @@ class Result:      # Api/Result.cs
     # Query.pre_filter_facets: the facets of the documents Query.pre_filter accepts (None: not asked for, or refused).  Set by search_queries; a plain
     # attribute, not a dataclass field: the constructor's positional fields end with total_in_filter, total_in_pre_filter and error, which callers rely on.
     pre_filter_facets = None
+    # Query.collapse_by (None for a query without it, or refused): per returned row the text of its group (as GroupListing.group_values spells it) and the rows
+    # of the ranked list in that group, itself included ("+12 more from this shop"); the distinct groups of the ranked list; its length.  Plain attributes too.
+    group_values = None
+    group_sizes = None
+    total_groups = None
+    total_ranked = None
 
     # SearchEngine.cs:312-316: index and score of the last returned row, and the row count
     @property
@@ -932,7 +943,7 @@ class SearchEngine:
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
-        if q.coverage_setup is not None or q.pre_filter is not None:
+        if q.coverage_setup is not None or q.pre_filter is not None or q.collapse_by is not None:
             return self.search_queries([q])[0]
         if q.filter is not None or q.enable_facets or (q.enable_boost and q.boosts) or q.sort_by is not None:
             return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
@@ -942,6 +953,10 @@ class SearchEngine:
     def last_count_stats(self, session=None):
         """(expressions the session's last per-query batch counted for NumberOfDocumentsInFilter, kernel launches it took)."""
         return _u32_stats(self, "infx_engine_last_count_stats", session.h if session is not None else self._default_session(), 2)
+
+    def last_collapse_stats(self, session=None):
+        """(queries with Query.collapse_by that were folded, k_collapse launches) of the session's last search: (k, 1), or (0, 0) for a batch without one."""
+        return _u32_stats(self, "infx_engine_last_collapse_stats", session.h if session is not None else self._default_session(), 2)
 
     def last_prefilter_stats(self, session=None):
         """(masks built, masks taken from the session's cache, k_filter_mask_multi launches) of the session's last search (or prefilter_mask call)."""
@@ -1254,6 +1269,10 @@ class Session:
         """SearchEngine.set_quantile_digit_bits of this session."""
         self.engine._check(self.engine.L.infx_engine_set_quantile_digit_bits(self.h, int(bits)))
 
+    def last_collapse_stats(self):
+        """SearchEngine.last_collapse_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_collapse_stats", self.h, 2)
+
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_prefilter_stats", self.h, 3)
@@ -1289,6 +1308,9 @@ class Session:
                         "k_ex_scan_ms": float(parts[0]), "k_ex_chunk_ms": float(parts[1]), "k_ex_heap_ms": float(parts[2]), "k_exact1_ms": float(parts[3]),
                         "k_accumulate_ms": float(kern[0]), "k_select_ms": float(kern[1]), "k_stage2_ms": float(kern[2]),
                         "k_prep2_ms": float(kern[3]), "k_finalize_ms": float(kern[4])})
+            clp = np.zeros(2, np.float32)      # a batch with Query.collapse_by: k_finalize alone and k_collapse (k_finalize_ms spans both and the post-processing)
+            self.engine._check(self.L.infx_engine_last_collapse_timings(self.h, _p(clp, C.c_float)))
+            out.update({"k_finalize_rows_ms": float(clp[0]), "k_collapse_ms": float(clp[1])})
         return out
 
 
@@ -1413,7 +1435,47 @@ def _install_query_options(engine, sh, qs):
         status[:n] = np.where(status[:n] != 0, status[:n], pst)
     else:
         engine._check(engine.L.infx_engine_set_query_prefilters(sh, 0, None, None))
+    if any(q.collapse_by is not None for q in qs):         # Query.collapse_by: likewise
+        try:
+            kst = _install_collapse(engine, sh, qs)
+        except Exception:
+            _clear_query_options(engine, sh)
+            raise
+        status[:n] = np.where(status[:n] != 0, status[:n], kst)
+    else:
+        engine._check(engine.L.infx_engine_set_query_collapse(sh, 0, None, None, None))
     return status[:n]
+
+
+def _install_collapse(engine, sh, qs):
+    """infx_engine_set_query_collapse for the coming batch on session handle sh (Query.collapse_by None: not collapsed); returns each query's status."""
+    n = len(qs)
+    arr = (C.c_char_p * max(n, 1))(*[str(q.collapse_by).encode() if q.collapse_by is not None else None for q in qs])
+    keeps = np.asarray([min(max(int(q.collapse_keep), -1), 2 ** 31 - 1) for q in qs] or [1], np.int32)
+    st = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_set_query_collapse(sh, n, arr, _p(keeps, C.c_int32), _p(st, C.c_int32)))
+    return st[:n]
+
+
+def _attach_collapse(engine, sh, qs, results):
+    """Result.group_values / group_sizes / total_groups / total_ranked of the queries of a batch just searched on session handle sh that ran with collapse_by."""
+    n = len(qs)
+    if not any(q.collapse_by is not None and r.error is None for q, r in zip(qs, results)):
+        return
+    groups = np.zeros(max(n, 1), np.uint32); ranked = np.zeros(max(n, 1), np.uint32)
+    engine._check(engine.L.infx_engine_last_collapse(sh, n, _p(groups, C.c_uint32), _p(ranked, C.c_uint32)))
+    texts = _value_texts(engine)
+    for j, (q, r) in enumerate(zip(qs, results)):
+        if q.collapse_by is None or r.error is not None:
+            continue
+        m = len(r.records); col = C.c_int32(-1)
+        codes = np.zeros(max(m, 1), np.uint32); sizes = np.zeros(max(m, 1), np.uint32)
+        got = engine.L.infx_engine_collapse_rows(sh, j, C.byref(col), _p(codes, C.c_uint32), _p(sizes, C.c_uint32), m)
+        if got != m:
+            engine._check(1 if got < 0 else 0)
+            raise InfidexError(1, "collapse_by: %d rows described, %d returned" % (got, m))
+        r.group_values = texts(str(q.collapse_by), codes[:m]); r.group_sizes = [int(x) for x in sizes[:m]]
+        r.total_groups = int(groups[j]); r.total_ranked = int(ranked[j])
 
 
 def _clear_query_options(engine, sh):
@@ -1421,6 +1483,7 @@ def _clear_query_options(engine, sh):
     engine.L.infx_engine_set_query_options(sh, 0, None, None)
     engine.L.infx_engine_set_query_coverage(sh, 0, None, None)
     engine.L.infx_engine_set_query_prefilters(sh, 0, None, None)
+    engine.L.infx_engine_set_query_collapse(sh, 0, None, None, None)
 
 
 def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
@@ -1433,12 +1496,13 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
     for j, q in enumerate(qs):
         err = None
         # (a pre-filter on a browse query is refused when the batch runs: result flag bit 4 without an install status)
-        if status[j] != 0 or (q.pre_filter is not None and flags[j] & 16):
+        if status[j] != 0 or ((q.pre_filter is not None or q.collapse_by is not None) and flags[j] & 16):
             err = _query_error(engine, sh, j, int(status[j]) or 5)
         recs = [ScoreEntry(float(scores[j, k]), int(keys[j, k]), int(ties[j, k])) for k in range(int(counts[j]))]
         facets = engine.facets_of(sh, n, j) if q.enable_facets and err is None else None
         out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]),
                           total_in_pre_filter=int(inpre[j]) if inpre is not None else 0, error=err))
+    _attach_collapse(engine, sh, qs, out)
     return out
 
 
