@@ -310,7 +310,9 @@ int32_t infx_engine_set_query_options(infx_session* s, uint32_t nq, const infx_q
 int32_t infx_engine_last_in_filter(infx_session* s, uint32_t nq, uint32_t* out);
 /* how many expressions the session's last per-query batch counted, and in how many kernel launches */
 int32_t infx_engine_last_count_stats(infx_session* s, uint32_t* counted, uint32_t* launches);
-/* the message of query qi's rejection in the last infx_engine_set_query_options ("" if it was accepted); returns its length, -1 out of range */
+/* why query qi of the session's coming batch, or of the batch just searched, is rejected: the message of the first part that refuses it among the ones installed
+ * for that batch, in the order infx_engine_set_query_options, _set_query_coverage, _set_query_prefilters, _set_query_collapse, whichever was installed last ("" if
+ * none refuses it); rewritten by each of the four calls and by the search that consumes them.  Returns its length, -1 out of range */
 int32_t infx_engine_query_error(infx_session* s, uint32_t qi, char* out, int32_t cap);
 /* ---- CoverageSetup (Coverage/CoverageSetup.cs): the Stage-2 settings, engine-wide and per query ---------------------------------------------------
  * infx_coverage_setup carries the 17 settable members (CoverageDepth is never read by the reference: Query.CoverageDepth is used instead).

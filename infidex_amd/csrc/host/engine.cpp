@@ -64,33 +64,37 @@ struct Batch {
     std::shared_ptr<FusedIn> pre;      // sharded phases: per-query device-pipeline inputs prepared in phase 0 (off the collective path)
 };
 
+// What the four per-query parts of the session's next batch share ("One frame behind the per-query parts"): whether the part is installed and for
+// how many queries, and per query whether the part refuses it, with which status and why
+struct QueryPart {
+    bool on = false, bound = false; uint32_t nq = 0;      // bound: a sharded phase 0 took the part for its batch (a second phase 0 finds it stale)
+    std::vector<uint8_t> reject; std::vector<int32_t> status; std::vector<std::string> err;
+    void open(uint32_t n) { nq = n; reject.assign(n, 0); status.assign(n, INFX_OK); err.assign(n, std::string()); }
+    void refuse(uint32_t i, int32_t rc, const std::string& why) { reject[i] = 1; status[i] = rc; err[i] = why; }
+};
+// The parts in their fixed order: a query that several refuse reports the first one's message
+enum { QP_OPTIONS, QP_COVERAGE, QP_PREFILTERS, QP_COLLAPSE, QP_PARTS };
+static const char* const QUERY_PART_NAMES[QP_PARTS] = {"options", "coverage setups", "pre-filters", "collapse requests"};
 // Per-query options of the session's next batch (infx_engine_set_query_options): consumed by that batch, whichever search path runs it
-struct QueryOpts {
-    bool on = false, bound = false; uint32_t nq = 0;      // bound: a sharded phase 0 took them for its batch (a second phase 0 finds them stale)
-    std::vector<int32_t> maxResults; std::vector<uint8_t> cov, reject, facets; std::vector<int32_t> status; std::vector<std::string> err;      // facets: the query counts facets (a blank text then browses)
+struct QueryOpts : QueryPart {
+    std::vector<int32_t> maxResults; std::vector<uint8_t> cov, facets;      // facets: the query counts facets (a blank text then browses)
     std::vector<std::string> filterExpr;       // per query: its filter ("" = none), for NumberOfDocumentsInFilter after the batch
     std::vector<std::string> pinned;           // cache entries the batch holds (filters and boosts)
     std::vector<std::string> countExprs; std::vector<uint32_t> counts;      // expressions the batch counts first (programs [0, n) of its table) + the device's counts
 };
 // Per-query CoverageSetup of the session's next batch (infx_engine_set_query_coverage): consumed by that batch like QueryOpts, with or without them.
 // fin / qLimit / relativeq: the six members SearchPipeline reads, already resolved against the engine-wide setup for a query without one of its own.
-struct QueryCov {
-    bool on = false, bound = false; uint32_t nq = 0;
-    std::vector<infx_finalize_setup> fin; std::vector<int32_t> qLimit; std::vector<double> relativeq;
-    std::vector<uint8_t> reject; std::vector<int32_t> status; std::vector<std::string> err;
-};
+struct QueryCov : QueryPart { std::vector<infx_finalize_setup> fin; std::vector<int32_t> qLimit; std::vector<double> relativeq; };
 // Pre-filters of the session's next batch (infx_engine_set_query_prefilters): consumed by that batch like QueryCov, with or without QueryOpts.
-struct QueryPre {
-    bool on = false, bound = false; uint32_t nq = 0;
+struct QueryPre : QueryPart {
     std::vector<std::string> expr;             // per query: its pre-filter ("" = none, or refused)
-    std::vector<uint8_t> has, reject; std::vector<int32_t> status; std::vector<std::string> err;      // has: the query asked for one
+    std::vector<uint8_t> has;                  // the query asked for one
     std::vector<std::string> pinned;           // cache entries the batch holds
 };
 // Query.collapse_by of the session's next batch (infx_engine_set_query_collapse): consumed by that batch like QueryPre, with or without QueryOpts.
-struct QueryClp {
-    bool on = false, bound = false; uint32_t nq = 0;
+struct QueryClp : QueryPart {
     std::vector<int32_t> col, keep;            // per query: its column (-1: none, or refused) and the rows kept per group
-    std::vector<uint8_t> has, reject; std::vector<int32_t> status; std::vector<std::string> err;      // has: the query asked for it
+    std::vector<uint8_t> has;                  // the query asked for it
 };
 // One mask of the session's cache (mask slot i of its stream): the expression it was built from, the engine's mask epoch at that time, the live documents
 // it accepts, when it was last used (least recently used first out)
@@ -129,13 +133,12 @@ struct BucketAnswer : Answer { std::vector<uint32_t> sizes; std::vector<infx_sta
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskUse masks; };
 struct infx_session {
-    QueryCov qc;
-    QueryPre qp;
-    QueryClp qk; std::vector<int32_t> lastClpCol;      // lastClpCol: per query of the last batch the column it was collapsed by (-1: it was not)
+    QueryOpts qo; QueryCov qc; QueryPre qp; QueryClp qk;
+    QueryPart* const parts[QP_PARTS] = {&qo, &qc, &qp, &qk};      // (indexed by QP_*)
+    std::vector<int32_t> lastClpCol;      // per query of the last batch the column it was collapsed by (-1: it was not)
     PreMask preMask[INFX_MAX_PREFILTERS]; uint64_t preTick = 0; uint32_t preCountBuf[INFX_MAX_PREFILTERS] = {};      // preCountBuf: where a build's counts land
     std::vector<uint32_t> lastInPre; uint32_t preBuilt = 0, preReused = 0, preLaunches = 0;      // of the last batch (or infx_engine_prefilter_mask)
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
-    QueryOpts qo;
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
     bool swFilter = false, swBoost = false, swSort = false;      // session-wide options installed (infx_engine_set_filter / _set_boosts / _set_sort)
     std::vector<uint32_t> facAllCols; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> facAll;      // infx_engine_facets_all: columns and their ordered (code, count) lists
@@ -219,17 +222,12 @@ static inline bool qo_browse(const infx_session* S, size_t i) {
     return S->swFilter && !S->facetCols.empty();
 }
 static inline bool qo_cov(const infx_session* S, size_t i, bool cov) { return cov && (!S->qo.on || i >= S->qo.nq || S->qo.cov[i]); }
-static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results);
-static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
-static void clear_query_options(infx_session* S);
-static int32_t query_cov_check(infx_session* S, uint32_t nq);
-static int32_t query_pre_check(infx_session* S, uint32_t nq);
-static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
-static void clear_query_prefilters(infx_session* S);
-static int32_t query_clp_check(infx_session* S, uint32_t nq);
-static void query_clp_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static bool host_phases() { static const bool on = getenv("INFX_PHASED") != nullptr; return on; }      // the host-driven phases (the sharded code path) on one GPU
+static int32_t query_parts_check(infx_session* S, uint32_t nq, int32_t max_results);
+static int32_t query_parts_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
+static void query_parts_unbind(infx_session* S);
+static void query_parts_bind(infx_session* S);
 static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq);
-static void clear_query_collapse(infx_session* S);
 // The filter and mask part of one call over the documents that filters accept: a batch with pre-filters, infx_engine_prefilter_mask, _list_documents,
 // _range_facets, _field_stats.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
 // the session's mask cache, mask(i) is request i's; the device call that follows ends in failed(rc) or done().  (Defined with the mask cache, below.)
@@ -246,7 +244,6 @@ struct MaskCall {
     void done(uint32_t nq = 0);                          // it succeeded: the built masks' counts, the statistics (nq: the batch whose queries' counts to take)
 };
 static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, MaskCall& pre);
-static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok);
 static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
 static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len);
 static inline infx_finalize_setup qc_finalize(const infx_session* S, size_t i);
@@ -1342,14 +1339,11 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
                                  int32_t depth, int32_t enable_coverage, int64_t* out_keys, float* out_scores, uint8_t* out_ties,
                                  uint32_t* out_counts, uint32_t* out_flags) {
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, nq, max_results); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (!rc) rc = query_clp_check(S, nq); if (rc) return rc; }
+    { int32_t rc = query_parts_check(S, nq, max_results); if (rc) return rc; }
     e->searched.store(true, std::memory_order_relaxed);
     S->lastInPre.assign(nq, 0);
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
-    const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
-    query_cov_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
-    query_pre_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
-    query_clp_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
+    const int32_t rc2 = query_parts_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     return rc ? rc : rc2;
 }
 static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, const uint16_t* q_arena, const uint64_t* q_offs, int32_t max_results,
@@ -1357,8 +1351,7 @@ static int32_t search_batch_run(infx_engine* e, infx_session* S, uint32_t nq, co
                                 uint32_t* out_counts, uint32_t* out_flags) {
     if (!e->indexed) { for (uint32_t i = 0; i < nq; i++) out_counts[i] = 0; return INFX_OK; }   // Result.MakeEmptyResult(), SearchEngine.cs:261-262
     if (e->nranks > 1) return efail(INFX_EINVAL, "sharded engine: drive the phase API (infx_session_phase1..4) with the collectives in between");
-    static const bool phased = getenv("INFX_PHASED") != nullptr;     // host-driven phases (the sharded code path) on one GPU
-    if (!phased) return search_batch_fused(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
+    if (!host_phases()) return search_batch_fused(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     int32_t rc = ph_plan(e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     rc = ph_plan_finish(e, S, S->batch->pendingCounts.data()); if (rc) return rc;
     rc = ph_accumulate(e, S); if (rc) return rc;
@@ -1423,17 +1416,13 @@ int32_t infx_session_phase0(infx_session* S, uint32_t nq, const uint16_t* q_aren
     if (!S) return efail(INFX_EINVAL, "null session");
     // the exact cut across shards falls back to a chained sequential replay whose exchanged state is laid out for max_depth entries (infx_shard_replay_chain)
     if (S->e && S->e->nranks > 1 && depth != S->e->ix.cfg.maxDepth) return efail(INFX_EINVAL, "document shards search with CoverageDepth == the engine's max_depth");
-    if (S->qo.on && S->qo.bound) clear_query_options(S);        // left by a sharded batch that failed between its phase 0 and phase 4
-    if (S->qc.on && S->qc.bound) S->qc = QueryCov();
-    if (S->qp.on && S->qp.bound) clear_query_prefilters(S);
-    if (S->qk.on && S->qk.bound) clear_query_collapse(S);
-    { int32_t rc = query_options_check(S, nq, 0); if (!rc) rc = query_cov_check(S, nq); if (!rc) rc = query_pre_check(S, nq); if (!rc) rc = query_clp_check(S, nq); if (rc) return rc; }
-    S->qo.bound = S->qo.on; S->qc.bound = S->qc.on; S->qp.bound = S->qp.on; S->qk.bound = S->qk.on; S->lastInPre.assign(nq, 0);
+    query_parts_unbind(S);        // what a sharded batch left that failed between its phase 0 and phase 4
+    { int32_t rc = query_parts_check(S, nq, 0); if (rc) return rc; }
+    query_parts_bind(S); S->lastInPre.assign(nq, 0);
     PlanGateHold hold(S->e->gate);
     int32_t rc = ph_plan(S->e, S, nq, q_arena, q_offs, depth); if (rc) return rc;
     if (nunions) *nunions = (uint32_t)S->batch->pending.size();
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    if (!hostPhases && nq) {     // WordMatcher descriptors + PrepareQuery now: phase 0 is off the collective path (sharded.py search_stream)
+    if (!host_phases() && nq) {     // WordMatcher descriptors + PrepareQuery now: phase 0 is off the collective path (sharded.py search_stream)
         S->batch->pre = std::make_shared<FusedIn>();
         rc = build_fused_inputs(S->e, S, 1, 1, *S->batch->pre); if (rc) return rc;
     }
@@ -1669,8 +1658,7 @@ int32_t infx_session_counts(infx_session* S, uint32_t* counts) {   // nd x INFX_
 }
 int32_t infx_session_phase2(infx_session* S, const uint32_t* global_counts, infx_hit* hits, uint32_t* hitcounts) {
     if (!S || !global_counts) return efail(INFX_EINVAL, "null");
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;      // the original host-side candidate assembly / final ordering
-    if (hostPhases) {
+    if (host_phases()) {      // the original host-side candidate assembly / final ordering
         int32_t rc = ph_select(S->e, S, (const infx_counts*)global_counts); if (rc) return rc;
         if (hits) std::memcpy(hits, S->lastHits.data(), S->lastHits.size() * sizeof(infx_hit));
         if (hitcounts) std::memcpy(hitcounts, S->lastHitCount.data(), S->lastHitCount.size() * 4);
@@ -1900,9 +1888,8 @@ int32_t infx_session_coll_stats(infx_session* S, uint64_t* out4) {      // all-r
 }
 int32_t infx_session_phase3(infx_session* S, int32_t W, const infx_hit* all_hits, const uint32_t* all_counts, int32_t max_results, int32_t enable_coverage, uint64_t* ncand) {
     if (!S || W < 1 || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (!rc) rc = query_clp_check(S, S->batch->nq); if (rc) return rc; }
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    if (hostPhases) {
+    { int32_t rc = query_parts_check(S, S->batch->nq, max_results); if (rc) return rc; }
+    if (host_phases()) {
         int32_t rc = ph_stage2(S->e, S, W, all_hits, all_counts, max_results, enable_coverage); if (rc) return rc;
         if (ncand) *ncand = S->lastCands.size();
         return INFX_OK;
@@ -1945,7 +1932,7 @@ int32_t infx_session_phase2x(infx_session* S, const uint32_t* global_counts, voi
 }
 int32_t infx_session_phase3x(infx_session* S, int32_t W, const void* all_hits, const void* all_counts, int32_t max_results, int32_t enable_coverage, void* outs) {
     if (!S || W < 1 || max_results < 1 || !outs) return efail(INFX_EINVAL, "bad arguments");
-    { int32_t rc = query_options_check(S, S->batch->nq, max_results); if (!rc) rc = query_cov_check(S, S->batch->nq); if (!rc) rc = query_pre_check(S, S->batch->nq); if (!rc) rc = query_clp_check(S, S->batch->nq); if (rc) return rc; }
+    { int32_t rc = query_parts_check(S, S->batch->nq, max_results); if (rc) return rc; }
     infx_engine* e = S->e; Batch& B = *S->batch;
     B.maxResults = max_results;
     std::shared_ptr<FusedIn> FIp; int32_t rc = fused_inputs_for_phase3(e, S, max_results, enable_coverage, FIp); if (rc) return rc;
@@ -1970,24 +1957,17 @@ int32_t infx_session_outs(infx_session* S, int32_t* outs3) {   // ncand x 3 int3
 }
 int32_t infx_session_phase4(infx_session* S, const int32_t* merged_outs3, int64_t* out_keys, float* out_scores, uint8_t* out_ties, uint32_t* out_counts, uint32_t* out_flags) {
     if (!S || !merged_outs3 || !out_keys || !out_scores || !out_counts) return efail(INFX_EINVAL, "null");
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    if (hostPhases) {
+    if (host_phases()) {
         int32_t rc = ph_finalize(S->e, S, (const infx_cov_out*)merged_outs3, out_keys, out_scores, out_ties, out_counts, out_flags);
-        const int32_t rc2 = query_options_finish(S, out_counts, out_flags, rc == INFX_OK);
-        query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
-        query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
-        query_clp_finish(S, out_counts, out_flags, rc == INFX_OK);
+        const int32_t rc2 = query_parts_finish(S, out_counts, out_flags, rc == INFX_OK);
         return rc ? rc : rc2;
     }
     Batch& B = *S->batch;
     if (B.nq) {
         int32_t rc = infx_shard_finalize(S->stream, B.nq, (const infx_cov_out*)merged_outs3, B.depth, B.maxResults, out_keys, out_scores, out_ties, out_counts, out_flags);
-        if (rc) { g_eerr = infx_last_error(); query_options_finish(S, out_counts, out_flags, false); query_cov_finish(S, out_counts, out_flags, false); query_pre_finish(S, out_counts, out_flags, false); query_clp_finish(S, out_counts, out_flags, false); return rc; }
-        rc = query_options_finish(S, out_counts, out_flags, true);
-        query_cov_finish(S, out_counts, out_flags, rc == INFX_OK);
-        query_pre_finish(S, out_counts, out_flags, rc == INFX_OK);
-        query_clp_finish(S, out_counts, out_flags, rc == INFX_OK);
-        if (rc) return rc;
+        if (rc) g_eerr = infx_last_error();
+        const int32_t rc2 = query_parts_finish(S, out_counts, out_flags, rc == INFX_OK);
+        if (rc || rc2) return rc ? rc : rc2;
         float ms5[5] = {0, 0, 0, 0, 0}; infx_last_fused_timings(S->stream, ms5); S->msFin = ms5[4];
     }
     double t5 = now_ms();
@@ -2711,22 +2691,105 @@ int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascendi
 }
 
 // ---- per-query options (Search(Query) for a batch of Query objects, each with its own options) ---------------------------------------------------
-static void clear_query_options(infx_session* S) {
-    if (!S->qo.on) return;
-    { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, S->qo.pinned, -1); S->e->evict_filters(); }
-    if (S->stream) infx_stream_set_query_post(S->stream, 0, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr);
-    S->qo = QueryOpts();
+// ---- the frame of the four per-query parts ("One frame behind the per-query parts") ----
+// Part k is dropped: what it holds in the filter cache and on the stream is released
+static void query_part_clear(infx_session* S, int k) {
+    if (!S->parts[k]->on) return;
+    auto unpin = [&](const std::vector<std::string>& pinned) { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, pinned, -1); S->e->evict_filters(); };
+    switch (k) {
+    case QP_OPTIONS:
+        unpin(S->qo.pinned);
+        if (S->stream) infx_stream_set_query_post(S->stream, 0, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr);
+        S->qo = QueryOpts(); break;
+    case QP_COVERAGE: S->qc = QueryCov(); break;
+    case QP_PREFILTERS: unpin(S->qp.pinned); S->qp = QueryPre(); break;
+    case QP_COLLAPSE: S->qk = QueryClp(); break;
+    }
+}
+// The messages infx_engine_query_error reads, for a batch of nq queries: per query the first one among the parts installed for nq queries, in their fixed order
+static void query_parts_publish(infx_session* S, uint32_t nq) {
+    S->lastErr.assign(nq, std::string());
+    for (const QueryPart* P : S->parts) if (P->on && P->nq == nq)
+        for (uint32_t i = 0; i < nq; i++) if (S->lastErr[i].empty() && !P->err[i].empty()) S->lastErr[i] = P->err[i];
+}
+// The end of an installer: part k as the call leaves it (installed, or cleared: the messages keep their number) is published, its statuses are copied out
+static int32_t query_part_installed(infx_session* S, int k, int32_t* out_status) {
+    const QueryPart& P = *S->parts[k];
+    query_parts_publish(S, P.on ? P.nq : (uint32_t)S->lastErr.size());
+    if (P.on && out_status) std::copy(P.status.begin(), P.status.end(), out_status);
+    return INFX_OK;
+}
+// A batch of nq queries is about to run on the session: every installed part must be for nq queries (one that is not is cleared, it alone), and the options'
+// max_results must fit the call's row stride
+static int32_t query_parts_check(infx_session* S, uint32_t nq, int32_t max_results) {
+    for (int k = 0; k < QP_PARTS; k++) {
+        if (!S->parts[k]->on) continue;
+        if (S->parts[k]->nq != nq) { query_part_clear(S, k); return efail(INFX_EINVAL, std::string("the per-query ") + QUERY_PART_NAMES[k] + " were installed for a batch of another size"); }
+        if (k == QP_OPTIONS && max_results > 0) for (uint32_t i = 0; i < nq; i++) if (!S->qo.reject[i] && S->qo.maxResults[i] > max_results) {
+            query_part_clear(S, k); return efail(INFX_EINVAL, "a query's max_results exceeds the call's (the row stride)");
+        }
+    }
+    return INFX_OK;
+}
+static void query_parts_unbind(infx_session* S) { for (int k = 0; k < QP_PARTS; k++) if (S->parts[k]->bound) query_part_clear(S, k); }
+static void query_parts_bind(infx_session* S) { for (QueryPart* P : S->parts) P->bound = P->on; }
+// The batch is done (ok: it succeeded): the expressions the options counted enter the cache, a query that a part refuses comes back empty with result flag bit 4,
+// which queries were collapsed by which column, the messages of the batch; every part is consumed.  Returns the options' status.
+static int32_t query_parts_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
+    S->lastClpCol.clear();
+    if (!S->qo.on && !S->qc.on && !S->qp.on && !S->qk.on) return INFX_OK;
+    infx_engine* e = S->e;
+    int32_t rc = INFX_OK;
+    if (S->qo.on) {
+        QueryOpts& Q = S->qo;
+        S->lastInFilter.assign(Q.nq, 0); S->lastCounted = 0; S->lastCountLaunches = 0;
+        if (ok) {
+            // The counts come from the batch's own finalize: infx_stream_set_query_post resets the stream's count stats and only the finalize that consumes
+            // the options sets them.  (The host phases refuse every query with a filter, so such a batch counts nothing.)
+            uint32_t counted = 0, launches = 0;
+            infx_last_filter_count_stats(S->stream, &counted, &launches);
+            if (counted != Q.countExprs.size()) rc = efail(INFX_EINVAL, "the batch's NumberOfDocumentsInFilter counts did not come back with it");
+            if (!rc) {
+                S->lastCounted = counted; S->lastCountLaunches = launches;
+                std::lock_guard<std::mutex> lk(e->filterMu);
+                for (size_t k = 0; k < Q.countExprs.size(); k++) {
+                    auto it = e->filters.find(Q.countExprs[k]);
+                    if (it == e->filters.end()) continue;
+                    it->second.inAll = Q.counts[k]; it->second.countedAll = true;
+                    if (!engine_sharded(e)) { it->second.inFilter = Q.counts[k]; it->second.counted = true; }
+                }
+                for (uint32_t i = 0; i < Q.nq; i++) if (!Q.filterExpr[i].empty() && !Q.reject[i]) {
+                    auto it = e->filters.find(Q.filterExpr[i]);
+                    if (it != e->filters.end() && it->second.countedAll) S->lastInFilter[i] = it->second.inAll;
+                }
+            }
+        }
+    }
+    uint32_t nq = 0;
+    for (const QueryPart* P : S->parts) {
+        if (!P->on) continue;
+        if (!nq) nq = P->nq;
+        if (ok) for (uint32_t i = 0; i < P->nq; i++) if (P->reject[i]) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
+        if (P == &S->qo) ok = ok && rc == INFX_OK;      // a batch whose options fail counts as failed for the parts after them
+    }
+    if (S->qk.on) {      // (after the loop: a query any part refused was not collapsed)
+        const QueryClp& Q = S->qk;
+        S->lastClpCol.assign(Q.nq, -1);
+        for (uint32_t i = 0; i < Q.nq; i++) if (ok && Q.has[i] && !Q.reject[i] && !(out_flags && (out_flags[i] & INFX_RESULT_REJECTED))) S->lastClpCol[i] = Q.col[i];
+    }
+    query_parts_publish(S, nq);
+    for (int k = 0; k < QP_PARTS; k++) query_part_clear(S, k);
+    return rc;
 }
 int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_query_options* opts, int32_t* out_status) {
     if (!S || (nq && !opts)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    clear_query_options(S);
-    if (nq == 0) return INFX_OK;
+    query_part_clear(S, QP_OPTIONS);
+    if (nq == 0) return query_part_installed(S, QP_OPTIONS, nullptr);
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the per-query options run on the device");
     if (S->swFilter || S->swBoost || S->swSort) return efail(INFX_EINVAL, "a session-wide filter, facets, boosts or sort is installed on this session: per-query options would conflict");
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    QueryOpts Q; Q.nq = nq;
-    Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.reject.assign(nq, 0); Q.facets.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string()); Q.filterExpr.assign(nq, std::string());
+    QueryOpts Q; Q.open(nq);
+    Q.maxResults.assign(nq, 0); Q.cov.assign(nq, 0); Q.facets.assign(nq, 0); Q.filterExpr.assign(nq, std::string());
     std::vector<infx_query_post> post(nq); std::vector<infx_query_boost> boosts;
     std::vector<const CompiledFilter*> progs; std::unordered_map<std::string, int32_t> progIdx;
     std::vector<uint32_t> facetCols = facet_columns(e);
@@ -2739,9 +2802,8 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
     auto hold = [&](const char* x) { if (all.insert(x).second) { Q.pinned.push_back(x); pin_filters(e, {std::string(x)}, +1); } };      // pinned as compiled: a small cache bound cannot evict the batch's own
     for (uint32_t i = 0; i < nq; i++) {
         const infx_query_options& O = opts[i]; QUse& U = use[i];
-        auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
         Q.maxResults[i] = O.max_results; Q.cov[i] = O.enable_coverage ? 1 : 0;
-        if (O.max_results < 1) { reject(INFX_EINVAL, "MaxNumberOfRecordsToReturn must be at least 1"); continue; }
+        if (O.max_results < 1) { Q.refuse(i, INFX_EINVAL, "MaxNumberOfRecordsToReturn must be at least 1"); continue; }
         int32_t rc = INFX_OK;
         if (O.filter) { CompiledFilter* cf = nullptr; rc = compile_filter(e, O.filter, &cf, false); if (!rc) { U.filter = O.filter; hold(O.filter); } }
         if (!rc && O.enable_boost && O.nboosts) {
@@ -2756,12 +2818,12 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
             }
         }
         if (!rc && O.sort_by) { U.sort = true; rc = sort_column(e, O.sort_by, &U.sortCol); }
-        if (rc) { reject(rc, g_eerr); U = QUse(); continue; }
+        if (rc) { Q.refuse(i, rc, g_eerr); U = QUse(); continue; }
         const bool pp = O.filter || (O.enable_facets && !facetCols.empty()) || !U.boosts.empty() || U.sort;      // (facets without a facetable field: {} as the session path)
-        if (pp && hostPhases) { reject(INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run in the device finalize: the host phases (INFX_PHASED) do not post-process rows"); U = QUse(); continue; }
+        if (pp && host_phases()) { Q.refuse(i, INFX_EUNSUPPORTED, "filter / facets / boosts / sort-by run in the device finalize: the host phases (INFX_PHASED) do not post-process rows"); U = QUse(); continue; }
         if (pp && O.max_results > e->postRows) {
-            reject(INFX_EUNSUPPORTED, e->postRows == INFX_FILTER_MAX_ROWS ? std::string("filter / facets / boosts / sort-by run on at most INFX_FILTER_MAX_ROWS (64) returned rows per query")
-                                                                          : "filter / facets / boosts / sort-by run on at most " + std::to_string(e->postRows) + " returned rows per query (the engine's post rows)");
+            Q.refuse(i, INFX_EUNSUPPORTED, e->postRows == INFX_FILTER_MAX_ROWS ? std::string("filter / facets / boosts / sort-by run on at most INFX_FILTER_MAX_ROWS (64) returned rows per query")
+                                                                               : "filter / facets / boosts / sort-by run on at most " + std::to_string(e->postRows) + " returned rows per query (the engine's post rows)");
             U = QUse(); continue;
         }
         if (O.enable_facets && !facetCols.empty()) anyFacets = true;
@@ -2790,53 +2852,9 @@ int32_t infx_engine_set_query_options(infx_session* S, uint32_t nq, const infx_q
                                             (uint32_t)facetCols.size(), facetCols.data(), (uint32_t)toCount.size(), Q.counts.data());
     if (rc) { g_eerr = infx_last_error(); pin_filters(e, Q.pinned, -1); return rc; }
     S->facetCols = facetCols;
-    S->lastErr = Q.err;
-    if (S->qc.on && S->qc.nq == nq) for (uint32_t i = 0; i < nq; i++) if (S->qc.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = S->qc.err[i];
-    if (S->qp.on && S->qp.nq == nq) for (uint32_t i = 0; i < nq; i++) if (S->qp.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = S->qp.err[i];
     Q.on = true;
     S->qo = std::move(Q);
-    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = S->qo.status[i];
-    return INFX_OK;
-}
-// A batch is about to run on the session: the per-query options installed must be for nq queries whose max_results fit the call's row stride
-static int32_t query_options_check(infx_session* S, uint32_t nq, int32_t max_results) {
-    if (!S->qo.on) return INFX_OK;
-    if (nq != S->qo.nq) { clear_query_options(S); return efail(INFX_EINVAL, "the per-query options were installed for a batch of another size"); }
-    if (max_results > 0) for (uint32_t i = 0; i < nq; i++) if (!S->qo.reject[i] && S->qo.maxResults[i] > max_results) {
-        clear_query_options(S); return efail(INFX_EINVAL, "a query's max_results exceeds the call's (the row stride)");
-    }
-    return INFX_OK;
-}
-// The batch is done: rejected queries come back empty with result flag bit 4, the expressions it counted enter the cache, the options are cleared
-static int32_t query_options_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
-    if (!S->qo.on) return INFX_OK;
-    infx_engine* e = S->e; QueryOpts& Q = S->qo; const uint32_t nq = Q.nq;
-    int32_t rc = INFX_OK;
-    S->lastInFilter.assign(nq, 0); S->lastErr = Q.err; S->lastCounted = 0; S->lastCountLaunches = 0;
-    if (ok) {
-        // The counts come from the batch's own finalize: infx_stream_set_query_post resets the stream's count stats and only the finalize that consumes
-        // the options sets them.  (The host phases refuse every query with a filter, so such a batch counts nothing.)
-        uint32_t counted = 0, launches = 0;
-        infx_last_filter_count_stats(S->stream, &counted, &launches);
-        if (counted != Q.countExprs.size()) rc = efail(INFX_EINVAL, "the batch's NumberOfDocumentsInFilter counts did not come back with it");
-        if (!rc) {
-            S->lastCounted = counted; S->lastCountLaunches = launches;
-            std::lock_guard<std::mutex> lk(e->filterMu);
-            for (size_t k = 0; k < Q.countExprs.size(); k++) {
-                auto it = e->filters.find(Q.countExprs[k]);
-                if (it == e->filters.end()) continue;
-                it->second.inAll = Q.counts[k]; it->second.countedAll = true;
-                if (!engine_sharded(e)) { it->second.inFilter = Q.counts[k]; it->second.counted = true; }
-            }
-            for (uint32_t i = 0; i < nq; i++) if (!Q.filterExpr[i].empty() && !Q.reject[i]) {
-                auto it = e->filters.find(Q.filterExpr[i]);
-                if (it != e->filters.end() && it->second.countedAll) S->lastInFilter[i] = it->second.inAll;
-            }
-        }
-        for (uint32_t i = 0; i < nq; i++) if (Q.reject[i]) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
-    }
-    clear_query_options(S);
-    return rc;
+    return query_part_installed(S, QP_OPTIONS, out_status);
 }
 int32_t infx_engine_last_in_filter(infx_session* S, uint32_t nq, uint32_t* out) {
     if (!S || (nq && !out)) return efail(INFX_EINVAL, "null argument");
@@ -2908,41 +2926,21 @@ static inline int32_t qc_tolerance(const infx_session* S, size_t i, int len) {
 }
 int32_t infx_engine_set_query_coverage(infx_session* S, uint32_t nq, const infx_coverage_setup* const* setups, int32_t* out_status) {
     if (!S || (nq && !setups)) return efail(INFX_EINVAL, "null argument");
-    S->qc = QueryCov();
-    if (nq == 0) return INFX_OK;
-    QueryCov Q; Q.nq = nq;
+    query_part_clear(S, QP_COVERAGE);
+    if (nq == 0) return query_part_installed(S, QP_COVERAGE, nullptr);
+    QueryCov Q; Q.open(nq);
     Q.fin.assign(nq, finalize_of(S->e->cs)); Q.qLimit.assign(nq, S->e->ix.cfg.covQLimit); Q.relativeq.assign(nq, S->e->ix.cfg.covRelativeq);
-    Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
     for (uint32_t i = 0; i < nq; i++) {
         if (!setups[i]) continue;
         const infx_coverage_setup& c = *setups[i];
         int32_t st = INFX_OK;
-        if (const char* why = coverage_setup_problem(c, &st)) { Q.reject[i] = 1; Q.status[i] = st; Q.err[i] = why; continue; }
+        if (const char* why = coverage_setup_problem(c, &st)) { Q.refuse(i, st, why); continue; }
         // Only what SearchPipeline reads; the matcher members stay the engine's (quirk Q19)
         Q.fin[i] = finalize_of(c); Q.qLimit[i] = c.coverage_q_limit_for_error_tolerance; Q.relativeq[i] = c.coverage_lcs_error_tolerance_relativeq;
     }
-    if (S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
-    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i]) S->lastErr[i] = Q.err[i];
-    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
     Q.on = true;
     S->qc = std::move(Q);
-    return INFX_OK;
-}
-static int32_t query_cov_check(infx_session* S, uint32_t nq) {
-    if (!S->qc.on) return INFX_OK;
-    if (nq != S->qc.nq) { S->qc = QueryCov(); return efail(INFX_EINVAL, "the per-query coverage setups were installed for a batch of another size"); }
-    return INFX_OK;
-}
-// The batch is done: a query whose setup was refused comes back empty with result flag bit 4; the setups are consumed
-static void query_cov_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
-    if (!S->qc.on) return;
-    const QueryCov& Q = S->qc;
-    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
-    for (uint32_t i = 0; i < Q.nq; i++) if (Q.reject[i]) {
-        if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
-        if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
-    }
-    S->qc = QueryCov();
+    return query_part_installed(S, QP_COVERAGE, out_status);
 }
 // The stream's next Stage-2 call gets the engine-wide matcher settings, its next finalize the per-query truncation records (deviceFinalize: the batch is
 // finalized by k_finalize; the host phases apply the same values in ph_finalize).  Defaults everywhere: nothing is staged.
@@ -2970,102 +2968,62 @@ static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFin
 // A query with a pre-filter P returns what it would return if every document P does not accept carried Document.Deleted (include/infidex_hip.h, "pre-filter
 // masks").  The masks live per session, in the mask slots of its stream: at most INFX_MAX_PREFILTERS, keyed by the expression, least recently used first out,
 // valid for one mask epoch of the engine.
-static void clear_query_prefilters(infx_session* S) {
-    if (!S->qp.on) return;
-    { std::lock_guard<std::mutex> lk(S->e->filterMu); pin_filters(S->e, S->qp.pinned, -1); S->e->evict_filters(); }
-    S->qp = QueryPre();
-}
 int32_t infx_engine_set_query_prefilters(infx_session* S, uint32_t nq, const char* const* exprs, int32_t* out_status) {
     if (!S || (nq && !exprs)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    clear_query_prefilters(S);
-    if (nq == 0) return INFX_OK;
+    query_part_clear(S, QP_PREFILTERS);
+    if (nq == 0) return query_part_installed(S, QP_PREFILTERS, nullptr);
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the pre-filter masks are built on the device");
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    QueryPre Q; Q.nq = nq;
-    Q.expr.assign(nq, std::string()); Q.has.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
+    QueryPre Q; Q.open(nq);
+    Q.expr.assign(nq, std::string()); Q.has.assign(nq, 0);
     {
         std::lock_guard<std::mutex> lk(e->filterMu);
         std::unordered_set<std::string> distinct;
         for (uint32_t i = 0; i < nq; i++) {
             if (!exprs[i]) continue;
             Q.has[i] = 1;
-            auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
-            if (engine_sharded(e)) { reject(INFX_EUNSUPPORTED, "a pre-filter needs an engine that is not sharded: the masks cover one device's documents"); continue; }
-            if (hostPhases) { reject(INFX_EUNSUPPORTED, "a pre-filter runs in the device pipeline: the host phases (INFX_PHASED) do not read the masks"); continue; }
+            if (engine_sharded(e)) { Q.refuse(i, INFX_EUNSUPPORTED, "a pre-filter needs an engine that is not sharded: the masks cover one device's documents"); continue; }
+            if (host_phases()) { Q.refuse(i, INFX_EUNSUPPORTED, "a pre-filter runs in the device pipeline: the host phases (INFX_PHASED) do not read the masks"); continue; }
             CompiledFilter* cf = nullptr;
             const int32_t rc = compile_filter(e, exprs[i], &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
-            if (rc) { reject(rc, g_eerr); continue; }
+            if (rc) { Q.refuse(i, rc, g_eerr); continue; }
             if (!distinct.count(exprs[i])) {
-                if (distinct.size() >= INFX_MAX_PREFILTERS) { reject(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch; split the batch"); continue; }
+                if (distinct.size() >= INFX_MAX_PREFILTERS) { Q.refuse(i, INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch; split the batch"); continue; }
                 distinct.insert(exprs[i]); Q.pinned.push_back(exprs[i]); pin_filters(e, {std::string(exprs[i])}, +1);
             }
             Q.expr[i] = exprs[i];
         }
     }
-    // the messages of this batch: beside the ones its options and coverage setups left (installed before, for the same nq); a message of an EARLIER batch goes
-    const bool sameBatch = (S->qo.on && S->qo.nq == nq) || (S->qc.on && S->qc.nq == nq);
-    if (!sameBatch || S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
-    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
-    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
     Q.on = true;
     S->qp = std::move(Q);
-    return INFX_OK;
-}
-static int32_t query_pre_check(infx_session* S, uint32_t nq) {
-    if (!S->qp.on) return INFX_OK;
-    if (nq != S->qp.nq) { clear_query_prefilters(S); return efail(INFX_EINVAL, "the per-query pre-filters were installed for a batch of another size"); }
-    return INFX_OK;
-}
-// The batch is done: a query whose pre-filter was refused comes back empty with result flag bit 4; the pre-filters are consumed
-static void query_pre_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
-    if (!S->qp.on) return;
-    const QueryPre& Q = S->qp;
-    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
-    for (uint32_t i = 0; i < Q.nq; i++) if (Q.reject[i]) {
-        if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
-        if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
-    }
-    clear_query_prefilters(S);
+    return query_part_installed(S, QP_PREFILTERS, out_status);
 }
 // ---- Query.collapse_by: at most collapse_keep ranked rows per group ------------------------------------------------------------------------------------
 // (include/infidex_engine.h, "collapse_by"; the step itself is the device library's: include/infidex_hip.h, "collapsing")
-static void clear_query_collapse(infx_session* S) { S->qk = QueryClp(); }
 int32_t infx_engine_set_query_collapse(infx_session* S, uint32_t nq, const char* const* fields, const int32_t* keeps, int32_t* out_status) {
     if (!S || (nq && fields && !keeps)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    clear_query_collapse(S);
-    if (nq == 0 || !fields) return INFX_OK;
-    static const bool hostPhases = getenv("INFX_PHASED") != nullptr;
-    QueryClp Q; Q.nq = nq;
-    Q.col.assign(nq, -1); Q.keep.assign(nq, 1); Q.has.assign(nq, 0); Q.reject.assign(nq, 0); Q.status.assign(nq, INFX_OK); Q.err.assign(nq, std::string());
+    query_part_clear(S, QP_COLLAPSE);
+    if (nq == 0 || !fields) return query_part_installed(S, QP_COLLAPSE, nullptr);
+    QueryClp Q; Q.open(nq);
+    Q.col.assign(nq, -1); Q.keep.assign(nq, 1); Q.has.assign(nq, 0);
     {
         std::lock_guard<std::mutex> lk(e->filterMu);
         for (uint32_t i = 0; i < nq; i++) {
             if (!fields[i]) continue;
             Q.has[i] = 1;
-            auto reject = [&](int32_t rc, const std::string& why) { Q.reject[i] = 1; Q.status[i] = rc; Q.err[i] = why; };
             const int32_t col = column_named(e, fields[i]);
-            if (col < 0) { reject(INFX_EINVAL, std::string("collapse_by: no field named '") + fields[i] + "'"); continue; }
-            if (keeps[i] < 1 || keeps[i] > INFX_COLLAPSE_MAX_KEEP) { reject(INFX_EINVAL, "collapse_keep is 1 .. 16 rows per group"); continue; }
-            if (engine_sharded(e)) { reject(INFX_EUNSUPPORTED, "collapse_by needs an engine that is not sharded: the ranked list is folded on one device"); continue; }
-            if (hostPhases) { reject(INFX_EUNSUPPORTED, "collapse_by runs in the device pipeline: the host phases (INFX_PHASED) do not fold the ranked list"); continue; }
-            if (!e->dev || !S->stream) { reject(INFX_EHIP, "no GPU: the ranked list is folded on the device"); continue; }
+            if (col < 0) { Q.refuse(i, INFX_EINVAL, std::string("collapse_by: no field named '") + fields[i] + "'"); continue; }
+            if (keeps[i] < 1 || keeps[i] > INFX_COLLAPSE_MAX_KEEP) { Q.refuse(i, INFX_EINVAL, "collapse_keep is 1 .. 16 rows per group"); continue; }
+            if (engine_sharded(e)) { Q.refuse(i, INFX_EUNSUPPORTED, "collapse_by needs an engine that is not sharded: the ranked list is folded on one device"); continue; }
+            if (host_phases()) { Q.refuse(i, INFX_EUNSUPPORTED, "collapse_by runs in the device pipeline: the host phases (INFX_PHASED) do not fold the ranked list"); continue; }
+            if (!e->dev || !S->stream) { Q.refuse(i, INFX_EHIP, "no GPU: the ranked list is folded on the device"); continue; }
             Q.col[i] = col; Q.keep[i] = keeps[i];
         }
     }
-    const bool sameBatch = (S->qo.on && S->qo.nq == nq) || (S->qc.on && S->qc.nq == nq) || (S->qp.on && S->qp.nq == nq);
-    if (!sameBatch || S->lastErr.size() != nq) S->lastErr.assign(nq, std::string());
-    for (uint32_t i = 0; i < nq; i++) if (Q.reject[i] && S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
-    if (out_status) for (uint32_t i = 0; i < nq; i++) out_status[i] = Q.status[i];
     Q.on = true;
     S->qk = std::move(Q);
-    return INFX_OK;
-}
-static int32_t query_clp_check(infx_session* S, uint32_t nq) {
-    if (!S->qk.on) return INFX_OK;
-    if (nq != S->qk.nq) { clear_query_collapse(S); return efail(INFX_EINVAL, "the per-query collapse requests were installed for a batch of another size"); }
-    return INFX_OK;
+    return query_part_installed(S, QP_COLLAPSE, out_status);
 }
 // Before the batch's infx_search_fused: refuses collapse_by on a browse query, installs each query's request on the stream
 static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq) {
@@ -3075,7 +3033,7 @@ static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fus
     for (uint32_t i = 0; i < nq; i++) {
         if (!Q.has[i] || Q.reject[i]) continue;
         if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: nothing is ranked
-            Q.reject[i] = 1; Q.status[i] = INFX_EUNSUPPORTED; Q.err[i] = "collapse_by does not apply to a browse query (empty text with EnableFacets): nothing is ranked; list_groups lists one row per group";
+            Q.refuse(i, INFX_EUNSUPPORTED, "collapse_by does not apply to a browse query (empty text with EnableFacets): nothing is ranked; list_groups lists one row per group");
             fq[i].flags &= ~INFX_FQ_BROWSE;
             continue;
         }
@@ -3085,20 +3043,6 @@ static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fus
     const int32_t rc = infx_stream_set_query_collapse(S->stream, nq, reqs.data());
     if (rc) g_eerr = infx_last_error();
     return rc;
-}
-// The batch is done: a query whose request was refused comes back empty with result flag bit 4; which queries were collapsed, by which column; consumed
-static void query_clp_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
-    if (!S->qk.on) { S->lastClpCol.clear(); return; }
-    const QueryClp& Q = S->qk;
-    if (S->lastErr.size() != Q.nq) S->lastErr.assign(Q.nq, std::string());
-    S->lastClpCol.assign(Q.nq, -1);
-    for (uint32_t i = 0; i < Q.nq; i++) {
-        if (Q.reject[i]) {
-            if (S->lastErr[i].empty()) S->lastErr[i] = Q.err[i];
-            if (ok) { if (out_counts) out_counts[i] = 0; if (out_flags) out_flags[i] |= INFX_RESULT_REJECTED; }
-        } else if (ok && Q.has[i] && !(out_flags && (out_flags[i] & INFX_RESULT_REJECTED))) S->lastClpCol[i] = Q.col[i];
-    }
-    clear_query_collapse(S);
 }
 int32_t infx_engine_last_collapse(infx_session* S, uint32_t nq, uint32_t* total_groups, uint32_t* total_ranked) {
     if (!S || (nq && (!total_groups || !total_ranked))) return efail(INFX_EINVAL, "null argument");
@@ -3197,7 +3141,7 @@ static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_f
     for (uint32_t i = 0; i < n; i++) {
         if (!Q.has[i] || Q.reject[i]) continue;
         if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: Filter already restricts the scan
-            Q.reject[i] = 1; Q.status[i] = INFX_EUNSUPPORTED; Q.err[i] = "a pre-filter does not apply to a browse query (empty text with EnableFacets): its Filter already restricts the scan";
+            Q.refuse(i, INFX_EUNSUPPORTED, "a pre-filter does not apply to a browse query (empty text with EnableFacets): its Filter already restricts the scan");
             fq[i].flags &= ~INFX_FQ_BROWSE;
             continue;
         }

@@ -1414,37 +1414,33 @@ def _install_query_options(engine, sh, qs):
         o.sort_by = q.sort_by.encode() if q.sort_by is not None else None; o.sort_ascending = int(bool(q.sort_ascending))
     status = np.zeros(max(n, 1), np.int32)
     engine._check(engine.L.infx_engine_set_query_options(sh, n, arr, _p(status, C.c_int32)))
-    if any(q.coverage_setup is not None for q in qs):      # Query.CoverageSetup: installed beside the options, consumed by the same batch
-        sts = [_coverage_struct(q.coverage_setup) if q.coverage_setup is not None else None for q in qs]
-        ptrs = (C.POINTER(_CoverageSetup) * max(n, 1))(*[C.pointer(st) if st is not None else None for st in sts])
-        cst = np.zeros(max(n, 1), np.int32)
+    status = status[:n]
+    # the other parts, installed beside the options and consumed by the same batch, in the library's fixed order: (what a query asks of it, install it, clear it)
+    L = engine.L
+    parts = ((lambda q: q.coverage_setup, lambda: _install_coverage(engine, sh, qs), lambda: L.infx_engine_set_query_coverage(sh, 0, None, None)),
+             (lambda q: q.pre_filter, lambda: _install_prefilters(engine, sh, [q.pre_filter for q in qs]), lambda: L.infx_engine_set_query_prefilters(sh, 0, None, None)),
+             (lambda q: q.collapse_by, lambda: _install_collapse(engine, sh, qs), lambda: L.infx_engine_set_query_collapse(sh, 0, None, None, None)))
+    for asked, install, clear in parts:
+        if not any(asked(q) is not None for q in qs):
+            engine._check(clear())
+            continue
         try:
-            engine._check(engine.L.infx_engine_set_query_coverage(sh, n, ptrs, _p(cst, C.c_int32)))
-        except Exception:
-            engine.L.infx_engine_set_query_options(sh, 0, None, None)
-            raise
-        status = np.where(status != 0, status, cst)
-    else:
-        engine._check(engine.L.infx_engine_set_query_coverage(sh, 0, None, None))
-    if any(q.pre_filter is not None for q in qs):          # Query.pre_filter: likewise
-        try:
-            pst = _install_prefilters(engine, sh, [q.pre_filter for q in qs])
+            st = install()
         except Exception:
             _clear_query_options(engine, sh)
             raise
-        status[:n] = np.where(status[:n] != 0, status[:n], pst)
-    else:
-        engine._check(engine.L.infx_engine_set_query_prefilters(sh, 0, None, None))
-    if any(q.collapse_by is not None for q in qs):         # Query.collapse_by: likewise
-        try:
-            kst = _install_collapse(engine, sh, qs)
-        except Exception:
-            _clear_query_options(engine, sh)
-            raise
-        status[:n] = np.where(status[:n] != 0, status[:n], kst)
-    else:
-        engine._check(engine.L.infx_engine_set_query_collapse(sh, 0, None, None, None))
-    return status[:n]
+        status = np.where(status != 0, status, st)
+    return status
+
+
+def _install_coverage(engine, sh, qs):
+    """infx_engine_set_query_coverage for the coming batch on session handle sh (Query.CoverageSetup None: the engine's); returns each query's status."""
+    n = len(qs)
+    sts = [_coverage_struct(q.coverage_setup) if q.coverage_setup is not None else None for q in qs]
+    ptrs = (C.POINTER(_CoverageSetup) * max(n, 1))(*[C.pointer(st) if st is not None else None for st in sts])
+    cst = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_set_query_coverage(sh, n, ptrs, _p(cst, C.c_int32)))
+    return cst[:n]
 
 
 def _install_collapse(engine, sh, qs):
