@@ -399,6 +399,39 @@ int32_t infx_engine_collapse_rows(infx_session* s, uint32_t qi, int32_t* col, ui
 int32_t infx_engine_last_collapse_stats(infx_session* s, uint32_t* queries, uint32_t* launches);
 /* ms2[0] k_finalize's and ms2[1] k_collapse's duration in the session's last search (HIP events on its stream; zeros when nothing was collapsed) */
 int32_t infx_engine_last_collapse_timings(infx_session* s, float* ms2);
+/* ---- Query.highlight: match spans and a snippet for every returned row (not in the reference; DESIGN.md "highlight") ---------------------------------
+ * What Elasticsearch calls highlight and Algolia _highlightResult: per returned row, which document word each query word matched and how, every occurrence
+ * of those words (the spans a UI paints) and a snippet of the stored text around them.  The match is Stage 2's: its four matchers (whole word, joined words,
+ * prefix / suffix / infix / tail, fuzzy prefix and fuzzy) over the stored text lower(normalize(IndexedText)) — infx_engine_document_text —, with the engine's
+ * CoverageSetup, alias folding and dedupe; a pure function of the query's Stage-2 words, that text and those settings, whatever the row's score came from
+ * (Stage-1 fallback rows and queries without coverage are highlighted too).  Offsets and lengths are UTF-16 units of the stored text, not of the input.
+ * infx_engine_set_query_highlight installs chars[i] (0: query i does not ask; else its snippet width, INFX_HIGHLIGHT_MIN_CHARS .. INFX_HIGHLIGHT_MAX_CHARS) for
+ * the session's NEXT search of nq queries: the fifth part of the per-query frame, behind the collapse requests — consumed by that search, usable with or without
+ * infx_engine_set_query_options, nq = 0 (or chars == NULL) clears, a search of another nq fails with INFX_EINVAL and clears it.  A query is rejected on its own
+ * (empty result, result flag bit 4, its status in out_status[i], its message from infx_engine_query_error, neighbours unaffected) for a width out of range
+ * (INFX_EINVAL), an empty text with EnableFacets (a browse query matched nothing; known when the batch runs), the host phases (INFX_PHASED) and a sharded
+ * engine (INFX_EUNSUPPORTED each), an engine without a GPU (INFX_EHIP).  A batch without a highlighting query launches and downloads what it did before.
+ * Limits of this version, stated per row and never silent: a document of more than INFX_MAX_DOC_TOKENS (192) Stage-2 words has status 1 ("too_long"), a query
+ * outside the fast envelope (more than INFX_MAX_QUERY_TOKENS words or INFX_MAX_QUERY_CHARS characters) status 2 ("long_query") on every row.
+ *   infx_engine_highlight_query        of highlighted query qi of the session's last search: its rows, the batch's term and snippet strides, whether it is a
+ *                                      long query, and its Stage-2 words in Stage 2's order as slices (word_off, word_len; at most INFX_MAX_QUERY_TOKENS) of
+ *                                      `text` (at most INFX_MAX_QUERY_CHARS units); any output may be NULL
+ *   infx_engine_highlight_rows         query qi's rows as returned (after Filter, SortBy and collapsing), each row hl_row_u16(term stride, snippet stride)
+ *                                      uint16 in the layout of csrc/highlight.h; returns the rows written (at most cap_u16 / row size), -1 on error
+ *   infx_engine_last_highlight_stats   highlighting queries and k_highlight launches of the session's last search: (k, 1), or (0, 0) without
+ *   infx_engine_last_highlight_timings k_highlight's duration in that search (HIP events on its stream) and the bytes of rows it downloaded
+ *   infx_engine_document_text          the stored text of document `document_index` (internal index): returns its length in UTF-16 units and copies at most
+ *                                      cap of them, -1 on error */
+#define INFX_HIGHLIGHT_MIN_CHARS 16
+#define INFX_HIGHLIGHT_MAX_CHARS 512
+#define INFX_HIGHLIGHT_MAX_SPANS 64
+int32_t infx_engine_set_query_highlight(infx_session* s, uint32_t nq, const int32_t* chars /* 0: none */, int32_t* out_status /* nq, may be NULL */);
+int32_t infx_engine_highlight_query(infx_session* s, uint32_t qi, int32_t* rows, int32_t* term_stride, int32_t* snippet_stride, int32_t* long_query,
+                                    uint16_t* text, int32_t* text_len, uint16_t* word_off, uint16_t* word_len, int32_t* words);
+int32_t infx_engine_highlight_rows(infx_session* s, uint32_t qi, uint16_t* out, int64_t cap_u16); /* rows written, -1 on error */
+int32_t infx_engine_last_highlight_stats(infx_session* s, uint32_t* queries, uint32_t* launches);
+int32_t infx_engine_last_highlight_timings(infx_session* s, float* ms, uint64_t* bytes);
+int64_t infx_engine_document_text(infx_engine* e, int64_t document_index, uint16_t* out, int64_t cap);
 /* ---- facets of the documents a filter accepts (not in the reference: the facet side of Query.pre_filter) --------------------------------------------------
  * The facets of an Infiscript expression P: the value counts of every facetable column (the first INFX_MAX_FACET_COLS) over the documents that are not Deleted
  * and whose OWN fields P accepts — per document, as NumberOfDocumentsInFilter counts and as the pre-filter masks are built, not through the key's first live

@@ -408,6 +408,29 @@ int32_t infx_collapse_rows(infx_stream* s, uint32_t qi, uint32_t* codes, uint32_
 int32_t infx_last_collapse_stats(infx_stream* s, uint32_t* queries, uint32_t* launches);
 int32_t infx_last_collapse_timings(infx_stream* s, float* ms2);
 
+/* ---- highlighting: where each returned document matched, the spans to paint, a snippet (not in the reference; DESIGN.md "highlight") -----------------
+ * infx_stream_set_query_highlight installs one width per query of the stream's NEXT finalize of nq queries (infx_search_fused): 0 = the query does not ask,
+ * else its snippet width in UTF-16 units, INFX_HIGHLIGHT_MIN_CHARS .. INFX_HIGHLIGHT_MAX_CHARS.  Installed BEFORE the batch (its Stage-2 call notes the matcher
+ * settings, the alias flag and the queries' word counts for it), consumed by the batch, whatever its outcome; nq = 0 clears; a batch of another size fails
+ * with INFX_EINVAL.  After k_postproc, ONE k_highlight launch — a lane per (query, row) slot of the result table, idle where the row is past the query's count
+ * or the query did not ask — re-runs Stage 2's four matchers over the stored text of each returned row's document with the batch's infx_cov_query table,
+ * infx_stage2_setup and alias flag, and writes per row: its status (0 ok, 1 the document has more than INFX_MAX_DOC_TOKENS words, 2 the query is outside the
+ * fast envelope), per query word what matched it, the spans, and the snippet (row layout, span walk and window rule: csrc/highlight.h).  The rows are strided by
+ * what the batch asked — its largest word count, its largest width — and come back with the batch's outputs.  A batch without a request launches and downloads
+ * exactly what it did before.
+ *   infx_highlight_layout        rows of query qi, the batch's term stride and snippet stride
+ *   infx_highlight_rows          query qi's rows as returned, hl_row_u16(term stride, snippet stride) uint16 each; returns the rows written, -1 on error
+ *   infx_last_highlight_stats    asking queries and k_highlight launches of the stream's last finalize: (k, 1), or (0, 0)
+ *   infx_last_highlight_timings  k_highlight's duration in that finalize (HIP events; 0 when nothing was highlighted) and the bytes of rows downloaded */
+#define INFX_HIGHLIGHT_MIN_CHARS 16
+#define INFX_HIGHLIGHT_MAX_CHARS 512
+#define INFX_HIGHLIGHT_MAX_SPANS 64
+int32_t infx_stream_set_query_highlight(infx_stream* s, uint32_t nq, const int32_t* chars);
+int32_t infx_highlight_layout(infx_stream* s, uint32_t qi, int32_t* rows, int32_t* term_stride, int32_t* snippet_stride);
+int32_t infx_highlight_rows(infx_stream* s, uint32_t qi, uint16_t* out, int64_t cap_u16);
+int32_t infx_last_highlight_stats(infx_stream* s, uint32_t* queries, uint32_t* launches);
+int32_t infx_last_highlight_timings(infx_stream* s, float* ms, uint64_t* bytes);
+
 /* ---- browse rows: a query with no text and EnableFacets (SearchEngine.HandleEmptyQueryWithFacets, SearchEngine.cs:321-346) -------------------------
  * A fused query flagged INFX_FQ_SKIP | INFX_FQ_BROWSE returns the first max_results (<= the index's post rows, else INFX_EUNSUPPORTED) documents in
  * internal order that are not Deleted and that its filter accepts — the filter of its infx_query_post descriptor (which must carry INFX_QP_FACETS) or

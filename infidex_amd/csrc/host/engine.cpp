@@ -73,8 +73,8 @@ struct QueryPart {
     void refuse(uint32_t i, int32_t rc, const std::string& why) { reject[i] = 1; status[i] = rc; err[i] = why; }
 };
 // The parts in their fixed order: a query that several refuse reports the first one's message
-enum { QP_OPTIONS, QP_COVERAGE, QP_PREFILTERS, QP_COLLAPSE, QP_PARTS };
-static const char* const QUERY_PART_NAMES[QP_PARTS] = {"options", "coverage setups", "pre-filters", "collapse requests"};
+enum { QP_OPTIONS, QP_COVERAGE, QP_PREFILTERS, QP_COLLAPSE, QP_HIGHLIGHT, QP_PARTS };
+static const char* const QUERY_PART_NAMES[QP_PARTS] = {"options", "coverage setups", "pre-filters", "collapse requests", "highlight requests"};
 // Per-query options of the session's next batch (infx_engine_set_query_options): consumed by that batch, whichever search path runs it
 struct QueryOpts : QueryPart {
     std::vector<int32_t> maxResults; std::vector<uint8_t> cov, facets;      // facets: the query counts facets (a blank text then browses)
@@ -96,6 +96,14 @@ struct QueryClp : QueryPart {
     std::vector<int32_t> col, keep;            // per query: its column (-1: none, or refused) and the rows kept per group
     std::vector<uint8_t> has;                  // the query asked for it
 };
+// Query.highlight of the session's next batch (infx_engine_set_query_highlight): consumed by that batch like QueryClp, with or without QueryOpts.
+struct QueryHl : QueryPart {
+    std::vector<int32_t> chars;                // per query: its snippet width (0: none, or refused)
+    std::vector<uint8_t> has;                  // the query asked for it
+    bool asks(uint32_t i) const { return on && i < nq && has[i] && !reject[i]; }
+};
+// A highlighted query of the session's last batch: its Stage-2 words (the text they are slices of, their offsets and lengths, in Stage 2's order)
+struct HlQuery { std::vector<uint16_t> text, off, len; bool longQuery = false; };
 // One mask of the session's cache (mask slot i of its stream): the expression it was built from, the engine's mask epoch at that time, the live documents
 // it accepts, when it was last used (least recently used first out)
 struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t count = 0; bool valid = false; };
@@ -133,9 +141,10 @@ struct BucketAnswer : Answer { std::vector<uint32_t> sizes; std::vector<infx_sta
 struct MaskUse { uint32_t built = 0, reused = 0; };      // masks a call built / found in the session's cache
 template <class A> struct LastCall { typedef A answer; std::vector<A> ans; MaskUse masks; };
 struct infx_session {
-    QueryOpts qo; QueryCov qc; QueryPre qp; QueryClp qk;
-    QueryPart* const parts[QP_PARTS] = {&qo, &qc, &qp, &qk};      // (indexed by QP_*)
+    QueryOpts qo; QueryCov qc; QueryPre qp; QueryClp qk; QueryHl qh;
+    QueryPart* const parts[QP_PARTS] = {&qo, &qc, &qp, &qk, &qh};      // (indexed by QP_*)
     std::vector<int32_t> lastClpCol;      // per query of the last batch the column it was collapsed by (-1: it was not)
+    std::vector<int32_t> lastHlChars; std::vector<HlQuery> lastHlQuery;      // per query of the last batch the width it was highlighted with (0: it was not) and its words
     PreMask preMask[INFX_MAX_PREFILTERS]; uint64_t preTick = 0; uint32_t preCountBuf[INFX_MAX_PREFILTERS] = {};      // preCountBuf: where a build's counts land
     std::vector<uint32_t> lastInPre; uint32_t preBuilt = 0, preReused = 0, preLaunches = 0;      // of the last batch (or infx_engine_prefilter_mask)
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
@@ -228,6 +237,7 @@ static int32_t query_parts_finish(infx_session* S, uint32_t* out_counts, uint32_
 static void query_parts_unbind(infx_session* S);
 static void query_parts_bind(infx_session* S);
 static int32_t stage_collapse(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq);
+static int32_t stage_highlight(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, const FusedIn& FI);
 // The filter and mask part of one call over the documents that filters accept: a batch with pre-filters, infx_engine_prefilter_mask, _list_documents,
 // _range_facets, _field_stats.  Request i's filter is interned (one cache lookup and one mask per distinct expression), acquire() finds or stages the masks of the call in
 // the session's mask cache, mask(i) is request i's; the device call that follows ends in failed(rc) or done().  (Defined with the mask cache, below.)
@@ -1194,7 +1204,15 @@ static int32_t build_fused_inputs(infx_engine* e, infx_session* S, int32_t max_r
             bool isShort = !st.empty() && st.size() <= 3;
             if (isShort) for (u16 ch : st) if (is_delim(ch)) { isShort = false; break; }
             if (isShort) { F.flags |= INFX_FQ_SHORT; int64_t pk = ix.prefixKeys.find(st); int shortCount = pk >= 0 ? (int)ix.prefixPop[pk] : 0; if (shortCount > 500) F.flags |= INFX_FQ_SHORTSKIP; }
-            if (!qo_cov(S, i, covEnabled) || (F.flags & INFX_FQ_SHORTSKIP)) continue;
+            if (!qo_cov(S, i, covEnabled) || (F.flags & INFX_FQ_SHORTSKIP)) {
+                // Query.highlight without coverage: k_highlight still reads the query's Stage-2 words from cq[i] (Stage 2 itself ignores the record: no
+                // INFX_FQ_COV).  A query beyond the fast envelope is marked (reserved = -1, no record in the long-query table): its rows report "long_query".
+                if (S->qh.asks((uint32_t)i)) {
+                    std::unique_ptr<infx_cov_query_long> lq;
+                    if (prepare_cov_any(ix, st, cq[i], lq) || lq) { std::memset(&cq[i], 0, sizeof cq[i]); cq[i].reserved = -1; }
+                }
+                continue;
+            }
             F.flags |= INFX_FQ_COV;
             const infx_session::PlanPre* pp = S->planPre.size() == nq ? S->planPre[i].get() : nullptr;      // (ph_plan dropped the entries that were not made for this batch)
             if (pp && pp->hasCov) {
@@ -1282,10 +1300,11 @@ static int32_t search_batch_fused(infx_engine* e, infx_session* S, uint32_t nq, 
     MaskCall pre(S, nq);
     rc = stage_prefilters(S, nq, fq, pre); if (rc) return rc;
     rc = stage_collapse(S, nq, fq); if (rc) return pre.failed(rc);
+    rc = stage_highlight(S, nq, fq, FI); if (rc) { if (S->qk.on) infx_stream_set_query_collapse(S->stream, 0, nullptr); return pre.failed(rc); }
     rc = infx_search_fused(S->stream, B.nd, B.dq.data(), (uint32_t)B.dterms.size(), B.dterms.data(), nq, fq.data(), cq.data(),
                            (uint32_t)lists.size(), lists.data(), (uint32_t)owned.size(), owned.data(), depth, max_results, dbg ? 1 : 0,
                            out_keys, out_scores, out_ties, out_counts, out_flags);
-    if (rc) { if (S->qk.on) infx_stream_set_query_collapse(S->stream, 0, nullptr); return pre.failed(rc); }
+    if (rc) { if (S->qk.on) infx_stream_set_query_collapse(S->stream, 0, nullptr); if (S->qh.on) infx_stream_set_query_highlight(S->stream, 0, nullptr); return pre.failed(rc); }
     pre.done(nq);
     B.t3 = now_ms();
     // Kernel durations are resolved when somebody asks (infx_engine_session_last_timings): every hipEventElapsedTime is a HIP API call that queues behind the
@@ -1341,7 +1360,7 @@ static int32_t search_batch_impl(infx_engine* e, infx_session* S, uint32_t nq, c
     if (!e || !S || (nq && (!q_arena || !q_offs || !out_keys || !out_scores || !out_counts)) || max_results < 1) return efail(INFX_EINVAL, "bad arguments");
     { int32_t rc = query_parts_check(S, nq, max_results); if (rc) return rc; }
     e->searched.store(true, std::memory_order_relaxed);
-    S->lastInPre.assign(nq, 0);
+    S->lastInPre.assign(nq, 0); S->lastHlChars.clear(); S->lastHlQuery.clear();
     int32_t rc = search_batch_run(e, S, nq, q_arena, q_offs, max_results, depth, enable_coverage, out_keys, out_scores, out_ties, out_counts, out_flags);
     const int32_t rc2 = query_parts_finish(S, out_counts, out_flags, rc == INFX_OK && e->indexed);
     return rc ? rc : rc2;
@@ -2704,6 +2723,7 @@ static void query_part_clear(infx_session* S, int k) {
     case QP_COVERAGE: S->qc = QueryCov(); break;
     case QP_PREFILTERS: unpin(S->qp.pinned); S->qp = QueryPre(); break;
     case QP_COLLAPSE: S->qk = QueryClp(); break;
+    case QP_HIGHLIGHT: S->qh = QueryHl(); break;
     }
 }
 // The messages infx_engine_query_error reads, for a batch of nq queries: per query the first one among the parts installed for nq queries, in their fixed order
@@ -2737,7 +2757,8 @@ static void query_parts_bind(infx_session* S) { for (QueryPart* P : S->parts) P-
 // which queries were collapsed by which column, the messages of the batch; every part is consumed.  Returns the options' status.
 static int32_t query_parts_finish(infx_session* S, uint32_t* out_counts, uint32_t* out_flags, bool ok) {
     S->lastClpCol.clear();
-    if (!S->qo.on && !S->qc.on && !S->qp.on && !S->qk.on) return INFX_OK;
+    if (!S->qh.on) { S->lastHlChars.clear(); S->lastHlQuery.clear(); }
+    if (!S->qo.on && !S->qc.on && !S->qp.on && !S->qk.on && !S->qh.on) return INFX_OK;
     infx_engine* e = S->e;
     int32_t rc = INFX_OK;
     if (S->qo.on) {
@@ -2776,6 +2797,11 @@ static int32_t query_parts_finish(infx_session* S, uint32_t* out_counts, uint32_
         const QueryClp& Q = S->qk;
         S->lastClpCol.assign(Q.nq, -1);
         for (uint32_t i = 0; i < Q.nq; i++) if (ok && Q.has[i] && !Q.reject[i] && !(out_flags && (out_flags[i] & INFX_RESULT_REJECTED))) S->lastClpCol[i] = Q.col[i];
+    }
+    if (S->qh.on) {      // (likewise: lastHlChars holds what stage_highlight installed; a query any part refused, or a failed batch, has no highlights)
+        const QueryHl& Q = S->qh;
+        S->lastHlChars.resize(Q.nq, 0); S->lastHlQuery.resize(Q.nq);
+        for (uint32_t i = 0; i < Q.nq; i++) if (!ok || !Q.asks(i) || (out_flags && (out_flags[i] & INFX_RESULT_REJECTED))) S->lastHlChars[i] = 0;
     }
     query_parts_publish(S, nq);
     for (int k = 0; k < QP_PARTS; k++) query_part_clear(S, k);
@@ -3073,6 +3099,104 @@ int32_t infx_engine_last_collapse_timings(infx_session* S, float* ms2) {
     const int32_t rc = infx_last_collapse_timings(S->stream, ms2);
     if (rc) g_eerr = infx_last_error();
     return rc;
+}
+// ---- Query.highlight: match spans and a snippet for every returned row ---------------------------------------------------------------------------------
+// (include/infidex_engine.h, "highlight"; the step itself is the device library's: include/infidex_hip.h, "highlighting")
+int32_t infx_engine_set_query_highlight(infx_session* S, uint32_t nq, const int32_t* chars, int32_t* out_status) {
+    if (!S) return efail(INFX_EINVAL, "null argument");
+    infx_engine* e = S->e;
+    query_part_clear(S, QP_HIGHLIGHT);
+    if (nq == 0 || !chars) return query_part_installed(S, QP_HIGHLIGHT, nullptr);
+    QueryHl Q; Q.open(nq);
+    Q.chars.assign(nq, 0); Q.has.assign(nq, 0);
+    for (uint32_t i = 0; i < nq; i++) {
+        if (chars[i] == 0) continue;
+        Q.has[i] = 1;
+        if (chars[i] < INFX_HIGHLIGHT_MIN_CHARS || chars[i] > INFX_HIGHLIGHT_MAX_CHARS) { Q.refuse(i, INFX_EINVAL, "highlight_chars is 16 .. 512 UTF-16 units"); continue; }
+        if (engine_sharded(e)) { Q.refuse(i, INFX_EUNSUPPORTED, "highlight needs an engine that is not sharded: the returned rows are highlighted on one device"); continue; }
+        if (host_phases()) { Q.refuse(i, INFX_EUNSUPPORTED, "highlight runs in the device pipeline: the host phases (INFX_PHASED) do not highlight the returned rows"); continue; }
+        if (!e->dev || !S->stream) { Q.refuse(i, INFX_EHIP, "no GPU: the returned rows are highlighted on the device"); continue; }
+        Q.chars[i] = chars[i];
+    }
+    Q.on = true;
+    S->qh = std::move(Q);
+    return query_part_installed(S, QP_HIGHLIGHT, out_status);
+}
+// Before the batch's infx_search_fused: refuses highlight on a browse query, installs each query's width on the stream, keeps each asking query's words
+static int32_t stage_highlight(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, const FusedIn& FI) {
+    QueryHl& Q = S->qh;
+    S->lastHlChars.assign(nq, 0); S->lastHlQuery.assign(nq, HlQuery());
+    if (!Q.on || Q.nq != nq) return INFX_OK;
+    bool any = false;
+    for (uint32_t i = 0; i < nq; i++) {
+        if (!Q.asks(i)) continue;
+        if (fq[i].flags & INFX_FQ_BROWSE) {      // empty text + EnableFacets: nothing was matched
+            Q.refuse(i, INFX_EUNSUPPORTED, "highlight does not apply to a browse query (empty text with EnableFacets): nothing was matched");
+            fq[i].flags &= ~INFX_FQ_BROWSE;
+            continue;
+        }
+        S->lastHlChars[i] = Q.chars[i]; any = true;
+        const infx_cov_query& c = FI.cq[i]; HlQuery& H = S->lastHlQuery[i];
+        H.longQuery = c.reserved != 0;
+        if (!H.longQuery) {
+            const int32_t n = std::min(std::max(c.num_tokens, 0), (int32_t)INFX_MAX_QUERY_TOKENS);
+            H.text.assign(c.text, c.text + std::min(std::max(c.text_len, 0), (int32_t)INFX_MAX_QUERY_CHARS));
+            H.off.assign(c.tok_off, c.tok_off + n); H.len.assign(c.tok_len, c.tok_len + n);
+        }
+    }
+    if (!any) return INFX_OK;
+    const int32_t rc = infx_stream_set_query_highlight(S->stream, nq, S->lastHlChars.data());
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+static const HlQuery* highlighted(infx_session* S, uint32_t qi) {
+    if (!S || qi >= S->lastHlChars.size() || S->lastHlChars[qi] == 0 || qi >= S->lastHlQuery.size() || !S->stream) { efail(INFX_EINVAL, "no highlighted query of this index in the session's last batch"); return nullptr; }
+    return &S->lastHlQuery[qi];
+}
+int32_t infx_engine_highlight_query(infx_session* S, uint32_t qi, int32_t* rows, int32_t* term_stride, int32_t* snippet_stride, int32_t* long_query,
+                                    uint16_t* text, int32_t* text_len, uint16_t* word_off, uint16_t* word_len, int32_t* words) {
+    const HlQuery* H = highlighted(S, qi);
+    if (!H) return INFX_EINVAL;
+    const int32_t rc = infx_highlight_layout(S->stream, qi, rows, term_stride, snippet_stride);
+    if (rc) { g_eerr = infx_last_error(); return rc; }
+    if (long_query) *long_query = H->longQuery ? 1 : 0;
+    if (text) std::copy(H->text.begin(), H->text.end(), text);
+    if (text_len) *text_len = (int32_t)H->text.size();
+    if (word_off) std::copy(H->off.begin(), H->off.end(), word_off);
+    if (word_len) std::copy(H->len.begin(), H->len.end(), word_len);
+    if (words) *words = (int32_t)H->off.size();
+    return INFX_OK;
+}
+int32_t infx_engine_highlight_rows(infx_session* S, uint32_t qi, uint16_t* out, int64_t cap_u16) {
+    if (!highlighted(S, qi)) return -1;
+    const int32_t n = infx_highlight_rows(S->stream, qi, out, cap_u16);
+    if (n < 0) g_eerr = infx_last_error();
+    return n;
+}
+int32_t infx_engine_last_highlight_stats(infx_session* S, uint32_t* queries, uint32_t* launches) {
+    if (!S) return efail(INFX_EINVAL, "null session");
+    if (!S->stream) return put_stats({{queries, 0u}, {launches, 0u}});
+    const int32_t rc = infx_last_highlight_stats(S->stream, queries, launches);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+int32_t infx_engine_last_highlight_timings(infx_session* S, float* ms, uint64_t* bytes) {
+    if (!S || !ms) return efail(INFX_EINVAL, "null argument");
+    *ms = 0.f; if (bytes) *bytes = 0;
+    if (!S->stream) return INFX_OK;
+    const int32_t rc = infx_last_highlight_timings(S->stream, ms, bytes);
+    if (rc) g_eerr = infx_last_error();
+    return rc;
+}
+// The host's copy of what Stage 2 reads of document `document_index` (an internal index): lower(normalize(IndexedText)), UTF-16.  Returns its length in units
+// (copies at most cap of them), -1 on error.
+int64_t infx_engine_document_text(infx_engine* e, int64_t document_index, uint16_t* out, int64_t cap) {
+    if (!e || cap < 0 || (cap && !out)) { efail(INFX_EINVAL, "null argument"); return -1; }
+    const HostIndex& ix = e->ix;
+    if (!e->indexed || document_index < 0 || document_index >= (int64_t)ix.N || ix.textOff.size() != (size_t)ix.N + 1) { efail(INFX_EINVAL, "no document of this index"); return -1; }
+    const uint64_t b = ix.textOff[document_index], n = ix.textOff[document_index + 1] - b;
+    std::copy(ix.text.begin() + b, ix.text.begin() + b + std::min<uint64_t>(n, (uint64_t)cap), out);
+    return (int64_t)n;
 }
 static void unstage_prefilters(infx_session* S, const std::vector<int>& builtSlots) {
     for (int b : builtSlots) S->preMask[b].valid = false;

@@ -275,6 +275,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "bclsort.hip.inc"
 #include "postproc.hip.inc"
 #include "collapse.hip.inc"
+#include "highlight.hip.inc"
 
 // ---------------------------------------------------------------------------------------------------------------
 struct infx_filter {
@@ -398,6 +399,15 @@ struct infx_stream {
     void* dClp = nullptr; size_t capClp = 0;
     std::vector<int32_t> clpSlot, clpDocs, clpFinalDocs; std::vector<uint32_t> clpCodes, clpSizes, clpGroups, clpRanked, clpReturned, clpCounts; uint32_t clpStride = 0; bool clpPosted = false;
     uint32_t lastClpQueries = 0, lastClpLaunches = 0;
+    // Query.highlight of the NEXT batch (infx_stream_set_query_highlight), consumed by its finalize.  dHl: one blob — each query's slot and width, then the rows
+    // k_highlight writes.  Of the last batch: each query's slot (-1: it did not ask), the strides, the rows as downloaded, each query's row count.
+    // hlCs / hlAlias: the matcher settings and the alias flag the batch's Stage 2 ran with (fused_enqueue_prep_stage2 notes them: Stage 2 consumes the settings).
+    bool hlOn = false; std::vector<int32_t> hlReq;
+    void* dHl = nullptr; size_t capHl = 0;
+    std::vector<int32_t> hlSlot; std::vector<uint16_t> hlRows; std::vector<uint32_t> hlCounts; uint32_t hlStride = 0, hlTermStride = 0, hlSnipStride = 0;
+    uint32_t lastHlQueries = 0, lastHlLaunches = 0; uint64_t lastHlBytes = 0;
+    infx_stage2_setup hlCs{}; bool hlAlias = false; std::vector<int32_t> hlWords;      // hlWords: per query of the batch its Stage-2 word count, -1 for a long query
+    hipEvent_t evH0 = nullptr, evH1 = nullptr; bool timedHl = false;      // around k_highlight (created by the first batch that highlights)
     hipEvent_t evK0 = nullptr, evK1 = nullptr; bool timedClp = false;      // around k_collapse (created by the first batch that collapses): evF0 .. evK0 is k_finalize_win
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
     void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
@@ -1341,7 +1351,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dClp};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dClp, s->dHl};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (const SetKindState& K : s->kind) { if (K.ws) hipFree(K.ws); if (K.out) hipFree(K.out); }
     for (void* p : ps) if (p) hipFree(p);
@@ -1357,6 +1367,8 @@ void infx_stream_destroy(infx_stream* s) {
     if (s->evJoin) hipEventDestroy(s->evJoin);
     if (s->evK0) hipEventDestroy(s->evK0);
     if (s->evK1) hipEventDestroy(s->evK1);
+    if (s->evH0) hipEventDestroy(s->evH0);
+    if (s->evH1) hipEventDestroy(s->evH1);
     { std::lock_guard<std::mutex> lk(s->ix->turnMu); if (s->ix->turnEvent == s->evTurn) s->ix->turnEvent = nullptr; }
     if (s->evTurn) hipEventDestroy(s->evTurn);
     if (s->stAux) { hipStreamSynchronize(s->stAux); hipStreamDestroy(s->stAux); }
@@ -1973,6 +1985,10 @@ static int32_t fused_enqueue_prep_stage2(infx_stream* s, int W, uint32_t nd, con
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->evP1, s->st));
     HIPCHK(hipEventRecord(s->evC0, s->st));
+    if (s->hlOn) {      // Query.highlight: what k_highlight needs of this Stage-2 call after it has consumed its settings — them, the alias flag, each query's word count
+        s->hlCs = S2_CS ? s->cs : S2_DEFAULT_SETUP; s->hlAlias = S2_AL;
+        s->hlWords.resize(nq); for (uint32_t i = 0; i < nq; i++) s->hlWords[i] = cq[i].reserved != 0 ? -1 : std::min(std::max(cq[i].num_tokens, 0), (int32_t)INFX_MAX_QUERY_TOKENS);
+    }
     S2_LAUNCH_FAST(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
                                                                                  (infx_cov_out*)s->dCovO, want_debug ? (int32_t*)s->dCovF : nullptr, 1, 0, (const int32_t*)s->dFPairs);
     S2_LAUNCH_SLOW(dev_index(s), (const infx_cov_query*)s->dCovQ, nq, (const infx_cov_cand*)s->dCovC, ncand,
@@ -2190,6 +2206,37 @@ static int32_t collapse_enqueue(infx_stream* s, const std::vector<DevCollapse>& 
     return INFX_OK;
 }
 
+// Query.highlight: ONE k_highlight launch over the result table as the post-processing left it, k asking queries (s->hlSlot).  One blob holds each query's
+// slot and width and the rows; the rows — strided by what the batch asked: its largest word count, its largest width — come back with the batch's other
+// outputs (no host wait here).
+static int32_t highlight_enqueue(infx_stream* s, uint32_t nq, int32_t max_results, uint32_t k) {
+    uint32_t T = 1, W = HL_MIN_CHARS;
+    for (uint32_t q = 0; q < nq; q++) if (s->hlSlot[q] >= 0) { T = std::max<uint32_t>(T, (uint32_t)std::max(s->hlWords[q], 0)); W = std::max<uint32_t>(W, (uint32_t)s->hlReq[q]); }
+    const size_t rowU16 = hl_row_u16(T, W), rows = (size_t)k * max_results;
+    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    const size_t oSlot = 0, oChars = al(oSlot + (size_t)nq * 4), oRows = al(oChars + (size_t)nq * 4), total = oRows + rows * rowU16 * 2;
+    GROW(s->dHl, s->capHl, total);
+    char* D = (char*)s->dHl;
+    std::vector<uint8_t> Hh(oRows, 0);
+    std::memcpy(Hh.data() + oSlot, s->hlSlot.data(), (size_t)nq * 4); std::memcpy(Hh.data() + oChars, s->hlReq.data(), (size_t)nq * 4);
+    UP(D, Hh.data(), oRows);
+    DevHighlight H{};
+    H.slot = (const int32_t*)(D + oSlot); H.chars = (const int32_t*)(D + oChars); H.docs = (const int32_t*)s->dFDocs; H.counts = (const uint32_t*)s->dFCounts;
+    H.nq = nq; H.stride = (uint32_t)max_results; H.out = (uint16_t*)(D + oRows); H.termStride = T; H.snipStride = W; H.poolChars = s2_pool();
+    if (!s->evH0) { HIPCHK(hipEventCreate(&s->evH0)); HIPCHK(hipEventCreate(&s->evH1)); }
+    HIPCHK(hipEventRecord(s->evH0, s->st));
+    const uint32_t grid = (uint32_t)(((size_t)nq * max_results + HL_THREADS - 1) / HL_THREADS);
+    if (s->hlAlias) k_highlight<true><<<grid, HL_THREADS, (size_t)H.poolChars * 2, s->st>>>(dev_index(s), (const infx_cov_query*)s->dCovQ, H, s->hlCs);
+    else k_highlight<false><<<grid, HL_THREADS, (size_t)H.poolChars * 2, s->st>>>(dev_index(s), (const infx_cov_query*)s->dCovQ, H, s->hlCs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->evH1, s->st)); s->timedHl = true;
+    s->hlStride = (uint32_t)max_results; s->hlTermStride = T; s->hlSnipStride = W; s->lastHlQueries = k; s->lastHlLaunches = 1; s->lastHlBytes = rows * rowU16 * 2;
+    // (rows past a query's count are never read: infx_highlight_rows stops at the count)
+    s->hlRows.resize(rows * rowU16); s->hlCounts.resize(nq);
+    DOWN(s->hlRows.data(), D + oRows, rows * rowU16 * 2); DOWN(s->hlCounts.data(), s->dFCounts, (size_t)nq * 4);
+    return INFX_OK;
+}
+
 // k_finalize over s->dCovC / s->dCovO / s->dFMeta / s->dFS1 -> result rows in s->dFKeys ...
 static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth, int32_t max_results, bool ties) {
     infx_index* ix = s->ix;
@@ -2220,6 +2267,21 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
             clpList.push_back(DevCollapse{ix->colCodes[R.col], q, (uint32_t)R.keep});
         }
         if (!clpList.empty() && depth > (int32_t)CLP_MAX_ROWS) return fail(INFX_EUNSUPPORTED, "collapsing works on a ranked list of at most 1024 rows (the depth)%s");
+    }
+    // Query.highlight: the asking queries of this batch get a slot each, in batch order (nothing below differs from a batch without one while hlK is 0)
+    const bool hl = s->hlOn; s->hlOn = false;
+    s->lastHlQueries = s->lastHlLaunches = 0; s->lastHlBytes = 0; s->hlSlot.clear(); s->timedHl = false;
+    uint32_t hlK = 0;
+    if (hl) {
+        if (s->hlReq.size() != nq) return fail(INFX_EINVAL, "the per-query highlight requests were installed for a batch of another size%s");
+        if (s->hlWords.size() != nq) return fail(INFX_EINVAL, "highlight requests need the batch's own Stage-2 call in front of its finalize (infx_search_fused)%s");
+        s->hlSlot.assign(nq, -1);
+        for (uint32_t q = 0; q < nq; q++) {
+            if (s->hlReq[q] == 0) continue;
+            if (s->hlReq[q] < HL_MIN_CHARS || s->hlReq[q] > HL_MAX_CHARS) return fail(INFX_EINVAL, "a highlight request's width is 16 .. 512 UTF-16 units%s");
+            s->hlSlot[q] = (int32_t)hlK++;
+        }
+        if (!hlK) s->hlSlot.clear();
     }
     if (qp && s->qpNq != nq) return fail(INFX_EINVAL, "the per-query options were installed for a batch of another size%s");
     const bool post = !qp && (s->postFilter != nullptr || s->nFacet > 0);
@@ -2255,7 +2317,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         if (qp) for (auto& b : s->browseQ) if (!(s->qpDesc[b.first].flags & QP_FACETS)) { s->browseQ.clear(); return fail(INFX_EINVAL, "a browse query needs INFX_QP_FACETS in its descriptor%s"); }
         if (!ix->d.docKeyAll) { s->browseQ.clear(); return fail(INFX_EINVAL, "index not uploaded%s"); }
     }
-    if (launchPF || launchPP || !clpList.empty()) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
+    if (launchPF || launchPP || !clpList.empty() || hlK) GROW(s->dFDocs, s->capFDocs, (size_t)nq * max_results * 4);
     const DevColumns cols = dev_columns(ix);
     const DevPostBatch* dPB = nullptr; const DevFilter* dProgs = nullptr; const char* dCode = nullptr;
     // the batch's program table, boost list and descriptors: the staged per-query ones, or the session-wide filters (resident entries) behind one shared descriptor
@@ -2311,7 +2373,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
     k_finalize<<<nq, P2_THREADS, lds, s->st>>>(dev_index(s), (const infx_fused_query*)s->dFQ, (const FusedMeta*)s->dFMeta, (const infx_cov_cand*)s->dCovC,
                                                 (const infx_cov_out*)s->dCovO, (const infx_hit*)s->dFS1, depth, (int)Cp, max_results,
                                                 (long long*)s->dFKeys, (float*)s->dFScores, ties ? (uint8_t*)s->dFTies : nullptr,
-                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP ? (int32_t*)s->dFDocs : nullptr,
+                                                (uint32_t*)s->dFCounts, (uint32_t*)s->dFFlags, (uint32_t*)s->dFErr, launchPF || launchPP || hlK ? (int32_t*)s->dFDocs : nullptr,
                                                 (const infx_finalize_setup*)s->dFin);
     else { int32_t rc_ = collapse_enqueue(s, clpList, nq, depth, (int)Cp, lds, max_results, ties); if (rc_) return rc_; }
     HIPCHK(hipGetLastError());
@@ -2355,6 +2417,7 @@ static int32_t fused_enqueue_finalize(infx_stream* s, uint32_t nq, int32_t depth
         DOWN(s->clpCounts.data(), s->dFCounts, (size_t)nq * 4);
         if (launchPF || launchPP) { s->clpFinalDocs.resize((size_t)nq * max_results); s->clpPosted = true; DOWN(s->clpFinalDocs.data(), s->dFDocs, (size_t)nq * max_results * 4); }
     }
+    if (hlK) { const int32_t rc_ = highlight_enqueue(s, nq, max_results, hlK); if (rc_) return rc_; }      // on the rows as they leave
     HIPCHK(hipEventRecord(s->evF1, s->st));
     s->timedFused = true;
     return INFX_OK;
@@ -3059,6 +3122,40 @@ int32_t infx_last_collapse_timings(infx_stream* s, float* ms2) {
     if (!s || !ms2) return fail(INFX_EINVAL, "null argument%s");
     ms2[0] = ms2[1] = 0.f;
     if (s->timedClp) { hipEventElapsedTime(&ms2[0], s->evF0, s->evK0); hipEventElapsedTime(&ms2[1], s->evK0, s->evK1); }
+    return INFX_OK;
+}
+// ---- Query.highlight (k_highlight) -----------------------------------------------------------------------------------------------------------------------
+int32_t infx_stream_set_query_highlight(infx_stream* s, uint32_t nq, const int32_t* chars) {
+    if (!s || (nq && !chars)) return fail(INFX_EINVAL, "null argument%s");
+    s->hlOn = nq > 0; s->hlReq.assign(chars, chars + nq); s->hlWords.clear();
+    return INFX_OK;
+}
+int32_t infx_highlight_layout(infx_stream* s, uint32_t qi, int32_t* rows, int32_t* term_stride, int32_t* snippet_stride) {
+    if (!s || qi >= s->hlSlot.size() || s->hlSlot[qi] < 0) return fail(INFX_EINVAL, "no highlighting query of this index in the stream's last batch%s");
+    if (rows) *rows = (int32_t)std::min(s->hlCounts[qi], s->hlStride);
+    if (term_stride) *term_stride = (int32_t)s->hlTermStride;
+    if (snippet_stride) *snippet_stride = (int32_t)s->hlSnipStride;
+    return INFX_OK;
+}
+// Query qi's rows as the batch returned them, hl_row_u16(term stride, snippet stride) uint16 each (csrc/highlight.h); returns the rows written, -1 on error
+int32_t infx_highlight_rows(infx_stream* s, uint32_t qi, uint16_t* out, int64_t cap_u16) {
+    if (!s || qi >= s->hlSlot.size() || s->hlSlot[qi] < 0 || cap_u16 < 0 || (cap_u16 && !out)) { fail(INFX_EINVAL, "no highlighting query of this index in the stream's last batch%s"); return -1; }
+    const size_t rowU16 = hl_row_u16(s->hlTermStride, s->hlSnipStride);
+    const uint32_t n = (uint32_t)std::min<uint64_t>(std::min(s->hlCounts[qi], s->hlStride), (uint64_t)cap_u16 / rowU16);
+    const uint16_t* src = s->hlRows.data() + (size_t)s->hlSlot[qi] * s->hlStride * rowU16;
+    for (uint32_t r = 0; r < n; r++) if (src[(size_t)r * rowU16] == HL_BAD_ROW) { fail(INFX_EINVAL, "a returned row's document is not one of the index%s"); return -1; }
+    std::memcpy(out, src, (size_t)n * rowU16 * 2);
+    return (int32_t)n;
+}
+int32_t infx_last_highlight_stats(infx_stream* s, uint32_t* queries, uint32_t* launches) {
+    if (!s) return fail(INFX_EINVAL, "null argument%s");
+    if (queries) *queries = s->lastHlQueries; if (launches) *launches = s->lastHlLaunches;
+    return INFX_OK;
+}
+int32_t infx_last_highlight_timings(infx_stream* s, float* ms, uint64_t* bytes) {
+    if (!s || !ms) return fail(INFX_EINVAL, "null argument%s");
+    *ms = 0.f; if (bytes) *bytes = s->lastHlBytes;
+    if (s->timedHl) hipEventElapsedTime(ms, s->evH0, s->evH1);
     return INFX_OK;
 }
 int32_t infx_last_browse_stats(infx_stream* s, uint32_t* groups, uint32_t* launches) {

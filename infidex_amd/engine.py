@@ -99,6 +99,12 @@ class Query:       # Api/Query.cs:9-45
     sort_by: Optional[str] = None          # Query.SortBy: a field (column) name, None = relevance order
     sort_ascending: bool = False           # Query.SortAscending
     coverage_setup: Optional[CoverageSetup] = None      # Query.CoverageSetup: None = the engine's (its matcher members are ignored, see CoverageSetup)
+    # Not in the reference: Result.highlights — per returned row which document word each Stage-2 query word matched and how, the spans a UI paints and a
+    # snippet of at most highlight_chars (16 .. 512) UTF-16 units of the stored text (SearchEngine.stored_text), computed on the device by Stage 2's matchers.
+    # Keyword-only, so they stand here without moving a positional parameter: the constructor takes them behind collapse_keep, and the dataclass's field list
+    # still ends with collapse_by, collapse_keep, which callers rely on.
+    highlight: bool = _dc_field(default=False, kw_only=True)
+    highlight_chars: int = _dc_field(default=160, kw_only=True)
     # Not in the reference: an Infiscript expression that restricts the set that is RANKED — the query returns what it would if every document the expression
     # does not accept were deleted (index statistics untouched).  `filter` then post-processes the returned rows as usual.
     pre_filter: Optional[str] = None
@@ -112,10 +118,40 @@ class Query:       # Api/Query.cs:9-45
     collapse_keep: int = 1                 # rows kept per group, 1 .. 16
 
     @property
-    def max_boost(self) -> int:            # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
+    def max_boost(self) -> int:           # Query.MaxBoost: the sum of every boost's strength when boosting is enabled
         if not self.enable_boost or self.boosts is None:
             return 0
         return sum(int(b.strength) for b in self.boosts)
+
+
+HIGHLIGHT_KINDS = ("none", "whole", "joined_query", "joined_doc", "prefix", "suffix", "infix", "tail", "fuzzy_prefix", "fuzzy")      # HL_K_* of csrc/highlight.h
+HIGHLIGHT_STATUS = ("ok", "too_long", "long_query")                                                                                  # HL_OK, HL_TOO_LONG, HL_LONG_QUERY
+HIGHLIGHT_MAX_SPANS = 64
+
+
+@dataclass
+class TermMatch:   # Query.highlight: what one Stage-2 query word matched in one returned document (offsets and lengths: UTF-16 units of the stored text)
+    word: str
+    kind: str = "none"         # one of HIGHLIGHT_KINDS
+    offset: int = 0            # the first occurrence of the matched document word (what Stage 2 feeds into FirstMatchIndex)
+    length: int = 0
+    match_offset: int = 0      # the part of that word the query word covers
+    match_length: int = 0
+    distance: int = 0          # edit distance of a fuzzy or fuzzy_prefix match
+    offset2: int = 0           # joined_doc: the second of the two consecutive document words
+    length2: int = 0
+
+
+@dataclass
+class Highlight:   # Query.highlight: one returned row
+    status: str = "ok"         # "ok", "too_long" (the document has more than 192 Stage-2 words) or "long_query" (the query is outside the fast envelope)
+    document_index: int = 0    # internal index of the document the row stands for (the segment that was scored)
+    terms: List[TermMatch] = _dc_field(default_factory=list)       # one per Stage-2 query word, in Stage 2's order
+    spans: List[Tuple[int, int, int, int, int]] = _dc_field(default_factory=list)      # (offset, length, match_offset, match_length, term), ascending offset, at most 64
+    truncated: bool = False    # occurrences beyond the 64th were left out
+    snippet: str = ""          # stored_text[snippet_start : snippet_start + n] in UTF-16 units, n <= highlight_chars
+    snippet_start: int = 0
+    words: int = 0             # raw words of the document under the batch's min_word_size (Stage 2's DocTokenCount)
 
 
 @dataclass
@@ -146,6 +182,8 @@ class Result:      # Api/Result.cs
     group_sizes = None
     total_groups = None
     total_ranked = None
+    # Query.highlight (None for a query without it, or refused): one Highlight per entry of `records`, as the rows finally come back.  A plain attribute too.
+    highlights = None
 
     # SearchEngine.cs:312-316: index and score of the last returned row, and the row count
     @property
@@ -943,7 +981,7 @@ class SearchEngine:
     # ---- search ----
     def search(self, query: Union[Query, str], max_results: Optional[int] = None) -> Result:
         q = query if isinstance(query, Query) else Query(query, max_results or 10)
-        if q.coverage_setup is not None or q.pre_filter is not None or q.collapse_by is not None:
+        if q.coverage_setup is not None or q.pre_filter is not None or q.collapse_by is not None or q.highlight:
             return self.search_queries([q])[0]
         if q.filter is not None or q.enable_facets or (q.enable_boost and q.boosts) or q.sort_by is not None:
             return self.search_filtered([q.text], q.max_number_of_records_to_return, q.coverage_depth, q.enable_coverage, q.filter, q.enable_facets,
@@ -957,6 +995,26 @@ class SearchEngine:
     def last_collapse_stats(self, session=None):
         """(queries with Query.collapse_by that were folded, k_collapse launches) of the session's last search: (k, 1), or (0, 0) for a batch without one."""
         return _u32_stats(self, "infx_engine_last_collapse_stats", session.h if session is not None else self._default_session(), 2)
+
+    def last_highlight_stats(self, session=None):
+        """(queries with Query.highlight that were highlighted, k_highlight launches) of the session's last search: (k, 1), or (0, 0) for a batch without one."""
+        return _u32_stats(self, "infx_engine_last_highlight_stats", session.h if session is not None else self._default_session(), 2)
+
+    def last_highlight_timings(self, session=None):
+        """(k_highlight's milliseconds, bytes of highlight rows downloaded) of the session's last search."""
+        return _highlight_timings(self, session.h if session is not None else self._default_session())
+
+    def stored_text(self, document_index: int) -> str:
+        """The stored text of one document (internal index): lower(normalize(IndexedText)), what Stage 2 and Query.highlight read; Highlight's offsets are
+        UTF-16 units of it."""
+        fn = self.L.infx_engine_document_text; fn.restype = C.c_int64
+        n = fn(self.h, C.c_int64(int(document_index)), None, C.c_int64(0))
+        if n < 0:
+            self._check(1)
+        buf = np.zeros(max(int(n), 1), np.uint16)
+        if fn(self.h, C.c_int64(int(document_index)), _p(buf, C.c_uint16), C.c_int64(int(n))) != n:
+            self._check(1)
+        return buf[:n].tobytes().decode("utf-16-le", errors="surrogatepass")
 
     def last_prefilter_stats(self, session=None):
         """(masks built, masks taken from the session's cache, k_filter_mask_multi launches) of the session's last search (or prefilter_mask call)."""
@@ -1273,6 +1331,14 @@ class Session:
         """SearchEngine.last_collapse_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_collapse_stats", self.h, 2)
 
+    def last_highlight_stats(self):
+        """SearchEngine.last_highlight_stats of this session."""
+        return _u32_stats(self.engine, "infx_engine_last_highlight_stats", self.h, 2)
+
+    def last_highlight_timings(self):
+        """SearchEngine.last_highlight_timings of this session."""
+        return _highlight_timings(self.engine, self.h)
+
     def last_prefilter_stats(self):
         """SearchEngine.last_prefilter_stats of this session."""
         return _u32_stats(self.engine, "infx_engine_last_prefilter_stats", self.h, 3)
@@ -1419,7 +1485,8 @@ def _install_query_options(engine, sh, qs):
     L = engine.L
     parts = ((lambda q: q.coverage_setup, lambda: _install_coverage(engine, sh, qs), lambda: L.infx_engine_set_query_coverage(sh, 0, None, None)),
              (lambda q: q.pre_filter, lambda: _install_prefilters(engine, sh, [q.pre_filter for q in qs]), lambda: L.infx_engine_set_query_prefilters(sh, 0, None, None)),
-             (lambda q: q.collapse_by, lambda: _install_collapse(engine, sh, qs), lambda: L.infx_engine_set_query_collapse(sh, 0, None, None, None)))
+             (lambda q: q.collapse_by, lambda: _install_collapse(engine, sh, qs), lambda: L.infx_engine_set_query_collapse(sh, 0, None, None, None)),
+             (lambda q: True if q.highlight else None, lambda: _install_highlight(engine, sh, qs), lambda: L.infx_engine_set_query_highlight(sh, 0, None, None)))
     for asked, install, clear in parts:
         if not any(asked(q) is not None for q in qs):
             engine._check(clear())
@@ -1474,12 +1541,74 @@ def _attach_collapse(engine, sh, qs, results):
         r.total_groups = int(groups[j]); r.total_ranked = int(ranked[j])
 
 
+def _install_highlight(engine, sh, qs):
+    """infx_engine_set_query_highlight for the coming batch on session handle sh (Query.highlight False: width 0, not asked); returns each query's status."""
+    n = len(qs)
+    # (a width of 0 would read as "not asked": an asking query's width is sent as given, 0 as -1, and refused by the library with the others out of range)
+    chars = np.asarray([(min(max(int(q.highlight_chars), -1), 2 ** 31 - 1) or -1) if q.highlight else 0 for q in qs] or [0], np.int32)
+    st = np.zeros(max(n, 1), np.int32)
+    engine._check(engine.L.infx_engine_set_query_highlight(sh, n, _p(chars, C.c_int32), _p(st, C.c_int32)))
+    return st[:n]
+
+
+def _highlight_timings(engine, sh):
+    ms = C.c_float(0); nbytes = C.c_uint64(0)
+    engine._check(engine.L.infx_engine_last_highlight_timings(sh, C.byref(ms), C.byref(nbytes)))
+    return float(ms.value), int(nbytes.value)
+
+
+def _u16_text(a):
+    return np.ascontiguousarray(a, np.uint16).tobytes().decode("utf-16-le", errors="surrogatepass")
+
+
+def _attach_highlights(engine, sh, qs, results):
+    """Result.highlights of the queries of a batch just searched on session handle sh that ran with Query.highlight: the rows k_highlight wrote (layout:
+    csrc/highlight.h), one Highlight per returned row."""
+    L = engine.L
+    for j, (q, r) in enumerate(zip(qs, results)):
+        if not q.highlight or r.error is not None:
+            continue
+        m = len(r.records)
+        rows = C.c_int32(0); ts = C.c_int32(0); ss = C.c_int32(0); lq = C.c_int32(0); tl = C.c_int32(0); nw = C.c_int32(0)
+        text = np.zeros(512, np.uint16); woff = np.zeros(32, np.uint16); wlen = np.zeros(32, np.uint16)
+        if m == 0:
+            r.highlights = []
+            continue
+        engine._check(L.infx_engine_highlight_query(sh, j, C.byref(rows), C.byref(ts), C.byref(ss), C.byref(lq), _p(text, C.c_uint16), C.byref(tl),
+                                                    _p(woff, C.c_uint16), _p(wlen, C.c_uint16), C.byref(nw)))
+        T, W = int(ts.value), int(ss.value)
+        row_u16 = 10 + 8 * T + 5 * HIGHLIGHT_MAX_SPANS + W
+        buf = np.zeros(max(m, 1) * row_u16, np.uint16)
+        got = L.infx_engine_highlight_rows(sh, j, _p(buf, C.c_uint16), C.c_int64(len(buf)))
+        if got != m:
+            engine._check(1 if got < 0 else 0)
+            raise InfidexError(1, "highlight: %d rows described, %d returned" % (got, m))
+        words = [_u16_text(text[int(woff[k]):int(woff[k]) + int(wlen[k])]) for k in range(int(nw.value))]
+        out = []
+        for k in range(m):
+            R = buf[k * row_u16:(k + 1) * row_u16]
+            h = Highlight(HIGHLIGHT_STATUS[int(R[0])], int(R[6]) | (int(R[7]) << 16))
+            if h.status == "ok":
+                nt, ns = int(R[1]), int(R[2])
+                h.truncated = bool(R[3]); h.snippet_start = int(R[4]); h.words = int(R[8])
+                for i in range(nt):
+                    t = R[10 + 8 * i:18 + 8 * i]
+                    h.terms.append(TermMatch(words[i], HIGHLIGHT_KINDS[int(t[0])], int(t[2]), int(t[3]), int(t[4]), int(t[5]), int(t[1]), int(t[6]), int(t[7])))
+                sp = R[10 + 8 * T:10 + 8 * T + 5 * ns].reshape(ns, 5)
+                h.spans = [tuple(int(x) for x in s) for s in sp]
+                at = 10 + 8 * T + 5 * HIGHLIGHT_MAX_SPANS
+                h.snippet = _u16_text(R[at:at + int(R[5])])
+            out.append(h)
+        r.highlights = out
+
+
 def _clear_query_options(engine, sh):
     """Drops the per-query options and coverage setups installed on session handle sh (a batch that failed before it consumed them)."""
     engine.L.infx_engine_set_query_options(sh, 0, None, None)
     engine.L.infx_engine_set_query_coverage(sh, 0, None, None)
     engine.L.infx_engine_set_query_prefilters(sh, 0, None, None)
     engine.L.infx_engine_set_query_collapse(sh, 0, None, None, None)
+    engine.L.infx_engine_set_query_highlight(sh, 0, None, None)
 
 
 def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
@@ -1492,13 +1621,14 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
     for j, q in enumerate(qs):
         err = None
         # (a pre-filter on a browse query is refused when the batch runs: result flag bit 4 without an install status)
-        if status[j] != 0 or ((q.pre_filter is not None or q.collapse_by is not None) and flags[j] & 16):
+        if status[j] != 0 or ((q.pre_filter is not None or q.collapse_by is not None or q.highlight) and flags[j] & 16):
             err = _query_error(engine, sh, j, int(status[j]) or 5)
         recs = [ScoreEntry(float(scores[j, k]), int(keys[j, k]), int(ties[j, k])) for k in range(int(counts[j]))]
         facets = engine.facets_of(sh, n, j) if q.enable_facets and err is None else None
         out.append(Result(recs, bool(flags[j] & 1), bool(flags[j] & 2), bool(flags[j] & 4), bool(flags[j] & 8), facets, int(inf[j]),
                           total_in_pre_filter=int(inpre[j]) if inpre is not None else 0, error=err))
     _attach_collapse(engine, sh, qs, out)
+    _attach_highlights(engine, sh, qs, out)
     return out
 
 
