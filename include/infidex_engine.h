@@ -240,12 +240,55 @@ int32_t infx_engine_index_from_host_cache(infx_engine* e, const char* path);
  * rows (Scoring/ResultProcessor.cs:35-70), Filter.NumberOfDocumentsInFilter and the facet counts (Core/FacetBuilder.cs:19-105) run on the
  * device (include/infidex_hip.h).  kind: 1 int64, 2 double, 3 UTF-8 strings (arena + n+1 offsets).  A name the engine already holds REPLACES
  * that column in its slot (new values, possibly of another kind): compiled filters, filter counts, masks, filtered-facet answers and the column's
- * sort rank are built again on their next use.  An exclusive call, like indexing: no search is in flight. */
+ * sort rank are built again on their next use.  An exclusive call, like indexing: no search is in flight.  The name must not be empty (INFX_EINVAL): a
+ * nameless slot is what a scalar column leaves behind when a list column takes its name (below). */
 int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, int32_t facetable, int64_t n, const int64_t* vals_i, const double* vals_d,
                                const char* arena, const uint64_t* offs);
 int32_t infx_engine_column_count(infx_engine* e);
 int32_t infx_engine_column_info(infx_engine* e, int32_t col, char* name, int32_t cap, int32_t* facetable, int32_t* num_values);
 int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, char* out, int32_t cap);
+/* ---- list columns: a field that holds a LIST of values per document (Field.IsArray: genres, tags, authors) ---------------------------------------------
+ * infx_engine_add_list_column gives one list per indexed document, in indexing order: doc_offs[n + 1] (ascending from 0) delimits document d's elements,
+ * which are vals_i (kind 1), vals_d (kind 2) or the strings arena[offs[j] .. offs[j + 1]) (kind 3) — kinds as in infx_engine_add_column; all elements of a
+ * column are of one kind.  Lists are kept as given: order and duplicates stay.  The elements are dictionary-encoded like a scalar column's values; the device
+ * holds the lists as a CSR pair of uint32 (fewer than 2^32 elements per column: INFX_ECAPACITY beyond).
+ * Names: list columns and scalar columns share ONE namespace — a name that either kind holds is replaced by the new column, of either kind, with the
+ * invalidation documented for infx_engine_add_column (a scalar column replaced by a list column leaves its slot behind as a nameless column that the next
+ * new scalar column takes).  List columns take no slot among the 64 scalar columns and none among the INFX_MAX_FACET_COLS facet columns: there are at most
+ * INFX_ENGINE_MAX_LIST_COLS of them, of which INFX_ENGINE_MAX_LIST_FACETS may be facetable (INFX_ECAPACITY beyond).  INFX_EUNSUPPORTED on a sharded engine.
+ * FILTERS.  A leaf of the filter language over a list column holds for a document iff its list is not empty and the leaf holds for AT LEAST ONE element
+ * (as it would for a scalar value), or its list is empty and the leaf holds for a null value: `tags IS NULL` accepts the empty lists (so do < and <=, for which a null is below every constant, as for a scalar field) and no other comparison does.
+ * NOT, AND, OR and ?: apply to that verdict: `NOT tags = 'sale'` and `tags != 'sale'` (which is NOT over an = leaf) both mean "no element equals sale".
+ * Such a leaf is lowered, on the first use of its expression, to a derived one-bit column on the device (k_list_leaf; all missing leaves of an expression
+ * over one list column in one launch) that takes a free slot among the 64 scalar slots and is read by every kernel that runs filter programs like any
+ * scalar column: post-filters, boosts, pre-filters, filtered facets, browse queries, listings and every aggregate's filter.  The engine caches at most
+ * INFX_ENGINE_MAX_DERIVED derived columns by (list column, operator, constants), least recently used first out among those no cached compiled filter uses;
+ * an expression that finds no entry or no slot free is refused alone with INFX_ECAPACITY.  infx_engine_last_list_leaf_stats: derived columns built and
+ * k_list_leaf launches of the last expression the engine COMPILED (an expression taken from the filter cache compiles nothing and leaves them as they are);
+ * infx_engine_list_leaf_totals: the same two figures summed over every compile of the engine — unchanged by a call that compiled or built nothing.
+ * FACETS.  A facetable list column is counted by infx_engine_facets_all and infx_engine_facets_filtered (k_list_facets): a value's count is the number of its
+ * element occurrences — a duplicate counts twice, as FacetBuilder counts it — among the live documents (the expression accepts); empty strings are left
+ * out; order and cut as the scalar facets.  Readers: infx_engine_facets_all_list_column / infx_engine_facets_filtered_list_column, as their scalar
+ * counterparts, with the list column's index in *lcol; names and values from infx_engine_list_column_info / _value.  totals count documents, not elements.
+ * NOT BUILT: the facets of the returned rows (infx_engine_last_facets) and of a browse query do not include list columns; a list column named as order_by,
+ * sort_by, group_by, collapse_by, field or bucket_by is refused for that request (query) alone, as an unknown field is; a session-wide
+ * infx_engine_set_sort by a list column returns INFX_EINVAL.
+ * infx_engine_list_column_document: the stored list of one document as element codes (up to cap; returns the list's length, -1 on error). */
+#define INFX_ENGINE_MAX_LIST_COLS 8
+#define INFX_ENGINE_MAX_LIST_FACETS 4
+#define INFX_ENGINE_MAX_DERIVED 16
+int32_t infx_engine_add_list_column(infx_engine* e, const char* name, int32_t kind, int32_t facetable, int64_t n, const uint64_t* doc_offs /* n+1 */,
+                                    const int64_t* vals_i, const double* vals_d, const char* arena, const uint64_t* offs);
+int32_t infx_engine_list_column_count(infx_engine* e);
+int32_t infx_engine_list_column_info(infx_engine* e, int32_t lcol, char* name, int32_t cap, int32_t* facetable, int32_t* num_values, int32_t* kind);
+int32_t infx_engine_list_column_value(infx_engine* e, int32_t lcol, uint32_t code, char* out, int32_t cap);
+int64_t infx_engine_list_column_document(infx_engine* e, int32_t lcol, int64_t document_index, uint32_t* codes, int64_t cap);
+int32_t infx_engine_last_list_leaf_stats(infx_engine* e, uint32_t* built, uint32_t* launches);
+int32_t infx_engine_list_leaf_totals(infx_engine* e, uint64_t* built, uint64_t* launches);
+int32_t infx_engine_facets_all_list_column_count(infx_session* s);
+int32_t infx_engine_facets_all_list_column(infx_session* s, uint32_t k, int32_t* lcol, uint32_t* codes, uint32_t* counts, int32_t cap);
+int32_t infx_engine_facets_filtered_list_column_count(infx_session* s);
+int32_t infx_engine_facets_filtered_list_column(infx_session* s, uint32_t which, uint32_t k, int32_t* lcol, uint32_t* codes, uint32_t* counts, int32_t cap);
 /* Post rows: how many returned rows per query the filter, facets, boosts, sort-by and browse rows accept — INFX_FILTER_MAX_ROWS (64, the default) up to
  * INFX_POST_MAX_ROWS (1024 = the largest max_depth, so no text query returns more).  The reference post-filters the truncated top-MaxNumberOfRecordsToReturn
  * rows (SearchEngine.cs:304-310): a caller who wants twenty rows that pass a selective filter asks for a few hundred.  An engine left at the default

@@ -463,6 +463,26 @@ int32_t infx_facets_all(infx_stream* s, uint32_t ncol, const uint32_t* cols, uin
 int32_t infx_facets_filtered(infx_stream* s, uint32_t k, const infx_filter_prog* progs, uint32_t ncol, const uint32_t* cols,
                              uint32_t* counts_out /* k x sum(num_values), program-major */, uint32_t* totals_out /* k */);
 int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint32_t* launches);
+/* ---- list columns: multi-valued document fields (Field.IsArray; kernels in csrc/list_columns.hip.inc) -------------------------------------------------
+ * A list column is a CSR pair on the device, beside the scalar columns and outside their FILT_MAXCOL slots: elem_off[total_docs + 1] (uint32, ascending from
+ * 0: a column holds fewer than 2^32 elements) and elem_codes[elem_off[total_docs]], the dictionary codes (< num_values) of the elements in document order.
+ * infx_upload_list_column uploads (or replaces) list column lcol < INFX_MAX_LIST_COLS; total_docs = 0 drops it.  Exclusive call, as infx_upload_column.
+ * Not on a sharded index (INFX_EUNSUPPORTED).
+ * infx_list_leaf_build lowers k (<= INFX_LIST_LEAF_MAX) filter leaves over list column lcol to derived scalar columns in ONE k_list_leaf launch: slots[i] <
+ * FILT_MAXCOL (64), distinct, names the scalar column slot that receives leaf i's column — uint32 per document, 1 where the leaf holds for at least one element
+ * of the document's list, or, for an empty list, bit i of empty_bits; the slot then is an uploaded column of 2 values that a filter program reads like any
+ * other.  maps: the leaves' bitmaps over the list column's codes side by side, word w of leaf i at maps[w * k + i], ceil(num_values / 32) * k words; they are
+ * staged in LDS while that is at most INFX_LIST_LEAF_LDS_WORDS words and read from global memory beyond.  Synchronous: the columns are complete on return.
+ * infx_list_facets counts, for each of k (<= INFX_MAX_PREFILTERS) accept sets, the element occurrences of every value of list column lcol among the accepted
+ * documents, in ONE k_list_facets launch: masks[i] = document flags on the device, one byte per document, 0 = accepted (a mask slot of this stream, built by
+ * infx_filter_masks: not Deleted and accepted) or NULL = every document that is not Deleted (the index's real flags).  counts_out: k x num_values words,
+ * set-major.  Duplicates in a list count every time.  Synchronous. */
+#define INFX_MAX_LIST_COLS 8
+#define INFX_LIST_LEAF_MAX 16
+#define INFX_LIST_LEAF_LDS_WORDS 2048
+int32_t infx_upload_list_column(infx_index* idx, uint32_t lcol, uint32_t total_docs, const uint32_t* elem_off, const uint32_t* elem_codes, uint32_t num_values);
+int32_t infx_list_leaf_build(infx_index* idx, uint32_t lcol, uint32_t k, const uint32_t* slots, const uint32_t* maps, uint32_t empty_bits);
+int32_t infx_list_facets(infx_stream* s, uint32_t lcol, uint32_t k, const uint8_t* const* masks, uint32_t* counts_out);
 /* A page of a document set in the order of a column (not in the reference: the order and the paging are this project's; DESIGN.md "list_documents").
  * Request i: the SET is the documents whose byte in `mask` is 0 — a mask slot of this stream (infx_stream_mask_slot, built by infx_filter_masks: not
  * Deleted and accepted) — or, mask = NULL, every document that is not Deleted (the index's real flags).  The KEY of a document is 1 + rank[its code] of

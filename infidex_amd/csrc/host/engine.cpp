@@ -8,6 +8,7 @@
 //   TopKHeap / ScoreEntry / ConsolidateSegments  Core/TopKHeap.cs, Core/ScoreEntry.cs:25-36, Scoring/SegmentProcessor.cs:15-37
 #include "query.h"
 #include "filter.h"
+#include "list_columns.h"
 #include "infdx2.h"
 #include "infdx2_verify.h"
 #include "infs.h"
@@ -109,7 +110,7 @@ struct HlQuery { std::vector<uint16_t> text, off, len; bool longQuery = false; }
 struct PreMask { std::string expr; uint64_t epoch = 0, lastUse = 0; uint32_t count = 0; bool valid = false; };
 // The facets of one Infiscript expression (infx_engine_facets_filtered), as the engine caches them: per facet column the ordered (code, count) list, cut to 100,
 // and the number of live documents the expression accepts; valid for the mask epoch it was counted in
-struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists; std::list<std::string>::iterator lru; };
+struct FfEntry { uint64_t epoch = 0; uint32_t total = 0; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists, listLists; std::list<std::string>::iterator lru; };      // listLists: the facetable list columns, after the scalar ones
 // What the answer to one request of a per-request call begins with: its status and message (why it was refused) and the size of its set (0 when refused)
 struct Answer { int32_t status = INFX_OK; std::string err; uint32_t total = 0; };
 // answer `which` of a session's last per-request call (null: no session, or no such answer)
@@ -150,6 +151,7 @@ struct infx_session {
     std::vector<uint32_t> facetCols;      // engine column indices whose facets the session's stream counts
     std::vector<std::string> swPinFilter, swPinBoosts;      // cache entries the session-wide filter / boosts hold
     bool swFilter = false, swBoost = false, swSort = false;      // session-wide options installed (infx_engine_set_filter / _set_boosts / _set_sort)
+    std::vector<uint32_t> facAllListCols, ffListCols; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> facAllList;      // the facetable list columns of the last infx_engine_facets_all / _facets_filtered, and the former's lists
     std::vector<uint32_t> facAllCols; std::vector<std::vector<std::pair<uint32_t, uint32_t>>> facAll;      // infx_engine_facets_all: columns and their ordered (code, count) lists
     // infx_engine_facets_filtered: the facet columns of the session's last call, one answer per expression of it (its entry of the engine's cache, or why it
     // was refused), and what the call cost: expressions counted on the device, expressions taken from the cache, k_facets_filtered launches
@@ -210,6 +212,7 @@ struct CompiledFilter {
     infx_filter* dev = nullptr;
     uint32_t inFilter = 0, inAll = 0; bool counted = false, countedAll = false;
     uint32_t pins = 0;                      // installs that hold the entry: it is not evicted while > 0
+    std::vector<std::pair<int, std::string>> derived;      // the derived leaf columns its program reads (list column, list_leaf_key): each holds one reference
     std::list<std::string>::iterator lru;
 };
 // the program of anything that holds ops, leaves and tables (a CompiledFilter, a copy taken out of the filter cache), as the device library takes it
@@ -252,6 +255,12 @@ struct MaskCall {
     uint8_t* mask(uint32_t i) const { return of[i] >= 0 ? masks[of[i]] : nullptr; }
     int32_t failed(int32_t rc);                          // the device call failed: its message is kept, nothing stays staged
     void done(uint32_t nq = 0);                          // it succeeded: the built masks' counts, the statistics (nq: the batch whose queries' counts to take)
+    // The filters whose masks the call builds stay pinned in the filter cache until the device has run the build (done / failed): a cached filter holds the
+    // derived columns of its list-column leaves, so no other compile can hand their slots to another leaf in between.
+    std::vector<std::string> pinned; bool locked = false;      // locked: acquire() holds filterMu
+    void release();
+    ~MaskCall() { release(); }
+    MaskCall(const MaskCall&) = delete; MaskCall& operator=(const MaskCall&) = delete;
 };
 static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_fused_query>& fq, MaskCall& pre);
 static int32_t stage_coverage_setup(infx_session* S, uint32_t nq, bool deviceFinalize);
@@ -313,7 +322,19 @@ struct infx_engine {
     std::vector<StatsIndex> statsIndex;
     // NumberOfDocumentsInFilter is cached per expression; a Filter parsed after a mutation counts again (the reference keeps the count on the Filter instance)
     void invalidate_filter_counts() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) kv.second.counted = kv.second.countedAll = false; }
-    void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); filterLru.clear(); }
+    void retire_filters() { std::lock_guard<std::mutex> lk(filterMu); for (auto& kv : filters) if (kv.second.dev) retiredFilters.push_back(kv.second.dev); filters.clear(); filterLru.clear(); derived.clear(); }
+    // List columns (infx_engine_add_list_column): their own INFX_ENGINE_MAX_LIST_COLS slots, outside `columns`; a slot whose name is empty is free.
+    // Derived leaf columns: a filter leaf over a list column is lowered to a one-bit scalar column on the device (k_list_leaf) that takes a free slot among
+    // the 64 scalar slots, from the top down, above `columns`.  They are cached by (list column, operator, constants), reference-counted by the compiled
+    // filters of the cache, at most INFX_ENGINE_MAX_DERIVED, least recently used first out among those no cached filter uses; whatever retires the compiled
+    // filters (a new or replaced column of either kind) drops them all.  Guarded by filterMu.
+    std::vector<filt::ListColumn> listCols;
+    struct DerivedCol { int lcol; std::string key; uint32_t slot; uint32_t refs; uint64_t lastUse; };
+    std::vector<DerivedCol> derived; uint64_t derivedTick = 0;
+    uint32_t llBuilt = 0, llLaunches = 0; uint64_t llBuiltAll = 0, llLaunchesAll = 0;      // infx_engine_last_list_leaf_stats: the last expression compiled; all compiles of the engine
+    void release_derived(const CompiledFilter& cf) {
+        for (auto& k : cf.derived) for (auto& D : derived) if (D.lcol == k.first && D.key == k.second && D.refs) { D.refs--; break; }
+    }
     // The cache is bounded (per-user expressions would grow it without limit): least recently used first, never an entry an install holds.  An evicted
     // expression is parsed and counted again on its next use.  Its device copy is parked with the retired ones (hipFree would wait for the whole device).
     std::list<std::string> filterLru; size_t filterCacheLimit = 4096;
@@ -323,6 +344,7 @@ struct infx_engine {
             auto f = filters.find(*it);
             if (f == filters.end() || f->second.pins) continue;
             if (f->second.dev) retiredFilters.push_back(f->second.dev);
+            release_derived(f->second);
             filters.erase(f); it = filterLru.erase(it);
         }
     }
@@ -2472,18 +2494,29 @@ static int32_t column_named(const infx_engine* e, const char* name) {
 // ---- Infiscript post-filter + facets (config 5): Query.Filter / Query.EnableFacets (SearchEngine.cs:298-316) ------------------------------
 // One non-indexed document field for all documents (DocumentFields / Field.Value), by internal id: kind 1 int64, 2 double, 3 UTF-8 strings
 // (arena + n+1 offsets).  facetable = Field.Facetable.  After infx_engine_index_documents.
+static int32_t install_column(infx_engine* e, size_t at, filt::Column&& c);
+static void drop_list_column_named(infx_engine* e, const char* name);
 int32_t infx_engine_add_column(infx_engine* e, const char* name, int32_t kind, int32_t facetable, int64_t n, const int64_t* vi, const double* vd,
                                const char* arena, const uint64_t* offs) {
     if (!e || !name || n < 0 || (kind == 1 && !vi) || (kind == 2 && !vd) || (kind == 3 && (!arena || !offs)) || kind < 1 || kind > 3) return efail(INFX_EINVAL, "bad column arguments");
     if (!e->indexed || n != e->ix.N) return efail(INFX_EINVAL, "a column needs one value per indexed document");
     // a name the engine already holds: the column is REPLACED in its slot (new values, possibly of another kind); everything derived from it goes
+    if (!name[0]) return efail(INFX_EINVAL, "a column needs a name");
     size_t at = e->columns.size();
     for (size_t i = 0; i < e->columns.size(); i++) if (e->columns[i].name == name) at = i;
+    if (at == e->columns.size()) for (size_t i = 0; i < e->columns.size(); i++) if (e->columns[i].name.empty()) { at = i; break; }      // the slot a list column took a scalar column's name from
     if (at == e->columns.size() && e->columns.size() >= 64) return efail(INFX_ECAPACITY, "too many columns");
     filt::Column c; c.name = name; c.facetable = facetable != 0;
     if (kind == 1) filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 1; b.i = vi[d]; return b; }, (long long)0);
     else if (kind == 2) filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 2; b.d = vd[d]; return b; }, (uint64_t)0);
     else filt::encode_column(c, (size_t)n, [&](size_t d) { filt::Boxed b; b.kind = 3; b.s.assign(arena + offs[d], arena + offs[d + 1]); return b; }, std::string());
+    { int32_t rc = install_column(e, at, std::move(c)); if (rc) return rc; }
+    drop_list_column_named(e, name);      // one namespace: a list column of this name is replaced by the scalar column
+    return INFX_OK;
+}
+// Puts column c into slot `at` (a new slot at the end, or a replaced one: everything derived from the old column goes) and invalidates what was compiled or counted
+static int32_t install_column(infx_engine* e, size_t at, filt::Column&& c) {
+    const size_t n = c.codes.size();
     if (e->dev) {
         int32_t rc = infx_upload_column(e->dev, (uint32_t)at, (uint32_t)n, c.codes.data(), (uint32_t)c.dict.size());      // (a re-upload voids the column's sort rank on the device)
         if (rc) { g_eerr = infx_last_error(); return rc; }
@@ -2515,6 +2548,167 @@ int32_t infx_engine_column_value(infx_engine* e, int32_t col, uint32_t code, cha
     if (out && cap > 0) snprintf(out, (size_t)cap, "%s", t.c_str());
     return (int32_t)t.size();
 }
+// ---- list columns: a field that holds a list of values per document (Field.IsArray), in filters and filtered / whole-corpus facets ---------------------
+static int32_t list_column_named(const infx_engine* e, const char* name) {
+    for (size_t c = 0; c < e->listCols.size(); c++) if (e->listCols[c].live() && e->listCols[c].name == name) return (int32_t)c;
+    return -1;
+}
+static void drop_list_column_named(infx_engine* e, const char* name) {
+    const int32_t lc = list_column_named(e, name);
+    if (lc < 0) return;
+    { std::lock_guard<std::mutex> lk(e->filterMu); e->listCols[lc] = filt::ListColumn(); }
+    if (e->dev) infx_upload_list_column(e->dev, (uint32_t)lc, 0, nullptr, nullptr, 0);
+}
+// the facetable list columns: the first INFX_ENGINE_MAX_LIST_FACETS of them
+static std::vector<uint32_t> list_facet_columns(const infx_engine* e) {
+    std::vector<uint32_t> cols;
+    for (size_t c = 0; c < e->listCols.size() && cols.size() < INFX_ENGINE_MAX_LIST_FACETS; c++) if (e->listCols[c].live() && e->listCols[c].facetable) cols.push_back((uint32_t)c);
+    return cols;
+}
+// One list of values per indexed document, by internal id: doc_offs[n + 1] (ascending from 0) delimits document d's elements in vals_i / vals_d / the
+// strings arena + offs (element j: arena[offs[j] .. offs[j + 1])).  See include/infidex_engine.h.
+int32_t infx_engine_add_list_column(infx_engine* e, const char* name, int32_t kind, int32_t facetable, int64_t n, const uint64_t* doc_offs, const int64_t* vi, const double* vd,
+                                    const char* arena, const uint64_t* offs) {
+    if (!e || !name || !name[0] || n < 0 || !doc_offs || kind < 1 || kind > 3) return efail(INFX_EINVAL, "bad list-column arguments");
+    if (e->nranks > 1) return efail(INFX_EUNSUPPORTED, "list columns need an engine that is not sharded");
+    if (!e->indexed || n != e->ix.N) return efail(INFX_EINVAL, "a list column needs one list per indexed document");
+    if (doc_offs[0] != 0) return efail(INFX_EINVAL, "a list column's offsets start at 0");
+    for (int64_t d = 0; d < n; d++) if (doc_offs[d + 1] < doc_offs[d]) return efail(INFX_EINVAL, "a list column's offsets must ascend");
+    const uint64_t total = doc_offs[n];
+    if (total > 0xFFFFFFFFull) return efail(INFX_ECAPACITY, "a list column holds fewer than 2^32 elements");
+    if (total && ((kind == 1 && !vi) || (kind == 2 && !vd) || (kind == 3 && (!arena || !offs)))) return efail(INFX_EINVAL, "bad list-column arguments");
+    int32_t at = list_column_named(e, name);
+    if (at < 0) {
+        size_t live = 0, facets = 0; for (auto& L : e->listCols) { live += L.live(); facets += L.live() && L.facetable; }
+        if (live >= INFX_ENGINE_MAX_LIST_COLS) return efail(INFX_ECAPACITY, "more than INFX_ENGINE_MAX_LIST_COLS (8) list columns");
+        if (facetable && facets >= INFX_ENGINE_MAX_LIST_FACETS) return efail(INFX_ECAPACITY, "more than INFX_ENGINE_MAX_LIST_FACETS (4) facetable list columns");
+        for (size_t c = 0; c < e->listCols.size() && at < 0; c++) if (!e->listCols[c].live()) at = (int32_t)c;
+        if (at < 0) { std::lock_guard<std::mutex> lk(e->filterMu); at = (int32_t)e->listCols.size(); e->listCols.emplace_back(); }
+    } else if (facetable && !e->listCols[at].facetable) {
+        size_t facets = 0; for (auto& L : e->listCols) facets += L.live() && L.facetable;
+        if (facets >= INFX_ENGINE_MAX_LIST_FACETS) return efail(INFX_ECAPACITY, "more than INFX_ENGINE_MAX_LIST_FACETS (4) facetable list columns");
+    }
+    filt::ListColumn c; c.name = name; c.facetable = facetable != 0; c.kind = kind;
+    if (kind == 1) filt::encode_column(c.dict, (size_t)total, [&](size_t j) { filt::Boxed b; b.kind = 1; b.i = vi[j]; return b; }, (long long)0);
+    else if (kind == 2) filt::encode_column(c.dict, (size_t)total, [&](size_t j) { filt::Boxed b; b.kind = 2; b.d = vd[j]; return b; }, (uint64_t)0);
+    else filt::encode_column(c.dict, (size_t)total, [&](size_t j) { filt::Boxed b; b.kind = 3; b.s.assign(arena + offs[j], arena + offs[j + 1]); return b; }, std::string());
+    c.off.resize((size_t)n + 1); for (int64_t d = 0; d <= n; d++) c.off[(size_t)d] = (uint32_t)doc_offs[d];
+    if (e->dev) {
+        int32_t rc = infx_upload_list_column(e->dev, (uint32_t)at, (uint32_t)n, c.off.data(), c.dict.codes.data(), (uint32_t)c.dict.dict.size());
+        if (rc) { g_eerr = infx_last_error(); return rc; }
+    }
+    { std::lock_guard<std::mutex> lk(e->filterMu); e->listCols[(size_t)at] = std::move(c); }
+    // one namespace: a scalar column of this name is replaced.  Its slot stays (the slots above it keep their indices) as a nameless column of one null
+    // value that no field name reaches, until infx_engine_add_column reuses it.
+    const int32_t sc = column_named(e, name);
+    if (sc >= 0) {
+        filt::Column t; t.dict.push_back(filt::Boxed()); t.text.push_back(std::string()); t.rank.push_back(0u); t.codes.assign((size_t)n, 0u);
+        return install_column(e, (size_t)sc, std::move(t));      // (invalidates, as below)
+    }
+    e->invalidate_filter_counts();
+    e->maskEpoch++;
+    e->retire_filters();      // with them go the derived leaf columns
+    return INFX_OK;
+}
+int32_t infx_engine_list_column_count(infx_engine* e) { return e ? (int32_t)e->listCols.size() : -1; }
+// list column slot lcol (a free slot has an empty name): its name, whether it is facetable, its number of distinct element values, the kind of its elements
+int32_t infx_engine_list_column_info(infx_engine* e, int32_t lcol, char* name, int32_t cap, int32_t* facetable, int32_t* num_values, int32_t* kind) {
+    if (!e || lcol < 0 || lcol >= (int32_t)e->listCols.size()) return INFX_EINVAL;
+    const filt::ListColumn& c = e->listCols[(size_t)lcol];
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", c.name.c_str());
+    if (facetable) *facetable = c.facetable ? 1 : 0; if (num_values) *num_values = (int32_t)c.dict.dict.size(); if (kind) *kind = c.kind;
+    return INFX_OK;
+}
+int32_t infx_engine_list_column_value(infx_engine* e, int32_t lcol, uint32_t code, char* out, int32_t cap) {      // ToString() of a distinct element value
+    if (!e || lcol < 0 || lcol >= (int32_t)e->listCols.size() || code >= e->listCols[(size_t)lcol].dict.text.size()) return -1;
+    return copy_message(e->listCols[(size_t)lcol].dict.text[code], out, cap);
+}
+// the stored list of one document: up to cap element codes into codes; returns the list's length, -1 on error
+int64_t infx_engine_list_column_document(infx_engine* e, int32_t lcol, int64_t document_index, uint32_t* codes, int64_t cap) {
+    if (!e || lcol < 0 || lcol >= (int32_t)e->listCols.size() || !e->listCols[(size_t)lcol].live()) { efail(INFX_EINVAL, "no such list column"); return -1; }
+    const filt::ListColumn& c = e->listCols[(size_t)lcol];
+    if (document_index < 0 || document_index >= (int64_t)c.docs()) { efail(INFX_EINVAL, "no document of this index"); return -1; }
+    const uint32_t b = c.off[(size_t)document_index], m = c.off[(size_t)document_index + 1] - b;
+    for (uint32_t j = 0; j < m && (int64_t)j < cap && codes; j++) codes[j] = c.dict.codes[b + j];
+    return (int64_t)m;
+}
+int32_t infx_engine_last_list_leaf_stats(infx_engine* e, uint32_t* built, uint32_t* launches) {
+    if (!e) return efail(INFX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    return put_stats({{built, e->llBuilt}, {launches, e->llLaunches}});
+}
+int32_t infx_engine_list_leaf_totals(infx_engine* e, uint64_t* built, uint64_t* launches) {
+    if (!e) return efail(INFX_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(e->filterMu);
+    if (built) *built = e->llBuiltAll; if (launches) *launches = e->llLaunchesAll;
+    return INFX_OK;
+}
+// The leaves of program P over list columns, lowered: for each such leaf its derived column's slot in slotOf[leaf index] (leaves over other fields: -1), the
+// missing derived columns built — one k_list_leaf launch per list column — and cached, and the (list column, key) references of the program in refs.
+// INFX_ECAPACITY when no cache entry or no scalar slot is free: the expression is refused alone.  Caller holds e->filterMu.
+static int32_t lower_list_leaves(infx_engine* e, const filt::Program& P, std::vector<int>& slotOf, std::vector<std::pair<int, std::string>>& refs) {
+    slotOf.assign(P.leaves.size(), -1); refs.clear();
+    struct Pending { int lcol; std::string key; std::vector<uint32_t> words; bool empty; uint32_t slot; };
+    std::vector<Pending> pend;
+    auto undo = [&](int32_t rc, const char* msg) {      // the entries this compile added are not built: they go
+        for (auto& p : pend) for (size_t i = 0; i < e->derived.size(); i++) if (e->derived[i].lcol == p.lcol && e->derived[i].key == p.key) { e->derived.erase(e->derived.begin() + (long)i); break; }
+        return efail(rc, msg);
+    };
+    // every derived column the expression reads is kept while room is made for the ones it is missing
+    std::vector<int> lcOf(P.leaves.size(), -1); std::vector<std::string> keyOf(P.leaves.size());
+    for (size_t l = 0; l < P.leaves.size(); l++) {
+        const filt::Leaf& L = P.leaves[l];
+        if (column_named(e, L.field.c_str()) >= 0) continue;
+        lcOf[l] = list_column_named(e, L.field.c_str());
+        if (lcOf[l] >= 0) keyOf[l] = filt::list_leaf_key(L);
+    }
+    for (size_t l = 0; l < P.leaves.size(); l++) {
+        const filt::Leaf& L = P.leaves[l];
+        const int32_t lc = lcOf[l];
+        if (lc < 0) continue;
+        const std::string& key = keyOf[l];
+        const uint64_t tick = ++e->derivedTick;
+        infx_engine::DerivedCol* D = nullptr;
+        for (auto& x : e->derived) if (x.lcol == lc && x.key == key) D = &x;
+        if (!D) {
+            auto pinned = [&](const infx_engine::DerivedCol& x) {      // in use by a cached filter, or by this very expression
+                if (x.refs) return true;
+                for (size_t j = 0; j < lcOf.size(); j++) if (lcOf[j] == x.lcol && keyOf[j] == x.key) return true;
+                return false;
+            };
+            if (e->derived.size() >= INFX_ENGINE_MAX_DERIVED) {
+                int victim = -1;
+                for (size_t i = 0; i < e->derived.size(); i++) if (!pinned(e->derived[i]) && (victim < 0 || e->derived[i].lastUse < e->derived[(size_t)victim].lastUse)) victim = (int)i;
+                if (victim < 0) return undo(INFX_ECAPACITY, "no derived leaf column is free: INFX_ENGINE_MAX_DERIVED (16) list-column leaves are in use by cached filters");
+                e->derived.erase(e->derived.begin() + victim);
+            }
+            int slot = -1;
+            for (int c = 63; c >= (int)e->columns.size() && slot < 0; c--) { bool used = false; for (auto& x : e->derived) used |= x.slot == (uint32_t)c; if (!used) slot = c; }
+            if (slot < 0) return undo(INFX_ECAPACITY, "no scalar column slot is free for a list-column leaf");
+            Pending p; p.lcol = lc; p.key = key; p.slot = (uint32_t)slot;
+            p.empty = filt::list_leaf_table(L, e->listCols[(size_t)lc], p.words);
+            pend.push_back(std::move(p));
+            e->derived.push_back(infx_engine::DerivedCol{lc, key, (uint32_t)slot, 0u, tick});
+            D = &e->derived.back();
+        }
+        D->lastUse = tick;
+        slotOf[l] = (int)D->slot;
+        bool seen = false; for (auto& r : refs) seen |= r.first == lc && r.second == key;
+        if (!seen) refs.push_back({lc, key});
+    }
+    e->llBuilt = 0; e->llLaunches = 0;
+    if (e->dev) for (size_t c = 0; c < e->listCols.size(); c++) {
+        std::vector<std::vector<uint32_t>> tables; std::vector<uint32_t> slots; uint32_t emptyBits = 0;
+        for (auto& p : pend) if (p.lcol == (int)c) { if (p.empty) emptyBits |= 1u << tables.size(); tables.push_back(p.words); slots.push_back(p.slot); }
+        if (tables.empty()) continue;
+        std::vector<uint32_t> maps; filt::list_leaf_maps(tables, (e->listCols[c].dict.dict.size() + 31) / 32, maps);
+        if (maps.empty()) maps.push_back(0u);
+        const int32_t rc = infx_list_leaf_build(e->dev, (uint32_t)c, (uint32_t)tables.size(), slots.data(), maps.data(), emptyBits);
+        if (rc) { const std::string m = infx_last_error(); return undo(rc, m.c_str()); }
+        e->llBuilt += (uint32_t)tables.size(); e->llLaunches++; e->llBuiltAll += tables.size(); e->llLaunchesAll++;
+    }
+    return INFX_OK;
+}
 // The compiled program of an Infiscript expression, from the engine's cache (parsed on first use; its device copy made on the first use that needs it:
 // dev = true).  Caller holds e->filterMu.  Marks the entry most recently used; may evict others.
 static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter** out, bool dev) {
@@ -2525,8 +2719,16 @@ static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter**
         catch (const filt::Unsupported& x) { return efail(INFX_EUNSUPPORTED, x.what()); }
         catch (const filt::SyntaxError& x) { return efail(INFX_EINVAL, std::string("filter syntax error: ") + x.what()); }
         CompiledFilter cf; std::vector<uint32_t> w;
+        std::vector<int> derivedSlot;
+        { int32_t rc = lower_list_leaves(e, P, derivedSlot, cf.derived); if (rc) return rc; }
         for (auto& in : P.code) cf.ops.push_back(infx_filter_op{in.op, in.arg});
         for (auto& L : P.leaves) {
+            const int ds = derivedSlot[(size_t)(&L - P.leaves.data())];
+            if (ds >= 0) {      // a list-column leaf: an ordinary leaf over its derived one-bit column, true for code 1
+                cf.leaves.push_back(infx_filter_leaf{(uint32_t)ds, (uint32_t)cf.tables.size(), 2u, 0});
+                cf.tables.push_back(2u);
+                continue;
+            }
             int ci = -1; for (size_t c = 0; c < e->columns.size(); c++) if (e->columns[c].name == L.field) ci = (int)c;      // field names are case sensitive (Dictionary<string, Field>)
             filt::leaf_table(L, ci >= 0 ? &e->columns[ci] : nullptr, w);
             cf.leaves.push_back(infx_filter_leaf{ci >= 0 ? (uint32_t)ci : 0xFFFFFFFFu, (uint32_t)cf.tables.size(), ci >= 0 ? (uint32_t)e->columns[ci].dict.size() : 1u, 0});
@@ -2538,6 +2740,7 @@ static int32_t compile_filter(infx_engine* e, const char* expr, CompiledFilter**
             int32_t rc = infx_filter_check(e->dev, (uint32_t)cf.ops.size(), cf.ops.data(), (uint32_t)cf.leaves.size(), cf.leaves.data(), (uint32_t)cf.tables.size());
             if (rc) { g_eerr = infx_last_error(); return rc; }
         }
+        for (auto& k : cf.derived) for (auto& D : e->derived) if (D.lcol == k.first && D.key == k.second) D.refs++;
         e->filterLru.push_front(expr);
         it = e->filters.emplace(expr, std::move(cf)).first;
         it->second.lru = e->filterLru.begin();
@@ -2626,10 +2829,18 @@ int32_t infx_engine_facets_all(infx_session* S, int32_t* ncols) {
     infx_engine* e = S->e;
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the facet counts run on the device");
     if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
-    S->facAllCols.clear(); S->facAll.clear();
+    S->facAllCols.clear(); S->facAll.clear(); S->facAllListCols.clear(); S->facAllList.clear();
     size_t total = 0;
     S->facAllCols = facet_columns(e, &total);
     if (ncols) *ncols = (int32_t)S->facAllCols.size();
+    // the facetable list columns: element occurrences among the documents that are not Deleted, one k_list_facets launch per column
+    for (uint32_t lc : list_facet_columns(e)) {
+        const filt::ListColumn& C = e->listCols[lc];
+        std::vector<uint32_t> cnt(std::max<size_t>(C.dict.dict.size(), 1)); const uint8_t* all = nullptr;
+        int32_t rc = infx_list_facets(S->stream, lc, 1, &all, cnt.data());
+        if (rc) { g_eerr = infx_last_error(); S->facAllListCols.clear(); S->facAllList.clear(); return rc; }
+        S->facAllListCols.push_back(lc); S->facAllList.push_back(facet_list(C.dict, cnt.data()));
+    }
     if (S->facAllCols.empty()) return INFX_OK;
     std::vector<uint32_t> counts(std::max<size_t>(total, 1));
     int32_t rc = infx_facets_all(S->stream, (uint32_t)S->facAllCols.size(), S->facAllCols.data(), counts.data());
@@ -2648,6 +2859,15 @@ int32_t infx_engine_facets_all_column(infx_session* S, uint32_t k, int32_t* col,
     if (!S || k >= S->facAll.size() || (cap > 0 && (!codes || !counts))) return -1;
     if (col) *col = (int32_t)S->facAllCols[k];
     return copy_pairs(S->facAll[k], codes, counts, cap);
+}
+
+// The facetable list columns of the session's last infx_engine_facets_all (their number; -1: no session), and the k-th of them as infx_engine_facets_all_column
+// gives a scalar column: list column index in *lcol, (element code, occurrences) pairs.
+int32_t infx_engine_facets_all_list_column_count(infx_session* S) { return S ? (int32_t)S->facAllList.size() : -1; }
+int32_t infx_engine_facets_all_list_column(infx_session* S, uint32_t k, int32_t* lcol, uint32_t* codes, uint32_t* counts, int32_t cap) {
+    if (!S || k >= S->facAllList.size() || (cap > 0 && (!codes || !counts))) return -1;
+    if (lcol) *lcol = (int32_t)S->facAllListCols[k];
+    return copy_pairs(S->facAllList[k], codes, counts, cap);
 }
 
 // ---- Query.Boosts / Query.SortBy (SearchEngine.cs:355-359): ResultProcessor.ApplyBoosts / ApplySort on the device after the post-filter -------------
@@ -2691,6 +2911,7 @@ static int32_t sort_rank_on_device(infx_engine* e, uint32_t col, std::vector<uin
 // the column of a SortBy field (0xFFFFFFFF: no such field), its sort rank on the device.  Caller holds e->filterMu.
 static int32_t sort_column(infx_engine* e, const char* field, uint32_t* out) {
     *out = (uint32_t)column_named(e, field);
+    if (*out == 0xFFFFFFFFu && list_column_named(e, field) >= 0) return efail(INFX_EINVAL, std::string("sort_by: no scalar field named '") + field + "': it is a list column");
     return *out != 0xFFFFFFFFu ? sort_rank_on_device(e, *out) : INFX_OK;
 }
 int32_t infx_engine_set_sort(infx_session* S, const char* field, int32_t ascending) {
@@ -3214,8 +3435,15 @@ int32_t MaskCall::intern(uint32_t i, const char* expr) {
     return INFX_OK;
 }
 int32_t MaskCall::failed(int32_t rc) {
-    g_eerr = infx_last_error(); unstage_prefilters(S, built); built.clear();
+    g_eerr = infx_last_error(); unstage_prefilters(S, built); built.clear(); release();
     return rc;
+}
+void MaskCall::release() {
+    if (pinned.empty()) return;
+    infx_engine* e = S->e;
+    if (locked) { pin_filters(e, pinned, -1); e->evict_filters(); }
+    else { std::lock_guard<std::mutex> lk(e->filterMu); pin_filters(e, pinned, -1); e->evict_filters(); }
+    pinned.clear();
 }
 // The masks of exprs (distinct, at most INFX_MAX_PREFILTERS) in the session's cache: masks[k] = the device flags of exprs[k]'s slot; the ones that have to be built
 // are staged on the stream as ONE build (infx_filter_masks) and listed in `built` — their counts land in S->preCountBuf, in that order, when the stream is next
@@ -3227,11 +3455,12 @@ int32_t MaskCall::acquire() {
     const uint64_t ep = e->maskEpoch.load(); const uint64_t tick = ++S->preTick;
     std::vector<int> slots(exprs.size(), -1);
     masks.assign(exprs.size(), nullptr); built.clear();
-    auto bail = [&](int32_t rc) { unstage_prefilters(S, built); built.clear(); return rc; };
+    auto bail = [&](int32_t rc) { unstage_prefilters(S, built); built.clear(); release(); return rc; };
     for (size_t k = 0; k < exprs.size(); k++)
         for (int i = 0; i < INFX_MAX_PREFILTERS; i++) { PreMask& M = S->preMask[i]; if (M.valid && M.epoch == ep && M.expr == exprs[k]) { slots[k] = i; M.lastUse = tick; S->preReused++; break; } }
     std::vector<infx_filter_prog> progs; std::vector<uint8_t*> ptrs;
     std::lock_guard<std::mutex> lk(e->filterMu);
+    struct Held { bool& f; explicit Held(bool& x) : f(x) { f = true; } ~Held() { f = false; } } held(locked);
     for (size_t k = 0; k < exprs.size(); k++) {
         if (slots[k] >= 0) { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)slots[k], &masks[k]); if (rc) return failed(rc); continue; }
         int best = -1;      // a slot of an earlier epoch or an empty one first, else the least recently used that this batch does not use
@@ -3246,6 +3475,7 @@ int32_t MaskCall::acquire() {
         if (best < 0) return bail(efail(INFX_ECAPACITY, "more than INFX_MAX_PREFILTERS (16) distinct pre-filters in one batch"));
         CompiledFilter* cf = nullptr;
         { int32_t rc = compile_filter(e, exprs[k].c_str(), &cf, false); if (rc) return bail(rc); }
+        pin_filters(e, {exprs[k]}, +1); pinned.push_back(exprs[k]);
         { int32_t rc = infx_stream_mask_slot(S->stream, (uint32_t)best, &masks[k]); if (rc) return failed(rc); }
         PreMask& M = S->preMask[best]; M.expr = exprs[k]; M.epoch = ep; M.lastUse = tick; M.count = 0; M.valid = true;
         built.push_back(best); progs.push_back(prog_of(*cf)); ptrs.push_back(masks[k]);
@@ -3280,6 +3510,7 @@ static int32_t stage_prefilters(infx_session* S, uint32_t nq, std::vector<infx_f
 }
 // After the call: the counts of the masks it built have landed; what it built and reused; each pre-filtered query's count
 void MaskCall::done(uint32_t nq) {
+    release();
     for (size_t k = 0; k < built.size(); k++) S->preMask[built[k]].count = S->preCountBuf[k];
     if (!built.empty()) { uint32_t b = 0, l = 0; infx_last_filter_mask_stats(S->stream, &b, &l); S->preLaunches = l; }
     if (use) *use = MaskUse{S->preBuilt, S->preReused};
@@ -3328,16 +3559,21 @@ int32_t infx_engine_prefilter_mask(infx_session* S, const char* expr, uint8_t* o
 int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* const* exprs, int32_t* out_status) {
     if (!S || (k && !exprs)) return efail(INFX_EINVAL, "null argument");
     infx_engine* e = S->e;
-    S->ff.clear(); S->ffCols.clear(); S->ffCounted = S->ffCached = S->ffLaunches = 0;
+    S->ff.clear(); S->ffCols.clear(); S->ffListCols.clear(); S->ffCounted = S->ffCached = S->ffLaunches = 0;
     if (!e->dev || !S->stream) return efail(INFX_EHIP, "no GPU: the filtered facet counts run on the device");
     if (!e->indexed) return efail(INFX_EINVAL, "facets before index_documents");
     S->ff.assign(k, FfAnswer());
     size_t total = 0;
     S->ffCols = facet_columns(e, &total);
+    S->ffListCols = list_facet_columns(e);
     const uint64_t ep = e->maskEpoch.load();
     // the call's distinct expressions: from the cache, refused, or missing (compiled here; the programs are copied out of the filter cache, which other
     // sessions may evict from while the device counts)
     struct Missing { std::string expr; std::vector<infx_filter_op> ops; std::vector<infx_filter_leaf> leaves; std::vector<uint32_t> tables; };
+    // ... and their cache entries stay pinned until the device has counted: an entry holds the derived columns of its list-column leaves, whose slots a later
+    // compile (of this call or of another session) could otherwise hand to another leaf while a copy here still reads them
+    struct Held { infx_engine* e; std::vector<std::string> keys;
+                  ~Held() { if (keys.empty()) return; std::lock_guard<std::mutex> lk(e->filterMu); pin_filters(e, keys, -1); e->evict_filters(); } } held{e, {}};
     std::unordered_map<std::string, FfAnswer> answer; std::vector<Missing> miss;
     for (uint32_t i = 0; i < k; i++) {
         if (!exprs[i]) { S->ff[i].status = INFX_EINVAL; S->ff[i].err = "null expression"; continue; }
@@ -3353,7 +3589,7 @@ int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* con
             CompiledFilter* cf = nullptr;
             const int32_t rc = compile_filter(e, exprs[i], &cf, false);      // syntax error: INFX_EINVAL; MATCHES: INFX_EUNSUPPORTED
             if (rc) { A.status = rc; A.err = g_eerr; }
-            else miss.push_back(Missing{exprs[i], cf->ops, cf->leaves, cf->tables});
+            else { miss.push_back(Missing{exprs[i], cf->ops, cf->leaves, cf->tables}); pin_filters(e, {exprs[i]}, +1); held.keys.push_back(exprs[i]); }
         }
         answer.emplace(exprs[i], std::move(A));
     }
@@ -3364,13 +3600,35 @@ int32_t infx_engine_facets_filtered(infx_session* S, uint32_t k, const char* con
         for (uint32_t j = 0; j < kk; j++) progs[j] = prog_of(miss[m0 + j]);
         counts.resize(std::max<size_t>((size_t)kk * total, 1));
         int32_t rc = infx_facets_filtered(S->stream, kk, progs.data(), (uint32_t)S->ffCols.size(), S->ffCols.data(), counts.data(), totals.data());
-        if (rc) { g_eerr = infx_last_error(); S->ff.clear(); S->ffCols.clear(); return rc; }
+        if (rc) { g_eerr = infx_last_error(); S->ff.clear(); S->ffCols.clear(); S->ffListCols.clear(); return rc; }
         uint32_t np = 0, nl = 0; infx_last_facets_filtered_stats(S->stream, &np, &nl);
         S->ffCounted += kk; S->ffLaunches += nl;
+        // the facetable list columns: the accept sets are the session's pre-filter masks of these expressions (built through the 16-mask cache, or reused),
+        // one k_list_facets launch per column for all kk of them
+        std::vector<std::vector<uint32_t>> listCounts(S->ffListCols.size());
+        if (!S->ffListCols.empty()) {
+            auto bail0 = [&](int32_t r) { S->ff.clear(); S->ffCols.clear(); S->ffListCols.clear(); return r; };
+            const uint32_t pre[3] = {S->preBuilt, S->preReused, S->preLaunches};      // (the session's last_prefilter_stats are the last search's, not this call's)
+            auto bail = [&](int32_t r) { S->preBuilt = pre[0]; S->preReused = pre[1]; S->preLaunches = pre[2]; return bail0(r); };
+            MaskCall mc(S, kk);
+            for (uint32_t j = 0; j < kk; j++) mc.add(j, miss[m0 + j].expr);
+            { int32_t r = mc.acquire(); if (r) return bail(r); }
+            { int32_t r = infx_stream_wait(S->stream); if (r) return bail(mc.failed(r)); }      // builds what was staged
+            mc.done();
+            std::vector<const uint8_t*> masks(kk); for (uint32_t j = 0; j < kk; j++) masks[j] = mc.mask(j);
+            for (size_t c = 0; c < S->ffListCols.size(); c++) {
+                const filt::ListColumn& C = e->listCols[S->ffListCols[c]];
+                listCounts[c].assign(std::max<size_t>((size_t)kk * C.dict.dict.size(), 1), 0u);
+                int32_t r = infx_list_facets(S->stream, S->ffListCols[c], kk, masks.data(), listCounts[c].data());
+                if (r) { g_eerr = infx_last_error(); return bail(r); }
+            }
+            S->preBuilt = pre[0]; S->preReused = pre[1]; S->preLaunches = pre[2];
+        }
         for (uint32_t j = 0; j < kk; j++) {
             auto E = std::make_shared<FfEntry>(); E->epoch = ep; E->total = totals[j];
             size_t o = (size_t)j * total;
             for (uint32_t col : S->ffCols) { const filt::Column& C = e->columns[col]; E->lists.push_back(facet_list(C, counts.data() + o)); o += C.dict.size(); }
+            for (size_t c = 0; c < S->ffListCols.size(); c++) { const filt::Column& C = e->listCols[S->ffListCols[c]].dict; E->listLists.push_back(facet_list(C, listCounts[c].data() + (size_t)j * C.dict.size())); }
             answer[miss[m0 + j].expr].r = E;
             std::lock_guard<std::mutex> lk(e->ffMu);
             auto it = e->ffCache.find(miss[m0 + j].expr);
@@ -3391,6 +3649,13 @@ int32_t infx_engine_facets_filtered_column(infx_session* S, uint32_t which, uint
     if (!S || which >= S->ff.size() || !S->ff[which].r || k >= S->ff[which].r->lists.size() || k >= S->ffCols.size() || (cap > 0 && (!codes || !counts))) return -1;
     if (col) *col = (int32_t)S->ffCols[k];
     return copy_pairs(S->ff[which].r->lists[k], codes, counts, cap);
+}
+// the facetable list columns of the session's last infx_engine_facets_filtered, and expression `which`'s k-th: list column index in *lcol, (element code, occurrences)
+int32_t infx_engine_facets_filtered_list_column_count(infx_session* S) { return S ? (int32_t)S->ffListCols.size() : -1; }
+int32_t infx_engine_facets_filtered_list_column(infx_session* S, uint32_t which, uint32_t k, int32_t* lcol, uint32_t* codes, uint32_t* counts, int32_t cap) {
+    if (!S || which >= S->ff.size() || !S->ff[which].r || k >= S->ff[which].r->listLists.size() || k >= S->ffListCols.size() || (cap > 0 && (!codes || !counts))) return -1;
+    if (lcol) *lcol = (int32_t)S->ffListCols[k];
+    return copy_pairs(S->ff[which].r->listLists[k], codes, counts, cap);
 }
 // the live documents expression `which` accepts (0 for a refused one, whose status is returned)
 int32_t infx_engine_facets_filtered_total(infx_session* S, uint32_t which, uint32_t* total) {

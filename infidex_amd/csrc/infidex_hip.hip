@@ -102,6 +102,9 @@ struct infx_index {
     const uint32_t* colTie[FILT_MAXCOL] = {}; uint32_t colTieCap[FILT_MAXCOL] = {}; bool colTieOk[FILT_MAXCOL] = {};        // facet tie order of their codes (infx_upload_group_rank, for infx_top_groups); a column re-upload voids it
     // raw values of their codes with the scale field_stats sums them at (infx_upload_column_values); a column re-upload voids them too
     const uint64_t* colBits[FILT_MAXCOL] = {}; uint32_t colBitsCap[FILT_MAXCOL] = {}; bool colBitsOk[FILT_MAXCOL] = {}; int32_t colKind[FILT_MAXCOL] = {}, colScale[FILT_MAXCOL] = {}; uint32_t colLimbs[FILT_MAXCOL] = {};
+    // list columns (infx_upload_list_column): the CSR pair of each, and the staging buffer of infx_list_leaf_build's leaf bitmaps
+    const uint32_t* listOff[INFX_MAX_LIST_COLS] = {}; const uint32_t* listCode[INFX_MAX_LIST_COLS] = {}; uint32_t listDocs[INFX_MAX_LIST_COLS] = {}, listValues[INFX_MAX_LIST_COLS] = {};
+    size_t listOffCap[INFX_MAX_LIST_COLS] = {}, listCodeCap[INFX_MAX_LIST_COLS] = {}; uint32_t* listMaps = nullptr; size_t listMapsCap = 0;
     std::vector<uint64_t> hPsOff;
     int rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;         // infx_set_shard_comm
@@ -263,6 +266,7 @@ __host__ __device__ static inline SelRule make_rule(const infx_query& Q, const u
 #include "filter.hip.inc"
 #include "browse.hip.inc"
 #include "facets_filtered.hip.inc"
+#include "list_columns.hip.inc"
 #include "listing.hip.inc"
 #include "ranges.hip.inc"
 #include "stats.hip.inc"
@@ -410,6 +414,7 @@ struct infx_stream {
     hipEvent_t evH0 = nullptr, evH1 = nullptr; bool timedHl = false;      // around k_highlight (created by the first batch that highlights)
     hipEvent_t evK0 = nullptr, evK1 = nullptr; bool timedClp = false;      // around k_collapse (created by the first batch that collapses): evF0 .. evK0 is k_finalize_win
     void* dFacAll = nullptr; size_t capFacAll = 0;              // infx_facets_all counters
+    void* dLfCnt = nullptr; size_t capLfCnt = 0;      // infx_list_facets: counters [k][num_values]
     void *dFfBlob = nullptr, *dFfCnt = nullptr; size_t capFfBlob = 0, capFfCnt = 0;      // infx_facets_filtered: the programs' blob; counters [k][sum of num_values] + totals [k]
     uint32_t lastFfProgs = 0, lastFfLaunches = 0;              // programs and k_facets_filtered launches of the last infx_facets_filtered
     SetKindState kind[SK_KINDS];                               // the set calls (infx_list_ordered .. infx_field_distinct): per kind its buffers, raw host copy and counters
@@ -1351,7 +1356,7 @@ void infx_stream_destroy(infx_stream* s) {
     void* ps[] = {s->dQueries, s->dTerms, s->dExtra, s->dRules, s->dHits, s->dHitCount, s->dBlockOut, s->dBlockOutHi, s->dQBytes, s->dUOffs, s->dUMem, s->dUCnt, s->dURange, s->dUBase, s->dUDocs, s->dCounts,
                   s->dCovQ, s->dCovC, s->dCovO, s->dCovF, s->arDoc, s->arScore, s->arCls, s->dCursor, s->dOverflow,
                   s->dFQ, s->dFLists, s->dFOwned, s->dFS1, s->dFMeta, s->dFQueries, s->dFKeys, s->dFScores, s->dFTies, s->dFCounts, s->dFFlags, s->dFErr, s->dFHitsAll, s->dFHcAll, s->dFPairs, s->arMask, s->dDir, s->dFDocs, s->dFacetCols, s->dFacCodes, s->dFacCounts, s->dFacN, s->dPostBlob, s->dQCount, s->dBrwBlob, s->dBrwWork, s->dFacAll, s->dRefTerms, s->dExactFlag, s->dExactStat, s->arExc, s->exCand, s->exOut, s->exChunks, s->exQueries, s->exTasks, s->exCounters, s->exContEnd, s->dExProf, s->dSelOrder,
-                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dClp, s->dHl};
+                  s->dNext, s->dPrior, s->shBlob, s->dAllBlobs, s->dAllNext, s->dChainState, s->dChainNeed, s->dHugeWs, s->dHugeCnt, s->dLWordOff, s->dLChars, s->dLMembers, s->dLCount, s->dDense, s->dSelG, s->dAccOrder, s->dFin, s->dMaskBlob, s->dMaskCnt, s->dQDel, s->dClp, s->dHl, s->dLfCnt};
     for (void* p : s->dMask) if (p) hipFree(p);
     for (const SetKindState& K : s->kind) { if (K.ws) hipFree(K.ws); if (K.out) hipFree(K.out); }
     for (void* p : ps) if (p) hipFree(p);
@@ -3288,6 +3293,97 @@ int32_t infx_last_facets_filtered_stats(infx_stream* s, uint32_t* programs, uint
     if (!s) return fail(INFX_EINVAL, "null argument%s");
     if (programs) *programs = s->lastFfProgs;
     if (launches) *launches = s->lastFfLaunches;
+    return INFX_OK;
+}
+// ---- list columns (list_columns.hip.inc) ----
+int32_t infx_upload_list_column(infx_index* ix, uint32_t lcol, uint32_t total_docs, const uint32_t* elem_off, const uint32_t* elem_codes, uint32_t num_values) {
+    if (!ix || lcol >= INFX_MAX_LIST_COLS || (total_docs && !elem_off)) return fail(INFX_EINVAL, "bad list-column arguments%s");
+    if (ix->nranks > 1) return fail(INFX_EUNSUPPORTED, "list columns need an index that is not sharded%s");
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());                      // exclusive call, as infx_upload_column
+    if (!total_docs) { ix->listDocs[lcol] = 0; ix->listValues[lcol] = 0; return INFX_OK; }      // dropped (its buffers are kept for the next upload)
+    if (ix->haveDocs && (uint64_t)total_docs != (uint64_t)ix->d.totalDocs) return fail(INFX_EINVAL, "a list column needs one list per document%s");
+    if (elem_off[0] != 0) return fail(INFX_EINVAL, "a list column's offsets start at 0%s");
+    for (uint32_t d = 0; d < total_docs; d++) if (elem_off[d + 1] < elem_off[d]) return fail(INFX_EINVAL, "a list column's offsets must ascend%s");
+    const size_t total = elem_off[total_docs];
+    if (total && !elem_codes) return fail(INFX_EINVAL, "bad list-column arguments%s");
+    for (size_t i = 0; i < total; i++) if (elem_codes[i] >= num_values) return fail(INFX_EINVAL, "a list column's element code is out of range%s");
+    uint32_t* dOff = const_cast<uint32_t*>(ix->listOff[lcol]); uint32_t* dCode = const_cast<uint32_t*>(ix->listCode[lcol]);
+    ix->listDocs[lcol] = 0;                              // (not uploaded while a step below can fail)
+    if (!dOff || ix->listOffCap[lcol] < (size_t)total_docs + 1) { HIPCHK(dalloc(ix, &dOff, (size_t)total_docs + 1)); ix->listOff[lcol] = dOff; ix->listOffCap[lcol] = (size_t)total_docs + 1; }
+    if (!dCode || ix->listCodeCap[lcol] < total) { HIPCHK(dalloc(ix, &dCode, total)); ix->listCode[lcol] = dCode; ix->listCodeCap[lcol] = std::max<size_t>(total, 1); }
+    HIPCHK(hipMemcpy(dOff, elem_off, ((size_t)total_docs + 1) * 4, hipMemcpyHostToDevice));
+    if (total) HIPCHK(hipMemcpy(dCode, elem_codes, total * 4, hipMemcpyHostToDevice));
+    ix->listDocs[lcol] = total_docs; ix->listValues[lcol] = num_values;
+    return INFX_OK;
+}
+int32_t infx_list_leaf_build(infx_index* ix, uint32_t lcol, uint32_t k, const uint32_t* slots, const uint32_t* maps, uint32_t empty_bits) {
+    if (!ix || lcol >= INFX_MAX_LIST_COLS || !k || k > INFX_LIST_LEAF_MAX || !slots || !maps) return fail(INFX_EINVAL, "bad list-leaf arguments%s");
+    const uint32_t n = ix->listDocs[lcol], nv = ix->listValues[lcol];
+    if (!n || !ix->haveDocs || (int64_t)n != (int64_t)ix->d.totalDocs) return fail(INFX_EINVAL, "the list column was not uploaded%s");
+    for (uint32_t i = 0; i < k; i++) {
+        if (slots[i] >= FILT_MAXCOL) return fail(INFX_EINVAL, "a derived column's slot is out of range%s");
+        for (uint32_t j = 0; j < i; j++) if (slots[j] == slots[i]) return fail(INFX_EINVAL, "two derived columns share a slot%s");
+    }
+    HIPCHK(enter_device(ix->cfg.device));
+    HIPCHK(hipDeviceSynchronize());                      // nothing in flight reads a slot that is rewritten
+    const size_t mapWords = (size_t)((nv + 31u) / 32u) * k;
+    if (!ix->listMaps || ix->listMapsCap < mapWords) { uint32_t* m = nullptr; HIPCHK(dalloc(ix, &m, mapWords)); ix->listMaps = m; ix->listMapsCap = std::max<size_t>(mapWords, 1); }
+    if (mapWords) HIPCHK(hipMemcpy(ix->listMaps, maps, mapWords * 4, hipMemcpyHostToDevice));
+    DevListLeaf A{}; A.elemOff = ix->listOff[lcol]; A.elemCode = ix->listCode[lcol]; A.maps = ix->listMaps;
+    A.K = k; A.nvals = nv; A.emptyBits = empty_bits; A.mapsInLds = mapWords <= INFX_LIST_LEAF_LDS_WORDS ? 1u : 0u; A.n = (int32_t)n;
+    // Other sessions read the column table (columns_cover, dev_columns) without a lock while this runs: a slot is never published half built.  A slot
+    // that already holds a buffer of n rows keeps its table entries and only gets new contents (its callers made sure no program in use reads it); a
+    // slot without one gets its buffer here and enters the table only after the kernel has completed, the pointer last.
+    uint32_t* fresh[INFX_LIST_LEAF_MAX] = {};
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t c = slots[i];
+        uint32_t* d = const_cast<uint32_t*>(ix->colCodes[c]);
+        if (!d || ix->colCap[c] < n || ix->colDocs[c] != n) { d = nullptr; HIPCHK(dalloc(ix, &d, (size_t)n + 1)); fresh[i] = d; }      // (a failure leaves the table as it was; the buffer is the index's to free)
+        A.out[i] = d;
+    }
+    const int grid = (int)std::min<int64_t>(LL_MAXGRID, ((int64_t)n + LL_DOCS - 1) / LL_DOCS);
+    k_list_leaf<<<grid, LL_THREADS, 0, 0>>>(A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t c = slots[i];
+        if (ix->colRankOk[c]) ix->colRankOk[c] = false; if (ix->colBitsOk[c]) ix->colBitsOk[c] = false; if (ix->colTieOk[c]) ix->colTieOk[c] = false;
+        if (ix->colValues[c] != 2) ix->colValues[c] = 2;
+        if (fresh[i]) {
+            ix->colCap[c] = n; ix->colDocs[c] = n;
+            __atomic_thread_fence(__ATOMIC_RELEASE);
+            ix->colCodes[c] = fresh[i];
+        }
+    }
+    return INFX_OK;
+}
+int32_t infx_list_facets(infx_stream* s, uint32_t lcol, uint32_t k, const uint8_t* const* masks, uint32_t* counts_out) {
+    if (!s || lcol >= INFX_MAX_LIST_COLS || !k || k > INFX_MAX_PREFILTERS || !masks) return fail(INFX_EINVAL, "bad list-facet arguments%s");
+    infx_index* ix = s->ix;
+    const uint32_t n = ix->listDocs[lcol], nv = ix->listValues[lcol];
+    if (!n || !ix->haveDocs || (int64_t)n != (int64_t)ix->d.totalDocs) return fail(INFX_EINVAL, "the list column was not uploaded%s");
+    if (nv && !counts_out) return fail(INFX_EINVAL, "bad list-facet arguments%s");
+    if ((uint64_t)nv * k > 0xFFFFFFFFull / 4) return fail(INFX_ECAPACITY, "the list column holds too many distinct values%s");
+    for (uint32_t i = 0; i < k; i++) if (masks[i]) { const int slot = mask_slot_of(s, masks[i]); if (slot < 0 || s->capMask[slot] < mask_bytes(ix)) return fail(INFX_EINVAL, "a list-facet mask is not a mask slot of this stream%s"); }
+    if (!nv) return INFX_OK;
+    HIPCHK(enter_device(ix->cfg.device));
+    { int32_t rc_ = pin_reset(s); if (rc_) return rc_; }
+    const size_t words = (size_t)k * nv;
+    GROW(s->dLfCnt, s->capLfCnt, words * 4);
+    HIPCHK(hipMemsetAsync(s->dLfCnt, 0, words * 4, s->st));
+    DevListFacets A{}; A.elemOff = ix->listOff[lcol]; A.elemCode = ix->listCode[lcol]; A.out = (uint32_t*)s->dLfCnt;
+    A.K = k; A.nvals = nv; A.inLds = words <= FFL_LDS_WORDS ? 1u : 0u; A.n = (int32_t)n;
+    for (uint32_t i = 0; i < k; i++) A.mask[i] = masks[i] ? masks[i] : ix->d.deleted;
+    const size_t lds = ((size_t)2 * LL_DOCS + 1 + (A.inLds ? words : 0)) * 4;
+    // counters beyond 16 KiB: fewer, longer-lived workgroups (each merges its counters once), two per CU's share of LDS
+    const int64_t maxGrid = lds > 16 * 1024 ? 512 : LL_MAXGRID;
+    const int grid = (int)std::min<int64_t>(maxGrid, ((int64_t)n + LL_DOCS - 1) / LL_DOCS);
+    HIPCHK(lds_limit((const void*)k_list_facets, ix->cfg.device, lds));
+    k_list_facets<<<grid, LL_THREADS, lds, s->st>>>(A);
+    HIPCHK(hipGetLastError());
+    DOWN(counts_out, s->dLfCnt, words * 4);
+    SYNC();
     return INFX_OK;
 }
 // ---- requests over document sets: a mask (null: every live document) and a column read through its sort rank ----

@@ -717,6 +717,66 @@ class SearchEngine:
             arena = b"".join(bs) + b"\0"
             self._check(self.L.infx_engine_add_column(self.h, name.encode(), 3, int(facetable), C.c_int64(n), None, None, C.c_char_p(arena), _p(offs, C.c_uint64)))
 
+    def set_list_column(self, name, lists, facetable=False):
+        """A field that holds a LIST of values per document (a film's genres, a product's tags): one sequence per indexed document, in indexing order, possibly
+        empty; all elements of a column are int, or all float, or all str.  Lists are kept as given (order and duplicates).  A filter leaf over the field
+        holds for a document when it holds for at least one element — for an empty list, when it holds for a null value: `tags IS NULL` (and `<`, `<=`: a null is below every constant) accepts the
+        empty lists, and `NOT tags = 'sale'` / `tags != 'sale'` mean "no element equals sale".  A facetable list column appears in facets_of_all_documents
+        and facets_of_documents (and Query.pre_filter_facets), a value's count being the number of its element occurrences; not in Result.facets.  Shares
+        one namespace with set_column: the newer column of a name replaces the older, of either kind.  At most 8 list columns, 4 of them facetable."""
+        n = int(self.index_stats()["docs"]) if self.h else 0
+        lists = [list(x) for x in lists]
+        if len(lists) != n:
+            raise InfidexError(1, "a list column needs one list per indexed document")
+        flat = [x for l in lists for x in l]
+        kinds = {1 if isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) else 2 if isinstance(x, (float, np.floating)) else 3 if isinstance(x, str) else 0 for x in flat}
+        if len(kinds) > 1 or 0 in kinds:
+            raise InfidexError(1, "the elements of a list column are all int, or all float, or all str")
+        kind = kinds.pop() if kinds else 3
+        doc_offs = np.zeros(n + 1, np.uint64); doc_offs[1:] = np.cumsum([len(l) for l in lists], dtype=np.uint64)
+        vi = vd = arena = offs = None
+        if kind == 1:
+            vi = np.ascontiguousarray(flat, np.int64) if flat else np.zeros(1, np.int64)
+        elif kind == 2:
+            vd = np.ascontiguousarray(flat, np.float64)
+        else:
+            bs = [x.encode() for x in flat]
+            offs = np.zeros(len(bs) + 1, np.uint64); offs[1:] = np.cumsum([len(b) for b in bs], dtype=np.uint64)
+            arena = b"".join(bs) + b"\0"
+        self._check(self.L.infx_engine_add_list_column(self.h, name.encode(), kind, int(facetable), C.c_int64(n), _p(doc_offs, C.c_uint64),
+                                                       _p(vi, C.c_int64) if vi is not None else None, _p(vd, C.c_double) if vd is not None else None,
+                                                       C.c_char_p(arena) if arena is not None else None, _p(offs, C.c_uint64) if offs is not None else None))
+
+    def list_column(self, name, document_index: int) -> list:
+        """The stored list of one document (internal index) in list column `name`, as it was given: ints, floats or strs."""
+        lcol, kind = _list_column_index(self, name)
+        if lcol < 0:
+            raise InfidexError(1, "no list column named %r" % (name,))
+        fn = self.L.infx_engine_list_column_document; fn.restype = C.c_int64
+        m = fn(self.h, lcol, C.c_int64(int(document_index)), None, C.c_int64(0))
+        if m < 0:
+            self._check(1)
+        codes = np.zeros(max(int(m), 1), np.uint32)
+        if fn(self.h, lcol, C.c_int64(int(document_index)), _p(codes, C.c_uint32), C.c_int64(int(m))) != m:
+            self._check(1)
+        conv = int if kind == 1 else float if kind == 2 else str
+        return [conv(_list_column_value(self, lcol, int(c))) for c in codes[:m]]
+
+    def last_list_leaf_stats(self):
+        """(derived leaf columns built, k_list_leaf launches) of the last expression the engine compiled: the list-column leaves of one expression that the
+        engine had not cached are lowered in one launch per list column.  An expression taken from the filter cache compiles nothing and leaves the figures
+        as they are: list_leaf_totals() shows that nothing was built."""
+        b = C.c_uint32(0); l = C.c_uint32(0)
+        self._check(self.L.infx_engine_last_list_leaf_stats(self.h, C.byref(b), C.byref(l)))
+        return int(b.value), int(l.value)
+
+    def list_leaf_totals(self):
+        """(derived leaf columns built, k_list_leaf launches) summed over every filter the engine has compiled: a call that leaves both as they were
+        launched nothing for list-column leaves."""
+        b = C.c_uint64(0); l = C.c_uint64(0)
+        self._check(self.L.infx_engine_list_leaf_totals(self.h, C.byref(b), C.byref(l)))
+        return int(b.value), int(l.value)
+
     def facets_of(self, sh, nq, i):
         """Facets of query i of the last batch (nq queries) searched on session handle sh with Query.EnableFacets: {field: [(value, count)]}, counts over
         the returned rows, (count desc, value asc) — Core/FacetBuilder.cs:19-105."""
@@ -1635,7 +1695,26 @@ def _query_results(engine, sh, qs, status, keys, scores, ties, counts, flags):
 def _facets_all(engine, sh):
     ncols = C.c_int32(0)
     engine._check(engine.L.infx_engine_facets_all(sh, C.byref(ncols)))
-    return _facet_columns(engine, int(ncols.value), lambda k, *out: engine.L.infx_engine_facets_all_column(sh, k, *out))
+    facets = _facet_columns(engine, int(ncols.value), lambda k, *out: engine.L.infx_engine_facets_all_column(sh, k, *out))
+    facets.update(_facet_columns(engine, int(engine.L.infx_engine_facets_all_list_column_count(sh)),
+                                 lambda k, *out: engine.L.infx_engine_facets_all_list_column(sh, k, *out), lists=True))
+    return facets
+
+
+def _list_column_index(engine, name):
+    """(the engine's list column of a field name, the kind of its elements), or (-1, 0)."""
+    for lcol in range(int(engine.L.infx_engine_list_column_count(engine.h))):
+        nb = C.create_string_buffer(256); kind = C.c_int32(0)
+        engine.L.infx_engine_list_column_info(engine.h, lcol, nb, 256, None, None, C.byref(kind))
+        if nb.value and nb.value.decode() == name:
+            return lcol, int(kind.value)
+    return -1, 0
+
+
+def _list_column_value(engine, lcol, code):
+    n = int(engine.L.infx_engine_list_column_value(engine.h, lcol, code, None, 0))
+    vb = C.create_string_buffer(max(n, 0) + 1); engine.L.infx_engine_list_column_value(engine.h, lcol, code, vb, n + 1)
+    return vb.value.decode()
 
 
 def _column_facets(engine, col, m, codes, cnts):
@@ -1648,15 +1727,19 @@ def _column_facets(engine, col, m, codes, cnts):
     return nb.value.decode(), vals
 
 
-def _facet_columns(engine, ncols, read):
-    """{field: [(value, count)]} of ncols facet columns; read(k, col, codes, counts, cap) is the library's reader of the k-th: the number of pairs, < 0 for an error."""
+def _facet_columns(engine, ncols, read, lists=False):
+    """{field: [(value, count)]} of ncols facet columns; read(k, col, codes, counts, cap) is the library's reader of the k-th: the number of pairs, < 0 for an error.
+    lists: the columns are list columns (their own index space and name / value readers)."""
     facets = {}
     for k in range(ncols):
         col = C.c_int32(0); codes = np.zeros(128, np.uint32); cnts = np.zeros(128, np.uint32)
         m = read(k, C.byref(col), _p(codes, C.c_uint32), _p(cnts, C.c_uint32), 128)
         if m < 0:
             engine._check(1)
-        if m > 0:
+        if m > 0 and lists:
+            nb = C.create_string_buffer(256); engine.L.infx_engine_list_column_info(engine.h, col.value, nb, 256, None, None, None)
+            facets[nb.value.decode()] = [(_list_column_value(engine, col.value, int(codes[j])), int(cnts[j])) for j in range(m)]
+        elif m > 0:
             name, vals = _column_facets(engine, col.value, m, codes, cnts)
             facets[name] = vals
     return facets
@@ -1684,7 +1767,10 @@ def _facets_filtered(engine, sh, filters):
         tot = C.c_uint32(0)
         engine._check(engine.L.infx_engine_facets_filtered_total(sh, i, C.byref(tot)))
         ncols = int(engine.L.infx_engine_facets_filtered_column_count(sh))
-        return FilteredFacets(_facet_columns(engine, ncols, lambda k, *out: engine.L.infx_engine_facets_filtered_column(sh, i, k, *out)), int(tot.value), None)
+        facets = _facet_columns(engine, ncols, lambda k, *out: engine.L.infx_engine_facets_filtered_column(sh, i, k, *out))
+        facets.update(_facet_columns(engine, int(engine.L.infx_engine_facets_filtered_list_column_count(sh)),
+                                     lambda k, *out: engine.L.infx_engine_facets_filtered_list_column(sh, i, k, *out), lists=True))
+        return FilteredFacets(facets, int(tot.value), None)
     single = isinstance(filters, str)
     return _per_request(engine, sh, "infx_engine_facets_filtered", "infx_engine_facets_filtered_error", C.c_char_p, [filters] if single else list(filters), single,
                         lambda x: x.encode(), read, lambda _, msg: FilteredFacets({}, 0, msg), chunk=None)
