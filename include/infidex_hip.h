@@ -844,6 +844,9 @@ int32_t infx_last_alg_bytes(infx_stream* s, uint64_t* bytes);
 int32_t infx_last_candidates(infx_stream* s, uint64_t* n);
 /* Queries of the last batch whose Stage-1 cut was ambiguous and was replayed with the reference's sequential semantics (k_exact1). */
 int32_t infx_last_exact_replays(infx_stream* s, uint32_t* n);
+/* ... of them handed to the sequential k_exact1 by the parallel replay (k_mark_wide, k_ex_theta, k_ex_heap); 0 where the parallel replay does not run
+ * (INFX_EXACT_SLOW=1, max_depth > 512: k_exact1 then takes every flagged query as it is). */
+int32_t infx_last_exact_fallbacks(infx_stream* s, uint32_t* n);
 /* The replay of the last batch: duration of its kernels (ms, HIP events on the stream) and why k_select flagged the queries:
  * why3[0] exact plateau (equal first-pass scores on both sides of the cut), [1] the best row left out lies inside the rounding band below the cut,
  * [2] the best row left out was not gathered (flagged conservatively). */

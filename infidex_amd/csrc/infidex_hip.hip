@@ -2875,6 +2875,10 @@ int32_t infx_last_exact_replays(infx_stream* s, uint32_t* n) {
     if (!s || !n) return fail(INFX_EINVAL, "null argument%s");
     *n = s->lastExact2[0] + s->lastExact2[1]; return INFX_OK;
 }
+int32_t infx_last_exact_fallbacks(infx_stream* s, uint32_t* n) {
+    if (!s || !n) return fail(INFX_EINVAL, "null argument%s");
+    *n = s->lastExact2[1]; return INFX_OK;
+}
 int32_t infx_last_candidates(infx_stream* s, uint64_t* n) {
     if (!s || !n) return fail(INFX_EINVAL, "null argument%s");
     *n = s->lastCandTotal; return INFX_OK;

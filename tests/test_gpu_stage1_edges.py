@@ -22,6 +22,8 @@ that mode and the idf handed over.  By those rules the half-full list t6 and the
 12 they still set candidate bits and score (several rounds per range at every R), and it is the class counts that make infx_stage1_select drop their rows.
 Queries 15 and 16 (t6 alone, t7 alone) and the prefix query over range 1 are where a cut runs through thousands of rows.  The DocSet of range 1 holds every
 (R / 4096)-th document from R = 8192 on, so that it stays within the 10 * depth documents prefix precedence accepts.
+This index gives every document its own length, so no tie is structural and a query is rarely if ever flagged: the exact replay is not exercised here.  That is
+done by tests/test_gpu_replay_plateaus.py (the replay kernels against tests/replay_model.py on constructed score plateaus, bit for bit).
 First run on an MI355X: every case passed with no row excused at any cut."""
 import os
 import subprocess
