@@ -628,8 +628,10 @@ __global__ __launch_bounds__(1024) void k_select_order(const uint32_t* __restric
 //                  serialised at L2 and cost 0.4 ms) and keeps the best row left out.
 // k_select then starts at its sort for such a query; any other case (an exact plateau wider than the sort across the cut, the window missed twice) leaves mode 0 and
 // k_select does all the work itself, as before.  The key list holds every row at or above the cut bin's lower edge, a superset of the top `depth` whatever the bin
-// width or origin: same rows after the sort, same best row left out: bit-identical (tests/test_gpu_parity.py::test_accumulate_schedules_agree_bit_for_bit runs
-// INFX_SEL_GIANT_MIN = 64 and 3000 against 0; tests/test_gpu_fullsize.py runs the default at 10 M documents against the oracle).
+// width or origin: same rows after the sort, same best row left out: bit-identical (tests/test_gpu_select_cuts.py holds every path of the cut — swept fine, coarse,
+// take-all and refused among them — to the plain model tests/select_model.py row for row, under INFX_SEL_GIANT_MIN = 64, 16384 and 0;
+// tests/test_gpu_parity.py::test_accumulate_schedules_agree_bit_for_bit runs INFX_SEL_GIANT_MIN = 64 and 3000 against 0; tests/test_gpu_fullsize.py runs the default at
+// 10 M documents against the oracle).
 // Per 1000-query launch at 10 M documents: k_select 1.06 ms -> 0.18 + 0.11 (hist) + 0.03 (cut) + 0.14 (gather) = 0.46 ms.
 #define SELG_MAX 256
 #define SELG_SHIFT2 16                     // bin width (score bits) of the coarse histogram: a window of 2^28 below the best row
